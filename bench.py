@@ -36,6 +36,18 @@ descriptors of overlapping images are in.
 
 `cpu_baseline` (rank 0, N = 1 only): the CPU oracle (a port of the reference's algorithm, see
 oracle/) timed on the box's host cores on a bounded sample of the same workload.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, print the line (`value`,
+`ms_per_step`, the per-leg split and the ViT's rate over the step time).  Everything else measured above — the matcher
+loops with `pair_matches_per_s*` and the `roofline*` objects, `matcher_c5_shape`, `strong_scaling_200`,
+`extract_e2e_images_per_s`, `trainable_extractor_images_per_s` and `cpu_baseline` — runs only with --full.
+
+--dump-outputs DIR (rank 0): after the timed steps, what the last step computed, as the caller of the path receives
+it, goes to DIR/<name>.npy in float32 / float64 (entries behind a count zeroed, -1 for matches), at most 64 MB in all:
+    keypoints (B, K, 2), descriptors (B, K, D), keypoint_counts (B,), matches (P, K, 2), match_counts (P,)
+An array over its share of that budget is cut to a fixed seeded sample of its rows (images / pairs); the rows
+kept are written beside it as <name>_rows.npy.  The inputs depend only on the arguments, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -75,15 +87,20 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=150, help="timed steps (default: > 1 s of timed region)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: matcher loops and rooflines, the 2048 x 256 block shape, "
+                         "the 200-image anchor, files -> database, the trainable extractor and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--match-launches", type=int, default=0,
-                    help="launches of the matcher micro-loops (default: enough for ~0.5 s each)")
+                    help="launches of the matcher micro-loops of --full (default: enough for ~0.5 s each)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--images-total", type=int, default=0,
                     help="images of the whole job (strong scaling); default 50 at --gpus 1, 200 at --gpus N > 1")
     ap.add_argument("--weak", action="store_true", help="50 images per GPU instead of a fixed set")
     ap.add_argument("--config", choices=["c2", "c5"], default="c2",
                     help="c2: configs[1]+[2] (ViT-S, 512 x 384); c5: configs[4]'s one-GPU share (ViT-B, 2048 x 256)")
-    ap.add_argument("--no-strong-anchor", action="store_true", help="skip the 200-image leg of the default N = 1 line")
+    ap.add_argument("--no-strong-anchor", action="store_true", help="skip the 200-image leg of the --full N = 1 line")
     ap.add_argument("--no-pipelining", action="store_true",
                     help="start every step's extraction behind the previous step's matching (no overlap between consecutive steps)")
     return ap.parse_args()
@@ -189,6 +206,93 @@ def cpu_baseline(frames):
     }
 
 
+DUMP_CAP_BYTES = {"descriptors": 40 << 20, "matches": 15 << 20, "keypoints": 3 << 20,   # 60 MiB < 64 MB in all
+                  "keypoint_counts": 1 << 20, "match_counts": 1 << 20}
+
+
+def dump_outputs(out_dir, res, n_local, matches, match_counts):
+    """--dump-outputs: the last step's results as the caller receives them -> out_dir/<name>.npy (float32 / float64).
+    Entries behind a count are not part of the result: zeroed (keypoints, descriptors) or -1 (matches), so that the
+    files depend only on what was computed.  An array over its cap is cut to a seeded sample of its rows."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    counts = res["count"][:n_local].long()
+    pair_counts = match_counts.long()
+    K = res["keypoints"].shape[1]
+    valid = torch.arange(K, device=counts.device)[None, :] < counts[:, None]                       # (B, K)
+    valid_m = torch.arange(matches.shape[1], device=counts.device)[None, :] < pair_counts[:, None]  # (P, K)
+    arrays = {
+        "keypoints": (res["keypoints"][:n_local].float() * valid[..., None], np.float32),
+        "descriptors": (res["desc_u8"][:n_local] * valid[..., None], np.float32),
+        "keypoint_counts": (counts, np.float64),
+        "matches": (torch.where(valid_m[..., None], matches, torch.full_like(matches, -1)), np.float32),
+        "match_counts": (pair_counts, np.float64),
+    }
+    for name, (t, dtype) in arrays.items():
+        a = t.cpu().numpy()
+        cap = DUMP_CAP_BYTES[name]
+        row_bytes = int(np.prod(a.shape[1:], dtype=np.int64)) * np.dtype(dtype).itemsize
+        rows_path = os.path.join(out_dir, f"{name}_rows.npy")
+        if os.path.exists(rows_path):
+            os.remove(rows_path)                                 # (left by an earlier run into the same directory)
+        if a.shape[0] * row_bytes > cap:
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], max(1, cap // row_bytes), replace=False))
+            a = a[rows]
+            np.save(rows_path, rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(dtype))
+
+
+def headline(args, cfg, world, n_total, scaling, n_local, n_pairs_global, elapsed, leg_ms, res, ex):
+    """The result line of a plain run: the timed steps alone (--full adds its legs to it)."""
+    K, D = cfg["num_keypoints"], cfg["desc_dim"]
+    images = n_total * args.steps
+    ms_per_step = elapsed / args.steps * 1e3
+    extract_ms = leg_ms["extract"] / args.steps
+    # consecutive steps pipeline (the next step's ViT starts under this step's matching), so the per-leg events no longer
+    # partition a step: the ViT's rate is stated against the WHOLE step time — a lower bound that needs no attribution
+    vit_ms = ms_per_step if not args.no_pipelining else extract_ms
+    vit_tflops = cfg["flop_per_image"] * n_local / (vit_ms * 1e-3) / 1e12
+    if args.config == "c5":
+        workload = (f"configs[4], one GPU's share: DINOv2 ViT-B/14 extract of {n_total} 640x480 images ({K} keypoint targets, "
+                    f"768 -> {D}-D projected uint8 descriptors) then exhaustive matching of all pairs among them; "
+                    f"matcher legs on {K} x {D} blocks")
+    elif n_total == IMAGES_PER_RANK and world == 1:
+        workload = ("configs[1]+configs[2]: DINOv2 ViT-S/14 extract of 50 640x480 images (512 keypoints, 384-D uint8 "
+                    "descriptors) then exhaustive mutual-NN + ratio matching of all pairs among the extracted images")
+    else:
+        workload = (f"configs[3]: the fixed {n_total}-image 640x480 set, DINOv2 ViT-S/14 extract sharded in contiguous blocks "
+                    f"over {world} GPU(s), one RCCL all-gather of the descriptor blocks, all {n_pairs_global} pairs dealt "
+                    f"p % {world}") if scaling == "strong" else \
+                   (f"weak scaling: {cfg['images']} images per GPU ({n_total} images), all {n_pairs_global} pairs dealt p % {world}")
+    return {
+        "metric": "images/sec extracted + pair-matches/sec (N×D brute-force NN)",
+        "value": round(images / elapsed, 2), "unit": "images/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "bf16 (ViT) / u8+i32 (matcher)",
+        "data": "synthetic", "full": args.full,
+        **({"rehearsal": True} if REHEARSE else {}),
+        "config": {
+            "workload": workload,
+            "images_total": n_total, "images_rank0": n_local, "image_size": [W, H], "num_keypoints": K,
+            "descriptor_dim": D, "pairs_per_step": n_pairs_global, "parallelism": f"images+pairs sharded x{world}",
+            "keypoints_kept_per_image_mean": round(float(res["count"].float().mean().item()), 1),
+            "vit_batch_shards": getattr(ex.model, "batch_shards", None) or int(os.environ.get("VITCOLMAP_VIT_SHARDS", "2")),
+        },
+        "timed_region_s": round(elapsed, 3),
+        "extract_images_per_s": round(n_local * world / (extract_ms * 1e-3), 1),
+        "steps_pipelined": not args.no_pipelining,
+        "legs_ms_per_step_rank0": {k: round(v / args.steps, 3) for k, v in leg_ms.items()},
+        "roofline_vit": {
+            "bound": "mfma", "achieved": round(vit_tflops, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(vit_tflops / MFMA_BF16_PEAK_TFLOPS, 4),
+            "note": "the ViT's FLOPs of one step over the WHOLE step time (preprocess + ViT + selection + gather + matching; "
+                    "consecutive steps overlap, so legs are not separable): a lower bound on the GEMM rate",
+        },
+    }
+
+
 def plan_job(config: str, world: int, images_total: int = 0, weak: bool = False):
     """-> (images of the whole job, "strong" | "weak").  Default: configs[1] (50 images) on one GPU, the fixed 200-image
     set of north_star / configs[3] on N > 1 GPUs (strong scaling); --weak: the per-GPU count times N; c5: 63 per GPU."""
@@ -272,7 +376,8 @@ def main():
     def run_job(n_images, steps, warmup):
         """The hot path over a fixed set of n_images synthetic frames sharded over the ranks (contiguous blocks of
         ceil(n / world), the last ranks padded with empty images; pair p of the exhaustive list -> rank p % world).
-        -> (elapsed seconds of `steps` steps, max over ranks; per-leg ms of rank 0; last result; pairs of the job)."""
+        -> (elapsed seconds of `steps` steps, max over ranks; per-leg ms of rank 0; last result; pairs of the job;
+        last step's matches and match counts of this rank's pairs)."""
         per = (n_images + world - 1) // world
         lo, hi = vd.shard_range(n_images, rank, world)
         frames_np = synthetic_frames(0, n_images)[lo:hi] if hi > lo else np.zeros((0, H, W, 3), np.uint8)
@@ -326,10 +431,18 @@ def main():
             legs["extract"] += ev[0].elapsed_time(ev[1])
             legs["gather"] += ev[1].elapsed_time(ev[2])
             legs["match"] += ev[2].elapsed_time(ev[3])
-        return elapsed, legs, res, frames_np, hi - lo, n_images * (n_images - 1) // 2
+        return elapsed, legs, res, frames_np, hi - lo, n_images * (n_images - 1) // 2, out_m, out_c
 
-    elapsed, leg_ms, res, frames_np, n_local, n_pairs_global = run_job(n_total, args.steps, args.warmup)
+    elapsed, leg_ms, res, frames_np, n_local, n_pairs_global, out_m, out_c = run_job(n_total, args.steps, args.warmup)
     sys.stdout = so
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, n_local, out_m, out_c)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, cfg, world, n_total, scaling, n_local, n_pairs_global, elapsed, leg_ms, res, ex)))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- matcher leg at the fixed block shape (configs[2]: 512 x 384; c5: 2048 x 256): all pairs among n_total blocks --
     def matcher_loop(blocks_np, n_blocks, rows, dim):
@@ -390,7 +503,7 @@ def main():
     if world == 1 and args.config == "c2" and n_total != STRONG_IMAGES and not args.no_strong_anchor:
         sys.stdout = quiet
         st = max(4, args.steps // 10)
-        el2, legs2, _, _, _, np2 = run_job(STRONG_IMAGES, st, 2)
+        el2, legs2, _, _, _, np2, _, _ = run_job(STRONG_IMAGES, st, 2)
         sys.stdout = so
         strong_anchor = {
             "images_total": STRONG_IMAGES, "pairs_per_step": np2, "steps": st, "value": round(STRONG_IMAGES * st / el2, 2),
@@ -505,60 +618,19 @@ def main():
             "input": "tests/util_data.image_set(kind='scene'): every image a noisy subset of one descriptor pool, so "
                      "every 32x32 similarity tile holds relevant entries (the update path runs everywhere; every MAC executes)",
         }
-        images = n_total * args.steps
-        ms_per_step = elapsed / args.steps * 1e3
-        extract_ms = leg_ms["extract"] / args.steps
-        # consecutive steps pipeline (the next step's ViT starts under this step's matching), so the per-leg events no longer
-        # partition a step: the ViT's rate is stated against the WHOLE step time — a lower bound that needs no attribution
-        vit_ms = ms_per_step if not args.no_pipelining else extract_ms
-        vit_tflops = cfg["flop_per_image"] * n_local / (vit_ms * 1e-3) / 1e12
-        if args.config == "c5":
-            workload = (f"configs[4], one GPU's share: DINOv2 ViT-B/14 extract of {n_total} 640x480 images ({K} keypoint targets, "
-                        f"768 -> {D}-D projected uint8 descriptors) then exhaustive matching of all pairs among them; "
-                        f"matcher legs on {K} x {D} blocks")
-        elif n_total == IMAGES_PER_RANK and world == 1:
-            workload = ("configs[1]+configs[2]: DINOv2 ViT-S/14 extract of 50 640x480 images (512 keypoints, 384-D uint8 "
-                        "descriptors) then exhaustive mutual-NN + ratio matching of all pairs among the extracted images")
-        else:
-            workload = (f"configs[3]: the fixed {n_total}-image 640x480 set, DINOv2 ViT-S/14 extract sharded in contiguous blocks "
-                        f"over {world} GPU(s), one RCCL all-gather of the descriptor blocks, all {n_pairs_global} pairs dealt "
-                        f"p % {world}") if scaling == "strong" else \
-                       (f"weak scaling: {cfg['images']} images per GPU ({n_total} images), all {n_pairs_global} pairs dealt p % {world}")
-        line = {
-            "metric": "images/sec extracted + pair-matches/sec (N×D brute-force NN)",
-            "value": round(images / elapsed, 2), "unit": "images/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "bf16 (ViT) / u8+i32 (matcher)",
-            "data": "synthetic",
-            **({"rehearsal": True} if REHEARSE else {}),
-            "config": {
-                "workload": workload,
-                "images_total": n_total, "images_rank0": n_local, "image_size": [W, H], "num_keypoints": K,
-                "descriptor_dim": D, "pairs_per_step": n_pairs_global, "parallelism": f"images+pairs sharded x{world}",
-                "keypoints_kept_per_image_mean": round(float(res["count"].float().mean().item()), 1),
-                "vit_batch_shards": getattr(ex.model, "batch_shards", None) or int(os.environ.get("VITCOLMAP_VIT_SHARDS", "2")),
-            },
-            "timed_region_s": round(elapsed, 3),
-            "extract_images_per_s": round(n_local * world / (extract_ms * 1e-3), 1),
-            "steps_pipelined": not args.no_pipelining,
+        line = headline(args, cfg, world, n_total, scaling, n_local, n_pairs_global, elapsed, leg_ms, res, ex)
+        line.update({
             "pair_matches_per_s": round(pair_rate, 1),
             "pair_matches_per_s_dense": round(pair_rate_dense, 1),
             "pair_matches_config": f"{n_blocks} blocks of {K}x{D} uint8, all {n_pairs_global} pairs dealt "
                                    f"round-robin to {world} rank(s), one launch per rank, slowest rank's time",
-            "legs_ms_per_step_rank0": {k: round(v / args.steps, 3) for k, v in leg_ms.items()},
             "roofline": roof,
             "roofline_dense": roof_dense,
-            "roofline_vit": {
-                "bound": "mfma", "achieved": round(vit_tflops, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(vit_tflops / MFMA_BF16_PEAK_TFLOPS, 4),
-                "note": "the ViT's FLOPs of one step over the WHOLE step time (preprocess + ViT + selection + gather + matching; "
-                        "consecutive steps overlap, so legs are not separable): a lower bound on the GEMM rate",
-            },
             "matcher_c5_shape": c5_shape,
             "strong_scaling_200": strong_anchor,
             "extract_e2e_images_per_s": e2e,
             "trainable_extractor_images_per_s": trainable,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline and args.config == "c2":
             line["cpu_baseline"] = cpu_baseline(frames_np)
         else:

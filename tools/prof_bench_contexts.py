@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: split the pair-kernel dispatches of a `rocprofv3 --kernel-trace` run of bench.py into the three
+"""Developer tool: split the pair-kernel dispatches of a `rocprofv3 --kernel-trace` run of `bench.py --full` into the three
 contexts bench.py launches it in (inside the timed steps / the configs[2] loop / the dense loop) and print the per-context
 average duration — the configs[2] loop is the launch `roofline.launch_ms` times with HIP events.
 usage: tools/prof_bench_contexts.py <kernel_trace.csv> <steps+warmup> [kernel name substring] """

@@ -4,7 +4,7 @@
 # with other trace domains).  Raw output under gpurun_out/prof_r02b/.
 set -eo pipefail
 cd "$(dirname "$0")/.."
-bash tools/prof_stats.sh prof_r02b/stats -- python3 bench.py --no-cpu-baseline | tee gpurun_out/prof_r02b_stats.txt
+bash tools/prof_stats.sh prof_r02b/stats -- python3 bench.py --full --no-cpu-baseline
 cp "$(find gpurun_out/prof_r02b/stats -name '*kernel_stats.csv' | head -1)" gpurun_out/prof_r02b_kernel_stats.csv
 grep '"metric"' gpurun_out/prof_r02b/stats/stdout.log | tail -1 > gpurun_out/prof_r02b_bench_line.json
 python3 tools/prof_bench_contexts.py "$(find gpurun_out/prof_r02b/stats -name '*kernel_trace.csv' | head -1)" 155 | tee gpurun_out/prof_r02b_contexts.txt

@@ -7,7 +7,7 @@
 set -eo pipefail
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/prof_r03
-bash tools/prof_stats.sh prof_r03/stats -- python3 bench.py --no-cpu-baseline --no-strong-anchor | tee gpurun_out/prof_r03_stats.txt
+bash tools/prof_stats.sh prof_r03/stats -- python3 bench.py --full --no-cpu-baseline --no-strong-anchor
 cp "$(find gpurun_out/prof_r03/stats -name '*kernel_stats.csv' | head -1)" gpurun_out/prof_r03_kernel_stats.csv
 grep '"metric"' gpurun_out/prof_r03/stats/stdout.log | tail -1 > gpurun_out/prof_r03_bench_line.json
 python3 tools/prof_bench_contexts.py "$(find gpurun_out/prof_r03/stats -name '*kernel_trace.csv' | head -1)" 155 "pair2_kernel<12>" | tee gpurun_out/prof_r03_contexts.txt

@@ -12,7 +12,7 @@ ctx = open("gpurun_out/prof_r02b_contexts.txt").read().strip().splitlines()
 sparse_us = float(ctx[1].split("|")[3])
 dense_us = float(ctx[2].split("|")[3])
 gbs = 1225 * 405504 / sparse_us / 1e3
-md = f"""# rocprofv3 --kernel-trace --stats — `python bench.py --no-cpu-baseline` (round 2 final, 1x MI355X, the driver's default command)
+md = f"""# rocprofv3 --kernel-trace --stats — `python bench.py --full --no-cpu-baseline` (round 2 final, 1x MI355X)
 
 155 end-to-end steps (5 warm-up + 150 timed, 50 images each), then the two matcher loops of the same process: 3 warm-up + 1 probe +
 {d['roofline']['launches_timed']} timed launches on the configs[2] input (`roofline`), the same on the dense input (`roofline_dense`).  Raw per-kernel

@@ -24,7 +24,7 @@ for r in rows:
     for key, lab in (("mlp2_kernel", "fused MLP"), ("attention_kernel<2, true", "attention"), ("xs_kernel<0, true", "qkv"), ("xs_kernel<2, false", "proj")):
         if key in r["Name"]:
             per_layer[lab] = float(r["AverageNs"]) / 1e3
-md = f"""# rocprofv3 --kernel-trace --stats — `python bench.py --no-cpu-baseline --no-strong-anchor` (round 3, 1x MI355X)
+md = f"""# rocprofv3 --kernel-trace --stats — `python bench.py --full --no-cpu-baseline --no-strong-anchor` (round 3, 1x MI355X)
 
 155 end-to-end steps (5 warm-up + 150 timed, 50 images each; consecutive steps are pipelined, whole batches alternating between two HIP streams), then the
 matcher loops of the same process on 512 x 384 blocks (3 warm-up + 1 probe + {d['roofline']['launches_timed']} timed launches on the configs[2] input —
