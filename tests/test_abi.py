@@ -73,3 +73,16 @@ def test_product_package_never_imports_oracle():
                 if re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M) or "libvco_oracle" in src:
                     bad.append(os.path.join(dirpath, f))
     assert not bad, f"product code references the oracle: {bad}"
+
+
+def test_kernel_sources_have_one_build():
+    """The shipped library is the only build: no conditional compilation and no run-time switch in the kernel sources."""
+    csrc = os.path.join(ROOT, "vit_colmap_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip")) + ["common.h"]
+    assert "matcher.hip" in files and "gemm.hip" in files
+    bad = []
+    for f in files:
+        for i, line in enumerate(open(os.path.join(csrc, f)), 1):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line) or "getenv" in line:
+                bad.append(f"{f}:{i}: {line.strip()}")
+    assert not bad, "conditional build or run-time switch in the kernel sources:\n" + "\n".join(bad)

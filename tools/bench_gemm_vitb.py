@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer tool: the four Linear shapes of ViT-B/14 at 50 x 1531 rows: csrc/gemm.hip with the 256 x 256 tile against
-the 128 x 128 tile (VITCOLMAP_GEMM_TILE=128, read once per process: run twice) and F.linear (hipBLASLt default heuristic)."""
+"""Developer tool: the four Linear shapes of ViT-B/14 at 50 x 1531 rows: csrc/gemm.hip (vc_linear_bf16, the 256 x 256 tile
+at these shapes) against F.linear (hipBLASLt default heuristic)."""
 import os, sys
 import torch
 import torch.nn.functional as F
@@ -30,6 +30,6 @@ for name, (K, N, epi) in {"qkv": (dim, 3 * dim, 0), "proj": (dim, dim, 2), "fc1"
     t = timeit(lambda: linear(a, w, b, epi, r))
     t_lib = timeit(lambda: F.linear(a, w, b))
     tot_h += t; tot_l += t_lib
-    print(f"{name:5s} {M}x{K}x{N}: hand-written (tile {os.environ.get('VITCOLMAP_GEMM_TILE', '256')}) {t*1e3:7.1f} us {fl/t/1e9:5.0f} TF/s | "
+    print(f"{name:5s} {M}x{K}x{N}: hand-written {t*1e3:7.1f} us {fl/t/1e9:5.0f} TF/s | "
           f"F.linear alone (no epilogue) {t_lib*1e3:7.1f} us {fl/t_lib/1e9:5.0f} TF/s", flush=True)
 print(f"sum per layer: hand-written {tot_h*1e3:.0f} us, F.linear {tot_l*1e3:.0f} us")

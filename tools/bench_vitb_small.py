@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer tool: ViT-B/14 token path at small batches (1, 2, 4, 8 images of 640 x 480): where the 256 x 256 GEMM tile stops paying
-(`VITCOLMAP_GEMM256_MIN_FILL=<percent of CUs the large tiles must occupy>`, 0 = always the large tile)."""
+"""Developer tool: ViT-B/14 token path at small batches (1, 2, 4, 8, 16 images of 640 x 480); vc_linear_bf16 takes the
+256 x 256 GEMM tile where its tiles fill at least half the CUs, the 128 x 128 tile below that."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vit_colmap_amd.features.vit_extractor import ViTExtractor

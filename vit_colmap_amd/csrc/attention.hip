@@ -23,7 +23,6 @@
 //   * online softmax in exp2 domain with the rescale skipped when no row maximum moved.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
@@ -59,19 +58,6 @@ __device__ inline uint32_t v_off(int key, int byte_in_row) {
 // The softmax over-subscribes the SIMD's issue port (~11 slots per MFMA gap against the ~6 that hide,
 // profiles/r02_overlap_probe.md): removing one of the five VALU issue slots per score is a direct saving.
 constexpr float kLazyTh = 6.0f;
-#ifdef VC_ATTN_STAMP
-// diagnostic build only (tools/stamp_attn.py): shader-clock totals per wave and phase, written over the wave's first output row
-__device__ __forceinline__ unsigned long long stamp_a() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define VC_AST(acc_) { const unsigned long long t_ = stamp_a(); acc_ += t_ - st_tp; st_tp = t_; }
-#else
-#define VC_AST(acc_)
-#endif
 template <int QT, bool LAZY>
 __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const __bf16* __restrict__ qkv,
                                                                            __bf16* __restrict__ out, int N, int H,
@@ -190,20 +176,13 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
   // columns 4p..4p+3 (p = i&3) of a 4-key x 16-d block
   const int grp = lane >> 4, gi = lane & 15, tq = gi >> 2, tp = gi & 3;
 
-#ifdef VC_ATTN_STAMP
-  unsigned long long st_wait = 0, st_dma = 0, st_qk = 0, st_sm = 0, st_pv = 0;
-  const unsigned long long st_t0 = stamp_a();
-  unsigned long long st_tp = st_t0;
-#endif
   int slot = 0;
   for (int blk = 0; blk < n_blk; ++blk) {
     // this wave's 4 pieces of block blk have landed when at most the 4 of block blk+1 are pending
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    VC_AST(st_wait)
     // the slot read in the previous iteration is free now: refill it two blocks ahead
     issue_block(blk + 2, slot == 0 ? 2 : slot - 1);
-    VC_AST(st_dma)
     const uint8_t* kt = lds[slot][0];
     const uint8_t* vt = lds[slot][1];
 
@@ -244,7 +223,6 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
           }
     }
 
-    VC_AST(st_qk)
     // ---- online softmax (exp2 domain); a lane and its partner (l ^ 32) share one query ------
     v8bf pf[QT][4];  // P^T as B operand: k-step s <- registers 8(s&1)..+7 of tile s>>1
 #pragma unroll
@@ -257,22 +235,6 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
 #pragma unroll
           for (int i = 0; i < 16; ++i) imax = max(imax, __float_as_int(acc_s[qt][t][i]));
         if (!__any(imax > __float_as_int(kLazyTh))) {
-#ifdef VC_ATTN_PKSUM
-          typedef float v2f __attribute__((ext_vector_type(2)));
-          v2f lsum2 = {0.f, 0.f};
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            const int t = s >> 1, r0 = 8 * (s & 1);
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-              const v2f pj = {__builtin_amdgcn_exp2f(acc_s[qt][t][r0 + j]), __builtin_amdgcn_exp2f(acc_s[qt][t][r0 + j + 1])};
-              lsum2 += pj;
-              pf[qt][s][j] = (__bf16)pj[0];
-              pf[qt][s][j + 1] = (__bf16)pj[1];
-            }
-          }
-          l_run[qt] += lsum2[0] + lsum2[1];
-#else
           float lsum[4] = {0.f, 0.f, 0.f, 0.f};   // four independent chains: an add never waits for its predecessor
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
@@ -285,7 +247,6 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
             }
           }
           l_run[qt] += (lsum[0] + lsum[1]) + (lsum[2] + lsum[3]);
-#endif
           continue;
         }
         // rare: back to absolute scores, then the standard update below
@@ -326,7 +287,6 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
       l_run[qt] += lsum;
     }
 
-    VC_AST(st_sm)
     // ---- O^T += V^T P^T : two 32-d tiles x four 16-key k-steps (each V fragment feeds QT MFMAs) --
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
@@ -348,12 +308,8 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
       }
     }
     slot = slot == 2 ? 0 : slot + 1;
-    VC_AST(st_pv)
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the two clamped refills before exiting
-#ifdef VC_ATTN_STAMP
-  const unsigned long long st_total = stamp_a() - st_t0;
-#endif
 
   // ---- normalise and store: lane (query r, half hh) holds d = (i&3) + 8(i>>2) + 4hh + 32dt -------
   // Stored from that layout (16 stores of 8 bytes per lane, 32 rows per instruction) the tail of a unit is bound by store
@@ -400,14 +356,6 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
         *(v4u32a*)(out + ((size_t)b * N + q_wave0 + row) * (size_t)H * kHD + (size_t)h * kHD + lslot * 8) = o;
     }
   }
-#ifdef VC_ATTN_STAMP
-  __syncthreads();   // after every wave's real stores: the wave's first output row now carries its stamps instead
-  if (lane == 0) {
-    uint32_t* dbg = (uint32_t*)(out + ((size_t)b * N + min(q_base + wave * (kQW * QT), N - 1)) * (size_t)H * kHD + (size_t)h * kHD);
-    dbg[0] = (uint32_t)st_wait; dbg[1] = (uint32_t)st_dma; dbg[2] = (uint32_t)st_qk; dbg[3] = (uint32_t)st_sm;
-    dbg[4] = (uint32_t)st_pv; dbg[5] = (uint32_t)st_total; dbg[6] = (uint32_t)n_blk; dbg[7] = 0x5354414du;
-  }
-#endif
 }
 
 }  // namespace
@@ -423,8 +371,7 @@ int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int
   // q_prescaled: the q rows already carry 1/sqrt(64) * log2(e) (folded into the qkv projection)
   const float scale_log2e = q_prescaled ? 1.0f : 0.125f * 1.4426950408889634f;
   // two query tiles per wave once the sequence is long enough to fill the chip with 256-row blocks
-  int qt = n_tokens >= 512 ? 2 : 1;
-  if (const char* e = getenv("VITCOLMAP_ATTN_QT")) qt = atoi(e) == 1 ? 1 : 2;   // developer A/B switch
+  const int qt = n_tokens >= 512 ? 2 : 1;
   const __bf16* pq = (const __bf16*)qkv;
   __bf16* po = (__bf16*)out;
   hipStream_t st = (hipStream_t)stream;

@@ -17,7 +17,6 @@
 // to 4-vectors and the bf16 result leaves as 8-byte stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
@@ -417,14 +416,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
   if (wr == 0) barrier();   // (same number of barriers in both halves)
 #undef G2_MFMA
 
-#ifdef VC_G2_PROBE_NOEPI   // timing probe: accumulators kept alive, nothing stored
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) asm volatile("" :: "v"(acc[a][b]));
-  asm volatile("s_barrier" ::: "memory");
-  continue;
-#endif
   // ---- epilogue ------------------------------------------------------------------------------------------------------------
   // A lane holds, per (feature block a, token block b), 4 consecutive features of token 16 b + fr: 8 bytes of an output row.
   // Stored from that layout, a store instruction touches 16 to 64 rows with 8 to 16 bytes each, and the epilogue cost 40-65 %
@@ -533,8 +524,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
 //     accumulator's initial value;
 //   * D^T orientation (features on registers, token on the lane); v_permlane32_swap + a wave-private
 //     LDS transposer turn a block into 16 rows x 64 contiguous bytes per store instruction.
-// Measured (76 550 rows, 1x MI355X): qkv+LN 100 us, proj+residual 46 us, fc1+LN+GELU 156 us; ablations
-// (tools/xs_variants.sh): MFMA + ring alone 64 / 32 / 80 us, the x reloads ~10 us, stores ~10-20 us.
+// Measured (76 550 rows, 1x MI355X): qkv+LN 100 us, proj+residual 46 us, fc1+LN+GELU 156 us; ablation
+// builds: MFMA + ring alone 64 / 32 / 80 us, the x reloads ~10 us, stores ~10-20 us.
 constexpr int XK = 384;
 constexpr int XKS = XK / 16;                 // 24 k-steps of v_mfma_f32_32x32x16_bf16
 constexpr int XStage = XKS * 1024;           // 24 KiB: one 32-feature block of W in fragment order
@@ -576,10 +567,9 @@ __global__ void gelu_table_kernel(uint16_t* __restrict__ tab) {
   tab[i] = (uint16_t)f32_to_bf16_rne(y);
 }
 
-#ifndef VC_XS_ISSUE0
-#define VC_XS_ISSUE0 1        // MFMA behind which the first piece of stage i + 2 is issued ...
-#define VC_XS_ISSUE_STEP 8    // ... and the distance to the next (the last one stays ahead of the result stores at slice 19)
-#endif
+constexpr int XReadAhead = 8;   // W fragments read ahead of the MFMA that uses them
+constexpr int XIssue0 = 1;      // MFMA behind which the first piece of stage i + 2 is issued ...
+constexpr int XIssueStep = 8;   // ... and the distance to the next (the last one stays ahead of the result stores at slice 19)
 template <int EPI, bool LN, bool GT>
 __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X, const uint8_t* __restrict__ Wp,
                                                     const float* __restrict__ biasf, const __bf16* res,
@@ -757,10 +747,6 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
   uint32_t gres[8];      // ... results, packed bf16 pairs, parked until the range check
   uint32_t gbad = 0;     // ... largest table index seen (out-of-range detector)
   auto slice = [&](int sl) {
-#ifdef VC_XS_NOEPI
-    if (sl == 23 && pa[0] == 12345.678f && pa[7] == 1.25f) out[pnb] = (__bf16)pa[1];
-    return;
-#endif
     if (EPI == EPI_GELU && GT) {
       // slices 0-3: pre-activations -> bf16 pairs (ep), the only float work; 4-11: table index + LDS gather of
       // packed register sl-4; 7-14: results packed back; 15: range check (+ float path); 16/17/19/22: exchange,
@@ -872,34 +858,15 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int row = crow + 16 * q;
-#ifdef VC_XS_NOSTORE
-        if (eo[q][0] == 0x12345678u && eo[q][3] == 0x9abcdef0u)
-#endif
         __builtin_amdgcn_raw_buffer_store_b128(eo[q], out_rs, (int)(((size_t)(pm_base + row) * N + pnb * 32 + cch * 8) * 2), 0, 0);
       }
     }
   };
 
-#ifdef VC_XS_STAMP
-  // diagnostic build only: per-wave cycle totals of the loop phases, written over the start of `out`
-  // after the last real store (tools/stamp_xs.py); no output value is computed from them
-  uint32_t st_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const uint64_t st_t0 = __builtin_amdgcn_s_memtime();
-  uint64_t st_prev = st_t0;
-#define XS_STAMP(k) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); st_c[k] += (uint32_t)(t_ - st_prev); st_prev = t_; }
-#else
-#define XS_STAMP(k)
-#endif
   v16f acc;
   int mt_cur = -1, slot = 0;
   int mt = s0 / n_nb, nb = s0 - mt * n_nb;
   for (int i = 0; i < n; ++i) {
-#if defined(VC_XS_STAMP) && defined(VC_XS_STAMP_STEADY)
-    if (i == 2) {   // steady-state totals: drop the pipeline fill and the first row tile's load (st_c[6] = stages counted)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) st_c[k] = 0;
-    }
-#endif
     // This wave's pieces of stage i (issued BETWEEN the MFMAs of iteration i-2) have landed once only operations issued
     // after them are pending.  Per iteration a wave issues (residual epilogue) 2 loads, then inside the MFMA loop its 3
     // pieces and the 2 result stores of the pending block: iteration i-1 alone accounts for 5 (+2) younger operations in
@@ -912,16 +879,10 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
     } else {
       asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     }
-    XS_STAMP(0)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    XS_STAMP(1)
     const bool pending = i > 0;
     if (pending) res_to_lds();
-#ifdef VC_XS_NOXRELOAD
-    const bool reload = mt_cur < 0;
-#else
     const bool reload = mt != mt_cur;
-#endif
     // (stage i + 2 goes into the slot read during iteration i - 1: its three pieces are issued between this
     // iteration's MFMAs — in a block behind the barrier they held every wave for 150-300 cycles with the matrix pipe idle)
     const int m_base = mt * XRows + wave * 32;
@@ -935,15 +896,10 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
       x_finish();
       mt_cur = mt;
     }
-    XS_STAMP(2)
     load_res(m_base, nb);
     const uint8_t* st = lds + slot * XStage + lane * 16;
     {
       // the bias is the accumulator's initial value: register 4g + j <- bias[32 nb + 8g + 4h + j]
-#ifdef VC_XS_NOBIAS
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-#else
       const float* bl = bias_l + nb * 32 + 4 * h;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -951,15 +907,11 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[4 * g + j] = bv[j];
       }
-#endif
     }
     {
       // W fragments are read XRD k-steps ahead of the MFMA that consumes them (LDS latency ~ 4 MFMAs);
       // sched_barrier pins [MFMA, fragment read, epilogue slice] per k-step, the compiler places the waits
-#ifndef VC_XS_RD
-#define VC_XS_RD 8
-#endif
-      constexpr int XRD = (EPI == EPI_GELU && GT) ? 6 : VC_XS_RD;   // the table epilogue needs the registers
+      constexpr int XRD = (EPI == EPI_GELU && GT) ? 6 : XReadAhead;   // the table epilogue needs the registers
       v8bf wf[XKS];
 #pragma unroll
       for (int ks = 0; ks < XRD; ++ks) wf[ks] = *(const v8bf*)(st + ks * 1024);
@@ -970,8 +922,8 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], acc, 0, 0, 0);
           if (ks + XRD < XKS) wf[ks + XRD] = *(const v8bf*)(st + (ks + XRD) * 1024);
           slice(ks);
-          if (ks == VC_XS_ISSUE0 || ks == VC_XS_ISSUE0 + VC_XS_ISSUE_STEP || ks == VC_XS_ISSUE0 + 2 * VC_XS_ISSUE_STEP)
-            issue_piece((ks - VC_XS_ISSUE0) / VC_XS_ISSUE_STEP);
+          if (ks == XIssue0 || ks == XIssue0 + XIssueStep || ks == XIssue0 + 2 * XIssueStep)
+            issue_piece((ks - XIssue0) / XIssueStep);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
@@ -979,13 +931,12 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
         for (int ks = 0; ks < XKS; ++ks) {
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], acc, 0, 0, 0);
           if (ks + XRD < XKS) wf[ks + XRD] = *(const v8bf*)(st + (ks + XRD) * 1024);
-          if (ks == VC_XS_ISSUE0 || ks == VC_XS_ISSUE0 + VC_XS_ISSUE_STEP || ks == VC_XS_ISSUE0 + 2 * VC_XS_ISSUE_STEP)
-            issue_piece((ks - VC_XS_ISSUE0) / VC_XS_ISSUE_STEP);
+          if (ks == XIssue0 || ks == XIssue0 + XIssueStep || ks == XIssue0 + 2 * XIssueStep)
+            issue_piece((ks - XIssue0) / XIssueStep);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     }
-    XS_STAMP(3)
     pa = acc;
     pm_base = m_base;
     pnb = nb;
@@ -997,20 +948,6 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
 #pragma unroll
   for (int sl = 0; sl < XKS; ++sl) slice(sl);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the clamped refills before the LDS is released
-#ifdef VC_XS_STAMP
-#ifdef VC_XS_STAMP_STEADY
-  st_c[6] = (uint32_t)(n > 2 ? n - 2 : 0);
-#else
-  XS_STAMP(6)
-#endif
-  st_c[7] = (uint32_t)(__builtin_amdgcn_s_memtime() - st_t0);
-  if (lane < 8) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v = lane == k ? st_c[k] : v;
-    ((uint32_t*)out)[(bid * 8 + wave) * 8 + lane] = v;
-  }
-#endif
 }
 
 // W [N][K] float32 (+ optional LayerNorm gamma / beta [K] folded in) -> fragment-ordered bf16 + float32 bias.
@@ -1202,9 +1139,6 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(__bf16* __restrict__ X, con
       for (int ks = 0; ks < RD; ++ks) wf[ks] = *(const v8bf*)(st + ks * 1024);
 #pragma unroll
       for (int ks = 0; ks < XKS; ++ks) {
-#ifdef VC_MLP_NOFC1
-        if (ks > 0) { asm volatile("" :: "v"(wf[ks])); if (ks + RD < XKS) wf[ks + RD] = *(const v8bf*)(st + (ks + RD) * 1024); continue; }
-#endif
         hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], hacc, 0, 0, 0);
         if (ks + RD < XKS) wf[ks + RD] = *(const v8bf*)(st + (ks + RD) * 1024);
       }
@@ -1228,11 +1162,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(__bf16* __restrict__ X, con
         g0[qd] = *(const uint16_t*)(gt_l + min(k0, kGtN - 1) * 4 + ((b0 >> 15) << 1));
         g1[qd] = *(const uint16_t*)(gt_l + min(k1, kGtN - 1) * 4 + ((b1 >> 15) << 1));
       }
-#ifdef VC_MLP_NOGELU
-      if (false) {
-#else
       if (__any(gbad >= kGtN)) {
-#endif
 #pragma unroll
         for (int qd = 0; qd < 8; ++qd) {
           const v2f_t y = gelu_erf2((v2f_t){__uint_as_float(pb[qd] << 16), __uint_as_float(pb[qd] & 0xffff0000u)});
@@ -1241,11 +1171,7 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(__bf16* __restrict__ X, con
         }
       } else {
 #pragma unroll
-#ifdef VC_MLP_NOGELU
-        for (int qd = 0; qd < 8; ++qd) gp[qd] = pb[qd];
-#else
         for (int qd = 0; qd < 8; ++qd) gp[qd] = g0[qd] | (g1[qd] << 16);
-#endif
       }
     }
     // ---- fc2 partial: Out^T[12 x 32 features][32 tokens] += W2c G^T (registers 8s..8s+7 of the hidden tile are k-step s)
@@ -1259,9 +1185,6 @@ __global__ __launch_bounds__(256, 1) void mlp_kernel(__bf16* __restrict__ X, con
       for (int q = 0; q < RD; ++q) wf[q] = *(const v8bf*)(st2 + q * 1024);
 #pragma unroll
       for (int q = 0; q < 24; ++q) {
-#ifdef VC_MLP_NOFC2
-        if (q > 0) { asm volatile("" :: "v"(wf[q])); continue; }
-#endif
         oacc[q >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[q], (q & 1) ? g_s1 : g_s0, oacc[q >> 1], 0, 0, 0);
         if (q + RD < 24) wf[q + RD] = *(const v8bf*)(st2 + (q + RD) * 1024);
       }
@@ -1330,16 +1253,11 @@ constexpr int M2OffG = M2OffTrB + 4 * XChunk;        // activation hand-off: [2 
 constexpr int M2Lds = M2OffG + 2 * 4 * 2048;         // 96 + 16 + 16 + 16 + 16 = 160 KiB
 static_assert(M2Lds <= 160 * 1024, "fused MLP: LDS budget");
 
-#ifndef VC_MLP_RD
-#define VC_MLP_RD 6          // weight fragments read ahead of the MFMA that uses them
-#endif
-#ifndef VC_MLP_NA
-#define VC_MLP_NA 3           // LDS-DMA pieces of a stage issued by each fc1 wave (each fc2 wave issues 12 - NA): the fc1 role is the longer one
-#endif
-#ifndef VC_MLP_ISSUE0
-#define VC_MLP_ISSUE0 1       // first MFMA behind which a piece of the next stage is issued ...
-#define VC_MLP_ISSUE_STEP 3   // ... and the distance to the next one (sweep: 1+3k 228 us, 1+2k 229, 0+k 233, 1+4k 235)
-#endif
+constexpr int M2ReadAhead = 6;    // weight fragments read ahead of the MFMA that uses them
+constexpr int M2PiecesA = 3;      // LDS-DMA pieces of a stage issued by each fc1 wave (each fc2 wave issues the other 9): the fc1 role is the longer one
+constexpr int M2Issue0 = 1;       // first MFMA behind which a piece of the next stage is issued ...
+constexpr int M2IssueStep = 3;    // ... and the distance to the next one (sweep: 1+3k 228 us, 1+2k 229, 0+k 233, 1+4k 235)
+constexpr int M2IssueStepB = 2;   // the distance on an fc2 wave with more than six pieces per stage
 __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, const uint8_t* __restrict__ Wm,
                                                       const float* __restrict__ b1f, const float* __restrict__ b2f,
                                                       int M, int n_chunks, int n_tiles, float eps,
@@ -1368,7 +1286,7 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
   // shared by all pieces — with a 64-bit address per piece in VGPRs the compiler kept six pairs alive, spilled them,
   // and every reload in the stage loop waited for vmcnt(0), i.e. for the copy just issued
   const uint32_t lane_off = (uint32_t)lane * 16u;
-  constexpr int NA = VC_MLP_NA, NB = 12 - NA;       // pieces per fc1 / fc2 wave and stage (48 pieces: 24 of W1, then 24 of W2)
+  constexpr int NA = M2PiecesA, NB = 12 - NA;       // pieces per fc1 / fc2 wave and stage (48 pieces: 24 of W1, then 24 of W2)
   auto issue_piece = [&](int c1, int c2, int slot, int i) {
     const int role = wave >> 2, q = wave & 3;
     if (i >= (role ? NB : NA)) return;
@@ -1405,14 +1323,6 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
     const int c1 = chunk_of(min(max(j, 0), n - 1)), c2 = chunk_of(min(max(j - 2, 0), n - 1));
     issue(c1, c2, slot_);
   };
-#ifdef VC_MLP_STAMP
-  uint32_t st_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const uint64_t st_t0 = __builtin_amdgcn_s_memtime();
-  uint64_t st_prev = st_t0;
-#define MS(k_) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); st_c[k_] += (uint32_t)(t_ - st_prev); st_prev = t_; }
-#else
-#define MS(k_)
-#endif
   issue_stage(0, 0);
   if (!roleB) {
     // =========================== A: x rows, fc1, GELU ======================================================
@@ -1460,7 +1370,6 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
     for (int i = 0; i <= n + 1; ++i) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      MS(0)
       // The six pieces of the next stage are issued BETWEEN this stage's MFMAs, one every four (round 2: issued in a
       // block they held the wave for 300-650 cycles with its matrix pipe idle; in the fc2 waves, where the block sat
       // behind the MFMAs, the copies' whole L2 latency was then waited for at the top of the next stage — ~750 cycles
@@ -1468,7 +1377,6 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
       const bool do_issue = i <= n;
       const int nc1 = chunk_of(min(max(i + 1, 0), n - 1)), nc2 = chunk_of(min(max(i - 1, 0), n - 1));
       if (do_issue && !(i < n && i > 0)) issue_stage(i + 1, slot ^ 1);
-      MS(1)
       if (i < n) {
         if (chunk == 0) {
           const int m0w = tile * 128 + pairw * 32;
@@ -1529,7 +1437,6 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
             }
           }
         }
-        MS(2)
         const uint8_t* st = lds + slot * MStage + lane * 16;
         v16f hacc;
         {
@@ -1542,24 +1449,22 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
           }
         }
         {
-          constexpr int RD = VC_MLP_RD;
+          constexpr int RD = M2ReadAhead;
           v8bf wf[XKS];
 #pragma unroll
           for (int ks = 0; ks < RD; ++ks) wf[ks] = *(const v8bf*)(st + ks * 1024);
           __builtin_amdgcn_sched_barrier(0);
-#ifndef VC_MLP_NO_PRIO_A
           // the fc1 role is the longer one (its GELU slices and x load ride in this phase): it gets the issue priority on
           // its SIMD — 238 -> 230 us per layer; raising the fc2 role instead loses
           __builtin_amdgcn_s_setprio(1);
-#endif
           if (i > 0) {
 #pragma unroll
             for (int ks = 0; ks < XKS; ++ks) {
               hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], hacc, 0, 0, 0);
               if (ks + RD < XKS) wf[ks + RD] = *(const v8bf*)(st + (ks + RD) * 1024);
               gelu_slice(ks, (i - 1) & 1);
-              if (ks >= VC_MLP_ISSUE0 && ks < VC_MLP_ISSUE0 + NA * VC_MLP_ISSUE_STEP && (ks - VC_MLP_ISSUE0) % VC_MLP_ISSUE_STEP == 0 && do_issue)
-                issue_piece(nc1, nc2, slot ^ 1, (ks - VC_MLP_ISSUE0) / VC_MLP_ISSUE_STEP);
+              if (ks >= M2Issue0 && ks < M2Issue0 + NA * M2IssueStep && (ks - M2Issue0) % M2IssueStep == 0 && do_issue)
+                issue_piece(nc1, nc2, slot ^ 1, (ks - M2Issue0) / M2IssueStep);
               __builtin_amdgcn_sched_barrier(0);
             }
           } else {
@@ -1571,17 +1476,13 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
             }
           }
         }
-#ifndef VC_MLP_NO_PRIO_A
         __builtin_amdgcn_s_setprio(0);
-#endif
         hprev = hacc;
-        MS(3)
         if (++chunk == n_chunks) { chunk = 0; tile += G; }
       } else if (i == n) {
         // the last stage's GELU has no MFMAs to ride under
 #pragma unroll
         for (int sl = 0; sl < XKS; ++sl) gelu_slice(sl, (i - 1) & 1);
-        MS(4)
       }
       slot ^= 1;
     }
@@ -1597,7 +1498,6 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
     for (int i = 0; i <= n + 1; ++i) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      MS(0)
       const bool do_issue = i <= n;
       const int nc1 = chunk_of(min(max(i + 1, 0), n - 1)), nc2 = chunk_of(min(max(i - 1, 0), n - 1));
       if (i >= 2) {
@@ -1611,32 +1511,19 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
         const v8bf g_s0 = *(const v8bf*)gb, g_s1 = *(const v8bf*)(gb + 1024);
         const uint8_t* st2 = lds + slot * MStage + XStage + lane * 16;
         {
-          constexpr int RD = VC_MLP_RD;
+          constexpr int RD = M2ReadAhead;
           v8bf wf[24];
 #pragma unroll
           for (int q = 0; q < RD; ++q) wf[q] = *(const v8bf*)(st2 + q * 1024);
-#ifdef VC_MLP_PRIO_B
-          __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
           for (int q = 0; q < 24; ++q) {
             oacc[q >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[q], (q & 1) ? g_s1 : g_s0, oacc[q >> 1], 0, 0, 0);
             if (q + RD < 24) wf[q + RD] = *(const v8bf*)(st2 + (q + RD) * 1024);
-#ifndef VC_MLP_BSTEP
-#define VC_MLP_BSTEP 2
-#endif
-            constexpr int BSTEP = NB <= 6 ? VC_MLP_ISSUE_STEP : VC_MLP_BSTEP;
-            if (q >= VC_MLP_ISSUE0 && q < VC_MLP_ISSUE0 + NB * BSTEP && (q - VC_MLP_ISSUE0) % BSTEP == 0 && do_issue)
-              issue_piece(nc1, nc2, slot ^ 1, (q - VC_MLP_ISSUE0) / BSTEP);   // (see the A waves)
+            constexpr int BSTEP = NB <= 6 ? M2IssueStep : M2IssueStepB;
+            if (q >= M2Issue0 && q < M2Issue0 + NB * BSTEP && (q - M2Issue0) % BSTEP == 0 && do_issue)
+              issue_piece(nc1, nc2, slot ^ 1, (q - M2Issue0) / BSTEP);   // (see the A waves)
           }
         }
-#ifdef VC_MLP_PRIO_B
-        __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef VC_MLP_STAMP
-        asm volatile("s_nop 0" :: "v"(oacc[11]));
-#endif
-        MS(3)
         if (pchunk == n_chunks - 1) {
           const int m0w = tile * 128 + pairw * 32;
 #pragma unroll 1
@@ -1687,24 +1574,11 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
           tile += G;
         }
         if (++pchunk == n_chunks) pchunk = 0;
-        MS(5)
       }
       if (do_issue && i < 2) issue_stage(i + 1, slot ^ 1);   // (no MFMAs to issue them between)
-      MS(1)
       slot ^= 1;
     }
   }
-#ifdef VC_MLP_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  st_c[7] = (uint32_t)(__builtin_amdgcn_s_memtime() - st_t0);
-  if (lane < 8) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int kq = 0; kq < 8; ++kq) v = lane == kq ? st_c[kq] : v;
-    ((uint32_t*)X)[(bid * 8 + wave) * 8 + lane] = v;   // diagnostic build: overwrites the first rows of x
-  }
-#endif
 }
 
 // MLP weights -> stage order: chunk c = [24 pieces of W1' (features 32c..+32, LayerNorm gamma folded) | 24 pieces of W2
@@ -1757,7 +1631,6 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
   const __bf16 *px = (const __bf16*)x, *pw = (const __bf16*)weight, *pb = (const __bf16*)bias,
                *pr = (const __bf16*)residual_or_null;
   __bf16* po = (__bf16*)out;
-  static const int tile256 = [] { const char* e = getenv("VITCOLMAP_GEMM_TILE"); return e ? atoi(e) : 256; }();   // developer A/B: 128
   int cus256 = 0;
   {
     int dev = 0;
@@ -1766,9 +1639,7 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
   }
   // wide layers with enough 256 x 256 tiles to occupy at least half the CUs (one workgroup per CU); below that the 128 x 128
   // tile, two workgroups per CU, fills the chip better (a single image of ViT-B is 18-72 large tiles)
-  static const int min_fill_pct = [] { const char* e = getenv("VITCOLMAP_GEMM256_MIN_FILL"); return e ? atoi(e) : 50; }();
-  if (n_out % G2N == 0 && tile256 == 256 &&
-      (long long)((rows + G2M - 1) / G2M) * (n_out / G2N) * 100 >= (long long)cus256 * min_fill_pct) {
+  if (n_out % G2N == 0 && (long long)((rows + G2M - 1) / G2M) * (n_out / G2N) * 2 >= (long long)cus256) {
     const int tiles_m = (rows + G2M - 1) / G2M, tiles_n = n_out / G2N;
     const long long nt = (long long)tiles_m * tiles_n;
     if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
@@ -1965,8 +1836,7 @@ int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded
     return vc::fail(hipErrorInvalidDevice);
   const int n_tiles = (rows + 127) / 128;
   const dim3 grid((unsigned)(n_tiles < cus ? n_tiles : cus));
-  static const bool single = [] { const char* e = getenv("VITCOLMAP_MLP_SINGLE"); return e && atoi(e) != 0; }();   // developer A/B switch
-  if (single || n_hidden > 1536)
+  if (n_hidden > 1536)
     hipLaunchKernelGGL(mlp_kernel, grid, dim3(256), 0, (hipStream_t)stream, (__bf16*)x_inout, (const uint8_t*)weights_tiled, b1_folded,
                        b2, rows, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
   else

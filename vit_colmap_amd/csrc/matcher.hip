@@ -32,10 +32,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef unsigned int u32;
 
-#ifndef VC_WAVES
-#define VC_WAVES 8
-#endif
-constexpr int kWaves = VC_WAVES;             // waves per workgroup: 8 (one workgroup per CU) or 4 (two per CU)
+constexpr int kWaves = 8;                    // waves per workgroup: one workgroup per CU
 constexpr int kThreads = kWaves * 64;
 constexpr int kTile = 32;                    // MFMA tile edge
 static_assert(VC_MAX_KEYPOINTS <= 64 * 32, "the row search packs the column-tile number into 6 bits");
@@ -48,13 +45,9 @@ __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; 
 __host__ __device__ inline int tiles_of(int n_max) { return ceil_div(ceil_div(n_max, kTile), 16) * 16; }
 __host__ __device__ inline int ksteps_of(int d) { return ceil_div(d, 32); }
 // K steps in the "head" of a descriptor for the exact early-out of pair2_kernel (== ks: no early-out for that length)
-#ifndef VC2_KH12
-#define VC2_KH12 4   // head k-steps of a 384-byte descriptor (a multiple of the window below)
-#endif
-#ifndef VC2_NB12
-#define VC2_NB12 4   // B window registers (fragments) at KS = 12
-#endif
-__host__ __device__ constexpr int head_steps_of(int ks) { return ks == 12 ? VC2_KH12 : (ks == 8 ? 4 : ks); }   // multiples of BWindow::NB
+constexpr int kHeadSteps12 = 4;   // head k-steps of a 384-byte descriptor (a multiple of the window below)
+constexpr int kWindow12 = 4;      // B window registers (fragments) at KS = 12
+__host__ __device__ constexpr int head_steps_of(int ks) { return ks == 12 ? kHeadSteps12 : (ks == 8 ? 4 : ks); }   // multiples of BWindow::NB
 // prepared image = fragments | row sums int32 [n_pad] | packed head / tail row sums int32 [n_pad] | per-tile tail norm bounds int32 [n_tiles]
 //   packed word   = (head << 16) | tail: sums of the row's bytes over the first head_steps_of(ks) * 32 dimensions and over the rest
 //                   (field widths: packed_sums_fit() below, asserted for every length the early-out kernels are built for)
@@ -62,7 +55,7 @@ __host__ __device__ constexpr int head_steps_of(int ks) { return ks == 12 ? VC2_
 __host__ __device__ constexpr bool packed_sums_fit(int ks) {   // head < 2^15 (the word stays positive), tail < 2^16
   return head_steps_of(ks) == ks || (255 * 32 * head_steps_of(ks) < (1 << 15) && 255 * 32 * (ks - head_steps_of(ks)) < (1 << 16));
 }
-static_assert(packed_sums_fit(8) && packed_sums_fit(12), "head / tail row sums must fit the packed word (VC2_KH12 is a build parameter)");
+static_assert(packed_sums_fit(8) && packed_sums_fit(12), "head / tail row sums must fit the packed word");
 __host__ __device__ inline int packed_head(int word) { return word >> 16; }
 __host__ __device__ inline int packed_tail(int word) { return word & 0xffff; }
 __host__ __device__ inline size_t image_bytes(int n_tiles, int ks) {
@@ -257,37 +250,15 @@ __host__ __device__ inline size_t lds_fixed_bytes2(int n_pad) {
 }
 // number of ring slots for this problem size (0 = does not fit)
 inline int plan_slots(int ks, int n_pad) {
-  if (kWaves == 4) {
-    // four-wave workgroups: stay within half the LDS when that still leaves a useful ring, so that two
-    // workgroups (two image pairs) share a CU and one's prologue / finalisation runs under the other's tiles
-    const long half = (long)kLdsBytes / 2 - (long)lds_fixed_bytes(n_pad);
-    const long nh = half / ((long)ks * kFragBytes);
-    if (nh >= 3) return (int)(nh > kMaxSlots ? kMaxSlots : nh);
-  }
   const long avail = (long)kLdsBytes - (long)lds_fixed_bytes(n_pad);
   long ns = avail / ((long)ks * kFragBytes);
   if (ns > kMaxSlots) ns = kMaxSlots;
   return ns >= 2 ? (int)ns : 0;
 }
 
-#ifdef VC_EXP_STAMP
-// diagnostic build only: shader-clock stamp (the wait keeps s_memtime ordered with LDS traffic)
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#endif
-
 __device__ inline void wg_barrier() {
   // LDS writes/atomics of this wave are complete before it arrives; LDS-DMA stays in flight
-#ifdef VC_EXP_NO_BARRIER
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
 }
 
 // One 1 KiB LDS-DMA piece: 64 lanes x 16 B, global source per lane, LDS destination =
@@ -358,9 +329,6 @@ struct Producer {
 template <int KS, int PW = kWaves>
 __device__ __forceinline__ void stage_tile(const uint8_t* __restrict__ tile_src, u32 slot_lds, int wave, int lane) {
   constexpr int M = Producer<KS, PW>::M;
-#ifdef VC_EXP_NO_STAGE
-  return;
-#endif
   if (wave < Producer<KS, PW>::NP) {
 #pragma unroll
     for (int m = 0; m < M; ++m) {
@@ -375,9 +343,6 @@ __device__ __forceinline__ void stage_tile(const uint8_t* __restrict__ tile_src,
 template <int KS, int PW = kWaves>
 __device__ __forceinline__ void wait_tile(int wave, int younger) {
   constexpr int M = Producer<KS, PW>::M;
-#ifdef VC_EXP_NO_WAIT
-  return;   // timing experiment only (results are wrong)
-#endif
   if (wave < Producer<KS, PW>::NP) {
 #define VC_W(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((n) * M) : "memory")
     // binary decision tree: three scalar branches per call instead of a chain of eight
@@ -411,42 +376,27 @@ __device__ __forceinline__ void mfma_phase(const v4i (&afrag)[RT][KS], v16i (&ac
   constexpr int NG = KS / G;
   static_assert(KS % G == 0, "KS must be a multiple of the fragment group");
   const uint8_t* src = slot + lane * 16;
-#ifndef VC_NO_SETPRIO
   // the wave that feeds the matrix pipe wins issue arbitration against its SIMD partner's epilogue
   __builtin_amdgcn_s_setprio(1);
-#endif
   v4i bf[2][G];
 #pragma unroll
-#ifdef VC_EXP_NO_LDSREAD
-  for (int i = 0; i < G; ++i) { bf[0][i] = afrag[0][i]; bf[1][i] = afrag[0][(i + 1) % KS]; }
-  asm volatile("" :: "v"(src));
-#else
   for (int i = 0; i < G; ++i) bf[0][i] = *(const v4i*)(src + i * kFragBytes);
-#endif
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
-#ifndef VC_EXP_NO_LDSREAD
     if (g + 1 < NG) {
 #pragma unroll
       for (int i = 0; i < G; ++i) bf[(g + 1) & 1][i] = *(const v4i*)(src + ((g + 1) * G + i) * kFragBytes);
     }
-#endif
 #pragma unroll
     for (int i = 0; i < G; ++i)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
-#ifdef VC_EXP_NO_MFMA
-        acc[rt][i] += afrag[rt][g * G + i][0] ^ bf[g & 1][i][1];
-#else
         acc[rt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[rt][g * G + i], bf[g & 1][i], acc[rt], 0, 0, 0);
-#endif
       }
     __builtin_amdgcn_sched_barrier(0);
     if (g == 0) mid();
   }
-#ifndef VC_NO_SETPRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 // Epilogue phase: top-2 updates for one column tile.
@@ -474,17 +424,6 @@ __device__ __forceinline__ void epilogue_phase(const v16i (&acc)[RT], u32 (&rbes
                                                const int* rterm_wave, const int* cterm,
                                                unsigned long long* colbest, u32* colsecond, int jt,
                                                int c, int h, u32 row_base, int s_low, bool (&dense)[RT]) {
-#ifdef VC_EXP_NO_EPILOGUE
-  {
-    int keep = 0;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int r = 0; r < 16; r += 4) keep ^= acc[rt][r];
-    asm volatile("" :: "v"(keep));
-    return;
-  }
-#endif
   const int ct = cterm[jt * kTile + c];
   const u32 jcode = 63u - (u32)jt;
   u32 cb = 0, cs2 = 0;
@@ -549,7 +488,6 @@ __device__ __forceinline__ void epilogue_phase(const v16i (&acc)[RT], u32 (&rbes
       dense[rt] = __any(m > s_low);
     }
   }
-#ifndef VC_EXP_NO_COLATOMIC
   if (FUSED && any_hit) {
     if (cb != 0) {
       const int j = jt * kTile + c;
@@ -562,9 +500,6 @@ __device__ __forceinline__ void epilogue_phase(const v16i (&acc)[RT], u32 (&rbes
       atomicMax(&colsecond[j], cand);
     }
   }
-#else
-  asm volatile("" :: "v"(cb), "v"(cs2));
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -582,7 +517,7 @@ __device__ __forceinline__ void epilogue_phase(const v16i (&acc)[RT], u32 (&rbes
 // pairs/s against 14.1 M with the staggered halves).
 template <int KS>
 struct BWindow {
-  static constexpr int NB = KS == 12 ? VC2_NB12 : (KS >= 4 ? 4 : KS);
+  static constexpr int NB = KS == 12 ? kWindow12 : (KS >= 4 ? 4 : KS);
   static constexpr int D = NB - 1;
   static_assert(KS % NB == 0 && head_steps_of(KS) % NB == 0, "window positions must line up at the head boundary");
 };
@@ -624,9 +559,7 @@ __device__ __forceinline__ int mfma_phase2(const v4i (&afrag)[2][KS], v16i (&acc
   constexpr int KH = head_steps_of(KS);
   constexpr int NB = BWindow<KS>::NB, D = BWindow<KS>::D;
   const uint8_t* src = slot + lane * 16;
-#ifdef VC2_SETPRIO   // (raising the MFMA phase's priority paid on the round's earlier kernels; on the final one it costs the dense path 4 %)
-  __builtin_amdgcn_s_setprio(1);
-#endif
+  // (no s_setprio here: raising the MFMA phase's priority paid on earlier kernels; on this one it costs the dense path 4 %)
   v4i bf[NB];
 #pragma unroll
   for (int i = 0; i < (NB > 1 ? D : 1); ++i) bf[i] = *(const v4i*)(src + i * kFragBytes);
@@ -661,9 +594,6 @@ __device__ __forceinline__ int mfma_phase2(const v4i (&afrag)[2][KS], v16i (&acc
   } else if (KH < KS) {
     mfma_steps<KS, KH, KS, KS>(afrag, acc, bf, src, nothing);
   }
-#ifdef VC2_SETPRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
   return cut;
 }
 
@@ -746,9 +676,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
   int* crow6 = ridx_s + n_pad;              // [wave][RT*32]: row terms 128*ra - 49024*D
   int* wave_count = crow6 + kWaves * 64 + kWaves * kRowScratchBytes / 4;
 
-#ifdef VC_EXP_STAMP
-  const unsigned long long t_kernel_start = stamp();
-#endif
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -815,12 +742,7 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
   // The two waves of a SIMD (w and w+4) run half a tile apart: while waves 0-3 issue the MFMAs of
   // tile t, waves 4-7 run the VALU epilogue of tile t-1, and vice versa, so the matrix pipe and the
   // vector pipe of a SIMD work at the same time instead of being fought over in lockstep.
-#ifndef VC_NO_STAGGER
-  // (with four-wave workgroups the SIMD partner is a wave of the other workgroup on the CU: no stagger)
-  const bool late = kWaves == 8 && wave >= kWaves / 2;
-#else
-  constexpr bool late = false;
-#endif
+  const bool late = wave >= kWaves / 2;
 
   for (int pass = 0; pass < n_pass; ++pass) {
     const int tile0 = (pass * kWaves + wave) * RT;  // first 32-row tile of a owned by this wave
@@ -875,38 +797,14 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
     // Staggered halves (late = waves 4-7): one loop, the epilogue shared, only the MFMA phase
     // placed before or after it.  The late half runs the epilogue of tile jt-1; for jt = 0 that
     // call is neutralised by an unreachable threshold (its accumulators are not defined yet).
-#ifdef VC_EXP_STAMP
-    unsigned long long sw = 0, sm = 0, se = 0, sm2 = 0;
-    const unsigned long long t_begin = stamp();
-    unsigned long long tp = t_begin;
-#endif
     for (int jt = 0; jt < n_ct; ++jt) {
       VC_TILE_HEAD()
-#ifdef VC_EXP_STAMP
-      unsigned long long ta = stamp(); sw += ta - tp;
-#endif
       if (!late) mfma_phase<KS, RT>(afrag, acc, slot, lane, produce);
-#ifdef VC_EXP_STAMP
-      unsigned long long tb = stamp(); sm += tb - ta;
-#endif
       const int ejt = late ? (jt > 0 ? jt - 1 : 0) : jt;
       const int eth = (late && jt == 0) ? 0x7fffffff : s_low;
       epilogue_phase<RT, FUSED>(acc, rbest, rsec, crow6_wave, cterm, colbest, colsecond, ejt, c, h, row_base, eth, dense);
-#ifdef VC_EXP_STAMP
-      unsigned long long tc = stamp(); se += tc - tb;
-#endif
       if (late) mfma_phase<KS, RT>(afrag, acc, slot, lane, produce);
-#ifdef VC_EXP_STAMP
-      tp = stamp(); sm2 += tp - tc;
-#endif
     }
-#ifdef VC_EXP_STAMP
-    if (FUSED && lane == 0 && pass == 0) {
-      uint32_t* dbg = out_matches + ((size_t)p * n_max + (n_max - 64)) * 2 + wave * 8;
-      dbg[0] = (uint32_t)sw; dbg[1] = (uint32_t)(sm + sm2); dbg[2] = (uint32_t)se;
-      dbg[3] = (uint32_t)(tp - t_begin); dbg[4] = (uint32_t)(t_begin - t_kernel_start);
-    }
-#endif
     if (late)
       epilogue_phase<RT, FUSED>(acc, rbest, rsec, crow6_wave, cterm, colbest, colsecond, n_ct - 1, c, h, row_base, s_low, dense);
     }
@@ -919,13 +817,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
     // (strict '>' keeps the lowest column on ties) and the four partial results of a row are
     // folded with two quad-permute steps.  No workgroup barrier: the slice belongs to the wave
     // and its LDS operations execute in order.
-#ifdef VC_EXP_NO_ROWREDUCE
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) asm volatile("" :: "v"(rbest[rt][r]), "v"(rsec[rt][r]));
-    if (false)
-#endif
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
 #pragma unroll
@@ -979,10 +870,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
   }  // passes
 
   if (!FUSED) return;
-#ifdef VC_EXP_NO_FINALIZE
-  if (tid == 0) out_counts[p] = 0;
-  return;
-#endif
   __syncthreads();
 
   // ---- angle + ratio tests, cross check, ordered compaction -----------------------------
@@ -1022,13 +909,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
     __syncthreads();
   }
   if (tid == 0) out_counts[p] = base;
-#ifdef VC_EXP_STAMP
-  if (lane == 0) {
-    const unsigned long long t_end = stamp();
-    uint32_t* dbg = out_matches + ((size_t)p * n_max + (n_max - 64)) * 2 + wave * 8;
-    dbg[5] = (uint32_t)(t_end - t_kernel_start);
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1078,15 +958,8 @@ __device__ __forceinline__ PairInfo next_pair_with_work(int p, int hi, const int
   return r;
 }
 
-#ifdef VC2_ALL_PRODUCE
-constexpr int kProd2 = kWaves;
-#else
 constexpr int kProd2 = kWaves / 2;   // LDS-DMA pieces are issued by the early half (waves 0..3)
-#endif
-#ifndef VC2_TILES_PER_BARRIER
-#define VC2_TILES_PER_BARRIER 2
-#endif
-constexpr int kTilesPerBarrier = VC2_TILES_PER_BARRIER;   // 1 or 2
+constexpr int kTilesPerBarrier = 2;
 template <int KS>
 __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
     const uint8_t* __restrict__ prepared, const int32_t* __restrict__ counts, int n_tiles_img, int d,
@@ -1117,30 +990,9 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   int* wmeta = (int*)(winfo + kPairWindow);        // [0] entries in the window
   int* crow6d = wmeta + 4;                         // [wave][RT*32]: full minus head row term (added when the early-out test fails)
   constexpr int KH = head_steps_of(KS);
-#ifdef VC2_NO_EARLY
-  constexpr bool kEarlyOut = false;
-#else
   constexpr bool kEarlyOut = KH < KS;
-#endif
   const int d_head = min(d, KH * 32);
 
-#ifdef VC_EXP_STAMP
-  // diagnostic build: per-wave cycle totals over the workgroup's whole range (tools/stamp_matcher.py)
-  unsigned long long st_wait = 0, st_mfma = 0, st_epi = 0, st_init = 0, st_rowred = 0, st_final = 0;
-  const unsigned long long st_t0 = stamp();
-  unsigned long long st_tp = st_t0;
-#define VC_ST(acc_) { const unsigned long long t_ = stamp(); acc_ += t_ - st_tp; st_tp = t_; }
-#else
-#define VC_ST(acc_)
-#endif
-#ifdef VC_EXP_TRACE
-  // diagnostic build (with VC_EXP_STAMP, data without matches): per column tile and wave eight words
-  // {barrier arrival, release, MFMA begin, MFMA end, epilogue end, cut, -, -} into the workgroup's own (empty) match blocks
-  int trace_i = 0;
-#define VC_TR(k_, v_) { if ((threadIdx.x & 63) == 0 && trace_i >= 16 && trace_i < trace_n) trace[((size_t)trace_i * 8 + wave) * 8 + (k_)] = (uint32_t)(v_); }
-#else
-#define VC_TR(k_, v_)
-#endif
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1202,10 +1054,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   PairInfo cur = fetch();
   if (cur.p >= hi) return;
   PairInfo nxt = fetch();
-#ifdef VC_EXP_TRACE
-  uint32_t* trace = out_matches + (size_t)lo * n_max * 2;
-  const int trace_n = (int)(((size_t)(hi - lo) * n_max * 2) / 64);
-#endif
 
   // ---- producer: a stream of column tiles over (pair, pass, tile), PF tiles ahead of the consumer ----------
   // It sweeps the current pair's image b once per row pass, then moves on to the NEXT pair (whose description is
@@ -1270,11 +1118,7 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   // The two waves of a SIMD (w and w + 4) run half a tile apart, see pair_kernel.  (On the final kernel: without it the
   // dense path loses 6 % and the sparse one gains 1.5-3 %; switching it per pair — on only behind a pair with relevant
   // similarities — was slower on both, 17.7 vs 18.1 M and 7.58 vs 7.71 M pairs/s: `late` is better a per-wave constant.)
-#ifdef VC2_NO_STAGGER
-  constexpr bool late = false;
-#else
   const bool late = wave >= kWaves / 2;
-#endif
   v4i afrag[RT][KS];
   int cur_a = -1, cur_tile0 = -1;
   int tna = 0;   // the larger tail norm bound of this wave's two row tiles (wave-uniform)
@@ -1346,7 +1190,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) { rbest[rt][r] = 0; rsec[rt][r] = 0; }
       const u32 row_base = (u32)(tile0 * kTile);
-      VC_ST(st_init)
 
       int ct = 0;   // column term of the tile whose epilogue comes next; always read ahead of an MFMA phase
       int cut = 0;  // row tiles of that tile the early-out cut short (wave-uniform)
@@ -1369,32 +1212,18 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
       // ahead so that the copy issued during the second tile never lands in a slot a slower wave is still reading.
       auto one_tile = [&](int jt, const uint8_t* slot) {
         if (!late) {
-          VC_TR(2, st_tp)
           ct = cterm[jt * kTile + c];
           cut = mfma_tile(jt, slot);
-          VC_ST(st_mfma)
-          VC_TR(3, st_tp)
-          VC_TR(5, cut)
         }
         const int ejt = late ? (jt > 0 ? jt - 1 : 0) : jt;
         const int eth = (late && jt == 0) ? 0x7fffffff : s_low;
         pair_hit |= epilogue_phase2(acc, rbest, rsec, ct, col, ejt, c, h, row_base, eth, cut);
-        VC_ST(st_epi)
-        VC_TR(4, st_tp)
         if (late) {
-          VC_TR(2, st_tp)
           ct = cterm[jt * kTile + c];
           cut = mfma_tile(jt, slot);
-          VC_ST(st_mfma)
-          VC_TR(3, st_tp)
-          VC_TR(5, cut)
         }
-#ifdef VC_EXP_TRACE
-        ++trace_i;
-#endif
       };
       for (int jt = 0; jt < n_ct;) {
-        VC_TR(0, st_tp)
         // (both tiles must be staged already: not so right after the producer idled — tiny images — or with a short ring)
         // Pairs after one that held relevant similarities run one tile per barrier: with the update path in every
         // epilogue the late half's deferred epilogue is the longer part and pairing the tiles loses 3 %.
@@ -1403,8 +1232,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
         wait_tile<KS, kProd2>(wave, max(prod_seq - cons_seq - (two ? 2 : 1), 0));
         wg_barrier();
         if (jt == 0 && pass == 0) stage_aux(nxt);   // (every thread is past this pair's initialisation)
-        VC_ST(st_wait)
-        VC_TR(1, st_tp)
         const int n_sub = two ? 2 : 1;
         {
           // (Straight-line on purpose.  As a second trip through ONE copy of this body hipcc 7.2.0 gave the SGPR pair that
@@ -1426,7 +1253,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
         jt += n_sub;
       }
       if (late) pair_hit |= epilogue_phase2(acc, rbest, rsec, ct, col, n_ct - 1, c, h, row_base, s_low, cut);
-      VC_ST(st_epi)
 
       // ---- row results of this pass (see pair_kernel) --------------------------------------------------------
 #pragma unroll
@@ -1475,7 +1301,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
           }
         }
       }
-      VC_ST(st_rowred)
     }  // passes
 
     int tidf = tid;   // (as tidp: the finalisation's addresses are computed here, not carried through the tile loop)
@@ -1539,7 +1364,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
     if (wave == kAuxWave) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();   // the flag and the per-pair state are rewritten by the next pair's initialisation
 
-    VC_ST(st_final)
     // ---- on to the next pair with work ---------------------------------------------------------------------------
     if (nxt.p >= hi) break;
     cur = nxt;
@@ -1552,15 +1376,6 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
       p_src = p_base = nxt.b_frags; p_left = p_nct = nxt.n_ct; p_sweeps = nxt.n_pass;
     }
   }  // pairs
-#ifdef VC_EXP_STAMP
-  if (lane == 0) {
-    uint32_t* dbg = out_matches + ((size_t)lo * n_max + (n_max - 64)) * 2 + wave * 8;
-    dbg[0] = (uint32_t)st_wait; dbg[1] = (uint32_t)st_mfma; dbg[2] = (uint32_t)st_epi; dbg[3] = (uint32_t)st_init;
-    dbg[4] = (uint32_t)st_rowred; dbg[5] = (uint32_t)st_final; dbg[6] = (uint32_t)(stamp() - st_t0); dbg[7] = (uint32_t)(hi - lo);
-  }
-#endif
-#undef VC_ST
-#undef VC_TR
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1772,7 +1587,6 @@ int vc_match_pairs_u8(const void* prepared, const int32_t* counts, int n_images,
   if (n_images <= 0 || n_max <= 0 || d <= 0 || n_pairs < 0) return VC_ERR_INVALID_ARG;
   if (n_max > VC_MAX_KEYPOINTS || d > VC_MAX_DESC_DIM) return VC_ERR_UNSUPPORTED;
   if (n_pairs == 0) return VC_OK;
-#if VC_WAVES == 8 && !defined(VC_OLD_PAIR_KERNEL)
   int st2 = VC_ERR_UNSUPPORTED;
   switch (pick_ks(d)) {   // descriptors up to 384 bytes: the persistent kernel (two row tiles per wave)
 #define VC_CASE2(K)                                                                                      \
@@ -1785,7 +1599,6 @@ int vc_match_pairs_u8(const void* prepared, const int32_t* counts, int n_images,
     default: break;
   }
   if (st2 != VC_ERR_UNSUPPORTED) return st2;   // (blocks too large for its LDS plan: the kernel with one workgroup per pair)
-#endif
   return dispatch_pair<true>(pick_ks(d), prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio,
                              max_distance, cross_check, n_max, out_matches, out_counts, nullptr,
                              nullptr, nullptr, (hipStream_t)stream);

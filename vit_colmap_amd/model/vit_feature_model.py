@@ -134,12 +134,11 @@ class ViTFeatureModel(nn.Module):
 
     def prepare_hip_heads(self):
         """After fold_batchnorm() and the cast to bf16 on the GPU: run upsampler, trunk and heads on the hand-written
-        implicit-GEMM convolution (model/hip_heads.py) instead of MIOpen.  `VITCOLMAP_HIP_HEADS=0` keeps the library path."""
-        import os
-
+        implicit-GEMM convolution (model/hip_heads.py) instead of MIOpen.  Without this call the heads run as torch
+        convolutions."""
         from .hip_heads import HipHeads
 
-        self._hip_heads = HipHeads(self) if os.environ.get("VITCOLMAP_HIP_HEADS", "1") != "0" else None
+        self._hip_heads = HipHeads(self)
         return self
 
     # ------------------------------------------------------------------------------------------

@@ -261,14 +261,11 @@ class DinoV2(nn.Module):
     @torch.no_grad()
     def prepare_hip(self):
         """Build the x-stationary GEMM operands (csrc/gemm.hip) of every block from the CURRENT parameters:
-        qkv with norm1 folded in, proj, fc1 with norm2 folded in.  Call it while the parameters are still
+        qkv with norm1 folded in, proj, the MLP with norm2 folded in.  Call it while the parameters are still
         float32 (after fold_layerscale, on the GPU) so gamma is folded before the one rounding to bf16;
         `_blocks_fused` calls it lazily otherwise.  ViT-S gets the x-stationary / fused-MLP operands, ViT-B / ViT-L bf16
         weights for the staged GEMM (q rows pre-scaled); the SwiGLU giant is not covered (`_hip = False`)."""
-        import os
-
         from .hip_ops import FusedMlp, XsLinear
-        from .hip_ops import gelu_table as hip_ops_gelu_table
 
         self._hip = False
         if self.arch.ffn != "mlp" or self.arch.dim % 128 != 0 or not all(b.folded for b in self.blocks):
@@ -291,14 +288,11 @@ class DinoV2(nn.Module):
                 fc2=(bf(b.mlp.fc2.weight), bf(b.mlp.fc2.bias)),
             ) for b in self.blocks]
             return self
-        self._gelu_tab = hip_ops_gelu_table(w.device)
-        self._use_fused_mlp = os.environ.get("VITCOLMAP_FUSED_MLP", "1") == "1"   # developer A/B switch: 0 = fc1 and fc2 as two kernels
         self._hip = [dict(
             qkv=XsLinear(*_prescale_q(b.attn.qkv.weight, b.attn.qkv.bias, self.arch.dim), b.norm1.weight, b.norm1.bias, b.norm1.eps),
             proj=XsLinear(b.attn.proj.weight, b.attn.proj.bias),
-            fc1=XsLinear(b.mlp.fc1.weight, b.mlp.fc1.bias, b.norm2.weight, b.norm2.bias, b.norm2.eps),
             mlp=FusedMlp(b.mlp.fc1.weight, b.mlp.fc1.bias, b.norm2.weight, b.norm2.bias, b.mlp.fc2.weight, b.mlp.fc2.bias,
-                         b.norm2.eps) if self._use_fused_mlp else None,
+                         b.norm2.eps),
         ) for b in self.blocks]
         return self
 
@@ -370,12 +364,7 @@ class DinoV2(nn.Module):
             blk, hw = blocks[i], hip[i]
             a = ops.attention(hw["qkv"](xi), blk.attn.num_heads, q_prescaled=True)   # LN1 + qkv (q pre-scaled), flash attention
             hw["proj"](a, ops.EPI_RESIDUAL, residual=xi, out=xi)            # x += proj(a)
-            if hw["mlp"] is not None:
-                hw["mlp"](xi)                                               # x += fc2(gelu(fc1(LN2 x))), one kernel
-                return
-            hdn = hw["fc1"](xi, ops.EPI_GELU, gelu_table=self._gelu_tab)    # gelu(fc1(LN2 x)), GELU by LDS table
-            fc2 = blk.mlp.fc2
-            ops.linear(hdn, fc2.weight, fc2.bias, ops.EPI_RESIDUAL, residual=xi, out=xi)   # x += fc2(hdn)
+            hw["mlp"](xi)                                                   # x += fc2(gelu(fc1(LN2 x))), one kernel
 
         return self._run_sharded(x, layer, *self._final_norm(x, drop_cls))
 
