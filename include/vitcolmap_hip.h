@@ -356,11 +356,11 @@ int vc_patch_embed_bf16(const void* patches, const void* weight, const void* bia
 
 /*
  * Fused MLP of a pre-norm block for dim == 384 (ViT-S):  x += fc2(gelu(fc1(LayerNorm(x))))  in one kernel — the
- * hidden tensor never exists in memory (csrc/gemm.hip: mlp2_kernel for n_hidden <= 1536, mlp_kernel above that).
+ * hidden tensor never exists in memory (csrc/gemm.hip: mlp2_kernel).
  * GELU as in vc_linear_xs_bf16 with a table.
  * vc_mlp_prepare (once per block): w1 [n_hidden][384], b1 [n_hidden], LayerNorm gamma / beta [384] (or both NULL),
  *   w2 [384][n_hidden], b2 [384], all float32  ->  weights_tiled (vc_mlp_weight_bytes bytes, stage order), b1_folded
- *   [n_hidden] float32, b2_out [384] float32.  n_hidden % 32 == 0, n_hidden <= 2048.
+ *   [n_hidden] float32, b2_out [384] float32.  n_hidden % 32 == 0, n_hidden <= 1536.
  * vc_mlp_bf16: x_inout [rows][384] bf16, updated in place.  gelu_table from vc_gelu_table_bf16.
  */
 size_t vc_mlp_weight_bytes(int n_hidden, int dim);

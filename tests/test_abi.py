@@ -44,6 +44,9 @@ def test_pure_host_entry_points():
     assert lib.vc_prepared_bytes(1, 300, 128) == 16 * 4 * 1024 + 2 * 512 * 4 + 16 * 4   # tiles round up to 16
     assert lib.vc_prepared_bytes(1, 512, 4096) == 0       # beyond VC_MAX_DESC_DIM
     assert lib.vc_knn_workspace_bytes(512, 512, 384) > 2 * 196608
+    # fused MLP: 48 stages of [W1 chunk | W2 chunk], 48 KiB each; only n_hidden <= 1536 has a kernel
+    assert lib.vc_mlp_weight_bytes(1536, 384) == 48 * 48 * 1024
+    assert lib.vc_mlp_weight_bytes(1568, 384) == 0
 
 
 def test_argument_validation_needs_no_gpu():
@@ -78,7 +81,7 @@ def test_product_package_never_imports_oracle():
 def test_kernel_sources_have_one_build():
     """The shipped library is the only build: no conditional compilation and no run-time switch in the kernel sources."""
     csrc = os.path.join(ROOT, "vit_colmap_amd", "csrc")
-    files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip")) + ["common.h"]
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip")) + ["common.h", "device.h"]
     assert "matcher.hip" in files and "gemm.hip" in files
     bad = []
     for f in files:
@@ -86,3 +89,18 @@ def test_kernel_sources_have_one_build():
             if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line) or "getenv" in line:
                 bad.append(f"{f}:{i}: {line.strip()}")
     assert not bad, "conditional build or run-time switch in the kernel sources:\n" + "\n".join(bad)
+
+
+def test_lds_dma_asm_only_in_device_header():
+    """The M0 save / set / restore around global_load_lds is written once, in csrc/device.h; kernels call its helpers."""
+    csrc = os.path.join(ROOT, "vit_colmap_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert "matcher.hip" in files and "gemm.hip" in files
+    bad = []
+    for f in files:
+        for i, line in enumerate(open(os.path.join(csrc, f)), 1):
+            code = line.split("//", 1)[0]
+            if any("global_load_lds" in s or re.search(r"\bm0\b", s) for s in re.findall(r'"(?:[^"\\]|\\.)*"', code)):
+                bad.append(f"{f}:{i}: {line.strip()}")
+    assert not bad, "LDS-DMA asm outside device.h:\n" + "\n".join(bad)
+    assert "global_load_lds_dwordx4" in open(os.path.join(csrc, "device.h")).read()

@@ -26,6 +26,7 @@
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
   // c' ^ (((k >> 1) & 1) << 2) (V).  Issued from inline asm and waited for with a counted vmcnt
   // (hipcc would drain them before every LDS read, and serialised the register-staged variant).
   const int n_blk = (N + kKV - 1) / kKV;
-  const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) void*)&lds[0][0][0]);
+  const uint32_t lds0 = vc::lds_addr(&lds[0][0][0]);
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   // Per-lane byte offsets of this wave's four pieces inside a block of 64 keys, computed ONCE: a block's source is then
   // a wave-uniform base (SGPR pair, advanced by scalar instructions) plus these.  Computing the full 64-bit address per
@@ -122,16 +123,7 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
       for (int i = 0; i < 4; ++i) {
         const int pce = wave_u * 4 + i;
         const uint32_t dst = lds0 + (uint32_t)slot * (2 * kTileBytes) + (uint32_t)(pce >> 3) * kTileBytes + (uint32_t)(pce & 7) * 1024u;
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %3\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %2\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(voff[i]), "s"(sbase), "s"(dst)
-            : "memory");
+        vc::lds_dma16(sbase, voff[i], dst);
       }
       return;
     }
@@ -145,16 +137,7 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
       const int tok = min(blk * kKV + key, N - 1);
       const __bf16* src = base + (size_t)tok * tok_stride + (size_t)(1 + which) * H * kHD + csrc * 8;
       const uint32_t dst = lds0 + (uint32_t)slot * (2 * kTileBytes) + (uint32_t)which * kTileBytes + (uint32_t)kg * 1024u;
-      uint32_t keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\t"
-          "s_mov_b32 m0, %2\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, off\n\t"
-          "s_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "v"(src), "s"(dst)
-          : "memory");
+      vc::lds_dma16(src, dst);
     }
   };
   issue_block(0, 0);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/vitcolmap_hip.h"
 
@@ -25,9 +26,7 @@ inline int check_launch() {
 
 // hipFuncSetAttribute applies to the CURRENT device only, so "this kernel is configured" is remembered
 // per device (one bit per device ordinal), not per thread: a process that drives several GPUs
-// configures every kernel once on each.  Usage:
-//   static vc::PerDeviceOnce once;
-//   if (int st = once.run([] { return hipFuncSetAttribute(...); })) return st;
+// configures every kernel once on each.
 struct PerDeviceOnce {
   std::atomic<unsigned long long> done{0};
   template <typename F>
@@ -43,5 +42,35 @@ struct PerDeviceOnce {
     return VC_OK;
   }
 };
+
+// Allows `kernels` up to `bytes` of dynamic LDS, once per device (`once` is the caller's static):
+//   static vc::PerDeviceOnce configured;
+//   if (int st = vc::allow_dynamic_lds(configured, bytes, kernel_a, kernel_b)) return st;
+template <typename... Kernels>
+int allow_dynamic_lds(PerDeviceOnce& once, int bytes, Kernels... kernels) {
+  return once.run([=] {
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : e), ...);
+    return e;
+  });
+}
+
+// Compute units of the current device (sizes persistent grids).
+inline int cu_count(int* cus) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e == hipSuccess && *cus <= 0) e = hipErrorInvalidDevice;
+  return e == hipSuccess ? VC_OK : fail(e);
+}
+
+// Runtime value -> template argument: calls f(std::integral_constant<decltype(V), V>{}) for the first V in Vs equal to
+// v and returns its status; VC_ERR_UNSUPPORTED when none is.  Only the listed values are instantiated.
+template <auto... Vs, typename F>
+int dispatch(int v, F&& f) {
+  int st = VC_ERR_UNSUPPORTED;
+  (void)((v == Vs && (st = f(std::integral_constant<decltype(Vs), Vs>{}), true)) || ...);
+  return st;
+}
 
 }  // namespace vc

@@ -1,0 +1,76 @@
+// Shared device-side idioms of the kernels: LDS-DMA issue, the wave-uniform LDS base and bf16 bit conversions.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace vc {
+
+// LDS-DMA (global_load_lds): each lane copies 16 (or 4) bytes from its own global address to LDS at the wave-uniform
+// byte address `lds_dst` + lane * 16 (or 4).  M0 holds the LDS destination; the compiler reserves it and does not
+// preserve it around an asm statement, so each statement saves M0, sets it, issues the load and restores M0 itself.
+// The copies are invisible to hipcc's s_waitcnt bookkeeping: the caller waits for them with its own vmcnt count, then
+// a barrier, before any LDS read of the data.  `lds_dst` must be an SGPR value (see lds_addr).
+
+// Per-lane 64-bit source address.
+__device__ __forceinline__ void lds_dma16(const void* vaddr, uint32_t lds_dst) {
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(vaddr), "s"(lds_dst)
+      : "memory");
+}
+
+// Wave-uniform base in an SGPR pair + per-lane 32-bit byte offset: one VGPR per lane instead of a 64-bit address.
+__device__ __forceinline__ void lds_dma16(const void* sbase, uint32_t voffset, uint32_t lds_dst) {
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %3\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voffset), "s"(sbase), "s"(lds_dst)
+      : "memory");
+}
+
+// 4 bytes per lane (inactive lanes copy nothing).
+__device__ __forceinline__ void lds_dma4(const void* vaddr, uint32_t lds_dst) {
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dword %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(vaddr), "s"(lds_dst)
+      : "memory");
+}
+
+// LDS byte address of a __shared__ object.
+__device__ __forceinline__ uint32_t lds_offset(const void* p) {
+  return (uint32_t)(size_t)(__attribute__((address_space(3))) const void*)p;
+}
+
+// The same, made provably wave-uniform so that it can feed an "s" operand.
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_offset(p));
+}
+
+__device__ __forceinline__ float bf16_to_f32(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
+
+// Round to nearest even; NaN stays NaN (quiet bit set, so the truncated mantissa cannot become zero).
+__device__ __forceinline__ uint16_t f32_to_bf16(float v) {
+  uint32_t u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+
+}  // namespace vc

@@ -20,6 +20,7 @@
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
   // ---- LDS-DMA staging: a stage is 32 pieces of 1 KiB (8 rows x 128 B); wave w issues x pieces
   // 4w..4w+3 and W pieces 4w..4w+3.  Lane l fills LDS row (l >> 3), chunk (l & 7) of its piece with
   // source chunk (l & 7) ^ (l >> 3)  [row & 7 == l >> 3 because pieces start at multiples of 8 rows].
-  const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) void*)&lds[0][0]);
+  const uint32_t lds0 = vc::lds_addr(&lds[0][0]);
   const int prow = lane >> 3, pchunk = (lane & 7) ^ prow;
   const __bf16* xsrc[4];
   const __bf16* wsrc[4];
@@ -113,16 +114,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
     for (int i = 0; i < 8; ++i) {
       const __bf16* src = (i < 4 ? xsrc[i] : wsrc[i - 4]) + kt * BK;
       const uint32_t dst = lds0 + (uint32_t)buf * kStage + (uint32_t)(i >> 2) * kImg + (uint32_t)(wave * 4 + (i & 3)) * 1024u;
-      uint32_t keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\t"
-          "s_mov_b32 m0, %2\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, off\n\t"
-          "s_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "v"(src), "s"(dst)
-          : "memory");
+      vc::lds_dma16(src, dst);
     }
   };
 
@@ -266,7 +258,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
 
   // ---- staging: unit u = 4 t + j of K tile t; j = 0: X0, 1: W0, 2: W1, 3: X1.  Wave w issues pieces 2w, 2w+1 (8 unit rows each).
   // unit row rho -> tile row:  X_h: rho < 64 ? rho + 64 h : 128 + (rho - 64) + 64 h;   W_h: (rho >> 5) * 64 + 32 h + (rho & 31)
-  const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) void*)&lds2[0]);
+  const uint32_t lds0 = vc::lds_addr(&lds2[0]);
   const int prow = lane >> 3, pchunk = (lane & 7) ^ prow;
   uint32_t voffx[2][2], voffw[2];          // per-lane byte offsets from X / W (+ k offset of the K tile added as a scalar)
   uint32_t vtaps[2][2];                    // CONV: bit t set = tap t of this lane's pixel lies inside the image
@@ -319,16 +311,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
       uint32_t vo = j == 0 ? voffx[0][i] : (j == 3 ? voffx[1][i] : voffw[i]);
       if (CONV && is_x) vo = ((j == 0 ? vtaps[0][i] : vtaps[1][i]) >> tap) & 1u ? vo + spos : zoff;
       const uint32_t dst = lds0 + (uint32_t)(t & 1) * kBuf2 + (uint32_t)j * kUnit2 + (uint32_t)(wave * 2 + i) * 1024u;
-      uint32_t keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\t"
-          "s_mov_b32 m0, %3\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, %2\n\t"
-          "s_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "v"(vo), "s"(sb), "s"(dst)
-          : "memory");
+      vc::lds_dma16(sb, vo, dst);
     }
   };
 
@@ -592,7 +575,7 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
   if (GT)
     for (int i = tid; i < kGtBytes / 4; i += 512) ((uint32_t*)gt_l)[i] = ((const uint32_t*)gelu_tab)[i];
 
-  const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) void*)&lds[0]);
+  const uint32_t lds0 = vc::lds_addr(&lds[0]);
   // ---- producer: wave w issues pieces 3w..3w+2 of every stage ------------------------------------
   int inb = s0 % n_nb, islot = 0, ileft = n;   // feature block / ring slot / stages left to issue
   // One piece: wave-uniform base in SGPRs + one per-lane offset (with per-piece 64-bit VGPR addresses the compiler keeps
@@ -601,16 +584,7 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
   auto issue_piece = [&](int i) {
     const uint8_t* sbase = Wp + (size_t)inb * XStage + (size_t)(wave * 3 + i) * 1024;
     const uint32_t dst = lds0 + (uint32_t)islot * XStage + (uint32_t)(wave * 3 + i) * 1024u;
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(lane_off16), "s"(sbase), "s"(dst)
-        : "memory");
+    vc::lds_dma16(sbase, lane_off16, dst);
     if (i == 2) {
       // past the end the last stage is staged again into a slot nobody reads (keeps the vmcnt counts uniform)
       if (ileft > 1) { --ileft; inb = inb + 1 == n_nb ? 0 : inb + 1; }
@@ -978,8 +952,6 @@ __global__ __launch_bounds__(256) void xs_prepare_kernel(const float* __restrict
 // (76 550 x 1536 bf16 = 235 MB, written by fc1 and read back by fc2: a third of a block's HBM traffic) never
 // exists and fc2 no longer stages both operands through L2 -> LDS.  Structure = the x-stationary kernel with a
 // second product per stage:
-//   * a wave keeps its 32 normalised token rows as B fragments (96 VGPRs) AND the 384 x 32 output tile of fc2 as
-//     12 accumulator tiles (192 VGPRs): one wave per SIMD (4 waves, 128 rows per workgroup, 512-register budget);
 //   * a stage is one 32-wide chunk of the hidden layer: 24 pieces of W1 (as in xs_kernel) + 24 pieces of W2
 //     (12 output blocks x 2 k-steps), 48 KiB, ring of 2;
 //   * per stage: H^T(32 hidden x 32 tokens) = W1c X^T (24 MFMAs, bias as initial value) -> GELU by the LDS table
@@ -989,257 +961,11 @@ __global__ __launch_bounds__(256) void xs_prepare_kernel(const float* __restrict
 // Row tiles are dealt round-robin to one persistent workgroup per CU.
 constexpr int MStage = 2 * XStage;                 // 48 KiB: [W1 chunk | W2 chunk]
 constexpr int MNS = 2;
-constexpr int MOffB1 = MNS * MStage;               // fc1 bias (<= 2048 floats)
-constexpr int MOffGt = MOffB1 + 2048 * 4;          // GELU table (8704 B)
-constexpr int MOffB2 = MOffGt + 9216;              // fc2 bias (384 floats)
-constexpr int MOffTr = MOffB2 + 2048;              // per-wave transposers, 4 x 4 KiB
-constexpr int MLds = MOffTr + 4 * XChunk;          // 96 + 8 + 9 + 2 + 16 = 131 KiB
 
-__global__ __launch_bounds__(256, 1) void mlp_kernel(__bf16* __restrict__ X, const uint8_t* __restrict__ Wm,
-                                                     const float* __restrict__ b1f, const float* __restrict__ b2f,
-                                                     int M, int n_chunks, int n_tiles, float eps,
-                                                     const uint16_t* __restrict__ gelu_tab) {
-  __shared__ __attribute__((aligned(1024))) uint8_t lds[MLds];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int G = gridDim.x, bid = blockIdx.x;
-  const int my_tiles = bid < n_tiles ? (n_tiles - bid + G - 1) / G : 0;
-  const int n = my_tiles * n_chunks;
-  if (n <= 0) return;
-
-  float* const b1_l = (float*)(lds + MOffB1);
-  float* const b2_l = (float*)(lds + MOffB2);
-  uint8_t* const gt_l = lds + MOffGt;
-  for (int i = tid; i < n_chunks * 32; i += 256) b1_l[i] = b1f[i];
-  for (int i = tid; i < XK; i += 256) b2_l[i] = b2f[i];
-  for (int i = tid; i < kGtBytes / 4; i += 256) ((uint32_t*)gt_l)[i] = ((const uint32_t*)gelu_tab)[i];
-
-  const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) void*)&lds[0]);
-  // producer: wave w issues pieces 12w .. 12w+11 of every stage
-  auto issue = [&](int chunk, int slot) {
-    const uint8_t* src = Wm + (size_t)chunk * MStage + (size_t)(wave * 12) * 1024 + lane * 16;
-    const uint32_t dst = lds0 + (uint32_t)slot * MStage + (uint32_t)(wave * 12) * 1024u;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      uint32_t keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\t"
-          "s_mov_b32 m0, %2\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, off\n\t"
-          "s_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "v"(src + i * 1024), "s"(dst + (uint32_t)i * 1024u)
-          : "memory");
-    }
-  };
-
-  // x rows of this wave: whole lines into registers, transposed to fragments through LDS, LayerNorm (see xs_kernel)
-  v8bf xf[XKS];
-  typedef float v2f __attribute__((ext_vector_type(2)));
-  uint8_t* const tp = lds + MOffTr + wave * XChunk;
-  const int prow = lane >> 3;
-  auto load_x = [&](int m0w) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int m = min(m0w + 8 * p + prow, M - 1);
-      const uint8_t* src = (const uint8_t*)X + (size_t)m * (XK * 2) + (lane & 7) * 16;
-#pragma unroll
-      for (int c = 0; c < XK / 64; ++c) *(v4u*)&xf[4 * c + p] = *(const v4u*)(src + c * 128);
-    }
-    const int fsw = (r >> 1) & 7;
-#pragma unroll
-    for (int c = 0; c < XK / 64; ++c) {
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int row = 8 * p + prow;
-        *(v4u*)(tp + row * 128 + (((lane & 7) ^ ((row >> 1) & 7)) << 4)) = *(const v4u*)&xf[4 * c + p];
-      }
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4)
-        xf[4 * c + k4] = *(const v8bf*)(tp + r * 128 + (((2 * k4 + h) ^ fsw) << 4));
-    }
-    auto expand = [](uint32_t u) { return (v2f){__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; };
-    v2f s2 = {0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < XKS; ++ks) {
-      const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s2 += expand(u[j]);
-    }
-    float sum = s2[0] + s2[1];
-    sum += __shfl_xor(sum, 32);
-    const float mean = sum * (1.0f / XK);
-    const v2f mean2 = {mean, mean};
-#pragma unroll
-    for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
-    v2f q2 = {0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < XKS; ++ks) {
-      const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { const v2f d = expand(u[j]) - mean2; q2 = __builtin_elementwise_fma(d, d, q2); }
-    }
-    float q = q2[0] + q2[1];
-    q += __shfl_xor(q, 32);
-    const float rstd = __builtin_amdgcn_rsqf(q * (1.0f / XK) + eps);
-    const v2f rstd2 = {rstd, rstd};
-#pragma unroll
-    for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
-#pragma unroll
-    for (int ks = 0; ks < XKS; ++ks) {
-      const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const v2f y = (expand(u[j]) - mean2) * rstd2;
-        xf[ks][2 * j] = (__bf16)y[0];
-        xf[ks][2 * j + 1] = (__bf16)y[1];
-      }
-    }
-  };
-
-  const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(X, 0, (int)((size_t)M * XK * 2), 0x00020000);
-  const int crow = lane >> 2, cch = lane & 3;
-  const int rsw = (r >> 2) & 3;
-  uint8_t* const tr_out = tp;
-  uint8_t* const tr_res = tp + 2048;
-
-  v16f oacc[12];
-  int tile = bid, chunk = 0, slot = 0;
-  issue(0, 0);
-  for (int i = 0; i < n; ++i) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (i + 1 < n) issue(chunk + 1 == n_chunks ? 0 : chunk + 1, slot ^ 1);   // into the slot read during iteration i-1
-    const int m0w = tile * 128 + wave * 32;
-    if (chunk == 0) {
-      load_x(m0w);
-#pragma unroll
-      for (int ob = 0; ob < 12; ++ob)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) oacc[ob][j] = 0.f;
-    }
-    const uint8_t* st = lds + slot * MStage + lane * 16;
-    // ---- fc1 chunk: H^T = W1c X^T, bias as the initial value --------------------------------------------
-    v16f hacc;
-    {
-      const float* bl = b1_l + chunk * 32 + 4 * h;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const v4f bv = *(const v4f*)(bl + 8 * g);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) hacc[4 * g + j] = bv[j];
-      }
-    }
-    {
-      constexpr int RD = 8;
-      v8bf wf[XKS];
-#pragma unroll
-      for (int ks = 0; ks < RD; ++ks) wf[ks] = *(const v8bf*)(st + ks * 1024);
-#pragma unroll
-      for (int ks = 0; ks < XKS; ++ks) {
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], hacc, 0, 0, 0);
-        if (ks + RD < XKS) wf[ks + RD] = *(const v8bf*)(st + (ks + RD) * 1024);
-      }
-    }
-    // ---- GELU: bf16 pairs -> table (float path for a wave that holds a value outside the table) -----------
-    typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-    uint32_t gp[8];
-    {
-      uint32_t pb[8], gbad = 0;
-#pragma unroll
-      for (int qd = 0; qd < 8; ++qd) {
-        const v2bf pr = {(__bf16)hacc[2 * qd], (__bf16)hacc[2 * qd + 1]};
-        pb[qd] = *(const uint32_t*)&pr;
-      }
-      uint32_t g0[8], g1[8];
-#pragma unroll
-      for (int qd = 0; qd < 8; ++qd) {
-        const uint32_t b0 = pb[qd] & 0xffffu, b1 = pb[qd] >> 16;
-        const uint32_t k0 = (b0 & 0x7fffu) - kGtLo, k1 = (b1 & 0x7fffu) - kGtLo;
-        gbad = max(gbad, max(k0, k1));
-        g0[qd] = *(const uint16_t*)(gt_l + min(k0, kGtN - 1) * 4 + ((b0 >> 15) << 1));
-        g1[qd] = *(const uint16_t*)(gt_l + min(k1, kGtN - 1) * 4 + ((b1 >> 15) << 1));
-      }
-      if (__any(gbad >= kGtN)) {
-#pragma unroll
-        for (int qd = 0; qd < 8; ++qd) {
-          const v2f_t y = gelu_erf2((v2f_t){__uint_as_float(pb[qd] << 16), __uint_as_float(pb[qd] & 0xffff0000u)});
-          const v2bf o = {(__bf16)y[0], (__bf16)y[1]};
-          gp[qd] = *(const uint32_t*)&o;
-        }
-      } else {
-#pragma unroll
-        for (int qd = 0; qd < 8; ++qd) gp[qd] = g0[qd] | (g1[qd] << 16);
-      }
-    }
-    // ---- fc2 partial: Out^T[12 x 32 features][32 tokens] += W2c G^T (registers 8s..8s+7 of the hidden tile are k-step s)
-    {
-      const v4u gA = {gp[0], gp[1], gp[2], gp[3]}, gB = {gp[4], gp[5], gp[6], gp[7]};
-      const v8bf g_s0 = *(const v8bf*)&gA, g_s1 = *(const v8bf*)&gB;
-      const uint8_t* st2 = st + XStage;
-      constexpr int RD = 8;
-      v8bf wf[24];
-#pragma unroll
-      for (int q = 0; q < RD; ++q) wf[q] = *(const v8bf*)(st2 + q * 1024);
-#pragma unroll
-      for (int q = 0; q < 24; ++q) {
-        oacc[q >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[q], (q & 1) ? g_s1 : g_s0, oacc[q >> 1], 0, 0, 0);
-        if (q + RD < 24) wf[q + RD] = *(const v8bf*)(st2 + (q + RD) * 1024);
-      }
-    }
-    // ---- last chunk of the row tile: + fc2 bias + residual, in place ----------------------------------------
-    if (chunk == n_chunks - 1) {
-#pragma unroll
-      for (int ob = 0; ob < 12; ++ob) {
-        v4u resq[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          resq[q] = *(const v4u*)(X + (size_t)min(m0w + crow + 16 * q, M - 1) * XK + ob * 32 + cch * 8);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int row = crow + 16 * q;
-          *(v4u*)(tr_res + row * 64 + ((cch ^ ((row >> 2) & 3)) << 4)) = resq[q];
-        }
-        uint32_t ep[8];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const v4bf rv = *(const v4bf*)(tr_res + r * 64 + ((g ^ rsw) << 4) + 8 * h);
-          const v4f bv = *(const v4f*)(b2_l + ob * 32 + 8 * g + 4 * h);
-          float v[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = oacc[ob][4 * g + j] + bv[j] + (float)rv[j];
-          const v2bf lo = {(__bf16)v[0], (__bf16)v[1]}, hi = {(__bf16)v[2], (__bf16)v[3]};
-          ep[2 * g] = *(const uint32_t*)&lo;
-          ep[2 * g + 1] = *(const uint32_t*)&hi;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(ep[k], ep[k + 4], false, false);
-          ep[k] = sw[0];
-          ep[k + 4] = sw[1];
-        }
-        *(v4u*)(tr_out + r * 64 + (((2 * h) ^ rsw) << 4)) = (v4u){ep[0], ep[1], ep[4], ep[5]};
-        *(v4u*)(tr_out + r * 64 + (((2 * h + 1) ^ rsw) << 4)) = (v4u){ep[2], ep[3], ep[6], ep[7]};
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int row = crow + 16 * q;
-          const v4u o = *(const v4u*)(tr_out + row * 64 + ((cch ^ ((row >> 2) & 3)) << 4));
-          __builtin_amdgcn_raw_buffer_store_b128(o, out_rs, (int)(((size_t)(m0w + row) * XK + ob * 32 + cch * 8) * 2), 0, 0);
-        }
-      }
-      tile += G;
-    }
-    slot ^= 1;
-    chunk = chunk + 1 == n_chunks ? 0 : chunk + 1;
-  }
-}
-
-// Role-split form of the fused MLP (the one that is launched): 8 waves, two per SIMD.  Waves 0-3 ("A") keep the
+// mlp2_kernel splits the work by role: 8 waves, two per SIMD.  Waves 0-3 ("A") keep the
 // normalised x rows and compute H^T chunk by chunk + the GELU; waves 4-7 ("B") keep the 384 x 32 output accumulators
 // and run fc2 one stage behind, taking the 32 x 32 bf16 activation tile of their partner (same SIMD, same 32 token rows)
-// through a 2 KiB LDS buffer.  Compared with one wave doing both (mlp_kernel above, kept for reference): both register
+// through a 2 KiB LDS buffer.  Compared with one wave doing both (the single-role kernel of DESIGN.md §4.3): both register
 // sets fit 256 VGPRs, so a SIMD holds an fc1 wave and an fc2 wave whose MFMA streams share the matrix pipe, the GELU's
 // integer work runs beside the partner's MFMAs, and the LDS-DMA pieces of a stage are issued by 8 waves instead of 4
 // (a piece occupies its wave for ~180 cycles: with 12 pieces per wave the staging alone took 2170 cycles per stage).
@@ -1280,7 +1006,7 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
   for (int i = tid; i < XK; i += 512) b2_l[i] = b2f[i];
   for (int i = tid; i < kGtBytes / 4; i += 512) ((uint32_t*)gt_l)[i] = ((const uint32_t*)gelu_tab)[i];
 
-  const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(__attribute__((address_space(3))) void*)&lds[0]);
+  const uint32_t lds0 = vc::lds_addr(&lds[0]);
   // producer: waves 0-3 issue the W1 half of a stage (chunk c1), waves 4-7 the W2 half (chunk c2), six pieces each.
   // One piece: wave-uniform base in SGPRs + one per-lane offset
   // shared by all pieces — with a 64-bit address per piece in VGPRs the compiler kept six pairs alive, spilled them,
@@ -1295,16 +1021,7 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
     const int c = half ? c2 : c1;
     const uint8_t* sbase = Wm + (size_t)c * MStage + (size_t)half * XStage + (size_t)idx * 1024;
     const uint32_t dst = lds0 + (uint32_t)slot * MStage + (uint32_t)half * XStage + (uint32_t)idx * 1024u;
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(lane_off), "s"(sbase), "s"(dst)
-        : "memory");
+    vc::lds_dma16(sbase, lane_off, dst);
   };
   auto issue = [&](int c1, int c2, int slot) {
 #pragma unroll
@@ -1631,58 +1348,32 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
   const __bf16 *px = (const __bf16*)x, *pw = (const __bf16*)weight, *pb = (const __bf16*)bias,
                *pr = (const __bf16*)residual_or_null;
   __bf16* po = (__bf16*)out;
-  int cus256 = 0;
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus256, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus256 <= 0)
-      cus256 = 256;
-  }
+  int cus = 0;
+  if (int st = vc::cu_count(&cus)) return st;
   // wide layers with enough 256 x 256 tiles to occupy at least half the CUs (one workgroup per CU); below that the 128 x 128
   // tile, two workgroups per CU, fills the chip better (a single image of ViT-B is 18-72 large tiles)
-  if (n_out % G2N == 0 && (long long)((rows + G2M - 1) / G2M) * (n_out / G2N) * 2 >= (long long)cus256) {
+  if (n_out % G2N == 0 && (long long)((rows + G2M - 1) / G2M) * (n_out / G2N) * 2 >= (long long)cus) {
     const int tiles_m = (rows + G2M - 1) / G2M, tiles_n = n_out / G2N;
     const long long nt = (long long)tiles_m * tiles_n;
     if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
-    const size_t smem = (size_t)G256_LDS;
     static vc::PerDeviceOnce configured;
-    if (int st = configured.run([] {
-          hipError_t r = hipFuncSetAttribute((const void*)gemm256_kernel<EPI_BIAS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          if (r == hipSuccess) r = hipFuncSetAttribute((const void*)gemm256_kernel<EPI_GELU, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          if (r == hipSuccess) r = hipFuncSetAttribute((const void*)gemm256_kernel<EPI_RESIDUAL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          return r;
-        }))
+    if (int st = vc::allow_dynamic_lds(configured, 160 * 1024, gemm256_kernel<EPI_BIAS, false>, gemm256_kernel<EPI_GELU, false>,
+                                       gemm256_kernel<EPI_RESIDUAL, false>))
       return st;
-    const int cus = cus256;
     const dim3 grid((unsigned)(nt < cus ? nt : cus)), block(512);
-    switch (epilogue) {
-      case EPI_BIAS:
-        hipLaunchKernelGGL((gemm256_kernel<EPI_BIAS, false>), grid, block, smem, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 0, 0, 0, 1, 0, 0, -1);
-        break;
-      case EPI_GELU:
-        hipLaunchKernelGGL((gemm256_kernel<EPI_GELU, false>), grid, block, smem, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 0, 0, 0, 1, 0, 0, -1);
-        break;
-      default:
-        hipLaunchKernelGGL((gemm256_kernel<EPI_RESIDUAL, false>), grid, block, smem, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 0, 0, 0, 1, 0, 0, -1);
-        break;
-    }
-    return vc::check_launch();
+    return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
+      hipLaunchKernelGGL((gemm256_kernel<epi, false>), grid, block, (size_t)G256_LDS, s, px, pw, pb, pr, po, rows, n_out, k_in,
+                         tiles_n, (int)nt, 0, 0, 0, 1, 0, 0, -1);
+      return vc::check_launch();
+    });
   }
   const int tiles_m = (rows + BM - 1) / BM, tiles_n = n_out / BN;
   const long long nt = (long long)tiles_m * tiles_n;
   if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)nt), block(256);
-  switch (epilogue) {
-    case EPI_BIAS:
-      hipLaunchKernelGGL(gemm_kernel<EPI_BIAS>, grid, block, 0, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 1);
-      break;
-    case EPI_GELU:
-      hipLaunchKernelGGL(gemm_kernel<EPI_GELU>, grid, block, 0, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 1);
-      break;
-    default:
-      hipLaunchKernelGGL(gemm_kernel<EPI_RESIDUAL>, grid, block, 0, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 1);
-      break;
-  }
-  return vc::check_launch();
+  return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
+    hipLaunchKernelGGL(gemm_kernel<epi>, dim3((unsigned)nt), dim3(256), 0, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 1);
+    return vc::check_launch();
+  });
 }
 
 
@@ -1705,25 +1396,18 @@ int vc_conv_taps_bf16(void* x, const void* weight, const void* bias, void* out, 
   const long long nt = (long long)tiles_m * tiles_n;
   if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
   static vc::PerDeviceOnce configured;
-  if (int st = configured.run([] {
-        hipError_t r = hipFuncSetAttribute((const void*)gemm256_kernel<EPI_BIAS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (r == hipSuccess) r = hipFuncSetAttribute((const void*)gemm256_kernel<EPI_GELU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return r;
-      }))
+  if (int st = vc::allow_dynamic_lds(configured, 160 * 1024, gemm256_kernel<EPI_BIAS, true>, gemm256_kernel<EPI_GELU, true>))
     return st;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  int cus = 0;
+  if (int st = vc::cu_count(&cus)) return st;
   const dim3 grid((unsigned)(nt < cus ? nt : cus)), block(512);
   const __bf16 *px = (const __bf16*)x, *pw = (const __bf16*)weight, *pb = (const __bf16*)bias;
   __bf16* po = (__bf16*)out;
-  if (epilogue == EPI_BIAS)
-    hipLaunchKernelGGL((gemm256_kernel<EPI_BIAS, true>), grid, block, (size_t)G256_LDS, s, px, pw, pb, (const __bf16*)nullptr, po, (int)rows,
-                       n_out, k_total, tiles_n, (int)nt, height, width, c_in, kw, dy0, dx0, out_parity);
-  else
-    hipLaunchKernelGGL((gemm256_kernel<EPI_GELU, true>), grid, block, (size_t)G256_LDS, s, px, pw, pb, (const __bf16*)nullptr, po, (int)rows,
-                       n_out, k_total, tiles_n, (int)nt, height, width, c_in, kw, dy0, dx0, out_parity);
-  return vc::check_launch();
+  return vc::dispatch<EPI_BIAS, EPI_GELU>(epilogue, [&](auto epi) {
+    hipLaunchKernelGGL((gemm256_kernel<epi, true>), grid, block, (size_t)G256_LDS, s, px, pw, pb, (const __bf16*)nullptr, po,
+                       (int)rows, n_out, k_total, tiles_n, (int)nt, height, width, c_in, kw, dy0, dx0, out_parity);
+    return vc::check_launch();
+  });
 }
 
 
@@ -1761,9 +1445,8 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
   if ((((uintptr_t)x) | ((uintptr_t)weight_tiled) | ((uintptr_t)bias_folded) | ((uintptr_t)residual_or_null) | ((uintptr_t)out)) % 16 != 0)
     return VC_ERR_INVALID_ARG;
   if (rows == 0) return VC_OK;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    return vc::fail(hipErrorInvalidDevice);
+  int cus = 0;
+  if (int st = vc::cu_count(&cus)) return st;
   const int n_nb = n_out / 32;
   const long long stages = (long long)((rows + XRows - 1) / XRows) * n_nb;
   if (stages > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
@@ -1776,17 +1459,19 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
   if (gt && (((uintptr_t)gt) % 16 != 0)) return VC_ERR_INVALID_ARG;
   // the table shares the 16 KiB staging area with the bias
   const bool use_gt = gt && epilogue == EPI_GELU && ((n_out * 4 + 15) & ~15) + kGtBytes <= XMaxN * 4;
-#define VC_XS_LAUNCH(E, L, G) \
-  hipLaunchKernelGGL((xs_kernel<E, L, G>), grid, block, 0, s, px, pw, bias_folded, pr, po, rows, n_out, n_nb, (int)stages, ln_eps, gt)
-  const bool ln = fuse_layernorm != 0;
-  if (epilogue == EPI_BIAS) { if (ln) VC_XS_LAUNCH(EPI_BIAS, true, false); else VC_XS_LAUNCH(EPI_BIAS, false, false); }
-  else if (epilogue == EPI_GELU) {
-    if (use_gt) { if (ln) VC_XS_LAUNCH(EPI_GELU, true, true); else VC_XS_LAUNCH(EPI_GELU, false, true); }
-    else { if (ln) VC_XS_LAUNCH(EPI_GELU, true, false); else VC_XS_LAUNCH(EPI_GELU, false, false); }
-  }
-  else { if (ln) VC_XS_LAUNCH(EPI_RESIDUAL, true, false); else VC_XS_LAUNCH(EPI_RESIDUAL, false, false); }
-#undef VC_XS_LAUNCH
-  return vc::check_launch();
+  auto launch = [&](auto epi, auto ln, auto gt_on) {
+    hipLaunchKernelGGL((xs_kernel<epi, ln, gt_on>), grid, block, 0, s, px, pw, bias_folded, pr, po, rows, n_out, n_nb, (int)stages,
+                       ln_eps, gt);
+    return vc::check_launch();
+  };
+  return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
+    return vc::dispatch<true, false>(fuse_layernorm != 0, [&](auto ln) {
+      if constexpr (epi == EPI_GELU) {   // only the GELU epilogue has a table variant
+        if (use_gt) return launch(epi, ln, std::true_type{});
+      }
+      return launch(epi, ln, std::false_type{});
+    });
+  });
 }
 
 
@@ -1809,7 +1494,7 @@ int vc_patch_embed_bf16(const void* patches, const void* weight, const void* bia
 
 
 size_t vc_mlp_weight_bytes(int n_hidden, int dim) {
-  if (dim != XK || n_hidden <= 0 || n_hidden % 32 != 0 || n_hidden > 2048) return 0;
+  if (dim != XK || n_hidden <= 0 || n_hidden % 32 != 0 || n_hidden > 1536) return 0;
   return (size_t)(n_hidden / 32) * MStage;
 }
 
@@ -1831,17 +1516,12 @@ int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded
   if ((((uintptr_t)x_inout) | ((uintptr_t)weights_tiled) | ((uintptr_t)b1_folded) | ((uintptr_t)b2) | ((uintptr_t)gelu_table)) % 16 != 0)
     return VC_ERR_INVALID_ARG;
   if (rows == 0) return VC_OK;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    return vc::fail(hipErrorInvalidDevice);
+  int cus = 0;
+  if (int st = vc::cu_count(&cus)) return st;
   const int n_tiles = (rows + 127) / 128;
   const dim3 grid((unsigned)(n_tiles < cus ? n_tiles : cus));
-  if (n_hidden > 1536)
-    hipLaunchKernelGGL(mlp_kernel, grid, dim3(256), 0, (hipStream_t)stream, (__bf16*)x_inout, (const uint8_t*)weights_tiled, b1_folded,
-                       b2, rows, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
-  else
-    hipLaunchKernelGGL(mlp2_kernel, grid, dim3(512), 0, (hipStream_t)stream, (__bf16*)x_inout, (const uint8_t*)weights_tiled, b1_folded,
-                       b2, rows, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
+  hipLaunchKernelGGL(mlp2_kernel, grid, dim3(512), 0, (hipStream_t)stream, (__bf16*)x_inout, (const uint8_t*)weights_tiled, b1_folded,
+                     b2, rows, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
   return vc::check_launch();
 }
 

@@ -25,6 +25,7 @@
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -274,17 +275,7 @@ __device__ __forceinline__ void glds16(const void* gsrc, u32 lds_dst_any) {
   // v_readfirstlane itself is the compiler's, which knows the wait state it needs after the VALU write of its
   // source — one written in asm right behind a v_mov read a stale register.)
   asm volatile("" : "+v"(lds_dst_any));
-  const u32 lds_dst = (u32)__builtin_amdgcn_readfirstlane((int)lds_dst_any);
-  u32 keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
+  vc::lds_dma16(gsrc, (u32)__builtin_amdgcn_readfirstlane((int)lds_dst_any));
 }
 
 inline int plan_slots2(int ks, int n_pad) {
@@ -296,21 +287,7 @@ inline int plan_slots2(int ks, int n_pad) {
 // One 256-byte LDS-DMA piece (64 lanes x 4 B; inactive lanes copy nothing): LDS destination = `lds_dst` + lane*4.
 __device__ __forceinline__ void glds4(const void* gsrc, u32 lds_dst_any) {
   asm volatile("" : "+v"(lds_dst_any));
-  const u32 lds_dst = (u32)__builtin_amdgcn_readfirstlane((int)lds_dst_any);
-  u32 keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dword %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
-__device__ __forceinline__ u32 lds_addr(const void* p) {
-  return (u32)(size_t)(__attribute__((address_space(3))) const void*)p;
+  vc::lds_dma4(gsrc, (u32)__builtin_amdgcn_readfirstlane((int)lds_dst_any));
 }
 
 // Producer side of the ring.  The KS pieces of a tile are dealt to NP producer waves, M pieces
@@ -729,7 +706,7 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
     for (int i = tid; i < n1; i += kThreads) { rbest_s[i] = 0; rsecond_s[i] = 0; ridx_s[i] = -1; }
   const int rbias = -49024 * d;
   int* crow6_wave = crow6 + wave * 64;
-  const u32 ring_lds = (u32)__builtin_amdgcn_readfirstlane((int)lds_addr(ring));
+  const u32 ring_lds = vc::lds_addr(ring);
 
   // producer / consumer cursors over the tile sequence
   int prod_seq = 0, prod_jt = 0, prod_slot = 0;
@@ -1003,7 +980,9 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   int* crow6d_wave = crow6d + wave * 64;
   const size_t img_stride = image_bytes(n_tiles_img, KS);
   const size_t frag_bytes_img = (size_t)n_tiles_img * KS * kFragBytes;
-  const u32 ring_lds = (u32)__builtin_amdgcn_readfirstlane((int)lds_addr(ring));
+  // readfirstlane written out here rather than vc::lds_addr: through the helper the compiler moves the address-space cast
+  // behind the readfirstlane and allocates this kernel's SGPRs differently
+  const u32 ring_lds = (u32)__builtin_amdgcn_readfirstlane((int)vc::lds_offset(ring));
 
   // this workgroup's range of the pair list
   const int G = gridDim.x;
@@ -1098,8 +1077,8 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   // thread has read that pair's own sums by then — and are read a whole pair later, after that wave's wait and the
   // barrier that ends the pair in between.
   constexpr int kAuxWave = kWaves / 2;
-  const u32 auxw_lds = (u32)__builtin_amdgcn_readfirstlane((int)lds_addr(auxw));
-  const u32 auxt_lds = (u32)__builtin_amdgcn_readfirstlane((int)lds_addr(auxt));
+  const u32 auxw_lds = (u32)__builtin_amdgcn_readfirstlane((int)vc::lds_offset(auxw));
+  const u32 auxt_lds = (u32)__builtin_amdgcn_readfirstlane((int)vc::lds_offset(auxt));
   auto stage_aux = [&](const PairInfo& pi) {
     if (wave == kAuxWave && pi.p < hi) {
       int ln = lane;   // (laundered: lane-derived addresses are computed here, not carried across the tile loop)
@@ -1497,11 +1476,7 @@ int launch_pair(const void* prepared, const int32_t* counts, int n_tiles, int d,
   if (ns == 0 || (RT == 2 && ns < 3)) return VC_ERR_UNSUPPORTED;
   const size_t smem = (size_t)ns * KS * kFragBytes + lds_fixed_bytes(n_pad);
   static vc::PerDeviceOnce configured;  // per instantiation and device
-  if (int st = configured.run([] {
-        return hipFuncSetAttribute((const void*)pair_kernel<KS, RT, FUSED>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-      }))
-    return st;
+  if (int st = vc::allow_dynamic_lds(configured, kLdsBytes, pair_kernel<KS, RT, FUSED>)) return st;
   hipLaunchKernelGGL((pair_kernel<KS, RT, FUSED>), dim3(n_pairs), dim3(kThreads), smem, stream,
                      (const uint8_t*)prepared, counts, n_tiles, d, pairs, max_ratio, max_distance,
                      cross_check, n_max, ns, s_low, out_matches, out_counts, o_idx, o_best, o_second);
@@ -1519,14 +1494,9 @@ int launch_pair2(const void* prepared, const int32_t* counts, int n_tiles, int d
   if (ns < 3) return VC_ERR_UNSUPPORTED;
   const size_t smem = (size_t)ns * KS * kFragBytes + lds_fixed_bytes2(n_pad);
   static vc::PerDeviceOnce configured;
-  if (int st = configured.run([] {
-        return hipFuncSetAttribute((const void*)pair2_kernel<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-      }))
-    return st;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  if (int st = vc::allow_dynamic_lds(configured, kLdsBytes, pair2_kernel<KS>)) return st;
+  int cus = 0;
+  if (int st = vc::cu_count(&cus)) return st;
   const int grid = n_pairs < cus ? n_pairs : cus;
   hipLaunchKernelGGL((pair2_kernel<KS>), dim3(grid), dim3(kThreads), smem, stream, (const uint8_t*)prepared, counts,
                      n_tiles, d, pairs, n_pairs, max_ratio, max_distance, cross_check, n_max, ns, s_low, out_matches,
@@ -1541,16 +1511,11 @@ int dispatch_pair(int ks, const void* prepared, const int32_t* counts, int n_til
                   const int32_t* pairs, int n_pairs, float max_ratio, float max_distance,
                   int cross_check, int n_max, uint32_t* out_matches, int32_t* out_counts,
                   int32_t* o_idx, int32_t* o_best, int32_t* o_second, hipStream_t stream) {
-#define VC_CASE(K, R)                                                                           \
-  case K:                                                                                       \
-    return launch_pair<K, R, FUSED>(prepared, counts, n_tiles, d, pairs, n_pairs, max_ratio,    \
-                                    max_distance, cross_check, n_max, out_matches, out_counts,  \
-                                    o_idx, o_best, o_second, stream);
-  switch (ks) {
-    VC_CASE(2, 2) VC_CASE(4, 2) VC_CASE(8, 2) VC_CASE(12, 2) VC_CASE(16, 1) VC_CASE(24, 1) VC_CASE(32, 1)
-    default: return VC_ERR_UNSUPPORTED;
-  }
-#undef VC_CASE
+  return vc::dispatch<2, 4, 8, 12, 16, 24, 32>(ks, [&](auto k) {
+    return launch_pair<k, (k <= 12 ? 2 : 1), FUSED>(prepared, counts, n_tiles, d, pairs, n_pairs, max_ratio, max_distance,
+                                                     cross_check, n_max, out_matches, out_counts, o_idx, o_best, o_second,
+                                                     stream);
+  });
 }
 
 }  // namespace
@@ -1587,17 +1552,11 @@ int vc_match_pairs_u8(const void* prepared, const int32_t* counts, int n_images,
   if (n_images <= 0 || n_max <= 0 || d <= 0 || n_pairs < 0) return VC_ERR_INVALID_ARG;
   if (n_max > VC_MAX_KEYPOINTS || d > VC_MAX_DESC_DIM) return VC_ERR_UNSUPPORTED;
   if (n_pairs == 0) return VC_OK;
-  int st2 = VC_ERR_UNSUPPORTED;
-  switch (pick_ks(d)) {   // descriptors up to 384 bytes: the persistent kernel (two row tiles per wave)
-#define VC_CASE2(K)                                                                                      \
-  case K:                                                                                                \
-    st2 = launch_pair2<K>(prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio, max_distance, \
-                          cross_check, n_max, out_matches, out_counts, (hipStream_t)stream);             \
-    break;
-    VC_CASE2(2) VC_CASE2(4) VC_CASE2(8) VC_CASE2(12)
-#undef VC_CASE2
-    default: break;
-  }
+  // descriptors up to 384 bytes: the persistent kernel (two row tiles per wave)
+  const int st2 = vc::dispatch<2, 4, 8, 12>(pick_ks(d), [&](auto k) {
+    return launch_pair2<k>(prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio, max_distance, cross_check,
+                           n_max, out_matches, out_counts, (hipStream_t)stream);
+  });
   if (st2 != VC_ERR_UNSUPPORTED) return st2;   // (blocks too large for its LDS plan: the kernel with one workgroup per pair)
   return dispatch_pair<true>(pick_ks(d), prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio,
                              max_distance, cross_check, n_max, out_matches, out_counts, nullptr,

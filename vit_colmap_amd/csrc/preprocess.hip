@@ -15,6 +15,7 @@
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -41,19 +42,12 @@ __device__ inline Coef linear_coef(int d, int src, double scale) {
   return c;
 }
 
-__device__ inline uint16_t f32_to_bf16(float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 template <typename OutT>
 __device__ inline void store(OutT* p, float v);
 template <>
 __device__ inline void store<float>(float* p, float v) { *p = v; }
 template <>
-__device__ inline void store<uint16_t>(uint16_t* p, float v) { *p = f32_to_bf16(v); }
+__device__ inline void store<uint16_t>(uint16_t* p, float v) { *p = vc::f32_to_bf16(v); }
 
 template <typename OutT>
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ img, int h, int w, int oh,
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(256) void preprocess_patches_kernel(const uint8_t* 
     for (int i = threadIdx.x; i < 768; i += 256) {
       const int c = i >> 8;
       const float t = (float)(i & 255) / 255.0f;
-      norm_l[c][i & 255] = f32_to_bf16((t - mean[c]) / stdv[c]);
+      norm_l[c][i & 255] = vc::f32_to_bf16((t - mean[c]) / stdv[c]);
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

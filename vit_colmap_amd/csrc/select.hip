@@ -26,6 +26,7 @@
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -33,14 +34,12 @@ constexpr int kMaxCells = 16384;      // H*W of one score map held in LDS (64 Ki
 constexpr int kMaxCandidates = 4096;  // keypoint candidates per image
 constexpr int kSelThreads = 512;
 
-__device__ inline float bf16_to_f32(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-
 template <typename T>
 __device__ inline float load_token(const T* p, int i);
 template <>
 __device__ inline float load_token<float>(const float* p, int i) { return p[i]; }
 template <>
-__device__ inline float load_token<uint16_t>(const uint16_t* p, int i) { return bf16_to_f32(p[i]); }
+__device__ inline float load_token<uint16_t>(const uint16_t* p, int i) { return vc::bf16_to_f32(p[i]); }
 
 __device__ inline float wave_sum(float v) {
 #pragma unroll
@@ -564,11 +563,7 @@ int vc_score_map(const float* st, int n_images, int H, int W, int method, float*
   if (n_images == 0) return VC_OK;
   const size_t smem = ((size_t)2 * H * W + 32) * sizeof(float);
   static vc::PerDeviceOnce configured;
-  if (int st = configured.run([] {
-        return hipFuncSetAttribute((const void*)score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)((2 * kMaxCells + 32) * sizeof(float)));
-      }))
-    return st;
+  if (int st = vc::allow_dynamic_lds(configured, (int)((2 * kMaxCells + 32) * sizeof(float)), score_kernel)) return st;
   // kernel sizes as the reference derives them: k = int(6 sigma + 1), made odd (vit_extractor.py:371-374)
   const Taps g3 = make_taps(3, 1.0f), g7 = make_taps(7, 1.0f), g11 = make_taps(11, 1.6f);
   hipLaunchKernelGGL(score_kernel, dim3(n_images), dim3(kSelThreads), smem, (hipStream_t)stream, st, H, W,
@@ -595,10 +590,7 @@ int vc_select_keypoints(const float* score, int n_images, int H, int W, int targ
   constexpr int kDynMax = 160 * 1024 - 1024;  // the kernel also has a few static LDS words
   if (smem > (size_t)kDynMax) return VC_ERR_UNSUPPORTED;
   static vc::PerDeviceOnce configured;
-  if (int st = configured.run([] {
-        return hipFuncSetAttribute((const void*)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynMax);
-      }))
-    return st;
+  if (int st = vc::allow_dynamic_lds(configured, kDynMax, select_kernel)) return st;
   hipLaunchKernelGGL(select_kernel, dim3(n_images), dim3(kSelThreads), smem, (hipStream_t)stream, score, H, W,
                      target, bin_size, nms_radius, kmax, out_yx, out_score, out_count, dbg_cand_yx,
                      dbg_cand_score, dbg_cand_count);

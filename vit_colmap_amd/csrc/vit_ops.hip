@@ -12,19 +12,13 @@
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
+#include "device.h"
 
 namespace {
 
 typedef uint16_t bf16_t;
 constexpr int kMaxChunksPerLane = 4;  // C <= 64 lanes * 4 chunks * 8 = 2048
 
-__device__ inline float bf2f(bf16_t v) { return __uint_as_float((uint32_t)v << 16); }
-__device__ inline bf16_t f2bf(float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
 __device__ inline float wsum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -65,10 +59,10 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const bf16_t* __rest
       Vec8 o;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        float t = bf2f(a.e[i]);
+        float t = vc::bf16_to_f32(a.e[i]);
         if (HAS_RES) {
-          o.e[i] = f2bf(t + bf2f(b.e[i]));   // the residual stream is stored in bf16
-          t = bf2f(o.e[i]);
+          o.e[i] = vc::f32_to_bf16(t + vc::bf16_to_f32(b.e[i]));   // the residual stream is stored in bf16
+          t = vc::bf16_to_f32(o.e[i]);
         }
         v[k][i] = t;
         s += t;
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const bf16_t* __rest
       const Vec8 bb = *(const Vec8*)(beta + ch * 8);
       Vec8 o;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o.e[i] = f2bf((v[k][i] - mean) * rstd * bf2f(g.e[i]) + bf2f(bb.e[i]));
+      for (int i = 0; i < 8; ++i) o.e[i] = vc::f32_to_bf16((v[k][i] - mean) * rstd * vc::bf16_to_f32(g.e[i]) + vc::bf16_to_f32(bb.e[i]));
       *(Vec8*)(y_out + ybase + ch * 8) = o;
     }
   }

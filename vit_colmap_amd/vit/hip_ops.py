@@ -173,9 +173,9 @@ def gelu_table(device) -> torch.Tensor:
 
 
 class FusedMlp:
-    """x += fc2(gelu(fc1(LayerNorm(x)))) in one kernel (csrc/gemm.hip, mlp2_kernel; mlp_kernel for n_hidden > 1536),
-    dim 384.  Built once from float32 parameters (fc2 with LayerScale already folded in); call with the bf16 residual
-    stream, updated in place."""
+    """x += fc2(gelu(fc1(LayerNorm(x)))) in one kernel (csrc/gemm.hip, mlp2_kernel), dim 384, n_hidden <= 1536.
+    Built once from float32 parameters (fc2 with LayerScale already folded in); call with the bf16 residual stream,
+    updated in place."""
 
     def __init__(self, w1, b1, ln_weight, ln_bias, w2, b2, ln_eps: float = 1e-6):
         lib = _lib.load()
