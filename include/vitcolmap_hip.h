@@ -321,7 +321,8 @@ int vc_conv_taps_bf16(void* x, const void* weight, const void* bias, void* out, 
  * vc_linear_xs_bf16: x [rows][384] bf16, out [rows][n_out] bf16, epilogue as vc_linear_bf16;
  *   fuse_layernorm != 0 normalises each x row first (two-pass float32 statistics, eps = ln_eps; the
  *   weights must have been prepared with that LayerNorm's gamma / beta).  residual may alias out.
- *   n_out % 32 == 0, n_out <= 4096, 16-byte aligned pointers.  Launches one persistent workgroup per CU.
+ *   n_out % 32 == 0, n_out <= 4096, 16-byte aligned pointers.  Launches one persistent workgroup per CU; an output of 2 GiB
+ *   or more is written by consecutive launches over row ranges (the kernel's result store takes 32-bit byte offsets).
  */
 size_t vc_linear_xs_weight_bytes(int n_out, int k_in);
 int vc_linear_xs_prepare(const float* weight, const float* bias_or_null, const float* ln_gamma_or_null,
@@ -361,7 +362,8 @@ int vc_patch_embed_bf16(const void* patches, const void* weight, const void* bia
  * vc_mlp_prepare (once per block): w1 [n_hidden][384], b1 [n_hidden], LayerNorm gamma / beta [384] (or both NULL),
  *   w2 [384][n_hidden], b2 [384], all float32  ->  weights_tiled (vc_mlp_weight_bytes bytes, stage order), b1_folded
  *   [n_hidden] float32, b2_out [384] float32.  n_hidden % 32 == 0, n_hidden <= 1536.
- * vc_mlp_bf16: x_inout [rows][384] bf16, updated in place.  gelu_table from vc_gelu_table_bf16.
+ * vc_mlp_bf16: x_inout [rows][384] bf16, updated in place.  gelu_table from vc_gelu_table_bf16.  Row ranges of less than
+ *   2 GiB per launch, as in vc_linear_xs_bf16.
  */
 size_t vc_mlp_weight_bytes(int n_hidden, int dim);
 int vc_mlp_prepare(const float* w1, const float* b1_or_null, const float* ln_gamma_or_null,

@@ -110,3 +110,63 @@ def test_checkpoint_roundtrip(tmp_path):
         assert n1 == n2 and torch.equal(p1, p2)
     with pytest.raises(ValueError):
         load_dinov2_weights(build_dinov2("dinov2_vitb14"), str(path))
+
+
+@pytest.mark.parametrize("name", ["dinov2_vits14", "dinov2_vitl14", "dinov2_vits14_reg", "dinov2_vitb14_reg", "dinov2_vitg14"])
+def test_padded_patch_layout_only_without_registers(name):
+    """The padded layout is taken only by prepared models without register tokens (the patch-embedding GEMM writes rows 1..
+    of every image): register models run the unpadded layout into the same hand-written block stack."""
+    from vit_colmap_amd.vit import DINOV2_ARCHS, build_dinov2
+
+    m = build_dinov2(name).eval()
+    assert m.accepts_padded_patches is False                          # nothing prepared yet
+    m._hip = [dict(kind="gemm")] * m.arch.depth                      # what prepare_hip leaves behind on the GPU
+    assert m.accepts_padded_patches is (DINOV2_ARCHS[name].registers == 0)
+    m._hip = False                                                    # an architecture prepare_hip does not cover
+    assert m.accepts_padded_patches is False
+    m._hip = [dict(kind="gemm")] * m.arch.depth
+    m.train()
+    assert m.accepts_padded_patches is False
+
+
+def test_prepare_grid_builds_the_position_embedding_once():
+    from vit_colmap_amd.vit import build_dinov2
+
+    m = build_dinov2("dinov2_vits14_reg").init_random(seed=2).eval()
+    with torch.no_grad():
+        assert m.prepare_grid(34, 45, "cpu") is None                  # (a CUDA model gets the event behind the build)
+        built = dict(m._pos_cache)
+        assert len(built) == 1
+        m.prepare_grid(34, 45, "cpu")
+        assert m._pos_cache == built                                  # once per grid
+        cached = m.interpolated_pos_embed(34, 45)
+        assert cached is next(iter(built.values()))
+        m.prepare_grid(20, 30, "cpu")
+    assert tuple(cached.shape) == (1, 1 + 34 * 45, 384) and len(m._pos_cache) == 2
+
+
+def test_token_error_report_localises_errors():
+    """tests/util_vit.py: one wrong image or one wrong tail row is visible per image / per row although the batch-wide
+    rel-L2 barely moves."""
+    from util_vit import TAIL_ROWS, assert_token_errors, token_errors
+
+    g = torch.Generator().manual_seed(0)
+    ref = torch.randn(50, 1531, 64, generator=g)
+    got = ref + 1e-2 * torch.randn(ref.shape, generator=g) * ref.norm(dim=2, keepdim=True) / 8
+    e = token_errors(got, ref)
+    assert len(e["per_image"]) == 50 and max(e["per_image"]) < 1.2e-2 and 0.9e-2 < e["row_median"] < 1.1e-2
+    assert_token_errors(e, 2e-2, 3.5e-2)
+    bad = got.clone()
+    bad[17, -31:] = ref[17, -31:] * 1.05                               # the ragged last row tile of one image, 5 % off
+    assert ((bad - ref).norm() / ref.norm()).item() < 1.1e-2          # invisible in the batch aggregate
+    e = token_errors(bad, ref)
+    assert e["row_argmax"][0] == 17 and e["row_argmax"][1] >= 1531 - 31 and e["tail_max"] > 4e-2
+    with pytest.raises(AssertionError):
+        assert_token_errors(e, 2e-2, 3.5e-2)
+    bad = got.clone()
+    bad[3] = ref[3] * 1.03                                            # one image 3 % off everywhere
+    e = token_errors(bad, ref)
+    assert e["per_image"][3] > 2.5e-2 and e["tail_max"] >= e["row_median"]
+    with pytest.raises(AssertionError):
+        assert_token_errors(e, 2e-2, 3.5e-2)
+    assert TAIL_ROWS == 256

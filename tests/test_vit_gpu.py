@@ -3,7 +3,13 @@ import numpy as np
 import pytest
 import torch
 
+from util_vit import attention_reference
+
 pytestmark = pytest.mark.gpu
+
+# product shapes of the attention kernel: (B, N, H) = the DTU grid of ViT-B (85 x 114 + 1 tokens), the bench batch (50 images x
+# 6 heads x 6 query blocks = 1800 work units, several rounds on the chip), ViT-L with 4 registers (16 heads)
+ATTN_PRODUCT_SHAPES = [(2, 9691, 12), (50, 1531, 6), (2, 1535, 16)]
 
 
 @pytest.mark.parametrize("rows,C", [(1531 * 3, 384), (777, 768), (5, 1024), (64, 1536), (1, 64)])
@@ -49,7 +55,8 @@ def test_fused_block_path_equals_unfused_modules():
     assert rel < 1e-2, rel           # two bf16 evaluation orders of the same network
 
 
-@pytest.mark.parametrize("B,N,H", [(2, 1531, 6), (1, 64, 1), (3, 257, 12), (1, 100, 2), (2, 128, 6), (1, 1, 6)])
+@pytest.mark.parametrize("B,N,H", [(2, 1531, 6), (1, 64, 1), (3, 257, 12), (1, 100, 2), (2, 128, 6), (1, 1, 6)]
+                         + ATTN_PRODUCT_SHAPES)
 def test_attention_matches_float32_reference(B, N, H):
     """Hand-written flash attention (through the C ABI) vs softmax(QK^T/8)V in float32."""
     from vit_colmap_amd.vit.hip_ops import attention
@@ -57,9 +64,7 @@ def test_attention_matches_float32_reference(B, N, H):
     g = torch.Generator(device="cuda").manual_seed(B * 1000 + N + H)
     qkv = torch.randn(B, N, 3 * H * 64, device="cuda", generator=g).to(torch.bfloat16)
     out = attention(qkv, H).float()
-    q, k, v = qkv.float().reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4)
-    att = torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1)
-    ref = (att @ v).transpose(1, 2).reshape(B, N, H * 64)
+    ref = attention_reference(qkv, H, 0.125)
     err = (out - ref).abs().max().item()
     rel = ((out - ref).norm() / ref.norm()).item()
     assert rel < 1e-2 and err < 5e-2, (err, rel)          # bf16 P and bf16 output
@@ -93,7 +98,10 @@ def test_attention_structured_values_catch_layout_errors():
                                       (1, 64, 128), (129, 768, 2304), (128, 128, 256),
                                       (1531 * 3, 1536, 384), (4096, 64, 128), (4097, 640, 384),
                                       # the 256 x 256 tile kernel (n_out % 256 == 0, >= 1024 rows): ragged last row tile, one and many K steps
-                                      (1531 * 2, 768, 2304), (1024, 64, 256), (1025, 3072, 768), (2047, 768, 768), (5000, 1024, 4096)])
+                                      (1531 * 2, 768, 2304), (1024, 64, 256), (1025, 3072, 768), (2047, 768, 768), (5000, 1024, 4096),
+                                      # ViT-L at two 640 x 480 frames (qkv, proj, fc1, fc2) and ViT-B at two DTU frames (qkv)
+                                      (3062, 1024, 3072), (3062, 1024, 1024), (3062, 1024, 4096), (3062, 4096, 1024),
+                                      (19382, 768, 2304)])
 @pytest.mark.parametrize("epi", [0, 1, 2])
 def test_linear_matches_float32_reference(rows, K, N, epi):
     """Hand-written bf16 GEMM + fused epilogue (through the C ABI) vs the float32 evaluation of the same bf16 data."""
@@ -323,7 +331,7 @@ def test_xs_gelu_table_is_the_bf16_gelu_for_every_input():
         assert bool((err <= ref32.abs() * 2 ** -8 + 2e-7 * (1 + x.float().abs())).all()), float(err.max())
 
 
-@pytest.mark.parametrize("B,N,H", [(2, 1531, 6), (1, 64, 1), (3, 257, 12), (1, 100, 2), (1, 1, 6)])
+@pytest.mark.parametrize("B,N,H", [(2, 1531, 6), (1, 64, 1), (3, 257, 12), (1, 100, 2), (1, 1, 6)] + ATTN_PRODUCT_SHAPES)
 @pytest.mark.parametrize("spread", [1.0, 6.0])
 def test_attention_prescaled_q_lazy_max(B, N, H, spread):
     """q_prescaled mode (q carries (1/8) log2 e; running maximum subtracted inside the product, deferred max) vs float32
@@ -339,9 +347,7 @@ def test_attention_prescaled_q_lazy_max(B, N, H, spread):
     qkv[:, :, 1] *= torch.linspace(0.5, 1.5, N, device="cuda")[None, :, None, None]
     qkv = qkv.to(torch.bfloat16).reshape(B, N, 3 * H * 64).contiguous()
     out = attention(qkv, H, q_prescaled=True).float()
-    q, k, v = qkv.float().reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4)
-    att = torch.softmax(q @ k.transpose(-1, -2) * math.log(2.0), dim=-1)
-    ref = (att @ v).transpose(1, 2).reshape(B, N, H * 64)
+    ref = attention_reference(qkv, H, math.log(2.0))
     err = (out - ref).abs()
     assert float(err.max()) < 3e-2 and float((out - ref).norm() / ref.norm()) < 1e-2, (float(err.max()), float((out - ref).norm() / ref.norm()))
 
@@ -386,3 +392,75 @@ def test_layernorm_drop_first_equals_layernorm_of_the_remaining_rows():
         y = layernorm_drop_first(x, w, b, 1e-6)
         assert tuple(y.shape) == (B, N - 1, C)
         assert torch.equal(y.view(torch.int16), full[:, 1:].contiguous().view(torch.int16))
+
+
+def _row_blocks(rows, row_bytes, n=64):
+    """Row ranges to check in an output of `rows` x `row_bytes`: the first rows, the rows straddling the 2 GiB and the 4 GiB
+    byte marks, the last rows."""
+    out = [(0, n)]
+    for mark in (1 << 31, 1 << 32):
+        r = mark // row_bytes
+        if r + n <= rows:
+            out.append((r - n // 2, r + n // 2))
+    out.append((rows - n, rows))
+    return out
+
+
+def test_xs_linear_output_past_4_gib():
+    """vc_linear_xs_bf16 with an output of 4.4 GB (1.9 M rows x 1152, the qkv GEMM of ~1240 frames of 640 x 480 in one call):
+    the kernel's result store addresses 32-bit byte offsets, so the entry has to split the launch.  The output is filled with a
+    sentinel first; sampled row blocks across the 2 GiB and 4 GiB marks are checked against float32, and no sentinel may be
+    left anywhere."""
+    from vit_colmap_amd.vit.hip_ops import XsLinear
+
+    rows, K, N = 1_900_000, 384, 1152
+    assert rows * N * 2 > 1 << 32
+    g = torch.Generator(device="cuda").manual_seed(41)
+    x = torch.randn(rows, K, device="cuda", generator=g, dtype=torch.bfloat16)
+    w = torch.randn(N, K, device="cuda", generator=g) / K ** 0.5 * torch.linspace(0.5, 2.0, N, device="cuda")[:, None]
+    b = torch.randn(N, device="cuda", generator=g)
+    gam = 1 + 0.2 * torch.randn(K, device="cuda", generator=g)
+    bet = 0.1 * torch.randn(K, device="cuda", generator=g)
+    sentinel = -12345.0                                   # exact in bf16, far outside the outputs' range
+    out = torch.full((rows, N), sentinel, dtype=torch.bfloat16, device="cuda")
+    XsLinear(w, b, gam, bet, 1e-6)(x, 0, out=out)
+    for lo, hi in _row_blocks(rows, N * 2):
+        ref = torch.nn.functional.layer_norm(x[lo:hi].float(), (K,), gam, bet, 1e-6) @ w.t() + b
+        got = out[lo:hi].float()
+        err = (got - ref).abs()
+        tol = ref.abs() * 2 ** -7 + 6e-2                  # the tolerance of test_xs_linear_matches_float32_reference
+        assert bool((err <= tol).all()), ((lo, hi), float(err.max()), int((err > tol).sum()))
+    for lo in range(0, rows, 1 << 18):                    # nothing left unwritten (in slices: no 4 GB temporary)
+        assert not bool((out[lo:lo + (1 << 18)] == sentinel).any()), f"sentinel left in rows {lo}.."
+    del x, out
+    torch.cuda.empty_cache()
+
+
+def test_fused_mlp_output_past_4_gib():
+    """vc_mlp_bf16 on 5.6 M rows x 384 (4.3 GB, updated in place: the stores pass the 4 GiB byte mark).  Sampled row blocks
+    across the 2 GiB and 4 GiB marks against float32 on a copy of their input rows."""
+    from vit_colmap_amd.vit.hip_ops import FusedMlp
+
+    K, Hd = 384, 1536
+    rows = (1 << 32) // (K * 2) + 7_595                   # 5 600 000: just past 4 GiB
+    assert rows * K * 2 > 1 << 32
+    g = torch.Generator(device="cuda").manual_seed(43)
+    x = torch.randn(rows, K, device="cuda", generator=g, dtype=torch.bfloat16)
+    w1 = torch.randn(Hd, K, device="cuda", generator=g) / K ** 0.5 * torch.linspace(0.5, 2.0, Hd, device="cuda")[:, None]
+    b1 = 0.5 * torch.randn(Hd, device="cuda", generator=g)
+    w2 = torch.randn(K, Hd, device="cuda", generator=g) / Hd ** 0.5 * torch.linspace(0.5, 1.5, K, device="cuda")[:, None]
+    b2 = torch.randn(K, device="cuda", generator=g)
+    gam = 1 + 0.2 * torch.randn(K, device="cuda", generator=g)
+    bet = 0.1 * torch.randn(K, device="cuda", generator=g)
+    blocks = _row_blocks(rows, K * 2)
+    inputs = [x[lo:hi].float() for lo, hi in blocks]
+    FusedMlp(w1, b1, gam, bet, w2, b2, 1e-6)(x)
+    for (lo, hi), xin in zip(blocks, inputs):
+        h = torch.nn.functional.layer_norm(xin, (K,), gam, bet, 1e-6) @ w1.t() + b1
+        hg = torch.nn.functional.gelu(h.to(torch.bfloat16).float()).to(torch.bfloat16).float()
+        ref = xin + hg @ w2.t() + b2
+        err = (x[lo:hi].float() - ref).abs()
+        tol = ref.abs() * 2 ** -6 + 0.12                  # the tolerance of test_fused_mlp_matches_float32_reference
+        assert bool((err <= tol).all()), ((lo, hi), float(err.max()), int((err > tol).sum()))
+    del x
+    torch.cuda.empty_cache()

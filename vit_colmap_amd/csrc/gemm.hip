@@ -1333,6 +1333,13 @@ __global__ __launch_bounds__(256) void mlp_prepare_kernel(const float* __restric
 
 }  // namespace
 
+// Rows per launch of a kernel whose result store addresses 32-bit byte offsets from the output base: the largest multiple of
+// `tile_rows` whose [rows][n_cols] bf16 output stays below 2 GiB.
+static int max_rows_below_2gib(int n_cols, int tile_rows) {
+  const long long r = ((1LL << 31) - 1) / ((long long)n_cols * 2);
+  return (int)(r / tile_rows * tile_rows);
+}
+
 extern "C" {
 
 int vc_linear_bf16(const void* x, const void* weight, const void* bias, const void* residual_or_null, void* out,
@@ -1448,30 +1455,38 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
   const int n_nb = n_out / 32;
-  const long long stages = (long long)((rows + XRows - 1) / XRows) * n_nb;
-  if (stages > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)(stages < cus ? stages : cus)), block(512);
   hipStream_t s = (hipStream_t)stream;
-  const __bf16 *px = (const __bf16*)x, *pr = (const __bf16*)residual_or_null;
   const uint8_t* pw = (const uint8_t*)weight_tiled;
-  __bf16* po = (__bf16*)out;
   const uint16_t* gt = (const uint16_t*)gelu_table_or_null;
   if (gt && (((uintptr_t)gt) % 16 != 0)) return VC_ERR_INVALID_ARG;
   // the table shares the 16 KiB staging area with the bias
   const bool use_gt = gt && epilogue == EPI_GELU && ((n_out * 4 + 15) & ~15) + kGtBytes <= XMaxN * 4;
-  auto launch = [&](auto epi, auto ln, auto gt_on) {
-    hipLaunchKernelGGL((xs_kernel<epi, ln, gt_on>), grid, block, 0, s, px, pw, bias_folded, pr, po, rows, n_out, n_nb, (int)stages,
-                       ln_eps, gt);
-    return vc::check_launch();
-  };
-  return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
-    return vc::dispatch<true, false>(fuse_layernorm != 0, [&](auto ln) {
-      if constexpr (epi == EPI_GELU) {   // only the GELU epilogue has a table variant
-        if (use_gt) return launch(epi, ln, std::true_type{});
-      }
-      return launch(epi, ln, std::false_type{});
+  // The kernel stores its results through a buffer resource with a 32-bit record count and 32-bit byte offsets: one launch
+  // writes less than 2 GiB of output, a longer call is split into launches over consecutive row ranges.
+  const int chunk = max_rows_below_2gib(n_out, XRows);
+  for (long long r0 = 0; r0 < rows; r0 += chunk) {
+    const int m = (int)(rows - r0 < chunk ? rows - r0 : chunk);
+    const int stages = (m + XRows - 1) / XRows * n_nb;
+    const dim3 grid((unsigned)(stages < cus ? stages : cus)), block(512);
+    const __bf16* px = (const __bf16*)x + (size_t)r0 * XK;
+    const __bf16* pr = residual_or_null ? (const __bf16*)residual_or_null + (size_t)r0 * n_out : nullptr;
+    __bf16* po = (__bf16*)out + (size_t)r0 * n_out;
+    auto launch = [&](auto epi, auto ln, auto gt_on) {
+      hipLaunchKernelGGL((xs_kernel<epi, ln, gt_on>), grid, block, 0, s, px, pw, bias_folded, pr, po, m, n_out, n_nb, stages,
+                         ln_eps, gt);
+      return vc::check_launch();
+    };
+    const int st = vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
+      return vc::dispatch<true, false>(fuse_layernorm != 0, [&](auto ln) {
+        if constexpr (epi == EPI_GELU) {   // only the GELU epilogue has a table variant
+          if (use_gt) return launch(epi, ln, std::true_type{});
+        }
+        return launch(epi, ln, std::false_type{});
+      });
     });
-  });
+    if (st != VC_OK) return st;
+  }
+  return VC_OK;
 }
 
 
@@ -1518,11 +1533,17 @@ int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded
   if (rows == 0) return VC_OK;
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
-  const int n_tiles = (rows + 127) / 128;
-  const dim3 grid((unsigned)(n_tiles < cus ? n_tiles : cus));
-  hipLaunchKernelGGL(mlp2_kernel, grid, dim3(512), 0, (hipStream_t)stream, (__bf16*)x_inout, (const uint8_t*)weights_tiled, b1_folded,
-                     b2, rows, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
-  return vc::check_launch();
+  // 32-bit buffer offsets in the result store, as in vc_linear_xs_bf16: launches of less than 2 GiB of rows each
+  const int chunk = max_rows_below_2gib(XK, 128);
+  for (long long r0 = 0; r0 < rows; r0 += chunk) {
+    const int m = (int)(rows - r0 < chunk ? rows - r0 : chunk);
+    const int n_tiles = (m + 127) / 128;
+    const dim3 grid((unsigned)(n_tiles < cus ? n_tiles : cus));
+    hipLaunchKernelGGL(mlp2_kernel, grid, dim3(512), 0, (hipStream_t)stream, (__bf16*)x_inout + (size_t)r0 * XK,
+                       (const uint8_t*)weights_tiled, b1_folded, b2, m, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
+    if (int st = vc::check_launch()) return st;
+  }
+  return VC_OK;
 }
 
 }  // extern "C"

@@ -138,7 +138,7 @@ class TrainableViTExtractor(BaseExtractor):
         """uint8 (B, h, w, 3) on the GPU -> (keypoints map (B, 4, H/4, W/4), descriptor map (B, D, H/4, W/4)) float32."""
         B, h, w, _ = images_bgr.shape
         hp, wp = h // PATCH, w // PATCH
-        layout = "patches_pad" if getattr(self.model.backbone, "_hip", None) else "patches"
+        layout = "patches_pad" if self.model.backbone.accepts_padded_patches else "patches"
         patches = hip_preprocess.preprocess(images_bgr, out_dtype=self.dtype, layout=layout)
         tokens = self.model.backbone.forward_patch_tokens(patches, hp, wp).contiguous()
         feats = ViTFeatureModel.tokens_to_grid(tokens, hp, wp)                 # channels-last view of the token grid

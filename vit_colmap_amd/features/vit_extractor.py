@@ -150,8 +150,9 @@ class ViTExtractor(BaseExtractor):
         """uint8 (B, h, w, 3) on the GPU -> patch tokens (B, Hp*Wp, C), Hp, Wp."""
         B, h, w, _ = images_bgr.shape
         hp, wp = h // PATCH, w // PATCH
-        if getattr(self.model, "_hip", None):
+        if self.model.accepts_padded_patches:
             # ViT-S / B / L bf16: every GEMM of the forward is hand-written (csrc/gemm.hip); no hipBLASLt, no TunableOp
+            # (the register variants take the unpadded layout below into the same hand-written block stack)
             patches = hip_preprocess.preprocess(images_bgr, out_dtype=self.dtype, layout="patches_pad")
             return self.model.forward_patch_tokens(patches, hp, wp).contiguous(), hp, wp
         patches = hip_preprocess.preprocess(images_bgr, out_dtype=self.dtype, layout="patches")
@@ -240,6 +241,9 @@ class ViTExtractor(BaseExtractor):
             self._shard_turn = 0
         cur = torch.cuda.current_stream(dev)
         side = self._shard_streams[1]
+        # the model's per-grid state (position embedding, class-token row) is built once, on the caller's stream, and read by
+        # every later call on any stream: the shards of every call start behind the event that marks its completion
+        grid_ready = self.model.prepare_grid(h // PATCH, w // PATCH, dev)
         if input_ready is None:               # shard 0 on the caller's stream, the others behind its present position
             streams = [cur] + side[1:n_sh]
             input_ready = torch.cuda.Event()
@@ -255,6 +259,7 @@ class ViTExtractor(BaseExtractor):
                 with torch.cuda.stream(s):
                     if s is not cur:
                         s.wait_event(input_ready)
+                        s.wait_event(grid_ready)
                     parts.append(self._extract_one(images_bgr[bounds[i]:bounds[i + 1]], hw))
         finally:
             self.model.batch_shards = inner

@@ -220,6 +220,44 @@ class DinoV2(nn.Module):
         self._pos_cache[key] = out
         return out
 
+    def _padded_pos(self, hp: int, wp: int, device):
+        """(position embedding as the patch-embedding GEMM wants it, class-token row cls + pos[0]): built once per grid."""
+        ckey = ("hip", hp, wp, torch.device(device))
+        cached = self._pos_cache.get(ckey)
+        if cached is None:
+            pos = self.interpolated_pos_embed(hp, wp).to(torch.bfloat16).contiguous()
+            cached = (pos, (self.cls_token[0, 0].float() + pos[0, 0].float()).to(torch.bfloat16))
+            self._pos_cache[ckey] = cached
+        return cached
+
+    @torch.no_grad()
+    def prepare_grid(self, hp: int, wp: int, device):
+        """Build the per-grid state `forward_patch_tokens` would otherwise build lazily (the interpolated position embedding;
+        for padded patches also the GEMM's copy and the class-token row) on the CURRENT stream, once.  -> the event recorded
+        behind that build (None on the CPU): the state is shared by every later call, so a stream other than the builder's
+        must wait for this event before its first read, in every call, not only the one that built it."""
+        device = torch.device(device)
+        key = ("ready", hp, wp, device)
+        ev = self._pos_cache.get(key)
+        if ev is None:
+            if self.accepts_padded_patches:
+                self._padded_pos(hp, wp, device)
+            elif self.pos_embed.device == device:
+                self.interpolated_pos_embed(hp, wp)
+            if device.type != "cuda":
+                return None
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(device))
+            self._pos_cache[key] = ev
+        return ev
+
+    @property
+    def accepts_padded_patches(self) -> bool:
+        """Whether `forward_patch_tokens` takes the padded layout ("patches_pad"): the bf16 GPU path on the hand-written
+        kernels, for models without register tokens (the patch-embedding GEMM writes rows 1.. of every image; registers would
+        sit between the class token and the patches).  Register models take the unpadded layout and the same block stack."""
+        return bool(getattr(self, "_hip", None)) and self.register_tokens is None and not self.training
+
     # -- forward ------------------------------------------------------------------------------------
     def forward_patch_tokens(self, patches: torch.Tensor, hp: int, wp: int) -> torch.Tensor:
         """patches (B, hp*wp, 588) -> x_norm_patchtokens (B, hp*wp, C)."""
@@ -235,13 +273,7 @@ class DinoV2(nn.Module):
                 raise ValueError("padded patches need prepare_hip() (ViT-S)")
             from . import hip_ops as ops
 
-            ckey = ("hip", hp, wp, patches.device)
-            cached = self._pos_cache.get(ckey)
-            if cached is None:      # position embedding as the kernel wants it + the class-token row (cls + pos[0]), once per grid
-                pos = self.interpolated_pos_embed(hp, wp).to(torch.bfloat16).contiguous()
-                cached = (pos, (self.cls_token[0, 0].float() + pos[0, 0].float()).to(torch.bfloat16))
-                self._pos_cache[ckey] = cached
-            pos, cls_row = cached
+            pos, cls_row = self._padded_pos(hp, wp, patches.device)
             x = torch.empty((B, 1 + hp * wp, self.arch.dim), dtype=torch.bfloat16, device=patches.device)
             ops.patch_embed(patches, self._pe_w, self.patch_embed.proj.bias, pos, x)
             x[:, 0] = cls_row
