@@ -372,6 +372,54 @@ int vc_mlp_prepare(const float* w1, const float* b1_or_null, const float* ln_gam
 int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded, const float* b2,
                 const void* gelu_table, int rows, int n_hidden, int dim, float ln_eps, vc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SIFT with COLMAP's default SiftExtractionOptions, computed as VLFeat's vl_sift does — replaces the
+ * pycolmap.extract_features call of the reference's ColmapSiftExtractor
+ * (vit_colmap/features/colmap_sift_extractor.py).  Specification: tests/util_sift.py; driven stage by
+ * stage by vit_colmap_amd/features/sift_extractor.py.  Batched over same-size images; the levels of one
+ * octave are level-major, levels [n_levels][n_images][h][w] float32, S = n_levels - 3 = n_dog_levels - 2.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_SIFT_MAX_RADIUS 64   /* Gaussian taps per side (taps = 2 radius + 1)                     */
+#define VC_SIFT_NORM_L2 0
+#define VC_SIFT_NORM_L1_ROOT 1
+
+/* images_bgr [n][h][w][3] uint8 -> grey [n][H][W] float32 in [0, 1]: uint8 grey = floor(0.2126 R + 0.7152 G +
+ * 0.0722 B + 0.5), bilinear (half-pixel centres) to out_h x out_w <= h x w when they differ, / 255; with upsample = 1,
+ * VLFeat's 2x linear upsampling on top (H = 2 out_h, W = 2 out_w), else H = out_h, W = out_w. */
+int vc_sift_grey(const uint8_t* images_bgr, int n_images, int h, int w, int out_h, int out_w, int upsample, float* out,
+                 vc_stream_t stream);
+/* dst = separable Gaussian of src ([n][h][w] each), rows then columns through tmp ([n][h][w]), edge replicate.
+ * taps [host] 2 radius + 1 float32 weights, 1 <= radius <= VC_SIFT_MAX_RADIUS. */
+int vc_sift_blur(const float* src, float* tmp, float* dst, int n_images, int h, int w, const float* taps, int radius,
+                 vc_stream_t stream);
+/* dst [n][h/2][w/2] = src [n][h][w] at even (y, x): the first level of the next octave. */
+int vc_sift_downsample(const float* src, int n_images, int h, int w, float* dst, vc_stream_t stream);
+/* dog [n_levels - 1][n][h][w] = levels[l + 1] - levels[l]. */
+int vc_sift_dog(const float* levels, int n_levels, int n_images, int h, int w, float* dog, vc_stream_t stream);
+/* Strict 26-neighbour extrema of DoG levels 1 .. S with |D| >= 0.8 peak_threshold, 1-pixel border excluded; with
+ * refine = 1 VLFeat's Newton refinement and acceptance (peak, edge ratio, offset, inside the octave), with refine = 0
+ * the raw extrema.  row_counts: workspace [n][S][h] int32.  out_keypoints [n][cap][8] float32 = x, y, s, sigma (octave
+ * units), j, y0, x0, 0 in (j, y0, x0) raster order of the unrefined extremum; out_count [n] = number found, which may
+ * exceed cap (only the first cap are written: call again with a larger cap). */
+int vc_sift_detect(const float* dog, int n_images, int h, int w, int n_dog_levels, float peak_threshold,
+                   float edge_threshold, int refine, int32_t* row_counts, int cap, float* out_keypoints,
+                   int32_t* out_count, vc_stream_t stream);
+/* 36-bin orientation histograms of keypoints [n][cap][8] (min(count, cap) per image) on their Gaussian level j:
+ * out_angles [n][cap][4] (peaks in bin order), out_n_angles [n][cap] = min(peaks, max_orientations) (1 and angle 0 when
+ * upright).  1 <= max_orientations <= 4. */
+int vc_sift_orient(const float* levels, int n_levels, int n_images, int h, int w, const float* keypoints,
+                   const int32_t* count, int cap, int max_orientations, int upright, float* out_angles,
+                   int32_t* out_n_angles, vc_stream_t stream);
+/* One row per (keypoint, orientation), in keypoint order: out_rows [n][row_cap][6] float32 = COLMAP's affine keypoint
+ * ((x 2^o + 0.5) scale_x, (y 2^o + 0.5) scale_y, s cos, -s sin, s sin, s cos with s = sigma 2^o; columns 0, 2, 3 times
+ * scale_x, 1, 4, 5 times scale_y), out_desc [n][row_cap][128] uint8 (VLFeat 4x4x8, L2 / clamp 0.2 / L2, optional
+ * L1_ROOT, min(255, round(512 v)), UBC bin order), out_row_count [n].  octave_scale = 2^o.  row_offsets: workspace
+ * [n][cap] int32.  row_cap >= cap * max_orientations (VC_ERR_WORKSPACE otherwise). */
+int vc_sift_describe(const float* levels, int n_levels, int n_images, int h, int w, const float* keypoints,
+                     const int32_t* count, int cap, const float* angles, const int32_t* n_angles, int max_orientations,
+                     int normalization, float octave_scale, float scale_x, float scale_y, int32_t* row_offsets,
+                     int row_cap, float* out_rows, uint8_t* out_desc, int32_t* out_row_count, vc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

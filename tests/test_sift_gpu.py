@@ -1,0 +1,209 @@
+"""The SIFT kernels (csrc/sift.hip) against their specification tests/util_sift.py, their determinism, the max_image_size
+path, a geometric check through the HIP matcher with no oracle involved, and the pipeline end to end."""
+import json
+import sqlite3
+
+import numpy as np
+import pytest
+import torch
+from scipy.spatial import cKDTree
+
+import util_sift as us
+from vit_colmap_amd.features import sift_extractor as se
+from vit_colmap_amd.features.sift_extractor import SiftExtractor, SiftOptions
+
+pytestmark = pytest.mark.gpu
+
+
+def textured(seed, h, w, sigma=2.0):
+    rs = np.random.RandomState(seed)
+    g = us.blur(rs.rand(h, w).astype(np.float32), us.gaussian_taps(sigma))
+    g = (g - g.min()) / (g.max() - g.min())
+    return np.repeat(np.round(255 * g).astype(np.uint8)[..., None], 3, 2)
+
+
+def colour(seed, h, w):
+    """Three independent textures: the grey conversion sees different R, G, B."""
+    return np.ascontiguousarray(np.stack([textured(seed + c, h, w)[..., 0] for c in range(3)], 2))
+
+
+def dev(imgs):
+    return torch.from_numpy(np.ascontiguousarray(np.stack(imgs))).cuda()
+
+
+def compare_rows(o_rows, o_desc, g_rows, g_desc):
+    """Oracle rows matched by position (1e-3 px), scale (1e-3 relative, i.e. the same octave and level) and angle
+    (1e-3 rad) -> (share of oracle rows matched, matched descriptor byte differences)."""
+    assert len(o_rows) > 0 and len(g_rows) > 0
+    tree = cKDTree(g_rows[:, :2].astype(np.float64))
+    o_s, g_s = np.hypot(o_rows[:, 2], o_rows[:, 4]), np.hypot(g_rows[:, 2], g_rows[:, 4])
+    o_t, g_t = np.arctan2(o_rows[:, 4], o_rows[:, 2]), np.arctan2(g_rows[:, 4], g_rows[:, 2])
+    diffs, hit = [], 0
+    for i, nb in enumerate(tree.query_ball_point(o_rows[:, :2].astype(np.float64), 1e-3)):
+        best = None
+        for k in nb:
+            dt = abs((g_t[k] - o_t[i] + np.pi) % (2 * np.pi) - np.pi)
+            if abs(g_s[k] - o_s[i]) <= 1e-3 * o_s[i] and dt <= 1e-3 and (best is None or dt < best[0]):
+                best = (dt, k)
+        if best is not None:
+            hit += 1
+            diffs.append(g_desc[best[1]].astype(np.int32) - o_desc[i].astype(np.int32))
+    return hit / len(o_rows), np.concatenate(diffs) if diffs else np.zeros(0, np.int32)
+
+
+@pytest.mark.parametrize("h,w", [(48, 64), (479, 641), (480, 640), (1200, 1600)])
+def test_kernels_match_oracle(h, w):
+    img = colour(11, h, w)
+    opts = SiftOptions()
+    S = opts.octave_resolution
+    batch = dev([img])
+    g = us.grey(img, opts.max_image_size)
+    o_pyr = us.pyramid(g, S, opts.first_octave, opts.num_octaves)
+    n_oct = 0
+    for (o, oc), (oo, lv, dog) in zip(se.pyramid_octaves(batch, opts), o_pyr):
+        n_oct += 1
+        assert o == oo
+        assert np.array_equal(oc.levels[:, 0].cpu().numpy(), lv), f"Gaussian levels differ (octave {o})"
+        assert np.array_equal(oc.dog[:, 0].cpu().numpy(), dog), f"DoG differs (octave {o})"
+        kp, _, n = se._detect(oc, S, opts, cap=4096, refine=False)
+        raw = kp[0, : int(n[0])].cpu().numpy()
+        exp = us._extrema(dog, S, us.prefilter_of(opts.peak_threshold))
+        assert np.array_equal(raw[:, 4:7].astype(np.int64), exp), f"unrefined extrema differ (octave {o})"
+        kp, _, n = se._detect(oc, S, opts, cap=4096)
+        ref = kp[0, : int(n[0])].cpu().numpy()
+        exp = us.detect(dog, S, opts.peak_threshold, opts.edge_threshold)
+        assert np.array_equal(ref[:, 4:7], exp[:, 4:7]), f"accepted keypoints differ (octave {o})"
+        assert np.abs(ref[:, :3] - exp[:, :3]).max(initial=0) <= 1e-5
+    assert n_oct == len(o_pyr)
+    res = se.extract_device(batch, opts)
+    m = int(res["count"][0])
+    g_rows, g_desc = res["keypoints"][0, :m].cpu().numpy(), res["descriptors"][0, :m].cpu().numpy()
+    o_rows, o_desc = us.extract(img, opts)
+    if len(o_rows) == 0:
+        assert m == 0
+        return
+    share, diffs = compare_rows(o_rows, o_desc, g_rows, g_desc)
+    assert share >= 0.995, share
+    assert (diffs == 0).mean() >= 0.99, (diffs == 0).mean()
+    assert np.abs(diffs).max() <= 1
+    assert abs(m - len(o_rows)) <= 0.005 * len(o_rows) + 1
+
+
+def test_batch_equals_single_calls_and_runs_repeat():
+    imgs = [colour(100 + i, 120, 160) for i in range(8)]
+    a = se.extract_device(dev(imgs))
+    b = se.extract_device(dev(imgs))
+    for k in ("keypoints", "descriptors", "count"):
+        assert torch.equal(a[k], b[k])
+    assert int(a["count"].min()) > 0
+    for i, im in enumerate(imgs):
+        s = se.extract_device(dev([im]))
+        n = int(s["count"][0])
+        assert n == int(a["count"][i])
+        assert torch.equal(s["keypoints"][0, :n], a["keypoints"][i, :n])
+        assert torch.equal(s["descriptors"][0, :n], a["descriptors"][i, :n])
+
+
+def test_max_image_size_path_returns_original_coordinates():
+    rs = np.random.RandomState(4)
+    small = rs.randint(0, 256, (375, 500, 3)).astype(np.uint8)
+    img = np.ascontiguousarray(np.repeat(np.repeat(small, 8, 0), 8, 1))          # 4000 x 3000
+    batch = dev([img])
+    g_gpu = se.grey(batch, 2400, 3200, False)[0].cpu().numpy()
+    assert np.array_equal(g_gpu, us.grey(img, 3200)), "resized grey image differs from the oracle"
+    res = se.extract_device(batch)                                           # the default options, octave -1 at 6400 x 4800
+    n = int(res["count"][0])
+    rows = res["keypoints"][0, :n].cpu().numpy()
+    assert 0 < n <= 8192 and rows[:, 0].max() <= 4000 and rows[:, 1].max() <= 3000 and rows[:, :2].min() >= 0
+    opts = SiftOptions(first_octave=0, num_octaves=2, max_num_features=100000)   # an oracle run of CPU-friendly size
+    res = se.extract_device(batch, opts)
+    n = int(res["count"][0])
+    o_rows, o_desc = us.extract_grey(g_gpu, opts, (4000 / 3200, 3000 / 2400))
+    share, diffs = compare_rows(o_rows, o_desc, res["keypoints"][0, :n].cpu().numpy(), res["descriptors"][0, :n].cpu().numpy())
+    assert share >= 0.995 and np.abs(diffs).max() <= 1
+
+
+def homography_warp(img, H, fill=128):
+    """Backward bilinear warp: out(p) = img(H^-1 p)."""
+    h, w = img.shape[:2]
+    Hi = np.linalg.inv(H)
+    ys, xs = np.mgrid[:h, :w].astype(np.float64)
+    p = Hi @ np.stack([xs.ravel() + 0.5, ys.ravel() + 0.5, np.ones(h * w)])
+    sx, sy = p[0] / p[2] - 0.5, p[1] / p[2] - 0.5
+    x0, y0 = np.floor(sx).astype(int), np.floor(sy).astype(int)
+    ax, ay = sx - x0, sy - y0
+    ok = (x0 >= 0) & (y0 >= 0) & (x0 < w - 1) & (y0 < h - 1)
+    x0c, y0c = np.clip(x0, 0, w - 2), np.clip(y0, 0, h - 2)
+    out = np.full((h * w, 3), fill, np.float64)
+    f = img.astype(np.float64)
+    v = (f[y0c, x0c] * ((1 - ax) * (1 - ay))[:, None] + f[y0c, x0c + 1] * (ax * (1 - ay))[:, None]
+         + f[y0c + 1, x0c] * ((1 - ax) * ay)[:, None] + f[y0c + 1, x0c + 1] * (ax * ay)[:, None])
+    out[ok] = v[ok]
+    return np.round(out).astype(np.uint8).reshape(h, w, 3)
+
+
+H_TRUE = np.array([[0.92, -0.16, 60.0], [0.14, 0.95, 10.0], [2e-5, 1e-5, 1.0]])
+
+
+def test_homography_matches_through_hip_matcher():
+    from vit_colmap_amd.matching.exhaustive import hip_match_blocks
+
+    img = colour(21, 480, 640)
+    warped = homography_warp(img, H_TRUE)
+    (k0, d0), (k1, d1) = SiftExtractor(device="cuda")._run_batch([img, warped])
+    n_max = max(len(d0), len(d1))
+    block = np.zeros((2, n_max, 128), np.uint8)
+    block[0, : len(d0)], block[1, : len(d1)] = d0, d1
+    m = hip_match_blocks(block, np.array([len(d0), len(d1)], np.int32), np.array([[0, 1]], np.int32))[0]
+    assert len(m) >= 100, len(m)
+    p = H_TRUE @ np.concatenate([k0[m[:, 0], :2].T.astype(np.float64), np.ones((1, len(m)))])
+    err = np.hypot(p[0] / p[2] - k1[m[:, 1], 0], p[1] / p[2] - k1[m[:, 1], 1])
+    assert (err <= 3.0).mean() >= 0.9, (err <= 3.0).mean()
+
+
+def write_scene(d):
+    from vit_colmap_amd.utils import image_io
+
+    d.mkdir(parents=True)
+    img = colour(31, 480, 640)
+    image_io.imwrite(d / "a.png", img)
+    image_io.imwrite(d / "b.png", homography_warp(img, H_TRUE))
+    image_io.imwrite(d / "c.png", homography_warp(img, np.array([[1.05, 0.05, -20.0], [-0.04, 1.02, 15.0], [0, 0, 1.0]])))
+
+
+def test_pipeline_end_to_end(tmp_path):
+    from vit_colmap_amd.pipeline import Pipeline
+    from vit_colmap_amd.utils import Config
+
+    write_scene(tmp_path / "images")
+    c = Config()
+    c.extractor.extractor_type = "sift"
+    c.do_reconstruction = False
+    db = tmp_path / "db" / "database.db"
+    Pipeline(c).run(tmp_path / "images", tmp_path / "out", db, "X", "Y", tmp_path / "results")
+    con = sqlite3.connect(str(db))
+    assert con.execute("SELECT COUNT(*) FROM cameras").fetchone()[0] == 3
+    assert con.execute("SELECT COUNT(*) FROM images").fetchone()[0] == 3
+    assert {r[0] for r in con.execute("SELECT cols FROM keypoints")} == {6}
+    assert {r[0] for r in con.execute("SELECT cols FROM descriptors")} == {128}
+    assert con.execute("SELECT COUNT(*) FROM matches WHERE rows > 0").fetchone()[0] >= 1
+    assert con.execute("SELECT COUNT(*) FROM two_view_geometries WHERE rows > 0").fetchone()[0] >= 1
+    cam = con.execute("SELECT params FROM cameras WHERE camera_id = 1").fetchone()[0]
+    assert np.allclose(np.frombuffer(cam, np.float64), [1.2 * 640, 320, 240])
+    con.close()
+    out = json.loads((tmp_path / "results" / "X" / "Y" / "sift.json").read_text())
+    assert out["extractor_type"] == "sift"
+
+
+def test_sharded_one_rank_equals_extract(tmp_path):
+    from vit_colmap_amd.database import ColmapDatabase
+    from vit_colmap_amd.pipeline.distributed import run_sharded
+
+    write_scene(tmp_path / "images")
+    ex = SiftExtractor(device="cuda")
+    ex.extract(tmp_path / "images", tmp_path / "a.db", "SIMPLE_PINHOLE")
+    run_sharded(tmp_path / "images", tmp_path / "b.db", "SIMPLE_PINHOLE", feature_fn=ex._run_batch, do_matching=False)
+    with ColmapDatabase.open_database(str(tmp_path / "a.db")) as a, ColmapDatabase.open_database(str(tmp_path / "b.db")) as b:
+        for i in (1, 2, 3):
+            assert np.array_equal(a.read_keypoints(i), b.read_keypoints(i))
+            assert np.array_equal(a.read_descriptors(i), b.read_descriptors(i))

@@ -73,6 +73,16 @@ SIGNATURES = {
     "vc_mlp_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "vc_preprocess_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p]),
+    "vc_sift_grey": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vc_sift_blur": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _f32p, c_int, c_void_p]),
+    "vc_sift_downsample": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vc_sift_dog": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vc_sift_detect": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p, c_int, c_void_p,
+                               c_void_p, c_void_p]),
+    "vc_sift_orient": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p]),
+    "vc_sift_describe": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                 c_int, c_float, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

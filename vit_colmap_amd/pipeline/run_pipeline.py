@@ -33,6 +33,11 @@ class Pipeline:
             raise NotImplementedError(
                 f"extractor_type={kind!r} is outside the accelerated hot path (SURVEY.md §2); "
                 "use the reference implementation for it")
+        if kind == "sift":                                    # COLMAP-default SIFT on the HIP kernels (csrc/sift.hip)
+            logger.info("Using SIFT extractor")
+            from ..features.sift_extractor import SiftExtractor
+
+            return SiftExtractor()
         if kind == "trainable_vit":                           # :326-333
             logger.info("Using Trainable ViT extractor")
             from ..features.trainable_vit_extractor import TrainableViTExtractor
@@ -137,7 +142,7 @@ def main() -> None:
     ap.add_argument("--output", type=Path, required=True)
     ap.add_argument("--db", type=Path, required=True)
     ap.add_argument("--camera-model", dest="camera_model", default="SIMPLE_PINHOLE")
-    ap.add_argument("--extractor", choices=["vit", "trainable_vit", "colmap_sift", "dummy"], default="vit")
+    ap.add_argument("--extractor", choices=["vit", "trainable_vit", "sift", "colmap_sift", "dummy"], default="vit")
     ap.add_argument("--vit-weights", dest="vit_weights", type=Path, default=None)
     ap.add_argument("--skip-matching", dest="skip_matching", action="store_true")
     ap.add_argument("--skip-reconstruction", dest="skip_reconstruction", action="store_true")
