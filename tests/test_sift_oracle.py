@@ -39,6 +39,27 @@ def test_gaussian_blob_gives_one_keypoint_at_its_centre(t):
     assert desc.shape == (len(rows), 128) and desc.dtype == np.uint8
 
 
+@pytest.mark.parametrize("S", [1, 2, 4, 8])
+def test_gaussian_blob_scale_for_every_octave_resolution(S):
+    sigma = {}
+    for t in (4, 8):
+        img, c = blob_image(24 * t + 48, t)
+        rows, _ = us.extract(img, SiftOptions(octave_resolution=S))
+        pos = np.unique(rows[:, :2], axis=0)
+        assert len(pos) == 1, rows
+        assert np.abs(pos[0] - (c + 0.5)).max() <= 0.05
+        s = np.hypot(rows[:, 2], rows[:, 4])
+        assert np.ptp(s) <= 1e-5 * s[0]
+        sigma[t] = float(s[0])
+        # the DoG between levels sigma and sigma 2^(1/S) peaks at sigma 2^(-1/2S) = t: within 3 % (1.1 % .. 2.4 % seen
+        # at S = 1, less for larger S); a sigma0 that ignores S is off by 2^(1/S - 1/3): 59 % at S = 1, 6 % at S = 4,
+        # 13 % at S = 8
+        assert abs(sigma[t] / (t * 2 ** (-1 / (2 * S))) - 1) <= 0.03, (t, sigma[t])
+    # doubling the blob doubles sigma: the image's own 0.5 px blur and sampling shift the ratio by about 0.3 % at
+    # t = 4 -> 8, so 1 % of 2 is a tight bound that still holds for every S
+    assert abs(sigma[8] / sigma[4] - 2) <= 0.02, sigma
+
+
 def test_flat_and_tiny_images_give_no_keypoints():
     for img in (np.full((120, 160, 3), 128, np.uint8), np.random.RandomState(1).randint(0, 256, (3, 2, 3), np.uint8)):
         rows, desc = us.extract(img, SiftOptions())

@@ -43,13 +43,13 @@ def resized_dims(w, h, max_image_size):
     return int(w * scale), int(h * scale)
 
 
-def grey(bgr, max_image_size=3200):
+def grey(bgr, max_image_size=3200, size=None):
     """uint8 BGR (h, w, 3) -> float32 grey in [0, 1] at the working size (bilinear, half-pixel centres, when larger
-    than max_image_size)."""
+    than max_image_size), or at size = (w, h) when given (as vc_sift_grey's out_w, out_h)."""
     b, g, r = (bgr[..., c].astype(F) for c in range(3))
     g8 = np.floor(F(0.2126) * r + F(0.7152) * g + F(0.0722) * b + F(0.5))
     h, w = g8.shape
-    nw, nh = resized_dims(w, h, max_image_size)
+    nw, nh = size if size is not None else resized_dims(w, h, max_image_size)
     if (nw, nh) != (w, h):
         def coef(n_out, n_in):
             f = ((np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5).astype(F)
@@ -259,8 +259,8 @@ def gradient(level):
     return mod, np.where(ang >= TWO_PI, F(0), ang).astype(F)
 
 
-def orientations(mod, ang, kp):
-    """VLFeat's 36-bin orientation histogram -> up to 4 angles, in bin order."""
+def orientations(mod, ang, kp, max_peaks=4):
+    """VLFeat's 36-bin orientation histogram -> up to max_peaks (VLFeat: 4) angles, in bin order."""
     h, w = mod.shape
     xk, yk, sigma = F(kp[0]), F(kp[1]), F(kp[3])
     xi, yi = int(np.floor(xk + F(0.5))), int(np.floor(yk + F(0.5)))
@@ -290,7 +290,7 @@ def orientations(mod, ang, kp):
         if h0 > F(0.8) * maxh and h0 > hm and h0 > hp:
             di = F(-0.5) * (hp - hm) / (hp + hm - F(2) * h0)
             angles.append(F(TWO_PI * (F(i) + di + F(0.5)) / F(36)))
-            if len(angles) == 4:
+            if len(angles) == max_peaks:
                 break
     return angles
 
