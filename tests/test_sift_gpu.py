@@ -202,8 +202,11 @@ def test_sharded_one_rank_equals_extract(tmp_path):
     write_scene(tmp_path / "images")
     ex = SiftExtractor(device="cuda")
     ex.extract(tmp_path / "images", tmp_path / "a.db", "SIMPLE_PINHOLE")
-    run_sharded(tmp_path / "images", tmp_path / "b.db", "SIMPLE_PINHOLE", feature_fn=ex._run_batch, do_matching=False)
+    run_sharded(tmp_path / "images", tmp_path / "b.db", "SIMPLE_PINHOLE", feature_fn=ex._run_batch, do_matching=False,
+                camera_params_for=ex.camera_params_for, camera_per_image=ex.camera_per_image)
     with ColmapDatabase.open_database(str(tmp_path / "a.db")) as a, ColmapDatabase.open_database(str(tmp_path / "b.db")) as b:
+        assert [vars(im) for im in a.read_all_images()] == [vars(im) for im in b.read_all_images()]
         for i in (1, 2, 3):
+            assert a.read_camera(i) == b.read_camera(i)
             assert np.array_equal(a.read_keypoints(i), b.read_keypoints(i))
             assert np.array_equal(a.read_descriptors(i), b.read_descriptors(i))

@@ -18,13 +18,16 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils import image_io
 from . import hip_select
-from .base_extractor import BaseExtractor, default_camera_params, list_images
+from .base_extractor import BaseExtractor, default_camera_params, extract_to_database
 from .vit_extractor import PATCH, ViTExtractor
 
 
 class HybridViTExtractor(BaseExtractor):
+    batch_size = 1                                             # per-image inference, as the reference
+    camera_params_for = staticmethod(default_camera_params)   # one camera, of the first image's size (extract_to_database)
+    camera_per_image = False
+
     def __init__(self, weights_path: Optional[str] = None, model_name: str = "dinov2_vitb14", num_keypoints: int = 2048,
                  descriptor_dim: int = 256, device: Optional[str] = None, detector_type: str = "sift", *,
                  keypoint_fn: Optional[Callable[[np.ndarray], np.ndarray]] = None, precision: str = "bf16",
@@ -112,40 +115,9 @@ class HybridViTExtractor(BaseExtractor):
             return keypoints, np.zeros((0, D), np.uint8)
         return keypoints, self.describe_batch([image_bgr], [keypoints])[0]
 
-    def extract(self, image_dir: Path, db_path: Path, camera_model: str, camera_params: Optional[list] = None) -> None:
-        """Same side effects as the reference's extract (hybrid_extractor.py:345-443): one camera, an image row per readable
-        image before inference, keypoints + descriptors per image."""
-        from ..database.colmap_db import Camera, ColmapDatabase
+    def _run_batch(self, images_bgr_np):
+        return [self._run_inference(img) for img in images_bgr_np]
 
-        image_files = list_images(Path(image_dir))
-        if not image_files:
-            raise ValueError(f"No images found in {image_dir}")
-        db = ColmapDatabase(str(db_path))
-        try:
-            first = image_io.imread(image_files[0])
-            if first is None:
-                raise ValueError(f"Failed to read first image: {image_files[0]}")
-            height, width = first.shape[:2]
-            if camera_params is None:
-                camera_params = default_camera_params(camera_model, width, height)
-            cam = db.db.write_camera(Camera(model=camera_model, width=width, height=height, params=camera_params))
-            for idx, f in enumerate(image_files):
-                img = first if idx == 0 else image_io.imread(f)
-                if img is None:
-                    print(f"{f.name}: ⚠ failed to read image, skipping")
-                    continue
-                image_id = db.add_image(f.name, camera_id=cam)
-                try:
-                    kp, desc = self._run_inference(img)
-                except _lib.HipLibraryError:
-                    raise
-                except Exception as e:  # noqa: BLE001 - one bad image never aborts the run
-                    print(f"  ✗ Error during feature extraction of {f.name}: {e}")
-                    continue
-                if len(kp) == 0:
-                    continue
-                db.add_keypoints(image_id, kp)
-                db.add_descriptors(image_id, desc)
-            db.commit()
-        finally:
-            db.db.close()
+    def extract(self, image_dir: Path, db_path: Path, camera_model: str, camera_params: Optional[list] = None) -> None:
+        """Same side effects as the reference's extract (hybrid_extractor.py:345-443): `extract_to_database`."""
+        extract_to_database(self, image_dir, db_path, camera_model, camera_params)

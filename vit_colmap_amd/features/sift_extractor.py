@@ -19,8 +19,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils import image_io
-from .base_extractor import BaseExtractor, list_images
+from .base_extractor import BaseExtractor, extract_to_database, host_rows
 
 SIGMA0_BASE = 1.6
 SIGMA_NOMINAL = 0.5
@@ -276,6 +275,8 @@ def select_rows(octave_rows, max_num_features):
 class SiftExtractor(BaseExtractor):
     """COLMAP-default SIFT on the GPU, written into a COLMAP database like the reference's ColmapSiftExtractor: one
     camera per image (CameraMode.AUTO); `camera_params` is ignored, as the reference wrapper ignores it."""
+    camera_params_for = staticmethod(camera_params_for)
+    camera_per_image = True
 
     def __init__(self, options: Optional[SiftOptions] = None, device: str | None = None, batch_size: int = 16):
         self.options = (options or SiftOptions()).validate()
@@ -304,9 +305,7 @@ class SiftExtractor(BaseExtractor):
         for s in range(0, len(images_bgr_np), g):
             batch = torch.from_numpy(np.ascontiguousarray(np.stack(images_bgr_np[s:s + g]))).to(self.device)
             res = extract_device(batch, self.options)
-            counts = res["count"].cpu().numpy()
-            kps, desc = res["keypoints"].cpu().numpy(), res["descriptors"].cpu().numpy()
-            out.extend((kps[i, : counts[i]].copy(), desc[i, : counts[i]].copy()) for i in range(len(counts)))
+            out.extend(host_rows(res["count"], res["keypoints"], res["descriptors"]))
         return out
 
     def _run_inference(self, image_bgr: np.ndarray):
@@ -315,59 +314,6 @@ class SiftExtractor(BaseExtractor):
 
     def extract(self, image_dir: Path, db_path: Path, camera_model: str,
                 camera_params: Optional[list[float]] = None) -> None:
-        from ..database.colmap_db import Camera, ColmapDatabase
-
         self._require_gpu()
-        image_dir, db_path = Path(image_dir), Path(db_path)
-        image_files = list_images(image_dir)
-        if not image_files:
-            raise ValueError(f"No images found in {image_dir}")
-        first = image_io.imread(image_files[0])
-        if first is None:
-            raise ValueError(f"Failed to read first image: {image_files[0]}")
-        camera_params_for(camera_model, 1, 1)            # ValueError for an unsupported model, before any row is written
-        print(f"SIFT extraction: {len(image_files)} images from {image_dir} into {db_path}")
-        db = ColmapDatabase(str(db_path))
-        pending = []                                     # (image_id, name, array) of equal size
-
-        def flush():
-            if not pending:
-                return
-            try:
-                results = self._run_batch([p[2] for p in pending])
-            except _lib.HipLibraryError:
-                raise
-            except Exception:  # noqa: BLE001 - isolate a failing image
-                results = []
-                for _, name, arr in pending:
-                    try:
-                        results.append(self._run_batch([arr])[0])
-                    except _lib.HipLibraryError:
-                        raise
-                    except Exception as e:  # noqa: BLE001
-                        print(f"  ✗ Error during feature extraction of {name}: {e}")
-                        results.append(None)
-            for (image_id, name, _), r in zip(pending, results):
-                if r is None:
-                    continue
-                kps, desc = r
-                print(f"  {name}: {len(kps)} keypoints")
-                if len(kps):
-                    db.add_keypoints(image_id, kps)
-                    db.add_descriptors(image_id, desc)
-            pending.clear()
-
-        for idx, path in enumerate(image_files):
-            img = first if idx == 0 else image_io.imread(path)
-            if img is None:
-                print(f"  {path.name}: ⚠ failed to read image, skipping")
-                continue
-            h, w = img.shape[:2]
-            cam = db.db.write_camera(Camera(model=camera_model, width=w, height=h,
-                                            params=camera_params_for(camera_model, w, h)))
-            image_id = db.add_image(path.name, camera_id=cam)
-            if pending and (pending[0][2].shape != img.shape or len(pending) >= self.batch_size):
-                flush()
-            pending.append((image_id, path.name, img))
-        flush()
-        db.commit()
+        print(f"SIFT extraction: {image_dir} into {db_path}")
+        extract_to_database(self, image_dir, db_path, camera_model, camera_params)

@@ -27,9 +27,8 @@ import torch
 
 from .. import _lib
 from ..model import ViTFeatureModel
-from ..utils import image_io
 from . import hip_preprocess, hip_select
-from .base_extractor import BaseExtractor, list_images
+from .base_extractor import IMAGE_EXTENSIONS, BaseExtractor, extract_to_database, host_rows
 
 PATCH = 14
 
@@ -49,6 +48,10 @@ def _default_camera_params(camera_model: str, width: int, height: int) -> list:
 
 
 class TrainableViTExtractor(BaseExtractor):
+    image_extensions = IMAGE_EXTENSIONS | {".ppm"}                # trainable_vit_extractor.py:300
+    camera_params_for = staticmethod(_default_camera_params)     # one camera, of the first image's size (extract_to_database)
+    camera_per_image = False
+
     def __init__(
         self,
         weights_path: Optional[str] = None,
@@ -161,10 +164,7 @@ class TrainableViTExtractor(BaseExtractor):
         self._require_gpu()
         batch = torch.from_numpy(np.ascontiguousarray(np.stack(images_bgr_np))).to(self.device, non_blocking=True)
         res = self.extract_device(batch)
-        counts = res["count"].cpu().numpy()
-        kps = res["keypoints"].cpu().numpy()
-        desc = res["desc_u8"].cpu().numpy()
-        return [(kps[i, : counts[i]].astype(np.float32).copy(), desc[i, : counts[i]].copy()) for i in range(len(images_bgr_np))]
+        return host_rows(res["count"], res["keypoints"], res["desc_u8"])
 
     def _run_inference(self, image_bgr: np.ndarray):
         """Single image (trainable_vit_extractor.py:139-269): keypoints (N, 6) float32, descriptors (N, D) uint8;
@@ -173,101 +173,10 @@ class TrainableViTExtractor(BaseExtractor):
 
     # ------------------------------------------------------------------------------------------
     def extract(self, image_dir: Path, db_path: Path, camera_model: str, camera_params: Optional[list[float]] = None):
-        """trainable_vit_extractor.py:271-392."""
-        from ..database.colmap_db import Camera, ColmapDatabase
-
-        image_dir, db_path = Path(image_dir), Path(db_path)
+        """trainable_vit_extractor.py:271-392 (files -> database: `extract_to_database`)."""
         print(f"\n{'='*60}\nTrainable ViT Feature Extraction\n{'='*60}")
         print(f"Image directory: {image_dir}\nDatabase: {db_path}\nModel: {self.model_name}")
         print(f"Target keypoints per image: {self.num_keypoints}\nScore threshold: {self.score_threshold}")
         print(f"NMS radius: {self.nms_radius}\n{'='*60}\n")
-        image_files = list_images(image_dir) + sorted(f for f in image_dir.iterdir() if f.suffix.lower() == ".ppm")  # :300
-        image_files = sorted(image_files)
-        if not image_files:
-            raise ValueError(f"No images found in {image_dir}")
-        print(f"Found {len(image_files)} images")
-        db = ColmapDatabase(str(db_path))
-        first_img = image_io.imread(image_files[0])
-        if first_img is None:
-            raise ValueError(f"Failed to read first image: {image_files[0]}")
-        height, width = first_img.shape[:2]
-        print(f"Image dimensions: {width}x{height}")
-        if camera_params is None:
-            camera_params = _default_camera_params(camera_model, width, height)
-        print(f"Camera model: {camera_model}\nCamera params: {camera_params}")
-        camera_id = db.db.write_camera(Camera(model=camera_model, width=width, height=height, params=camera_params))
-        print(f"Camera ID: {camera_id}\n")
-
-        pending = []  # (image_id, name, array): equal-size images, in file order
-
-        def flush():
-            if not pending:
-                return
-            try:
-                results = self._run_batch([p[2] for p in pending])
-            except _lib.HipLibraryError:
-                raise
-            except Exception:                          # isolate the failing image (:380-385)
-                results = []
-                for _, name, arr in pending:
-                    try:
-                        results.append(self._run_batch([arr])[0])
-                    except Exception as e:  # noqa: BLE001
-                        import traceback
-
-                        print(f"  Error during feature extraction of {name}: {e}")
-                        traceback.print_exc()
-                        results.append(None)
-            for (image_id, name, _), r in zip(pending, results):
-                if r is None:
-                    continue
-                keypoints, descriptors = r
-                print(f"  {name}: extracted {len(keypoints)} keypoints, descriptor shape {descriptors.shape}")
-                if len(keypoints) == 0:
-                    print("  Warning: No keypoints extracted")              # :371-373: nothing is written
-                    continue
-                scores = keypoints[:, 4]
-                print(f"  Score range: [{scores.min():.3f}, {scores.max():.3f}]")
-                db.add_keypoints(image_id, keypoints)
-                db.add_descriptors(image_id, descriptors)
-            pending.clear()
-
-        # files are decoded ahead of the loop by a thread pool (the reference's loop is serial: imread -> inference -> write,
-        # :340-390); results are consumed in file order, so image ids are those of the serial loop
-        import os
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
-
-        workers = max(1, min(16, len(os.sched_getaffinity(0)) - 1 if hasattr(os, "sched_getaffinity") else 4))
-        window = max(2 * self.batch_size, 2 * workers)
-        pool = ThreadPoolExecutor(max_workers=workers)
-        ahead = deque()
-        files_iter = iter(image_files[1:])
-
-        def refill():
-            while len(ahead) < window:
-                f = next(files_iter, None)
-                if f is None:
-                    return
-                ahead.append(pool.submit(image_io.imread, f))
-
-        try:
-            refill()
-            for idx, img_file in enumerate(image_files, start=1):
-                if idx == 1:
-                    img = first_img
-                else:
-                    img = ahead.popleft().result()
-                    refill()
-                if img is None:
-                    print(f"[{idx}/{len(image_files)}] {img_file.name}: Warning: Failed to read image, skipping")
-                    continue
-                image_id = db.add_image(img_file.name, camera_id=camera_id)      # before inference (:358)
-                if pending and (pending[0][2].shape != img.shape or len(pending) >= self.batch_size):
-                    flush()
-                pending.append((image_id, img_file.name, img))
-            flush()
-        finally:
-            pool.shutdown(wait=False, cancel_futures=True)
-        db.commit()
+        extract_to_database(self, image_dir, db_path, camera_model, camera_params)
         print(f"\n{'='*60}\nFeature extraction complete!\n{'='*60}\n")

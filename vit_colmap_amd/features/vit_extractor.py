@@ -31,12 +31,15 @@ from .. import _lib
 from ..utils import image_io
 from ..vit import build_dinov2, load_dinov2_weights
 from . import hip_preprocess, hip_select
-from .base_extractor import BaseExtractor, default_camera_params, list_images
+from .base_extractor import BaseExtractor, default_camera_params, extract_to_database, host_rows, list_images
 
 PATCH = 14
 
 
 class ViTExtractor(BaseExtractor):
+    camera_params_for = staticmethod(default_camera_params)   # one camera, of the first image's size (extract_to_database)
+    camera_per_image = False
+
     def __init__(
         self,
         weights_path: str | None = None,
@@ -289,11 +292,7 @@ class ViTExtractor(BaseExtractor):
         proj = self.descriptor_projection if tokens.shape[-1] > self.descriptor_dim else None
         res = hip_select.dense_to_sparse(tokens, hp, wp, (w, h), (w_new, h_new), self.num_keypoints,
                                          self.detection_method, proj)
-        counts = res["count"].cpu().numpy()
-        kps = res["keypoints"].cpu().numpy()
-        desc = res["desc_u8"].cpu().numpy()
-        return [(kps[i, : counts[i]].astype(np.float32).copy(), desc[i, : counts[i]].copy())
-                for i in range(len(images_bgr_np))]
+        return host_rows(res["count"], res["keypoints"], res["desc_u8"])
 
     # ---- asynchronous form of _run_batch: what extract() pipelines --------------------------------------------
     def _staging(self, slot, shape):
@@ -331,15 +330,14 @@ class ViTExtractor(BaseExtractor):
                 out[k] = dst
             done = torch.cuda.Event()
             done.record(self._io_stream)
-        return dict(n=n, out=out, done=done, keep=(batch, res))   # (device tensors stay referenced until the event)
+        return dict(out=out, done=done, keep=(batch, res))   # (device tensors stay referenced until the event)
 
     def _finish_batch(self, handle):
         """Wait for a launched batch -> list of (keypoints (N, 2) float32, descriptors (N, D) uint8)."""
         handle["done"].synchronize()
-        counts = handle["out"]["count"].numpy()
-        kps, desc = handle["out"]["keypoints"].numpy(), handle["out"]["desc_u8"].numpy()
         handle["keep"] = None
-        return [(kps[i, : counts[i]].astype(np.float32).copy(), desc[i, : counts[i]].copy()) for i in range(handle["n"])]
+        out = handle["out"]
+        return host_rows(out["count"], out["keypoints"], out["desc_u8"])
 
     def _run_inference(self, image_bgr: np.ndarray):
         """Single image (vit_extractor.py:106-166): keypoints (N, 2) float32 (x, y) in original-image
@@ -354,143 +352,12 @@ class ViTExtractor(BaseExtractor):
         camera_model: str,
         camera_params: Optional[list[float]] = None,
     ):
-        """vit_extractor.py:655-768."""
-        import time
-
-        from ..database.colmap_db import Camera, ColmapDatabase
-
-        image_dir, db_path = Path(image_dir), Path(db_path)
+        """vit_extractor.py:655-768.  The reference's loop is serial: imread -> inference -> two database writes per image,
+        the GPU idle during the host work (:729-755).  Here (`extract_to_database`) files are decoded ahead by a thread
+        pool, a batch is uploaded from pinned staging and runs on its own stream without a host wait (`_launch_batch`),
+        and the rows of batch k-1 are written while batch k runs (`_finish_batch`)."""
         print(f"\n{'='*60}\nViT Feature Extraction\n{'='*60}")
         print(f"Image directory: {image_dir}\nDatabase: {db_path}\nModel: {self.model_name}")
         print(f"Target keypoints per image: {self.num_keypoints}\n{'='*60}\n")
-
-        image_files = list_images(image_dir)
-        if not image_files:
-            raise ValueError(f"No images found in {image_dir}")
-        print(f"Found {len(image_files)} images")
-
-        db = ColmapDatabase(str(db_path))
-        first_img = image_io.imread(image_files[0])
-        if first_img is None:
-            raise ValueError(f"Failed to read first image: {image_files[0]}")
-        height, width = first_img.shape[:2]
-        print(f"Image dimensions: {width}x{height}")
-        if camera_params is None:
-            camera_params = default_camera_params(camera_model, width, height)  # ValueError if unsupported
-        print(f"Camera model: {camera_model}\nCamera params: {camera_params}")
-        camera_id = db.db.write_camera(Camera(model=camera_model, width=width, height=height, params=camera_params))
-        print(f"Camera ID: {camera_id}\n")
-
-        # ---- batches of equal-size images, in file order, three overlapped stages -----------------------------------
-        # The reference's loop is serial: imread -> inference -> two DB writes per image, the GPU idle during the host
-        # work (vit_extractor.py:729-755).  Here (VERDICT r02 #9):
-        #   * files are decoded by a small thread pool running ahead of the loop (PIL / OpenCV release the GIL), results
-        #     consumed in file order so image ids stay those of the serial loop;
-        #   * a batch is uploaded from a pinned staging buffer and runs on its own stream without a host wait; its
-        #     keypoints / descriptors come back by asynchronous copies into pinned buffers behind an event;
-        #   * the rows of batch k-1 are written while batch k runs (two staging buffers, one batch in flight).
-        # `add_image` still precedes inference, and a failing batch is re-run image by image so that one bad image never
-        # takes its neighbours with it (vit_extractor.py:739-762).
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
-
-        pending = []      # (image_id, name, array): the batch being collected
-        in_flight = []    # at most one launched batch: (items, handle)
-
-        def write_rows(items, results):
-            t1 = time.perf_counter()
-            for (image_id, name, _), r in zip(items, results):
-                if r is None:
-                    continue
-                keypoints, descriptors = r
-                print(f"  {name}: {len(keypoints)} keypoints, descriptors {descriptors.shape}")
-                if len(keypoints) == 0:
-                    print("  ⚠ Warning: No keypoints extracted")
-                    continue
-                db.add_keypoints(image_id, keypoints)
-                db.add_descriptors(image_id, descriptors)
-            self.timings["db_s"] += time.perf_counter() - t1
-            self.timings["images"] += len(items)
-
-        def one_by_one(items):                 # isolate the failing image (vit_extractor.py:757-762)
-            results = []
-            for _, name, arr in items:
-                try:
-                    results.append(self._run_batch([arr])[0])
-                except _lib.HipLibraryError:
-                    raise
-                except Exception as e:  # noqa: BLE001
-                    import traceback
-
-                    print(f"  ✗ Error during feature extraction of {name}: {e}")
-                    traceback.print_exc()
-                    results.append(None)
-            return results
-
-        def finish():
-            if not in_flight:
-                return
-            items, handle = in_flight.pop()
-            t0 = time.perf_counter()
-            try:
-                results = self._finish_batch(handle)
-            except _lib.HipLibraryError:
-                raise
-            except Exception:  # noqa: BLE001
-                results = one_by_one(items)
-            self.timings["gpu_s"] += time.perf_counter() - t0      # host time spent WAITING for the GPU
-            write_rows(items, results)
-
-        def flush():
-            if not pending:
-                return
-            items = list(pending)
-            pending.clear()
-            t0 = time.perf_counter()
-            try:
-                handle = self._launch_batch([p[2] for p in items])   # returns without waiting for the GPU
-            except _lib.HipLibraryError:
-                raise                          # a missing GPU / library is not a per-image problem
-            except Exception:  # noqa: BLE001
-                finish()
-                self.timings["gpu_s"] += time.perf_counter() - t0
-                write_rows(items, one_by_one(items))
-                return
-            self.timings["gpu_s"] += time.perf_counter() - t0
-            finish()                           # the PREVIOUS batch: its rows are written while this one runs
-            in_flight.append((items, handle))
-
-        def decode(path):
-            t0 = time.perf_counter()
-            img = image_io.imread(path)
-            return img, time.perf_counter() - t0
-
-        n_files = len(image_files)
-        workers = max(1, min(16, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 2)) - 1))
-        ahead = 2 * self.batch_size
-        with ThreadPoolExecutor(workers) as pool:
-            futures = deque()
-            nxt = 1                            # index (0-based) of the next file to hand to the pool; file 0 is decoded
-            while nxt < n_files and len(futures) < ahead:
-                futures.append(pool.submit(decode, image_files[nxt]))
-                nxt += 1
-            for idx, img_file in enumerate(image_files, start=1):
-                if idx == 1:
-                    img = first_img
-                else:
-                    img, dt = futures.popleft().result()
-                    self.timings["decode_s"] += dt
-                    if nxt < n_files:
-                        futures.append(pool.submit(decode, image_files[nxt]))
-                        nxt += 1
-                if img is None:
-                    print(f"[{idx}/{n_files}] {img_file.name}: ⚠ failed to read image, skipping")
-                    continue
-                image_id = db.add_image(img_file.name, camera_id=camera_id)  # before inference (:739)
-                if pending and (pending[0][2].shape != img.shape or len(pending) >= self.batch_size):
-                    flush()
-                pending.append((image_id, img_file.name, img))
-            flush()
-            finish()
-        db.commit()
+        extract_to_database(self, image_dir, db_path, camera_model, camera_params)
         print(f"\n{'='*60}\n✓ Feature extraction complete!\n{'='*60}\n")

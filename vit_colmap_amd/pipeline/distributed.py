@@ -2,10 +2,12 @@
 torch.distributed process group with more than one rank exists (one process per GPU, backend "nccl" = RCCL).
 
   1. every rank lists the images (sorted, as the reference does) and takes a contiguous block of them;
-  2. rank 0 — the only process that ever touches the SQLite file — writes the camera and ONE image row per readable
-     image before any inference (reference vit_extractor.py:739: a failed image still has its row);
-  3. every rank extracts its block on its own GPU; the per-image uint8 descriptor blocks, padded to a common
-     (n_max, D), are ALL-GATHERED (the one collective of the data path, RCCL over xGMI), keypoints with them;
+  2. every rank decodes and extracts its block on its own GPU, in batches of equal-size images
+     (features/base_extractor.py `image_batches`); the per-image uint8 descriptor blocks, padded to a common (n_max, D),
+     are ALL-GATHERED (the one collective of the data path, RCCL over xGMI), keypoints and image sizes with them;
+  3. rank 0 — the only process that ever touches the SQLite file — writes the camera rows by the extractor's camera
+     policy (`camera_params_for`, `camera_per_image`: `base_extractor.camera_policy`, as its `extract()` does) and ONE
+     image row per readable image, in file order (reference vit_extractor.py:739: a failed image still has its row);
   4. rank 0 writes keypoints / descriptors; the exhaustive pair list is dealt round-robin, every rank matches
      and geometrically verifies its share from the gathered blocks and keypoints (no database read); the match lists
      and two-view geometries are gathered to rank 0, which writes them in pair order.
@@ -26,15 +28,15 @@ import numpy as np
 import torch
 
 from .. import dist as vd
-from ..features.base_extractor import default_camera_params, list_images
-from ..utils import image_io
+from ..features.base_extractor import add_image_row, camera_policy, default_camera_params, image_batches, list_images
 
 logger = logging.getLogger(__name__)
 
 
 def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn=None, matching_options=None,
-                match_fn=None, do_matching=True, verify=True, device="cuda", batch_size=50, verify_fn=None) -> dict:
-    from ..database.colmap_db import Camera, ColmapDatabase
+                match_fn=None, do_matching=True, verify=True, device="cuda", batch_size=50, verify_fn=None,
+                camera_params_for=default_camera_params, camera_per_image=False) -> dict:
+    from ..database.colmap_db import ColmapDatabase
     from ..matching.exhaustive import _sift_options, hip_match_blocks
 
     rank, world = vd.rank_world()
@@ -47,29 +49,12 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
     cdev = vd.comm_device(device)
 
     # ---- this rank's block ------------------------------------------------------------------------------------------
-    readable = np.zeros(per, np.int32)
+    hw = np.zeros((per, 2), np.int32)                     # (height, width) of each image, (0, 0) for an unreadable one
     feats = [None] * per
-    first_shape = np.zeros(2, np.int64)
-    pending = []
-
-    def flush():
-        if pending:
-            for (k, _), r in zip(pending, feature_fn([img for _, img in pending])):
-                feats[k] = r
-            pending.clear()
-
-    for k, f in enumerate(image_files[lo:hi]):
-        img = image_io.imread(f)
-        if img is None:
-            print(f"{f.name}: ⚠ failed to read image, skipping")
-            continue
-        readable[k] = 1
-        if lo + k == 0:
-            first_shape[:] = img.shape[:2]
-        if pending and (pending[0][1].shape != img.shape or len(pending) >= batch_size):
-            flush()
-        pending.append((k, img))
-    flush()
+    for batch in image_batches(image_files[lo:hi], batch_size):
+        for (k, _, img), r in zip(batch, feature_fn([img for _, _, img in batch])):
+            hw[k] = img.shape[:2]
+            feats[k] = r
     kdim = max([f[0].shape[1] for f in feats if f is not None] + [2])
     n_max, D, kdim = vd.max_over_ranks(max([len(f[0]) for f in feats if f is not None] + [1]),
                                        max([f[1].shape[1] for f in feats if f is not None] + [1]), kdim)
@@ -82,15 +67,15 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
             kps[k, : counts[k]] = f[0]
             desc[k, : counts[k]] = f[1]
 
-    # ---- the collective: descriptor blocks (+ counts, keypoints, readability) of every rank ------------------------------
+    # ---- the collective: descriptor blocks (+ counts, keypoints, image sizes) of every rank -------------------------------
     all_desc, all_counts = vd.all_gather_descriptors(torch.from_numpy(desc).to(cdev), torch.from_numpy(counts).to(cdev))
     all_kps = vd.all_gather_rows(torch.from_numpy(kps).to(cdev))
-    all_readable = vd.all_gather_rows(torch.from_numpy(readable).to(cdev)).cpu().numpy()[:n]
-    shape0 = vd.broadcast_array(first_shape, 0, device)
+    all_hw = vd.all_gather_rows(torch.from_numpy(hw).to(cdev)).cpu().numpy()[:n].tolist()
+    all_readable = np.array([h > 0 for h, _ in all_hw])
     if not all_readable[0]:
         raise ValueError(f"Failed to read first image: {image_files[0]}")
 
-    # ---- rank 0: image rows in file order, then features ----------------------------------------------------------------
+    # ---- rank 0: camera and image rows in file order, then features ------------------------------------------------------
     stats = dict(images=int(all_readable.sum()), ranks=world, pairs=0, matches=0, verified_pairs=0)
     ids = None
     db = None
@@ -99,12 +84,9 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
     kp_np = all_kps.cpu().numpy()
     if rank == 0:
         try:
+            camera_of = camera_policy(camera_model, camera_params, all_hw[0], camera_params_for, camera_per_image)
             db = ColmapDatabase(str(db_path))
-            height, width = int(shape0[0]), int(shape0[1])
-            if camera_params is None:
-                camera_params = default_camera_params(camera_model, width, height)
-            cam = db.db.write_camera(Camera(model=camera_model, width=width, height=height, params=camera_params))
-            ids = [db.add_image(f.name, camera_id=cam) if all_readable[k] else None for k, f in enumerate(image_files)]
+            ids = [add_image_row(db, f.name, camera_of(h, w)) if h else None for f, (h, w) in zip(image_files, all_hw)]
             d_np = all_desc.cpu().numpy()
             for k, image_id in enumerate(ids):
                 if image_id is not None and cnt[k] > 0:

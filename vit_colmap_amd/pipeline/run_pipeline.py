@@ -70,6 +70,8 @@ class Pipeline:
             if hasattr(extractor, "sync_projection"):
                 extractor.sync_projection(image_dir)      # the PCA / random projection is fitted once, on rank 0
             self.last_stats = run_sharded(image_dir, db_path, camera_model, camera_params, feature_fn=extractor._run_batch,
+                                          camera_params_for=extractor.camera_params_for,
+                                          camera_per_image=extractor.camera_per_image,
                                           matching_options=self.config.matching.to_matching_options(),
                                           do_matching=self.config.do_matching, device=str(getattr(extractor, "device", "cuda")))
             if vd.rank_world()[0] != 0:
