@@ -420,6 +420,44 @@ int vc_sift_describe(const float* levels, int n_levels, int n_images, int h, int
                      int normalization, float octave_scale, float scale_x, float scale_y, int32_t* row_offsets,
                      int row_cap, float* out_rows, uint8_t* out_desc, int32_t* out_row_count, vc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Classical detectors of the hybrid extractor — replace the OpenCV calls of the reference's
+ * vit_colmap/features/hybrid_extractor.py:110-180 (cv2.FastFeatureDetector, cv2.goodFeaturesToTrack).
+ * Specification: tests/util_detect.py, a numpy restatement of OpenCV's algorithms (parity with OpenCV
+ * itself is unpinned).  Batched over same-size images; both convert to 8-bit grey with
+ * OpenCV's fixed-point BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14, and equal the specification exactly.
+ * Images under VC_DETECT_MIN_SIZE pixels in either dimension: VC_ERR_UNSUPPORTED.  Workspaces must be 16-byte
+ * aligned; the *_workspace_bytes queries return 0 for sizes the entries refuse.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_DETECT_MIN_SIZE 8
+#define VC_DETECT_GFTT_MAX_CANDIDATES 16384 /* candidates per image the selection kernel ranks in LDS */
+
+size_t vc_detect_fast_workspace_bytes(int n_images, int h, int w);
+/* FAST-9/16 with non-maximum suppression.  images_bgr [n][h][w][3] uint8.  Score of a pixel p, integer: S = max over
+ * the 16 arcs of 9 contiguous pixels c_k of the radius-3 circle of max(min_k(c_k - p), min_k(p - c_k)); S <= threshold
+ * (0 .. 254) counts as 0, and so does every pixel closer than 3 to the edge.  A corner is kept iff S is strictly
+ * greater than S of its 8 neighbours.  If more than max_keypoints are kept, those with the largest S stay, the
+ * earlier raster position first among equal S (a 256-bin histogram per image finds the cut).  out_xy
+ * [n][max_keypoints][2] float32 (x, y) in raster order, rows past the count zero; out_count [n] = rows written,
+ * out_total [n] = corners before the limit. */
+int vc_detect_fast(const uint8_t* images_bgr, int n_images, int h, int w, int threshold, int max_keypoints, void* workspace,
+                   size_t workspace_bytes, float* out_xy, int32_t* out_count, int32_t* out_total, vc_stream_t stream);
+
+size_t vc_detect_gftt_workspace_bytes(int n_images, int h, int w, int cand_cap);
+/* Shi-Tomasi corners.  gx, gy = 3x3 Sobel of the grey image (reflect-101), int32; a, b, c = sums of gx^2, gx gy, gy^2
+ * over the block_size x block_size window (3, 5 or 7; product images extended by reflect-101), int32; lambda =
+ * (0.5 a + 0.5 c) - sqrt((0.5 a - 0.5 c)^2 + b^2) in float32, in this order, no fused multiply-add.  lambda <
+ * quality_level * max(lambda) (float32 product, max over the image) counts as 0.  Candidates: lambda != 0 and equal to
+ * the maximum of its 3x3 neighbourhood, outermost rows and columns excluded; none if max(lambda) <= 0.  Ranked by
+ * lambda descending, the LATER raster position first among equals; a candidate is accepted iff no accepted candidate of
+ * higher rank lies at squared distance < min_distance^2 (1 .. 64); the first max_corners accepted are written.
+ * out_xy [n][max_corners][2] float32 (x, y) in acceptance order, rows past the count zero; out_count [n];
+ * out_candidates [n] = candidates found, which may exceed cand_cap (<= VC_DETECT_GFTT_MAX_CANDIDATES): then out_count
+ * is 0 for that image and the call must be repeated with a larger cand_cap. */
+int vc_detect_gftt(const uint8_t* images_bgr, int n_images, int h, int w, float quality_level, int min_distance,
+                   int block_size, int max_corners, int cand_cap, void* workspace, size_t workspace_bytes, float* out_xy,
+                   int32_t* out_count, int32_t* out_candidates, vc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

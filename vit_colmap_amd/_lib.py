@@ -83,6 +83,12 @@ SIGNATURES = {
                                c_void_p, c_void_p]),
     "vc_sift_describe": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                  c_int, c_float, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_detect_fast_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vc_detect_fast": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "vc_detect_gftt_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "vc_detect_gftt": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

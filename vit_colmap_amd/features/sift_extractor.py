@@ -242,23 +242,60 @@ def extract_device(images_bgr: torch.Tensor, opts: Optional[SiftOptions] = None)
                                         _lib.ptr(angles), _lib.ptr(n_angles), n_ori, NORMALIZATIONS[opts.normalization],
                                         float(2.0 ** o), float(sx), float(sy), _lib.ptr(offs), rcap, _lib.ptr(rows),
                                         _lib.ptr(desc), _lib.ptr(rcount), _lib.stream_ptr()), "vc_sift_describe")
-        per_octave.append((rows, desc, rcount))
-    K = opts.max_num_features
-    out_kp = torch.zeros((B, K, 6), dtype=torch.float32, device=dev)
-    out_desc = torch.zeros((B, K, 128), dtype=torch.uint8, device=dev)
+        per_octave.append(((rows, desc), rcount))
+    rc = torch.stack([r for _, r in per_octave]).cpu().numpy() if per_octave else None      # (octaves, B)
+    (out_kp, out_desc), count = _gather_octaves([t for t, _ in per_octave], rc, opts.max_num_features, B, dev,
+                                                ((6, torch.float32), (128, torch.uint8)))
+    return dict(keypoints=out_kp, descriptors=out_desc, count=count)
+
+
+def _gather_octaves(per_octave, row_counts, K, B, dev, columns):
+    """Per-octave padded tensors (finest octave first; per_octave[i][j] is (B, cap_i, columns[j][0])) and their host row
+    counts (octaves, B) -> one zero-padded (B, K, width) tensor per column and count (B,) int32 on the device, the rows
+    of each image chosen by `select_rows`."""
+    outs = [torch.zeros((B, K, width), dtype=dtype, device=dev) for width, dtype in columns]
     counts = np.zeros(B, np.int32)
     if per_octave:
-        rc = torch.stack([r for _, _, r in per_octave]).cpu().numpy()      # (octaves, B)
         for b in range(B):
-            keep = select_rows(rc[:, b].tolist(), K)
+            keep = select_rows(row_counts[:, b].tolist(), K)
             at = 0
-            for (rows, desc, _), k in zip(per_octave, keep):
+            for tensors, k in zip(per_octave, keep):
                 if k:
-                    out_kp[b, at:at + k] = rows[b, :k]
-                    out_desc[b, at:at + k] = desc[b, :k]
+                    for out, t in zip(outs, tensors):
+                        out[b, at:at + k] = t[b, :k]
                     at += k
             counts[b] = at
-    return dict(keypoints=out_kp, descriptors=out_desc, count=torch.from_numpy(counts).to(dev))
+    return outs, torch.from_numpy(counts).to(dev)
+
+
+def detect_device(images_bgr: torch.Tensor, max_num_features: int):
+    """SIFT as a detector only: uint8 BGR (B, h, w, 3) on the GPU -> (xy float32 (B, max_num_features, 2) in
+    original-image pixels, rows past the count zero; count (B,) int32).  The points are columns 0 and 1 of the rows
+    `extract_device(images_bgr, SiftOptions(max_num_features=max_num_features, upright=True))` returns, bit for bit:
+    the same pyramid, extremum kernels and `select_rows`, the position (x 2^o + 0.5) scale_x in the three float32
+    operations of the descriptor kernel; the orientation and descriptor kernels are not run.
+
+    Known deviation from the reference's `cv2.SIFT_create(nfeatures=N)`: OpenCV keeps the N strongest responses, this
+    keeps whole octaves from the coarsest down (COLMAP's rule, the one csrc/sift.hip implements)."""
+    opts = SiftOptions(max_num_features=int(max_num_features), upright=True).validate()
+    if not images_bgr.is_cuda:
+        raise _lib.HipLibraryError("images must live on the GPU (the SIFT path is HIP-only, no CPU fallback)")
+    assert images_bgr.dtype == torch.uint8 and images_bgr.dim() == 4 and images_bgr.shape[3] == 3
+    images_bgr = images_bgr.contiguous()
+    B, h, w, _ = images_bgr.shape
+    dev = images_bgr.device
+    ww, wh = working_size(w, h, opts.max_image_size)
+    scale = torch.tensor([w / ww, h / wh], dtype=torch.float32, device=dev)
+    per_octave, row_counts = [], []
+    for o, oc in pyramid_octaves(images_bgr, opts):
+        hh, w_o = oc.levels.shape[2:]
+        kp, _, n = _detect(oc, opts.octave_resolution, opts, cap=max(1024, hh * w_o // 64))
+        xy = kp[:, :max(int(n.max()), 1), :2]
+        per_octave.append((((xy * float(2.0 ** o)) + 0.5) * scale,))
+        row_counts.append(n.numpy())
+    (out_xy,), count = _gather_octaves(per_octave, np.stack(row_counts) if row_counts else None, opts.max_num_features, B,
+                                       dev, ((2, torch.float32),))
+    return out_xy, count
 
 
 def select_rows(octave_rows, max_num_features):

@@ -44,6 +44,12 @@ class Pipeline:
 
             return TrainableViTExtractor(weights_path=self.config.extractor.vit_weights_path, num_keypoints=20480,
                                          nms_radius=1, score_threshold=0.4)
+        if kind == "hybrid":                                  # classical keypoints + ViT descriptors, detection on the device
+            logger.info("Using Hybrid extractor (%s keypoints)", self.config.extractor.detector_type)
+            from ..features.hybrid_extractor import HybridViTExtractor
+
+            return HybridViTExtractor(weights_path=self.config.extractor.vit_weights_path,
+                                      detector_type=self.config.extractor.detector_type, detector_backend="hip")
         logger.info("Using ViT extractor")                     # :335-339 (any other value -> ViT)
         from ..features.vit_extractor import ViTExtractor
 
@@ -144,7 +150,9 @@ def main() -> None:
     ap.add_argument("--output", type=Path, required=True)
     ap.add_argument("--db", type=Path, required=True)
     ap.add_argument("--camera-model", dest="camera_model", default="SIMPLE_PINHOLE")
-    ap.add_argument("--extractor", choices=["vit", "trainable_vit", "sift", "colmap_sift", "dummy"], default="vit")
+    ap.add_argument("--extractor", choices=["vit", "trainable_vit", "hybrid", "sift", "colmap_sift", "dummy"], default="vit")
+    ap.add_argument("--detector", choices=["sift", "fast", "gftt"], default="sift",
+                    help="keypoint detector of --extractor hybrid (runs on the GPU)")
     ap.add_argument("--vit-weights", dest="vit_weights", type=Path, default=None)
     ap.add_argument("--skip-matching", dest="skip_matching", action="store_true")
     ap.add_argument("--skip-reconstruction", dest="skip_reconstruction", action="store_true")

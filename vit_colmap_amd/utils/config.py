@@ -107,6 +107,7 @@ class ExtractorConfig:
 
     extractor_type: str = "vit"  # "vit" or "colmap_sift"
     vit_weights_path: Optional[str] = None
+    detector_type: str = "sift"  # keypoint detector of extractor_type "hybrid": "sift", "fast" or "gftt"
 
 
 @dataclass
@@ -137,6 +138,8 @@ class Config:
             config.extractor.vit_weights_path = str(args.vit_weights)
         elif hasattr(args, "model") and args.model:
             config.extractor.vit_weights_path = str(args.model)
+        if hasattr(args, "detector") and args.detector:
+            config.extractor.detector_type = args.detector
         if hasattr(args, "use_gpu"):
             config.matching.use_gpu = args.use_gpu
         if hasattr(args, "skip_matching"):
