@@ -277,15 +277,28 @@ int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int
  * The pre-activation is NOT rounded to bf16 before GELU / the residual add (one rounding less than
  * the unfused sequence).  n_out % 128 == 0, k_in % 64 == 0, pointers 16-byte aligned,
  * residual_or_null non-NULL exactly for VC_EPI_RESIDUAL.
+ *           VC_EPI_SWIGLU   the gated activation of DINOv2's SwiGLU FFN (mlp.w12 of the ViT-g models) fused into the
+ *                           product.  weight [n_out][k_in] and bias [n_out] exactly as mlp.w12 stores them: with
+ *                           H = n_out / 2, rows 0 .. H-1 produce the gate a, rows H .. 2H-1 the value b,
+ *                             a[m][j] = x[m] W[j]^T + bias[j],   b[m][j] = x[m] W[H + j]^T + bias[H + j],
+ *                           and out is [rows][H], HALF as wide as the product:
+ *                             out[m][j] = silu(a[m][j]) * b[m][j],   silu(a) = a / (1 + exp(-a)).
+ *                           Both pre-activations stay in float32 until the one rounding of the product (NOT rounded to
+ *                           bf16 before, as above); a gate far below zero gives 0, far above zero a * b, never NaN.
+ *                           residual_or_null must be NULL (VC_ERR_INVALID_ARG otherwise), n_out % 256 == 0 (so
+ *                           H % 128 == 0; VC_ERR_UNSUPPORTED otherwise), out must not alias x.  No copy or permutation of
+ *                           the weight: a tile fetches its W operand from the two row ranges.
  * Two tile forms behind the one entry: a 256 x 256 persistent tile (one workgroup per CU, 128 KiB staging ring) when
- * n_out % 256 == 0 and rows >= 1024 — the ViT-B / ViT-L layers — and a 128 x 128 tile otherwise; same arithmetic, the
- * accumulation order over k_in is the same in both.
+ * n_out % 256 == 0 and rows >= 1024 — the ViT-B / ViT-L / ViT-g layers — and a 128 x 128 tile otherwise, for every
+ * epilogue (VC_EPI_SWIGLU: a tile then makes 128 resp. 64 output columns); same arithmetic, the accumulation order over
+ * k_in is the same in both.
  * Replaces the nn.Linear / GELU / residual-add calls inside the hub model's blocks
  * (reference vit_extractor.py:135-146).
  */
 #define VC_EPI_BIAS 0
 #define VC_EPI_GELU 1
 #define VC_EPI_RESIDUAL 2
+#define VC_EPI_SWIGLU 4 /* (3 is taken inside the library: the patch-embedding epilogue, not accepted here) */
 int vc_linear_bf16(const void* x, const void* weight, const void* bias, const void* residual_or_null,
                    void* out, int rows, int n_out, int k_in, int epilogue, vc_stream_t stream);
 

@@ -1,7 +1,8 @@
 // bf16 linear layer with fused epilogue for the DINOv2 blocks (the model behind reference
 // vit_colmap/features/vit_extractor.py:135-146):  out = epi(x W^T + b)  with
-//   epi = identity (qkv), exact-erf GELU (fc1), or "+ residual" (attn.proj / fc2 — the residual
-//   stream update), so the activation and the residual add never make their own pass over HBM.
+//   epi = identity (qkv), exact-erf GELU (fc1), "+ residual" (attn.proj / fc2 — the residual
+//   stream update), or the SwiGLU gate of ViT-g (w12: silu(gate half) * value half, out half as wide),
+//   so the activation and the residual add never make their own pass over HBM.
 //
 // x [M][K] bf16 (token rows), W [N][K] bf16 (torch Linear layout: one output feature per row),
 // out [M][N] bf16.  M is arbitrary (76 550 at 50 images x 1531 tokens), N % 128 == 0, K % 64 == 0.
@@ -34,7 +35,10 @@ constexpr int BK = 64;               // K step: 64 bf16 = one 128-byte LDS row
 constexpr int kImg = 128 * 128;      // bytes of one operand image (128 rows x 128 B)
 constexpr int kStage = 2 * kImg;     // [x image | W image]
 
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3 };
+// EPI_PATCH is internal (vc_patch_embed_bf16); the others are the public VC_EPI_* codes of vc_linear_bf16.
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3, EPI_SWIGLU = 4 };
+static_assert(EPI_BIAS == VC_EPI_BIAS && EPI_GELU == VC_EPI_GELU && EPI_RESIDUAL == VC_EPI_RESIDUAL && EPI_SWIGLU == VC_EPI_SWIGLU,
+              "epilogue codes of the ABI");
 
 // exact GELU, 0.5 x (1 + erf(x / sqrt 2)), erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7):
 // with q = (1 - erf|z|) = poly(t) t exp(-z^2), t = 1 / (1 + p|z|):  gelu = max(x, 0) - 0.5 |x| q.
@@ -72,6 +76,18 @@ __device__ __forceinline__ v2f_t gelu_erf2(v2f_t x) {
   return __builtin_elementwise_fma(ax * (v2f_t){-0.5f, -0.5f}, q, pos);
 }
 
+// EPI_SWIGLU: silu(a) b = a b / (1 + exp(-a)) on the two float32 pre-activations.  exp(-a) overflows to +inf below
+// a ~ -88.7 and v_rcp_f32(+inf) = 0: the gate saturates to (-)0 there and to a itself above, never to NaN.
+__device__ __forceinline__ float swiglu_f32(float a, float b) {
+  const float e = __builtin_amdgcn_exp2f(a * -1.4426950408889634f);
+  return a * __builtin_amdgcn_rcpf(1.0f + e) * b;
+}
+
+// EPI_SWIGLU (both tile forms): N is the width of the PRODUCT (2 H, DINOv2's w12: rows [0, H) of W make the gate, rows
+// [H, 2H) the value) and `out` is [M][H].  A tile's W operand comes from two row ranges — the first half of every wave's
+// feature rows from the gate rows of the tile's output columns, the second half from the matching value rows — so a lane's
+// accumulators [a] and [a + half] are the gate and the value of the SAME output elements: the tile loop, the staging ring and
+// the accumulation order over K are those of the other epilogues, only the W source rows and the store side differ.
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__ X, const __bf16* __restrict__ W,
                                                       const __bf16* __restrict__ bias,
@@ -95,6 +111,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
   }
   const int tm = tile / n_tiles_n, tn = tile - tm * n_tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
+  // EPI_SWIGLU: the tile makes output columns j0 .. j0 + 63; W image rows [64 wn, 64 wn + 32) are gate rows
+  // j0 + 32 wn .. + 31, rows [64 wn + 32, 64 wn + 64) the value rows H + the same
+  const int H = N >> 1, j0 = tn * (BN / 2);
 
   // ---- LDS-DMA staging: a stage is 32 pieces of 1 KiB (8 rows x 128 B); wave w issues x pieces
   // 4w..4w+3 and W pieces 4w..4w+3.  Lane l fills LDS row (l >> 3), chunk (l & 7) of its piece with
@@ -107,7 +126,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
   for (int i = 0; i < 4; ++i) {
     const int row = (wave * 4 + i) * 8 + prow;
     xsrc[i] = X + (size_t)min(m0 + row, M - 1) * K + pchunk * 8;
-    wsrc[i] = W + (size_t)(n0 + row) * K + pchunk * 8;
+    const int wrow = EPI == EPI_SWIGLU ? ((row & 32) ? H : 0) + j0 + (row >> 6) * 32 + (row & 31) : n0 + row;
+    wsrc[i] = W + (size_t)wrow * K + pchunk * 8;
   }
   auto issue = [&](int kt, int buf) {
 #pragma unroll
@@ -160,6 +180,26 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
   }
 
   // ---- epilogue: lane (token = l & 15 of block b, features 4 (l >> 4) .. +3 of block a) -------------
+  if (EPI == EPI_SWIGLU) {
+    // blocks a = 0, 1 hold the gate and a + 2 the value of output columns j0 + 32 wn + 16 a + 4 fq .. + 3
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const int n = j0 + wn * 32 + a * 16 + fq * 4;
+      const v4bf bg = *(const v4bf*)(bias + n), bv = *(const v4bf*)(bias + H + n);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int m = m0 + wm * 64 + b * 16 + fr;
+        if (m < M) {
+          v4bf ov;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            ov[j] = (__bf16)swiglu_f32(acc[a][b][j] + (float)bg[j], acc[a + 2][b][j] + (float)bv[j]);
+          *(v4bf*)(out + (size_t)m * H + n) = ov;
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
     const int n = n0 + wn * 64 + a * 16 + fq * 4;
@@ -283,12 +323,14 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
         voffx[h][i] = (uint32_t)(((size_t)min(m0 + xr, M - 1) * K + pchunk * 8) * 2 - (size_t)min(m0, M - 1) * K * 2);
       }
     }
-    const int wrow = (rho >> 5) * 64 + (rho & 31);
+    // EPI_SWIGLU: unit W0 is gate rows j0 .. j0 + 127 of W (wave column wc takes 32 wc .. + 31), unit W1 the value rows H + the same
+    const int wrow = EPI == EPI_SWIGLU ? rho : (rho >> 5) * 64 + (rho & 31);
     voffw[i] = (uint32_t)(((size_t)wrow * K + pchunk * 8) * 2);
   }
+  const int H = N >> 1, j0 = tn * (G2N / 2);   // EPI_SWIGLU: width of `out`, first output column of the tile
   const char* const xbase = CONV ? (const char*)X : (const char*)(X + (size_t)min(m0, M - 1) * K);
-  const char* const wbase = (const char*)(W + (size_t)n0 * K);
-  const size_t whalf = (size_t)32 * K * 2;
+  const char* const wbase = (const char*)(W + (size_t)(EPI == EPI_SWIGLU ? j0 : n0) * K);
+  const size_t whalf = (size_t)(EPI == EPI_SWIGLU ? H : 32) * K * 2;
   auto issue = [&](int u) {
     if (u >= n_units) return;
     const int t = u >> 2, j = u & 3;
@@ -417,6 +459,37 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
   uint8_t* const ep = lds2 + (size_t)wave * 16384;
   const int lrow = lane >> 3, lslot = lane & 7;          // whole-line view: row 8 i + lrow, 16-byte slot lslot
   auto ep_at = [&](int row, int byte) { return ep + row * 128 + (byte ^ (((row >> 1) & 7) << 4)); };
+  if (EPI == EPI_SWIGLU) {
+    // The wave's block is 128 tokens x 32 output columns: feature blocks a = 0, 1 are the gate, a + 2 the value of columns
+    // j0 + 32 wc + 16 a + 4 fq .. + 3, and a row of the block is 64 bytes, half a line.  Two consecutive token rows share one
+    // 128-byte row of the transposer (row r -> transposer row r >> 1, bytes 64 (r & 1) ..), which keeps the slot swizzle and
+    // both access patterns of the full-width epilogue: 8-byte writes from the accumulator layout (the same 2-way conflict),
+    // conflict-free 16-byte reads of 8 transposer rows per instruction — now 16 token rows x 64 contiguous bytes per store
+    // instruction, lane -> (row 16 i + (l >> 2), 16-byte slot l & 3).  The wave columns 2c and 2c + 1 complete each other's lines.
+    const size_t colh = (size_t)j0 + wc * 32;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const v4bf bg = *(const v4bf*)(bias + colh + a * 16 + fq * 4), bv = *(const v4bf*)(bias + H + colh + a * 16 + fq * 4);
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const int row = 16 * b + fr;
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = swiglu_f32(acc[a][b][j] + (float)bg[j], acc[a + 2][b][j] + (float)bv[j]);
+        const v2bf16 q0 = {(__bf16)v[0], (__bf16)v[1]}, q1 = {(__bf16)v[2], (__bf16)v[3]};
+        *(v2u32*)ep_at(row >> 1, 64 * (row & 1) + 32 * a + 8 * fq) = (v2u32){*(const unsigned int*)&q0, *(const unsigned int*)&q1};
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int m = m0 + wr * 128 + 16 * i + (lane >> 2);
+      const v4u32 o = *(const v4u32*)ep_at(8 * i + lrow, lslot * 16);
+      if (m < M) *(v4u32*)(out + (size_t)m * H + colh + (lane & 3) * 8) = o;
+    }
+    asm volatile("s_barrier" ::: "memory");   // as below: the next tile's copies land in this buffer
+    continue;
+  }
   const size_t col0 = (size_t)n0 + wc * 64;
   if (EPI == EPI_RESIDUAL) {
     v4u32 rr[16];
@@ -1345,9 +1418,11 @@ extern "C" {
 int vc_linear_bf16(const void* x, const void* weight, const void* bias, const void* residual_or_null, void* out,
                    int rows, int n_out, int k_in, int epilogue, vc_stream_t stream) {
   if (!x || !weight || !bias || !out || rows < 0 || n_out <= 0 || k_in <= 0) return VC_ERR_INVALID_ARG;
-  if (epilogue < EPI_BIAS || epilogue > EPI_RESIDUAL) return VC_ERR_INVALID_ARG;
+  if (epilogue != EPI_BIAS && epilogue != EPI_GELU && epilogue != EPI_RESIDUAL && epilogue != EPI_SWIGLU)
+    return VC_ERR_INVALID_ARG;   // (EPI_PATCH is vc_patch_embed_bf16's alone)
   if ((epilogue == EPI_RESIDUAL) != (residual_or_null != nullptr)) return VC_ERR_INVALID_ARG;
-  if (n_out % BN != 0 || k_in % BK != 0) return VC_ERR_UNSUPPORTED;
+  // EPI_SWIGLU: a tile of either form holds the gate and the value half of its output columns, 128 product columns at least
+  if (n_out % (epilogue == EPI_SWIGLU ? 2 * BN : BN) != 0 || k_in % BK != 0) return VC_ERR_UNSUPPORTED;
   if ((((uintptr_t)x) | ((uintptr_t)weight) | ((uintptr_t)bias) | ((uintptr_t)residual_or_null) | ((uintptr_t)out)) % 16 != 0)
     return VC_ERR_INVALID_ARG;
   if (rows == 0) return VC_OK;
@@ -1365,10 +1440,10 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
     if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
     static vc::PerDeviceOnce configured;
     if (int st = vc::allow_dynamic_lds(configured, 160 * 1024, gemm256_kernel<EPI_BIAS, false>, gemm256_kernel<EPI_GELU, false>,
-                                       gemm256_kernel<EPI_RESIDUAL, false>))
+                                       gemm256_kernel<EPI_RESIDUAL, false>, gemm256_kernel<EPI_SWIGLU, false>))
       return st;
     const dim3 grid((unsigned)(nt < cus ? nt : cus)), block(512);
-    return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
+    return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_SWIGLU>(epilogue, [&](auto epi) {
       hipLaunchKernelGGL((gemm256_kernel<epi, false>), grid, block, (size_t)G256_LDS, s, px, pw, pb, pr, po, rows, n_out, k_in,
                          tiles_n, (int)nt, 0, 0, 0, 1, 0, 0, -1);
       return vc::check_launch();
@@ -1377,7 +1452,7 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
   const int tiles_m = (rows + BM - 1) / BM, tiles_n = n_out / BN;
   const long long nt = (long long)tiles_m * tiles_n;
   if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
-  return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
+  return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_SWIGLU>(epilogue, [&](auto epi) {
     hipLaunchKernelGGL(gemm_kernel<epi>, dim3((unsigned)nt), dim3(256), 0, s, px, pw, pb, pr, po, rows, n_out, k_in, tiles_n, (int)nt, 1);
     return vc::check_launch();
   });

@@ -79,15 +79,16 @@ class ViTExtractor(BaseExtractor):
         self.model.fold_layerscale()
         if self.device.type == "cuda" and self.dtype == torch.bfloat16:
             self.model.to(device=self.device)
-            self.model.prepare_hip()      # GEMM operands from the float32 parameters (csrc/gemm.hip), ViT-S only
+            self.model.prepare_hip()      # GEMM operands from the float32 parameters (csrc/gemm.hip)
         self.model.to(device=self.device, dtype=self.dtype)
         self.patch_size = PATCH
         self.descriptor_projection = None  # vit_extractor.py:82
         if projection is not None:
             self.set_projection(projection)
         self.timings = {"decode_s": 0.0, "gpu_s": 0.0, "db_s": 0.0, "images": 0}
-        # Wider backbones (ViT-B/L/g) still run their GEMMs on hipBLASLt, whose default heuristic is poor for these
-        # shapes; TunableOp times the candidate kernels once per new GEMM shape (~1 s each, first batch only).
+        # A model `prepare_hip` does not cover (a width the GEMM does not tile) runs its GEMMs on hipBLASLt, whose default
+        # heuristic is poor for these shapes; TunableOp times the candidate kernels once per new GEMM shape (~1 s each, first
+        # batch only).  Every DINOv2 variant in DINOV2_ARCHS is covered, the SwiGLU giant included, so none of them takes it.
         # It is used ONLY for bf16 on models the hand-written GEMMs do not cover, only around the ViT forward
         # (`_tokens`), never process-wide and never for float32: round 1 recorded a SIGABRT inside an unrelated
         # float32 batched matmul while it was enabled process-wide ("TunableOp").  Results are kept in
@@ -154,7 +155,7 @@ class ViTExtractor(BaseExtractor):
         B, h, w, _ = images_bgr.shape
         hp, wp = h // PATCH, w // PATCH
         if self.model.accepts_padded_patches:
-            # ViT-S / B / L bf16: every GEMM of the forward is hand-written (csrc/gemm.hip); no hipBLASLt, no TunableOp
+            # ViT-S / B / L / g bf16: every GEMM of the forward is hand-written (csrc/gemm.hip); no hipBLASLt, no TunableOp
             # (the register variants take the unpadded layout below into the same hand-written block stack)
             patches = hip_preprocess.preprocess(images_bgr, out_dtype=self.dtype, layout="patches_pad")
             return self.model.forward_patch_tokens(patches, hp, wp).contiguous(), hp, wp

@@ -16,9 +16,11 @@ MI355X-first choices
     (LN2+fc1+GELU+fc2+residual, the hidden tensor never leaves the chip) are hand-written bf16 MFMA kernels with fused
     prologues / epilogues, the attention a hand-written flash kernel — four kernels per block, no library GEMM and no
     standalone elementwise pass;
-  * ViT-B / ViT-L (`_blocks_gemm`): the staged 128x128 MFMA GEMM (vc_linear_bf16) with bias / GELU / residual epilogues,
-    the LayerNorm and attention kernels — hand-written as well; only the SwiGLU giant (`_blocks_fused`) still uses
-    `F.linear`; plain `nn.Module` path (`Block.forward`, SDPA) on the CPU / in float32 — the oracle-side evaluation;
+  * ViT-B / ViT-L / ViT-g (`_blocks_gemm`): the staged MFMA GEMM (vc_linear_bf16) with bias / GELU / residual epilogues
+    and, for the giant's SwiGLU FFN, the gated epilogue that turns the w12 product into silu(x1) * x2 in the accumulators;
+    the LayerNorm and attention kernels — hand-written as well; `_blocks_fused` (`F.linear`) is left for models that were
+    not prepared (LayerScale not folded); plain `nn.Module` path (`Block.forward`, SDPA) on the CPU / in float32 — the
+    oracle-side evaluation;
   * LayerScale is folded into the projection weights at load time, LayerNorm gamma / beta into the GEMM that
     follows (`prepare_hip`);
   * the forward is shape-static per batch size (no data-dependent control flow on the host).
@@ -264,13 +266,13 @@ class DinoV2(nn.Module):
         B = patches.shape[0]
         if patches.shape[-1] == 640:
             # padded patches (preprocess layout "patches_pad"): patch embedding, bias and position embedding in
-            # one hand-written GEMM (csrc/gemm.hip); ViT-S bf16 GPU path only
+            # one hand-written GEMM (csrc/gemm.hip); prepared bf16 GPU models only
             if not (patches.is_cuda and patches.dtype == torch.bfloat16 and self.register_tokens is None and not self.training):
                 raise ValueError("padded patches are only accepted by the bf16 GPU path")
             if getattr(self, "_hip", None) is None:
                 self.prepare_hip()
             if not self._hip:
-                raise ValueError("padded patches need prepare_hip() (ViT-S)")
+                raise ValueError("padded patches need a model that prepare_hip() covers")
             from . import hip_ops as ops
 
             pos, cls_row = self._padded_pos(hp, wp, patches.device)
@@ -278,7 +280,14 @@ class DinoV2(nn.Module):
             ops.patch_embed(patches, self._pe_w, self.patch_embed.proj.bias, pos, x)
             x[:, 0] = cls_row
             return self._blocks_hip(x)
-        x = self.patch_embed.forward_patches(patches)
+        if patches.is_cuda and patches.dtype == torch.bfloat16 and getattr(self, "_hip", None) and not self.training:
+            # prepared register models: the patch embedding on the project's GEMM as well (K zero padded to the operand
+            # prepare_hip made for the padded layout), so that no Linear of a prepared model is a library call
+            from . import hip_ops as ops
+
+            x = ops.linear(F.pad(patches, (0, self._pe_w.shape[1] - patches.shape[-1])), self._pe_w, self.patch_embed.proj.bias)
+        else:
+            x = self.patch_embed.forward_patches(patches)
         x = torch.cat([self.cls_token.expand(B, -1, -1), x], dim=1) + self.interpolated_pos_embed(hp, wp)
         if self.register_tokens is not None:
             x = torch.cat([x[:, :1], self.register_tokens.expand(B, -1, -1), x[:, 1:]], dim=1)
@@ -295,12 +304,13 @@ class DinoV2(nn.Module):
         """Build the x-stationary GEMM operands (csrc/gemm.hip) of every block from the CURRENT parameters:
         qkv with norm1 folded in, proj, the MLP with norm2 folded in.  Call it while the parameters are still
         float32 (after fold_layerscale, on the GPU) so gamma is folded before the one rounding to bf16;
-        `_blocks_fused` calls it lazily otherwise.  ViT-S gets the x-stationary / fused-MLP operands, ViT-B / ViT-L bf16
-        weights for the staged GEMM (q rows pre-scaled); the SwiGLU giant is not covered (`_hip = False`)."""
+        `_blocks_fused` calls it lazily otherwise.  ViT-S gets the x-stationary / fused-MLP operands, ViT-B / ViT-L / ViT-g
+        bf16 weights for the staged GEMM (q rows pre-scaled; the giant's fused w12 as the checkpoint stores it, gate rows
+        then value rows, for the SwiGLU epilogue).  `_hip = False`: LayerScale not folded, or a width the GEMM does not tile."""
         from .hip_ops import FusedMlp, XsLinear
 
         self._hip = False
-        if self.arch.ffn != "mlp" or self.arch.dim % 128 != 0 or not all(b.folded for b in self.blocks):
+        if self.arch.dim % 128 != 0 or not all(b.folded for b in self.blocks):
             return self
         if not self.pos_embed.is_cuda:
             raise RuntimeError("prepare_hip needs the model on the GPU")
@@ -308,16 +318,18 @@ class DinoV2(nn.Module):
         wp = torch.zeros(self.arch.dim, 640, dtype=torch.float32, device=w.device)
         wp[:, : w.shape[1]] = w
         self._pe_w = wp.to(torch.bfloat16).contiguous()          # conv weight as a [C][640] GEMM operand (zero padded K)
-        if self.arch.dim != 384:
-            # ViT-B / ViT-L: every Linear on the staged 128x128 MFMA kernel (csrc/gemm.hip, vc_linear_bf16) with bias /
-            # GELU / residual epilogues, the softmax scale folded into the q rows in float32 — no library GEMM either
+        if self.arch.dim != 384 or self.arch.ffn != "mlp":
+            # ViT-B / ViT-L / ViT-g: every Linear on the staged MFMA kernels (csrc/gemm.hip, vc_linear_bf16) with bias /
+            # GELU / SwiGLU / residual epilogues, the softmax scale folded into the q rows in float32 — no library GEMM either
             bf = lambda t: t.detach().float().to(torch.bfloat16).contiguous()
+            lin = lambda m: (bf(m.weight), bf(m.bias))
+            mlp = ((lambda m: dict(fc1=lin(m.fc1), fc2=lin(m.fc2))) if self.arch.ffn == "mlp" else
+                   (lambda m: dict(w12=lin(m.w12), w3=lin(m.w3))))
             self._hip = [dict(
                 kind="gemm",
                 qkv=tuple(bf(t) for t in _prescale_q(b.attn.qkv.weight, b.attn.qkv.bias, self.arch.dim)),
-                proj=(bf(b.attn.proj.weight), bf(b.attn.proj.bias)),
-                fc1=(bf(b.mlp.fc1.weight), bf(b.mlp.fc1.bias)),
-                fc2=(bf(b.mlp.fc2.weight), bf(b.mlp.fc2.bias)),
+                proj=lin(b.attn.proj),
+                **mlp(b.mlp),
             ) for b in self.blocks]
             return self
         self._hip = [dict(
@@ -417,9 +429,10 @@ class DinoV2(nn.Module):
         return all_rows, out
 
     def _blocks_gemm(self, x, drop_cls: bool = True):
-        """ViT-B / ViT-L bf16 path: LayerNorm kernel + staged MFMA GEMMs with fused epilogues (bias; exact GELU; bias +
-        residual written in place on the residual stream) + the flash attention kernel; six launches per block, none of
-        them a library call.  x (B, 1 + T, C) -> normalised patch tokens (B, T, C), or all rows with drop_cls=False."""
+        """ViT-B / ViT-L / ViT-g bf16 path: LayerNorm kernel + staged MFMA GEMMs with fused epilogues (bias; exact GELU or,
+        for the SwiGLU FFN, silu(gate) * value; bias + residual written in place on the residual stream) + the flash
+        attention kernel; six launches per block, none of them a library call.
+        x (B, 1 + T, C) -> normalised patch tokens (B, T, C), or all rows with drop_cls=False."""
         from . import hip_ops as ops
 
         blocks, hip = list(self.blocks), self._hip
@@ -430,6 +443,10 @@ class DinoV2(nn.Module):
             a = ops.attention(ops.linear(h, *hw["qkv"]), blk.attn.num_heads, q_prescaled=True)
             ops.linear(a, *hw["proj"], ops.EPI_RESIDUAL, residual=xi, out=xi)          # x += proj(a)
             _, h = ops.add_layernorm(xi, None, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+            if "w12" in hw:
+                hdn = ops.linear(h, *hw["w12"], ops.EPI_SWIGLU)                          # silu(x1) * x2, half as wide as w12
+                ops.linear(hdn, *hw["w3"], ops.EPI_RESIDUAL, residual=xi, out=xi)      # x += w3(silu(x1) * x2)
+                return
             hdn = ops.linear(h, *hw["fc1"], ops.EPI_GELU)
             ops.linear(hdn, *hw["fc2"], ops.EPI_RESIDUAL, residual=xi, out=xi)        # x += fc2(gelu(fc1(LN2 x)))
 

@@ -49,25 +49,41 @@ def attention(qkv: torch.Tensor, n_heads: int, q_prescaled: bool = False) -> tor
 
 
 EPI_BIAS, EPI_GELU, EPI_RESIDUAL = 0, 1, 2
+EPI_SWIGLU = 4    # VC_EPI_SWIGLU (3 is the library's internal patch-embedding epilogue)
 
 
-def linear_supported(weight: torch.Tensor) -> bool:
-    """Shapes csrc/gemm.hip covers (every Linear of DINOv2 ViT-S/B/L/g does)."""
+def linear_supported(weight: torch.Tensor, epilogue: int = EPI_BIAS) -> bool:
+    """Shapes csrc/gemm.hip covers (every Linear of DINOv2 ViT-S/B/L/g does); EPI_SWIGLU: `weight` is the fused w12,
+    whose gate and value halves each fill whole tiles."""
     n, k = weight.shape
-    return n % 128 == 0 and k % 64 == 0
+    return n % (256 if epilogue == EPI_SWIGLU else 128) == 0 and k % 64 == 0
+
+
+def linear_out_shape(x_shape, weight_shape, epilogue: int = EPI_BIAS) -> tuple:
+    """Shape of `linear`'s result: x's leading dimensions and n_out columns, n_out // 2 for EPI_SWIGLU (the gate and the
+    value half of the product become one column)."""
+    n, k = weight_shape
+    if tuple(x_shape[-1:]) != (k,):
+        raise ValueError(f"x {tuple(x_shape)} does not fit weight {tuple(weight_shape)}")
+    if epilogue == EPI_SWIGLU and n % 2:
+        raise ValueError(f"EPI_SWIGLU needs an even n_out, got {n}")
+    return tuple(x_shape[:-1]) + (n // 2 if epilogue == EPI_SWIGLU else n,)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, epilogue: int = EPI_BIAS,
            residual=None, out=None) -> torch.Tensor:
-    """out = epi(x W^T + b) (csrc/gemm.hip): EPI_GELU applies the exact GELU, EPI_RESIDUAL adds `residual`."""
+    """out = epi(x W^T + b) (csrc/gemm.hip): EPI_GELU applies the exact GELU, EPI_RESIDUAL adds `residual`, EPI_SWIGLU
+    takes DINOv2's fused w12 (gate rows, then value rows) and returns silu(gate) * value, half as wide as the product
+    (no residual; the library refuses one)."""
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
     assert weight.dtype == torch.bfloat16 and weight.is_contiguous() and bias.dtype == torch.bfloat16
     n, k = weight.shape
     assert x.shape[-1] == k
+    shape = linear_out_shape(x.shape, weight.shape, epilogue)
     rows = x.numel() // k
     if out is None:
-        out = torch.empty(x.shape[:-1] + (n,), dtype=torch.bfloat16, device=x.device)
-    assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() == rows * n
+        out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+    assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() == rows * shape[-1]
     if residual is not None:
         assert residual.shape == out.shape and residual.dtype == torch.bfloat16 and residual.is_contiguous()
     lib = _lib.load()
