@@ -146,7 +146,9 @@ int vc_two_view_inliers(const float* pts, const int32_t* offsets, int n_pairs, c
 int vc_structure_tensor(const void* tokens, int token_dtype, int n_images, int H, int W, int C,
                         float* st, vc_stream_t stream);
 
-/* st -> score [n_images][H*W] in [0,1] (method: VC_METHOD_*).  H*W <= 16384. */
+/* st -> score [n_images][H*W] in [0,1] (method: VC_METHOD_*).  H*W <= 16384 cells, VC_ERR_UNSUPPORTED above.
+ * NOTE the two cell limits: this entry scores up to 16384 cells, vc_select_keypoints below takes 10112 at most.  A
+ * 1920x1080 frame (77 x 137 = 10549 cells) is scored here and then refused there. */
 int vc_score_map(const float* st, int n_images, int H, int W, int method, float* score,
                  vc_stream_t stream);
 
@@ -157,7 +159,13 @@ int vc_score_map(const float* st, int n_images, int H, int W, int method, float*
  * out_yx [n_images][kmax][2] (y, x), out_score [n_images][kmax], out_count [n_images]; the kernel writes every slot
  * (zeros behind the kept points), so the buffers may be handed over uninitialised.
  * dbg_cand_* (all NULL or all non-NULL, same shapes): the candidate list before NMS (slots behind it are left as they were).
- * Limits: target <= 4096, H*W*8 + 80 KiB <= 159 KiB, nms_radius <= 8; kmax >= min(target, candidates).
+ * NMS rule, as the reference states it (vit_extractor.py:534-537): a kept point suppresses the later points at squared cell
+ * distance d2 > 0 with sqrtf((float)d2) < nms_radius, both in float32.  The entry turns the radius into the largest such d2 with
+ * the host's IEEE sqrtf and the kernel compares integers.  (This is not d2 < nms_radius^2: at nms_radius = sqrtf(37) the float32
+ * square is above 37, yet distance^2 37 is kept.)
+ * Limits: target <= 4096 and at most 4096 candidates before the global cut (bins * max(1, target / bins));
+ * H*W*8 + 80 KiB <= 159 KiB, i.e. H*W <= 10112 cells (vc_score_map goes on to 16384: see there); 0 <= nms_radius <= 8;
+ * all of these VC_ERR_UNSUPPORTED.  kmax >= min(target, candidates), else VC_ERR_INVALID_ARG.  A refusal launches nothing.
  */
 int vc_select_keypoints(const float* score, int n_images, int H, int W, int target, int bin_size,
                         float nms_radius, int kmax, int32_t* out_yx, float* out_score,

@@ -188,14 +188,16 @@ def apply_nms(coords: np.ndarray, scores: np.ndarray, nms_radius: float = 1.5):
     c = coords[order].astype(np.int64)
     s = scores[order]
     keep = np.ones(n, dtype=bool)
-    r2 = float(nms_radius) ** 2
+    r = F32(nms_radius)
     for i in range(n):
         if not keep[i]:
             continue
         d2 = ((c - c[i]) ** 2).sum(axis=1)
-        # sqrt is monotone and exact at 0, so (0 < d < r) == (0 < d^2 < r^2) for integer d^2
-        # and r^2 = 2.25 (float32 sqrt of 1, 2, 4 ... is exact or far from 1.5).
-        keep[(d2 > 0) & (d2 < r2)] = False
+        # The reference's own comparison (vit_extractor.py:534-537): the float32 square root of the
+        # integer d^2 against the float32 radius.  Comparing d^2 with r^2 instead is NOT the same
+        # rule: where r is the rounded root of d^2 (r = float32(sqrt(5)), say) r^2 lies above
+        # d^2 and the squared form suppresses a point that sqrt(d^2) < r keeps.
+        keep[(d2 > 0) & (np.sqrt(d2.astype(F32)) < r)] = False
     return c[keep], s[keep]
 
 

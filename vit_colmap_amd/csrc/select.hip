@@ -240,7 +240,7 @@ __global__ __launch_bounds__(kSelThreads) void score_kernel(const float* __restr
 __device__ inline bool before(float sa, int pa, float sb, int pb) { return sa > sb || (sa == sb && pa < pb); }
 
 __global__ __launch_bounds__(kSelThreads) void select_kernel(const float* __restrict__ score_g, int H, int W,
-                                                             int target, int bin, float nms_radius, int kmax,
+                                                             int target, int bin, int nms_reach, int nms_d2_max, int kmax,
                                                              int32_t* __restrict__ out_yx,
                                                              float* __restrict__ out_score,
                                                              int32_t* __restrict__ out_count,
@@ -346,10 +346,11 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(const float* __rest
   __syncthreads();
   for (int r = tid; r < K; r += nt) cell_rank[tmp_cell[r]] = r;
   __syncthreads();
-  const int R = (int)floorf(nms_radius);
-  const float r2 = nms_radius * nms_radius;
-  // point r is kept iff no KEPT point of smaller rank lies at distance 0 < d < radius
-  // (distances compare exactly on squared integers: sqrt is monotone and exact at 0)
+  const int R = nms_reach;
+  // point r is kept iff no KEPT point of smaller rank lies at distance 0 < d < radius.  The reference compares
+  // sqrtf((float)d2) < radius in float32 (vit_extractor.py:534-537); the host entry has turned that into the largest squared
+  // distance that is suppressed, so the comparison here is on integers (d2 < radius^2 in float32 is a different rule at radii
+  // that are the rounded root of a d2: it suppresses d2 = 37 at radius sqrtf(37), which the reference keeps)
   // (one barrier per round: __syncthreads_or carries the "somebody decided" flag; a point reads its neighbours' states while
   // others write theirs, which is harmless — a state changes once, 0 -> 1 or 0 -> 2, and a point decides only when every
   // lower-ranked neighbour has, so it sees their final values whichever side of a write the read falls)
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(const float* __rest
       for (int dy = -R; dy <= R; ++dy)
         for (int dx = -R; dx <= R; ++dx) {
           const int d2 = dy * dy + dx * dx;
-          if (d2 == 0 || !((float)d2 < r2)) continue;
+          if (d2 == 0 || d2 > nms_d2_max) continue;
           const int yy = y + dy, xx = x + dx;
           if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
           const int o = cell_rank[yy * W + xx];
@@ -591,8 +592,13 @@ int vc_select_keypoints(const float* score, int n_images, int H, int W, int targ
   if (smem > (size_t)kDynMax) return VC_ERR_UNSUPPORTED;
   static vc::PerDeviceOnce configured;
   if (int st = vc::allow_dynamic_lds(configured, kDynMax, select_kernel)) return st;
+  // NMS rule of the reference, sqrtf((float)d2) < nms_radius in float32, as an integer bound: sqrtf is IEEE (correctly
+  // rounded, monotone), so the suppressed d2 are 1 .. nms_d2_max; nms_radius <= 8 keeps them below 64 and |dy|, |dx| <= 7
+  int nms_d2_max = 0;
+  while (nms_d2_max < 2 * 8 * 8 && sqrtf((float)(nms_d2_max + 1)) < nms_radius) ++nms_d2_max;
+  const int nms_reach = (int)sqrtf((float)nms_d2_max);   // exact for these small integers: floor of the root
   hipLaunchKernelGGL(select_kernel, dim3(n_images), dim3(kSelThreads), smem, (hipStream_t)stream, score, H, W,
-                     target, bin_size, nms_radius, kmax, out_yx, out_score, out_count, dbg_cand_yx,
+                     target, bin_size, nms_reach, nms_d2_max, kmax, out_yx, out_score, out_count, dbg_cand_yx,
                      dbg_cand_score, dbg_cand_count);
   return vc::check_launch();
 }
