@@ -81,6 +81,25 @@ int vc_match_pairs_u8(const void* prepared, const int32_t* counts, int n_images,
                       vc_stream_t stream);
 
 /*
+ * Guided matching (COLMAP's `guided_matching` option; the build's own published rule, DESIGN.md §4.2e — parity with
+ * COLMAP unpinned): vc_match_pairs_u8 on similarities masked by a two-view model.  For pair p, image a = pairs[2p] is
+ * image 1.  A candidate (i, j) is admissible iff vc_two_view_inliers would call (keypoint i of a, keypoint j of b) an
+ * inlier of models[p] under max_error (VC_MODEL_FUNDAMENTAL: Sampson error, VC_MODEL_HOMOGRAPHY: transfer error from
+ * image 1 to image 2; float32 in the same operation order, so a NaN model admits nothing); the similarity of every
+ * other candidate is replaced by 0, the value that neither matches nor serves as a runner-up, and the match rule of
+ * vc_match_pairs_u8 runs on the result.  Specification: tests/util_guided.py (oracle/matcher_oracle.py on the masked
+ * matrix, mask from oracle/two_view_oracle.py inliers_f32).
+ *   keypoints_xy  [n_images][n_max][2] float32 (x, y), 8-byte aligned; rows >= counts[image] are ignored
+ *   models        [n_pairs][9] float32, row-major
+ *   model_kind    [n_pairs] int32: VC_MODEL_FUNDAMENTAL, VC_MODEL_HOMOGRAPHY, or -1: the pair is skipped (count 0)
+ * Limits, argument checks and output layout as vc_match_pairs_u8; max_error >= 0.  One workgroup per pair.
+ */
+int vc_match_pairs_guided_u8(const void* prepared, const int32_t* counts, int n_images, int n_max, int d,
+                             const float* keypoints_xy, const int32_t* pairs, int n_pairs, const float* models,
+                             const int32_t* model_kind, float max_error, float max_ratio, float max_distance,
+                             int cross_check, uint32_t* out_matches, int32_t* out_counts, vc_stream_t stream);
+
+/*
  * One-way search on raw descriptors: for each of the n1 rows of d1, index of the most similar
  * of the n2 rows of d2 (-1 if every similarity is 0), its similarity and the runner-up's.
  * workspace: at least vc_knn_workspace_bytes(n1, n2, d) bytes, 16-byte aligned.

@@ -32,6 +32,8 @@ SIGNATURES = {
     "vc_prepare_descriptors": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vc_match_pairs_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_float,
                                   c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "vc_match_pairs_guided_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "vc_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vc_knn_top2_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]),

@@ -5,6 +5,8 @@
 // Replaces the per-pair arithmetic of pycolmap.match_exhaustive (reference call site
 // vit_colmap/pipeline/run_pipeline.py:351-363, options vit_colmap/utils/config.py:64-96).
 // Specification: oracle/matcher_oracle.py (bit-exact target).
+// Guided matching (vc_match_pairs_guided_u8, COLMAP's `guided_matching`): the same search on similarities masked by the
+// pair's fundamental matrix or homography, the geometric test fused into the tile epilogue.
 //
 // Data layout
 //   prepared image = n_tiles x KS fragments of 1 KiB + n_tiles*32 int32 row sums, where
@@ -396,15 +398,78 @@ __device__ __forceinline__ void mfma_phase(const v4i (&afrag)[RT][KS], v16i (&ac
 //   best64  = max over keys (s << 32 | ~row): highest s, lowest row on ties
 //   second  = max over { every lane's second } U { every best that is not THE best }: a best that
 //             loses its max contributes itself, one that wins contributes the value it displaced.
-template <int RT, bool FUSED>
+//
+// Guided matching (GUIDED, pair_kernel<..., GUIDED = true>): the update pass first replaces every similarity whose candidate
+// (row keypoint, column keypoint) fails the pair's geometric test by 0 — the value that never matches and never
+// is a runner-up — so both searches see the masked matrix.  The relevance test of pass 1 stays on the unmasked
+// similarities: masking only lowers a value, so a tile that is irrelevant unmasked is irrelevant masked.
+// The test is inlier_f / inlier_h of two_view.hip (specification: oracle/two_view_oracle.py inliers_f32), float32 in
+// the same operation order, factorised into terms of the row (LDS, GuidedWave::rowg, written once per pass), terms
+// of the lane's column (once per tile) and what is left per candidate:
+//   F  row (fx0, fx1, fx2, r = fx0 fx0 + fx1 fx1)   column (x2, y2, q0 = ft0 ft0, q1 = ft1 ft1)
+//      c = x2 fx0 + y2 fx1 + fx2,  den = (r + q0) + q1,  admissible iff c c <= t2 den
+//   H  row (p0, p1, pw, e = pw != 0 ? t2 (pw pw) : NaN)   column (x2, y2)
+//      dx = p0 - x2 pw,  dy = p1 - y2 pw,  admissible iff dx dx + dy dy <= e
+// A NaN model makes every comparison false: nothing is admissible.
+struct GuidedWave {          // wave-uniform state of the geometric test
+  bool is_f;                 // VC_MODEL_FUNDAMENTAL, else VC_MODEL_HOMOGRAPHY
+  float t2;
+  float m[9];                // the pair's model, row-major
+  const v4i* rowg;           // [RT*32] row terms of this wave's rows (float bits)
+  const int* cx;             // [n_pad] column keypoints of image b (float bits)
+  const int* cy;
+};
+struct NoGuide {};
+
+__device__ __forceinline__ v4i guided_row_terms(const GuidedWave& g, float x1, float y1) {
+  const float (&m)[9] = g.m;
+  const float a0 = m[0] * x1 + m[1] * y1 + m[2];
+  const float a1 = m[3] * x1 + m[4] * y1 + m[5];
+  const float a2 = m[6] * x1 + m[7] * y1 + m[8];
+  // F: a = F x1 and the row's share of the Sampson denominator; H: a = H x1 = (p0, p1, pw) and the right-hand side
+  const float w = g.is_f ? a0 * a0 + a1 * a1 : (a2 != 0.f ? g.t2 * (a2 * a2) : __int_as_float(0x7fc00000));
+  v4i r;
+  r[0] = __float_as_int(a0); r[1] = __float_as_int(a1); r[2] = __float_as_int(a2); r[3] = __float_as_int(w);
+  return r;
+}
+
+template <bool IS_F>
+__device__ __forceinline__ int guided_mask(int v, const v4i row, float x2, float y2, float q0, float q1, float t2) {
+  const float r0 = __int_as_float(row[0]), r1 = __int_as_float(row[1]), r2 = __int_as_float(row[2]), r3 = __int_as_float(row[3]);
+  bool adm;
+  if (IS_F) {
+    const float cc = x2 * r0 + y2 * r1 + r2;
+    const float den = (r3 + q0) + q1;
+    adm = cc * cc <= t2 * den;
+  } else {
+    const float dx = r0 - x2 * r2;
+    const float dy = r1 - y2 * r2;
+    adm = dx * dx + dy * dy <= r3;
+  }
+  return adm ? v : 0;
+}
+
+template <int RT, bool FUSED, bool GUIDED = false, bool IS_F = false, typename Guide = NoGuide>
 __device__ __forceinline__ void epilogue_phase(const v16i (&acc)[RT], u32 (&rbest)[RT][16], u32 (&rsec)[RT][16],
                                                const int* rterm_wave, const int* cterm,
                                                unsigned long long* colbest, u32* colsecond, int jt,
-                                               int c, int h, u32 row_base, int s_low, bool (&dense)[RT]) {
+                                               int c, int h, u32 row_base, int s_low, bool (&dense)[RT],
+                                               const Guide guide = Guide()) {
   const int ct = cterm[jt * kTile + c];
   const u32 jcode = 63u - (u32)jt;
   u32 cb = 0, cs2 = 0;
   bool any_hit = false;
+  float gx2 = 0.f, gy2 = 0.f, gq0 = 0.f, gq1 = 0.f;   // GUIDED: terms of the lane's column
+  if constexpr (GUIDED) {
+    gx2 = __int_as_float(guide.cx[jt * kTile + c]);
+    gy2 = __int_as_float(guide.cy[jt * kTile + c]);
+    if (IS_F) {
+      const float ft0 = guide.m[0] * gx2 + guide.m[3] * gy2 + guide.m[6];
+      const float ft1 = guide.m[1] * gx2 + guide.m[4] * gy2 + guide.m[7];
+      gq0 = ft0 * ft0;
+      gq1 = ft1 * ft1;
+    }
+  }
   // Two regimes, chosen per row tile from what the previous column tile looked like (wave-uniform):
   //   sparse: pass 1 computes the lane's largest similarity only (24 VALU); if some lane is
   //           relevant, pass 2 recomputes the similarities and updates (and switches to dense);
@@ -450,7 +515,9 @@ __device__ __forceinline__ void epilogue_phase(const v16i (&acc)[RT], u32 (&rbes
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * q + i;
-          const int v = acc[rt][r] + cr[i] + ct;
+          int v = acc[rt][r] + cr[i] + ct;
+          if constexpr (GUIDED)
+            v = guided_mask<IS_F>(v, guide.rowg[rt * kTile + 8 * q + 4 * h + i], gx2, gy2, gq0, gq1, guide.t2);
           m = max(m, v);
           const u32 rk = ((u32)v << 6) | jcode;
           rsec[rt][r] = umed3(rbest[rt][r], rsec[rt][r], rk);
@@ -461,6 +528,8 @@ __device__ __forceinline__ void epilogue_phase(const v16i (&acc)[RT], u32 (&rbes
             cb = umax(cb, ck);
           }
         }
+        // four rows' terms at a time: hoisted, the 16 LDS reads of a row tile hold 64 registers and spill
+        if constexpr (GUIDED) __builtin_amdgcn_sched_barrier(0);
       }
       dense[rt] = __any(m > s_low);
     }
@@ -633,13 +702,30 @@ __device__ __forceinline__ bool epilogue_phase2(const v16i (&acc)[2], u32 (&rbes
   return hit;
 }
 
-template <int KS, int RT, bool FUSED>
+// Launch arguments of guided matching (pair_kernel<..., GUIDED = true>); the unguided kernels carry none.
+template <bool GUIDED>
+struct GuidedArgs {};
+template <>
+struct GuidedArgs<true> {
+  const float* keypoints;   // [n_images][n_max][2]; rows >= counts are never read
+  const float* models;      // [n_pairs][9] row-major
+  const int32_t* kind;      // [n_pairs]: VC_MODEL_FUNDAMENTAL, VC_MODEL_HOMOGRAPHY, anything else: the pair is skipped
+  float t2;                 // max_error squared (float32 product)
+};
+// guided matching adds to the LDS plan: column keypoint y (x lives in m21, which the tile loop leaves alone) and the
+// row terms of every wave's RT * 32 rows
+__host__ __device__ inline size_t lds_guided_bytes(int n_pad, int rt) { return (size_t)n_pad * 4 + (size_t)kWaves * rt * kTile * 16; }
+
+// GUIDED (FUSED only): guided matching, the similarities pass the pair's geometric test first (epilogue_phase).
+template <int KS, int RT, bool FUSED, bool GUIDED = false>
 __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
     const uint8_t* __restrict__ prepared, const int32_t* __restrict__ counts, int n_tiles_img, int d,
     const int32_t* __restrict__ pairs, float max_ratio, float max_distance, int cross_check,
     int n_max, int ns, int s_low, uint32_t* __restrict__ out_matches, int32_t* __restrict__ out_counts,
     // !FUSED: one-way outputs (rows of A against B)
-    int32_t* __restrict__ o_idx, int32_t* __restrict__ o_best, int32_t* __restrict__ o_second) {
+    int32_t* __restrict__ o_idx, int32_t* __restrict__ o_best, int32_t* __restrict__ o_second,
+    const GuidedArgs<GUIDED> ga) {
+  static_assert(FUSED || !GUIDED, "guided matching exists for the fused match list only");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int n_pad = n_tiles_img * kTile;
   uint8_t* ring = smem;
@@ -652,6 +738,8 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
   int* ridx_s = rsecond_s + n_pad;
   int* crow6 = ridx_s + n_pad;              // [wave][RT*32]: row terms 128*ra - 49024*D
   int* wave_count = crow6 + kWaves * 64 + kWaves * kRowScratchBytes / 4;
+  int* gcy = wave_count + 16;               // GUIDED: [n_pad] column keypoint y; x is kept in m21 until the finalisation
+  v4i* growg = (v4i*)(gcy + n_pad);         // GUIDED: [wave][RT*32] row terms of the geometric test
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -687,8 +775,22 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
   constexpr int kRowsPerPass = kWaves * RT * kTile;
   const int n_ct = ceil_div(n2, kTile);  // column tiles of b that hold valid rows
   const int n_pass = ceil_div(n1, kRowsPerPass);
-  const int total = n_pass * n_ct;       // tiles consumed, in order (pass, jt)
+  int kind = VC_MODEL_FUNDAMENTAL;
+  if constexpr (GUIDED) kind = ga.kind[p];
+  const bool skipped = kind != VC_MODEL_FUNDAMENTAL && kind != VC_MODEL_HOMOGRAPHY;   // GUIDED: a skipped pair has count 0
+  const int total = skipped ? 0 : n_pass * n_ct;   // tiles consumed, in order (pass, jt)
   const int pf = ns - 1;
+
+  GuidedWave gw;
+  if constexpr (GUIDED) {
+    gw.is_f = kind == VC_MODEL_FUNDAMENTAL;
+    gw.t2 = ga.t2;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) gw.m[i] = ga.models[(size_t)p * 9 + i];
+    gw.rowg = growg + wave * RT * kTile;
+    gw.cx = m21;
+    gw.cy = gcy;
+  }
 
   if (total == 0) {  // an empty image: nothing can match (uniform exit)
     if (FUSED) { if (tid == 0) out_counts[p] = 0; }
@@ -701,6 +803,11 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
     cterm[j] = 128 * b_rowsum[j] + 32640 * d;
     colbest[j] = 0ull;
     colsecond[j] = 0u;
+    if constexpr (GUIDED) {   // padded columns hold similarity 0: their keypoint is never decisive
+      const float2 kp = j < n2 ? *(const float2*)(ga.keypoints + ((size_t)img_b * n_max + j) * 2) : make_float2(0.f, 0.f);
+      m21[j] = __float_as_int(kp.x);
+      gcy[j] = __float_as_int(kp.y);
+    }
   }
   if (FUSED)  // defaults for rows whose reduction round is skipped (ordered by the tile barriers)
     for (int i = tid; i < n1; i += kThreads) { rbest_s[i] = 0; rsecond_s[i] = 0; ridx_s[i] = -1; }
@@ -741,6 +848,13 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
       for (int r = 0; r < 16; ++r) { rbest[rt][r] = 0; rsec[rt][r] = 0; }
     // row term of this lane's row (lane <-> row tile0*32 + lane of the wave's RT*32 rows)
     if (lane < RT * kTile) crow6_wave[lane] = 128 * rowsum + rbias;
+    if constexpr (GUIDED) {   // consumed (stored to LDS) before the tile loop: no load of this wave's own is in flight inside it
+      if (lane < RT * kTile) {
+        const int row = tile0 * kTile + lane;
+        const float2 kp = row < n1 ? *(const float2*)(ga.keypoints + ((size_t)img_a * n_max + row) * 2) : make_float2(0.f, 0.f);
+        growg[wave * RT * kTile + lane] = guided_row_terms(gw, kp.x, kp.y);
+      }
+    }
     const u32 row_base = (u32)(tile0 * kTile);
     bool dense[RT];
 #pragma unroll
@@ -770,6 +884,18 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
       }
     };
 
+    // the model kind is uniform over the workgroup: one scalar branch per tile
+#define VC_EPILOGUE(ejt, eth)                                                                                                  \
+    if constexpr (GUIDED) {                                                                                                    \
+      if (gw.is_f)                                                                                                             \
+        epilogue_phase<RT, FUSED, true, true>(acc, rbest, rsec, crow6_wave, cterm, colbest, colsecond, ejt, c, h, row_base,   \
+                                              eth, dense, gw);                                                                 \
+      else                                                                                                                     \
+        epilogue_phase<RT, FUSED, true, false>(acc, rbest, rsec, crow6_wave, cterm, colbest, colsecond, ejt, c, h, row_base,  \
+                                               eth, dense, gw);                                                                \
+    } else {                                                                                                                   \
+      epilogue_phase<RT, FUSED>(acc, rbest, rsec, crow6_wave, cterm, colbest, colsecond, ejt, c, h, row_base, eth, dense);     \
+    }
     {
     // Staggered halves (late = waves 4-7): one loop, the epilogue shared, only the MFMA phase
     // placed before or after it.  The late half runs the epilogue of tile jt-1; for jt = 0 that
@@ -779,13 +905,13 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
       if (!late) mfma_phase<KS, RT>(afrag, acc, slot, lane, produce);
       const int ejt = late ? (jt > 0 ? jt - 1 : 0) : jt;
       const int eth = (late && jt == 0) ? 0x7fffffff : s_low;
-      epilogue_phase<RT, FUSED>(acc, rbest, rsec, crow6_wave, cterm, colbest, colsecond, ejt, c, h, row_base, eth, dense);
+      VC_EPILOGUE(ejt, eth)
       if (late) mfma_phase<KS, RT>(afrag, acc, slot, lane, produce);
     }
-    if (late)
-      epilogue_phase<RT, FUSED>(acc, rbest, rsec, crow6_wave, cterm, colbest, colsecond, n_ct - 1, c, h, row_base, s_low, dense);
+    if (late) { VC_EPILOGUE(n_ct - 1, s_low) }
     }
 #undef VC_TILE_HEAD
+#undef VC_EPILOGUE
 
     // ---- row results of this pass ------------------------------------------------------
     // Each row's candidates sit in 32 lanes (one per column residue c).  Transpose through a
@@ -855,7 +981,9 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
       const unsigned long long kb = colbest[j];
       const int sb = (int)(kb >> 32);
       const int row = (int)(0xFFFFFFFFu - (u32)kb);
-      m21[j] = accept_dev(sb, (int)colsecond[j], max_ratio, max_distance) ? row : -1;
+      const bool ok = GUIDED ? accept_tab(sb, (int)colsecond[j], max_ratio, max_distance, s_low)
+                             : accept_dev(sb, (int)colsecond[j], max_ratio, max_distance);
+      m21[j] = ok ? row : -1;
     }
   }
   __syncthreads();
@@ -867,7 +995,8 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
     int j = -1;
     if (i < n1) {
       j = ridx_s[i];
-      ok = accept_dev(rbest_s[i], rsecond_s[i], max_ratio, max_distance);
+      ok = GUIDED ? accept_tab(rbest_s[i], rsecond_s[i], max_ratio, max_distance, s_low)
+                  : accept_dev(rbest_s[i], rsecond_s[i], max_ratio, max_distance);
       if (ok && cross_check) ok = (m21[j] == i);
     }
     const unsigned long long mask = __ballot(ok);
@@ -1479,7 +1608,27 @@ int launch_pair(const void* prepared, const int32_t* counts, int n_tiles, int d,
   if (int st = vc::allow_dynamic_lds(configured, kLdsBytes, pair_kernel<KS, RT, FUSED>)) return st;
   hipLaunchKernelGGL((pair_kernel<KS, RT, FUSED>), dim3(n_pairs), dim3(kThreads), smem, stream,
                      (const uint8_t*)prepared, counts, n_tiles, d, pairs, max_ratio, max_distance,
-                     cross_check, n_max, ns, s_low, out_matches, out_counts, o_idx, o_best, o_second);
+                     cross_check, n_max, ns, s_low, out_matches, out_counts, o_idx, o_best, o_second, GuidedArgs<false>());
+  return vc::check_launch();
+}
+
+template <int KS, int RT>
+int launch_pair_guided(const void* prepared, const int32_t* counts, int n_tiles, int d, const int32_t* pairs, int n_pairs,
+                       const GuidedArgs<true>& ga, float max_ratio, float max_distance, int cross_check, int n_max,
+                       uint32_t* out_matches, int32_t* out_counts, hipStream_t stream) {
+  // the relevance shortcut holds for the masked similarities as it does for the plain ones: the rule is the same
+  const int s_low = relevance_threshold(max_ratio, max_distance);
+  const int n_pad = n_tiles * kTile;
+  const size_t fixed = lds_fixed_bytes(n_pad) + lds_guided_bytes(n_pad, RT);
+  long ns = ((long)kLdsBytes - (long)fixed) / ((long)KS * kFragBytes);
+  if (ns > kMaxSlots) ns = kMaxSlots;
+  if (ns < (RT == 2 ? 3 : 2)) return VC_ERR_UNSUPPORTED;
+  const size_t smem = (size_t)ns * KS * kFragBytes + fixed;
+  static vc::PerDeviceOnce configured;  // per instantiation and device
+  if (int st = vc::allow_dynamic_lds(configured, kLdsBytes, pair_kernel<KS, RT, true, true>)) return st;
+  hipLaunchKernelGGL((pair_kernel<KS, RT, true, true>), dim3(n_pairs), dim3(kThreads), smem, stream, (const uint8_t*)prepared,
+                     counts, n_tiles, d, pairs, max_ratio, max_distance, cross_check, n_max, (int)ns, s_low, out_matches,
+                     out_counts, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, ga);
   return vc::check_launch();
 }
 
@@ -1561,6 +1710,28 @@ int vc_match_pairs_u8(const void* prepared, const int32_t* counts, int n_images,
   return dispatch_pair<true>(pick_ks(d), prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio,
                              max_distance, cross_check, n_max, out_matches, out_counts, nullptr,
                              nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vc_match_pairs_guided_u8(const void* prepared, const int32_t* counts, int n_images, int n_max, int d,
+                             const float* keypoints_xy, const int32_t* pairs, int n_pairs, const float* models,
+                             const int32_t* model_kind, float max_error, float max_ratio, float max_distance,
+                             int cross_check, uint32_t* out_matches, int32_t* out_counts, vc_stream_t stream) {
+  if (!prepared || !counts || !keypoints_xy || !pairs || !models || !model_kind || !out_matches || !out_counts)
+    return VC_ERR_INVALID_ARG;
+  if (n_images <= 0 || n_max <= 0 || d <= 0 || n_pairs < 0) return VC_ERR_INVALID_ARG;
+  if (((uintptr_t)keypoints_xy) % 8 != 0 || !(max_error >= 0.f)) return VC_ERR_INVALID_ARG;
+  if (n_max > VC_MAX_KEYPOINTS || d > VC_MAX_DESC_DIM) return VC_ERR_UNSUPPORTED;
+  if (n_pairs == 0) return VC_OK;
+  GuidedArgs<true> ga;
+  ga.keypoints = keypoints_xy;
+  ga.models = models;
+  ga.kind = model_kind;
+  ga.t2 = max_error * max_error;
+  return vc::dispatch<2, 4, 8, 12, 16, 24, 32>(pick_ks(d), [&](auto k) {
+    // one row tile per wave for every length: the geometric test needs the registers a second one would take
+    return launch_pair_guided<k, 1>(prepared, counts, tiles_of(n_max), d, pairs, n_pairs, ga, max_ratio, max_distance,
+                                    cross_check, n_max, out_matches, out_counts, (hipStream_t)stream);
+  });
 }
 
 // workspace: prepared copies of d1 and d2 (each as a 1-image set, same n_max), a 2-entry counts

@@ -6,6 +6,8 @@ Reads every image's uint8 descriptors, matches all unordered pairs (a < b in ima
 the GPU, and writes one `matches` row per pair (also when it is empty, as COLMAP does [recalled]).
 With `verify=True` (default) the match lists are then geometrically verified (matching/two_view.py) and
 `two_view_geometries` rows written, as `match_exhaustive` does inside COLMAP.
+With the `guided_matching` option (off by default) every pair whose verification is not DEGENERATE is matched once more
+under its estimated F or H and that list replaces the pair's inlier matches.
 
 Multi-GPU (`distributed=True`, or automatically when a torch.distributed group with more than one rank exists):
 rank 0 reads the database and broadcasts the descriptor blocks, the pair list is dealt round-robin over the
@@ -21,7 +23,7 @@ import torch
 from .. import _lib
 from .. import dist as vd
 from ..database.colmap_db import SqliteColmapDatabase
-from .hip_matcher import exhaustive_pairs, match_pairs, prepare_descriptors
+from .hip_matcher import MODEL_KIND, exhaustive_pairs, match_pairs, match_pairs_guided, prepare_descriptors
 
 logger = logging.getLogger(__name__)
 
@@ -33,6 +35,12 @@ def _sift_options(matching_options, sift_options):
 
         opts = MatchingConfig().to_matching_options()
     return getattr(opts, "sift", opts)  # FeatureMatchingOptions(.sift) or SiftMatchingOptions
+
+
+def _guided_option(matching_options, sift_options) -> bool:
+    """`guided_matching` of the options object: on the outer object (pycolmap 3.13) or on its SIFT options (3.12)."""
+    opts = matching_options if matching_options is not None else sift_options
+    return bool(getattr(opts, "guided_matching", False) or getattr(getattr(opts, "sift", None), "guided_matching", False))
 
 
 def load_descriptor_blocks(db: SqliteColmapDatabase):
@@ -77,12 +85,80 @@ def hip_match_blocks(block, counts, pairs, max_ratio=0.8, max_distance=0.7, cros
         chunk = torch.from_numpy(pairs[s:s + pair_chunk]).to(device)
         m, c = match_pairs(prepared, d_counts, n, n_max, D, chunk, max_ratio, max_distance, cross_check)
         c_np = c.cpu().numpy()
-        if (c_np < 0).any():   # VC_COUNT_SELFCHECK_FAILED: the kernel's cursor check (include/vitcolmap_hip.h) — never a result
-            bad = np.nonzero(c_np < 0)[0][:8] + s
-            raise _lib.HipLibraryError(f"vc_match_pairs_u8: consistency check failed for pairs {bad.tolist()}")
+        _selfcheck(c_np, s, "vc_match_pairs_u8")
         m_np = m.cpu().numpy().view(np.uint32)
         out.extend(m_np[p, : c_np[p]].copy() for p in range(len(c_np)))
     return out
+
+
+def _selfcheck(c_np, first_pair, what):
+    if (c_np < 0).any():   # VC_COUNT_SELFCHECK_FAILED: the kernel's cursor check (include/vitcolmap_hip.h) — never a result
+        bad = np.nonzero(c_np < 0)[0][:8] + first_pair
+        raise _lib.HipLibraryError(f"{what}: consistency check failed for pairs {bad.tolist()}")
+
+
+def check_guided_block_size(n_max: int):
+    """Guided matching runs in one kernel block per image; the sub-blocked path of larger images is unguided only."""
+    if n_max > _lib.VC_MAX_KEYPOINTS:
+        raise _lib.HipLibraryError(f"guided matching needs at most VC_MAX_KEYPOINTS = {_lib.VC_MAX_KEYPOINTS} keypoints per "
+                                   f"image (the largest image has {n_max})")
+
+
+def hip_guided_blocks(block, counts, keypoints_xy, pairs, models, kinds, max_error, max_ratio=0.8, max_distance=0.7,
+                      cross_check=True, device="cuda", pair_chunk: int = 16384):
+    """Guided matching of `pairs` (P, 2) on the HIP matcher: uint8 blocks [n][n_max][D] + counts, keypoints float32
+    [n][>= 1][2] (zero padded), models float32 (P, 9), kinds list of "F" / "H" -> list of P uint32 (M, 2) match lists."""
+    if not torch.cuda.is_available():
+        raise _lib.HipLibraryError("guided matching is HIP-only (no CPU fallback): no GPU visible")
+    d_desc = block if torch.is_tensor(block) else torch.from_numpy(np.ascontiguousarray(block))
+    d_counts = counts if torch.is_tensor(counts) else torch.from_numpy(np.ascontiguousarray(counts, np.int32))
+    d_desc, d_counts = d_desc.to(device), d_counts.to(device)
+    n, n_max, D = d_desc.shape
+    check_guided_block_size(n_max)
+    if D > _lib.VC_MAX_DESC_DIM:
+        raise _lib.HipLibraryError(f"descriptors of {D} bytes exceed the kernels' limit ({_lib.VC_MAX_DESC_DIM})")
+    kp = np.asarray(keypoints_xy, np.float32)
+    kp_block = np.zeros((n, n_max, 2), np.float32)                        # the kernel's layout: one row per descriptor row
+    rows = min(n_max, kp.shape[1])
+    kp_block[:, :rows] = kp[:, :rows, :2]
+    d_kp = torch.from_numpy(kp_block).to(device)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    models = np.ascontiguousarray(models, np.float32).reshape(-1, 9)
+    kind = np.array([MODEL_KIND[k] for k in kinds], np.int32)
+    prepared = prepare_descriptors(d_desc, d_counts)
+    out = []
+    for s in range(0, len(pairs), pair_chunk):
+        sl = slice(s, s + pair_chunk)
+        m, c = match_pairs_guided(prepared, d_counts, n, n_max, D, d_kp, torch.from_numpy(pairs[sl]).to(device),
+                                  torch.from_numpy(models[sl]).to(device), torch.from_numpy(kind[sl]).to(device), max_error,
+                                  max_ratio, max_distance, cross_check)
+        c_np = c.cpu().numpy()
+        _selfcheck(c_np, s, "vc_match_pairs_guided_u8")
+        m_np = m.cpu().numpy().view(np.uint32)
+        out.extend(m_np[p, : c_np[p]].copy() for p in range(len(c_np)))
+    return out
+
+
+def rematch_guided(block, counts, keypoints_xy, pairs, results, max_ratio, max_distance, cross_check, guided_fn) -> int:
+    """The guided pass over one rank's share: every result of `results` (verify_pairs' format, parallel to `pairs`) that is
+    not DEGENERATE has its `inlier_matches` replaced by the list matched under the model that produced them (`model`,
+    `model9`), with the verifier's own error bound.  Returns the number of pairs re-matched."""
+    from .two_view import CONFIG_DEGENERATE, MAX_ERROR
+
+    sel = [i for i, r in enumerate(results) if r["config"] != CONFIG_DEGENERATE]
+    if not sel:
+        return 0
+    missing = [i for i in sel if results[i].get("model") not in ("F", "H") or results[i].get("model9") is None]
+    if missing:
+        raise ValueError("guided matching needs `model` and `model9` in every verified result "
+                         f"(missing for pairs {[tuple(map(int, pairs[i])) for i in missing[:8]]})")
+    models = np.stack([np.asarray(results[i]["model9"], np.float32).reshape(9) for i in sel])
+    kinds = [results[i]["model"] for i in sel]
+    lists = guided_fn(block, counts, keypoints_xy, np.asarray(pairs, np.int32).reshape(-1, 2)[sel], models, kinds, MAX_ERROR,
+                      max_ratio, max_distance, cross_check)
+    for i, lst in zip(sel, lists):
+        results[i]["inlier_matches"] = np.asarray(lst, np.uint32).reshape(-1, 2)
+    return len(sel)
 
 
 def _pack_keypoints(kps: dict, n: int):
@@ -99,7 +175,8 @@ def _unpack_keypoints(arr, cnt):
 
 
 def match_exhaustive(database_path: str, matching_options=None, sift_options=None, device="cuda",
-                     pair_chunk: int = 16384, distributed=None, match_fn=None, verify: bool = True, verify_fn=None) -> dict:
+                     pair_chunk: int = 16384, distributed=None, match_fn=None, verify: bool = True, verify_fn=None,
+                     guided_fn=None) -> dict:
     """Returns a small stats dict (pairs, matches, seconds); the result proper is in the database.
     Multi-rank (`distributed`): rank 0 — the only process that touches the SQLite file — reads descriptors and keypoints
     and broadcasts them; EVERY rank matches and geometrically verifies its share of the pair list (pair p -> rank
@@ -107,9 +184,15 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
     on any rank (e.g. rank 0's database) is raised on all of them (dist.raise_if_any_failed).
     `match_fn(block, counts, pairs, max_ratio, max_distance, cross_check) -> list of match lists` and
     `verify_fn(keypoints, pair_images, pair_ids, lists) -> list of results` replace the HIP matcher / scorer (the CPU
-    tests of the multi-rank path pass the oracles; the product never does)."""
+    tests of the multi-rank path pass the oracles; the product never does).
+    Guided matching (the options' `guided_matching`, off by default; needs `verify`): after verification each rank
+    re-matches the non-degenerate pairs of its own share under their models and the lists replace those pairs'
+    `inlier_matches` (rematch_guided); `matches`, `config`, F and H are untouched.  `guided_fn(block, counts, keypoints_xy,
+    pairs, models, kinds, max_error, max_ratio, max_distance, cross_check) -> list of match lists` replaces
+    hip_guided_blocks in the CPU tests."""
     sift = _sift_options(matching_options, sift_options)
     max_ratio, max_distance, cross_check = float(sift.max_ratio), float(sift.max_distance), bool(sift.cross_check)
+    guided = _guided_option(matching_options, sift_options) and verify
     if distributed is None:
         distributed = vd.is_distributed()
     if distributed and not vd.is_distributed():
@@ -122,7 +205,15 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
         def match_fn(block, counts, pairs, r, dmax, cc):
             return hip_match_blocks(block, counts, pairs, r, dmax, cc, device=device, pair_chunk=pair_chunk)
 
-    from .two_view import read_keypoints_by_index, verify_pair_lists, write_two_view_rows
+    if guided and guided_fn is None:
+        if not torch.cuda.is_available():
+            raise _lib.HipLibraryError("guided matching needs an MI355X: the matcher is HIP-only (no CPU fallback)")
+
+        def guided_fn(block, counts, kp_xy, pairs, models, kinds, e, r, dmax, cc):
+            return hip_guided_blocks(block, counts, kp_xy, pairs, models, kinds, e, r, dmax, cc, device=device,
+                                     pair_chunk=pair_chunk)
+
+    from .two_view import CONFIG_DEGENERATE, read_keypoints_by_index, verify_pair_lists, write_two_view_rows
 
     t0 = time.perf_counter()
     db = None
@@ -148,9 +239,12 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
         elif err is not None:
             raise err
         n = len(ids)
-        stats = dict(images=n, pairs=n * (n - 1) // 2, matches=0, gpu_s=0.0, db_s=0.0, verified_pairs=0, ranks=world)
+        stats = dict(images=n, pairs=n * (n - 1) // 2, matches=0, gpu_s=0.0, db_s=0.0, verified_pairs=0, ranks=world,
+                     guided_pairs=0)
         if n < 2:
             return stats
+        if guided and D != 0:
+            check_guided_block_size(int(np.asarray(block).shape[1]))           # before any matching starts, on every rank
         my_pairs = vd.pairs_for_rank(n, rank, world)
         t1 = time.perf_counter()
         err, lists, results = None, [], None
@@ -163,6 +257,9 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
                     vdev = device if (verify_fn is not None or torch.cuda.is_available()) else "cpu"
                     results = verify_pair_lists(_unpack_keypoints(kp_arr, kp_cnt), ids, my_pairs, lists, device=vdev,
                                                 verify_fn=verify_fn)
+                    if guided:
+                        rematch_guided(block, counts, kp_arr, my_pairs, results, max_ratio, max_distance, cross_check,
+                                       guided_fn)
         except Exception as e:  # noqa: BLE001
             err = e
         if distributed:
@@ -187,6 +284,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
                 db.commit()
                 if verified is not None:
                     stats["verified_pairs"] = write_two_view_rows(db, ids, verified)
+                    stats["guided_pairs"] = sum(r["config"] != CONFIG_DEGENERATE for r in verified.values()) if guided else 0
                 stats["db_s"] = time.perf_counter() - t2
             except Exception as e:  # noqa: BLE001
                 err = e

@@ -57,6 +57,32 @@ def match_pairs(prepared, counts, n_images, n_max, d, pairs, max_ratio=0.8, max_
     return out_matches, out_counts
 
 
+MODEL_KIND = {"F": 0, "H": 1, None: -1}   # VC_MODEL_FUNDAMENTAL, VC_MODEL_HOMOGRAPHY, "skip this pair"
+
+
+def match_pairs_guided(prepared, counts, n_images, n_max, d, keypoints_xy, pairs, models, model_kind, max_error=4.0,
+                       max_ratio=0.8, max_distance=0.7, cross_check=True, out_matches=None, out_counts=None):
+    """Guided matching: match_pairs on similarities masked by each pair's two-view model.
+    keypoints_xy float32 [n_images, n_max, 2], models float32 [P, 9] row-major, model_kind int32 [P] (MODEL_KIND codes;
+    -1 skips the pair: count 0).  -> (matches int32-viewed-uint32 [P, n_max, 2], match counts int32 [P])."""
+    _need_cuda(prepared, counts, keypoints_xy, pairs, models, model_kind)
+    assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.shape[-1] == 2
+    P = pairs.shape[0]
+    assert keypoints_xy.dtype == torch.float32 and keypoints_xy.is_contiguous() and tuple(keypoints_xy.shape) == (n_images, n_max, 2)
+    assert models.dtype == torch.float32 and models.is_contiguous() and tuple(models.shape) == (P, 9)
+    assert model_kind.dtype == torch.int32 and model_kind.is_contiguous() and model_kind.numel() == P
+    lib = _lib.load()
+    if out_matches is None:
+        out_matches = torch.empty((P, n_max, 2), dtype=torch.int32, device=prepared.device)
+    if out_counts is None:
+        out_counts = torch.empty((P,), dtype=torch.int32, device=prepared.device)
+    _lib.check(lib.vc_match_pairs_guided_u8(_lib.ptr(prepared), _lib.ptr(counts), n_images, n_max, d, _lib.ptr(keypoints_xy),
+                                            _lib.ptr(pairs), P, _lib.ptr(models), _lib.ptr(model_kind), float(max_error),
+                                            max_ratio, max_distance, int(cross_check), _lib.ptr(out_matches),
+                                            _lib.ptr(out_counts), _lib.stream_ptr()), "vc_match_pairs_guided_u8")
+    return out_matches, out_counts
+
+
 def knn_top2(d1: torch.Tensor, d2: torch.Tensor):
     """One-way search: per row of d1 -> (idx, best, second) against the rows of d2."""
     _need_cuda(d1, d2)

@@ -169,7 +169,9 @@ def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
 def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", num_f=NUM_HYP_F, num_h=NUM_HYP_H,
                  max_error=MAX_ERROR, chunk_pairs: int = 1024):
     """keypoints: dict image index -> float32 (N, >= 2); pair_images: list of (a, b); pair_ids: COLMAP pair ids;
-    match_lists: list of uint32 (M, 2).  -> list of dict(config, inlier_matches, F, H, n_f, n_h), one per pair."""
+    match_lists: list of uint32 (M, 2).  -> list of dict(config, inlier_matches, F, H, n_f, n_h), one per pair.
+    A result that is not DEGENERATE also carries the model whose mask produced `inlier_matches` — `model` ("F" or "H") and
+    `model9` (float32 (9,), row-major; NOT the stored rank-2 F): what guided matching re-matches the pair under."""
     if not torch.cuda.is_available():
         raise _lib.HipLibraryError("geometric verification scores its hypotheses on the GPU (no CPU fallback)")
     results = [dict(config=CONFIG_DEGENERATE, inlier_matches=np.zeros((0, 2), np.uint32), F=np.zeros((3, 3)),
@@ -201,6 +203,7 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
             F2 = (F2 / nrm[:, None, None]).cpu().numpy()
         H = torch.nan_to_num(h9.to(torch.float64)).reshape(P, 3, 3).cpu().numpy()
         fmask, hmask, nf, nh = fmask.cpu().numpy(), hmask.cpu().numpy(), nf.cpu().numpy(), nh.cpu().numpy()
+        f9_np, h9_np = f9.cpu().numpy(), h9.cpu().numpy()
         for q, i in enumerate(sel):
             r = results[i]
             r["n_f"], r["n_h"] = int(nf[q]), int(nh[q])
@@ -212,9 +215,12 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
             if r["n_h"] / r["n_f"] > MAX_H_INLIER_RATIO:
                 r["config"] = CONFIG_PLANAR_OR_PANORAMIC
                 mask = hmask[lo:hi] if r["n_h"] > r["n_f"] else fmask[lo:hi]
+                r["model"] = "H" if r["n_h"] > r["n_f"] else "F"
             else:
                 r["config"] = CONFIG_UNCALIBRATED
                 mask = fmask[lo:hi]
+                r["model"] = "F"
+            r["model9"] = (h9_np if r["model"] == "H" else f9_np)[q].copy()
             r["inlier_matches"] = np.asarray(match_lists[i], np.uint32).reshape(-1, 2)[mask]
     return results
 

@@ -35,9 +35,10 @@ logger = logging.getLogger(__name__)
 
 def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn=None, matching_options=None,
                 match_fn=None, do_matching=True, verify=True, device="cuda", batch_size=50, verify_fn=None,
-                camera_params_for=default_camera_params, camera_per_image=False) -> dict:
+                camera_params_for=default_camera_params, camera_per_image=False, guided_fn=None) -> dict:
     from ..database.colmap_db import ColmapDatabase
-    from ..matching.exhaustive import _sift_options, hip_match_blocks
+    from ..matching.exhaustive import (_guided_option, _sift_options, check_guided_block_size, hip_guided_blocks,
+                                       hip_match_blocks, rematch_guided)
 
     rank, world = vd.rank_world()
     image_files = list_images(Path(image_dir))
@@ -112,8 +113,11 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
         bcounts = all_counts[torch.from_numpy(keep).to(all_counts.device)]
         kept_ids = [ids[k] for k in keep]
         my_pairs = vd.pairs_for_rank(m, rank, world)
+        guided = _guided_option(matching_options, None) and verify            # the options' guided_matching
         err, lists, results = None, [], None
         try:
+            if guided:
+                check_guided_block_size(int(blocks.shape[1]))                   # before any matching starts
             if match_fn is None:
                 lists = hip_match_blocks(blocks, bcounts, my_pairs, r_, d_, c_, device=device)
             else:
@@ -121,6 +125,11 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
             if verify:                                                          # every rank verifies the pairs it matched
                 kps = {i: kp_np[k, : cnt[k], :2] for i, k in enumerate(keep)}
                 results = verify_pair_lists(kps, kept_ids, my_pairs, lists, device=device, verify_fn=verify_fn)
+                if guided:                                                      # ... and re-matches them under their models
+                    if guided_fn is None:
+                        def guided_fn(blk, cts, kp_xy, prs, models, kinds, e, r, dmax, cc):
+                            return hip_guided_blocks(blk, cts, kp_xy, prs, models, kinds, e, r, dmax, cc, device=device)
+                    rematch_guided(blocks, bcounts, kp_np[keep][:, :, :2], my_pairs, results, r_, d_, c_, guided_fn)
         except Exception as e:  # noqa: BLE001
             err = e
         vd.raise_if_any_failed(err, "matching / verification")

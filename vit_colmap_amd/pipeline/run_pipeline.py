@@ -155,6 +155,8 @@ def main() -> None:
                     help="keypoint detector of --extractor hybrid (runs on the GPU)")
     ap.add_argument("--vit-weights", dest="vit_weights", type=Path, default=None)
     ap.add_argument("--skip-matching", dest="skip_matching", action="store_true")
+    ap.add_argument("--guided-matching", dest="guided_matching", action="store_true",
+                    help="re-match every verified pair under its estimated F or H (COLMAP's guided_matching)")
     ap.add_argument("--skip-reconstruction", dest="skip_reconstruction", action="store_true")
     ap.add_argument("--dataset", default=None)
     ap.add_argument("--scene", default=None)

@@ -48,6 +48,7 @@ class SiftMatchingOptions:
     cross_check: bool = True
     use_gpu: bool = True
     num_threads: int = -1
+    guided_matching: bool = False   # pycolmap 3.12 keeps the option here [recalled]
 
 
 @dataclass
@@ -56,6 +57,7 @@ class FeatureMatchingOptions:
 
     use_gpu: bool = True
     num_threads: int = -1
+    guided_matching: bool = False   # pycolmap 3.13 moved the option to the outer object [recalled]
     sift: SiftMatchingOptions = field(default_factory=SiftMatchingOptions)
 
 
@@ -68,20 +70,23 @@ class MatchingConfig:
     max_distance: float = 0.7
     cross_check: bool = True
     num_threads: int = -1  # -1 means auto-detect
+    guided_matching: bool = False  # re-match verified pairs under their F or H model (not set by the reference)
 
     def to_matching_options(self) -> FeatureMatchingOptions:
-        opts = FeatureMatchingOptions(use_gpu=self.use_gpu, num_threads=self.num_threads)
+        opts = FeatureMatchingOptions(use_gpu=self.use_gpu, num_threads=self.num_threads,
+                                      guided_matching=self.guided_matching)
         opts.sift.max_ratio = self.max_ratio
         opts.sift.max_distance = self.max_distance
         opts.sift.cross_check = self.cross_check
         opts.sift.use_gpu = self.use_gpu
         opts.sift.num_threads = self.num_threads
+        opts.sift.guided_matching = self.guided_matching
         return opts
 
     def _to_sift_options_legacy(self) -> SiftMatchingOptions:
         return SiftMatchingOptions(max_ratio=self.max_ratio, max_distance=self.max_distance,
                                    cross_check=self.cross_check, use_gpu=self.use_gpu,
-                                   num_threads=self.num_threads)
+                                   num_threads=self.num_threads, guided_matching=self.guided_matching)
 
 
 @dataclass
@@ -142,6 +147,8 @@ class Config:
             config.extractor.detector_type = args.detector
         if hasattr(args, "use_gpu"):
             config.matching.use_gpu = args.use_gpu
+        if getattr(args, "guided_matching", False):
+            config.matching.guided_matching = True
         if hasattr(args, "skip_matching"):
             config.do_matching = not args.skip_matching
         if hasattr(args, "skip_reconstruction"):
