@@ -146,6 +146,23 @@ int vc_two_view_inliers(const float* pts, const int32_t* offsets, int n_pairs, c
                         float max_error, uint8_t* out_mask, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Calibrated two-view geometry, the minimal solver: every real essential matrix E with
+ * x2' E x1 = 0 for five correspondences, for n_hyp samples of each of n_pairs image pairs.  float64 throughout.
+ * Specification: tests/util_essential.py.
+ *   pts_n      [total][4] float64 (x1, y1, x2, y2) in normalised camera coordinates (K^-1 applied), all pairs concatenated
+ *   offsets    [n_pairs + 1] int32: pair p owns pts_n[offsets[p] .. offsets[p+1])
+ *   samples    [n_pairs][n_hyp][5] int32 indices into the pair's own list; samples[..][0] < 0: the hypothesis is void
+ *   out_E      [n_pairs][n_hyp][10][9] float64: row-major 3x3 at unit Frobenius norm, ascending in the solver's root
+ *              variable; the slots past out_count are NaN
+ *   out_count  [n_pairs][n_hyp] int32: number of real solutions, 0 .. 10.  0 for a void sample, an index outside the
+ *              pair's list, a repeated index or point, non-finite points and a singular elimination; a matrix that is
+ *              not finite is never counted.
+ * Every iterative part runs a bounded number of steps.  n_pairs * n_hyp above 64 * (2^31 - 1): VC_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+int vc_essential_5pt(const double* pts_n, const int32_t* offsets, int n_pairs, const int32_t* samples, int n_hyp,
+                     double* out_E, int32_t* out_count, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

@@ -17,6 +17,8 @@ from ..utils import image_io
 
 
 class BaseExtractor(ABC):
+    prior_focal_length = False     # True: the camera rows this extractor writes carry `has_prior_focal_length`
+
     @abstractmethod
     def extract(
         self,
@@ -47,17 +49,22 @@ def default_camera_params(camera_model: str, width: int, height: int) -> list:
     raise ValueError(f"Unsupported camera model: {camera_model}")
 
 
-def camera_policy(camera_model, camera_params, first_hw, params_for=default_camera_params, per_image=False):
+def camera_policy(camera_model, camera_params, first_hw, params_for=default_camera_params, per_image=False,
+                  prior_focal_length=False):
     """-> camera_of(height, width): the Camera of an image.  One camera for all images (the same object), of the first
     image's size, with `camera_params` or else `params_for(camera_model, w, h)`; with `per_image`, one camera per image
     from `params_for` and `camera_params` ignored (COLMAP's ImageReader with CameraMode.AUTO).  ValueError for a model
-    `params_for` does not support, raised here, before any database is opened."""
+    `params_for` does not support, raised here, before any database is opened.  `prior_focal_length` marks every camera
+    row as carrying trusted intrinsics (`has_prior_focal_length`: the calibrated branch of verification)."""
     h0, w0 = (int(x) for x in first_hw)
+    prior = bool(prior_focal_length)
     if per_image:
         params_for(camera_model, w0, h0)
-        return lambda h, w: Camera(model=camera_model, width=w, height=h, params=params_for(camera_model, w, h))
+        return lambda h, w: Camera(model=camera_model, width=w, height=h, params=params_for(camera_model, w, h),
+                                   has_prior_focal_length=prior)
     camera = Camera(model=camera_model, width=w0, height=h0,
-                    params=camera_params if camera_params is not None else params_for(camera_model, w0, h0))
+                    params=camera_params if camera_params is not None else params_for(camera_model, w0, h0),
+                    has_prior_focal_length=prior)
     return lambda h, w: camera
 
 
@@ -160,7 +167,7 @@ def extract_to_database(extractor, image_dir, db_path, camera_model, camera_para
     if first is None:
         raise ValueError(f"Failed to read first image: {files[0]}")
     camera_of = camera_policy(camera_model, camera_params, first.shape[:2], extractor.camera_params_for,
-                              extractor.camera_per_image)
+                              extractor.camera_per_image, getattr(extractor, "prior_focal_length", False))
 
     def write_rows(items, results):
         t0 = time.perf_counter()

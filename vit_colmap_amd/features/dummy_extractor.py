@@ -59,7 +59,8 @@ class DummyExtractor(BaseExtractor):
         height, width = first_img.shape[:2]
         if camera_params is None:
             camera_params = default_camera_params(camera_model, width, height)
-        camera_id = db.db.write_camera(Camera(model=camera_model, width=width, height=height, params=camera_params))
+        camera_id = db.db.write_camera(Camera(model=camera_model, width=width, height=height, params=camera_params,
+                                              has_prior_focal_length=bool(self.prior_focal_length)))
 
         for img_file in image_files:
             img = image_io.imread(img_file)

@@ -185,6 +185,9 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
     `match_fn(block, counts, pairs, max_ratio, max_distance, cross_check) -> list of match lists` and
     `verify_fn(keypoints, pair_images, pair_ids, lists) -> list of results` replace the HIP matcher / scorer (the CPU
     tests of the multi-rank path pass the oracles; the product never does).
+    Calibrated pairs: rank 0 reads every image's camera and broadcasts a (3, 3) K and a usable-prior flag
+    per image next to the keypoints; a pair with the prior on both images is also verified under an essential matrix
+    (`verify_fn` then gets the keyword `cameras=(K, prior)`).
     Guided matching (the options' `guided_matching`, off by default; needs `verify`): after verification each rank
     re-matches the non-degenerate pairs of its own share under their models and the lists replace those pairs'
     `inlier_matches` (rematch_guided); `matches`, `config`, F and H are untouched.  `guided_fn(block, counts, keypoints_xy,
@@ -213,12 +216,13 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
             return hip_guided_blocks(block, counts, kp_xy, pairs, models, kinds, e, r, dmax, cc, device=device,
                                      pair_chunk=pair_chunk)
 
+    from .essential import camera_table
     from .two_view import CONFIG_DEGENERATE, read_keypoints_by_index, verify_pair_lists, write_two_view_rows
 
     t0 = time.perf_counter()
     db = None
     try:
-        ids = block = counts = D = kp_arr = kp_cnt = None
+        ids = block = counts = D = kp_arr = kp_cnt = cam_k = cam_prior = None
         err = None
         if rank == 0:                                                          # rank 0 is the only reader and writer
             try:
@@ -226,6 +230,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
                 ids, block, counts, D = load_descriptor_blocks(db)
                 if verify and D != 0:
                     kp_arr, kp_cnt = _pack_keypoints(read_keypoints_by_index(db, ids), len(ids))
+                    cam_k, cam_prior = camera_table(db, ids)               # focal-length priors
             except Exception as e:  # noqa: BLE001 - handed to every rank below
                 err = e
         if distributed:
@@ -236,6 +241,8 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
             if verify and D != 0:
                 kp_arr = vd.broadcast_array(kp_arr, 0, device)
                 kp_cnt = vd.broadcast_array(kp_cnt, 0, device)
+                cam_k = vd.broadcast_array(cam_k, 0, device)
+                cam_prior = vd.broadcast_array(cam_prior, 0, device)
         elif err is not None:
             raise err
         n = len(ids)
@@ -256,7 +263,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
                 if verify:                                                     # this rank verifies the pairs it matched
                     vdev = device if (verify_fn is not None or torch.cuda.is_available()) else "cpu"
                     results = verify_pair_lists(_unpack_keypoints(kp_arr, kp_cnt), ids, my_pairs, lists, device=vdev,
-                                                verify_fn=verify_fn)
+                                                verify_fn=verify_fn, cameras=(cam_k, cam_prior))
                     if guided:
                         rematch_guided(block, counts, kp_arr, my_pairs, results, max_ratio, max_distance, cross_check,
                                        guided_fn)

@@ -6,7 +6,8 @@ with a published sampler; parity with COLMAP's estimator is unpinned — COLMAP 
 
 Where the work runs
   HIP     scoring of every hypothesis against every match of every pair, and the inlier masks
-          (csrc/two_view.hip, vc_two_view_score / vc_two_view_inliers): O(pairs x hypotheses x matches)
+          (csrc/two_view.hip, vc_two_view_score / vc_two_view_inliers): O(pairs x hypotheses x matches);
+          the five-point solver of the calibrated branch (csrc/essential.hip; matching/essential.py)
   torch   the minimal solvers: batched 8x8 linear systems (float64) for all pairs and hypotheses at once, the
           normal equations of the one refit, a 3x3 SVD per pair for the stored F — plumbing around the kernels
   host    gathering matched keypoints from the database, writing the rows (rank 0 only in a multi-GPU run)
@@ -26,7 +27,7 @@ MAX_H_INLIER_RATIO = 0.8
 MIN_INLIER_RATIO = 0.25
 NUM_HYP_F, NUM_HYP_H = 512, 128
 NUM_CANDIDATES = 32
-SALT = {"F": 0x0F0F0F0F, "H": 0x3C3C3C3C}
+SALT = {"F": 0x0F0F0F0F, "H": 0x3C3C3C3C, "E": 0x5A5A5A5A}
 MODEL_CODE = {"F": 0, "H": 1}
 _M32 = 0xFFFFFFFF
 
@@ -165,13 +166,45 @@ def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
     return final, fmask, fcount
 
 
+def _stored_f(f9):
+    """float32 (9,) -> the closest rank-2 matrix at unit Frobenius norm, float64 (3, 3)."""
+    U, sv, Vt = np.linalg.svd(np.nan_to_num(np.asarray(f9, np.float64)).reshape(3, 3))
+    F2 = U @ np.diag([sv[0], sv[1], 0.0]) @ Vt
+    n = np.linalg.norm(F2)
+    return F2 / n if n > 0 else F2
+
+
+def _estimate_calibrated(cal, sel, pts_np, pair_images, pair_ids, cameras, device, max_error):
+    """The E estimate of the chunk's calibrated pairs `cal` (positions in `sel`) as one batch of their own
+    -> {position: dict(n, E, f9, mask, xn)} (matching/essential.py)."""
+    from . import essential
+
+    K, _ = cameras
+    pts = torch.from_numpy(np.concatenate([pts_np[q] for q in cal])).to(device).contiguous()
+    offs = np.concatenate([[0], np.cumsum([len(pts_np[q]) for q in cal])])
+    offsets = torch.tensor(offs, dtype=torch.int32, device=device)
+    pair_of = torch.repeat_interleave(torch.arange(len(cal), device=device), (offsets[1:] - offsets[:-1]).to(torch.int64))
+    seeds = torch.tensor([int(pair_ids[sel[q]]) & _M32 for q in cal], dtype=torch.int64, device=device)
+    K1 = torch.from_numpy(np.stack([K[pair_images[sel[q]][0]] for q in cal]).astype(np.float64)).to(device)
+    K2 = torch.from_numpy(np.stack([K[pair_images[sel[q]][1]] for q in cal]).astype(np.float64)).to(device)
+    with torch.cuda.device(pts.device):
+        E, f9, mask, n, xn = essential.estimate_e(pts, offsets, pair_of, seeds, K1, K2, essential.NUM_HYP_E, max_error)
+    E, f9, mask, n, xn = E.cpu().numpy(), f9.cpu().numpy(), mask.cpu().numpy(), n.cpu().numpy(), xn.cpu().numpy()
+    return {q: dict(n=int(n[j]), E=E[j], f9=f9[j], mask=mask[offs[j]:offs[j + 1]], xn=xn[offs[j]:offs[j + 1]])
+            for j, q in enumerate(cal)}
+
+
 @torch.no_grad()
 def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", num_f=NUM_HYP_F, num_h=NUM_HYP_H,
-                 max_error=MAX_ERROR, chunk_pairs: int = 1024):
+                 max_error=MAX_ERROR, chunk_pairs: int = 1024, cameras=None):
     """keypoints: dict image index -> float32 (N, >= 2); pair_images: list of (a, b); pair_ids: COLMAP pair ids;
     match_lists: list of uint32 (M, 2).  -> list of dict(config, inlier_matches, F, H, n_f, n_h), one per pair.
     A result that is not DEGENERATE also carries the model whose mask produced `inlier_matches` — `model` ("F" or "H") and
-    `model9` (float32 (9,), row-major; NOT the stored rank-2 F): what guided matching re-matches the pair under."""
+    `model9` (float32 (9,), row-major; NOT the stored rank-2 F): what guided matching re-matches the pair under.
+    `cameras`: None, or (K float64 (n, 3, 3), prior (n,)) indexed like `keypoints` (essential.camera_table).  A pair whose
+    two images have a usable focal-length prior also gets an essential-matrix estimate (`n_e`); where it reaches
+    max(15, 0.25 M) and 0.95 n_f inliers the best model is E: config CALIBRATED (or PLANAR_OR_PANORAMIC by the H rule on
+    n_e), `E`, `qvec`, `tvec`, F from E, `model` "F" with `model9` the pixel F of E.  Every other pair: exactly as without."""
     if not torch.cuda.is_available():
         raise _lib.HipLibraryError("geometric verification scores its hypotheses on the GPU (no CPU fallback)")
     results = [dict(config=CONFIG_DEGENERATE, inlier_matches=np.zeros((0, 2), np.uint32), F=np.zeros((3, 3)),
@@ -204,10 +237,32 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
         H = torch.nan_to_num(h9.to(torch.float64)).reshape(P, 3, 3).cpu().numpy()
         fmask, hmask, nf, nh = fmask.cpu().numpy(), hmask.cpu().numpy(), nf.cpu().numpy(), nh.cpu().numpy()
         f9_np, h9_np = f9.cpu().numpy(), h9.cpu().numpy()
+        cal = [] if cameras is None else [q for q, i in enumerate(sel) if cameras[1][pair_images[i][0]] and cameras[1][pair_images[i][1]]]
+        est_e = {}
+        if cal:
+            from .essential import MIN_E_F_INLIER_RATIO, choose_pose
+
+            est_e = _estimate_calibrated(cal, sel, pts_np, pair_images, pair_ids, cameras, device, max_error)
         for q, i in enumerate(sel):
             r = results[i]
             r["n_f"], r["n_h"] = int(nf[q]), int(nh[q])
-            if r["n_f"] < max(MIN_NUM_INLIERS, MIN_INLIER_RATIO * len(match_lists[i])):
+            floor = max(MIN_NUM_INLIERS, MIN_INLIER_RATIO * len(match_lists[i]))
+            e = est_e.get(q)
+            if e is not None:
+                r["n_e"] = e["n"]
+                if e["n"] >= floor and e["n"] >= MIN_E_F_INLIER_RATIO * r["n_f"]:      # the best model is E
+                    lo, hi = offs[q], offs[q + 1]
+                    r["E"], r["F"] = e["E"], _stored_f(e["f9"])
+                    r["H"] = H[q] / H[q][2, 2] if H[q][2, 2] != 0 else H[q]
+                    r["config"], mask, r["model"], r["model9"] = CONFIG_CALIBRATED, e["mask"], "F", e["f9"].copy()
+                    if r["n_h"] / e["n"] > MAX_H_INLIER_RATIO:
+                        r["config"] = CONFIG_PLANAR_OR_PANORAMIC
+                        if r["n_h"] > e["n"]:
+                            mask, r["model"], r["model9"] = hmask[lo:hi], "H", h9_np[q].copy()
+                    r["qvec"], r["tvec"] = choose_pose(e["E"], e["xn"][e["mask"]])
+                    r["inlier_matches"] = np.asarray(match_lists[i], np.uint32).reshape(-1, 2)[mask]
+                    continue
+            if r["n_f"] < floor:
                 continue
             r["F"] = F2[q]
             r["H"] = H[q] / H[q][2, 2] if H[q][2, 2] != 0 else H[q]
@@ -234,15 +289,20 @@ def read_keypoints_by_index(db, ids):
     return kps
 
 
-def verify_pair_lists(kps, ids, pairs, lists, device="cuda", verify_fn=None):
+def verify_pair_lists(kps, ids, pairs, lists, device="cuda", verify_fn=None, cameras=None):
     """This rank's share of the verification: pairs (P, 2) image indices with their match lists -> one result dict per
     pair (verify_pairs' format).  The sampler is seeded by the COLMAP pair id, so a pair's result does not depend on the
-    rank that verifies it.  `verify_fn(kps, pair_images, pair_ids, lists)` replaces verify_pairs in the CPU tests."""
+    rank that verifies it.  `verify_fn(kps, pair_images, pair_ids, lists)` replaces verify_pairs in the CPU tests.
+    `cameras` (verify_pairs' form) is handed on, to `verify_fn` as the keyword `cameras=`, only when some pair of this
+    share has a usable prior on both images."""
     pair_images = [(int(a), int(b)) for a, b in pairs]
     pids = [pair_id_of(ids[a], ids[b]) for a, b in pair_images]
+    if cameras is not None and not any(cameras[1][a] and cameras[1][b] for a, b in pair_images):
+        cameras = None
+    extra = {} if cameras is None else dict(cameras=cameras)
     if verify_fn is not None:
-        return verify_fn(kps, pair_images, pids, lists)
-    return verify_pairs(kps, pair_images, pids, lists, device=device)
+        return verify_fn(kps, pair_images, pids, lists, **extra)
+    return verify_pairs(kps, pair_images, pids, lists, device=device, **extra)
 
 
 def write_two_view_rows(db, ids, results) -> int:
@@ -251,7 +311,8 @@ def write_two_view_rows(db, ids, results) -> int:
     n_ok = 0
     for (a, b) in sorted(results):
         r = results[(a, b)]
-        db.write_two_view_geometry(ids[a], ids[b], r["inlier_matches"], r["config"], F=r["F"], H=r["H"], commit=False)
+        db.write_two_view_geometry(ids[a], ids[b], r["inlier_matches"], r["config"], F=r["F"], E=r.get("E"), H=r["H"],
+                                   qvec=r.get("qvec"), tvec=r.get("tvec"), commit=False)
         n_ok += r["config"] != CONFIG_DEGENERATE
     db.commit()
     return int(n_ok)
@@ -260,7 +321,9 @@ def write_two_view_rows(db, ids, results) -> int:
 def verify_database_pairs(db, ids, merged, device="cuda", verify_fn=None) -> int:
     """Single-process form: verify every matched pair of a database that is open for writing and write its rows.
     `merged`: {(a, b): uint32 (M, 2)} with a < b image indices into `ids`.  Returns the number of verified pairs."""
+    from .essential import camera_table
+
     pairs = sorted(merged)
     res = verify_pair_lists(read_keypoints_by_index(db, ids), ids, pairs, [merged[p] for p in pairs], device=device,
-                            verify_fn=verify_fn)
+                            verify_fn=verify_fn, cameras=camera_table(db, ids))
     return write_two_view_rows(db, ids, dict(zip(pairs, res)))

@@ -35,7 +35,8 @@ logger = logging.getLogger(__name__)
 
 def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn=None, matching_options=None,
                 match_fn=None, do_matching=True, verify=True, device="cuda", batch_size=50, verify_fn=None,
-                camera_params_for=default_camera_params, camera_per_image=False, guided_fn=None) -> dict:
+                camera_params_for=default_camera_params, camera_per_image=False, guided_fn=None,
+                prior_focal_length=False) -> dict:
     from ..database.colmap_db import ColmapDatabase
     from ..matching.exhaustive import (_guided_option, _sift_options, check_guided_block_size, hip_guided_blocks,
                                        hip_match_blocks, rematch_guided)
@@ -81,13 +82,19 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
     ids = None
     db = None
     err = None
+    cameras = None
     cnt = all_counts.cpu().numpy()
     kp_np = all_kps.cpu().numpy()
     if rank == 0:
         try:
-            camera_of = camera_policy(camera_model, camera_params, all_hw[0], camera_params_for, camera_per_image)
+            camera_of = camera_policy(camera_model, camera_params, all_hw[0], camera_params_for, camera_per_image,
+                                      prior_focal_length)
             db = ColmapDatabase(str(db_path))
             ids = [add_image_row(db, f.name, camera_of(h, w)) if h else None for f, (h, w) in zip(image_files, all_hw)]
+            if prior_focal_length:
+                from ..matching.essential import camera_table
+
+                cameras = camera_table(db.db, ids)                     # (K, usable prior) per file, read back from the rows
             d_np = all_desc.cpu().numpy()
             for k, image_id in enumerate(ids):
                 if image_id is not None and cnt[k] > 0:
@@ -105,6 +112,9 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
 
         ids = vd.broadcast_object(ids, 0)                                   # pair ids seed the verification sampler
         keep = np.nonzero(all_readable)[0]
+        if prior_focal_length:                                              # calibrated pairs
+            cameras = vd.broadcast_object(cameras, 0)
+            cameras = (cameras[0][keep], cameras[1][keep])
         m = len(keep)
         stats["pairs"] = m * (m - 1) // 2
         sift = _sift_options(matching_options, None)
@@ -124,7 +134,7 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
                 lists = match_fn(blocks.cpu().numpy(), bcounts.cpu().numpy(), my_pairs, r_, d_, c_)
             if verify:                                                          # every rank verifies the pairs it matched
                 kps = {i: kp_np[k, : cnt[k], :2] for i, k in enumerate(keep)}
-                results = verify_pair_lists(kps, kept_ids, my_pairs, lists, device=device, verify_fn=verify_fn)
+                results = verify_pair_lists(kps, kept_ids, my_pairs, lists, device=device, verify_fn=verify_fn, cameras=cameras)
                 if guided:                                                      # ... and re-matches them under their models
                     if guided_fn is None:
                         def guided_fn(blk, cts, kp_xy, prs, models, kinds, e, r, dmax, cc):

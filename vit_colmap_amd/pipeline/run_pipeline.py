@@ -64,6 +64,7 @@ class Pipeline:
         db_path.parent.mkdir(parents=True, exist_ok=True)
 
         extractor = self._make_extractor()
+        extractor.prior_focal_length = bool(self.config.camera.prior_focal_length)
         from .. import dist as vd
 
         if vd.is_distributed():
@@ -78,6 +79,7 @@ class Pipeline:
             self.last_stats = run_sharded(image_dir, db_path, camera_model, camera_params, feature_fn=extractor._run_batch,
                                           camera_params_for=extractor.camera_params_for,
                                           camera_per_image=extractor.camera_per_image,
+                                          prior_focal_length=extractor.prior_focal_length,
                                           matching_options=self.config.matching.to_matching_options(),
                                           do_matching=self.config.do_matching, device=str(getattr(extractor, "device", "cuda")))
             if vd.rank_world()[0] != 0:
@@ -150,6 +152,8 @@ def main() -> None:
     ap.add_argument("--output", type=Path, required=True)
     ap.add_argument("--db", type=Path, required=True)
     ap.add_argument("--camera-model", dest="camera_model", default="SIMPLE_PINHOLE")
+    ap.add_argument("--prior-focal-length", dest="prior_focal_length", action="store_true",
+                    help="mark the cameras as calibrated: pairs are also verified under an essential matrix")
     ap.add_argument("--extractor", choices=["vit", "trainable_vit", "hybrid", "sift", "colmap_sift", "dummy"], default="vit")
     ap.add_argument("--detector", choices=["sift", "fast", "gftt"], default="sift",
                     help="keypoint detector of --extractor hybrid (runs on the GPU)")

@@ -27,6 +27,7 @@ class CameraConfig:
     width: Optional[int] = None
     height: Optional[int] = None
     params: Optional[list[float]] = None
+    prior_focal_length: bool = False   # the intrinsics are trusted: pairs are also verified under E (not set by the reference)
 
     def get_default_params(self, width: int, height: int) -> list[float]:
         if self.params is not None:
@@ -135,6 +136,8 @@ class Config:
         config = cls()
         if hasattr(args, "camera_model"):
             config.camera.model = args.camera_model
+        if getattr(args, "prior_focal_length", False):
+            config.camera.prior_focal_length = True
         if hasattr(args, "extractor") and args.extractor:
             config.extractor.extractor_type = args.extractor
         elif hasattr(args, "use_colmap_sift") and args.use_colmap_sift:
