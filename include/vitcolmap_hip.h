@@ -163,6 +163,28 @@ int vc_essential_5pt(const double* pts_n, const int32_t* offsets, int n_pairs, c
                      double* out_E, int32_t* out_count, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Two-view relative pose: every inlier of every pair triangulated under each of the pair's
+ * (at most four) pose candidates (R, t), X2 = R X1 + t, in one launch.  float64 throughout, in the operation order of the
+ * specification tests/util_pose.py, so everything but the angle equals it bit for bit.
+ *   pts_n          [total][4] float64 (x1, y1, x2, y2): the pairs' INLIERS in normalised camera coordinates, concatenated
+ *   offsets        [n_pairs + 1] int32: pair p owns pts_n[offsets[p] .. offsets[p+1]); any number of inliers per pair
+ *   cand           [n_pairs][4][12] float64: R row-major, then t (unit norm); NaN in the first element: unused slot
+ *   out_front      [n_pairs][4] int32: points with finite positive depth in both cameras; 0 for an unused slot and for t = 0
+ *   out_best       [n_pairs] int32: the slot with most points in front, the lowest on ties
+ *   out_tri_angle  [n_pairs] float64: median over the best candidate's in-front points of the angle between the rays to
+ *                  the point from the two camera centres (rad; the mean of the two middle values for an even count; 0 for none)
+ *   out_points     [total][3] float64 or NULL: the midpoint of each inlier under the best candidate in camera-1 coordinates,
+ *                  NaN where it is not in front
+ *   workspace      vc_two_view_pose_workspace_bytes(n_pairs, total) bytes, 8-byte aligned: the angle keys of the pairs
+ *                  with more than 4096 inliers (smaller pairs keep them in LDS).  NULL only with workspace_bytes 0.  A pair
+ *                  whose keys the workspace cannot hold gets out_best -1, out_tri_angle NaN, out_points NaN.
+ * ------------------------------------------------------------------------------------------ */
+size_t vc_two_view_pose_workspace_bytes(int n_pairs, int total);
+int vc_two_view_pose(const double* pts_n, const int32_t* offsets, int n_pairs, const double* cand, int32_t* out_front,
+                     int32_t* out_best, double* out_tri_angle, double* out_points, void* workspace, size_t workspace_bytes,
+                     vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

@@ -8,6 +8,8 @@ With `verify=True` (default) the match lists are then geometrically verified (ma
 `two_view_geometries` rows written, as `match_exhaustive` does inside COLMAP.
 With the `guided_matching` option (off by default) every pair whose verification is not DEGENERATE is matched once more
 under its estimated F or H and that list replaces the pair's inlier matches.
+With the `compute_relative_pose` option (off by default) the verified pairs whose cameras have a focal-length prior get a
+pose and a triangulation angle, and PLANAR_OR_PANORAMIC is split into PLANAR and PANORAMIC.
 
 Multi-GPU (`distributed=True`, or automatically when a torch.distributed group with more than one rank exists):
 rank 0 reads the database and broadcasts the descriptor blocks, the pair list is dealt round-robin over the
@@ -41,6 +43,23 @@ def _guided_option(matching_options, sift_options) -> bool:
     """`guided_matching` of the options object: on the outer object (pycolmap 3.13) or on its SIFT options (3.12)."""
     opts = matching_options if matching_options is not None else sift_options
     return bool(getattr(opts, "guided_matching", False) or getattr(getattr(opts, "sift", None), "guided_matching", False))
+
+
+def _relative_pose_option(matching_options, sift_options) -> bool:
+    """`compute_relative_pose` of the options object, looked up where `guided_matching` is."""
+    opts = matching_options if matching_options is not None else sift_options
+    return bool(getattr(opts, "compute_relative_pose", False) or getattr(getattr(opts, "sift", None), "compute_relative_pose", False))
+
+
+def pose_stats(results) -> dict:
+    """The relative-pose totals of a run's results (an iterable of verify_pairs results)."""
+    from .two_view import CONFIG_PANORAMIC, CONFIG_PLANAR
+
+    posed = [r for r in results if "tri_angle" in r]
+    angles = [r["tri_angle"] for r in posed if r["config"] != CONFIG_PANORAMIC and r["n_front"] > 0]
+    return dict(pose_pairs=len(posed), planar_pairs=sum(r["config"] == CONFIG_PLANAR for r in posed),
+                panoramic_pairs=sum(r["config"] == CONFIG_PANORAMIC for r in posed),
+                median_tri_angle_deg=float(np.degrees(np.median(angles))) if angles else 0.0)
 
 
 def load_descriptor_blocks(db: SqliteColmapDatabase):
@@ -192,10 +211,14 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
     re-matches the non-degenerate pairs of its own share under their models and the lists replace those pairs'
     `inlier_matches` (rematch_guided); `matches`, `config`, F and H are untouched.  `guided_fn(block, counts, keypoints_xy,
     pairs, models, kinds, max_error, max_ratio, max_distance, cross_check) -> list of match lists` replaces
-    hip_guided_blocks in the CPU tests."""
+    hip_guided_blocks in the CPU tests.
+    Relative pose (the options' `compute_relative_pose`, off by default; needs `verify` and usable priors):
+    `verify_fn` then also gets the keyword `relative_pose=True`; the stats gain `pose_pairs`, `planar_pairs`,
+    `panoramic_pairs` and `median_tri_angle_deg` (over the posed pairs that are not PANORAMIC)."""
     sift = _sift_options(matching_options, sift_options)
     max_ratio, max_distance, cross_check = float(sift.max_ratio), float(sift.max_distance), bool(sift.cross_check)
     guided = _guided_option(matching_options, sift_options) and verify
+    relative_pose = _relative_pose_option(matching_options, sift_options) and verify
     if distributed is None:
         distributed = vd.is_distributed()
     if distributed and not vd.is_distributed():
@@ -231,6 +254,9 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
                 if verify and D != 0:
                     kp_arr, kp_cnt = _pack_keypoints(read_keypoints_by_index(db, ids), len(ids))
                     cam_k, cam_prior = camera_table(db, ids)               # focal-length priors
+                    if relative_pose and not cam_prior.any():
+                        logger.warning("compute_relative_pose is set and no camera has a usable focal-length prior: "
+                                       "it has no effect")
             except Exception as e:  # noqa: BLE001 - handed to every rank below
                 err = e
         if distributed:
@@ -247,7 +273,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
             raise err
         n = len(ids)
         stats = dict(images=n, pairs=n * (n - 1) // 2, matches=0, gpu_s=0.0, db_s=0.0, verified_pairs=0, ranks=world,
-                     guided_pairs=0)
+                     guided_pairs=0, pose_pairs=0, planar_pairs=0, panoramic_pairs=0, median_tri_angle_deg=0.0)
         if n < 2:
             return stats
         if guided and D != 0:
@@ -263,7 +289,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
                 if verify:                                                     # this rank verifies the pairs it matched
                     vdev = device if (verify_fn is not None or torch.cuda.is_available()) else "cpu"
                     results = verify_pair_lists(_unpack_keypoints(kp_arr, kp_cnt), ids, my_pairs, lists, device=vdev,
-                                                verify_fn=verify_fn, cameras=(cam_k, cam_prior))
+                                                verify_fn=verify_fn, cameras=(cam_k, cam_prior), relative_pose=relative_pose)
                     if guided:
                         rematch_guided(block, counts, kp_arr, my_pairs, results, max_ratio, max_distance, cross_check,
                                        guided_fn)
@@ -292,6 +318,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
                 if verified is not None:
                     stats["verified_pairs"] = write_two_view_rows(db, ids, verified)
                     stats["guided_pairs"] = sum(r["config"] != CONFIG_DEGENERATE for r in verified.values()) if guided else 0
+                    stats.update(pose_stats(verified.values()))
                 stats["db_s"] = time.perf_counter() - t2
             except Exception as e:  # noqa: BLE001
                 err = e

@@ -8,6 +8,7 @@ Where the work runs
   HIP     scoring of every hypothesis against every match of every pair, and the inlier masks
           (csrc/two_view.hip, vc_two_view_score / vc_two_view_inliers): O(pairs x hypotheses x matches);
           the five-point solver of the calibrated branch (csrc/essential.hip; matching/essential.py)
+          the triangulation behind the relative pose (csrc/pose.hip; matching/pose.py)
   torch   the minimal solvers: batched 8x8 linear systems (float64) for all pairs and hypotheses at once, the
           normal equations of the one refit, a 3x3 SVD per pair for the stored F — plumbing around the kernels
   host    gathering matched keypoints from the database, writing the rows (rank 0 only in a multi-GPU run)
@@ -194,9 +195,30 @@ def _estimate_calibrated(cal, sel, pts_np, pair_images, pair_ids, cameras, devic
             for j, q in enumerate(cal)}
 
 
+def _relative_poses(posed, sel, results, pair_images, cameras, est_e, device, max_error):
+    """Relative pose of the chunk's qualifying pairs `posed` [(position in `sel`, inlier mask)] as one batch (matching/pose.py):
+    a PLANAR_OR_PANORAMIC pair is decomposed from its H, any other from E where the best model is E, else from its F."""
+    from .pose import relative_poses
+
+    entries = []
+    for q, mask in posed:
+        r = results[sel[q]]
+        a, b = pair_images[sel[q]]
+        if r["config"] == CONFIG_PLANAR_OR_PANORAMIC:
+            kind, matrix = "H", r["H"]
+        elif "E" in r:
+            kind, matrix = "E", r["E"]
+        else:
+            kind, matrix = "F", np.asarray(r["model9"], np.float64).reshape(3, 3)
+        entries.append(dict(config=r["config"], kind=kind, matrix=matrix, K1=cameras[0][a], K2=cameras[0][b],
+                            xn=est_e[q]["xn"][mask]))
+    for (q, _), pose in zip(posed, relative_poses(entries, device, max_error)):
+        results[sel[q]].update(pose)
+
+
 @torch.no_grad()
 def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", num_f=NUM_HYP_F, num_h=NUM_HYP_H,
-                 max_error=MAX_ERROR, chunk_pairs: int = 1024, cameras=None):
+                 max_error=MAX_ERROR, chunk_pairs: int = 1024, cameras=None, relative_pose=False):
     """keypoints: dict image index -> float32 (N, >= 2); pair_images: list of (a, b); pair_ids: COLMAP pair ids;
     match_lists: list of uint32 (M, 2).  -> list of dict(config, inlier_matches, F, H, n_f, n_h), one per pair.
     A result that is not DEGENERATE also carries the model whose mask produced `inlier_matches` — `model` ("F" or "H") and
@@ -204,7 +226,11 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
     `cameras`: None, or (K float64 (n, 3, 3), prior (n,)) indexed like `keypoints` (essential.camera_table).  A pair whose
     two images have a usable focal-length prior also gets an essential-matrix estimate (`n_e`); where it reaches
     max(15, 0.25 M) and 0.95 n_f inliers the best model is E: config CALIBRATED (or PLANAR_OR_PANORAMIC by the H rule on
-    n_e), `E`, `qvec`, `tvec`, F from E, `model` "F" with `model9` the pixel F of E.  Every other pair: exactly as without."""
+    n_e), `E`, `qvec`, `tvec`, F from E, `model` "F" with `model9` the pixel F of E.  Every other pair: exactly as without.
+    `relative_pose` (needs `cameras`): every pair with two usable priors that is not DEGENERATE gets `qvec`,
+    `tvec`, `tri_angle` (rad) and `n_front` from the triangulation of its inliers under the pose candidates of its model
+    (matching/pose.py), and PLANAR_OR_PANORAMIC becomes PLANAR or PANORAMIC; E, F, H, `inlier_matches`, `model` and `model9`
+    are as without."""
     if not torch.cuda.is_available():
         raise _lib.HipLibraryError("geometric verification scores its hypotheses on the GPU (no CPU fallback)")
     results = [dict(config=CONFIG_DEGENERATE, inlier_matches=np.zeros((0, 2), np.uint32), F=np.zeros((3, 3)),
@@ -238,7 +264,7 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
         fmask, hmask, nf, nh = fmask.cpu().numpy(), hmask.cpu().numpy(), nf.cpu().numpy(), nh.cpu().numpy()
         f9_np, h9_np = f9.cpu().numpy(), h9.cpu().numpy()
         cal = [] if cameras is None else [q for q, i in enumerate(sel) if cameras[1][pair_images[i][0]] and cameras[1][pair_images[i][1]]]
-        est_e = {}
+        est_e, posed = {}, []
         if cal:
             from .essential import MIN_E_F_INLIER_RATIO, choose_pose
 
@@ -259,7 +285,10 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
                         r["config"] = CONFIG_PLANAR_OR_PANORAMIC
                         if r["n_h"] > e["n"]:
                             mask, r["model"], r["model9"] = hmask[lo:hi], "H", h9_np[q].copy()
-                    r["qvec"], r["tvec"] = choose_pose(e["E"], e["xn"][e["mask"]])
+                    if relative_pose:
+                        posed.append((q, mask))
+                    else:
+                        r["qvec"], r["tvec"] = choose_pose(e["E"], e["xn"][e["mask"]])
                     r["inlier_matches"] = np.asarray(match_lists[i], np.uint32).reshape(-1, 2)[mask]
                     continue
             if r["n_f"] < floor:
@@ -277,6 +306,10 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
                 r["model"] = "F"
             r["model9"] = (h9_np if r["model"] == "H" else f9_np)[q].copy()
             r["inlier_matches"] = np.asarray(match_lists[i], np.uint32).reshape(-1, 2)[mask]
+            if relative_pose and e is not None:
+                posed.append((q, mask))
+        if posed:
+            _relative_poses(posed, sel, results, pair_images, cameras, est_e, device, max_error)
     return results
 
 
@@ -289,17 +322,20 @@ def read_keypoints_by_index(db, ids):
     return kps
 
 
-def verify_pair_lists(kps, ids, pairs, lists, device="cuda", verify_fn=None, cameras=None):
+def verify_pair_lists(kps, ids, pairs, lists, device="cuda", verify_fn=None, cameras=None, relative_pose=False):
     """This rank's share of the verification: pairs (P, 2) image indices with their match lists -> one result dict per
     pair (verify_pairs' format).  The sampler is seeded by the COLMAP pair id, so a pair's result does not depend on the
     rank that verifies it.  `verify_fn(kps, pair_images, pair_ids, lists)` replaces verify_pairs in the CPU tests.
     `cameras` (verify_pairs' form) is handed on, to `verify_fn` as the keyword `cameras=`, only when some pair of this
-    share has a usable prior on both images."""
+    share has a usable prior on both images; `relative_pose=True` likewise, only when the option is on and
+    the cameras are handed on."""
     pair_images = [(int(a), int(b)) for a, b in pairs]
     pids = [pair_id_of(ids[a], ids[b]) for a, b in pair_images]
     if cameras is not None and not any(cameras[1][a] and cameras[1][b] for a, b in pair_images):
         cameras = None
     extra = {} if cameras is None else dict(cameras=cameras)
+    if relative_pose and cameras is not None:
+        extra["relative_pose"] = True
     if verify_fn is not None:
         return verify_fn(kps, pair_images, pids, lists, **extra)
     return verify_pairs(kps, pair_images, pids, lists, device=device, **extra)

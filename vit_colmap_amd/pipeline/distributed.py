@@ -38,8 +38,8 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
                 camera_params_for=default_camera_params, camera_per_image=False, guided_fn=None,
                 prior_focal_length=False) -> dict:
     from ..database.colmap_db import ColmapDatabase
-    from ..matching.exhaustive import (_guided_option, _sift_options, check_guided_block_size, hip_guided_blocks,
-                                       hip_match_blocks, rematch_guided)
+    from ..matching.exhaustive import (_guided_option, _relative_pose_option, _sift_options, check_guided_block_size,
+                                       hip_guided_blocks, hip_match_blocks, rematch_guided)
 
     rank, world = vd.rank_world()
     image_files = list_images(Path(image_dir))
@@ -134,7 +134,8 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
                 lists = match_fn(blocks.cpu().numpy(), bcounts.cpu().numpy(), my_pairs, r_, d_, c_)
             if verify:                                                          # every rank verifies the pairs it matched
                 kps = {i: kp_np[k, : cnt[k], :2] for i, k in enumerate(keep)}
-                results = verify_pair_lists(kps, kept_ids, my_pairs, lists, device=device, verify_fn=verify_fn, cameras=cameras)
+                results = verify_pair_lists(kps, kept_ids, my_pairs, lists, device=device, verify_fn=verify_fn, cameras=cameras,
+                                            relative_pose=_relative_pose_option(matching_options, None))
                 if guided:                                                      # ... and re-matches them under their models
                     if guided_fn is None:
                         def guided_fn(blk, cts, kp_xy, prs, models, kinds, e, r, dmax, cc):

@@ -161,6 +161,9 @@ def main() -> None:
     ap.add_argument("--skip-matching", dest="skip_matching", action="store_true")
     ap.add_argument("--guided-matching", dest="guided_matching", action="store_true",
                     help="re-match every verified pair under its estimated F or H (COLMAP's guided_matching)")
+    ap.add_argument("--relative-pose", dest="relative_pose", action="store_true",
+                    help="pose, triangulation angle and the PLANAR / PANORAMIC split of the pairs whose cameras have a "
+                         "focal-length prior (COLMAP's compute_relative_pose)")
     ap.add_argument("--skip-reconstruction", dest="skip_reconstruction", action="store_true")
     ap.add_argument("--dataset", default=None)
     ap.add_argument("--scene", default=None)

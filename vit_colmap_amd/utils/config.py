@@ -50,6 +50,7 @@ class SiftMatchingOptions:
     use_gpu: bool = True
     num_threads: int = -1
     guided_matching: bool = False   # pycolmap 3.12 keeps the option here [recalled]
+    compute_relative_pose: bool = False   # carried as guided_matching is (COLMAP: TwoViewGeometryOptions [recalled])
 
 
 @dataclass
@@ -59,6 +60,7 @@ class FeatureMatchingOptions:
     use_gpu: bool = True
     num_threads: int = -1
     guided_matching: bool = False   # pycolmap 3.13 moved the option to the outer object [recalled]
+    compute_relative_pose: bool = False
     sift: SiftMatchingOptions = field(default_factory=SiftMatchingOptions)
 
 
@@ -72,22 +74,26 @@ class MatchingConfig:
     cross_check: bool = True
     num_threads: int = -1  # -1 means auto-detect
     guided_matching: bool = False  # re-match verified pairs under their F or H model (not set by the reference)
+    compute_relative_pose: bool = False  # pose, triangulation angle, PLANAR / PANORAMIC of the pairs with priors (not set by it)
 
     def to_matching_options(self) -> FeatureMatchingOptions:
         opts = FeatureMatchingOptions(use_gpu=self.use_gpu, num_threads=self.num_threads,
-                                      guided_matching=self.guided_matching)
+                                      guided_matching=self.guided_matching,
+                                      compute_relative_pose=self.compute_relative_pose)
         opts.sift.max_ratio = self.max_ratio
         opts.sift.max_distance = self.max_distance
         opts.sift.cross_check = self.cross_check
         opts.sift.use_gpu = self.use_gpu
         opts.sift.num_threads = self.num_threads
         opts.sift.guided_matching = self.guided_matching
+        opts.sift.compute_relative_pose = self.compute_relative_pose
         return opts
 
     def _to_sift_options_legacy(self) -> SiftMatchingOptions:
         return SiftMatchingOptions(max_ratio=self.max_ratio, max_distance=self.max_distance,
                                    cross_check=self.cross_check, use_gpu=self.use_gpu,
-                                   num_threads=self.num_threads, guided_matching=self.guided_matching)
+                                   num_threads=self.num_threads, guided_matching=self.guided_matching,
+                                   compute_relative_pose=self.compute_relative_pose)
 
 
 @dataclass
@@ -152,6 +158,8 @@ class Config:
             config.matching.use_gpu = args.use_gpu
         if getattr(args, "guided_matching", False):
             config.matching.guided_matching = True
+        if getattr(args, "relative_pose", False):
+            config.matching.compute_relative_pose = True
         if hasattr(args, "skip_matching"):
             config.do_matching = not args.skip_matching
         if hasattr(args, "skip_reconstruction"):
