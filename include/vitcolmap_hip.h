@@ -37,6 +37,7 @@ extern "C" {
 
 #define VC_MAX_KEYPOINTS 2048 /* rows per image the matcher kernels accept                  */
 #define VC_MAX_DESC_DIM 1024  /* descriptor bytes per row (255^2 * D must stay below 2^26)  */
+#define VC_MAX_NEIGHBOURS 64  /* neighbours per image the retrieval search returns          */
 
 typedef void* vc_stream_t;
 
@@ -118,6 +119,37 @@ int vc_mutual_ratio(const int32_t* idx12, const int32_t* best12, const int32_t* 
                     const int32_t* idx21, const int32_t* best21, const int32_t* second21, int n2,
                     float max_ratio, float max_distance, int cross_check, uint32_t* out_pairs,
                     int32_t* out_count, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Retrieval matching: the two device steps that choose WHICH image pairs are matched, in place
+ * of all n (n - 1) / 2 — the build's own published rule (COLMAP's vocabulary-tree matcher and hloc's pairs-from-retrieval
+ * play this part there; parity with either is not claimed).  Specification: tests/util_retrieval.py.  All integer, so
+ * the neighbour lists equal the specification bit for bit on every device and rank.
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * Pooling: out_sums[i][c] = sum over the rows r < counts[i] of desc[i][r][c], int32 (at most 255 * 2048).
+ * desc [n_images][n_max][d] uint8, counts [n_images] int32 (values outside 0..n_max are clamped to it),
+ * out_sums [n_images][d] int32, overwritten.  One read of the blocks, several workgroups per image.
+ * Limits: 1 <= n_max <= VC_MAX_KEYPOINTS, 1 <= d <= VC_MAX_DESC_DIM (VC_ERR_UNSUPPORTED above).
+ */
+int vc_pool_descriptors_u8(const uint8_t* desc, const int32_t* counts, int n_images, int n_max, int d,
+                           int32_t* out_sums, vc_stream_t stream);
+
+/*
+ * Nearest images: score[i][j] = sum over c of q[i][c] q[j][c] in int32 (v_mfma_i32_32x32x32_i8); for every row i with
+ * valid[i] != 0 the k best j != i with valid[j] != 0, by score descending, then index ascending.
+ *   q          [n][d_pad] int8, 16-byte aligned; d_pad % 32 == 0 (pad the columns with zeros), d_pad <= VC_MAX_DESC_DIM
+ *   valid      [n] int32
+ *   out_idx    [n][k] int32: the neighbours in rank order; -1 behind the last candidate and in every slot of an invalid row
+ *   out_score  [n][k] int32: their scores; INT32_MIN wherever out_idx is -1
+ *   workspace  vc_retrieval_workspace_bytes(n, d_pad, k) bytes, 8-byte aligned: at most 16 n k 8-byte keys, never n x n
+ *              (VC_ERR_WORKSPACE when shorter; the query returns 0 for a shape the entry refuses)
+ * Limits: 1 <= k <= VC_MAX_NEIGHBOURS, n <= 2^20, d_pad <= VC_MAX_DESC_DIM: VC_ERR_UNSUPPORTED beyond.
+ */
+size_t vc_retrieval_workspace_bytes(int n, int d_pad, int k);
+int vc_retrieval_topk_i8(const int8_t* q, const int32_t* valid, int n, int d_pad, int k, int32_t* out_idx,
+                         int32_t* out_score, void* workspace, size_t workspace_bytes, vc_stream_t stream);
 
 /* Test hooks: out[s] = theta(s) = angle assigned to integer similarity s, for s in [0, n).
  * vc_theta_table reads the table the pair kernel's acceptance tests use (generated at build time by

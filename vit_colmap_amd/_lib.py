@@ -15,6 +15,8 @@ VC_OK = 0
 ABI_VERSION = 1
 VC_MAX_KEYPOINTS = 2048
 VC_MAX_DESC_DIM = 1024
+VC_MAX_NEIGHBOURS = 64
+VC_ERR_INVALID_ARG, VC_ERR_UNSUPPORTED, VC_ERR_LAUNCH, VC_ERR_WORKSPACE = -1, -2, -3, -4
 
 
 class HipLibraryError(RuntimeError):
@@ -39,6 +41,9 @@ SIGNATURES = {
                                c_void_p, c_size_t, c_void_p]),
     "vc_mutual_ratio": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                 c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "vc_pool_descriptors_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vc_retrieval_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vc_retrieval_topk_i8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vc_theta_table": (c_int, [c_void_p, c_int, c_void_p]),
     "vc_theta_eval": (c_int, [c_void_p, c_int, c_void_p]),
     "vc_two_view_score": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),

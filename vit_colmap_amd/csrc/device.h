@@ -1,9 +1,14 @@
-// Shared device-side idioms of the kernels: LDS-DMA issue, the wave-uniform LDS base and bf16 bit conversions.
+// Shared device-side idioms of the kernels: the int8 MFMA register types, LDS-DMA issue, the wave-uniform LDS base and bf16 bit conversions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace vc {
+
+// Operand and accumulator registers of v_mfma_i32_32x32x32_i8: lane 32 h + c holds 16 operand bytes [32 kk + 16 h, +16) of
+// row c at k-step kk, and accumulator element 4 q + i is row 8 q + 4 h + i against column c.
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
 
 // LDS-DMA (global_load_lds): each lane copies 16 (or 4) bytes from its own global address to LDS at the wave-uniform
 // byte address `lds_dst` + lane * 16 (or 4).  M0 holds the LDS destination; the compiler reserves it and does not

@@ -31,8 +31,8 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+using vc::v16i;
+using vc::v4i;
 typedef unsigned int u32;
 
 constexpr int kWaves = 8;                    // waves per workgroup: one workgroup per CU

@@ -46,6 +46,12 @@ def pairs_for_rank(n_images: int, rank: int, world: int) -> np.ndarray:
     return np.stack([a[sel], b[sel]], axis=1).astype(np.int32)
 
 
+def listed_pairs_for_rank(pairs, rank: int, world: int) -> np.ndarray:
+    """Rows p of a given pair list (P, 2) with p % world == rank; int32 (P_r, 2).  The deal of pairs_for_rank for a list
+    that is not the exhaustive one (retrieval matching: the same list on every rank, broadcast by rank 0)."""
+    return np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2)[rank::world])
+
+
 def pair_index(n_images: int, a, b):
     """Position of pair (a < b) in the row-major exhaustive list."""
     a = np.asarray(a, np.int64)

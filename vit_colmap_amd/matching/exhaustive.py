@@ -215,6 +215,18 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
     Relative pose (the options' `compute_relative_pose`, off by default; needs `verify` and usable priors):
     `verify_fn` then also gets the keyword `relative_pose=True`; the stats gain `pose_pairs`, `planar_pairs`,
     `panoramic_pairs` and `median_tri_angle_deg` (over the posed pairs that are not PANORAMIC)."""
+    return match_database(database_path, matching_options, sift_options, device, pair_chunk, distributed, match_fn, verify,
+                          verify_fn, guided_fn)
+
+
+def match_database(database_path, matching_options, sift_options, device, pair_chunk, distributed, match_fn, verify,
+                   verify_fn, guided_fn, select_pairs=None, what="match_exhaustive") -> dict:
+    """The database-in / database-out body that match_exhaustive and matching.retrieval.match_retrieval share; they differ
+    only in where the pair list comes from.  `select_pairs` None: every pair (a < b), dealt to the ranks by
+    dist.pairs_for_rank.  Otherwise rank 0 calls `select_pairs(block, counts, stats)` once the descriptor blocks are
+    loaded -> int32 (P, 2) image-index pairs, a < b, ascending (a sub-sequence of the exhaustive list; it may add keys
+    to `stats`); the list is broadcast, pair p goes to rank p % world (dist.listed_pairs_for_rank), and only the listed
+    pairs are matched, verified and written."""
     sift = _sift_options(matching_options, sift_options)
     max_ratio, max_distance, cross_check = float(sift.max_ratio), float(sift.max_distance), bool(sift.cross_check)
     guided = _guided_option(matching_options, sift_options) and verify
@@ -226,7 +238,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
     rank, world = vd.rank_world() if distributed else (0, 1)
     if match_fn is None:
         if not torch.cuda.is_available():
-            raise _lib.HipLibraryError("match_exhaustive needs an MI355X: the matcher is HIP-only (no CPU fallback)")
+            raise _lib.HipLibraryError(f"{what} needs an MI355X: the matcher is HIP-only (no CPU fallback)")
 
         def match_fn(block, counts, pairs, r, dmax, cc):
             return hip_match_blocks(block, counts, pairs, r, dmax, cc, device=device, pair_chunk=pair_chunk)
@@ -278,12 +290,30 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
             return stats
         if guided and D != 0:
             check_guided_block_size(int(np.asarray(block).shape[1]))           # before any matching starts, on every rank
-        my_pairs = vd.pairs_for_rank(n, rank, world)
+        if select_pairs is None:
+            all_pairs = exhaustive_pairs(n).numpy()
+            my_pairs = vd.pairs_for_rank(n, rank, world)
+        else:
+            err = all_pairs = None
+            if rank == 0:
+                try:
+                    all_pairs = np.ascontiguousarray(select_pairs(block, counts, stats), np.int32).reshape(-1, 2)
+                except Exception as e:  # noqa: BLE001 - handed to every rank below
+                    err = e
+            if distributed:
+                vd.raise_if_any_failed(err, "selecting the pairs")
+                all_pairs = vd.broadcast_array(all_pairs, 0, device)
+            elif err is not None:
+                raise err
+            my_pairs = vd.listed_pairs_for_rank(all_pairs, rank, world)
+            stats["pairs"] = len(all_pairs)
         t1 = time.perf_counter()
         err, lists, results = None, [], None
         try:
             if D == 0:
                 lists = [np.zeros((0, 2), np.uint32) for _ in my_pairs]      # no descriptors anywhere: every pair is empty
+            elif select_pairs is not None and len(my_pairs) == 0:
+                results = [] if verify else None                               # nothing selected fell to this rank
             else:
                 lists = match_fn(block, counts, my_pairs, max_ratio, max_distance, cross_check)
                 if verify:                                                     # this rank verifies the pairs it matched
@@ -310,7 +340,7 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
         if rank == 0:
             try:
                 t2 = time.perf_counter()
-                for a, b in exhaustive_pairs(n).numpy():                       # COLMAP's pair order, whatever rank matched it
+                for a, b in all_pairs:                                         # COLMAP's pair order, whatever rank matched it
                     m = merged[(int(a), int(b))]
                     db.write_matches(ids[a], ids[b], m, commit=False)
                     stats["matches"] += len(m)

@@ -36,11 +36,15 @@ logger = logging.getLogger(__name__)
 def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn=None, matching_options=None,
                 match_fn=None, do_matching=True, verify=True, device="cuda", batch_size=50, verify_fn=None,
                 camera_params_for=default_camera_params, camera_per_image=False, guided_fn=None,
-                prior_focal_length=False) -> dict:
+                prior_focal_length=False, matcher_type="exhaustive") -> dict:
     from ..database.colmap_db import ColmapDatabase
     from ..matching.exhaustive import (_guided_option, _relative_pose_option, _sift_options, check_guided_block_size,
                                        hip_guided_blocks, hip_match_blocks, rematch_guided)
 
+    if matcher_type != "exhaustive":
+        # the in-memory path matches every pair; the choice of pairs exists database to database only
+        raise ValueError(f"the sharded in-memory pipeline matches exhaustively: for matcher_type {matcher_type!r} extract to "
+                         "the database first and call matching.match_retrieval on it (it runs multi-rank as well)")
     rank, world = vd.rank_world()
     image_files = list_images(Path(image_dir))
     if not image_files:

@@ -18,6 +18,8 @@ from ..utils.config import Config
 
 logger = logging.getLogger(__name__)
 
+MATCHER_TYPES = ("exhaustive", "retrieval")   # MatchingConfig.matcher_type / --matcher
+
 
 class Pipeline:
     def __init__(self, config: Optional[Config] = None):
@@ -63,6 +65,12 @@ class Pipeline:
         output_dir.mkdir(parents=True, exist_ok=True)
         db_path.parent.mkdir(parents=True, exist_ok=True)
 
+        matcher_type, num_neighbors = self.config.matching.matcher_type, self.config.matching.num_neighbors
+        if matcher_type not in MATCHER_TYPES:
+            raise ValueError(f"unknown matcher_type {matcher_type!r}: expected one of {', '.join(MATCHER_TYPES)}")
+        if matcher_type == "retrieval" and int(num_neighbors) < 1:
+            raise ValueError(f"num_neighbors must be at least 1 (got {num_neighbors})")
+
         extractor = self._make_extractor()
         extractor.prior_focal_length = bool(self.config.camera.prior_focal_length)
         from .. import dist as vd
@@ -81,7 +89,8 @@ class Pipeline:
                                           camera_per_image=extractor.camera_per_image,
                                           prior_focal_length=extractor.prior_focal_length,
                                           matching_options=self.config.matching.to_matching_options(),
-                                          do_matching=self.config.do_matching, device=str(getattr(extractor, "device", "cuda")))
+                                          do_matching=self.config.do_matching, device=str(getattr(extractor, "device", "cuda")),
+                                          matcher_type=matcher_type)
             if vd.rank_world()[0] != 0:
                 return None
         else:
@@ -92,11 +101,15 @@ class Pipeline:
                 logger.info(f"Extracted features for {num_imgs} images")
 
             if self.config.do_matching:
-                from ..matching import match_exhaustive
+                from ..matching import match_exhaustive, match_retrieval
 
                 logger.info("Running feature matching...")
                 opts = self.config.matching.to_matching_options()
-                self.last_stats = match_exhaustive(database_path=str(db_path), matching_options=opts)
+                if matcher_type == "retrieval":
+                    self.last_stats = match_retrieval(database_path=str(db_path), matching_options=opts,
+                                                      num_neighbors=num_neighbors)
+                else:
+                    self.last_stats = match_exhaustive(database_path=str(db_path), matching_options=opts)
         if self.config.do_matching:
             with ColmapDatabase.open_database(str(db_path)) as db_check:
                 num_pairs = ColmapDatabase.get_db_count(db_check, "num_matched_image_pairs")
@@ -164,6 +177,10 @@ def main() -> None:
     ap.add_argument("--relative-pose", dest="relative_pose", action="store_true",
                     help="pose, triangulation angle and the PLANAR / PANORAMIC split of the pairs whose cameras have a "
                          "focal-length prior (COLMAP's compute_relative_pose)")
+    ap.add_argument("--matcher", choices=list(MATCHER_TYPES), default="exhaustive",
+                    help="exhaustive: every image pair; retrieval: each image against its --num-neighbors nearest images")
+    ap.add_argument("--num-neighbors", dest="num_neighbors", type=int, default=20,
+                    help="images per image that --matcher retrieval matches (at most 64)")
     ap.add_argument("--skip-reconstruction", dest="skip_reconstruction", action="store_true")
     ap.add_argument("--dataset", default=None)
     ap.add_argument("--scene", default=None)

@@ -75,6 +75,8 @@ class MatchingConfig:
     num_threads: int = -1  # -1 means auto-detect
     guided_matching: bool = False  # re-match verified pairs under their F or H model (not set by the reference)
     compute_relative_pose: bool = False  # pose, triangulation angle, PLANAR / PANORAMIC of the pairs with priors (not set by it)
+    matcher_type: str = "exhaustive"  # "exhaustive": every pair; "retrieval": each image against its nearest images only
+    num_neighbors: int = 20  # images per image that matcher_type "retrieval" matches (at most VC_MAX_NEIGHBOURS)
 
     def to_matching_options(self) -> FeatureMatchingOptions:
         opts = FeatureMatchingOptions(use_gpu=self.use_gpu, num_threads=self.num_threads,
@@ -160,6 +162,10 @@ class Config:
             config.matching.guided_matching = True
         if getattr(args, "relative_pose", False):
             config.matching.compute_relative_pose = True
+        if getattr(args, "matcher", None):
+            config.matching.matcher_type = args.matcher
+        if getattr(args, "num_neighbors", None) is not None:
+            config.matching.num_neighbors = args.num_neighbors
         if hasattr(args, "skip_matching"):
             config.do_matching = not args.skip_matching
         if hasattr(args, "skip_reconstruction"):
