@@ -177,6 +177,50 @@ def test_flag_reaches_camera_policy_and_the_command_line(monkeypatch, tmp_path):
     assert seen == [False, True]
 
 
+# ---- the rule on the counts alone ---------------------------------------------------------------------------------------------
+def _spec_decision(monkeypatch, M, n_f, n_h, n_e):
+    """The specification's rule for one pair whose estimators are replaced by given inlier counts: F and E keep the first
+    n rows of the match list, H the last n_h -> (verify_pair_calibrated's result, the matches)."""
+    first, last = (lambda n: np.arange(M) < n), (lambda n: np.arange(M) >= M - n)
+    eye9 = np.eye(3, dtype=np.float32).reshape(9)
+    monkeypatch.setattr(tv, "estimate_model", lambda kind, pts, seed, n_hyp: (eye9, first(n_f) if kind == "F" else last(n_h)))
+    monkeypatch.setattr(ue, "estimate_e", lambda pts, seed, K1, K2, n_hyp, perturb: (ue.true_essential(), eye9, first(n_e)))
+    kp = (np.random.RandomState(M).rand(M, 2) * 400).astype(np.float32)
+    m = np.stack([np.arange(M), np.arange(M)], axis=1).astype(np.uint32)
+    cams = [pinhole(flag=n_e is not None)] * 2
+    return ue.verify_pair_calibrated(kp, kp + np.float32(1.0), m, PAIR_ID, *cams), m
+
+
+def test_pair_decision_is_the_specifications_rule_on_both_sides_of_every_threshold(monkeypatch):
+    """two_view.pair_decision against util_essential.verify_pair_calibrated (and, without a prior, the oracle's verify_pair)
+    for M = 40 (floor 15) and M = 100 (floor 0.25 M = 25): n_f and n_e one below and at the floor, n_e one below and at
+    0.95 n_f (37 | 38 of 40, 94 | 95 of 100), n_h at and one above 0.8 n (20 | 21 of 25, 32 | 33 of 40, 80 | 81 of 100) and
+    at and one above n; n_e absent included."""
+    from vit_colmap_amd.matching.two_view import pair_decision
+
+    seen = set()
+    for M in (40, 100):
+        for n_f in (14, 15, 24, 25, 40, 100):
+            for n_e in (None, 14, 15, 24, 25, 37, 38, 40, 94, 95, 100):
+                for n_h in (0, 15, 16, 20, 21, 25, 26, 32, 33, 40, 41, 80, 81, 100):
+                    if max(n_f, n_h, n_e or 0) > M:
+                        continue
+                    res, m = _spec_decision(monkeypatch, M, n_f, n_h, n_e)
+                    config, best, model = pair_decision(M, n_f, n_h, n_e)
+                    assert config == res["config"], (M, n_f, n_h, n_e)
+                    assert (best == "E") == ("E" in res) and (best is None) == (config == tv.CONFIG_DEGENERATE), (M, n_f, n_h, n_e)
+                    if best is None:
+                        assert model is None and len(res["inlier_matches"]) == 0
+                        continue
+                    n = n_e if best == "E" else n_f
+                    mask = np.arange(M) >= M - n_h if model == "H" else np.arange(M) < n
+                    assert np.array_equal(res["inlier_matches"], m[mask]), (M, n_f, n_h, n_e)
+                    assert res.get("model", model) == model
+                    seen.add((config, best, model))
+    assert seen == {(c, b, k) for b, c0 in (("E", tv.CONFIG_CALIBRATED), ("F", tv.CONFIG_UNCALIBRATED))
+                    for c, k in ((c0, "F"), (tv.CONFIG_PLANAR_OR_PANORAMIC, "F"), (tv.CONFIG_PLANAR_OR_PANORAMIC, "H"))}
+
+
 # ---- match_exhaustive with the specification in the seams ------------------------------------------------------------------------
 def make_calibrated_db(path, flag=True, n=160):
     """Three views of one scene (view 3: view 2 again, so pair (1, 3) is pair (1, 2) with another seed) with descriptors

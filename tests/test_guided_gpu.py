@@ -1,6 +1,8 @@
 """GPU parity of guided matching: vc_match_pairs_guided_u8 against the numpy specification of
 tests/util_guided.py — bit-equal, no tolerance — then against the unguided matcher where the model admits every
 candidate, and end to end behind verify_pairs and match_exhaustive."""
+from functools import lru_cache
+
 import numpy as np
 import pytest
 import torch
@@ -195,6 +197,46 @@ def test_verify_pairs_then_guided_equals_the_spec_fed_the_gpus_model():
         assert np.array_equal(got[p], ref), p
         assert set(map(tuple, r["inlier_matches"])) <= set(map(tuple, got[p])), p     # guided ⊇ the verifier's inliers
         assert sum(1 for i, j in got[p] if i == j and twins[p][i]) >= 0.9 * twins[p].sum(), p
+
+
+@lru_cache(maxsize=None)
+def three_pairs():
+    """Three scenes of at most 300 keypoints, D = 128, as one block of six images: pair p is images (2p, 2p + 1) under the
+    specification's own F, H, F -> images, (desc, counts, kps), pairs, models, kinds."""
+    images, models = [], []
+    for kind, (seed, n, n_unique, planar) in zip("FHF", [(40, 300, 140, False), (41, 300, 140, True), (43, 200, 60, False)]):
+        kp1, kp2, d1, d2, _, f9, h9 = scene_models(seed, n, n_unique, planar)
+        images += [(kp1, d1), (kp2, d2)]
+        models.append(f9 if kind == "F" else h9)
+    return images, blocks(images), np.array([[0, 1], [2, 3], [4, 5]], np.int32), np.stack(models), list("FHF")
+
+
+def test_hip_guided_blocks_in_two_launches_equals_one_launch_and_the_spec():
+    """pair_chunk = 2: three pairs in two launches, the second of a single pair."""
+    from vit_colmap_amd.matching.exhaustive import hip_guided_blocks
+
+    images, (desc, counts, kps), pairs, models, kinds = three_pairs()
+    two = hip_guided_blocks(desc, counts, kps, pairs, models, kinds, tv.MAX_ERROR, pair_chunk=2)
+    one = hip_guided_blocks(desc, counts, kps, pairs, models, kinds, tv.MAX_ERROR, pair_chunk=16384)
+    assert len(two) == len(one) == 3
+    for p, (a, b) in enumerate(pairs):
+        ref = guided_match_pair(images[a][1], images[b][1], images[a][0], images[b][0], kinds[p], models[p], tv.MAX_ERROR)
+        assert len(ref) > 150 and two[p].dtype == np.uint32
+        assert np.array_equal(two[p], one[p]) and np.array_equal(two[p], ref), p
+
+
+def test_hip_match_blocks_takes_device_tensors_and_host_arrays_alike():
+    """The upload and unpack paths that the unguided and the guided function share, in two launches."""
+    from vit_colmap_amd.matching.exhaustive import hip_match_blocks
+
+    images, (desc, counts, _), pairs, _, _ = three_pairs()
+    from_device = hip_match_blocks(dev(desc), dev(counts), pairs, pair_chunk=2)
+    from_host = hip_match_blocks(desc, counts, pairs, pair_chunk=2)
+    assert len(from_device) == len(from_host) == 3
+    for p, (a, b) in enumerate(pairs):
+        ref = mo.match_pair(images[a][1], images[b][1])
+        assert len(ref) > 50 and from_device[p].dtype == np.uint32
+        assert np.array_equal(from_device[p], from_host[p]) and np.array_equal(from_device[p], ref), p
 
 
 def test_match_exhaustive_with_and_without_the_flag(tmp_path):

@@ -112,36 +112,20 @@ def broadcast_array(arr, src: int = 0, device=None):
     return t.cpu().numpy().view(np.dtype(dtype)).reshape(shape)
 
 
-def gather_pair_lists(pairs: np.ndarray, lists, dst: int = 0):
-    """Variable-length gather of (pair, match list) results to `dst` (host arrays; small).
-    Returns on dst a dict {(a, b): uint32 (M, 2)} over all ranks' pairs, elsewhere None."""
-    if not is_distributed():
-        return {(int(a), int(b)): m for (a, b), m in zip(pairs, lists)}
-    out = [None] * dist.get_world_size() if dist.get_rank() == dst else None
-    dist.gather_object((np.asarray(pairs), [np.asarray(m) for m in lists]), out, dst=dst)
-    if out is None:
-        return None
-    merged = {}
-    for prs, ls in out:
-        for (a, b), m in zip(prs, ls):
-            merged[(int(a), int(b))] = m
-    return merged
-
-
-def gather_pair_results(pairs: np.ndarray, results, dst: int = 0):
-    """Variable-size gather of one picklable result per pair (two-view geometries: inlier lists + matrices; small) to
-    `dst`.  Returns on dst a dict {(a, b): result} over all ranks' pairs, elsewhere None."""
-    if not is_distributed():
+def gather_pair_results(pairs: np.ndarray, results, dst: int = 0, distributed: bool = True):
+    """Variable-size gather of one picklable result per pair (match lists; two-view geometries: inlier lists + matrices;
+    small host objects) to `dst`.  Returns on dst a dict {(a, b): result} over all ranks' pairs, elsewhere None.
+    `distributed` False: this process' own pairs, whatever process group exists."""
+    if not (distributed and is_distributed()):
         return {(int(a), int(b)): r for (a, b), r in zip(pairs, results)}
     out = [None] * dist.get_world_size() if dist.get_rank() == dst else None
     dist.gather_object((np.asarray(pairs), list(results)), out, dst=dst)
     if out is None:
         return None
-    merged = {}
-    for prs, rs in out:
-        for (a, b), r in zip(prs, rs):
-            merged[(int(a), int(b))] = r
-    return merged
+    return {(int(a), int(b)): r for prs, rs in out for (a, b), r in zip(prs, rs)}
+
+
+gather_pair_lists = gather_pair_results     # {(a, b): uint32 (M, 2)}: a match list is one more result per pair
 
 
 def raise_if_any_failed(local_error=None, what: str = ""):
@@ -159,6 +143,22 @@ def raise_if_any_failed(local_error=None, what: str = ""):
         raise local_error
     if int(flag.item()):
         raise RuntimeError(f"rank {int(flag.item()) - 1} failed{(' in ' + what) if what else ''}; this rank stops with it")
+
+
+def run_guarded(fn, what: str = "", distributed: bool = True, rank0_only: bool = True):
+    """`fn()` on rank 0 (or, `rank0_only` False, on every rank) with the hand-shake of raise_if_any_failed behind it, so that
+    an exception in it is raised on every rank.  Returns fn's value where it ran, None elsewhere.  `distributed` False:
+    a plain call in this process, whatever process group exists."""
+    if not (distributed and is_distributed()):
+        return fn()
+    value = err = None
+    if not rank0_only or dist.get_rank() == 0:
+        try:
+            value = fn()
+        except Exception as e:  # noqa: BLE001 - handed to every rank below
+            err = e
+    raise_if_any_failed(err, what)
+    return value
 
 
 def broadcast_object(obj, src: int = 0):

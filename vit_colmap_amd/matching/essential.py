@@ -4,7 +4,7 @@ cameras carry a usable focal-length prior.  Specification: tests/util_essential.
 Where the work runs
   HIP     the five-point solver, every hypothesis of every pair in one launch (csrc/essential.hip, vc_essential_5pt);
           scoring and masks by the F kernels of csrc/two_view.hip on F_px = K2^-T E K1^-1
-  torch   the sampler (two_view._sample_indices), K^-1, the one eight-point refit (a 9x9 and a 3x3 SVD per pair)
+  torch   the sampler (_common._sample_indices), K^-1, the one eight-point refit (a 9x9 and a 3x3 SVD per pair)
   host    the camera rows -> K table, the pose choice per CALIBRATED pair (numpy on the pair's inliers)
 """
 import logging
@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ._common import SALT, _ransac_tail, _sample_indices, _score
 
 logger = logging.getLogger(__name__)
 
@@ -94,8 +95,6 @@ def estimate_e(pts, offsets, pair_of, seeds, K1, K2, n_hyp=NUM_HYP_E, max_error=
     """All calibrated pairs at once.  pts float32 (total, 4) pixels, K1, K2 float64 (P, 3, 3) on the device
     -> E float64 (P, 3, 3) at unit norm, F_px float32 (P, 9) (NaN where none), inlier mask bool (total,), counts int64 (P,),
     the normalised points float64 (total, 4)."""
-    from .two_view import SALT, _mask, _sample_indices, _score
-
     dev = pts.device
     P = offsets.shape[0] - 1
     M = (offsets[1:] - offsets[:-1]).to(torch.int64)
@@ -103,38 +102,35 @@ def estimate_e(pts, offsets, pair_of, seeds, K1, K2, n_hyp=NUM_HYP_E, max_error=
     xn = normalise_points(pts.to(torch.float64), pair_of, K1i, K2i)
     idx = _sample_indices(seeds, M, n_hyp, 5, SALT["E"]).to(torch.int32).contiguous()
     sol, _ = solve_five_point(xn, offsets, idx)
-    n_all = n_hyp * MAX_SOLUTIONS
-    sol = sol.reshape(P, n_all, 3, 3)
+    sol = sol.reshape(P, n_hyp * MAX_SOLUTIONS, 3, 3)                       # ranked by (hypothesis, solution)
     hyp32 = _pixel_f(sol, K1i, K2i)
     counts = _score(pts, offsets, hyp32, "F", max_error).to(torch.int64)
-    # most inliers, lowest (hypothesis, solution) on ties
-    key = counts * n_all + (n_all - 1 - torch.arange(n_all, device=dev))[None, :]
-    kbest = (n_all - 1) - (key.max(dim=1).values % n_all)
-    rows = torch.arange(P, device=dev)
-    best, e_best, nbest = hyp32[rows, kbest].contiguous(), sol[rows, kbest], counts[rows, kbest]
-    mask = _mask(pts, offsets, best, "F", max_error)
-    # one refit: eight-point least squares over the best hypothesis' inliers in normalised coordinates (the singular vector
-    # of A'A with the smallest singular value), projected onto the essential manifold
-    x1, y1, x2, y2 = xn.unbind(dim=1)
-    A = torch.stack([x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, torch.ones_like(x1)], dim=1)
-    AtA = torch.zeros((P, 9, 9), dtype=torch.float64, device=dev).index_add_(
-        0, pair_of, (A[:, :, None] * A[:, None, :]) * mask.to(torch.float64)[:, None, None])
-    m9 = torch.linalg.svd(AtA).Vh[:, -1, :].reshape(P, 3, 3)
-    U, _, Vt = torch.linalg.svd(m9)
-    d = torch.tensor([1.0, 1.0, 0.0], dtype=torch.float64, device=dev) / np.sqrt(2.0)
-    e_refit = U @ torch.diag_embed(d.expand(P, 3)) @ Vt
-    ok = torch.isfinite(e_refit).all(dim=-1).all(dim=-1) & (nbest >= 8)
-    refit32 = _pixel_f(e_refit[:, None], K1i, K2i)[:, 0]
-    refit32 = torch.where(ok[:, None], refit32, torch.full_like(refit32, float("nan"))).contiguous()
-    rcount = _score(pts, offsets, refit32[:, None, :].contiguous(), "F", max_error).to(torch.int64)[:, 0]
-    use = ok & (rcount >= nbest)
-    final = torch.where(use[:, None], refit32, best).contiguous()
-    e_final = torch.where(use[:, None, None], e_refit, e_best)
+    e_refit = None
+
+    def refit(mask, nbest):
+        # eight-point least squares over the best hypothesis' inliers in normalised coordinates (the singular vector of A'A
+        # with the smallest singular value), projected onto the essential manifold
+        nonlocal e_refit
+        x1, y1, x2, y2 = xn.unbind(dim=1)
+        A = torch.stack([x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, torch.ones_like(x1)], dim=1)
+        AtA = torch.zeros((P, 9, 9), dtype=torch.float64, device=dev).index_add_(
+            0, pair_of, (A[:, :, None] * A[:, None, :]) * mask.to(torch.float64)[:, None, None])
+        e_refit = project_to_essential(torch.linalg.svd(AtA).Vh[:, -1, :].reshape(P, 3, 3))
+        ok = torch.isfinite(e_refit).all(dim=-1).all(dim=-1) & (nbest >= 8)
+        refit32 = _pixel_f(e_refit[:, None], K1i, K2i)[:, 0]
+        return torch.where(ok[:, None], refit32, torch.full_like(refit32, float("nan"))).contiguous(), ok
+
+    final, fmask, fcount, kbest, use = _ransac_tail(pts, offsets, hyp32, counts, "F", max_error, refit)
+    e_final = torch.where(use[:, None, None], e_refit, sol[torch.arange(P, device=dev), kbest])
     e_final = e_final / torch.linalg.norm(e_final.reshape(P, 9), dim=1).clamp(min=1e-300)[:, None, None]
-    fmask = _mask(pts, offsets, final, "F", max_error)
-    fcount = torch.where(use, rcount, nbest)
-    final = torch.where((fcount > 0)[:, None], final, torch.full_like(final, float("nan")))
     return e_final, final, fmask, fcount, xn
+
+
+def project_to_essential(M):
+    """Batched closest matrix with singular values (1, 1, 0), at unit Frobenius norm."""
+    U, _, Vt = torch.linalg.svd(M)
+    d = torch.tensor([1.0, 1.0, 0.0], dtype=M.dtype, device=M.device) / np.sqrt(2.0)
+    return U @ torch.diag_embed(d.expand(M.shape[0], 3)) @ Vt
 
 
 def rot_to_quat(R):

@@ -18,6 +18,8 @@ ranks, every rank matches its share on its own GPU, the lists are gathered to ra
 """
 import logging
 import time
+from dataclasses import dataclass
+from functools import partial
 
 import numpy as np
 import torch
@@ -25,7 +27,12 @@ import torch
 from .. import _lib
 from .. import dist as vd
 from ..database.colmap_db import SqliteColmapDatabase
-from .hip_matcher import MODEL_KIND, exhaustive_pairs, match_pairs, match_pairs_guided, prepare_descriptors
+from ..utils.config import MatchingConfig
+from .essential import camera_table
+from .hip_matcher import (MODEL_KIND, exhaustive_pairs, match_pairs, match_pairs_blocked, match_pairs_guided,
+                          prepare_descriptors)
+from .two_view import (CONFIG_DEGENERATE, CONFIG_PANORAMIC, CONFIG_PLANAR, MAX_ERROR, read_keypoints_by_index,
+                       verify_pair_lists, write_two_view_rows)
 
 logger = logging.getLogger(__name__)
 
@@ -33,8 +40,6 @@ logger = logging.getLogger(__name__)
 def _sift_options(matching_options, sift_options):
     opts = matching_options if matching_options is not None else sift_options
     if opts is None:
-        from ..utils.config import MatchingConfig
-
         opts = MatchingConfig().to_matching_options()
     return getattr(opts, "sift", opts)  # FeatureMatchingOptions(.sift) or SiftMatchingOptions
 
@@ -51,10 +56,31 @@ def _relative_pose_option(matching_options, sift_options) -> bool:
     return bool(getattr(opts, "compute_relative_pose", False) or getattr(getattr(opts, "sift", None), "compute_relative_pose", False))
 
 
+@dataclass(frozen=True)
+class MatchSettings:
+    """What a run reads from its options objects, looked up once."""
+    max_ratio: float
+    max_distance: float
+    cross_check: bool
+    guided: bool            # the options' guided_matching (DESIGN.md §4.2e); needs `verify`
+    relative_pose: bool     # the options' compute_relative_pose (DESIGN.md §4.2g); needs `verify`
+
+    @classmethod
+    def from_options(cls, matching_options=None, sift_options=None, verify: bool = True):
+        sift = _sift_options(matching_options, sift_options)
+        return cls(float(sift.max_ratio), float(sift.max_distance), bool(sift.cross_check),
+                   verify and _guided_option(matching_options, sift_options),
+                   verify and _relative_pose_option(matching_options, sift_options))
+
+
+def new_stats(images: int, pairs: int, ranks: int) -> dict:
+    """The stats dict of a matching run before anything is matched."""
+    return dict(images=images, pairs=pairs, matches=0, gpu_s=0.0, db_s=0.0, verified_pairs=0, ranks=ranks, guided_pairs=0,
+                **pose_stats(()))
+
+
 def pose_stats(results) -> dict:
     """The relative-pose totals of a run's results (an iterable of verify_pairs results)."""
-    from .two_view import CONFIG_PANORAMIC, CONFIG_PLANAR
-
     posed = [r for r in results if "tri_angle" in r]
     angles = [r["tri_angle"] for r in posed if r["config"] != CONFIG_PANORAMIC and r["n_front"] > 0]
     return dict(pose_pairs=len(posed), planar_pairs=sum(r["config"] == CONFIG_PLANAR for r in posed),
@@ -80,40 +106,44 @@ def load_descriptor_blocks(db: SqliteColmapDatabase):
     return ids, block, counts, D
 
 
+def _upload_blocks(block, counts, device, what):
+    """uint8 blocks [n][n_max][D] + counts (host or device) -> both on `device`, checked against the kernels' limits."""
+    if not torch.cuda.is_available():
+        raise _lib.HipLibraryError(f"{what} is HIP-only (no CPU fallback): no GPU visible")
+    d_desc = block if torch.is_tensor(block) else torch.from_numpy(np.ascontiguousarray(block))
+    d_counts = counts if torch.is_tensor(counts) else torch.from_numpy(np.ascontiguousarray(counts, np.int32))
+    if d_desc.shape[2] > _lib.VC_MAX_DESC_DIM:
+        raise _lib.HipLibraryError(f"descriptors of {d_desc.shape[2]} bytes exceed the kernels' limit ({_lib.VC_MAX_DESC_DIM})")
+    return d_desc.to(device), d_counts.to(device)
+
+
+def _unpack_chunk(m, c, first_pair, what):
+    """One launch's (matches [P, n_max, 2], counts [P]) on the device -> list of P uint32 (M, 2) host arrays."""
+    c_np = c.cpu().numpy()
+    if (c_np < 0).any():   # VC_COUNT_SELFCHECK_FAILED: the kernel's cursor check (include/vitcolmap_hip.h) — never a result
+        bad = np.nonzero(c_np < 0)[0][:8] + first_pair
+        raise _lib.HipLibraryError(f"{what}: consistency check failed for pairs {bad.tolist()}")
+    m_np = m.cpu().numpy().view(np.uint32)
+    return [m_np[p, : c_np[p]].copy() for p in range(len(c_np))]
+
+
 def hip_match_blocks(block, counts, pairs, max_ratio=0.8, max_distance=0.7, cross_check=True, device="cuda",
                      pair_chunk: int = 16384):
     """uint8 blocks [n][n_max][D] + counts (host or device) and pairs int32 (P, 2) (host) -> list of P uint32 (M, 2)
     match lists, on the HIP matcher.  Blocks with more rows than one kernel block holds (VC_MAX_KEYPOINTS) are
     matched in row / column sub-blocks whose top-2 results are merged (hip_matcher.match_pairs_blocked)."""
-    if not torch.cuda.is_available():
-        raise _lib.HipLibraryError("the matcher is HIP-only (no CPU fallback): no GPU visible")
-    d_desc = block if torch.is_tensor(block) else torch.from_numpy(np.ascontiguousarray(block))
-    d_counts = counts if torch.is_tensor(counts) else torch.from_numpy(np.ascontiguousarray(counts, np.int32))
-    d_desc, d_counts = d_desc.to(device), d_counts.to(device)
+    d_desc, d_counts = _upload_blocks(block, counts, device, "the matcher")
     n, n_max, D = d_desc.shape
     pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    if D > _lib.VC_MAX_DESC_DIM:
-        raise _lib.HipLibraryError(f"descriptors of {D} bytes exceed the kernels' limit ({_lib.VC_MAX_DESC_DIM})")
     if n_max > _lib.VC_MAX_KEYPOINTS:
-        from .hip_matcher import match_pairs_blocked
-
         return match_pairs_blocked(d_desc, d_counts, pairs, max_ratio, max_distance, cross_check)
     prepared = prepare_descriptors(d_desc, d_counts)
     out = []
     for s in range(0, len(pairs), pair_chunk):
         chunk = torch.from_numpy(pairs[s:s + pair_chunk]).to(device)
         m, c = match_pairs(prepared, d_counts, n, n_max, D, chunk, max_ratio, max_distance, cross_check)
-        c_np = c.cpu().numpy()
-        _selfcheck(c_np, s, "vc_match_pairs_u8")
-        m_np = m.cpu().numpy().view(np.uint32)
-        out.extend(m_np[p, : c_np[p]].copy() for p in range(len(c_np)))
+        out.extend(_unpack_chunk(m, c, s, "vc_match_pairs_u8"))
     return out
-
-
-def _selfcheck(c_np, first_pair, what):
-    if (c_np < 0).any():   # VC_COUNT_SELFCHECK_FAILED: the kernel's cursor check (include/vitcolmap_hip.h) — never a result
-        bad = np.nonzero(c_np < 0)[0][:8] + first_pair
-        raise _lib.HipLibraryError(f"{what}: consistency check failed for pairs {bad.tolist()}")
 
 
 def check_guided_block_size(n_max: int):
@@ -127,15 +157,9 @@ def hip_guided_blocks(block, counts, keypoints_xy, pairs, models, kinds, max_err
                       cross_check=True, device="cuda", pair_chunk: int = 16384):
     """Guided matching of `pairs` (P, 2) on the HIP matcher: uint8 blocks [n][n_max][D] + counts, keypoints float32
     [n][>= 1][2] (zero padded), models float32 (P, 9), kinds list of "F" / "H" -> list of P uint32 (M, 2) match lists."""
-    if not torch.cuda.is_available():
-        raise _lib.HipLibraryError("guided matching is HIP-only (no CPU fallback): no GPU visible")
-    d_desc = block if torch.is_tensor(block) else torch.from_numpy(np.ascontiguousarray(block))
-    d_counts = counts if torch.is_tensor(counts) else torch.from_numpy(np.ascontiguousarray(counts, np.int32))
-    d_desc, d_counts = d_desc.to(device), d_counts.to(device)
+    d_desc, d_counts = _upload_blocks(block, counts, device, "guided matching")
     n, n_max, D = d_desc.shape
     check_guided_block_size(n_max)
-    if D > _lib.VC_MAX_DESC_DIM:
-        raise _lib.HipLibraryError(f"descriptors of {D} bytes exceed the kernels' limit ({_lib.VC_MAX_DESC_DIM})")
     kp = np.asarray(keypoints_xy, np.float32)
     kp_block = np.zeros((n, n_max, 2), np.float32)                        # the kernel's layout: one row per descriptor row
     rows = min(n_max, kp.shape[1])
@@ -151,10 +175,7 @@ def hip_guided_blocks(block, counts, keypoints_xy, pairs, models, kinds, max_err
         m, c = match_pairs_guided(prepared, d_counts, n, n_max, D, d_kp, torch.from_numpy(pairs[sl]).to(device),
                                   torch.from_numpy(models[sl]).to(device), torch.from_numpy(kind[sl]).to(device), max_error,
                                   max_ratio, max_distance, cross_check)
-        c_np = c.cpu().numpy()
-        _selfcheck(c_np, s, "vc_match_pairs_guided_u8")
-        m_np = m.cpu().numpy().view(np.uint32)
-        out.extend(m_np[p, : c_np[p]].copy() for p in range(len(c_np)))
+        out.extend(_unpack_chunk(m, c, s, "vc_match_pairs_guided_u8"))
     return out
 
 
@@ -162,8 +183,6 @@ def rematch_guided(block, counts, keypoints_xy, pairs, results, max_ratio, max_d
     """The guided pass over one rank's share: every result of `results` (verify_pairs' format, parallel to `pairs`) that is
     not DEGENERATE has its `inlier_matches` replaced by the list matched under the model that produced them (`model`,
     `model9`), with the verifier's own error bound.  Returns the number of pairs re-matched."""
-    from .two_view import CONFIG_DEGENERATE, MAX_ERROR
-
     sel = [i for i, r in enumerate(results) if r["config"] != CONFIG_DEGENERATE]
     if not sel:
         return 0
@@ -221,142 +240,59 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
 
 def match_database(database_path, matching_options, sift_options, device, pair_chunk, distributed, match_fn, verify,
                    verify_fn, guided_fn, select_pairs=None, what="match_exhaustive") -> dict:
-    """The database-in / database-out body that match_exhaustive and matching.retrieval.match_retrieval share; they differ
+    """The database-in / database-out entry that match_exhaustive and matching.retrieval.match_retrieval share; they differ
     only in where the pair list comes from.  `select_pairs` None: every pair (a < b), dealt to the ranks by
     dist.pairs_for_rank.  Otherwise rank 0 calls `select_pairs(block, counts, stats)` once the descriptor blocks are
     loaded -> int32 (P, 2) image-index pairs, a < b, ascending (a sub-sequence of the exhaustive list; it may add keys
     to `stats`); the list is broadcast, pair p goes to rank p % world (dist.listed_pairs_for_rank), and only the listed
-    pairs are matched, verified and written."""
-    sift = _sift_options(matching_options, sift_options)
-    max_ratio, max_distance, cross_check = float(sift.max_ratio), float(sift.max_distance), bool(sift.cross_check)
-    guided = _guided_option(matching_options, sift_options) and verify
-    relative_pose = _relative_pose_option(matching_options, sift_options) and verify
+    pairs are matched, verified and written.  This function reads and broadcasts; match_loaded does the rest."""
+    settings = MatchSettings.from_options(matching_options, sift_options, verify)
     if distributed is None:
         distributed = vd.is_distributed()
     if distributed and not vd.is_distributed():
         raise RuntimeError("distributed=True needs an initialised torch.distributed process group with > 1 rank")
     rank, world = vd.rank_world() if distributed else (0, 1)
-    if match_fn is None:
-        if not torch.cuda.is_available():
-            raise _lib.HipLibraryError(f"{what} needs an MI355X: the matcher is HIP-only (no CPU fallback)")
-
-        def match_fn(block, counts, pairs, r, dmax, cc):
-            return hip_match_blocks(block, counts, pairs, r, dmax, cc, device=device, pair_chunk=pair_chunk)
-
-    if guided and guided_fn is None:
-        if not torch.cuda.is_available():
-            raise _lib.HipLibraryError("guided matching needs an MI355X: the matcher is HIP-only (no CPU fallback)")
-
-        def guided_fn(block, counts, kp_xy, pairs, models, kinds, e, r, dmax, cc):
-            return hip_guided_blocks(block, counts, kp_xy, pairs, models, kinds, e, r, dmax, cc, device=device,
-                                     pair_chunk=pair_chunk)
-
-    from .essential import camera_table
-    from .two_view import CONFIG_DEGENERATE, read_keypoints_by_index, verify_pair_lists, write_two_view_rows
-
+    if not torch.cuda.is_available() and (match_fn is None or (settings.guided and guided_fn is None)):
+        raise _lib.HipLibraryError(f"{what} needs an MI355X: the matcher is HIP-only (no CPU fallback)")
     t0 = time.perf_counter()
     db = None
+
+    def read():                                                                # rank 0 is the only reader and writer
+        nonlocal db
+        db = SqliteColmapDatabase(str(database_path))
+        ids, block, counts, D = load_descriptor_blocks(db)
+        kp_arr = kp_cnt = cam_k = cam_prior = None
+        if verify and D != 0:
+            kp_arr, kp_cnt = _pack_keypoints(read_keypoints_by_index(db, ids), len(ids))
+            cam_k, cam_prior = camera_table(db, ids)                           # focal-length priors (DESIGN.md §4.2f)
+            if settings.relative_pose and not cam_prior.any():
+                logger.warning("compute_relative_pose is set and no camera has a usable focal-length prior: it has no effect")
+        return ids, D, [block, counts, kp_arr, kp_cnt, cam_k, cam_prior]
+
     try:
-        ids = block = counts = D = kp_arr = kp_cnt = cam_k = cam_prior = None
-        err = None
-        if rank == 0:                                                          # rank 0 is the only reader and writer
-            try:
-                db = SqliteColmapDatabase(str(database_path))
-                ids, block, counts, D = load_descriptor_blocks(db)
-                if verify and D != 0:
-                    kp_arr, kp_cnt = _pack_keypoints(read_keypoints_by_index(db, ids), len(ids))
-                    cam_k, cam_prior = camera_table(db, ids)               # focal-length priors (DESIGN.md §4.2f)
-                    if relative_pose and not cam_prior.any():
-                        logger.warning("compute_relative_pose is set and no camera has a usable focal-length prior: "
-                                       "it has no effect")
-            except Exception as e:  # noqa: BLE001 - handed to every rank below
-                err = e
+        ids, D, arrays = vd.run_guarded(read, "reading the database", distributed) or (None, None, [None] * 6)
         if distributed:
-            vd.raise_if_any_failed(err, "reading the database")
             ids, D = vd.broadcast_object((ids, D), 0)
-            block = vd.broadcast_array(block, 0, device)
-            counts = vd.broadcast_array(counts, 0, device)
-            if verify and D != 0:
-                kp_arr = vd.broadcast_array(kp_arr, 0, device)
-                kp_cnt = vd.broadcast_array(kp_cnt, 0, device)
-                cam_k = vd.broadcast_array(cam_k, 0, device)
-                cam_prior = vd.broadcast_array(cam_prior, 0, device)
-        elif err is not None:
-            raise err
+            k = 6 if verify and D != 0 else 2                                  # keypoints and cameras travel where they are used
+            arrays = [vd.broadcast_array(a, 0, device) for a in arrays[:k]] + arrays[k:]
+        block, counts, kp_arr, kp_cnt, cam_k, cam_prior = arrays
         n = len(ids)
-        stats = dict(images=n, pairs=n * (n - 1) // 2, matches=0, gpu_s=0.0, db_s=0.0, verified_pairs=0, ranks=world,
-                     guided_pairs=0, pose_pairs=0, planar_pairs=0, panoramic_pairs=0, median_tri_angle_deg=0.0)
+        stats = new_stats(n, n * (n - 1) // 2, world)
         if n < 2:
             return stats
-        if guided and D != 0:
-            check_guided_block_size(int(np.asarray(block).shape[1]))           # before any matching starts, on every rank
         if select_pairs is None:
             all_pairs = exhaustive_pairs(n).numpy()
             my_pairs = vd.pairs_for_rank(n, rank, world)
         else:
-            err = all_pairs = None
-            if rank == 0:
-                try:
-                    all_pairs = np.ascontiguousarray(select_pairs(block, counts, stats), np.int32).reshape(-1, 2)
-                except Exception as e:  # noqa: BLE001 - handed to every rank below
-                    err = e
+            all_pairs = vd.run_guarded(lambda: np.ascontiguousarray(select_pairs(block, counts, stats), np.int32).reshape(-1, 2),
+                                       "selecting the pairs", distributed)
             if distributed:
-                vd.raise_if_any_failed(err, "selecting the pairs")
                 all_pairs = vd.broadcast_array(all_pairs, 0, device)
-            elif err is not None:
-                raise err
             my_pairs = vd.listed_pairs_for_rank(all_pairs, rank, world)
             stats["pairs"] = len(all_pairs)
-        t1 = time.perf_counter()
-        err, lists, results = None, [], None
-        try:
-            if D == 0:
-                lists = [np.zeros((0, 2), np.uint32) for _ in my_pairs]      # no descriptors anywhere: every pair is empty
-            elif select_pairs is not None and len(my_pairs) == 0:
-                results = [] if verify else None                               # nothing selected fell to this rank
-            else:
-                lists = match_fn(block, counts, my_pairs, max_ratio, max_distance, cross_check)
-                if verify:                                                     # this rank verifies the pairs it matched
-                    vdev = device if (verify_fn is not None or torch.cuda.is_available()) else "cpu"
-                    results = verify_pair_lists(_unpack_keypoints(kp_arr, kp_cnt), ids, my_pairs, lists, device=vdev,
-                                                verify_fn=verify_fn, cameras=(cam_k, cam_prior), relative_pose=relative_pose)
-                    if guided:
-                        rematch_guided(block, counts, kp_arr, my_pairs, results, max_ratio, max_distance, cross_check,
-                                       guided_fn)
-        except Exception as e:  # noqa: BLE001
-            err = e
-        if distributed:
-            vd.raise_if_any_failed(err, "matching / verification")
-        elif err is not None:
-            raise err
-        stats["gpu_s"] = time.perf_counter() - t1
-        merged = vd.gather_pair_lists(my_pairs, lists, dst=0) if distributed else \
-            {(int(a), int(b)): m for (a, b), m in zip(my_pairs, lists)}
-        verified = None
-        if results is not None:
-            verified = vd.gather_pair_results(my_pairs, results, dst=0) if distributed else \
-                {(int(a), int(b)): r for (a, b), r in zip(my_pairs, results)}
-        err = None
-        if rank == 0:
-            try:
-                t2 = time.perf_counter()
-                for a, b in all_pairs:                                         # COLMAP's pair order, whatever rank matched it
-                    m = merged[(int(a), int(b))]
-                    db.write_matches(ids[a], ids[b], m, commit=False)
-                    stats["matches"] += len(m)
-                db.commit()
-                if verified is not None:
-                    stats["verified_pairs"] = write_two_view_rows(db, ids, verified)
-                    stats["guided_pairs"] = sum(r["config"] != CONFIG_DEGENERATE for r in verified.values()) if guided else 0
-                    stats.update(pose_stats(verified.values()))
-                stats["db_s"] = time.perf_counter() - t2
-            except Exception as e:  # noqa: BLE001
-                err = e
-        if distributed:
-            vd.raise_if_any_failed(err, "writing the database")
-            stats = vd.broadcast_object(stats, 0)                              # every rank returns rank 0's totals
-        elif err is not None:
-            raise err
+        stats = match_loaded(ids, block, counts, kp_arr, kp_cnt, (cam_k, cam_prior), all_pairs, my_pairs, settings, verify,
+                             db, stats, match_fn=match_fn, verify_fn=verify_fn, guided_fn=guided_fn, device=device,
+                             pair_chunk=pair_chunk, distributed=distributed, skip_empty_share=select_pairs is not None)
         stats["total_s"] = time.perf_counter() - t0
         logger.info("matched %d pairs (%d matches) on %d rank(s): gpu %.3f s, db %.3f s", stats["pairs"], stats["matches"],
                     world, stats["gpu_s"], stats["db_s"])
@@ -364,3 +300,71 @@ def match_database(database_path, matching_options, sift_options, device, pair_c
     finally:
         if db is not None:
             db.close()
+
+
+def _host(x):
+    return x.cpu().numpy() if torch.is_tensor(x) else x
+
+
+def match_loaded(ids, block, counts, kp_arr, kp_cnt, cameras, all_pairs, my_pairs, settings, verify, db, stats, *,
+                 match_fn=None, verify_fn=None, guided_fn=None, device="cuda", pair_chunk: int = 16384, distributed=False,
+                 write_what="writing the database", skip_empty_share=False) -> dict:
+    """Match my share, verify, re-match guided, gather, rank 0 writes: the body that match_database and
+    pipeline.distributed.run_sharded share.  Everything is in memory and the same on every rank: the image ids, the uint8
+    descriptor blocks [n][n_max][D] + counts (host or device), the keypoints float32 [n][>= 1][2] zero padded + counts
+    (host; unused without `verify`), `cameras` (K, prior) or None (essential.camera_table), the full pair list (P, 2) and
+    this rank's share of it, `settings` (MatchSettings).  `db` is rank 0's open SqliteColmapDatabase (unused elsewhere).
+    Seams left None default to the HIP functions, which take the blocks as they are; a caller's `match_fn` / `guided_fn`
+    takes them as host arrays.  `distributed` False runs every collective step locally, whatever process group exists.
+    An error on any rank is raised on every rank (`write_what` names rank 0's writing phase in the others' message).
+    `skip_empty_share`: a rank whose share is empty calls neither the matcher nor the verifier.
+    Returns `stats` with the totals filled in — rank 0's, on every rank."""
+    s = settings
+    empty = not _host(counts).any()                                            # no descriptors anywhere: every pair is empty
+    if s.guided and not empty:
+        check_guided_block_size(int(block.shape[1]))                           # before any matching starts, on every rank
+    if match_fn is None:
+        match_fn, m_blocks = partial(hip_match_blocks, device=device, pair_chunk=pair_chunk), (block, counts)
+    else:
+        m_blocks = (_host(block), _host(counts))
+    if guided_fn is None:
+        guided_fn, g_blocks = partial(hip_guided_blocks, device=device, pair_chunk=pair_chunk), (block, counts)
+    else:
+        g_blocks = (_host(block), _host(counts))
+
+    def match_my_share():
+        if empty:
+            return [np.zeros((0, 2), np.uint32) for _ in my_pairs], None
+        if skip_empty_share and len(my_pairs) == 0:
+            return [], ([] if verify else None)
+        lists = match_fn(*m_blocks, my_pairs, s.max_ratio, s.max_distance, s.cross_check)
+        if not verify:
+            return lists, None
+        vdev = device if (verify_fn is not None or torch.cuda.is_available()) else "cpu"
+        results = verify_pair_lists(_unpack_keypoints(kp_arr, kp_cnt), ids, my_pairs, lists, device=vdev, verify_fn=verify_fn,
+                                    cameras=cameras, relative_pose=s.relative_pose)
+        if s.guided:
+            rematch_guided(*g_blocks, kp_arr, my_pairs, results, s.max_ratio, s.max_distance, s.cross_check, guided_fn)
+        return lists, results
+
+    t1 = time.perf_counter()
+    lists, results = vd.run_guarded(match_my_share, "matching / verification", distributed, rank0_only=False)
+    stats["gpu_s"] = time.perf_counter() - t1
+    merged = vd.gather_pair_lists(my_pairs, lists, dst=0, distributed=distributed)
+    verified = None if results is None else vd.gather_pair_results(my_pairs, results, dst=0, distributed=distributed)
+
+    def write():
+        t2 = time.perf_counter()
+        for a, b in all_pairs:                                                 # COLMAP's pair order, whatever rank matched it
+            m = merged[(int(a), int(b))]
+            db.write_matches(ids[a], ids[b], m, commit=False)
+            stats["matches"] += len(m)
+        db.commit()
+        if verified is not None:
+            stats["verified_pairs"] = write_two_view_rows(db, ids, verified)
+            stats["guided_pairs"] = sum(r["config"] != CONFIG_DEGENERATE for r in verified.values()) if s.guided else 0
+            stats.update(pose_stats(verified.values()))
+        stats["db_s"] = time.perf_counter() - t2
+
+    vd.run_guarded(write, write_what, distributed)
+    return vd.broadcast_object(stats, 0) if distributed else stats             # every rank returns rank 0's totals

@@ -39,6 +39,15 @@ def prepare_descriptors(desc: torch.Tensor, counts: torch.Tensor) -> torch.Tenso
     return prepared
 
 
+def _outputs(P, n_max, device, out_matches=None, out_counts=None):
+    """The pair kernels' outputs, allocated where the caller brought none: matches int32 [P, n_max, 2], counts int32 [P]."""
+    if out_matches is None:
+        out_matches = torch.empty((P, n_max, 2), dtype=torch.int32, device=device)
+    if out_counts is None:
+        out_counts = torch.empty((P,), dtype=torch.int32, device=device)
+    return out_matches, out_counts
+
+
 def match_pairs(prepared, counts, n_images, n_max, d, pairs, max_ratio=0.8, max_distance=0.7,
                 cross_check=True, out_matches=None, out_counts=None):
     """-> (matches int32-viewed-uint32 [P, n_max, 2], match counts int32 [P])."""
@@ -46,10 +55,7 @@ def match_pairs(prepared, counts, n_images, n_max, d, pairs, max_ratio=0.8, max_
     assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.shape[-1] == 2
     lib = _lib.load()
     P = pairs.shape[0]
-    if out_matches is None:
-        out_matches = torch.empty((P, n_max, 2), dtype=torch.int32, device=prepared.device)
-    if out_counts is None:
-        out_counts = torch.empty((P,), dtype=torch.int32, device=prepared.device)
+    out_matches, out_counts = _outputs(P, n_max, prepared.device, out_matches, out_counts)
     _lib.check(lib.vc_match_pairs_u8(_lib.ptr(prepared), _lib.ptr(counts), n_images, n_max, d,
                                      _lib.ptr(pairs), P, max_ratio, max_distance, int(cross_check),
                                      _lib.ptr(out_matches), _lib.ptr(out_counts), _lib.stream_ptr()),
@@ -72,10 +78,7 @@ def match_pairs_guided(prepared, counts, n_images, n_max, d, keypoints_xy, pairs
     assert models.dtype == torch.float32 and models.is_contiguous() and tuple(models.shape) == (P, 9)
     assert model_kind.dtype == torch.int32 and model_kind.is_contiguous() and model_kind.numel() == P
     lib = _lib.load()
-    if out_matches is None:
-        out_matches = torch.empty((P, n_max, 2), dtype=torch.int32, device=prepared.device)
-    if out_counts is None:
-        out_counts = torch.empty((P,), dtype=torch.int32, device=prepared.device)
+    out_matches, out_counts = _outputs(P, n_max, prepared.device, out_matches, out_counts)
     _lib.check(lib.vc_match_pairs_guided_u8(_lib.ptr(prepared), _lib.ptr(counts), n_images, n_max, d, _lib.ptr(keypoints_xy),
                                             _lib.ptr(pairs), P, _lib.ptr(models), _lib.ptr(model_kind), float(max_error),
                                             max_ratio, max_distance, int(cross_check), _lib.ptr(out_matches),

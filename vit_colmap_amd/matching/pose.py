@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .essential import rot_to_quat
+from ._common import CONFIG_PANORAMIC, CONFIG_PLANAR, CONFIG_PLANAR_OR_PANORAMIC, _pair_batch
+from .essential import project_to_essential, rot_to_quat
 
 H_ROTATION_EPS = 1e-10      # sigma_1^2 - sigma_3^2 of Hn (middle singular value 1) below this: Hn is a rotation, t = 0
 
@@ -36,13 +37,6 @@ def e_candidates(E):
     u = U[:, :, 2] / torch.linalg.norm(U[:, :, 2], dim=1, keepdim=True)
     Ra, Rb = U @ W @ Vt, U @ W.T @ Vt
     return torch.stack([_pack(Ra, u), _pack(Ra, -u), _pack(Rb, u), _pack(Rb, -u)], dim=1)
-
-
-def project_to_essential(M):
-    """Batched closest matrix with singular values (1, 1, 0), at unit Frobenius norm."""
-    U, _, Vt = torch.linalg.svd(M)
-    d = torch.tensor([1.0, 1.0, 0.0], dtype=M.dtype, device=M.device) / np.sqrt(2.0)
-    return U @ torch.diag_embed(d.expand(M.shape[0], 3)) @ Vt
 
 
 def _positive(v):
@@ -114,8 +108,6 @@ def relative_poses(entries, device, max_error):
     """The rule for a chunk's qualifying pairs.  entries: list of dict(config, kind "E" | "F" | "H", matrix (3, 3) — E in
     normalised coordinates, or the pixel F / H —, K1, K2 (3, 3), xn float64 (n, 4) the pair's inliers)
     -> list of dict(config, qvec, tvec, tri_angle, n_front)."""
-    from .two_view import CONFIG_PANORAMIC, CONFIG_PLANAR, CONFIG_PLANAR_OR_PANORAMIC
-
     n = len(entries)
     if n == 0:
         return []
@@ -133,9 +125,7 @@ def relative_poses(entries, device, max_error):
             cand[idx] = e_candidates(project_to_essential(K2[idx].transpose(1, 2) @ M[idx] @ K1[idx]))
         else:
             cand[idx] = h_candidates(torch.linalg.inv(K2[idx]) @ M[idx] @ K1[idx])
-    offs = np.concatenate([[0], np.cumsum([len(e["xn"]) for e in entries])])
-    xn = torch.from_numpy(np.concatenate([np.asarray(e["xn"], np.float64).reshape(-1, 4) for e in entries])).to(device)
-    offsets = torch.tensor(offs, dtype=torch.int32, device=device)
+    xn, offsets, _, _ = _pair_batch([np.asarray(e["xn"], np.float64).reshape(-1, 4) for e in entries], None, device)
     front, best, tri, _ = two_view_pose(xn, offsets, cand)
     front, best, tri, cand = front.cpu().numpy(), best.cpu().numpy(), tri.cpu().numpy(), cand.cpu().numpy()
     if (best < 0).any():

@@ -19,50 +19,13 @@ import torch
 
 from .. import _lib
 from ..database.colmap_db import pair_id_of
-
-CONFIG_UNDEFINED, CONFIG_DEGENERATE, CONFIG_CALIBRATED, CONFIG_UNCALIBRATED = 0, 1, 2, 3
-CONFIG_PLANAR, CONFIG_PANORAMIC, CONFIG_PLANAR_OR_PANORAMIC = 4, 5, 6
-MIN_NUM_INLIERS = 15
-MAX_ERROR = 4.0
-MAX_H_INLIER_RATIO = 0.8
-MIN_INLIER_RATIO = 0.25
-NUM_HYP_F, NUM_HYP_H = 512, 128
-NUM_CANDIDATES = 32
-SALT = {"F": 0x0F0F0F0F, "H": 0x3C3C3C3C, "E": 0x5A5A5A5A}
-MODEL_CODE = {"F": 0, "H": 1}
-_M32 = 0xFFFFFFFF
-
-
-def _lowbias32(x):
-    """int64 tensor holding 32-bit values -> lowbias32 hash (Python-int constants keep the products below 2^63)."""
-    x = x & _M32
-    x = x ^ (x >> 16)
-    x = (x * 0x7FEB352D) & _M32
-    x = x ^ (x >> 15)
-    x = (x * 0x846CA68B) & _M32
-    return x ^ (x >> 16)
-
-
-def _sample_indices(seeds, counts, n_hyp, S, salt):
-    """seeds, counts int64 (P,) -> int64 (P, n_hyp, S): the first S distinct values of hash(seed, k, j) mod M, -1 if void."""
-    dev = seeds.device
-    P = seeds.shape[0]
-    k = torch.arange(n_hyp, dtype=torch.int64, device=dev)[None, :, None]
-    j = torch.arange(NUM_CANDIDATES, dtype=torch.int64, device=dev)[None, None, :]
-    # 32-bit wrap-around arithmetic on int64: every product is reduced before it can reach 2^63
-    x = ((seeds[:, None, None] & _M32) * 0x9E3779B1) & _M32
-    x = (x + ((k * 0x85EBCA6B) & _M32) + ((j * 0xC2B2AE35) & _M32) + salt) & _M32
-    cand = _lowbias32(x) % counts[:, None, None].clamp(min=1)
-    chosen = torch.full((P, n_hyp, S), -1, dtype=torch.int64, device=dev)
-    count = torch.zeros((P, n_hyp), dtype=torch.int64, device=dev)
-    slot = torch.arange(S, dtype=torch.int64, device=dev)[None, None, :]
-    for jj in range(NUM_CANDIDATES):
-        c = cand[:, :, jj]
-        take = ~(chosen == c[:, :, None]).any(dim=2) & (count < S)
-        put = take[:, :, None] & (slot == count[:, :, None])
-        chosen = torch.where(put, c[:, :, None], chosen)
-        count = count + take.to(torch.int64)
-    return torch.where((count < S)[:, :, None], torch.full_like(chosen, -1), chosen)
+from . import essential
+from ._common import (CONFIG_CALIBRATED, CONFIG_DEGENERATE, CONFIG_PANORAMIC, CONFIG_PLANAR,  # noqa: F401 - re-exported
+                      CONFIG_PLANAR_OR_PANORAMIC, CONFIG_UNCALIBRATED, CONFIG_UNDEFINED, MAX_ERROR, MAX_H_INLIER_RATIO,
+                      MIN_INLIER_RATIO, MIN_NUM_INLIERS, MODEL_CODE, NUM_CANDIDATES, NUM_HYP_F, NUM_HYP_H, SALT, _mask,
+                      _pair_batch, _ransac_tail, _sample_indices, _score)
+from .essential import MIN_E_F_INLIER_RATIO, camera_table, choose_pose
+from .pose import relative_poses
 
 
 def _rows(model, x1, y1, x2, y2):
@@ -84,23 +47,6 @@ def _denormalise(model, Mn, T1, T2):
     if model == "F":
         return T2.transpose(-1, -2)[:, None] @ Mn @ T1[:, None]
     return torch.linalg.inv(T2)[:, None] @ Mn @ T1[:, None]
-
-
-def _score(pts, offsets, hyp, model, max_error):
-    lib = _lib.load()
-    P, K, _ = hyp.shape
-    counts = torch.zeros((P, K), dtype=torch.int32, device=pts.device)
-    _lib.check(lib.vc_two_view_score(_lib.ptr(pts), _lib.ptr(offsets), P, _lib.ptr(hyp), K, MODEL_CODE[model], float(max_error),
-                                     _lib.ptr(counts), _lib.stream_ptr()), "vc_two_view_score")
-    return counts
-
-
-def _mask(pts, offsets, models, model, max_error):
-    lib = _lib.load()
-    mask = torch.zeros((pts.shape[0],), dtype=torch.uint8, device=pts.device)
-    _lib.check(lib.vc_two_view_inliers(_lib.ptr(pts), _lib.ptr(offsets), models.shape[0], _lib.ptr(models), MODEL_CODE[model],
-                                       float(max_error), _lib.ptr(mask), _lib.stream_ptr()), "vc_two_view_inliers")
-    return mask.bool()
 
 
 def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
@@ -139,32 +85,23 @@ def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
     hyp = torch.where(void[:, :, None] | ~torch.isfinite(sol).all(dim=-1, keepdim=True), torch.full_like(hyp, float("nan")), hyp)
     hyp32 = hyp.to(torch.float32).contiguous()
     counts = _score(pts, offsets, hyp32, model, max_error).to(torch.int64)
-    # most inliers, lowest k on ties
-    key = counts * n_hyp + (n_hyp - 1 - torch.arange(n_hyp, device=dev))[None, :]
-    kbest = (n_hyp - 1) - (key.max(dim=1).values % n_hyp)
-    best = hyp32[torch.arange(P, device=dev), kbest].contiguous()
-    nbest = counts[torch.arange(P, device=dev), kbest]
-    mask = _mask(pts, offsets, best, model, max_error)
-    # one refit over the inliers of the best hypothesis: normal equations per pair (float64)
     Ar, br = _rows(model, n1[:, 0], n1[:, 1], n2[:, 0], n2[:, 1])             # F: (total, 8); H: (2 total, 8) stacked x then y
-    if model == "H":
-        w = torch.cat([mask, mask]).to(torch.float64)
-        seg = torch.cat([pair_of, pair_of])
-    else:
-        w, seg = mask.to(torch.float64), pair_of
-    AtA = torch.zeros((P, 8, 8), dtype=torch.float64, device=dev).index_add_(0, seg, (Ar[:, :, None] * Ar[:, None, :]) * w[:, None, None])
-    Atb = torch.zeros((P, 8), dtype=torch.float64, device=dev).index_add_(0, seg, Ar * (br * w)[:, None])
-    rsol = torch.linalg.solve_ex(AtA, Atb.unsqueeze(-1)).result.squeeze(-1)
-    refit = _denormalise(model, _to_matrix(rsol)[:, None], T1, T2).reshape(P, 9)
-    ok = torch.isfinite(rsol).all(dim=-1) & (nbest >= S)
-    refit32 = torch.where(ok[:, None], refit, torch.full_like(refit, float("nan"))).to(torch.float32).contiguous()
-    rcount = _score(pts, offsets, refit32[:, None, :].contiguous(), model, max_error).to(torch.int64)[:, 0]
-    use = ok & (rcount >= nbest)
-    final = torch.where(use[:, None], refit32, best).contiguous()
-    fmask = _mask(pts, offsets, final, model, max_error)
-    fcount = torch.where(use, rcount, nbest)
-    final = torch.where((fcount > 0)[:, None], final, torch.full_like(final, float("nan")))
-    return final, fmask, fcount
+
+    def refit(mask, nbest):
+        # over the inliers of the best hypothesis: normal equations per pair (float64)
+        if model == "H":
+            w = torch.cat([mask, mask]).to(torch.float64)
+            seg = torch.cat([pair_of, pair_of])
+        else:
+            w, seg = mask.to(torch.float64), pair_of
+        AtA = torch.zeros((P, 8, 8), dtype=torch.float64, device=dev).index_add_(0, seg, (Ar[:, :, None] * Ar[:, None, :]) * w[:, None, None])
+        Atb = torch.zeros((P, 8), dtype=torch.float64, device=dev).index_add_(0, seg, Ar * (br * w)[:, None])
+        rsol = torch.linalg.solve_ex(AtA, Atb.unsqueeze(-1)).result.squeeze(-1)
+        refit = _denormalise(model, _to_matrix(rsol)[:, None], T1, T2).reshape(P, 9)
+        ok = torch.isfinite(rsol).all(dim=-1) & (nbest >= S)
+        return torch.where(ok[:, None], refit, torch.full_like(refit, float("nan"))).to(torch.float32).contiguous(), ok
+
+    return _ransac_tail(pts, offsets, hyp32, counts, model, max_error, refit)[:3]
 
 
 def _stored_f(f9):
@@ -178,14 +115,10 @@ def _stored_f(f9):
 def _estimate_calibrated(cal, sel, pts_np, pair_images, pair_ids, cameras, device, max_error):
     """The E estimate of the chunk's calibrated pairs `cal` (positions in `sel`) as one batch of their own
     -> {position: dict(n, E, f9, mask, xn)} (matching/essential.py)."""
-    from . import essential
-
     K, _ = cameras
-    pts = torch.from_numpy(np.concatenate([pts_np[q] for q in cal])).to(device).contiguous()
-    offs = np.concatenate([[0], np.cumsum([len(pts_np[q]) for q in cal])])
-    offsets = torch.tensor(offs, dtype=torch.int32, device=device)
-    pair_of = torch.repeat_interleave(torch.arange(len(cal), device=device), (offsets[1:] - offsets[:-1]).to(torch.int64))
-    seeds = torch.tensor([int(pair_ids[sel[q]]) & _M32 for q in cal], dtype=torch.int64, device=device)
+    rows = [pts_np[q] for q in cal]
+    offs = np.cumsum([0] + [len(r) for r in rows])
+    pts, offsets, pair_of, seeds = _pair_batch(rows, [pair_ids[sel[q]] for q in cal], device)
     K1 = torch.from_numpy(np.stack([K[pair_images[sel[q]][0]] for q in cal]).astype(np.float64)).to(device)
     K2 = torch.from_numpy(np.stack([K[pair_images[sel[q]][1]] for q in cal]).astype(np.float64)).to(device)
     with torch.cuda.device(pts.device):
@@ -198,8 +131,6 @@ def _estimate_calibrated(cal, sel, pts_np, pair_images, pair_ids, cameras, devic
 def _relative_poses(posed, sel, results, pair_images, cameras, est_e, device, max_error):
     """Relative pose of the chunk's qualifying pairs `posed` [(position in `sel`, inlier mask)] as one batch (matching/pose.py):
     a PLANAR_OR_PANORAMIC pair is decomposed from its H, any other from E where the best model is E, else from its F."""
-    from .pose import relative_poses
-
     entries = []
     for q, mask in posed:
         r = results[sel[q]]
@@ -214,6 +145,25 @@ def _relative_poses(posed, sel, results, pair_images, cameras, est_e, device, ma
                             xn=est_e[q]["xn"][mask]))
     for (q, _), pose in zip(posed, relative_poses(entries, device, max_error)):
         results[sel[q]].update(pose)
+
+
+def pair_decision(M, n_f, n_h, n_e=None):
+    """The rule for one pair, on the numbers alone: M putative matches, the inlier counts of its F and H and, where both
+    cameras have a usable prior, of its E (None: not estimated) -> (config, best, model).  `best` is the two-view model that
+    reaches max(15, 0.25 M) inliers — "E" where n_e also reaches 0.95 n_f, else "F"; (DEGENERATE, None, None) where neither
+    does.  With n the count of `best`: n_h / n > 0.8 makes the pair PLANAR_OR_PANORAMIC, and n_h > n hands the inliers to H.
+    `model` ("F" or "H") is the model whose mask gives `inlier_matches`: H's, or that of `best` (E's mask is that of its
+    pixel F)."""
+    floor = max(MIN_NUM_INLIERS, MIN_INLIER_RATIO * M)
+    if n_e is not None and n_e >= floor and n_e >= MIN_E_F_INLIER_RATIO * n_f:
+        best, n, config = "E", n_e, CONFIG_CALIBRATED
+    elif n_f >= floor:
+        best, n, config = "F", n_f, CONFIG_UNCALIBRATED
+    else:
+        return CONFIG_DEGENERATE, None, None
+    if n_h / n > MAX_H_INLIER_RATIO:
+        config = CONFIG_PLANAR_OR_PANORAMIC
+    return config, best, "H" if n_h > n else "F"
 
 
 @torch.no_grad()
@@ -238,17 +188,14 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
     todo = [i for i, m in enumerate(match_lists) if len(m) >= MIN_NUM_INLIERS]
     for c0 in range(0, len(todo), chunk_pairs):
         sel = todo[c0:c0 + chunk_pairs]
-        pts_np, offs = [], [0]
+        pts_np = []
         for i in sel:
             a, b = pair_images[i]
             m = np.asarray(match_lists[i], np.int64).reshape(-1, 2)
             pts_np.append(np.concatenate([keypoints[a][m[:, 0], :2], keypoints[b][m[:, 1], :2]], axis=1).astype(np.float32))
-            offs.append(offs[-1] + len(m))
-        pts = torch.from_numpy(np.concatenate(pts_np)).to(device).contiguous()
-        offsets = torch.tensor(offs, dtype=torch.int32, device=device)
+        offs = np.cumsum([0] + [len(p) for p in pts_np])
+        pts, offsets, pair_of, seeds = _pair_batch(pts_np, [pair_ids[i] for i in sel], device)
         P = len(sel)
-        pair_of = torch.repeat_interleave(torch.arange(P, device=device), (offsets[1:] - offsets[:-1]).to(torch.int64))
-        seeds = torch.tensor([int(pair_ids[i]) & _M32 for i in sel], dtype=torch.int64, device=device)
         with torch.cuda.device(pts.device):
             f9, fmask, nf = _estimate("F", pts, offsets, pair_of, seeds, num_f, max_error)
             h9, hmask, nh = _estimate("H", pts, offsets, pair_of, seeds, num_h, max_error)
@@ -264,50 +211,33 @@ def verify_pairs(keypoints, pair_images, pair_ids, match_lists, device="cuda", n
         fmask, hmask, nf, nh = fmask.cpu().numpy(), hmask.cpu().numpy(), nf.cpu().numpy(), nh.cpu().numpy()
         f9_np, h9_np = f9.cpu().numpy(), h9.cpu().numpy()
         cal = [] if cameras is None else [q for q, i in enumerate(sel) if cameras[1][pair_images[i][0]] and cameras[1][pair_images[i][1]]]
-        est_e, posed = {}, []
-        if cal:
-            from .essential import MIN_E_F_INLIER_RATIO, choose_pose
-
-            est_e = _estimate_calibrated(cal, sel, pts_np, pair_images, pair_ids, cameras, device, max_error)
+        posed = []
+        est_e = _estimate_calibrated(cal, sel, pts_np, pair_images, pair_ids, cameras, device, max_error) if cal else {}
         for q, i in enumerate(sel):
-            r = results[i]
+            r, e = results[i], est_e.get(q)
             r["n_f"], r["n_h"] = int(nf[q]), int(nh[q])
-            floor = max(MIN_NUM_INLIERS, MIN_INLIER_RATIO * len(match_lists[i]))
-            e = est_e.get(q)
             if e is not None:
                 r["n_e"] = e["n"]
-                if e["n"] >= floor and e["n"] >= MIN_E_F_INLIER_RATIO * r["n_f"]:      # the best model is E
-                    lo, hi = offs[q], offs[q + 1]
-                    r["E"], r["F"] = e["E"], _stored_f(e["f9"])
-                    r["H"] = H[q] / H[q][2, 2] if H[q][2, 2] != 0 else H[q]
-                    r["config"], mask, r["model"], r["model9"] = CONFIG_CALIBRATED, e["mask"], "F", e["f9"].copy()
-                    if r["n_h"] / e["n"] > MAX_H_INLIER_RATIO:
-                        r["config"] = CONFIG_PLANAR_OR_PANORAMIC
-                        if r["n_h"] > e["n"]:
-                            mask, r["model"], r["model9"] = hmask[lo:hi], "H", h9_np[q].copy()
-                    if relative_pose:
-                        posed.append((q, mask))
-                    else:
-                        r["qvec"], r["tvec"] = choose_pose(e["E"], e["xn"][e["mask"]])
-                    r["inlier_matches"] = np.asarray(match_lists[i], np.uint32).reshape(-1, 2)[mask]
-                    continue
-            if r["n_f"] < floor:
+            config, best, model = pair_decision(len(match_lists[i]), r["n_f"], r["n_h"], r.get("n_e"))
+            if best is None:
                 continue
-            r["F"] = F2[q]
-            r["H"] = H[q] / H[q][2, 2] if H[q][2, 2] != 0 else H[q]
             lo, hi = offs[q], offs[q + 1]
-            if r["n_h"] / r["n_f"] > MAX_H_INLIER_RATIO:
-                r["config"] = CONFIG_PLANAR_OR_PANORAMIC
-                mask = hmask[lo:hi] if r["n_h"] > r["n_f"] else fmask[lo:hi]
-                r["model"] = "H" if r["n_h"] > r["n_f"] else "F"
+            r["config"], r["model"] = config, model
+            r["H"] = H[q] / H[q][2, 2] if H[q][2, 2] != 0 else H[q]
+            if best == "E":
+                r["E"], r["F"] = e["E"], _stored_f(e["f9"])
+                mask, m9 = e["mask"], e["f9"]
             else:
-                r["config"] = CONFIG_UNCALIBRATED
-                mask = fmask[lo:hi]
-                r["model"] = "F"
-            r["model9"] = (h9_np if r["model"] == "H" else f9_np)[q].copy()
+                r["F"] = F2[q]
+                mask, m9 = fmask[lo:hi], f9_np[q]
+            if model == "H":
+                mask, m9 = hmask[lo:hi], h9_np[q]
+            r["model9"] = m9.copy()
             r["inlier_matches"] = np.asarray(match_lists[i], np.uint32).reshape(-1, 2)[mask]
             if relative_pose and e is not None:
                 posed.append((q, mask))
+            elif best == "E":
+                r["qvec"], r["tvec"] = choose_pose(e["E"], e["xn"][e["mask"]])
         if posed:
             _relative_poses(posed, sel, results, pair_images, cameras, est_e, device, max_error)
     return results
@@ -357,8 +287,6 @@ def write_two_view_rows(db, ids, results) -> int:
 def verify_database_pairs(db, ids, merged, device="cuda", verify_fn=None) -> int:
     """Single-process form: verify every matched pair of a database that is open for writing and write its rows.
     `merged`: {(a, b): uint32 (M, 2)} with a < b image indices into `ids`.  Returns the number of verified pairs."""
-    from .essential import camera_table
-
     pairs = sorted(merged)
     res = verify_pair_lists(read_keypoints_by_index(db, ids), ids, pairs, [merged[p] for p in pairs], device=device,
                             verify_fn=verify_fn, cameras=camera_table(db, ids))

@@ -10,7 +10,8 @@ torch.distributed process group with more than one rank exists (one process per 
      image row per readable image, in file order (reference vit_extractor.py:739: a failed image still has its row);
   4. rank 0 writes keypoints / descriptors; the exhaustive pair list is dealt round-robin, every rank matches
      and geometrically verifies its share from the gathered blocks and keypoints (no database read); the match lists
-     and two-view geometries are gathered to rank 0, which writes them in pair order.
+     and two-view geometries are gathered to rank 0, which writes them in pair order (matching/exhaustive.py:
+     match_loaded, the body that match_exhaustive runs on what it read from a database).
 An error on any rank (rank 0's database included) is raised on every rank instead of leaving the others in a collective
 (dist.raise_if_any_failed).
 The reference is single-process; there is no counterpart to cite beyond the plugin API it keeps
@@ -28,7 +29,11 @@ import numpy as np
 import torch
 
 from .. import dist as vd
+from ..database.colmap_db import ColmapDatabase
 from ..features.base_extractor import add_image_row, camera_policy, default_camera_params, image_batches, list_images
+from ..matching.essential import camera_table
+from ..matching.exhaustive import MatchSettings, match_loaded, new_stats
+from ..matching.hip_matcher import exhaustive_pairs
 
 logger = logging.getLogger(__name__)
 
@@ -37,10 +42,6 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
                 match_fn=None, do_matching=True, verify=True, device="cuda", batch_size=50, verify_fn=None,
                 camera_params_for=default_camera_params, camera_per_image=False, guided_fn=None,
                 prior_focal_length=False, matcher_type="exhaustive") -> dict:
-    from ..database.colmap_db import ColmapDatabase
-    from ..matching.exhaustive import (_guided_option, _relative_pose_option, _sift_options, check_guided_block_size,
-                                       hip_guided_blocks, hip_match_blocks, rematch_guided)
-
     if matcher_type != "exhaustive":
         # the in-memory path matches every pair; the choice of pairs exists database to database only
         raise ValueError(f"the sharded in-memory pipeline matches exhaustively: for matcher_type {matcher_type!r} extract to "
@@ -82,87 +83,44 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
         raise ValueError(f"Failed to read first image: {image_files[0]}")
 
     # ---- rank 0: camera and image rows in file order, then features ------------------------------------------------------
-    stats = dict(images=int(all_readable.sum()), ranks=world, pairs=0, matches=0, verified_pairs=0)
-    ids = None
+    stats = new_stats(int(all_readable.sum()), 0, world)
     db = None
-    err = None
-    cameras = None
     cnt = all_counts.cpu().numpy()
     kp_np = all_kps.cpu().numpy()
-    if rank == 0:
-        try:
-            camera_of = camera_policy(camera_model, camera_params, all_hw[0], camera_params_for, camera_per_image,
-                                      prior_focal_length)
-            db = ColmapDatabase(str(db_path))
-            ids = [add_image_row(db, f.name, camera_of(h, w)) if h else None for f, (h, w) in zip(image_files, all_hw)]
-            if prior_focal_length:
-                from ..matching.essential import camera_table
 
-                cameras = camera_table(db.db, ids)                     # (K, usable prior) per file, read back from the rows
-            d_np = all_desc.cpu().numpy()
-            for k, image_id in enumerate(ids):
-                if image_id is not None and cnt[k] > 0:
-                    db.add_keypoints(image_id, kp_np[k, : cnt[k]])
-                    db.add_descriptors(image_id, d_np[k, : cnt[k]])
-            db.commit()
-        except Exception as e:  # noqa: BLE001 - handed to every rank below
-            err = e
+    def write_rows():
+        nonlocal db
+        camera_of = camera_policy(camera_model, camera_params, all_hw[0], camera_params_for, camera_per_image,
+                                  prior_focal_length)
+        db = ColmapDatabase(str(db_path))
+        ids = [add_image_row(db, f.name, camera_of(h, w)) if h else None for f, (h, w) in zip(image_files, all_hw)]
+        cameras = camera_table(db.db, ids) if prior_focal_length else None   # (K, usable prior) per file, read back from the rows
+        d_np = all_desc.cpu().numpy()
+        for k, image_id in enumerate(ids):
+            if image_id is not None and cnt[k] > 0:
+                db.add_keypoints(image_id, kp_np[k, : cnt[k]])
+                db.add_descriptors(image_id, d_np[k, : cnt[k]])
+        db.commit()
+        return ids, cameras
+
     try:
-        vd.raise_if_any_failed(err, "writing images / features")
+        rows = vd.run_guarded(write_rows, "writing images / features")
         if not do_matching:
             return stats
         # ---- matching + verification: images with a database row, in id order; pairs dealt round-robin -----------------
-        from ..matching.two_view import verify_pair_lists, write_two_view_rows
-
-        ids = vd.broadcast_object(ids, 0)                                   # pair ids seed the verification sampler
+        ids, cameras = vd.broadcast_object(rows, 0)                          # pair ids seed the verification sampler
         keep = np.nonzero(all_readable)[0]
-        if prior_focal_length:                                              # calibrated pairs
-            cameras = vd.broadcast_object(cameras, 0)
+        if cameras is not None:                                             # calibrated pairs
             cameras = (cameras[0][keep], cameras[1][keep])
         m = len(keep)
         stats["pairs"] = m * (m - 1) // 2
-        sift = _sift_options(matching_options, None)
-        r_, d_, c_ = float(sift.max_ratio), float(sift.max_distance), bool(sift.cross_check)
-        blocks = all_desc[torch.from_numpy(keep).to(all_desc.device)]
-        bcounts = all_counts[torch.from_numpy(keep).to(all_counts.device)]
-        kept_ids = [ids[k] for k in keep]
-        my_pairs = vd.pairs_for_rank(m, rank, world)
-        guided = _guided_option(matching_options, None) and verify            # the options' guided_matching
-        err, lists, results = None, [], None
-        try:
-            if guided:
-                check_guided_block_size(int(blocks.shape[1]))                   # before any matching starts
-            if match_fn is None:
-                lists = hip_match_blocks(blocks, bcounts, my_pairs, r_, d_, c_, device=device)
-            else:
-                lists = match_fn(blocks.cpu().numpy(), bcounts.cpu().numpy(), my_pairs, r_, d_, c_)
-            if verify:                                                          # every rank verifies the pairs it matched
-                kps = {i: kp_np[k, : cnt[k], :2] for i, k in enumerate(keep)}
-                results = verify_pair_lists(kps, kept_ids, my_pairs, lists, device=device, verify_fn=verify_fn, cameras=cameras,
-                                            relative_pose=_relative_pose_option(matching_options, None))
-                if guided:                                                      # ... and re-matches them under their models
-                    if guided_fn is None:
-                        def guided_fn(blk, cts, kp_xy, prs, models, kinds, e, r, dmax, cc):
-                            return hip_guided_blocks(blk, cts, kp_xy, prs, models, kinds, e, r, dmax, cc, device=device)
-                    rematch_guided(blocks, bcounts, kp_np[keep][:, :, :2], my_pairs, results, r_, d_, c_, guided_fn)
-        except Exception as e:  # noqa: BLE001
-            err = e
-        vd.raise_if_any_failed(err, "matching / verification")
-        merged = vd.gather_pair_lists(my_pairs, lists, dst=0)
-        verified = vd.gather_pair_results(my_pairs, results, dst=0) if results is not None else None
-        err = None
-        if rank == 0:
-            try:
-                for (a, b), lst in sorted(merged.items()):
-                    db.db.write_matches(kept_ids[a], kept_ids[b], lst, commit=False)
-                    stats["matches"] += len(lst)
-                db.commit()
-                if verified is not None:
-                    stats["verified_pairs"] = write_two_view_rows(db.db, kept_ids, verified)
-            except Exception as e:  # noqa: BLE001
-                err = e
-        vd.raise_if_any_failed(err, "writing matches / two-view geometries")
-        return vd.broadcast_object(stats, 0)                                    # every rank returns rank 0's totals
+        return match_loaded([ids[k] for k in keep], all_desc[torch.from_numpy(keep).to(all_desc.device)],
+                            all_counts[torch.from_numpy(keep).to(all_counts.device)], kp_np[keep][:, :, :2], cnt[keep], cameras,
+                            exhaustive_pairs(m).numpy(), vd.pairs_for_rank(m, rank, world),
+                            MatchSettings.from_options(matching_options, None, verify), verify,
+                            db.db if db is not None else None, stats, match_fn=match_fn, verify_fn=verify_fn,
+                            guided_fn=guided_fn, device=device, distributed=vd.is_distributed(),
+                            write_what="writing matches / two-view geometries")
     finally:
         if db is not None:
             db.db.close()
