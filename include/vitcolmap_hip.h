@@ -358,8 +358,11 @@ int vc_layernorm_drop_first_bf16(const void* x, const void* gamma, const void* b
  * qkv [batch][n_tokens][3][n_heads][64] bfloat16 (the fused qkv projection's output as it is),
  * out [batch][n_tokens][n_heads*64] bfloat16 (what the output projection reads).  16-byte aligned.
  * q_prescaled != 0: the q part of qkv already carries the factor (1/8) * log2(e) (fold it into the rows of the qkv
- * projection that produce q, weights and bias): the kernel then subtracts the running row maximum inside the matrix
- * product and evaluates exp2 of the accumulator directly — one float instruction less per score, same softmax.
+ * projection that produce q, weights and bias): the kernel then subtracts the row maximum inside the matrix product and
+ * evaluates exp2 of the accumulator directly — one float instruction less per score, same softmax.  The maximum is that of
+ * the first 64 keys; if later scores of any row in a block of 128 or 256 query rows exceed it so far that the row's sum of
+ * exp2(score - maximum) passes 64 * n_tokens, the block is recomputed with the running maximum and rescale, at about twice
+ * the time for that block.  NaN inputs give NaN rows.
  */
 int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int head_dim, int q_prescaled,
                       void* out, vc_stream_t stream);

@@ -20,9 +20,12 @@
 //     issued before the block's MFMAs, the LDS writes after them), double buffered, one barrier
 //     per block; both tiles are XOR-swizzled against bank conflicts (K: 16-byte slot ^ (key & 7)
 //     for the ds_read_b128 column slices; V: byte bit 6 ^ bit 1 of the key for the transposed reads);
-//   * online softmax in exp2 domain with the rescale skipped when no row maximum moved.
+//   * softmax in exp2 domain: with pre-scaled q a pass that keeps the first key block's row maximum as its reference and
+//     checks the range once per unit, backed by the exact online-softmax pass for units that leave it (see attention_kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/vitcolmap_hip.h"
 #include "common.h"
@@ -50,15 +53,35 @@ __device__ inline uint32_t v_off(int key, int byte_in_row) {
 
 // QT = 32-query tiles per wave.  QT = 2 reads every K / V fragment from LDS once for two MFMAs and
 // stages every K / V tile once for 256 instead of 128 query rows (at 2 waves per SIMD instead of 3).
-// LAZY: the queries arrive already multiplied by scale * log2(e) (folded into the qkv projection), and from the
-// second key block on the running maximum is subtracted INSIDE the matrix product — it is the accumulator's
-// initial value — so a probability is exp2(accumulator) with no v_fma_f32 per score, and the per-block maximum
-// is only an integer test "some score exceeds the running maximum by more than kLazyTh" (float bit patterns of
-// positive numbers order as integers).  Any reference value gives the same softmax after normalisation; the
-// exact maximum is re-established (standard rescale) when the test fires, so probabilities stay <= 2^kLazyTh.
-// The softmax over-subscribes the SIMD's issue port (~11 slots per MFMA gap against the ~6 that hide,
-// profiles/r02_overlap_probe.md): removing one of the five VALU issue slots per score is a direct saving.
+// LAZY: the queries arrive already multiplied by scale * log2(e) (folded into the qkv projection), so a score is a base-2
+// exponent as it leaves the matrix product.  Block 0 takes the standard update (exact row maximum m0); from the second key
+// block on the running maximum is subtracted INSIDE the matrix product — it is the accumulators' initial value — so a
+// probability is exp2(accumulator) with no v_fma_f32 per score.  A unit is computed in up to two passes over its key blocks,
+// both instantiated from one loop body:
+//   * the FAST pass never looks at a later block's maximum: m0 stays the reference to the end, p = exp2(s - m0), l = sum p,
+//     O = sum p v.  Any reference value gives the same softmax after normalisation, and float32 / bf16 carry the same
+//     relative precision at every scale, so only the RANGE can fail, and only upwards: the row's own block-0 maximum
+//     contributes p = 1, so l >= 1 and what underflows is negligible against it.  Per score that leaves v_exp_f32, the
+//     row-sum add and the bf16 pack: no maximum test, no ballot, no branch in the loop.  The softmax over-subscribes the
+//     SIMD's issue port (~11 slots per MFMA gap against the ~6 that hide, profiles/r02_overlap_probe.md), so every VALU
+//     instruction removed here is a direct saving.  Where the EXACT pass's test would never have fired — scores that stay
+//     within kLazyTh of the block-0 maximum, the common case — the FAST pass performs exactly the EXACT pass's operations
+//     in its order, so the results are bit-identical to it;
+//   * after the last block each query row is tested once: l <= N * 2^kLazyTh and its normalised outputs finite.  While no
+//     score exceeds m0 by more than kLazyTh every p is <= 2^kLazyTh, so a larger l proves that the EXACT pass's test would
+//     have fired for the row; such rows go to the EXACT pass, which re-centres a row on its largest score (that key's p is
+//     then exactly 1, where a p of 2^x here carries a bf16 rounding error that the row sum, taken before the rounding, does
+//     not share — visible in rows that a single far-out key dominates).  The bound also keeps l and 1 / l far inside
+//     float32; an O that overflows all the same (|v| near the top of bf16) is +-inf or NaN to the end and fails "finite";
+//   * if ANY row of the workgroup's unit fails (a workgroup-wide OR: the loop's barriers pair across the four waves, so no
+//     wave can repeat it alone), blocks 0 and 1 are staged again and the unit is recomputed by the EXACT pass: the
+//     per-block maximum is an integer test "some score exceeds the running maximum by more than kLazyTh" (float bit
+//     patterns of positive numbers order as integers), and the exact maximum is re-established (standard rescale) when it
+//     fires, so probabilities stay <= 2^kLazyTh.  At most one redo per unit; such a unit costs about twice the time.  NaN
+//     inputs give NaN rows either way.
+// LAZY = false (q not pre-scaled) needs the multiply by scale_log2e per score anyway and runs the exact pass only.
 constexpr float kLazyTh = 6.0f;
+constexpr float kLMaxPerKey = 64.0f;   // 2^kLazyTh: the fast pass is final for a row with l <= N * this
 template <int QT, bool LAZY>
 __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const __bf16* __restrict__ qkv,
                                                                            __bf16* __restrict__ out, int N, int H,
@@ -145,6 +168,16 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
 
   v16f acc_o[QT][2];
   float m_run[QT], l_run[QT];
+
+  // transposed-read addressing: 16-lane group g, lane i of the group supplies row q = i>>2,
+  // columns 4p..4p+3 (p = i&3) of a 4-key x 16-d block
+  const int grp = lane >> 4, gi = lane & 15, tq = gi >> 2, tp = gi & 3;
+
+  // One pass over every key block of the unit.  FAST (LAZY only) is the pass without the maximum test, otherwise the exact one; both are
+  // this one body, instantiated once each, so that the fast loop's registers are allocated without the exact pass's state.
+  // Blocks 0 and 1 are in flight (issue_block) and nothing else is pending when a pass starts.
+  auto run_pass = [&](auto fast_c) __attribute__((always_inline)) {
+  constexpr bool FAST = decltype(fast_c)::value;
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     m_run[qt] = -1e30f;
@@ -154,11 +187,6 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc_o[qt][dt][i] = 0.f;
   }
-
-  // transposed-read addressing: 16-lane group g, lane i of the group supplies row q = i>>2,
-  // columns 4p..4p+3 (p = i&3) of a 4-key x 16-d block
-  const int grp = lane >> 4, gi = lane & 15, tq = gi >> 2, tp = gi & 3;
-
   int slot = 0;
   for (int blk = 0; blk < n_blk; ++blk) {
     // this wave's 4 pieces of block blk have landed when at most the 4 of block blk+1 are pending
@@ -211,13 +239,18 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       if (LAZY && blk > 0) {
-        // scores are relative to the running maximum already; integer test for "one of them is too large"
-        int imax = __float_as_int(acc_s[qt][0][0]);
+        // scores are relative to the running maximum already.  EXACT pass: integer test for "one of them is too large";
+        // FAST pass: no test, the maximum of block 0 stays the reference to the end
+        bool in_reach = true;
+        if constexpr (!FAST) {
+          int imax = __float_as_int(acc_s[qt][0][0]);
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+          for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) imax = max(imax, __float_as_int(acc_s[qt][t][i]));
-        if (!__any(imax > __float_as_int(kLazyTh))) {
+            for (int i = 0; i < 16; ++i) imax = max(imax, __float_as_int(acc_s[qt][t][i]));
+          in_reach = !__any(imax > __float_as_int(kLazyTh));
+        }
+        if (in_reach) {
           float lsum[4] = {0.f, 0.f, 0.f, 0.f};   // four independent chains: an add never waits for its predecessor
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
@@ -292,7 +325,36 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
     }
     slot = slot == 2 ? 0 : slot + 1;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the two clamped refills before exiting
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the two clamped refills: the ring is idle after a pass
+  };
+
+  if constexpr (LAZY) {
+    run_pass(std::true_type{});
+    // ---- was every row of the unit in range?  (window: see the header comment) -------------------------------------------
+    const float l_max = (float)N * kLMaxPerKey;
+    bool bad = false;
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+      const float l_tot = l_run[qt] + __shfl_xor(l_run[qt], 32);
+      const float inv = 1.0f / l_tot;
+      float oabs[4] = {0.f, 0.f, 0.f, 0.f};   // sum of |normalised output|: an infinity or a NaN anywhere stays in it
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) oabs[i & 3] = __builtin_fmaf(__builtin_fabsf(acc_o[qt][dt][i]), inv, oabs[i & 3]);
+      const float osum = (oabs[0] + oabs[1]) + (oabs[2] + oabs[3]);
+      bad |= !(l_tot <= l_max) || !(osum <= 3.0e38f);   // written so that a NaN fails
+    }
+    // The verdict is the workgroup's (its barrier also orders every wave's last LDS read before the refill): the loop's
+    // s_barriers pair across the four waves, so no wave may run it again alone.
+    if (__syncthreads_or(bad)) {
+      issue_block(0, 0);
+      issue_block(1, 1);
+      run_pass(std::false_type{});
+    }
+  } else {
+    run_pass(std::false_type{});
+  }
 
   // ---- normalise and store: lane (query r, half hh) holds d = (i&3) + 8(i>>2) + 4hh + 32dt -------
   // Stored from that layout (16 stores of 8 bytes per lane, 32 rows per instruction) the tail of a unit is bound by store
