@@ -217,6 +217,37 @@ int vc_two_view_pose(const double* pts_n, const int32_t* offsets, int n_pairs, c
                      vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image registration: absolute pose from 2D-3D correspondences, for n_hyp samples of each of
+ * n_prob registration problems (one problem: one image against the model's points).  Specification:
+ * tests/util_absolute_pose.py.
+ *   offsets    [n_prob + 1] int32: problem p owns rows offsets[p] .. offsets[p+1]) of the per-correspondence arrays
+ * vc_p3p — the minimal solver, float64 throughout: every pose (R, t), X_cam = R X + t, that maps three world points onto
+ * their three image rays with positive depths.
+ *   rays_n     [total][2] float64: the image points in normalised camera coordinates (K^-1 applied)
+ *   xyz        [total][3] float64: the world points
+ *   samples    [n_prob][n_hyp][3] int32 indices into the problem's own list; samples[..][0] < 0: the hypothesis is void
+ *   out_pose   [n_prob][n_hyp][4][12] float64: R row-major then t, ascending in the solver's root variable (the depth
+ *              ratio s2 / s1); the slots past out_count are NaN
+ *   out_count  [n_prob][n_hyp] int32: 0 .. 4.  0 for a void sample, an index outside the problem's list, a repeated index,
+ *              two coincident world points or rays, collinear world points, non-finite input and a quartic without a
+ *              finite non-zero coefficient; a pose that is not finite and proper (|det R - 1| < 1e-9) is never counted.
+ * Every iterative part runs a bounded number of steps.  n_prob * n_hyp above 64 * (2^31 - 1): VC_ERR_UNSUPPORTED.
+ * vc_absolute_pose_score / vc_absolute_pose_inliers — float32, no division, in the specification's operation order:
+ * p = P (X, 1); inlier iff p_w > 0 and |p_xy - obs p_w|^2 <= max_error^2 p_w^2.
+ *   obs        [total][2] float32 pixels, 8-byte aligned
+ *   xyz4       [total][4] float32 world points, w ignored, 16-byte aligned
+ *   hyp        [n_prob][n_hyp][12] float32: row-major 3x4 pixel projection matrices P = K [R | t] -> out_counts
+ *              [n_prob][n_hyp] (a NaN hypothesis counts 0).  n_prob above 65535 * 32: VC_ERR_UNSUPPORTED.
+ *   models     [n_prob][12] -> out_mask [total] uint8
+ * ------------------------------------------------------------------------------------------ */
+int vc_p3p(const double* rays_n, const double* xyz, const int32_t* offsets, int n_prob, const int32_t* samples, int n_hyp,
+           double* out_pose, int32_t* out_count, vc_stream_t stream);
+int vc_absolute_pose_score(const float* obs, const float* xyz4, const int32_t* offsets, int n_prob, const float* hyp, int n_hyp,
+                           float max_error, int32_t* out_counts, vc_stream_t stream);
+int vc_absolute_pose_inliers(const float* obs, const float* xyz4, const int32_t* offsets, int n_prob, const float* models,
+                             float max_error, uint8_t* out_mask, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

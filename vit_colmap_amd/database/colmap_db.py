@@ -309,6 +309,11 @@ class SqliteColmapDatabase:
             m, F, E, H, qvec, tvec = _swap_two_view(m, F, E, H, qvec, tvec)
         return dict(inlier_matches=np.ascontiguousarray(m), config=int(config), F=F, E=E, H=H, qvec=qvec, tvec=tvec)
 
+    def read_two_view_geometry_pairs(self):
+        """-> [(image_id1, image_id2, rows, config)] of every two_view_geometries row, ascending in pair_id."""
+        return [pair_id_to_image_ids(int(pid)) + (int(rows), int(config)) for pid, rows, config in
+                self._conn.execute("SELECT pair_id, rows, config FROM two_view_geometries ORDER BY pair_id")]
+
     def read_matches(self, image_id1: int, image_id2: int):
         m = self._read_blob("matches", "pair_id", pair_id_of(image_id1, image_id2), np.uint32)
         if m is not None and image_id1 > image_id2:

@@ -1,0 +1,268 @@
+"""The seed model: an initial pair, that pair's triangulated points, every other image registered against
+those points in one batched launch, written as a COLMAP text model.  It is NOT a mapper: no point is triangulated after the
+seed, there is no bundle adjustment and no second registration round.  Specification: tests/util_absolute_pose.py
+(`seed_model`).  This build's own published rule; parity with COLMAP's mapper is unpinned.
+
+Where the work runs
+  HIP     the triangulation of every candidate pair's inliers (vc_two_view_pose, one launch over all candidates) and the
+          registration of every other image (mapping/absolute_pose.py, one batch)
+  host    the database rows, the choice of the pair, the per-point filters (numpy on one pair's inliers), the tracks
+"""
+import logging
+import os
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from ..database.colmap_db import Camera, ColmapDatabase, _quat_to_rot
+from ..matching._common import CONFIG_CALIBRATED, MAX_ERROR
+from ..matching.essential import camera_prior
+from .absolute_pose import (ABS_POSE_MIN_NUM_INLIERS, FILTER_MIN_TRI_ANGLE, INIT_MIN_NUM_INLIERS, INIT_MIN_TRI_ANGLE,
+                            estimate_absolute_poses)
+
+logger = logging.getLogger(__name__)
+
+SEED_CAMERA_MODELS = ("SIMPLE_PINHOLE", "PINHOLE")
+
+
+@dataclass
+class SparseModel:
+    """cameras {camera_id: Camera}; images {image_id: dict(qvec (w, x, y, z), tvec, camera_id, name, xys float64 (n, 2),
+    point3D_ids int64 (n,), -1 where the keypoint observes no point)}, X_cam = R(qvec) X + tvec; points3D {point3D_id:
+    dict(xyz, rgb, error, track [(image_id, keypoint index)])}; initial_pair (image_id, image_id) or None."""
+
+    cameras: dict = field(default_factory=dict)
+    images: dict = field(default_factory=dict)
+    points3D: dict = field(default_factory=dict)
+    initial_pair: tuple = None
+
+    def mean_track_length(self):
+        return float(np.mean([len(p["track"]) for p in self.points3D.values()])) if self.points3D else 0.0
+
+    def stats(self):
+        return dict(initial_pair=list(self.initial_pair) if self.initial_pair else None, registered_images=len(self.images),
+                    num_points3D=len(self.points3D), mean_track_length=self.mean_track_length())
+
+    # COLMAP's text layout [recalled: colmap/src/colmap/scene/reconstruction_io.cc]; floats are written with repr, so a model
+    # reads back equal
+    def write_text(self, directory):
+        os.makedirs(directory, exist_ok=True)
+        with open(os.path.join(directory, "cameras.txt"), "w") as f:
+            f.write("# Camera list with one line of data per camera:\n#   CAMERA_ID, MODEL, WIDTH, HEIGHT, PARAMS[]\n")
+            f.write(f"# Number of cameras: {len(self.cameras)}\n")
+            for cid in sorted(self.cameras):
+                c = self.cameras[cid]
+                f.write(" ".join([str(cid), c.model, str(int(c.width)), str(int(c.height))] + [repr(float(v)) for v in c.params]) + "\n")
+        with open(os.path.join(directory, "images.txt"), "w") as f:
+            n_obs = sum(int((im["point3D_ids"] >= 0).sum()) for im in self.images.values())
+            f.write("# Image list with two lines of data per image:\n#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME\n"
+                    "#   POINTS2D[] as (X, Y, POINT3D_ID)\n")
+            f.write(f"# Number of images: {len(self.images)}, mean observations per image: {n_obs / max(len(self.images), 1)}\n")
+            for iid in sorted(self.images):
+                im = self.images[iid]
+                f.write(" ".join([str(iid)] + [repr(float(v)) for v in list(im["qvec"]) + list(im["tvec"])]
+                                 + [str(int(im["camera_id"])), im["name"]]) + "\n")
+                f.write(" ".join(f"{float(x)!r} {float(y)!r} {int(p)}" for (x, y), p in zip(im["xys"], im["point3D_ids"])) + "\n")
+        with open(os.path.join(directory, "points3D.txt"), "w") as f:
+            f.write("# 3D point list with one line of data per point:\n"
+                    "#   POINT3D_ID, X, Y, Z, R, G, B, ERROR, TRACK[] as (IMAGE_ID, POINT2D_IDX)\n")
+            f.write(f"# Number of points: {len(self.points3D)}, mean track length: {self.mean_track_length()}\n")
+            for pid in sorted(self.points3D):
+                p = self.points3D[pid]
+                f.write(" ".join([str(pid)] + [repr(float(v)) for v in p["xyz"]] + [str(int(v)) for v in p["rgb"]]
+                                 + [repr(float(p["error"]))] + [f"{int(i)} {int(k)}" for i, k in p["track"]]) + "\n")
+
+    @classmethod
+    def read_text(cls, directory):
+        def lines(name):
+            with open(os.path.join(directory, name)) as f:
+                return [ln.rstrip("\n") for ln in f if not ln.startswith("#")]
+
+        model = cls()
+        for ln in lines("cameras.txt"):
+            w = ln.split()
+            if w:
+                model.cameras[int(w[0])] = Camera(model=w[1], width=int(w[2]), height=int(w[3]), params=[float(v) for v in w[4:]],
+                                                  camera_id=int(w[0]))
+        rows = lines("images.txt")
+        for head, pts in zip(rows[0::2], rows[1::2]):
+            w, q = head.split(), pts.split()
+            model.images[int(w[0])] = dict(
+                qvec=np.array([float(v) for v in w[1:5]]), tvec=np.array([float(v) for v in w[5:8]]), camera_id=int(w[8]),
+                name=" ".join(w[9:]), xys=np.array([float(v) for v in q]).reshape(-1, 3)[:, :2].copy(),
+                point3D_ids=np.array([int(v) for v in q[2::3]], np.int64))
+        for ln in lines("points3D.txt"):
+            w = ln.split()
+            if w:
+                model.points3D[int(w[0])] = dict(xyz=np.array([float(v) for v in w[1:4]]), rgb=tuple(int(v) for v in w[4:7]),
+                                                 error=float(w[7]), track=[(int(i), int(k)) for i, k in zip(w[8::2], w[9::2])])
+        return model
+
+    def __eq__(self, other):
+        if not isinstance(other, SparseModel):
+            return NotImplemented
+
+        def cam(c):
+            return (c.model, int(c.width), int(c.height), [float(v) for v in c.params])
+
+        if {k: cam(c) for k, c in self.cameras.items()} != {k: cam(c) for k, c in other.cameras.items()}:
+            return False
+        if sorted(self.images) != sorted(other.images) or sorted(self.points3D) != sorted(other.points3D):
+            return False
+        for k, a in self.images.items():
+            b = other.images[k]
+            if not (np.array_equal(a["qvec"], b["qvec"]) and np.array_equal(a["tvec"], b["tvec"]) and a["camera_id"] == b["camera_id"]
+                    and a["name"] == b["name"] and np.array_equal(np.asarray(a["xys"], np.float64).reshape(-1, 2), np.asarray(b["xys"], np.float64).reshape(-1, 2))
+                    and np.array_equal(a["point3D_ids"], b["point3D_ids"])):
+                return False
+        for k, a in self.points3D.items():
+            b = other.points3D[k]
+            if not (np.array_equal(a["xyz"], b["xyz"]) and tuple(a["rgb"]) == tuple(b["rgb"]) and float(a["error"]) == float(b["error"])
+                    and [tuple(t) for t in a["track"]] == [tuple(t) for t in b["track"]]):
+                return False
+        return True
+
+
+def _gpu_two_view_pose(xn_rows, cand, device):
+    """The one triangulation launch over all candidate pairs -> front (P, 4), tri_angle (P,), midpoints per pair."""
+    import torch
+
+    from ..matching._common import _pair_batch
+    from ..matching.pose import two_view_pose
+
+    xn, offsets, _, _ = _pair_batch(xn_rows, None, device)
+    front, best, tri, pts = two_view_pose(xn, offsets, torch.from_numpy(cand).to(device), points=True)
+    if bool((best < 0).any()):
+        raise RuntimeError("vc_two_view_pose: the workspace did not hold the keys of every pair")
+    cuts = np.cumsum([len(r) for r in xn_rows])[:-1]
+    return front.cpu().numpy(), tri.cpu().numpy(), np.split(pts.cpu().numpy(), cuts)
+
+
+def _normalise(pts, K1, K2):
+    K1i, K2i = np.linalg.inv(K1), np.linalg.inv(K2)
+    p64 = np.asarray(pts, np.float64)
+    return np.concatenate([p64[:, :2] * [K1i[0, 0], K1i[1, 1]] + [K1i[0, 2], K1i[1, 2]],
+                           p64[:, 2:] * [K2i[0, 0], K2i[1, 1]] + [K2i[0, 2], K2i[1, 2]]], axis=1)
+
+
+def _point_angles(X, centre):
+    """Angle at each point X (n, 3) between the rays to the origin and to `centre`."""
+    e = X - centre
+    k = np.cross(X, e)
+    return np.arctan2(np.linalg.norm(k, axis=1), (X * e).sum(axis=1))
+
+
+def _pixel_errors(K, R, t, xyz, obs):
+    Xc = xyz @ R.T + t
+    with np.errstate(all="ignore"):
+        p = np.stack([K[0, 0] * Xc[:, 0] / Xc[:, 2] + K[0, 2], K[1, 1] * Xc[:, 1] / Xc[:, 2] + K[1, 2]], axis=1)
+        err = np.linalg.norm(p - obs, axis=1)
+    return np.where(Xc[:, 2] > 0, err, np.inf)
+
+
+def build_seed_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None) -> SparseModel:
+    """Read a matched database -> the seed model.  Raises ValueError, naming the condition, when no pair can start it.
+    `two_view_pose_fn(xn_rows, cand, device)` and `estimate_fn(problems, device)` replace the two GPU steps (tests)."""
+    two_view_pose_fn = two_view_pose_fn or _gpu_two_view_pose
+    estimate_fn = estimate_fn or estimate_absolute_poses
+    with ColmapDatabase.open_database(str(database_path)) as db:
+        images = {im.image_id: im for im in db.read_all_images()}
+        cameras, K, kps = {}, {}, {}
+        for iid, im in images.items():
+            if im.camera_id not in cameras:
+                cameras[im.camera_id] = db.read_camera(im.camera_id)
+            cam = cameras[im.camera_id]
+            Kc, ok, _ = camera_prior(cam)
+            K[iid] = Kc if ok and cam.model in SEED_CAMERA_MODELS else None
+            kp = db.read_keypoints(iid)
+            kps[iid] = np.zeros((0, 2), np.float32) if kp is None else kp[:, :2]
+        geoms = {}
+        for i, j, rows, config in db.read_two_view_geometry_pairs():
+            if rows > 0 and config == CONFIG_CALIBRATED and i in images and j in images:
+                geoms[(i, j)] = db.read_two_view_geometry(i, j)
+
+    def directed(i, j):
+        """The CALIBRATED geometry of (i -> j): match columns (i, j), X_j = R X_i + t; None where there is no such row."""
+        g = geoms.get((min(i, j), max(i, j)))
+        if g is None:
+            return None
+        m, R, t = g["inlier_matches"].astype(np.int64), _quat_to_rot(g["qvec"]), np.asarray(g["tvec"], np.float64)
+        if i > j:
+            m, R, t = m[:, ::-1], R.T, -R.T @ t
+        return m, R, t
+
+    # 1. candidate pairs, one triangulation launch
+    cands = [(i, j) for (i, j), g in sorted(geoms.items())
+             if np.any(g["tvec"]) and len(g["inlier_matches"]) >= INIT_MIN_NUM_INLIERS and K[i] is not None and K[j] is not None]
+    if not cands:
+        raise ValueError("seed model: no CALIBRATED pair with a translation, two focal-length priors and at least "
+                         f"{INIT_MIN_NUM_INLIERS} inliers")
+    pix, xn_rows = [], []
+    cand = np.full((len(cands), 4, 12), np.nan)
+    for p, (i, j) in enumerate(cands):
+        m, R, t = directed(i, j)
+        pix.append(np.concatenate([kps[i][m[:, 0]], kps[j][m[:, 1]]], axis=1).astype(np.float32))
+        xn_rows.append(_normalise(pix[-1], K[i], K[j]))
+        cand[p, 0, :9], cand[p, 0, 9:] = R.reshape(9), t
+    front, tri, midpoints = two_view_pose_fn(xn_rows, cand, device)
+    best = None
+    for p in range(len(cands)):                                     # most points in front, the lowest pair id on ties
+        if tri[p] >= INIT_MIN_TRI_ANGLE and (best is None or front[p, 0] > front[best, 0]):
+            best = p
+    if best is None:
+        raise ValueError(f"seed model: no candidate pair reaches a triangulation angle of {np.degrees(INIT_MIN_TRI_ANGLE):.0f} degrees")
+
+    # 2. world frame: the camera of the lower image id; points: in front, wide enough, inliers of both cameras
+    a, b = cands[best]
+    m, R, t = directed(a, b)
+    X, pts = midpoints[best], pix[best]
+    is_front = np.isfinite(X).all(axis=1)
+    Xs = np.where(is_front[:, None], X, 1.0)
+    keep = is_front & (_point_angles(Xs, -R.T @ t) >= FILTER_MIN_TRI_ANGLE)
+    keep &= _pixel_errors(K[a], np.eye(3), np.zeros(3), Xs, pts[:, :2].astype(np.float64)) <= MAX_ERROR
+    keep &= _pixel_errors(K[b], R, t, Xs, pts[:, 2:].astype(np.float64)) <= MAX_ERROR
+    xyz, m = X[keep], m[keep]
+    tracks = [[(a, int(ka)), (b, int(kb))] for ka, kb in m]
+    point_of = {a: {int(ka): k for k, (ka, _) in enumerate(m)}, b: {int(kb): k for k, (_, kb) in enumerate(m)}}
+    poses = {a: (np.array([1.0, 0.0, 0.0, 0.0]), np.zeros(3)), b: (geoms[(a, b)]["qvec"].copy(), t.copy())}
+
+    # 3. every other image against those points, one batch
+    problems, meta = [], []
+    for c in sorted(images):
+        if c in (a, b) or K[c] is None:
+            continue
+        used, kp_idx, pt_idx = set(), [], []
+        for other in (a, b):
+            g = directed(c, other)
+            if g is None:
+                continue
+            for kc, ko in g[0]:
+                k = point_of[other].get(int(ko))
+                if k is not None and int(kc) not in used:
+                    used.add(int(kc)), kp_idx.append(int(kc)), pt_idx.append(k)
+        if len(kp_idx) >= ABS_POSE_MIN_NUM_INLIERS:
+            problems.append(dict(obs=kps[c][kp_idx], xyz=xyz[pt_idx], K=K[c], seed=c))
+            meta.append((c, kp_idx, pt_idx))
+    for (c, kp_idx, pt_idx), r in zip(meta, estimate_fn(problems, device) if problems else []):
+        if not r["success"]:
+            continue
+        poses[c] = (np.asarray(r["qvec"], np.float64), np.asarray(r["tvec"], np.float64))
+        for kc, k, ok in zip(kp_idx, pt_idx, r["inlier_mask"]):
+            if ok:
+                tracks[k].append((c, kc))
+
+    # 4. the model
+    model = SparseModel(initial_pair=(a, b))
+    for iid, (q, tv) in sorted(poses.items()):
+        cid = images[iid].camera_id
+        model.cameras[cid] = cameras[cid]
+        model.images[iid] = dict(qvec=q, tvec=tv, camera_id=cid, name=images[iid].name, xys=kps[iid].astype(np.float64),
+                                 point3D_ids=np.full(len(kps[iid]), -1, np.int64))
+    for k, track in enumerate(tracks):
+        errs = []
+        for iid, kp in track:
+            model.images[iid]["point3D_ids"][kp] = k + 1
+            q, tv = poses[iid]
+            errs.append(_pixel_errors(K[iid], _quat_to_rot(q), tv, xyz[k][None], kps[iid][kp][None].astype(np.float64))[0])
+        model.points3D[k + 1] = dict(xyz=xyz[k].copy(), rgb=(0, 0, 0), error=float(np.mean(errs)), track=list(track))
+    return model

@@ -70,6 +70,13 @@ class Pipeline:
             raise ValueError(f"unknown matcher_type {matcher_type!r}: expected one of {', '.join(MATCHER_TYPES)}")
         if matcher_type == "retrieval" and int(num_neighbors) < 1:
             raise ValueError(f"num_neighbors must be at least 1 (got {num_neighbors})")
+        seed_model = bool(getattr(self.config.reconstruction, "seed_model", False))
+        if seed_model:                                          # the seed model reads calibrated rows with a pose (§4.2i)
+            for on, flag in ((self.config.camera.prior_focal_length, "camera.prior_focal_length (--prior-focal-length)"),
+                             (self.config.matching.compute_relative_pose, "matching.compute_relative_pose (--relative-pose)"),
+                             (self.config.do_matching, "do_matching (no --skip-matching)")):
+                if not on:
+                    raise ValueError(f"seed_model needs {flag}")
 
         extractor = self._make_extractor()
         extractor.prior_focal_length = bool(self.config.camera.prior_focal_length)
@@ -115,6 +122,9 @@ class Pipeline:
                 num_pairs = ColmapDatabase.get_db_count(db_check, "num_matched_image_pairs")
                 logger.info(f"Matched {num_pairs} image pairs ({db_check.num_verified_image_pairs()} geometrically verified)")
 
+        if seed_model:                                          # under torchrun only rank 0 arrives here
+            self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
+
         reconstructions = None
         if self.config.do_reconstruction:
             try:
@@ -138,6 +148,20 @@ class Pipeline:
         if dataset and scene:                                   # run_pipeline.py:406-415
             self.extract_and_export_metrics(db_path, output_dir, reconstructions, dataset, scene, results_dir)
         return reconstructions
+
+    def _write_seed_model(self, db_path, output_dir, device):
+        """output_dir/sparse/seed and `last_stats["seed_model"]`; a scene without an admissible initial pair writes nothing."""
+        from ..mapping import build_seed_model
+
+        try:
+            model = build_seed_model(str(db_path), device=device)
+        except ValueError as e:
+            logger.warning("no seed model written: %s", e)
+            return
+        model.write_text(str(Path(output_dir) / "sparse" / "seed"))
+        self.last_stats = dict(self.last_stats or {}, seed_model=model.stats())
+        logger.info("Seed model: pair %s, %d images, %d points", *[model.stats()[k] for k in
+                                                                    ("initial_pair", "registered_images", "num_points3D")])
 
     def extract_and_export_metrics(self, db_path, output_dir, reconstructions, dataset, scene, results_dir=None):
         """Database metrics -> `{results_dir}/{dataset}/{scene}/{extractor}.json` + summary.csv row
@@ -177,6 +201,9 @@ def main() -> None:
     ap.add_argument("--relative-pose", dest="relative_pose", action="store_true",
                     help="pose, triangulation angle and the PLANAR / PANORAMIC split of the pairs whose cameras have a "
                          "focal-length prior (COLMAP's compute_relative_pose)")
+    ap.add_argument("--seed-model", dest="seed_model", action="store_true",
+                    help="write output/sparse/seed: an initial pair, its triangulated points and every other image registered "
+                         "against them (needs --prior-focal-length and --relative-pose)")
     ap.add_argument("--matcher", choices=list(MATCHER_TYPES), default="exhaustive",
                     help="exhaustive: every image pair; retrieval: each image against its --num-neighbors nearest images")
     ap.add_argument("--num-neighbors", dest="num_neighbors", type=int, default=20,
