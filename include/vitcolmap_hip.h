@@ -165,8 +165,11 @@ int vc_theta_eval(float* out, int n, vc_stream_t stream);
  * everything that is O(pairs x hypotheses x matches) runs here.
  *   pts      [total][4] float32 (x1, y1, x2, y2): the matched keypoints of all pairs, concatenated; 16-byte aligned
  *   offsets  [n_pairs + 1] int32: pair p owns pts[offsets[p] .. offsets[p+1])
- *   model    VC_MODEL_FUNDAMENTAL: row-major F, inlier iff (x2' F x1)^2 <= e^2 (|F x1|_xy^2 + |F' x2|_xy^2)  (Sampson)
+ *   model    VC_MODEL_FUNDAMENTAL: row-major F, inlier iff (x2' F x1)^2 <= e^2 den, den = |F x1|_xy^2 + |F' x2|_xy^2  (Sampson)
  *            VC_MODEL_HOMOGRAPHY : row-major H, inlier iff |(H x1)_xy - x2 (H x1)_w|^2 <= e^2 (H x1)_w^2      (transfer)
+ *            float32 in the specification's operation order; a zero denominator (den, (H x1)_w) or a bound e^2 den,
+ *            e^2 (H x1)_w^2 that is not finite has no inlier: F: den > 0 and e^2 den < inf; H: (H x1)_w != 0 and
+ *            e^2 (H x1)_w^2 < inf.  NaN compares false.
  * vc_two_view_score:   hypotheses [n_pairs][n_hyp][9] -> out_counts [n_pairs][n_hyp] (NaN hypotheses count 0)
  * vc_two_view_inliers: models [n_pairs][9] -> out_mask [total] uint8
  * ------------------------------------------------------------------------------------------ */

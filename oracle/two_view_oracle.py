@@ -17,7 +17,9 @@ vit_colmap_amd/matching/two_view.py follow it step by step):
   normalise   per pair and image: x~ = (x - mean) * sqrt(2) / mean |x - mean|   (float64, all matches of the pair)
   F (S = 8)   f_33 = 1; the eight epipolar equations form an 8x8 linear system (float64); F = T2' F~ T1
   H (S = 4)   h_33 = 1; the four correspondences form an 8x8 linear system (float64);   H = T2^-1 H~ T1
-  score       float32, no division:  F: (x2'Fx1)^2 <= e^2 (|Fx1|_xy^2 + |F'x2|_xy^2);  H: |p_xy - x2 p_w|^2 <= e^2 p_w^2
+  score       float32, no division:  F: (x2'Fx1)^2 <= e^2 den, den = |Fx1|_xy^2 + |F'x2|_xy^2;  H: |p_xy - x2 p_w|^2 <= e^2 p_w^2
+              and no inlier where the denominator (den, p_w) is zero or the bound e^2 den, e^2 p_w^2 is not finite:
+              F: den > 0 and e^2 den < inf and ...;  H: p_w != 0 and e^2 p_w^2 < inf and ...  (NaN compares false)
   best        most inliers, lowest k on ties; one refit by linear least squares over the best hypothesis' inliers
               (same parametrisation, normal equations in float64), kept if it has at least as many inliers
   decision    F inliers < max(15, 0.25 M): DEGENERATE, no inlier matches [recalled: COLMAP's min_num_inliers and RANSAC
@@ -119,13 +121,15 @@ def inliers_f32(model, m9, pts, max_error=MAX_ERROR):
             ft1 = m[1] * x2 + m[4] * y2 + m[7]
             c = x2 * fx0 + y2 * fx1 + fx2
             den = fx0 * fx0 + fx1 * fx1 + ft0 * ft0 + ft1 * ft1
-            return c * c <= t2 * den
+            bound = t2 * den
+            return (den > 0) & (bound < np.inf) & (c * c <= bound)
         p0 = m[0] * x1 + m[1] * y1 + m[2]
         p1 = m[3] * x1 + m[4] * y1 + m[5]
         pw = m[6] * x1 + m[7] * y1 + m[8]
         dx = p0 - x2 * pw
         dy = p1 - y2 * pw
-        return (pw != 0) & (dx * dx + dy * dy <= t2 * (pw * pw))
+        bound = t2 * (pw * pw)
+        return (pw != 0) & (bound < np.inf) & (dx * dx + dy * dy <= bound)
 
 
 def hypotheses(model, pts, seed, n_hyp):

@@ -403,6 +403,10 @@ def test_pipeline_without_the_flag_writes_no_seed_model_and_todays_rows(tmp_path
         return write_seed(self, db_path, output_dir, device)
 
     monkeypatch.setattr(rp.Pipeline, "_write_seed_model", snapshot_then_write)
+    import vit_colmap_amd
+
+    if hasattr(vit_colmap_amd, "mapping"):      # restored with sys.modules, so that both name the same module for later tests
+        monkeypatch.setattr(vit_colmap_amd, "mapping", vit_colmap_amd.mapping)
     monkeypatch.delitem(sys.modules, "vit_colmap_amd.mapping", raising=False)
     for name, flag in (("off", False), ("on", True)):
         write_scene_db(tmp_path / f"{name}.db", scene)

@@ -79,6 +79,85 @@ def test_database_row_round_trip_and_metrics(tmp_path):
     assert rows[0].split(",")[-1] == "avg_reprojection_error" and rows[1].split(",")[:3] == ["DTU", "scan1", "vit"]
 
 
+@pytest.mark.parametrize("model", ["F", "H"])
+def test_a_non_finite_or_zero_denominator_has_no_inliers(model):
+    """The scoring rule over a power-of-two scale sweep of a valid model: wherever no intermediate overflows or underflows
+    (float64 conditions of util_two_view.sweep_conditions) the decision is the unscaled one, wherever the bound t2 * den
+    overflows or the denominator is 0 there is no inlier, and the all-zero matrix has none."""
+    import util_two_view as u
+
+    pts, m9 = u.best_hypothesis(model)
+    base = tv.inliers_f32(model, m9, pts)
+    assert 100 < base.sum() < len(pts)
+    all_safe = all_dead = 0
+    for k, scaled in zip(u.SCALE_EXPONENTS, u.scale_sweep(m9)):
+        safe, dead = u.sweep_conditions(model, m9, k, pts)
+        got = tv.inliers_f32(model, scaled, pts)
+        assert not (safe & dead).any()
+        assert np.array_equal(got[safe], base[safe]), k
+        assert not got[dead].any(), k
+        all_safe += safe.all()
+        all_dead += dead.all()
+    assert all_safe >= 20 and all_dead >= 10              # the sweep reaches both regimes on every match
+    assert u.sweep_conditions(model, m9, 0, pts)[0].all()
+    assert tv.inliers_f32(model, np.zeros(9, np.float32), pts).sum() == 0
+    assert tv.inliers_f32(model, np.float32(2.0 ** 72) * m9, pts).sum() == 0       # finite entries, every bound overflows
+
+
+@pytest.mark.parametrize("model", ["F", "H"])
+def test_threshold_set_separates_a_contracted_evaluation_from_the_oracle(model):
+    """The condition of the GPU threshold test: on the boundary correspondences an evaluation with fused multiply-adds
+    disagrees with the oracle on at least 1 % of the points, so a library built without -ffp-contract=off cannot pass."""
+    import util_two_view as u
+
+    m9, pts = u.threshold_set(model)
+    assert 4000 <= len(pts) <= 4096 and np.isfinite(pts).all()
+    res = u.residual64(model, m9, pts)
+    assert np.abs(res / tv.MAX_ERROR - 1).max() < 1e-4         # 2e-5 relative in the radius, float32 rounding of the point
+    ref = tv.inliers_f32(model, m9, pts)
+    assert 0.3 < ref.mean() < 0.7                              # both sides of the boundary
+    assert (u.contracted_inliers(model, m9, pts) != ref).mean() >= 0.01
+    # away from the boundary the two evaluations agree: the set, not the emulation, is what separates them
+    far, _ = u.scene_hypotheses(model, 51, 1000, model == "H", 64)
+    assert (u.contracted_inliers(model, m9, far) != tv.inliers_f32(model, m9, far)).sum() == 0
+
+
+SAMPLER_SEEDS = [0, 1, 2 ** 31, 2 ** 32 - 1, 1234567, (3 * 2147483647 + 17) % 2 ** 32]      # the last: pair_id_of(3, 17) mod 2^32
+SAMPLER_COUNTS = [1, 3, 4, 5, 7, 8, 9, 15, 16, 33, 300, 65536, 2 ** 20 + 3, 2 ** 31 - 1]
+SAMPLER_MODELS = [(8, "F"), (4, "H"), (5, "E"), (3, "P")]
+
+
+def sampler_parity(device):
+    """_common._sample_indices against the oracle's sampler, element for element, on `device`."""
+    import torch
+
+    from vit_colmap_amd.matching import _common
+
+    assert (3 * 2147483647 + 17) == __import__("vit_colmap_amd.database.colmap_db", fromlist=["pair_id_of"]).pair_id_of(3, 17)
+    seeds = [s for s in SAMPLER_SEEDS for _ in SAMPLER_COUNTS]
+    counts = [m for _ in SAMPLER_SEEDS for m in SAMPLER_COUNTS]
+    for S, name in SAMPLER_MODELS:
+        salt = _common.SALT[name]
+        got = _common._sample_indices(torch.tensor(seeds, dtype=torch.int64, device=device),
+                                      torch.tensor(counts, dtype=torch.int64, device=device), 130, S, salt).cpu().numpy()
+        assert got.shape == (len(seeds), 130, S) and got.dtype == np.int64
+        for row, (seed, m) in enumerate(zip(seeds, counts)):
+            want = tv.sample_indices(seed, 130, S, m, salt)
+            assert np.array_equal(got[row], want), (name, seed, m)
+            if m < S:
+                assert (want == -1).all()
+        if S in (8, 4):
+            assert salt == {8: tv.SALT_F, 4: tv.SALT_H}[S]
+        assert (got[counts.index(300)] >= 0).all()             # not a comparison of voids
+        empty = _common._sample_indices(torch.tensor(SAMPLER_SEEDS, dtype=torch.int64, device=device),
+                                        torch.zeros(len(SAMPLER_SEEDS), dtype=torch.int64, device=device), 130, S, salt)
+        assert empty.shape == (len(SAMPLER_SEEDS), 130, S) and bool((empty == -1).all())
+
+
+def test_torch_sampler_equals_the_oracle_sampler_on_the_cpu():
+    sampler_parity("cpu")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_scoring_kernels_bit_exact_against_oracle_scoring():

@@ -403,8 +403,8 @@ __device__ __forceinline__ void mfma_phase(const v4i (&afrag)[RT][KS], v16i (&ac
 // (row keypoint, column keypoint) fails the pair's geometric test by 0 — the value that never matches and never
 // is a runner-up — so both searches see the masked matrix.  The relevance test of pass 1 stays on the unmasked
 // similarities: masking only lowers a value, so a tile that is irrelevant unmasked is irrelevant masked.
-// The test is inlier_f / inlier_h of two_view.hip (specification: oracle/two_view_oracle.py inliers_f32), float32 in
-// the same operation order, factorised into terms of the row (LDS, GuidedWave::rowg, written once per pass), terms
+// The test is inlier_f / inlier_h of two_view.hip without their guards on a zero denominator and an overflowing bound
+// (specification: oracle/two_view_oracle.py inliers_f32), float32 in the same operation order, factorised into terms of the row (LDS, GuidedWave::rowg, written once per pass), terms
 // of the lane's column (once per tile) and what is left per candidate:
 //   F  row (fx0, fx1, fx2, r = fx0 fx0 + fx1 fx1)   column (x2, y2, q0 = ft0 ft0, q1 = ft1 ft1)
 //      c = x2 fx0 + y2 fx1 + fx2,  den = (r + q0) + q1,  admissible iff c c <= t2 den

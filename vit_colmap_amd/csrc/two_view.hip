@@ -7,8 +7,10 @@
 // arithmetic in exactly this operation order; the library is built with -ffp-contract=off).
 //
 // Residuals (no division, so host oracle and device agree bit for bit):
-//   F: Sampson error  (x2' F x1)^2 <= t^2 * (|F x1|_xy^2 + |F' x2|_xy^2)
-//   H: forward transfer error  |p_xy - x2 p_w|^2 <= t^2 * p_w^2  with p = H x1, p_w != 0
+//   F: Sampson error  (x2' F x1)^2 <= t^2 * den  with den = |F x1|_xy^2 + |F' x2|_xy^2
+//   H: forward transfer error  |p_xy - x2 p_w|^2 <= t^2 * p_w^2  with p = H x1
+// A denominator that is zero, or whose bound t^2 * denominator is not finite, has no inliers: `inf <= inf` and `0 <= 0`
+// would otherwise count every match of an overflowing or an all-zero hypothesis.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,7 +27,8 @@ __device__ __forceinline__ bool inlier_f(const float (&m)[9], float x1, float y1
   const float ft1 = m[1] * x2 + m[4] * y2 + m[7];
   const float c = x2 * fx0 + y2 * fx1 + fx2;
   const float den = fx0 * fx0 + fx1 * fx1 + ft0 * ft0 + ft1 * ft1;
-  return c * c <= t2 * den;          // NaN hypotheses compare false
+  const float bound = t2 * den;
+  return den > 0.f && bound < INFINITY && c * c <= bound;          // NaN hypotheses compare false
 }
 
 __device__ __forceinline__ bool inlier_h(const float (&m)[9], float x1, float y1, float x2, float y2, float t2) {
@@ -34,7 +37,8 @@ __device__ __forceinline__ bool inlier_h(const float (&m)[9], float x1, float y1
   const float pw = m[6] * x1 + m[7] * y1 + m[8];
   const float dx = p0 - x2 * pw;
   const float dy = p1 - y2 * pw;
-  return pw != 0.f && dx * dx + dy * dy <= t2 * (pw * pw);
+  const float bound = t2 * (pw * pw);
+  return pw != 0.f && bound < INFINITY && dx * dx + dy * dy <= bound;
 }
 
 // grid (n_pairs, hypothesis groups); 4 waves per workgroup, one hypothesis per wave and round, lanes over matches

@@ -49,8 +49,10 @@ def _denormalise(model, Mn, T1, T2):
     return torch.linalg.inv(T2)[:, None] @ Mn @ T1[:, None]
 
 
-def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
-    """All pairs at once -> best model float32 (P, 9) (NaN where none), inlier mask bool (total,), counts int64 (P,)."""
+def _hypotheses(model, pts, offsets, pair_of, seeds, n_hyp):
+    """The hypothesis half of `_estimate`, all pairs at once -> hypotheses float32 (P, n_hyp, 9) in pixel coordinates (NaN
+    rows for void samples and singular systems), the sample indices int64 (P, n_hyp, S) into each pair's own list (-1 where
+    void) and the normalisation (T1, T2, n1, n2) that the refit works in."""
     dev = pts.device
     P = offsets.shape[0] - 1
     M = (offsets[1:] - offsets[:-1]).to(torch.int64)
@@ -83,7 +85,15 @@ def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
     sol = torch.linalg.solve_ex(A, b.unsqueeze(-1)).result.squeeze(-1)        # singular systems give inf / nan
     hyp = _denormalise(model, _to_matrix(sol), T1, T2).reshape(P, n_hyp, 9)
     hyp = torch.where(void[:, :, None] | ~torch.isfinite(sol).all(dim=-1, keepdim=True), torch.full_like(hyp, float("nan")), hyp)
-    hyp32 = hyp.to(torch.float32).contiguous()
+    return hyp.to(torch.float32).contiguous(), idx, (T1, T2, n1, n2)
+
+
+def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
+    """All pairs at once -> best model float32 (P, 9) (NaN where none), inlier mask bool (total,), counts int64 (P,)."""
+    dev = pts.device
+    P = offsets.shape[0] - 1
+    S = 8 if model == "F" else 4
+    hyp32, _, (T1, T2, n1, n2) = _hypotheses(model, pts, offsets, pair_of, seeds, n_hyp)
     counts = _score(pts, offsets, hyp32, model, max_error).to(torch.int64)
     Ar, br = _rows(model, n1[:, 0], n1[:, 1], n2[:, 0], n2[:, 1])             # F: (total, 8); H: (2 total, 8) stacked x then y
 
