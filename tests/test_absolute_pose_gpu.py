@@ -1,7 +1,8 @@
 """GPU tests of image registration: vc_p3p against the numpy specification of tests/util_absolute_pose.py
 on the 300 exact minimal problems, its shapes, degenerate inputs and argument checks; the scoring kernels bit for bit;
-estimate_absolute_poses against the specification's rule; match_exhaustive + build_seed_model end to end."""
-from functools import lru_cache
+the RANSAC tail under this residual with a refit the test owns (exact); estimate_absolute_poses against the specification's
+rule; match_exhaustive + build_seed_model end to end."""
+from functools import lru_cache, partial
 
 import numpy as np
 import pytest
@@ -300,6 +301,114 @@ def test_argument_checks_on_device_pointers():
     assert lib.vc_absolute_pose_inliers(*args) == -1
     torch.cuda.synchronize()
     assert (counts.cpu().numpy() == 0).all() and (mask.cpu().numpy() == 0).all()      # the zero matrix has p_w = 0: no inlier
+
+
+# ---- the RANSAC tail ------------------------------------------------------------------------------------------------------------------
+NAN12 = np.full(12, np.nan, np.float32)
+TAIL_K = 69
+
+
+def tail_problems():
+    """-> list of dict(obs, xyz, hyp (69, 12), kind, refit (12,), ok): the ragged batch of the tail tests.  The correspondences
+    are those of test_scores_and_masks_equal_the_spec_bit_for_bit (below a wave, a partial fourth wave, many rounds), the
+    hypotheses its poses around the scene pose without the exact one; `refit` and `ok` are what the callback hands back.
+    Counts measured with the specification on the CPU: the best hypothesis of the 1 / 255 / 1500 problems has 1 / 176 / 1040
+    inliers, the true pose 1 / 177 / 1043, the turned pose 0; 21 hypotheses of the 1-point problem tie at 1."""
+    rs = np.random.RandomState(11)
+    true = ua.projection_matrix(ue.SCENE_K, ue.SCENE_R, ue.SCENE_T)
+    turned = ua.projection_matrix(ue.SCENE_K, ua.rodrigues(np.array([0.0, 0.05, 0.0])) @ ue.SCENE_R, ue.SCENE_T)
+    data = []
+    for k, n in enumerate([1, 255, 1500]):
+        o, X, _ = ua.registration_problem(40 + k, n, 0.3, noise=4.0)
+        hyp = np.zeros((TAIL_K + 1, 12), np.float32)
+        for j in range(TAIL_K + 1):
+            R = ua.rodrigues(rs.normal(0, 0.004 * (j % 10), 3)) @ ue.SCENE_R
+            hyp[j] = ua.projection_matrix(ue.SCENE_K, R, ue.SCENE_T + rs.normal(0, 0.02 * (j % 7), 3))
+        data.append((o, X, hyp[1:]))                                   # j = 0 is the scene pose itself
+
+    def problem(which, kind, refit, ok=True):
+        o, X, hyp = data[which]
+        return dict(obs=o, xyz=X, hyp=hyp.copy(), kind=kind, refit=refit, ok=ok)
+
+    ps = [problem(0, "taken", true), problem(1, "taken", true), problem(2, "taken", true),      # the 1-point problem on equality
+          problem(1, "rejected", turned),                              # a refit with fewer inliers
+          problem(2, "ok_false", true, ok=False),                      # the callback offers a better model but says ok = False
+          problem(1, "nan_ok", NAN12),                                 # the callback says ok = True and hands back NaN
+          dict(obs=np.zeros((0, 2), np.float32), xyz=np.zeros((0, 3), np.float32), hyp=np.tile(NAN12, (TAIL_K, 1)), kind="empty",
+               refit=NAN12, ok=False)]
+    void = problem(1, "void", NAN12, ok=False)                         # every hypothesis void: NaN model, empty mask, count 0
+    void["hyp"][:] = np.nan
+    return ps + [void]
+
+
+def run_tail(ps):
+    """_ransac_tail with counts from score_poses and a refit callback that hands back the problems' own models on the CPU
+    -> (final, mask, count, kbest, use) as numpy, what the callback saw, and the offsets."""
+    from vit_colmap_amd.mapping.absolute_pose import pose_masks, score_poses
+    from vit_colmap_amd.matching import _common
+
+    offs = np.cumsum([0] + [len(p["obs"]) for p in ps])
+    xyz4, offsets, _, _ = _common._pair_batch([np.concatenate([p["xyz"], np.ones((len(p["xyz"]), 1), np.float32)], axis=1) for p in ps],
+                                              None, "cuda")
+    obs = dev(np.concatenate([p["obs"] for p in ps]))
+    hyp32 = dev(np.stack([p["hyp"] for p in ps]).astype(np.float32))
+    score, mask = partial(score_poses, obs, xyz4, offsets, max_error=12.0), partial(pose_masks, obs, xyz4, offsets, max_error=12.0)
+    counts = score(hyp32).to(torch.int64)
+    seen = {}
+
+    def refit(m, nbest):
+        assert m.dtype == torch.bool and m.shape == (offs[-1],) and nbest.shape == (len(ps),)
+        seen.update(mask=m.cpu().numpy(), nbest=nbest.cpu().numpy())
+        return dev(np.stack([p["refit"] for p in ps])), dev(np.array([p["ok"] for p in ps]))
+
+    res = _common._ransac_tail(hyp32, counts, score, mask, refit)
+    torch.cuda.synchronize()
+    return [r.cpu().numpy() for r in res], seen, offs
+
+
+def check_tail(ps):
+    (final, mask, count, kbest, use), seen, offs = run_tail(ps)
+    assert final.dtype == np.float32 and mask.dtype == bool and mask.shape == (offs[-1],)
+    kinds = {}
+    for p, pr in enumerate(ps):
+        obs, xyz, hyp = pr["obs"], pr["xyz"], pr["hyp"]
+        # the rule: most inliers, lowest index on ties; the refit is taken iff it is ok and has no fewer inliers; no inlier, no model
+        c = np.array([ua.score(h, obs, xyz) for h in hyp])
+        k = int(np.argmax(c))
+        rc = ua.score(pr["refit"], obs, xyz)
+        take = bool(pr["ok"] and rc >= c[k])
+        want, n = (pr["refit"], rc) if take else (hyp[k], int(c[k]))
+        want = want if n > 0 else NAN12
+        sl = slice(offs[p], offs[p + 1])
+        assert np.array_equal(seen["mask"][sl], ua.inliers(hyp[k], obs, xyz)) and seen["nbest"][p] == c[k], (p, pr["kind"])
+        assert kbest[p] == k and bool(use[p]) == take and count[p] == n, (p, pr["kind"], kbest[p], k, use[p], take, count[p], n)
+        assert np.array_equal(final[p], want, equal_nan=True), (p, pr["kind"])
+        assert np.array_equal(mask[sl], ua.inliers(want, obs, xyz)) and mask[sl].sum() == n, (p, pr["kind"])
+        kinds.setdefault(pr["kind"], []).append(dict(k=k, n=n, best=int(c[k]), rc=rc, take=take, ties=int((c == c[k]).sum())))
+    return kinds
+
+
+def test_ransac_tail_follows_the_rule_exactly_under_the_pose_residual():
+    kinds = check_tail(tail_problems())
+    assert [d["take"] for d in kinds["taken"]] == [True] * 3
+    assert kinds["taken"][0]["rc"] == kinds["taken"][0]["best"] == 1 and kinds["taken"][0]["ties"] > 1      # equality; lowest rank
+    assert all(d["rc"] > d["best"] > 0 for d in kinds["taken"][1:])
+    assert kinds["rejected"][0]["rc"] < kinds["rejected"][0]["best"] and not kinds["rejected"][0]["take"]
+    assert kinds["ok_false"][0]["rc"] > kinds["ok_false"][0]["best"] and not kinds["ok_false"][0]["take"]
+    assert kinds["nan_ok"][0]["rc"] == 0 and not kinds["nan_ok"][0]["take"] and kinds["nan_ok"][0]["n"] > 0
+    assert kinds["void"][0]["n"] == 0 and kinds["empty"][0]["n"] == 0
+
+
+def test_ransac_tail_with_a_single_pose_hypothesis():
+    """K = 1, the shape in which three of a workgroup's four waves idle: every problem of the batch with one hypothesis, the
+    255-point one with its best."""
+    ps = tail_problems()
+    best = int(np.argmax([ua.score(h, ps[1]["obs"], ps[1]["xyz"]) for h in ps[1]["hyp"]]))
+    one = [dict(pr, hyp=pr["hyp"][[best if p == 1 else 0]]) for p, pr in enumerate(ps)]
+    kinds = check_tail(one)
+    assert [d["take"] for d in kinds["taken"]] == [True] * 3 and kinds["taken"][1]["best"] > 0
+    assert not kinds["rejected"][0]["take"] and kinds["rejected"][0]["n"] > 0
+    assert kinds["void"][0]["n"] == 0 and kinds["empty"][0]["n"] == 0
 
 
 # ---- the rule ---------------------------------------------------------------------------------------------------------------------------

@@ -101,7 +101,8 @@ def run_tail(model, pairs):
         seen.update(mask=mask_np, nbest=nbest.cpu().numpy(), out=out, ok=ok)
         return torch.from_numpy(out).cuda(), torch.from_numpy(ok).cuda()
 
-    res = _common._ransac_tail(pts, offsets, hyp32, counts, model, tv.MAX_ERROR, refit)
+    res = _common._ransac_tail(hyp32, counts, lambda h: _common._score(pts, offsets, h, model, tv.MAX_ERROR),
+                               lambda m: _common._mask(pts, offsets, m, model, tv.MAX_ERROR), refit)
     torch.cuda.synchronize()
     return [r.cpu().numpy() for r in res], seen, offs
 

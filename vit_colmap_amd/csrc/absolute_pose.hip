@@ -26,14 +26,13 @@
 // __host__ __device__: a host program that includes this file can call solve_p3p on one problem.
 //
 // Scoring — float32 in exactly the specification's order of single operations (the library is built with -ffp-contract=off),
-// no division: p = P (X, 1); inlier iff p_w > 0 and |p_xy - obs p_w|^2 <= e^2 p_w^2.  The layout is two_view.hip's: grid
-// (problem, hypothesis group), four waves per workgroup, one hypothesis per wave and round, lanes over the points.
+// no division: p = P (X, 1); inlier iff p_w > 0 and |p_xy - obs p_w|^2 <= e^2 p_w^2.  The kernels are those of inlier_count.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/vitcolmap_hip.h"
-#include "common.h"
+#include "inlier_count.h"
 
 namespace {
 
@@ -324,46 +323,18 @@ __device__ __forceinline__ bool inlier_p(const float (&m)[12], float x, float y,
   return pw > 0.f && dx * dx + dy * dy <= t2 * (pw * pw);   // NaN hypotheses compare false
 }
 
-// grid (n_prob, hypothesis groups); 4 waves per workgroup, one hypothesis per wave and round, lanes over the points
-__global__ __launch_bounds__(256) void absolute_pose_score_kernel(const float2* __restrict__ obs, const float4* __restrict__ xyz4,
-                                                                  const int32_t* __restrict__ offsets, const float* __restrict__ hyp,
-                                                                  int K, float t2, int32_t* __restrict__ counts) {
-  const int p = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = offsets[p], hi = offsets[p + 1];
-  for (int k = blockIdx.y * 4 + wave; k < K; k += gridDim.y * 4) {
-    float m[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) m[i] = hyp[((size_t)p * K + k) * 12 + i];
-    int n = 0;
-    for (int base = lo; base < hi; base += 64) {            // whole waves: the ballot needs every lane (base is wave-uniform)
-      const int i = base + lane;
-      bool in = false;
-      if (i < hi) {
-        const float4 q = xyz4[i];
-        const float2 o = obs[i];
-        in = inlier_p(m, q.x, q.y, q.z, o.x, o.y, t2);
-      }
-      n += __popcll(__ballot(in));
-    }
-    if (lane == 0) counts[(size_t)p * K + k] = n;
-  }
-}
+struct Points { const float2* __restrict__ obs; const float4* __restrict__ xyz4; };   // pixel observations; world points, w not read
 
-__global__ __launch_bounds__(256) void absolute_pose_mask_kernel(const float2* __restrict__ obs, const float4* __restrict__ xyz4,
-                                                                 const int32_t* __restrict__ offsets, const float* __restrict__ model12,
-                                                                 float t2, uint8_t* __restrict__ mask) {
-  const int p = blockIdx.x;
-  const int lo = offsets[p], hi = offsets[p + 1];
-  float m[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) m[i] = model12[(size_t)p * 12 + i];
-  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    const float4 q = xyz4[i];
-    const float2 o = obs[i];
-    mask[i] = inlier_p(m, q.x, q.y, q.z, o.x, o.y, t2) ? 1 : 0;
+struct RuleP {
+  static constexpr int W = 12;
+  using Data = Points;
+  static bool usable(Data d) { return d.obs && d.xyz4 && ((uintptr_t)d.xyz4) % 16 == 0 && ((uintptr_t)d.obs) % 8 == 0; }
+  static __device__ __forceinline__ bool inlier(const float (&m)[12], Data d, int i, float t2) {
+    const float4 q = d.xyz4[i];
+    const float2 o = d.obs[i];
+    return inlier_p(m, q.x, q.y, q.z, o.x, o.y, t2);
   }
-}
+};
 
 }  // namespace
 
@@ -384,26 +355,14 @@ int vc_p3p(const double* rays_n, const double* xyz, const int32_t* offsets, int 
 
 int vc_absolute_pose_score(const float* obs, const float* xyz4, const int32_t* offsets, int n_prob, const float* hyp, int n_hyp,
                            float max_error, int32_t* out_counts, vc_stream_t stream) {
-  if (n_prob < 0 || n_hyp < 0) return VC_ERR_INVALID_ARG;
-  if (n_prob == 0 || n_hyp == 0) return VC_OK;
-  if (!obs || !xyz4 || !offsets || !hyp || !out_counts || !(max_error >= 0.f)) return VC_ERR_INVALID_ARG;
-  if (((uintptr_t)xyz4) % 16 != 0 || ((uintptr_t)obs) % 8 != 0) return VC_ERR_INVALID_ARG;
-  if (n_prob > 65535 * 32) return VC_ERR_UNSUPPORTED;
-  const int groups = n_hyp >= 64 ? 16 : (n_hyp + 3) / 4;
-  hipLaunchKernelGGL(absolute_pose_score_kernel, dim3(n_prob, groups), dim3(256), 0, (hipStream_t)stream, (const float2*)obs,
-                     (const float4*)xyz4, offsets, hyp, n_hyp, max_error * max_error, out_counts);
-  return vc::check_launch();
+  return vc::launch_inlier_count<RuleP>({(const float2*)obs, (const float4*)xyz4}, offsets, n_prob, hyp, n_hyp, max_error,
+                                        out_counts, stream);
 }
 
 int vc_absolute_pose_inliers(const float* obs, const float* xyz4, const int32_t* offsets, int n_prob, const float* models,
                              float max_error, uint8_t* out_mask, vc_stream_t stream) {
-  if (n_prob < 0) return VC_ERR_INVALID_ARG;
-  if (n_prob == 0) return VC_OK;
-  if (!obs || !xyz4 || !offsets || !models || !out_mask || !(max_error >= 0.f)) return VC_ERR_INVALID_ARG;
-  if (((uintptr_t)xyz4) % 16 != 0 || ((uintptr_t)obs) % 8 != 0) return VC_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(absolute_pose_mask_kernel, dim3(n_prob), dim3(256), 0, (hipStream_t)stream, (const float2*)obs,
-                     (const float4*)xyz4, offsets, models, max_error * max_error, out_mask);
-  return vc::check_launch();
+  return vc::launch_inlier_mask<RuleP>({(const float2*)obs, (const float4*)xyz4}, offsets, n_prob, models, max_error, out_mask,
+                                       stream);
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/vitcolmap_hip.h"
-#include "common.h"
+#include "inlier_count.h"
 
 namespace {
 
@@ -41,44 +41,21 @@ __device__ __forceinline__ bool inlier_h(const float (&m)[9], float x1, float y1
   return pw != 0.f && bound < INFINITY && dx * dx + dy * dy <= bound;
 }
 
-// grid (n_pairs, hypothesis groups); 4 waves per workgroup, one hypothesis per wave and round, lanes over matches
-__global__ __launch_bounds__(256) void two_view_score_kernel(const float4* __restrict__ pts, const int32_t* __restrict__ offsets,
-                                                             const float* __restrict__ hyp, int K, int model, float t2,
-                                                             int32_t* __restrict__ counts) {
-  const int p = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lo = offsets[p], hi = offsets[p + 1];
-  for (int k = blockIdx.y * 4 + wave; k < K; k += gridDim.y * 4) {
-    float m[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) m[i] = hyp[((size_t)p * K + k) * 9 + i];
-    int n = 0;
-    for (int base = lo; base < hi; base += 64) {   // whole waves: the ballot needs every lane (base is wave-uniform)
-      const int i = base + lane;
-      bool in = false;
-      if (i < hi) {
-        const float4 q = pts[i];
-        in = model == 0 ? inlier_f(m, q.x, q.y, q.z, q.w, t2) : inlier_h(m, q.x, q.y, q.z, q.w, t2);
-      }
-      n += __popcll(__ballot(in));
-    }
-    if (lane == 0) counts[(size_t)p * K + k] = n;
-  }
-}
+struct Matches { const float4* __restrict__ pts; };                 // (x1, y1, x2, y2) per match
 
-__global__ __launch_bounds__(256) void two_view_mask_kernel(const float4* __restrict__ pts, const int32_t* __restrict__ offsets,
-                                                            const float* __restrict__ model9, int model, float t2,
-                                                            uint8_t* __restrict__ mask) {
-  const int p = blockIdx.x;
-  const int lo = offsets[p], hi = offsets[p + 1];
-  float m[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) m[i] = model9[(size_t)p * 9 + i];
-  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-    const float4 q = pts[i];
-    mask[i] = (model == 0 ? inlier_f(m, q.x, q.y, q.z, q.w, t2) : inlier_h(m, q.x, q.y, q.z, q.w, t2)) ? 1 : 0;
+template <bool (*Inlier)(const float (&)[9], float, float, float, float, float)>
+struct MatchRule {
+  static constexpr int W = 9;
+  using Data = Matches;
+  static bool usable(Data d) { return d.pts && ((uintptr_t)d.pts) % 16 == 0; }
+  static __device__ __forceinline__ bool inlier(const float (&m)[9], Data d, int i, float t2) {
+    const float4 q = d.pts[i];
+    asm volatile("" ::"v"(q.w));   // keeps the 16-byte load whole: left alone, H loads (x2, y2) apart, behind its pw test
+    return Inlier(m, q.x, q.y, q.z, q.w, t2);
   }
-}
+};
+using RuleF = MatchRule<inlier_f>;
+using RuleH = MatchRule<inlier_h>;
 
 }  // namespace
 
@@ -86,26 +63,16 @@ extern "C" {
 
 int vc_two_view_score(const float* pts, const int32_t* offsets, int n_pairs, const float* hypotheses, int n_hyp,
                       int model, float max_error, int32_t* out_counts, vc_stream_t stream) {
-  if (n_pairs < 0 || n_hyp < 0 || (model != VC_MODEL_FUNDAMENTAL && model != VC_MODEL_HOMOGRAPHY)) return VC_ERR_INVALID_ARG;
-  if (n_pairs == 0 || n_hyp == 0) return VC_OK;
-  if (!pts || !offsets || !hypotheses || !out_counts || !(max_error >= 0.f)) return VC_ERR_INVALID_ARG;
-  if (((uintptr_t)pts) % 16 != 0) return VC_ERR_INVALID_ARG;
-  if (n_pairs > 65535 * 32) return VC_ERR_UNSUPPORTED;
-  const int groups = n_hyp >= 64 ? 16 : (n_hyp + 3) / 4;
-  hipLaunchKernelGGL(two_view_score_kernel, dim3(n_pairs, groups), dim3(256), 0, (hipStream_t)stream, (const float4*)pts,
-                     offsets, hypotheses, n_hyp, model, max_error * max_error, out_counts);
-  return vc::check_launch();
+  if (model != VC_MODEL_FUNDAMENTAL && model != VC_MODEL_HOMOGRAPHY) return VC_ERR_INVALID_ARG;
+  const auto launch = model == VC_MODEL_FUNDAMENTAL ? vc::launch_inlier_count<RuleF> : vc::launch_inlier_count<RuleH>;
+  return launch({(const float4*)pts}, offsets, n_pairs, hypotheses, n_hyp, max_error, out_counts, stream);
 }
 
 int vc_two_view_inliers(const float* pts, const int32_t* offsets, int n_pairs, const float* models, int model,
                         float max_error, uint8_t* out_mask, vc_stream_t stream) {
-  if (n_pairs < 0 || (model != VC_MODEL_FUNDAMENTAL && model != VC_MODEL_HOMOGRAPHY)) return VC_ERR_INVALID_ARG;
-  if (n_pairs == 0) return VC_OK;
-  if (!pts || !offsets || !models || !out_mask || !(max_error >= 0.f)) return VC_ERR_INVALID_ARG;
-  if (((uintptr_t)pts) % 16 != 0) return VC_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(two_view_mask_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, (const float4*)pts, offsets,
-                     models, model, max_error * max_error, out_mask);
-  return vc::check_launch();
+  if (model != VC_MODEL_FUNDAMENTAL && model != VC_MODEL_HOMOGRAPHY) return VC_ERR_INVALID_ARG;
+  const auto launch = model == VC_MODEL_FUNDAMENTAL ? vc::launch_inlier_mask<RuleF> : vc::launch_inlier_mask<RuleH>;
+  return launch({(const float4*)pts}, offsets, n_pairs, models, max_error, out_mask, stream);
 }
 
 }  // extern "C"

@@ -5,15 +5,17 @@ published rule; parity with COLMAP's absolute-pose estimator is unpinned.
 Where the work runs
   HIP     the P3P solver, every sample of every problem in one launch (csrc/absolute_pose.hip, vc_p3p); the inlier counts
           of every hypothesis and the masks (vc_absolute_pose_score, vc_absolute_pose_inliers)
-  torch   the sampler (matching/_common._sample_indices), P = K [R | t], the Gauss-Newton refit over the best hypothesis'
-          inliers (batched float64, a 6x6 solve per problem and step) — plumbing, as the refit SVDs of estimate_e are
+  torch   the sampler and the tail of the RANSAC (matching/_common.py), P = K [R | t], the Gauss-Newton refit over the best
+          hypothesis' inliers (batched float64, a 6x6 solve per problem and step) — plumbing, as the refit SVDs of estimate_e are
   host    K^-1 per problem, the acceptance rule, the quaternion
 """
+from functools import partial
+
 import numpy as np
 import torch
 
 from .. import _lib
-from ..matching._common import SALT, _sample_indices
+from ..matching._common import SALT, _best_hypothesis, _pair_batch, _ransac_tail, _sample_indices
 from ..matching.essential import rot_to_quat
 
 NUM_HYP_P = 128
@@ -149,43 +151,32 @@ def estimate_absolute_poses(problems, device, max_error=ABS_POSE_MAX_ERROR, n_hy
     which = np.repeat(np.arange(n_prob), sizes)
     rays = obs32.astype(np.float64) * np.stack([Ki[which, 0, 0], Ki[which, 1, 1]], axis=1) + np.stack([Ki[which, 0, 2], Ki[which, 1, 2]], axis=1)
 
-    obs = torch.from_numpy(obs32).to(device).contiguous()
-    xyz4 = torch.from_numpy(np.concatenate([xyz32, np.ones((len(xyz32), 1), np.float32)], axis=1)).to(device).contiguous()
-    xyz64 = torch.from_numpy(xyz32.astype(np.float64)).to(device).contiguous()
-    obs64 = obs.to(torch.float64)
+    xyz4_rows = np.split(np.concatenate([xyz32, np.ones((len(xyz32), 1), np.float32)], axis=1), np.cumsum(sizes)[:-1])
+    xyz4, offsets, prob_of, seeds = _pair_batch(xyz4_rows, [p["seed"] for p in problems], device)
+    obs, xyz64 = torch.from_numpy(obs32).to(device).contiguous(), xyz4[:, :3].to(torch.float64).contiguous()
     rays = torch.from_numpy(rays).to(device).contiguous()
     K = torch.from_numpy(Kn).to(device)
-    offsets = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=device)
-    prob_of = torch.from_numpy(which).to(device)
-    counts_n = torch.tensor(sizes, dtype=torch.int64, device=device)
-    seeds = torch.tensor([int(p["seed"]) & 0xFFFFFFFF for p in problems], dtype=torch.int64, device=device)
 
-    idx = _sample_indices(seeds, counts_n, n_hyp, 3, SALT["P"]).to(torch.int32).contiguous()
+    idx = _sample_indices(seeds, (offsets[1:] - offsets[:-1]).to(torch.int64), n_hyp, 3, SALT["P"]).to(torch.int32).contiguous()
     pose, _ = solve_p3p(rays, xyz64, offsets, idx)
     pose = pose.reshape(n_prob, n_hyp * MAX_SOLUTIONS, 12)                                   # ranked by (sample, solution)
     hyp32 = projection_matrices(K, pose[:, :, :9].reshape(n_prob, -1, 3, 3), pose[:, :, 9:])
-    counts = score_poses(obs, xyz4, offsets, hyp32, max_error).to(torch.int64)
-    n = counts.shape[1]
-    key = counts * n + (n - 1 - torch.arange(n, device=counts.device))[None, :]              # most inliers, lowest rank on ties
-    kbest = (n - 1) - (key.max(dim=1).values % n)
+    score = partial(score_poses, obs, xyz4, offsets, max_error=max_error)
+    counts = score(hyp32).to(torch.int64)
     rows = torch.arange(n_prob, device=counts.device)
-    nbest = counts[rows, kbest]
-    best = torch.nan_to_num(pose[rows, kbest])                                               # NaN only where nbest is 0
-    Rb, tb = best[:, :9].reshape(n_prob, 3, 3), best[:, 9:]
-    best32 = hyp32[rows, kbest].contiguous()
-    mask = pose_masks(obs, xyz4, offsets, best32, max_error)
+    refit64 = None
 
-    Rr, tr = refit_poses(K, Rb, tb, obs64, xyz64, prob_of, mask.to(torch.float64))
-    ok = torch.isfinite(Rr).all(dim=-1).all(dim=-1) & torch.isfinite(tr).all(dim=-1) & (nbest > 0)
-    refit32 = projection_matrices(K, Rr[:, None], tr[:, None])[:, 0]
-    refit32 = torch.where(ok[:, None], refit32, torch.full_like(refit32, float("nan"))).contiguous()
-    rcount = score_poses(obs, xyz4, offsets, refit32[:, None, :].contiguous(), max_error).to(torch.int64)[:, 0]
-    use = ok & (rcount >= nbest)
-    final32 = torch.where(use[:, None], refit32, best32).contiguous()
-    fmask = pose_masks(obs, xyz4, offsets, final32, max_error).cpu().numpy()
-    Rf = torch.where(use[:, None, None], Rr, Rb).cpu().numpy()
-    tf = torch.where(use[:, None], tr, tb).cpu().numpy()
-    fcount = torch.where(use, rcount, nbest).cpu().numpy()
+    def refit(mask, nbest):                                                                  # Gauss-Newton from the best hypothesis
+        nonlocal refit64
+        best = torch.nan_to_num(pose[rows, _best_hypothesis(counts)])                        # NaN only where nbest is 0
+        Rr, tr = refit_poses(K, best[:, :9].reshape(n_prob, 3, 3), best[:, 9:], obs.to(torch.float64), xyz64, prob_of,
+                             mask.to(torch.float64))
+        refit64 = torch.cat([Rr.reshape(n_prob, 9), tr], dim=1)
+        return projection_matrices(K, Rr[:, None], tr[:, None])[:, 0], torch.isfinite(refit64).all(dim=1) & (nbest > 0)
+
+    _, fmask, fcount, kbest, use = _ransac_tail(hyp32, counts, score, partial(pose_masks, obs, xyz4, offsets, max_error=max_error), refit)
+    final = torch.where(use[:, None], refit64, pose[rows, kbest]).cpu().numpy()              # R row-major, then t
+    fmask, fcount = fmask.cpu().numpy(), fcount.cpu().numpy()
 
     out, lo = [], 0
     for p, size in enumerate(sizes):
@@ -194,7 +185,7 @@ def estimate_absolute_poses(problems, device, max_error=ABS_POSE_MAX_ERROR, n_hy
             out.append(_failure(size))
         else:
             ok_p = num >= ABS_POSE_MIN_NUM_INLIERS and num / size >= ABS_POSE_MIN_INLIER_RATIO
-            out.append(dict(success=bool(ok_p), qvec=rot_to_quat(Rf[p]), tvec=tf[p].copy(), num_inliers=num,
+            out.append(dict(success=bool(ok_p), qvec=rot_to_quat(final[p, :9].reshape(3, 3)), tvec=final[p, 9:].copy(), num_inliers=num,
                             inlier_mask=fmask[lo:lo + size].copy()))
         lo += size
     return out

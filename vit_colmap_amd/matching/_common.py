@@ -1,7 +1,7 @@
-"""What the two-view modules share (two_view.py, essential.py, pose.py): the constants of the verification rule, the
-published sampler, the front ends of the scoring kernels (csrc/two_view.hip), the batch layout of a chunk of pairs and
-the tail of the RANSAC that the F / H and the E estimators have in common.  matching/two_view.py re-exports all of it
-under these names."""
+"""What the estimators share (two_view.py, essential.py, pose.py and mapping/absolute_pose.py): the constants of the
+verification rule, the published sampler, the front ends of the two-view scoring kernels (csrc/two_view.hip), the batch
+layout of a chunk of pairs or problems and the tail of the RANSAC, which is the same for F, H, E and the absolute pose
+whatever residual scores them.  matching/two_view.py re-exports the two-view part under these names."""
 import numpy as np
 import torch
 
@@ -81,22 +81,27 @@ def _pair_batch(rows, seeds, device):
     return pts, offsets, pair_of, seeds
 
 
-def _ransac_tail(pts, offsets, hyp32, counts, model, max_error, refit):
-    """What every estimator does once its hypotheses hyp32 float32 (P, n, 9) are scored (counts int64 (P, n)): take the
-    hypothesis with most inliers (the lowest index on ties) and mask it; `refit(mask, nbest) -> (float32 (P, 9), ok bool
-    (P,))` fits one model to those inliers; the refit is taken iff it is `ok` and has no fewer inliers.
-    -> final model float32 (P, 9) (NaN where it has no inlier), its inlier mask bool (total,), its counts int64 (P,),
-    the index of the best hypothesis (P,) and where the refit was taken bool (P,)."""
+def _best_hypothesis(counts):
+    """counts int64 (P, n) -> the index of the hypothesis with most inliers (P,), the lowest on ties."""
     n = counts.shape[1]
     key = counts * n + (n - 1 - torch.arange(n, device=counts.device))[None, :]
-    kbest = (n - 1) - (key.max(dim=1).values % n)
+    return (n - 1) - (key.max(dim=1).values % n)
+
+
+def _ransac_tail(hyp32, counts, score, mask, refit):
+    """What every estimator does once its hypotheses hyp32 float32 (P, n, W) are scored (counts int64 (P, n)): take the
+    best one (_best_hypothesis) and mask it; `refit(mask, nbest) -> (float32 (P, W), ok bool (P,))` fits one model to those
+    inliers; the refit is taken iff it is `ok` and has no fewer inliers.  The residual is the caller's:
+    `score(float32 (P, n, W)) -> counts (P, n)` and `mask(float32 (P, W)) -> bool (total,)`.  -> final model float32 (P, W)
+    (NaN where it has no inlier), its inlier mask bool (total,), its count int64 (P,), kbest (P,), refit taken? bool (P,)."""
+    kbest = _best_hypothesis(counts)
     rows = torch.arange(counts.shape[0], device=counts.device)
     best, nbest = hyp32[rows, kbest].contiguous(), counts[rows, kbest]
-    refit32, ok = refit(_mask(pts, offsets, best, model, max_error), nbest)
-    rcount = _score(pts, offsets, refit32[:, None, :].contiguous(), model, max_error).to(torch.int64)[:, 0]
+    refit32, ok = refit(mask(best), nbest)
+    rcount = score(refit32[:, None, :].contiguous()).to(torch.int64)[:, 0]
     use = ok & (rcount >= nbest)
     final = torch.where(use[:, None], refit32, best).contiguous()
-    fmask = _mask(pts, offsets, final, model, max_error)
+    fmask = mask(final)
     fcount = torch.where(use, rcount, nbest)
     final = torch.where((fcount > 0)[:, None], final, torch.full_like(final, float("nan")))
     return final, fmask, fcount, kbest, use

@@ -8,12 +8,13 @@ Where the work runs
   host    the camera rows -> K table, the pose choice per CALIBRATED pair (numpy on the pair's inliers)
 """
 import logging
+from functools import partial
 
 import numpy as np
 import torch
 
 from .. import _lib
-from ._common import SALT, _ransac_tail, _sample_indices, _score
+from ._common import SALT, _mask, _ransac_tail, _sample_indices, _score
 
 logger = logging.getLogger(__name__)
 
@@ -104,7 +105,8 @@ def estimate_e(pts, offsets, pair_of, seeds, K1, K2, n_hyp=NUM_HYP_E, max_error=
     sol, _ = solve_five_point(xn, offsets, idx)
     sol = sol.reshape(P, n_hyp * MAX_SOLUTIONS, 3, 3)                       # ranked by (hypothesis, solution)
     hyp32 = _pixel_f(sol, K1i, K2i)
-    counts = _score(pts, offsets, hyp32, "F", max_error).to(torch.int64)
+    score = partial(_score, pts, offsets, model="F", max_error=max_error)
+    counts = score(hyp32).to(torch.int64)
     e_refit = None
 
     def refit(mask, nbest):
@@ -120,7 +122,7 @@ def estimate_e(pts, offsets, pair_of, seeds, K1, K2, n_hyp=NUM_HYP_E, max_error=
         refit32 = _pixel_f(e_refit[:, None], K1i, K2i)[:, 0]
         return torch.where(ok[:, None], refit32, torch.full_like(refit32, float("nan"))).contiguous(), ok
 
-    final, fmask, fcount, kbest, use = _ransac_tail(pts, offsets, hyp32, counts, "F", max_error, refit)
+    final, fmask, fcount, kbest, use = _ransac_tail(hyp32, counts, score, partial(_mask, pts, offsets, model="F", max_error=max_error), refit)
     e_final = torch.where(use[:, None, None], e_refit, sol[torch.arange(P, device=dev), kbest])
     e_final = e_final / torch.linalg.norm(e_final.reshape(P, 9), dim=1).clamp(min=1e-300)[:, None, None]
     return e_final, final, fmask, fcount, xn

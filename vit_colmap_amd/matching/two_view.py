@@ -14,6 +14,8 @@ Where the work runs
   host    gathering matched keypoints from the database, writing the rows (rank 0 only in a multi-GPU run)
 All pairs are verified in one batch: nothing loops over pairs on the device side.
 """
+from functools import partial
+
 import numpy as np
 import torch
 
@@ -94,7 +96,8 @@ def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
     P = offsets.shape[0] - 1
     S = 8 if model == "F" else 4
     hyp32, _, (T1, T2, n1, n2) = _hypotheses(model, pts, offsets, pair_of, seeds, n_hyp)
-    counts = _score(pts, offsets, hyp32, model, max_error).to(torch.int64)
+    score = partial(_score, pts, offsets, model=model, max_error=max_error)
+    counts = score(hyp32).to(torch.int64)
     Ar, br = _rows(model, n1[:, 0], n1[:, 1], n2[:, 0], n2[:, 1])             # F: (total, 8); H: (2 total, 8) stacked x then y
 
     def refit(mask, nbest):
@@ -111,7 +114,7 @@ def _estimate(model, pts, offsets, pair_of, seeds, n_hyp, max_error):
         ok = torch.isfinite(rsol).all(dim=-1) & (nbest >= S)
         return torch.where(ok[:, None], refit, torch.full_like(refit, float("nan"))).to(torch.float32).contiguous(), ok
 
-    return _ransac_tail(pts, offsets, hyp32, counts, model, max_error, refit)[:3]
+    return _ransac_tail(hyp32, counts, score, partial(_mask, pts, offsets, model=model, max_error=max_error), refit)[:3]
 
 
 def _stored_f(f9):
