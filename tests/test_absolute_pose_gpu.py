@@ -11,6 +11,7 @@ import torch
 from oracle import two_view_oracle as tv
 import util_absolute_pose as ua
 import util_essential as ue
+import util_solver
 from test_absolute_pose_spec import read_pairs, scene_images, write_scene_db
 
 pytestmark = pytest.mark.gpu
@@ -69,17 +70,7 @@ def minimal_problems():
     return np.concatenate(rays), np.concatenate(xyz), sols
 
 
-def compare_with_spec(device_sets, spec_sets):
-    """-> (problems with an unmatched solution, worst matched distance)."""
-    bad, worst = [], 0.0
-    for i, (D, S) in enumerate(zip(device_sets, spec_sets)):
-        d = np.array([[ua.pose_distance(*a, *b) for b in S] for a in D]).reshape(len(D), len(S))
-        ok = len(D) > 0 and len(S) > 0 and d.min(axis=1).max() <= TOL_POSE and d.min(axis=0).max() <= TOL_POSE
-        if ok:
-            worst = max(worst, d.min(axis=1).max(), d.min(axis=0).max())
-        elif len(D) or len(S):
-            bad.append(i)
-    return bad, worst
+compare_with_spec = partial(util_solver.compare_with_spec, distance=lambda a, b: ua.pose_distance(*a, *b), tol=TOL_POSE)
 
 
 def truth_distance(sols):

@@ -1,7 +1,7 @@
 """GPU tests of the calibrated branch: vc_essential_5pt against the numpy specification of
 tests/util_essential.py on the 300 exact minimal problems, its shapes, degenerate inputs and argument checks, then
 verify_pairs with cameras against the specification's rule and match_exhaustive end to end."""
-from functools import lru_cache
+from functools import lru_cache, partial
 
 import numpy as np
 import pytest
@@ -9,6 +9,7 @@ import torch
 
 from oracle import two_view_oracle as tv
 import util_essential as ue
+import util_solver
 from test_essential_spec import NONPLANAR, PAIR_ID, PLANAR, make_calibrated_db, scene_result
 
 pytestmark = pytest.mark.gpu
@@ -57,17 +58,7 @@ def minimal_problems():
     return np.concatenate(pts), sols
 
 
-def compare_with_spec(device_sets, spec_sets):
-    """-> (problems with an unmatched solution, worst matched distance)."""
-    bad, worst = [], 0.0
-    for i, (D, S) in enumerate(zip(device_sets, spec_sets)):
-        d = np.array([[ue.matrix_distance(a, b) for b in S] for a in D]).reshape(len(D), len(S))
-        ok = len(D) > 0 and len(S) > 0 and d.min(axis=1).max() <= TOL and d.min(axis=0).max() <= TOL
-        if ok:
-            worst = max(worst, d.min(axis=1).max(), d.min(axis=0).max())
-        elif len(D) or len(S):
-            bad.append(i)
-    return bad, worst
+compare_with_spec = partial(util_solver.compare_with_spec, distance=ue.matrix_distance, tol=TOL)
 
 
 def test_kernel_matches_the_spec_on_the_300_minimal_problems_one_hypothesis_per_pair():

@@ -1,7 +1,8 @@
 // The P3P solver of vit_colmap_amd/csrc/absolute_pose.hip on the CPU: its solver functions are __host__ __device__, so this
 // program includes the kernel source and calls solve_p3p on one problem after another.  It is how the solver is compared
-// with the specification without a GPU (the tolerance of tests/test_absolute_pose_gpu.py was measured with it), how it is
-// run under a host sanitizer and where a fault in it is looked for with a host debugger.
+// with the specification without a GPU (tests/test_solver_host.py; the tolerance of tests/test_absolute_pose_gpu.py was
+// measured with it), how it is run under a host sanitizer and where a fault in it is looked for with a host debugger.
+// tools/five_point_host.cpp is its counterpart for csrc/essential.hip.
 //
 //   hipcc -x hip --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -o p3p_host tools/p3p_host.cpp
 //   ./p3p_host problems.bin poses.bin

@@ -22,8 +22,9 @@
 //                   the rounding of the quartic's coefficients and of the division by D
 //   4. pose         an orthonormal frame on the world triangle and one on the camera-frame triangle: R = Fc Fw', t from the
 //                   centroids
-// Every loop has a constant trip count but the bisection and the polish, which are capped.  The solver functions are
-// __host__ __device__: a host program that includes this file can call solve_p3p on one problem.
+// Every loop has a constant trip count but the bisection and the polish, which are capped.  The kernel around solve_p3p and
+// the pieces of the root bracketing are those of minimal_solver.h, shared with the five-point solver.  The solver functions are
+// __host__ __device__: tools/p3p_host.cpp includes this file and calls solve_p3p on one problem after another.
 //
 // Scoring — float32 in exactly the specification's order of single operations (the library is built with -ffp-contract=off),
 // no division: p = P (X, 1); inlier iff p_w > 0 and |p_xy - obs p_w|^2 <= e^2 p_w^2.  The kernels are those of inlier_count.h.
@@ -33,23 +34,14 @@
 
 #include "../../include/vitcolmap_hip.h"
 #include "inlier_count.h"
+#include "minimal_solver.h"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kMaxPoses = 4;
-constexpr int kBisections = 64;
 constexpr int kPolish = 3;
 constexpr double kParallelTol = 1e-20;      // squared sine below which two rays, or two sides of the world triangle, are parallel
 constexpr double kProperTol = 1e-9;         // |det R - 1| of a returned rotation
-
-template <int DEG>
-__host__ __device__ __forceinline__ double horner(const double (&c)[DEG + 1], double t) {
-  double v = c[DEG];
-#pragma unroll
-  for (int i = DEG - 1; i >= 0; --i) v = v * t + c[i];
-  return v;
-}
 
 // One level of the bracketing: the (4 - DEG)-th derivative of sum a[i] t^i over (4 - DEG)!, of degree DEG, on [0, 1].  prev:
 // the roots of its derivative in positional slots 0 .. DEG - 2 (NaN: none), ascending among the slots that are set; with 0
@@ -59,29 +51,15 @@ template <int DEG>
 __host__ __device__ __forceinline__ void roots_level(const double (&a)[5], const double (&prev)[4], double (&cur)[4]) {
   constexpr int K = 4 - DEG;
   double coef[DEG + 1];
-  double binom = 1.0;
-#pragma unroll
-  for (int i = 0; i <= DEG; ++i) {
-    coef[i] = a[i + K] * binom;
-    binom = binom * (double)(i + 1 + K) / (double)(i + 1);
-  }
-  double lo = 0.0, f_lo = horner<DEG>(coef, 0.0);
+  vc::derivative_coefficients(coef, DEG, K, a);
+  double lo = 0.0, f_lo = vc::horner(coef, DEG, 0.0);
 #pragma unroll
   for (int s = 0; s < DEG; ++s) {
     const double hi = s < DEG - 1 ? prev[s] : 1.0;
     double root = NAN;
     if (hi == hi) {                                          // a breakpoint that is set
-      const double f_hi = horner<DEG>(coef, hi);
-      if ((f_lo < 0.0) != (f_hi < 0.0) && hi > lo) {
-        double l = lo, h = hi;
-        const bool neg = f_lo < 0.0;
-        for (int it = 0; it < kBisections; ++it) {
-          const double mid = 0.5 * (l + h);
-          if (!(mid > l && mid < h)) break;
-          if ((horner<DEG>(coef, mid) < 0.0) == neg) l = mid; else h = mid;
-        }
-        root = 0.5 * (l + h);
-      }
+      const double f_hi = vc::horner(coef, DEG, hi);
+      root = vc::root_of_piece(coef, DEG, lo, hi, f_lo, f_hi);
       lo = hi, f_lo = f_hi;
     }
     cur[s] = root;
@@ -275,43 +253,25 @@ __host__ __device__ __forceinline__ int solve_p3p(const double (&x)[3], const do
   return count;
 }
 
-__global__ __launch_bounds__(kWave) void p3p_kernel(const double* __restrict__ rays_n, const double* __restrict__ xyz,
-                                                    const int32_t* __restrict__ offsets, long long total,
-                                                    const int32_t* __restrict__ samples, int n_hyp, double* __restrict__ out_pose,
-                                                    int32_t* __restrict__ out_count) {
-  const long long h = (long long)blockIdx.x * kWave + threadIdx.x;
-  if (h >= total) return;
-  const int prob = (int)(h / n_hyp);
-  const long long lo = offsets[prob], m = (long long)offsets[prob + 1] - lo;
-  int s[3];
-  bool valid = lo >= 0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    s[i] = samples[h * 3 + i];
-    valid = valid && s[i] >= 0 && s[i] < m;
-  }
-  valid = valid && s[0] != s[1] && s[0] != s[2] && s[1] != s[2];
-  double* o = out_pose + h * (kMaxPoses * 12);                // the poses go straight to their slots: no per-lane array
-  int count = 0;
-  if (valid) {
+struct Correspondences { const double* __restrict__ rays_n; const double* __restrict__ xyz; };   // normalised (x, y); world points
+
+struct P3P {
+  static constexpr int kSample = 3, kMaxSolutions = kMaxPoses, kWidth = 12, kWorkDoubles = 0;
+  using Data = Correspondences;
+  static bool usable(Data d) { return d.rays_n && d.xyz; }
+  static __device__ __forceinline__ int solve(Data d, long long lo, const int (&s)[3], double*, int, double* out) {
     Triangle g;
     double x[3], y[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      const double* r = rays_n + (lo + s[i]) * 2;
-      const double* w = xyz + (lo + s[i]) * 3;
+      const double* r = d.rays_n + (lo + s[i]) * 2;
+      const double* w = d.xyz + (lo + s[i]) * 3;
       x[i] = r[0], y[i] = r[1];
       g.X[i][0] = w[0], g.X[i][1] = w[1], g.X[i][2] = w[2];
     }
-    count = solve_p3p(x, y, g, o);
+    return solve_p3p(x, y, g, out);
   }
-#pragma unroll
-  for (int k = 0; k < kMaxPoses; ++k)
-    if (k >= count)
-#pragma unroll
-      for (int i = 0; i < 12; ++i) o[12 * k + i] = NAN;
-  out_count[h] = count;
-}
+};
 
 // ---- scoring ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool inlier_p(const float (&m)[12], float x, float y, float z, float ox, float oy, float t2) {
@@ -342,15 +302,7 @@ extern "C" {
 
 int vc_p3p(const double* rays_n, const double* xyz, const int32_t* offsets, int n_prob, const int32_t* samples, int n_hyp,
            double* out_pose, int32_t* out_count, vc_stream_t stream) {
-  if (n_prob < 0 || n_hyp < 0) return VC_ERR_INVALID_ARG;
-  if (n_prob == 0 || n_hyp == 0) return VC_OK;
-  if (!rays_n || !xyz || !offsets || !samples || !out_pose || !out_count) return VC_ERR_INVALID_ARG;
-  const long long total = (long long)n_prob * n_hyp;
-  const long long blocks = (total + kWave - 1) / kWave;
-  if (blocks > 2147483647LL) return VC_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(p3p_kernel, dim3((unsigned)blocks), dim3(kWave), 0, (hipStream_t)stream, rays_n, xyz, offsets, total, samples,
-                     n_hyp, out_pose, out_count);
-  return vc::check_launch();
+  return vc::launch_minimal_solver<P3P>({rays_n, xyz}, offsets, n_prob, samples, n_hyp, out_pose, out_count, stream);
 }
 
 int vc_absolute_pose_score(const float* obs, const float* xyz4, const int32_t* offsets, int n_prob, const float* hyp, int n_hyp,

@@ -18,21 +18,20 @@
 //                   Gauss-Newton steps on the ten constraints themselves, evaluated on the orthonormal basis, take out the
 //                   rounding of the elimination and of the polynomial's coefficients; E is scaled to unit Frobenius norm
 // The run-time indexed arrays of step 5 (52 doubles per lane) live in LDS, lane-interleaved, 26 KiB per workgroup.
-// Every loop has a constant trip count but the bisection and the polish, which are capped (kBisections, kPolish).
-// The solver functions are __host__ __device__: a host program that includes this file can call solve_five_point on one
-// problem (stride 1 for the work area), which is how a fault in it is looked for with a host debugger.
+// Every loop has a constant trip count but the bisection and the polish, which are capped (vc::kBisections, kPolish).
+// The kernel around solve_five_point and the pieces of the root bracketing are those of minimal_solver.h, shared with P3P.
+// The solver functions are __host__ __device__: tools/five_point_host.cpp includes this file and calls solve_five_point on one
+// problem after another (stride 1 for the work area); tests/test_solver_host.py compares that program with the specification.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/vitcolmap_hip.h"
-#include "common.h"
+#include "minimal_solver.h"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kMaxSolutions = 10;
-constexpr int kBisections = 64;
 constexpr int kPolish = 3;
 constexpr int kWorkDoubles = 11 + 11 + 10 + 10 + 10; // polynomial, one derivative's coefficients, three root lists
 constexpr double kRankTol = 1e-12;                   // relative: a column of the 9x5 system inside the span of the others
@@ -219,41 +218,29 @@ struct Strided {
   __host__ __device__ __forceinline__ double& operator[](int i) const { return p[i * stride]; }
 };
 
-__host__ __device__ __forceinline__ double horner(const Strided c, int degree, double t) {
-  double v = c[degree];
-  for (int i = degree - 1; i >= 0; --i) v = v * t + c[i];
-  return v;
-}
+// The polynomial's coefficients from the constant up, or those of its reversal.
+struct Poly10 {
+  Strided a;
+  bool reversed;
+  __host__ __device__ __forceinline__ double operator[](int i) const { return reversed ? a[10 - i] : a[i]; }
+};
 
 // The real roots in [-1, 1] of sum a[i] t^i (reversed: of sum a[10 - i] t^i), ascending, into the list the function
 // returns through `roots`; -> their number.  Level k works on the k-th derivative over k!, whose coefficients are
 // a[i + k] binomial(i + k, k); its roots in [-1, 1] and the two ends split the interval into pieces on which the
 // (k - 1)-th derivative is monotone, so a sign change at the ends of a piece brackets exactly one root.
-__host__ __device__ __forceinline__ int real_roots_unit(const Strided a, bool reversed, const Strided coef, Strided prev, Strided cur,
-                                                        Strided* roots) {
+__host__ __device__ __forceinline__ int real_roots_unit(const Poly10 a, const Strided coef, Strided prev, Strided cur, Strided* roots) {
   int n_prev = 0;
   for (int k = 9; k >= 0; --k) {
     const int degree = 10 - k;
-    double binom = 1.0;
-    for (int i = 0; i <= degree; ++i) {
-      coef[i] = (reversed ? a[10 - (i + k)] : a[i + k]) * binom;
-      binom = binom * (double)(i + 1 + k) / (double)(i + 1);
-    }
+    vc::derivative_coefficients(coef, degree, k, a);
     int n_cur = 0;
-    double lo = -1.0, f_lo = horner(coef, degree, lo);
+    double lo = -1.0, f_lo = vc::horner(coef, degree, lo);
     for (int s = 0; s <= n_prev; ++s) {
       const double hi = s < n_prev ? prev[s] : 1.0;
-      const double f_hi = horner(coef, degree, hi);
-      if ((f_lo < 0.0) != (f_hi < 0.0) && hi > lo) {
-        double l = lo, h = hi;
-        const bool neg = f_lo < 0.0;
-        for (int it = 0; it < kBisections; ++it) {
-          const double mid = 0.5 * (l + h);
-          if (!(mid > l && mid < h)) break;
-          if ((horner(coef, degree, mid) < 0.0) == neg) l = mid; else h = mid;
-        }
-        if (n_cur < kMaxSolutions) cur[n_cur++] = 0.5 * (l + h);
-      }
+      const double f_hi = vc::horner(coef, degree, hi);
+      const double root = vc::root_of_piece(coef, degree, lo, hi, f_lo, f_hi);
+      if (root == root && n_cur < kMaxSolutions) cur[n_cur++] = root;
       lo = hi, f_lo = f_hi;
     }
     const Strided t = prev;
@@ -466,9 +453,9 @@ __host__ __device__ __forceinline__ int solve_five_point(const double (&x1)[5], 
     for (int i = 0; i < 11; ++i) poly[i] = p[i] / big;
   }
   Strided roots{nullptr, stride};
-  const int n_dir = real_roots_unit(poly, false, coef, r0, r1, &roots);
+  const int n_dir = real_roots_unit({poly, false}, coef, r0, r1, &roots);
   for (int i = 0; i < n_dir; ++i) mid[i] = roots[i];
-  const int n_rev = real_roots_unit(poly, true, coef, r0, r1, &roots);
+  const int n_rev = real_roots_unit({poly, true}, coef, r0, r1, &roots);
   // ascending z: the roots below -1 (w in (-1, 0), descending), those in [-1, 1], those above 1 (w in (0, 1), descending)
   int count = 0;
   for (int i = n_rev - 1; i >= 0; --i) {
@@ -484,39 +471,22 @@ __host__ __device__ __forceinline__ int solve_five_point(const double (&x1)[5], 
   return count;
 }
 
-__global__ __launch_bounds__(kWave) void essential_5pt_kernel(const double* __restrict__ pts_n, const int32_t* __restrict__ offsets,
-                                                              long long total, const int32_t* __restrict__ samples, int n_hyp,
-                                                              double* __restrict__ out_e, int32_t* __restrict__ out_count) {
-  __shared__ double work[kWorkDoubles][kWave];
-  const long long h = (long long)blockIdx.x * kWave + threadIdx.x;
-  if (h >= total) return;
-  const int pair = (int)(h / n_hyp);
-  const long long lo = offsets[pair], m = (long long)offsets[pair + 1] - lo;
-  double x1[5], y1[5], x2[5], y2[5];
-  int s[5];
-  bool valid = lo >= 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    s[i] = samples[h * 5 + i];
-    valid = valid && s[i] >= 0 && s[i] < m;
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i)
-#pragma unroll
-    for (int j = i + 1; j < 5; ++j) valid = valid && s[i] != s[j];
-  double* e = out_e + h * (kMaxSolutions * 9);
-  int count = 0;
-  if (valid) {
+struct Matches { const double* __restrict__ pts_n; };       // normalised x1 y1 x2 y2 per correspondence
+
+struct FivePoint {
+  static constexpr int kSample = 5, kMaxSolutions = ::kMaxSolutions, kWidth = 9, kWorkDoubles = ::kWorkDoubles;
+  using Data = Matches;
+  static bool usable(Data d) { return d.pts_n; }
+  static __device__ __forceinline__ int solve(Data d, long long lo, const int (&s)[5], double* work, int stride, double* out) {
+    double x1[5], y1[5], x2[5], y2[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-      const double* q = pts_n + (lo + s[i]) * 4;
+      const double* q = d.pts_n + (lo + s[i]) * 4;
       x1[i] = q[0], y1[i] = q[1], x2[i] = q[2], y2[i] = q[3];
     }
-    count = solve_five_point(x1, y1, x2, y2, &work[0][threadIdx.x], kWave, e);
+    return solve_five_point(x1, y1, x2, y2, work, stride, out);
   }
-  for (int i = count * 9; i < kMaxSolutions * 9; ++i) e[i] = NAN;
-  out_count[h] = count;
-}
+};
 
 }  // namespace
 
@@ -524,15 +494,7 @@ extern "C" {
 
 int vc_essential_5pt(const double* pts_n, const int32_t* offsets, int n_pairs, const int32_t* samples, int n_hyp,
                      double* out_E, int32_t* out_count, vc_stream_t stream) {
-  if (n_pairs < 0 || n_hyp < 0) return VC_ERR_INVALID_ARG;
-  if (n_pairs == 0 || n_hyp == 0) return VC_OK;
-  if (!pts_n || !offsets || !samples || !out_E || !out_count) return VC_ERR_INVALID_ARG;
-  const long long total = (long long)n_pairs * n_hyp;
-  const long long blocks = (total + kWave - 1) / kWave;
-  if (blocks > 2147483647LL) return VC_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(essential_5pt_kernel, dim3((unsigned)blocks), dim3(kWave), 0, (hipStream_t)stream, pts_n, offsets, total,
-                     samples, n_hyp, out_E, out_count);
-  return vc::check_launch();
+  return vc::launch_minimal_solver<FivePoint>({pts_n}, offsets, n_pairs, samples, n_hyp, out_E, out_count, stream);
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..matching._common import SALT, _best_hypothesis, _pair_batch, _ransac_tail, _sample_indices
+from ..matching._common import SALT, _best_hypothesis, _pair_batch, _ransac_tail, _sample_indices, _solve_minimal
 from ..matching.essential import rot_to_quat
 
 NUM_HYP_P = 128
@@ -32,17 +32,7 @@ REFIT_STEPS = 10
 def solve_p3p(rays_n, xyz, offsets, samples):
     """rays_n float64 (total, 2), xyz float64 (total, 3), offsets int32 (P + 1), samples int32 (P, n_hyp, 3), all on one GPU
     -> pose float64 (P, n_hyp, 4, 12) (R row-major then t; NaN past the count), count int32 (P, n_hyp)."""
-    if not (rays_n.is_cuda and rays_n.dtype == torch.float64 and xyz.dtype == torch.float64 and offsets.dtype == torch.int32
-            and samples.dtype == torch.int32):
-        raise ValueError("solve_p3p needs float64 rays and points and int32 offsets / samples on the GPU")
-    lib = _lib.load()
-    P, n_hyp = int(samples.shape[0]), int(samples.shape[1])
-    rays_n, xyz, offsets, samples = rays_n.contiguous(), xyz.contiguous(), offsets.contiguous(), samples.contiguous()
-    pose = torch.empty((P, n_hyp, MAX_SOLUTIONS, 12), dtype=torch.float64, device=rays_n.device)
-    count = torch.zeros((P, n_hyp), dtype=torch.int32, device=rays_n.device)
-    _lib.check(lib.vc_p3p(_lib.ptr(rays_n), _lib.ptr(xyz), _lib.ptr(offsets), P, _lib.ptr(samples), n_hyp, _lib.ptr(pose),
-                          _lib.ptr(count), _lib.stream_ptr()), "vc_p3p")
-    return pose, count
+    return _solve_minimal("vc_p3p", "solve_p3p needs float64 rays and points", [rays_n, xyz], offsets, samples, MAX_SOLUTIONS, 12)
 
 
 def score_poses(obs, xyz4, offsets, hyp, max_error):

@@ -69,6 +69,23 @@ def _mask(pts, offsets, models, model, max_error):
     return mask.bool()
 
 
+def _solve_minimal(entry, needs, points, offsets, samples, max_solutions, width):
+    """The front end of a minimal-solver kernel (csrc/minimal_solver.h).  points: the float64 arrays of the correspondences,
+    in the entry point's order; offsets int32 (P + 1), samples int32 (P, n_hyp, S), all on one GPU
+    -> solutions float64 (P, n_hyp, max_solutions, width) (NaN past the count), count int32 (P, n_hyp)."""
+    if not (points[0].is_cuda and all(p.dtype == torch.float64 for p in points) and offsets.dtype == torch.int32
+            and samples.dtype == torch.int32):
+        raise ValueError(f"{needs} and int32 offsets / samples on the GPU")
+    lib = _lib.load()
+    P, n_hyp = int(samples.shape[0]), int(samples.shape[1])
+    points, offsets, samples = [p.contiguous() for p in points], offsets.contiguous(), samples.contiguous()
+    out = torch.empty((P, n_hyp, max_solutions, width), dtype=torch.float64, device=points[0].device)
+    count = torch.zeros((P, n_hyp), dtype=torch.int32, device=points[0].device)
+    _lib.check(getattr(lib, entry)(*map(_lib.ptr, points), _lib.ptr(offsets), P, _lib.ptr(samples), n_hyp, _lib.ptr(out),
+                                   _lib.ptr(count), _lib.stream_ptr()), entry)
+    return out, count
+
+
 def _pair_batch(rows, seeds, device):
     """The device layout of a chunk of pairs.  rows: one (M_i, 4) array per pair, seeds: one integer per pair (or None)
     -> points (sum M_i, 4) in the arrays' dtype, offsets int32 (P + 1,), pair_of int64 (sum M_i,) the pair of every

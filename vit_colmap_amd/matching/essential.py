@@ -13,8 +13,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from .. import _lib
-from ._common import SALT, _mask, _ransac_tail, _sample_indices, _score
+from ._common import SALT, _mask, _ransac_tail, _sample_indices, _score, _solve_minimal
 
 logger = logging.getLogger(__name__)
 
@@ -66,16 +65,7 @@ def camera_table(db, ids):
 def solve_five_point(pts_n, offsets, samples):
     """pts_n float64 (total, 4), offsets int32 (P + 1), samples int32 (P, n_hyp, 5), all on one GPU
     -> E float64 (P, n_hyp, 10, 9) (NaN past the count), count int32 (P, n_hyp)."""
-    if not (pts_n.is_cuda and pts_n.dtype == torch.float64 and offsets.dtype == torch.int32 and samples.dtype == torch.int32):
-        raise ValueError("solve_five_point needs float64 points and int32 offsets / samples on the GPU")
-    lib = _lib.load()
-    P, n_hyp = int(samples.shape[0]), int(samples.shape[1])
-    pts_n, offsets, samples = pts_n.contiguous(), offsets.contiguous(), samples.contiguous()
-    E = torch.empty((P, n_hyp, MAX_SOLUTIONS, 9), dtype=torch.float64, device=pts_n.device)
-    count = torch.zeros((P, n_hyp), dtype=torch.int32, device=pts_n.device)
-    _lib.check(lib.vc_essential_5pt(_lib.ptr(pts_n), _lib.ptr(offsets), P, _lib.ptr(samples), n_hyp, _lib.ptr(E), _lib.ptr(count),
-                                    _lib.stream_ptr()), "vc_essential_5pt")
-    return E, count
+    return _solve_minimal("vc_essential_5pt", "solve_five_point needs float64 points", [pts_n], offsets, samples, MAX_SOLUTIONS, 9)
 
 
 def normalise_points(p64, pair_of, K1i, K2i):
