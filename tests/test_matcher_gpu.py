@@ -132,6 +132,24 @@ def test_match_pairs_ragged_counts_and_empty_images():
     assert_batch_equal(desc, counts, pairs, max_ratio=0.95, max_distance=1.2)
 
 
+@pytest.mark.parametrize("d", [512, 768, 1024])
+def test_match_pairs_long_descriptors_exact(d):
+    """Descriptors beyond 384 bytes run the fused kernel with one row tile per wave (256 rows per pass: 300 rows are two
+    passes, 257 cross the pass boundary by one row) and its own finalisation (acos, not the table).  Duplicate rows give
+    ties and rows that only the cross check removes; the three option sets must give three different lists."""
+    counts = [300, 257, 0, 64, 1]
+    desc, counts = image_set(900 + d, 5, 300, d, kind="scene", counts=counts, noise=0.6)
+    desc[1, 200:210] = desc[1, 0:10]
+    desc = np.ascontiguousarray(desc)
+    pairs = mo.exhaustive_pairs(5)
+    pairs = np.ascontiguousarray(np.concatenate([pairs, pairs[:, ::-1]]).astype(np.int32))
+    totals = [int(assert_batch_equal(desc, counts, pairs).sum()),
+              int(assert_batch_equal(desc, counts, pairs, cross_check=False).sum()),
+              int(assert_batch_equal(desc, counts, pairs, max_ratio=0.95, max_distance=1.2).sum())]
+    assert len(set(totals)) == 3, totals
+    assert totals[0] > 200, totals
+
+
 def test_match_pairs_max_size_and_order_of_pairs():
     n_images, n_max, d = 3, 2048, 256
     desc, counts = image_set(7, n_images, n_max, d, kind="scene", noise=0.15)

@@ -5,7 +5,7 @@
  *
  *   theta(s) = RN_f32(acos_f64(min(f32(s) * 2^-18, 1)))     (specification: oracle/matcher_oracle.py)
  *
- * The same expression runs on the device in theta_dev(); tests/test_matcher_gpu.py compares the
+ * The same expression runs on the device in theta() of matcher.hip; tests/test_matcher_gpu.py compares the
  * table (vc_theta_table), the device evaluation (vc_theta_eval) and the oracle for every input.
  */
 #include <math.h>

@@ -41,11 +41,11 @@ constexpr int kTile = 32;                    // MFMA tile edge
 static_assert(VC_MAX_KEYPOINTS <= 64 * 32, "the row search packs the column-tile number into 6 bits");
 constexpr int kFragBytes = 1024;             // 64 lanes x 16 B
 
-__host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+__host__ __device__ constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
 // 32-row tiles per prepared image, rounded up to a whole pass of the pair kernel (8 waves x 2
 // row tiles) so that every tile index a workgroup touches exists; the extra tiles hold
 // neutral rows (all-zero descriptors: similarity 0 with everything).
-__host__ __device__ inline int tiles_of(int n_max) { return ceil_div(ceil_div(n_max, kTile), 16) * 16; }
+__host__ __device__ constexpr int tiles_of(int n_max) { return ceil_div(ceil_div(n_max, kTile), 16) * 16; }
 __host__ __device__ inline int ksteps_of(int d) { return ceil_div(d, 32); }
 // K steps in the "head" of a descriptor for the exact early-out of pair2_kernel (== ks: no early-out for that length)
 constexpr int kHeadSteps12 = 4;   // head k-steps of a 384-byte descriptor (a multiple of the window below)
@@ -63,46 +63,6 @@ __host__ __device__ inline int packed_head(int word) { return word >> 16; }
 __host__ __device__ inline int packed_tail(int word) { return word & 0xffff; }
 __host__ __device__ inline size_t image_bytes(int n_tiles, int ks) {
   return (size_t)n_tiles * ks * kFragBytes + (size_t)n_tiles * kTile * sizeof(int32_t) * 2 + (size_t)n_tiles * sizeof(int32_t);
-}
-
-// ---------------------------------------------------------------------------------------
-// theta / accept — identical arithmetic to oracle/matcher_oracle.c
-// ---------------------------------------------------------------------------------------
-__device__ inline float theta_dev(int s) {
-  float x = (float)s * (1.0f / (512.0f * 512.0f));
-  x = x > 1.0f ? 1.0f : x;
-  return (float)acos((double)x);
-}
-
-__device__ inline bool accept_dev(int best, int second, float max_ratio, float max_distance) {
-  if (best <= 0) return false;
-  const float tb = theta_dev(best);
-  if (tb > max_distance) return false;
-  const float ts = theta_dev(second);
-  if (tb >= max_ratio * ts) return false;
-  return true;
-}
-
-// theta(s) for every s in [0, 512^2], generated at build time by gen_theta_table.c (same expression as
-// theta_dev; compared entry by entry on the device and against the oracle in tests/test_matcher_gpu.py).
-// With it the acceptance tests of a row are two L2-resident loads, a multiply and two compares: no
-// double-precision acos in the pair kernel, hence no register pressure from it around the pair loop.
-__device__ inline unsigned int umin(unsigned int a, unsigned int b);
-__device__ const uint32_t kThetaBits[512 * 512 + 1] = {
-#include "theta_table.inc"
-};
-__device__ __forceinline__ float theta_tab(int s) {
-  return __uint_as_float(kThetaBits[umin((u32)s, 512u * 512u)]);   // (unsigned clamp: no index is ever out of the table)
-}
-// accept_dev with table angles.  `s_low` (relevance_threshold): a best <= s_low is rejected whatever the
-// runner-up is, so those rows never touch the table (on non-matching image pairs that is every row).
-__device__ __forceinline__ bool accept_tab(int best, int second, float max_ratio, float max_distance, int s_low) {
-  if (best <= 0 || best <= s_low) return false;
-  const float tb = theta_tab(best);
-  const float ts = theta_tab(second);
-  if (tb > max_distance) return false;
-  if (tb >= max_ratio * ts) return false;
-  return true;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -127,6 +87,57 @@ __device__ inline u32 half_max(u32 v) {
   v = umax(v, (u32)__builtin_amdgcn_ds_swizzle((int)v, 0x401F));  // lane ^ 16
   return v;
 }
+
+// ---------------------------------------------------------------------------------------
+// theta / accept — identical arithmetic to oracle/matcher_oracle.c
+// ---------------------------------------------------------------------------------------
+__host__ __device__ inline float theta(int s) {
+  float x = (float)s * (1.0f / (512.0f * 512.0f));
+  x = x > 1.0f ? 1.0f : x;
+  return (float)acos((double)x);
+}
+
+__device__ inline bool accept_dev(int best, int second, float max_ratio, float max_distance) {
+  if (best <= 0) return false;
+  const float tb = theta(best);
+  if (tb > max_distance) return false;
+  const float ts = theta(second);
+  if (tb >= max_ratio * ts) return false;
+  return true;
+}
+
+// theta(s) for every s in [0, 512^2], generated at build time by gen_theta_table.c (same expression as
+// theta(); compared entry by entry on the device and against the oracle in tests/test_matcher_gpu.py).
+// With it the acceptance tests of a row are two L2-resident loads, a multiply and two compares: no
+// double-precision acos in the pair kernel, hence no register pressure from it around the pair loop.
+__device__ const uint32_t kThetaBits[512 * 512 + 1] = {
+#include "theta_table.inc"
+};
+__device__ __forceinline__ float theta_tab(int s) {
+  return __uint_as_float(kThetaBits[umin((u32)s, 512u * 512u)]);   // (unsigned clamp: no index is ever out of the table)
+}
+// accept_dev with table angles.  `s_low` (relevance_threshold): a best <= s_low is rejected whatever the
+// runner-up is, so those rows never touch the table (on non-matching image pairs that is every row).
+__device__ __forceinline__ bool accept_tab(int best, int second, float max_ratio, float max_distance, int s_low) {
+  if (best <= 0 || best <= s_low) return false;
+  const float tb = theta_tab(best);
+  const float ts = theta_tab(second);
+  if (tb > max_distance) return false;
+  if (tb >= max_ratio * ts) return false;
+  return true;
+}
+// the two rules as finalise_pair takes them: ok = accept(best, second)
+struct AcceptAcos {
+  float max_ratio, max_distance;
+  __device__ __forceinline__ bool operator()(int best, int second) const { return accept_dev(best, second, max_ratio, max_distance); }
+};
+struct AcceptTable {
+  float max_ratio, max_distance;
+  int s_low;
+  __device__ __forceinline__ bool operator()(int best, int second) const {
+    return accept_tab(best, second, max_ratio, max_distance, s_low);
+  }
+};
 
 // ---------------------------------------------------------------------------------------
 // prepare: uint8 [n_images][n_max][d] -> fragment-major biased int8 + row sums
@@ -229,35 +240,84 @@ __global__ void prepare_kernel(const uint8_t* __restrict__ desc, const int32_t* 
 //     vmcnt(0) in the wave whose tile is due (no wave has more than one tile in flight);
 //   * per-row top-2 lives in registers as packed keys, per-column top-2 is merged across
 //     waves with two LDS atomics per lane and tile (order independent, see col_merge).
-//
-// Dynamic LDS: [ring NS x KS KiB][colbest u64 x n_pad][colsecond u32 x n_pad]
-//              [cterm i32 x n_pad][m21 i32 x n_pad][rbest, rsecond, ridx i32 x n_pad]
-//              [crow6 i32 x 8 waves x 64 rows][row-reduce scratch 8 waves x 4224 B][8 ints]
 constexpr int kLdsBytes = 160 * 1024;
 // end-of-pass row reduction: per wave 16 rows x (32 + 1 pad) entries of {best key, second key}
 constexpr int kRowScratchEntries = 16 * 33;
 constexpr int kRowScratchBytes = kRowScratchEntries * 8;
 constexpr int kMaxSlots = 8;  // PF <= 7 keeps "one tile in flight per wave" true for 8 waves
-constexpr int kPairWindow = 32;   // pair2_kernel: pairs-with-work described in LDS at a time (half a wave builds the list)
 
-__host__ __device__ inline size_t lds_fixed_bytes(int n_pad) {
-  return (size_t)n_pad * (8 + 4 + 4 + 4 + 12) + kWaves * 64 * 4 + kWaves * kRowScratchBytes + 64;
+// K-step counts with a compiled kernel; a descriptor is zero-padded up to the next one.
+#define VC_KS_LIST 2, 4, 8, 12, 16, 24, 32
+constexpr int kKsList[] = {VC_KS_LIST};
+constexpr int kMaxKs2 = 12;   // RT = 2 (512 rows per pass) while its register budget holds (A fragments: 2*KS*4 VGPRs)
+constexpr int row_tiles_of(int ks) { return ks <= kMaxKs2 ? 2 : 1; }   // long descriptors: one row tile per wave
+constexpr int kMaxPad = tiles_of(VC_MAX_KEYPOINTS) * kTile;   // rows of the largest prepared image
+
+// The dynamic LDS of a pair kernel is laid out ONCE, by a constexpr plan that both sides use: the kernel takes every
+// pointer from it, the host the fixed size (the plan with an empty ring), from that the number of ring slots, and the
+// launch's LDS size (`end`).  LdsCursor hands out consecutive regions; all offsets are in bytes from the start of LDS.
+struct LdsCursor {
+  u32 at;
+  __host__ __device__ constexpr u32 take(u32 bytes, u32 align = 4) {
+    at = (at + align - 1) / align * align;
+    const u32 off = at;
+    at += bytes;
+    return off;
+  }
+};
+// pair_kernel:      [ring NS x KS KiB][colbest u64 x n_pad][colsecond u32 x n_pad]
+//                   [cterm i32 x n_pad][m21 i32 x n_pad][rbest, rsecond, ridx i32 x n_pad]
+//                   [crow6 i32 x 8 waves x 64 rows][row-reduce scratch 8 waves x 4224 B][wave_count 8 ints]
+// guided matching adds: column keypoint y (x lives in m21, which the tile loop leaves alone) and the row terms of
+// every wave's RT * 32 rows
+struct PairLds {
+  u32 colbest, colsecond;        // [n_pad] column search: (s << 32 | ~row) and the runner-up's s
+  u32 cterm;                     // [n_pad] column terms 128*rb + 32640*D
+  u32 m21;                       // [n_pad] accepted row of every column (cross check); GUIDED: column keypoint x until then
+  u32 rbest, rsecond, ridx;      // [n_pad] row results
+  u32 crow6;                     // [wave][64] row terms 128*ra - 49024*D
+  u32 rscratch;                  // [wave][kRowScratchEntries] uint2: reduce_rows
+  u32 wave_count;                // [kWaves] append_ordered
+  u32 gcy;                       // GUIDED: [n_pad] column keypoint y
+  u32 growg;                     // GUIDED: [wave][RT*32] v4i row terms of the geometric test
+  u32 end;
+};
+__host__ __device__ constexpr PairLds pair_lds(u32 ring_bytes, int n_pad, int rt, bool guided) {
+  LdsCursor c{ring_bytes};
+  PairLds l{};
+  l.colbest = c.take(n_pad * 8, 8);
+  l.colsecond = c.take(n_pad * 4);
+  l.cterm = c.take(n_pad * 4);
+  l.m21 = c.take(n_pad * 4);
+  l.rbest = c.take(n_pad * 4);
+  l.rsecond = c.take(n_pad * 4);
+  l.ridx = c.take(n_pad * 4);
+  l.crow6 = c.take(kWaves * 64 * 4, 16);
+  l.rscratch = c.take(kWaves * kRowScratchBytes, 8);
+  l.wave_count = c.take(kWaves * 4);
+  l.gcy = c.take(guided ? n_pad * 4 : 0);
+  l.growg = c.take(guided ? kWaves * rt * kTile * 16 : 0, 16);
+  l.end = c.take(0, 16);
+  return l;
 }
-// pair2_kernel: column records of 16 bytes (best key, second, pad), column terms, m21 + row results, three row-term arrays per
-// wave (full, head, full - head), row-reduce scratch, head column terms + tile bounds of b, the copy of the NEXT pair's
-// column sums / tile bounds (LDS-DMA), the pair window
-__host__ __device__ inline size_t lds_fixed_bytes2(int n_pad) {
-  return (size_t)n_pad * (16 + 4 + 4 + 12) + 3 * (kWaves * 64 * 4) + kWaves * kRowScratchBytes + 64 +
-         (size_t)n_pad * 4 + (size_t)(n_pad / kTile) * 4 + ((size_t)n_pad * 4 + (size_t)(n_pad / kTile) * 4) +
-         kPairWindow * 16 + 16;
-}
-// number of ring slots for this problem size (0 = does not fit)
-inline int plan_slots(int ks, int n_pad) {
-  const long avail = (long)kLdsBytes - (long)lds_fixed_bytes(n_pad);
-  long ns = avail / ((long)ks * kFragBytes);
+// Ring slots that fit beside `fixed_bytes` (0 = the kernel does not fit).  Two row tiles per wave and the persistent
+// kernel need three slots, one row tile two.
+constexpr int min_slots(int rt, bool persistent) { return (rt == 2 || persistent) ? 3 : 2; }
+constexpr int slots_beside(u32 fixed_bytes, int ks, int least) {
+  long ns = ((long)kLdsBytes - (long)fixed_bytes) / ((long)ks * kFragBytes);
   if (ns > kMaxSlots) ns = kMaxSlots;
-  return ns >= 2 ? (int)ns : 0;
+  return ns >= least ? (int)ns : 0;
 }
+constexpr int plan_slots(int ks, int n_pad, int rt, bool guided) {
+  return slots_beside(pair_lds(0, n_pad, rt, guided).end, ks, min_slots(rt, false));
+}
+constexpr bool pair_lds_ok(int ks, int rt, bool guided) {
+  const PairLds l = pair_lds(plan_slots(ks, kMaxPad, rt, guided) * ks * kFragBytes, kMaxPad, rt, guided);
+  return l.end <= (u32)kLdsBytes && l.colbest % 8 == 0 && l.rscratch % 8 == 0 && l.crow6 % 16 == 0 && l.growg % 16 == 0;
+}
+template <int... KS>   // the instantiations: row_tiles_of(KS) unguided, one row tile guided (vc_match_pairs_guided_u8)
+constexpr bool pair_lds_ok() { return ((pair_lds_ok(KS, row_tiles_of(KS), false) && pair_lds_ok(KS, 1, true)) && ...); }
+static_assert(pair_lds_ok<VC_KS_LIST>(), "pair_kernel's LDS plan: size and alignment at the largest block, every length");
 
 __device__ inline void wg_barrier() {
   // LDS writes/atomics of this wave are complete before it arrives; LDS-DMA stays in flight
@@ -278,12 +338,6 @@ __device__ __forceinline__ void glds16(const void* gsrc, u32 lds_dst_any) {
   // source — one written in asm right behind a v_mov read a stale register.)
   asm volatile("" : "+v"(lds_dst_any));
   vc::lds_dma16(gsrc, (u32)__builtin_amdgcn_readfirstlane((int)lds_dst_any));
-}
-
-inline int plan_slots2(int ks, int n_pad) {
-  long ns = ((long)kLdsBytes - (long)lds_fixed_bytes2(n_pad)) / ((long)ks * kFragBytes);
-  if (ns > kMaxSlots) ns = kMaxSlots;
-  return ns >= 3 ? (int)ns : 0;
 }
 
 // One 256-byte LDS-DMA piece (64 lanes x 4 B; inactive lanes copy nothing): LDS destination = `lds_dst` + lane*4.
@@ -702,6 +756,128 @@ __device__ __forceinline__ bool epilogue_phase2(const v16i (&acc)[2], u32 (&rbes
   return hit;
 }
 
+// ---------------------------------------------------------------------------------------
+// What follows the tile loop: the row results of a pass (both pair kernels), then the match list (pair_kernel; pair2_kernel
+// keeps these steps written out, see there)
+// ---------------------------------------------------------------------------------------
+// Row results of a pass: store(row, best, second, idx) for every row < n1 of the wave's RT row tiles.
+// Each row's candidates sit in 32 lanes (one per column residue c).  Transpose through a
+// wave-private LDS slice, 16 rows per round: lane (c, h) writes its {best, second} keys of
+// 8 registers, then lane L re-reads row L>>2, columns 8*(L&3) .. +7 in ascending order
+// (strict '>' keeps the lowest column on ties) and the four partial results of a row are
+// folded with two quad-permute steps.  No workgroup barrier: the slice belongs to the wave
+// and its LDS operations execute in order.
+// SKIP_UNSEEN: a round whose 16 rows never saw a relevant similarity stores nothing (the caller has preset the
+// (0, 0, -1) defaults); the one-way API reports every row.
+template <int RT, bool SKIP_UNSEEN, typename Store>
+__device__ __forceinline__ void reduce_rows(const u32 (&rbest)[RT][16], const u32 (&rsec)[RT][16], uint2* rscratch,
+                                            int lane, int c, int h, int tile0, int n1, Store store) {
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      u32 seen = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) seen |= rbest[rt][8 * half + j];
+      if (SKIP_UNSEEN && !__any(seen != 0)) continue;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int r = 8 * half + j;
+        rscratch[(j + 8 * h) * 33 + c] = make_uint2(rbest[rt][r], rsec[rt][r]);
+      }
+      const int rl = lane >> 2, qd = lane & 3;       // row of the round, column quarter
+      u32 rb = 0, rs = 0, rc = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const uint2 en = rscratch[rl * 33 + qd * 8 + e];
+        const bool gt = en.x > rb;
+        rs = gt ? umax(rb, en.y) : umax(rs, en.x);
+        rc = gt ? (u32)(qd * 8 + e) : rc;
+        rb = umax(rb, en.x);
+      }
+      // fold quarters: the lower quarter absorbs the higher one (strict '>': lower column wins)
+#pragma unroll
+      for (int step = 0; step < 2; ++step) {
+        u32 pb, ps, pc;
+        if (step == 0) { pb = dpp_mov<0xB1>(rb); ps = dpp_mov<0xB1>(rs); pc = dpp_mov<0xB1>(rc); }   // quad_perm [1,0,3,2]
+        else           { pb = dpp_mov<0x4E>(rb); ps = dpp_mov<0x4E>(rs); pc = dpp_mov<0x4E>(rc); }   // quad_perm [2,3,0,1]
+        const bool gt = pb > rb;
+        rs = gt ? umax(rb, ps) : umax(rs, pb);
+        rc = gt ? pc : rc;
+        rb = umax(rb, pb);
+      }
+      // row of this lane's result inside the wave's RT*32 rows (see the MFMA C layout)
+      const int jj = rl & 7, hh = rl >> 3;
+      const int lrow = (jj & 3) + 16 * half + 8 * (jj >> 2) + 4 * hh;
+      if (qd == 0) {
+        const int row = (tile0 + rt) * kTile + lrow;
+        if (row < n1) {
+          const int sb = (int)(rb >> 6);
+          store(row, sb, sb > 0 ? (int)(rs >> 6) : 0, sb > 0 ? (63 - (int)(rb & 63)) * kTile + (int)rc : -1);
+        }
+      }
+    }
+  }
+}
+
+// Ordered compaction, one chunk of kThreads candidates: every thread with `ok` stores (i, j) behind those of the lower
+// threads, starting at out[2 * base]; returns the base of the next chunk.  Called by all kWaves waves of the workgroup
+// (two barriers); wave_count: kWaves ints of LDS.  `lane` and `wave` are the caller's own values: recomputed here from
+// threadIdx they change the register allocation of pair2_kernel<12> around its pair loop (measured slower on sparse input).
+__device__ __forceinline__ int append_ordered(bool ok, int i, int j, int base, int* wave_count, uint32_t* out, int lane,
+                                              int wave) {
+  const unsigned long long mask = __ballot(ok);
+  if (lane == 0) wave_count[wave] = __popcll(mask);
+  __syncthreads();
+  int before = base, chunk_total = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const int wc = wave_count[w];
+    before += w < wave ? wc : 0;
+    chunk_total += wc;
+  }
+  if (ok) {
+    const int pos = before + __popcll(mask & ((1ull << lane) - 1ull));
+    out[2 * pos] = (uint32_t)i;
+    out[2 * pos + 1] = (uint32_t)j;
+  }
+  __syncthreads();
+  return base + chunk_total;
+}
+
+// Angle + ratio tests, cross check, ordered compaction of one pair: returns the number of matches written to `out`.
+//   accept(best, second): AcceptTable or AcceptAcos;  column(j): column j's search result as a ColState, whichever way
+//   the kernel keeps it
+// The column pass leaves in m21[j] the row that column j accepts (or -1); row i matches its best column j if it accepts
+// it and, with the cross check, m21[j] == i.  Called by the whole workgroup behind a barrier that publishes the searches'
+// results; `tid` is the caller's (laundered) thread index, `lane` and `wave` its own too (see append_ordered).
+template <typename Accept, typename Column>
+__device__ __forceinline__ int finalise_pair(Accept accept, Column column, int* m21, const int* rbest_s, const int* rsecond_s,
+                                             const int* ridx_s, int n1, int n2, int cross_check, int tid, int lane, int wave,
+                                             int* wave_count, uint32_t* out) {
+  if (cross_check) {
+    for (int j = tid; j < n2; j += kThreads) {
+      const ColState cs = column(j);
+      const int row = (int)(0xFFFFFFFFu - (u32)cs.best);
+      m21[j] = accept((int)(cs.best >> 32), (int)cs.second) ? row : -1;
+    }
+    __syncthreads();
+  }
+  int base = 0;
+  for (int i0 = 0; i0 < n1; i0 += kThreads) {
+    const int i = i0 + tid;
+    bool ok = false;
+    int j = -1;
+    if (i < n1) {
+      j = ridx_s[i];
+      ok = accept(rbest_s[i], rsecond_s[i]);
+      if (ok && cross_check) ok = (m21[j] == i);
+    }
+    base = append_ordered(ok, i, j, base, wave_count, out, lane, wave);
+  }
+  return base;
+}
+
 // Launch arguments of guided matching (pair_kernel<..., GUIDED = true>); the unguided kernels carry none.
 template <bool GUIDED>
 struct GuidedArgs {};
@@ -712,9 +888,6 @@ struct GuidedArgs<true> {
   const int32_t* kind;      // [n_pairs]: VC_MODEL_FUNDAMENTAL, VC_MODEL_HOMOGRAPHY, anything else: the pair is skipped
   float t2;                 // max_error squared (float32 product)
 };
-// guided matching adds to the LDS plan: column keypoint y (x lives in m21, which the tile loop leaves alone) and the
-// row terms of every wave's RT * 32 rows
-__host__ __device__ inline size_t lds_guided_bytes(int n_pad, int rt) { return (size_t)n_pad * 4 + (size_t)kWaves * rt * kTile * 16; }
 
 // GUIDED (FUSED only): guided matching, the similarities pass the pair's geometric test first (epilogue_phase).
 template <int KS, int RT, bool FUSED, bool GUIDED = false>
@@ -729,23 +902,24 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int n_pad = n_tiles_img * kTile;
   uint8_t* ring = smem;
-  unsigned long long* colbest = (unsigned long long*)(smem + (size_t)ns * KS * kFragBytes);
-  u32* colsecond = (u32*)(colbest + n_pad);
-  int* cterm = (int*)(colsecond + n_pad);
-  int* m21 = cterm + n_pad;
-  int* rbest_s = m21 + n_pad;
-  int* rsecond_s = rbest_s + n_pad;
-  int* ridx_s = rsecond_s + n_pad;
-  int* crow6 = ridx_s + n_pad;              // [wave][RT*32]: row terms 128*ra - 49024*D
-  int* wave_count = crow6 + kWaves * 64 + kWaves * kRowScratchBytes / 4;
-  int* gcy = wave_count + 16;               // GUIDED: [n_pad] column keypoint y; x is kept in m21 until the finalisation
-  v4i* growg = (v4i*)(gcy + n_pad);         // GUIDED: [wave][RT*32] row terms of the geometric test
+  const PairLds lds = pair_lds((u32)ns * (KS * kFragBytes), n_pad, RT, GUIDED);
+  unsigned long long* colbest = (unsigned long long*)(smem + lds.colbest);
+  u32* colsecond = (u32*)(smem + lds.colsecond);
+  int* cterm = (int*)(smem + lds.cterm);
+  int* m21 = (int*)(smem + lds.m21);
+  int* rbest_s = (int*)(smem + lds.rbest);
+  int* rsecond_s = (int*)(smem + lds.rsecond);
+  int* ridx_s = (int*)(smem + lds.ridx);
+  int* crow6 = (int*)(smem + lds.crow6);
+  int* wave_count = (int*)(smem + lds.wave_count);
+  int* gcy = (int*)(smem + lds.gcy);
+  v4i* growg = (v4i*)(smem + lds.growg);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 31, h = lane >> 5;
-  uint2* rscratch = (uint2*)(crow6 + kWaves * 64) + wave * kRowScratchEntries;  // this wave's slice
+  uint2* rscratch = (uint2*)(smem + lds.rscratch) + wave * kRowScratchEntries;  // this wave's slice
 
   const int p = blockIdx.x;
   const int img_a = pairs[2 * p], img_b = pairs[2 * p + 1];
@@ -914,107 +1088,24 @@ __global__ __launch_bounds__(kThreads, 2) void pair_kernel(
 #undef VC_EPILOGUE
 
     // ---- row results of this pass ------------------------------------------------------
-    // Each row's candidates sit in 32 lanes (one per column residue c).  Transpose through a
-    // wave-private LDS slice, 16 rows per round: lane (c, h) writes its {best, second} keys of
-    // 8 registers, then lane L re-reads row L>>2, columns 8*(L&3) .. +7 in ascending order
-    // (strict '>' keeps the lowest column on ties) and the four partial results of a row are
-    // folded with two quad-permute steps.  No workgroup barrier: the slice belongs to the wave
-    // and its LDS operations execute in order.
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        // a round whose 16 rows never saw a relevant similarity keeps the (0, 0, -1) defaults
-        u32 seen = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) seen |= rbest[rt][8 * half + j];
-        if (FUSED && !__any(seen != 0)) continue;  // (the one-way API reports every row)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int r = 8 * half + j;
-          rscratch[(j + 8 * h) * 33 + c] = make_uint2(rbest[rt][r], rsec[rt][r]);
-        }
-        const int rl = lane >> 2, qd = lane & 3;       // row of the round, column quarter
-        u32 rb = 0, rs = 0, rc = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const uint2 en = rscratch[rl * 33 + qd * 8 + e];
-          const bool gt = en.x > rb;
-          rs = gt ? umax(rb, en.y) : umax(rs, en.x);
-          rc = gt ? (u32)(qd * 8 + e) : rc;
-          rb = umax(rb, en.x);
-        }
-        // fold quarters: the lower quarter absorbs the higher one (strict '>': lower column wins)
-#pragma unroll
-        for (int step = 0; step < 2; ++step) {
-          u32 pb, ps, pc;
-          if (step == 0) { pb = dpp_mov<0xB1>(rb); ps = dpp_mov<0xB1>(rs); pc = dpp_mov<0xB1>(rc); }   // quad_perm [1,0,3,2]
-          else           { pb = dpp_mov<0x4E>(rb); ps = dpp_mov<0x4E>(rs); pc = dpp_mov<0x4E>(rc); }   // quad_perm [2,3,0,1]
-          const bool gt = pb > rb;
-          rs = gt ? umax(rb, ps) : umax(rs, pb);
-          rc = gt ? pc : rc;
-          rb = umax(rb, pb);
-        }
-        // row of this lane's result inside the wave's RT*32 rows (see the MFMA C layout)
-        const int jj = rl & 7, hh = rl >> 3;
-        const int lrow = (jj & 3) + 16 * half + 8 * (jj >> 2) + 4 * hh;
-        if (qd == 0) {
-          const int row = (tile0 + rt) * kTile + lrow;
-          if (row < n1) {
-            const int sb = (int)(rb >> 6);
-            const int idx = sb > 0 ? (63 - (int)(rb & 63)) * kTile + (int)rc : -1;
-            const int s2v = sb > 0 ? (int)(rs >> 6) : 0;
-            if (FUSED) { rbest_s[row] = sb; rsecond_s[row] = s2v; ridx_s[row] = idx; }
-            else { o_idx[row] = idx; o_best[row] = sb; o_second[row] = s2v; }
-          }
-        }
-      }
-    }
+    reduce_rows<RT, FUSED>(rbest, rsec, rscratch, lane, c, h, tile0, n1, [&](int row, int best, int second, int idx) {
+      if (FUSED) { rbest_s[row] = best; rsecond_s[row] = second; ridx_s[row] = idx; }
+      else { o_idx[row] = idx; o_best[row] = best; o_second[row] = second; }
+    });
   }  // passes
 
   if (!FUSED) return;
   __syncthreads();
 
   // ---- angle + ratio tests, cross check, ordered compaction -----------------------------
-  if (cross_check) {
-    for (int j = tid; j < n2; j += kThreads) {
-      const unsigned long long kb = colbest[j];
-      const int sb = (int)(kb >> 32);
-      const int row = (int)(0xFFFFFFFFu - (u32)kb);
-      const bool ok = GUIDED ? accept_tab(sb, (int)colsecond[j], max_ratio, max_distance, s_low)
-                             : accept_dev(sb, (int)colsecond[j], max_ratio, max_distance);
-      m21[j] = ok ? row : -1;
-    }
-  }
-  __syncthreads();
-  uint32_t* out = out_matches + (size_t)p * n_max * 2;
-  int base = 0;
-  for (int i0 = 0; i0 < n1; i0 += kThreads) {
-    const int i = i0 + tid;
-    bool ok = false;
-    int j = -1;
-    if (i < n1) {
-      j = ridx_s[i];
-      ok = GUIDED ? accept_tab(rbest_s[i], rsecond_s[i], max_ratio, max_distance, s_low)
-                  : accept_dev(rbest_s[i], rsecond_s[i], max_ratio, max_distance);
-      if (ok && cross_check) ok = (m21[j] == i);
-    }
-    const unsigned long long mask = __ballot(ok);
-    if (lane == 0) wave_count[wave] = __popcll(mask);
-    __syncthreads();
-    int before = base;
-    for (int w = 0; w < wave; ++w) before += wave_count[w];
-    int chunk_total = 0;
-    for (int w = 0; w < kWaves; ++w) chunk_total += wave_count[w];
-    if (ok) {
-      const int pos = before + __popcll(mask & ((1ull << lane) - 1ull));
-      out[2 * pos] = (uint32_t)i;
-      out[2 * pos + 1] = (uint32_t)j;
-    }
-    base += chunk_total;
-    __syncthreads();
-  }
-  if (tid == 0) out_counts[p] = base;
+  auto finalise = [&](auto accept) {
+    return finalise_pair(accept, [&](int j) { return ColState{colbest[j], colsecond[j], 0u}; }, m21, rbest_s, rsecond_s, ridx_s,
+                         n1, n2, cross_check, tid, lane, wave, wave_count, out_matches + (size_t)p * n_max * 2);
+  };
+  int n_matches;
+  if constexpr (GUIDED) n_matches = finalise(AcceptTable{max_ratio, max_distance, s_low});
+  else n_matches = finalise(AcceptAcos{max_ratio, max_distance});
+  if (tid == 0) out_counts[p] = n_matches;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1042,30 +1133,75 @@ struct PairInfo {     // wave-uniform description of one pair with work (n_ct * 
   const uint8_t* b_frags;
 };
 
-// first pair at or after `p` that has tiles to process (scalar loads; runs once per pair, outside the tile loop)
-__device__ __forceinline__ PairInfo next_pair_with_work(int p, int hi, const int32_t* __restrict__ pairs,
-                                                        const int32_t* __restrict__ counts, int n_max,
-                                                        const uint8_t* __restrict__ prepared, size_t img_stride,
-                                                        int rows_per_pass = kWaves * 2 * kTile) {
-  PairInfo r;
-  r.a = 0; r.n1 = 0; r.n2 = 0; r.n_ct = 0; r.n_pass = 0; r.b_frags = prepared;
-  for (; p < hi; ++p) {
-    const int a = pairs[2 * p], b = pairs[2 * p + 1];
-    const int n1 = min(max(counts[a], 0), n_max), n2 = min(max(counts[b], 0), n_max);
-    if (n1 > 0 && n2 > 0) {
-      r.a = a; r.n1 = n1; r.n2 = n2;
-      r.n_ct = ceil_div(n2, kTile);
-      r.n_pass = ceil_div(n1, rows_per_pass);
-      r.b_frags = prepared + (size_t)b * img_stride;
-      break;
-    }
-  }
-  r.p = p;
-  return r;
-}
-
+constexpr int kPairWindow = 32;      // pairs-with-work described in LDS at a time (half a wave builds the list)
 constexpr int kProd2 = kWaves / 2;   // LDS-DMA pieces are issued by the early half (waves 0..3)
 constexpr int kTilesPerBarrier = 2;
+
+// pair2_kernel's dynamic LDS (see pair_lds): the ring, column records of 16 bytes, column terms, m21 + row results, three
+// row-term arrays per wave (full, head, full - head), row-reduce scratch, head column terms + tile bounds of b, the copy
+// of the NEXT pair's column sums / tile bounds (LDS-DMA), the pair window
+struct Pair2Lds {
+  u32 col;                       // [n_pad] ColState
+  u32 cterm;                     // [n_pad] (kept out of the 16-byte column records: a stride-16 read is 4-way bank conflicted, -3 %)
+  u32 m21, rbest, rsecond, ridx; // [n_pad] as in PairLds
+  u32 crow6;                     // [wave][64] row terms 128*ra - 49024*D
+  u32 rscratch;                  // [wave][kRowScratchEntries] uint2: reduce_rows
+  u32 pair_flag;                 // [1] some tile of the current pair was relevant (not next to cursor_chk: hipcc then resets
+                                 //     all three words with one 12-byte store of constants it keeps across the pair loop, and spills)
+  u32 wave_count;                // [kWaves] append_ordered
+  u32 cursor_chk;                // [2] max, min over the waves' ring cursors
+  // early-out state (head_steps_of(KS) < KS): head column terms, tail norm bounds of b's tiles, head row terms per wave
+  u32 cterm_h;                   // [n_pad]
+  u32 tnb;                       // [n_pad / 32]
+  u32 crow6h;                    // [wave][64] HEAD row terms 128*ra_head - 49024*D_head
+  // column sums (packed with the early-out) and tile bounds of the NEXT pair's image b, copied in by LDS-DMA while the
+  // current pair runs (no global load, hence no compiler vmcnt wait, at a pair boundary)
+  u32 auxw;                      // [n_pad]
+  u32 auxt;                      // [n_pad / 32]
+  u32 winfo;                     // [kPairWindow] int4 {p, a, b, n1 | n2 << 16}: pairs with work, in order
+  u32 wmeta;                     // [4] [0]: entries in the window
+  u32 crow6d;                    // [wave][64] full minus head row term (added when the early-out test fails)
+  u32 end;
+};
+__host__ __device__ constexpr Pair2Lds pair2_lds(u32 ring_bytes, int n_pad) {
+  LdsCursor c{ring_bytes};
+  Pair2Lds l{};
+  l.col = c.take(n_pad * 16, 16);
+  l.cterm = c.take(n_pad * 4);
+  l.m21 = c.take(n_pad * 4);
+  l.rbest = c.take(n_pad * 4);
+  l.rsecond = c.take(n_pad * 4);
+  l.ridx = c.take(n_pad * 4);
+  l.crow6 = c.take(kWaves * 64 * 4, 16);
+  l.rscratch = c.take(kWaves * kRowScratchBytes, 8);
+  l.pair_flag = c.take(4);
+  l.wave_count = c.take(kWaves * 4);
+  l.cursor_chk = c.take(2 * 4);
+  l.cterm_h = c.take(n_pad * 4);
+  l.tnb = c.take(n_pad / kTile * 4);
+  l.crow6h = c.take(kWaves * 64 * 4, 16);
+  l.auxw = c.take(n_pad * 4, 16);
+  l.auxt = c.take(n_pad / kTile * 4);
+  l.winfo = c.take(kPairWindow * 16, 16);
+  l.wmeta = c.take(4 * 4);
+  l.crow6d = c.take(kWaves * 64 * 4, 16);
+  l.end = c.take(0, 16);
+  return l;
+}
+constexpr int plan_slots2(int ks, int n_pad) { return slots_beside(pair2_lds(0, n_pad).end, ks, min_slots(2, true)); }
+constexpr bool pair2_lds_ok(int ks) {
+  const Pair2Lds l = pair2_lds(plan_slots2(ks, kMaxPad) * ks * kFragBytes, kMaxPad);
+  return l.end <= (u32)kLdsBytes && l.col % 16 == 0 && l.rscratch % 8 == 0 && l.crow6 % 16 == 0 && l.crow6h % 16 == 0 &&
+         l.crow6d % 16 == 0 && l.auxw % 16 == 0 && l.winfo % 16 == 0;
+}
+static_assert(pair2_lds_ok(2) && pair2_lds_ok(4) && pair2_lds_ok(8) && pair2_lds_ok(12),
+              "pair2_kernel's LDS plan: size and alignment at the largest block");
+// Which lengths ever need the fallback to pair_kernel<KS, 2, true> (vc_match_pairs_u8): only those whose plan does not
+// fit at the largest block.
+constexpr bool persistent_always_fits(int ks) { return ks <= kMaxKs2 && plan_slots2(ks, kMaxPad) > 0; }
+static_assert(persistent_always_fits(2) && persistent_always_fits(4) && persistent_always_fits(8), "no fallback below KS = 12");
+static_assert(!persistent_always_fits(12), "KS = 12 at 2048 rows leaves two ring slots: the fallback is live");
+
 template <int KS>
 __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
     const uint8_t* __restrict__ prepared, const int32_t* __restrict__ counts, int n_tiles_img, int d,
@@ -1076,25 +1212,23 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int n_pad = n_tiles_img * kTile;
   uint8_t* ring = smem;
-  ColState* col = (ColState*)(smem + (size_t)ns * KS * kFragBytes);
-  int* cterm = (int*)(col + n_pad);   // (kept out of the 16-byte column records: a stride-16 read is 4-way bank conflicted, -3 %)
-  int* m21 = cterm + n_pad;
-  int* rbest_s = m21 + n_pad;
-  int* rsecond_s = rbest_s + n_pad;
-  int* ridx_s = rsecond_s + n_pad;
-  int* crow6 = ridx_s + n_pad;              // [wave][RT*32]: row terms 128*ra - 49024*D (the HEAD part with the early-out)
-  int* wave_count = crow6 + kWaves * 64 + kWaves * kRowScratchBytes / 4;
-  // early-out state (head_steps_of(KS) < KS): head column terms, tail norm bounds of b's tiles, tail row terms per wave
-  int* cterm_h = wave_count + 16;
-  int* tnb = cterm_h + n_pad;
-  int* crow6h = tnb + n_pad / kTile;        // [wave][RT*32]: HEAD row terms 128*ra_head - 49024*D_head
-  // column sums (packed with the early-out) and tile bounds of the NEXT pair's image b, copied in by LDS-DMA while the
-  // current pair runs (no global load, hence no compiler vmcnt wait, at a pair boundary)
-  int* auxw = crow6h + kWaves * 64;         // [n_pad]
-  int* auxt = auxw + n_pad;                 // [n_tiles_img]
-  int4* winfo = (int4*)(auxt + n_tiles_img);       // [kPairWindow] {p, a, b, n1 | n2 << 16}: pairs with work, in order
-  int* wmeta = (int*)(winfo + kPairWindow);        // [0] entries in the window
-  int* crow6d = wmeta + 4;                         // [wave][RT*32]: full minus head row term (added when the early-out test fails)
+  const Pair2Lds lds = pair2_lds((u32)ns * (KS * kFragBytes), n_pad);
+  ColState* col = (ColState*)(smem + lds.col);
+  int* cterm = (int*)(smem + lds.cterm);
+  int* m21 = (int*)(smem + lds.m21);
+  int* rbest_s = (int*)(smem + lds.rbest);
+  int* rsecond_s = (int*)(smem + lds.rsecond);
+  int* ridx_s = (int*)(smem + lds.ridx);
+  int* crow6 = (int*)(smem + lds.crow6);
+  int* wave_count = (int*)(smem + lds.wave_count);
+  int* cterm_h = (int*)(smem + lds.cterm_h);
+  int* tnb = (int*)(smem + lds.tnb);
+  int* crow6h = (int*)(smem + lds.crow6h);
+  int* auxw = (int*)(smem + lds.auxw);
+  int* auxt = (int*)(smem + lds.auxt);
+  int4* winfo = (int4*)(smem + lds.winfo);
+  int* wmeta = (int*)(smem + lds.wmeta);
+  int* crow6d = (int*)(smem + lds.crow6d);
   constexpr int KH = head_steps_of(KS);
   constexpr bool kEarlyOut = KH < KS;
   const int d_head = min(d, KH * 32);
@@ -1103,7 +1237,7 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 31, h = lane >> 5;
-  uint2* rscratch = (uint2*)(crow6 + kWaves * 64) + wave * kRowScratchEntries;  // this wave's slice
+  uint2* rscratch = (uint2*)(smem + lds.rscratch) + wave * kRowScratchEntries;  // this wave's slice
   int* crow6_wave = crow6 + wave * 64;
   int* crow6h_wave = crow6h + wave * 64;
   int* crow6d_wave = crow6d + wave * 64;
@@ -1194,11 +1328,11 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
   };
   for (int i = 0; i < pf; ++i) produce();
 
-  int* pair_flag = wave_count + kWaves;   // "some tile of the current pair was relevant"
+  int* pair_flag = (int*)(smem + lds.pair_flag);   // "some tile of the current pair was relevant"
   // Cursor check: prod_seq / cons_seq exist once per wave (SGPRs) and must agree across the workgroup — `two`, the slot
   // indices and the counted waits are all derived from them.  Every wave folds its pair of cursors into a max and a min
   // word at the end of a pair's tile loop; if they differ the pair's count is written as -1 instead of a match count.
-  int* cursor_chk = pair_flag + 1;        // [2]: max, min over the waves
+  int* cursor_chk = (int*)(smem + lds.cursor_chk);   // [2]: max, min over the waves
   // with the early-out the per-row word is the packed (head << 16 | tail) sum, else the plain row sum
   const int rs_off = kEarlyOut ? n_pad : 0;
   // Image b's column sums for pair X travel by LDS-DMA into the aux buffer, issued by one LATE wave (which has no other
@@ -1362,53 +1496,10 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
       }
       if (late) pair_hit |= epilogue_phase2(acc, rbest, rsec, ct, col, n_ct - 1, c, h, row_base, s_low, cut);
 
-      // ---- row results of this pass (see pair_kernel) --------------------------------------------------------
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          u32 seen = 0;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) seen |= rbest[rt][8 * half + j];
-          if (!__any(seen != 0)) continue;   // the 16 rows keep the (0, 0, -1) defaults
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int r = 8 * half + j;
-            rscratch[(j + 8 * h) * 33 + c] = make_uint2(rbest[rt][r], rsec[rt][r]);
-          }
-          const int rl = lane >> 2, qd = lane & 3;       // row of the round, column quarter
-          u32 rb = 0, rs = 0, rc = 0;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const uint2 en = rscratch[rl * 33 + qd * 8 + e];
-            const bool gt = en.x > rb;
-            rs = gt ? umax(rb, en.y) : umax(rs, en.x);
-            rc = gt ? (u32)(qd * 8 + e) : rc;
-            rb = umax(rb, en.x);
-          }
-#pragma unroll
-          for (int step = 0; step < 2; ++step) {
-            u32 pb, ps, pc;
-            if (step == 0) { pb = dpp_mov<0xB1>(rb); ps = dpp_mov<0xB1>(rs); pc = dpp_mov<0xB1>(rc); }   // quad_perm [1,0,3,2]
-            else           { pb = dpp_mov<0x4E>(rb); ps = dpp_mov<0x4E>(rs); pc = dpp_mov<0x4E>(rc); }   // quad_perm [2,3,0,1]
-            const bool gt = pb > rb;
-            rs = gt ? umax(rb, ps) : umax(rs, pb);
-            rc = gt ? pc : rc;
-            rb = umax(rb, pb);
-          }
-          const int jj = rl & 7, hh = rl >> 3;
-          const int lrow = (jj & 3) + 16 * half + 8 * (jj >> 2) + 4 * hh;
-          if (qd == 0) {
-            const int row = (tile0 + rt) * kTile + lrow;
-            if (row < n1) {
-              const int sb = (int)(rb >> 6);
-              rbest_s[row] = sb;
-              rsecond_s[row] = sb > 0 ? (int)(rs >> 6) : 0;
-              ridx_s[row] = sb > 0 ? (63 - (int)(rb & 63)) * kTile + (int)rc : -1;
-            }
-          }
-        }
-      }
+      // ---- row results of this pass ----------------------------------------------------------------------------
+      reduce_rows<RT, true>(rbest, rsec, rscratch, lane, c, h, tile0, n1, [&](int row, int best, int second, int idx) {
+        rbest_s[row] = best; rsecond_s[row] = second; ridx_s[row] = idx;
+      });
     }  // passes
 
     int tidf = tid;   // (as tidp: the finalisation's addresses are computed here, not carried through the tile loop)
@@ -1429,6 +1520,8 @@ __global__ __launch_bounds__(kThreads, 2) void pair2_kernel(
       if (tidf == 0) out_counts[p] = cursors_agree ? 0 : VC_COUNT_SELFCHECK_FAILED;
     } else {
     // ---- angle + ratio tests, cross check, ordered compaction ---------------------------------------------------
+    // (finalise_pair's steps written out: through the shared function this kernel's 2048 x 256 sparse rate fell 0.5 % below
+    // what it is with its own copy, whichever way lane / wave reached append_ordered)
     if (cross_check) {
       for (int j = tidf; j < n2; j += kThreads) {
         const unsigned long long kb = col[j].best;
@@ -1494,11 +1587,11 @@ __global__ void mutual_ratio_kernel(const int32_t* idx12, const int32_t* best12,
                                     const int32_t* second21, int n2, float max_ratio,
                                     float max_distance, int cross_check, uint32_t* out_pairs,
                                     int32_t* out_count) {
-  // single workgroup: ordered compaction over i
-  __shared__ int wave_count[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  // single workgroup of kThreads: ordered compaction over i
+  __shared__ int wave_count[kWaves];
+  const int tid = threadIdx.x;
   int base = 0;
-  for (int i0 = 0; i0 < n1; i0 += blockDim.x) {
+  for (int i0 = 0; i0 < n1; i0 += kThreads) {
     const int i = i0 + tid;
     bool ok = false;
     int j = -1;
@@ -1508,18 +1601,7 @@ __global__ void mutual_ratio_kernel(const int32_t* idx12, const int32_t* best12,
       if (ok && cross_check)
         ok = idx21[j] == i && accept_dev(best21[j], second21[j], max_ratio, max_distance);
     }
-    const unsigned long long mask = __ballot(ok);
-    if (lane == 0) wave_count[wave] = __popcll(mask);
-    __syncthreads();
-    int before = base, tot = 0;
-    for (int w = 0; w < nw; ++w) { if (w < wave) before += wave_count[w]; tot += wave_count[w]; }
-    if (ok) {
-      const int pos = before + __popcll(mask & ((1ull << lane) - 1ull));
-      out_pairs[2 * pos] = (uint32_t)i;
-      out_pairs[2 * pos + 1] = (uint32_t)j;
-    }
-    base += tot;
-    __syncthreads();
+    base = append_ordered(ok, i, j, base, wave_count, out_pairs, tid & 63, tid >> 6);
   }
   if (tid == 0) *out_count = base;
 }
@@ -1531,23 +1613,12 @@ __global__ void knn_setup_kernel(int32_t* meta, int n1, int n2) {
 
 __global__ void theta_table_kernel(float* out, int n, int from_table) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < n) out[s] = from_table ? theta_tab(s) : theta_dev(s);
+  if (s < n) out[s] = from_table ? theta_tab(s) : theta(s);
 }
 
-// ---------------------------------------------------------------------------------------
-// launch helpers
-// ---------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------
 // relevance threshold (host side launch parameter)
 // ---------------------------------------------------------------------------------------
-// theta on the host, same definition as theta_dev (tests/test_matcher_gpu.py compares the
-// device table with the oracle's for every possible input).
-inline float theta_host(int s) {
-  float x = (float)s * (1.0f / (512.0f * 512.0f));
-  x = x > 1.0f ? 1.0f : x;
-  return (float)acos((double)x);
-}
-
 // Largest similarity that can be ignored by the searches without changing the match list.
 //   S_T   = smallest s with theta(s) <= max_distance: a best below it is always rejected.
 //   S_low = largest s (< S_T) with max_ratio * theta(s) > theta(S_T).
@@ -1564,27 +1635,24 @@ inline float theta_host(int s) {
 inline int relevance_threshold(float max_ratio, float max_distance) {
   if (!(max_ratio >= 0.0f) || !(max_distance == max_distance)) return -1;
   constexpr int kSat = 512 * 512;
-  if (theta_host(kSat) > max_distance) return kSat;  // nothing is ever accepted (max_distance < 0)
+  if (theta(kSat) > max_distance) return kSat;  // nothing is ever accepted (max_distance < 0)
   int lo = 0, hi = kSat;  // smallest s with theta(s) <= max_distance
   while (lo < hi) {
     const int mid = (lo + hi) / 2;
-    if (theta_host(mid) <= max_distance) hi = mid; else lo = mid + 1;
+    if (theta(mid) <= max_distance) hi = mid; else lo = mid + 1;
   }
   const int s_t = lo;
-  const float t_t = theta_host(s_t);
-  if (!(max_ratio * theta_host(0) > t_t)) return -1;
+  const float t_t = theta(s_t);
+  if (!(max_ratio * theta(0) > t_t)) return -1;
   lo = 0; hi = s_t > 0 ? s_t - 1 : 0;  // largest s with max_ratio*theta(s) > t_t
   while (lo < hi) {
     const int mid = (lo + hi + 1) / 2;
-    if (max_ratio * theta_host(mid) > t_t) lo = mid; else hi = mid - 1;
+    if (max_ratio * theta(mid) > t_t) lo = mid; else hi = mid - 1;
   }
   int s_low = lo < s_t - 1 ? lo : s_t - 1;
   s_low -= 4;
   return s_low < -1 ? -1 : s_low;
 }
-
-// K-step counts with a compiled kernel; a descriptor is zero-padded up to the next one.
-constexpr int kKsList[] = {2, 4, 8, 12, 16, 24, 32};
 
 inline int pick_ks(int d) {
   const int need = ksteps_of(d);
@@ -1593,78 +1661,73 @@ inline int pick_ks(int d) {
   return -1;
 }
 
-template <int KS, int RT, bool FUSED>
-int launch_pair(const void* prepared, const int32_t* counts, int n_tiles, int d, const int32_t* pairs,
-                int n_pairs, float max_ratio, float max_distance, int cross_check, int n_max,
-                uint32_t* out_matches, int32_t* out_counts, int32_t* o_idx, int32_t* o_best,
-                int32_t* o_second, hipStream_t stream) {
-  // the one-way API reports every row's best / second, so nothing may be skipped there
-  const int s_low = FUSED ? relevance_threshold(max_ratio, max_distance) : -1;
-  const int n_pad = n_tiles * kTile;
-  const int ns = plan_slots(KS, n_pad);
-  if (ns == 0 || (RT == 2 && ns < 3)) return VC_ERR_UNSUPPORTED;
-  const size_t smem = (size_t)ns * KS * kFragBytes + lds_fixed_bytes(n_pad);
-  static vc::PerDeviceOnce configured;  // per instantiation and device
-  if (int st = vc::allow_dynamic_lds(configured, kLdsBytes, pair_kernel<KS, RT, FUSED>)) return st;
-  hipLaunchKernelGGL((pair_kernel<KS, RT, FUSED>), dim3(n_pairs), dim3(kThreads), smem, stream,
-                     (const uint8_t*)prepared, counts, n_tiles, d, pairs, max_ratio, max_distance,
-                     cross_check, n_max, ns, s_low, out_matches, out_counts, o_idx, o_best, o_second, GuidedArgs<false>());
-  return vc::check_launch();
+void launch_prepare(const uint8_t* desc, const int32_t* counts, int n_images, int n_max, int d, int n_tiles, void* prepared,
+                    hipStream_t stream) {
+  hipLaunchKernelGGL(prepare_kernel, dim3(n_tiles, n_images), dim3(256), 0, stream, desc, counts, n_max, d, n_tiles,
+                     pick_ks(d), (uint8_t*)prepared);
 }
 
-template <int KS, int RT>
-int launch_pair_guided(const void* prepared, const int32_t* counts, int n_tiles, int d, const int32_t* pairs, int n_pairs,
-                       const GuidedArgs<true>& ga, float max_ratio, float max_distance, int cross_check, int n_max,
-                       uint32_t* out_matches, int32_t* out_counts, hipStream_t stream) {
-  // the relevance shortcut holds for the masked similarities as it does for the plain ones: the rule is the same
-  const int s_low = relevance_threshold(max_ratio, max_distance);
-  const int n_pad = n_tiles * kTile;
-  const size_t fixed = lds_fixed_bytes(n_pad) + lds_guided_bytes(n_pad, RT);
-  long ns = ((long)kLdsBytes - (long)fixed) / ((long)KS * kFragBytes);
-  if (ns > kMaxSlots) ns = kMaxSlots;
-  if (ns < (RT == 2 ? 3 : 2)) return VC_ERR_UNSUPPORTED;
-  const size_t smem = (size_t)ns * KS * kFragBytes + fixed;
-  static vc::PerDeviceOnce configured;  // per instantiation and device
-  if (int st = vc::allow_dynamic_lds(configured, kLdsBytes, pair_kernel<KS, RT, true, true>)) return st;
-  hipLaunchKernelGGL((pair_kernel<KS, RT, true, true>), dim3(n_pairs), dim3(kThreads), smem, stream, (const uint8_t*)prepared,
-                     counts, n_tiles, d, pairs, max_ratio, max_distance, cross_check, n_max, (int)ns, s_low, out_matches,
-                     out_counts, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, ga);
+// what every pair launch is given
+struct MatchJob {
+  const void* prepared;
+  const int32_t* counts;
+  int n_tiles, d;
+  const int32_t* pairs;
+  int n_pairs;
+  float max_ratio, max_distance;
+  int cross_check, n_max;
+  uint32_t* out_matches;
+  int32_t* out_counts;
+  hipStream_t stream;
+};
+
+// the pair kernels may use the whole LDS: set once per kernel and device
+template <auto Kernel>
+int allow_full_lds() {
+  static vc::PerDeviceOnce configured;
+  return vc::allow_dynamic_lds(configured, kLdsBytes, Kernel);
+}
+
+// pair_kernel: one workgroup per pair.  !FUSED: the one-way outputs instead of the match list; GUIDED: see GuidedArgs.
+template <int KS, int RT, bool FUSED, bool GUIDED = false>
+int launch_pair(const MatchJob& m, int32_t* o_idx, int32_t* o_best, int32_t* o_second,
+                const GuidedArgs<GUIDED>& ga = GuidedArgs<GUIDED>()) {
+  // The one-way API reports every row's best / second, so nothing may be skipped there.  The relevance shortcut holds for
+  // the masked similarities of guided matching as it does for the plain ones: the rule is the same.
+  const int s_low = FUSED ? relevance_threshold(m.max_ratio, m.max_distance) : -1;
+  const int n_pad = m.n_tiles * kTile;
+  const int ns = plan_slots(KS, n_pad, RT, GUIDED);
+  if (ns == 0) return VC_ERR_UNSUPPORTED;
+  if (int st = allow_full_lds<pair_kernel<KS, RT, FUSED, GUIDED>>()) return st;
+  hipLaunchKernelGGL((pair_kernel<KS, RT, FUSED, GUIDED>), dim3(m.n_pairs), dim3(kThreads),
+                     pair_lds(ns * KS * kFragBytes, n_pad, RT, GUIDED).end, m.stream, (const uint8_t*)m.prepared, m.counts,
+                     m.n_tiles, m.d, m.pairs, m.max_ratio, m.max_distance, m.cross_check, m.n_max, ns, s_low, m.out_matches,
+                     m.out_counts, o_idx, o_best, o_second, ga);
   return vc::check_launch();
 }
 
 // The persistent kernel: one workgroup per CU, each walking a contiguous range of the pair list.
 template <int KS>
-int launch_pair2(const void* prepared, const int32_t* counts, int n_tiles, int d, const int32_t* pairs,
-                 int n_pairs, float max_ratio, float max_distance, int cross_check, int n_max,
-                 uint32_t* out_matches, int32_t* out_counts, hipStream_t stream) {
-  const int s_low = relevance_threshold(max_ratio, max_distance);
-  const int n_pad = n_tiles * kTile;
+int launch_pair2(const MatchJob& m) {
+  const int s_low = relevance_threshold(m.max_ratio, m.max_distance);
+  const int n_pad = m.n_tiles * kTile;
   const int ns = plan_slots2(KS, n_pad);
-  if (ns < 3) return VC_ERR_UNSUPPORTED;
-  const size_t smem = (size_t)ns * KS * kFragBytes + lds_fixed_bytes2(n_pad);
-  static vc::PerDeviceOnce configured;
-  if (int st = vc::allow_dynamic_lds(configured, kLdsBytes, pair2_kernel<KS>)) return st;
+  if (ns == 0) return VC_ERR_UNSUPPORTED;
+  if (int st = allow_full_lds<pair2_kernel<KS>>()) return st;
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
-  const int grid = n_pairs < cus ? n_pairs : cus;
-  hipLaunchKernelGGL((pair2_kernel<KS>), dim3(grid), dim3(kThreads), smem, stream, (const uint8_t*)prepared, counts,
-                     n_tiles, d, pairs, n_pairs, max_ratio, max_distance, cross_check, n_max, ns, s_low, out_matches,
-                     out_counts);
+  const int grid = m.n_pairs < cus ? m.n_pairs : cus;
+  hipLaunchKernelGGL((pair2_kernel<KS>), dim3(grid), dim3(kThreads), pair2_lds(ns * KS * kFragBytes, n_pad).end, m.stream,
+                     (const uint8_t*)m.prepared, m.counts, m.n_tiles, m.d, m.pairs, m.n_pairs, m.max_ratio, m.max_distance,
+                     m.cross_check, m.n_max, ns, s_low, m.out_matches, m.out_counts);
   return vc::check_launch();
 }
 
-// RT = 2 (512 rows per pass) while its register budget holds (A fragments: 2*KS*4 VGPRs);
-// long descriptors fall back to one row tile per wave.
-template <bool FUSED>
-int dispatch_pair(int ks, const void* prepared, const int32_t* counts, int n_tiles, int d,
-                  const int32_t* pairs, int n_pairs, float max_ratio, float max_distance,
-                  int cross_check, int n_max, uint32_t* out_matches, int32_t* out_counts,
-                  int32_t* o_idx, int32_t* o_best, int32_t* o_second, hipStream_t stream) {
-  return vc::dispatch<2, 4, 8, 12, 16, 24, 32>(ks, [&](auto k) {
-    return launch_pair<k, (k <= 12 ? 2 : 1), FUSED>(prepared, counts, n_tiles, d, pairs, n_pairs, max_ratio, max_distance,
-                                                     cross_check, n_max, out_matches, out_counts, o_idx, o_best, o_second,
-                                                     stream);
-  });
+int launch_theta(float* out, int n, int from_table, vc_stream_t stream) {
+  if (!out || n < 0) return VC_ERR_INVALID_ARG;
+  if (n == 0) return VC_OK;
+  hipLaunchKernelGGL(theta_table_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, n, from_table);
+  return vc::check_launch();
 }
 
 }  // namespace
@@ -1687,10 +1750,7 @@ int vc_prepare_descriptors(const uint8_t* desc, const int32_t* counts, int n_ima
   if (n_max > VC_MAX_KEYPOINTS || d > VC_MAX_DESC_DIM) return VC_ERR_UNSUPPORTED;
   if (((uintptr_t)prepared) % 16 != 0) return VC_ERR_INVALID_ARG;
   if (n_images == 0) return VC_OK;
-  const int ks = pick_ks(d);
-  const int n_tiles = tiles_of(n_max);
-  hipLaunchKernelGGL(prepare_kernel, dim3(n_tiles, n_images), dim3(256), 0, (hipStream_t)stream, desc,
-                     counts, n_max, d, n_tiles, ks, (uint8_t*)prepared);
+  launch_prepare(desc, counts, n_images, n_max, d, tiles_of(n_max), prepared, (hipStream_t)stream);
   return vc::check_launch();
 }
 
@@ -1701,15 +1761,20 @@ int vc_match_pairs_u8(const void* prepared, const int32_t* counts, int n_images,
   if (n_images <= 0 || n_max <= 0 || d <= 0 || n_pairs < 0) return VC_ERR_INVALID_ARG;
   if (n_max > VC_MAX_KEYPOINTS || d > VC_MAX_DESC_DIM) return VC_ERR_UNSUPPORTED;
   if (n_pairs == 0) return VC_OK;
-  // descriptors up to 384 bytes: the persistent kernel (two row tiles per wave)
-  const int st2 = vc::dispatch<2, 4, 8, 12>(pick_ks(d), [&](auto k) {
-    return launch_pair2<k>(prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio, max_distance, cross_check,
-                           n_max, out_matches, out_counts, (hipStream_t)stream);
+  const MatchJob job = {prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio, max_distance, cross_check, n_max,
+                        out_matches, out_counts, (hipStream_t)stream};
+  return vc::dispatch<VC_KS_LIST>(pick_ks(d), [&](auto k) {
+    // descriptors up to 384 bytes: the persistent kernel (two row tiles per wave)
+    if constexpr (persistent_always_fits(k)) {
+      return launch_pair2<k>(job);
+    } else {
+      if constexpr (k <= kMaxKs2) {   // (blocks too large for its LDS plan: the kernel with one workgroup per pair)
+        const int st2 = launch_pair2<k>(job);
+        if (st2 != VC_ERR_UNSUPPORTED) return st2;
+      }
+      return launch_pair<k, row_tiles_of(k), true>(job, nullptr, nullptr, nullptr);
+    }
   });
-  if (st2 != VC_ERR_UNSUPPORTED) return st2;   // (blocks too large for its LDS plan: the kernel with one workgroup per pair)
-  return dispatch_pair<true>(pick_ks(d), prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio,
-                             max_distance, cross_check, n_max, out_matches, out_counts, nullptr,
-                             nullptr, nullptr, (hipStream_t)stream);
 }
 
 int vc_match_pairs_guided_u8(const void* prepared, const int32_t* counts, int n_images, int n_max, int d,
@@ -1727,10 +1792,11 @@ int vc_match_pairs_guided_u8(const void* prepared, const int32_t* counts, int n_
   ga.models = models;
   ga.kind = model_kind;
   ga.t2 = max_error * max_error;
-  return vc::dispatch<2, 4, 8, 12, 16, 24, 32>(pick_ks(d), [&](auto k) {
+  const MatchJob job = {prepared, counts, tiles_of(n_max), d, pairs, n_pairs, max_ratio, max_distance, cross_check, n_max,
+                        out_matches, out_counts, (hipStream_t)stream};
+  return vc::dispatch<VC_KS_LIST>(pick_ks(d), [&](auto k) {
     // one row tile per wave for every length: the geometric test needs the registers a second one would take
-    return launch_pair_guided<k, 1>(prepared, counts, tiles_of(n_max), d, pairs, n_pairs, ga, max_ratio, max_distance,
-                                    cross_check, n_max, out_matches, out_counts, (hipStream_t)stream);
+    return launch_pair<k, 1, true, true>(job, nullptr, nullptr, nullptr, ga);
   });
 }
 
@@ -1760,14 +1826,14 @@ int vc_knn_top2_u8(const uint8_t* d1, int n1, const uint8_t* d2, int n2, int d, 
   int32_t* meta = (int32_t*)(ws + 2 * img);
   hipLaunchKernelGGL(knn_setup_kernel, dim3(1), dim3(1), 0, s, meta, n1, n2);
   // each set is prepared as image 0 of its own 1-image block, with its own row count
-  hipLaunchKernelGGL(prepare_kernel, dim3(n_tiles, 1), dim3(256), 0, s, d1, meta + 0, n1, d, n_tiles, ks, ws);
-  if (n2 > 0)
-    hipLaunchKernelGGL(prepare_kernel, dim3(n_tiles, 1), dim3(256), 0, s, d2, meta + 1, n2, d, n_tiles, ks,
-                       ws + img);
+  launch_prepare(d1, meta + 0, 1, n1, d, n_tiles, ws, s);
+  if (n2 > 0) launch_prepare(d2, meta + 1, 1, n2, d, n_tiles, ws + img, s);
   int st = vc::check_launch();
   if (st != VC_OK) return st;
-  return dispatch_pair<false>(ks, ws, meta, n_tiles, d, meta + 2, 1, 0.f, 0.f, 0, n_max, nullptr, nullptr,
-                              out_idx, out_best, out_second, s);
+  const MatchJob job = {ws, meta, n_tiles, d, meta + 2, 1, 0.f, 0.f, 0, n_max, nullptr, nullptr, s};
+  return vc::dispatch<VC_KS_LIST>(ks, [&](auto k) {
+    return launch_pair<k, row_tiles_of(k), false>(job, out_idx, out_best, out_second);
+  });
 }
 
 int vc_mutual_ratio(const int32_t* idx12, const int32_t* best12, const int32_t* second12, int n1,
@@ -1777,24 +1843,14 @@ int vc_mutual_ratio(const int32_t* idx12, const int32_t* best12, const int32_t* 
   if (n1 < 0 || n2 < 0 || !out_count) return VC_ERR_INVALID_ARG;
   if (n1 > 0 && (!idx12 || !best12 || !second12 || !out_pairs)) return VC_ERR_INVALID_ARG;
   if (cross_check && n1 > 0 && n2 > 0 && (!idx21 || !best21 || !second21)) return VC_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(mutual_ratio_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, idx12, best12,
+  // (one workgroup of exactly kThreads: append_ordered counts kWaves waves)
+  hipLaunchKernelGGL(mutual_ratio_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, idx12, best12,
                      second12, n1, idx21, best21, second21, n2, max_ratio, max_distance, cross_check,
                      out_pairs, out_count);
   return vc::check_launch();
 }
 
-int vc_theta_table(float* out, int n, vc_stream_t stream) {
-  if (!out || n < 0) return VC_ERR_INVALID_ARG;
-  if (n == 0) return VC_OK;
-  hipLaunchKernelGGL(theta_table_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, n, 1);
-  return vc::check_launch();
-}
-
-int vc_theta_eval(float* out, int n, vc_stream_t stream) {
-  if (!out || n < 0) return VC_ERR_INVALID_ARG;
-  if (n == 0) return VC_OK;
-  hipLaunchKernelGGL(theta_table_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, out, n, 0);
-  return vc::check_launch();
-}
+int vc_theta_table(float* out, int n, vc_stream_t stream) { return launch_theta(out, n, 1, stream); }
+int vc_theta_eval(float* out, int n, vc_stream_t stream) { return launch_theta(out, n, 0, stream); }
 
 }  // extern "C"
