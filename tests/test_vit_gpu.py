@@ -141,7 +141,8 @@ def test_linear_rejects_unsupported_shapes():
 @pytest.mark.parametrize("ln", [False, True])
 def test_xs_linear_matches_float32_reference(rows, N, epi, ln):
     """K=384 GEMM (+ fused LayerNorm / epilogue) through the C ABI vs float32 on the same bf16 data: the x-stationary kernel
-    and, for the long launches without LayerNorm (the last three shapes), the weight-stationary one behind the same entry."""
+    at every epilogue with and without LayerNorm, from one row to the long launches of a 50-image batch (the last three
+    shapes: every workgroup walks many row tiles)."""
     from vit_colmap_amd.vit.hip_ops import XsLinear
 
     K = 384
@@ -331,6 +332,58 @@ def test_xs_gelu_table_is_the_bf16_gelu_for_every_input():
         assert bool((err <= ref32.abs() * 2 ** -8 + 2e-7 * (1 + x.float().abs())).all()), float(err.max())
 
 
+def _xs_table_gelu_case(rows, N, ln):
+    """An fc1-type XsLinear with inputs, and the float32 evaluation with GELU taken on the bf16-rounded pre-activation
+    (what the table defines; see test_fused_mlp_matches_float32_reference)."""
+    from vit_colmap_amd.vit.hip_ops import XsLinear
+
+    K = 384
+    g = torch.Generator(device="cuda").manual_seed(rows + N + 7 * ln)
+    x = (torch.randn(rows, K, device="cuda", generator=g) * 1.5 + 0.3).to(torch.bfloat16)
+    w = torch.randn(N, K, device="cuda", generator=g) / K ** 0.5 * torch.linspace(0.5, 2.0, N, device="cuda")[:, None]
+    b = torch.randn(N, device="cuda", generator=g)
+    gam = 1 + 0.2 * torch.randn(K, device="cuda", generator=g) if ln else None
+    bet = 0.1 * torch.randn(K, device="cuda", generator=g) if ln else None
+    xin = x.float()
+    if ln:
+        xin = torch.nn.functional.layer_norm(xin, (K,), gam, bet, 1e-6)
+    ref = torch.nn.functional.gelu((xin @ w.t() + b).to(torch.bfloat16).float())
+    return XsLinear(w, b, gam, bet, 1e-6), x, ref
+
+
+def _assert_xs_close(out, ref):
+    # the three assertions of test_xs_linear_matches_float32_reference
+    err = (out - ref).abs()
+    tol = ref.abs() * 2 ** -7 + 6e-2
+    assert bool((err <= tol).all()), (float(err.max()), int((err > tol).sum()))
+    assert float((err > ref.abs() * 2 ** -7 + 3e-2).float().mean()) < 1e-5
+    assert float((out - ref).norm() / ref.norm()) < 6e-3
+
+
+@pytest.mark.parametrize("rows,N", [(1, 32), (257, 96), (300, 1536)])
+def test_xs_table_gelu_with_layernorm_matches_float32_reference(rows, N):
+    """The fc1 form of the x-stationary kernel as the unfused ViT-S path runs it: LayerNorm fused into the x load AND the
+    GELU taken from the table."""
+    from vit_colmap_amd.vit.hip_ops import EPI_GELU, gelu_table
+
+    lin, x, ref = _xs_table_gelu_case(rows, N, True)
+    _assert_xs_close(lin(x, EPI_GELU, gelu_table=gelu_table("cuda")).float(), ref)
+
+
+def test_xs_table_gelu_is_used_exactly_while_bias_and_table_fit():
+    """The table shares a 16 KiB LDS area with the float32 bias.  N = 1920: 7680 + 8704 = 16384 bytes, the last width at
+    which it fits, and it is used; N = 1952: it does not fit, and passing one changes nothing."""
+    from vit_colmap_amd.vit.hip_ops import EPI_GELU, gelu_table
+
+    tab = gelu_table("cuda")
+    lin, x, ref = _xs_table_gelu_case(33, 1920, False)
+    out = lin(x, EPI_GELU, gelu_table=tab)
+    _assert_xs_close(out.float(), ref)
+    assert not torch.equal(out.view(torch.int16), lin(x, EPI_GELU).view(torch.int16))   # (the float path rounds elsewhere)
+    lin, x, _ = _xs_table_gelu_case(33, 1952, False)
+    assert torch.equal(lin(x, EPI_GELU, gelu_table=tab).view(torch.int16), lin(x, EPI_GELU).view(torch.int16))
+
+
 @pytest.mark.parametrize("B,N,H", [(2, 1531, 6), (1, 64, 1), (3, 257, 12), (1, 100, 2), (1, 1, 6)] + ATTN_PRODUCT_SHAPES)
 @pytest.mark.parametrize("spread", [1.0, 6.0])
 def test_attention_prescaled_q_lazy_max(B, N, H, spread):
@@ -356,9 +409,21 @@ def test_attention_prescaled_q_lazy_max(B, N, H, spread):
 def test_fused_mlp_matches_float32_reference(rows):
     """x += fc2(gelu(fc1(LN(x)))) in one kernel vs the float32 evaluation (GELU on the bf16-rounded pre-activation, as the
     bf16 pipeline and the kernel's table define it)."""
+    _check_fused_mlp(rows, 1536)
+
+
+@pytest.mark.parametrize("rows", [1, 129, 300])
+@pytest.mark.parametrize("n_hidden", [64, 768])
+def test_fused_mlp_off_the_default_width(rows, n_hidden):
+    """The same at hidden widths other than ViT-S's 1536 (the ABI accepts every multiple of 32 up to it): two chunks per
+    row tile, the shortest stream that fills the two-stage pipeline, and 24."""
+    _check_fused_mlp(rows, n_hidden)
+
+
+def _check_fused_mlp(rows, Hd):
     from vit_colmap_amd.vit.hip_ops import FusedMlp
 
-    K, Hd = 384, 1536
+    K = 384
     g = torch.Generator(device="cuda").manual_seed(rows)
     x = (torch.randn(rows, K, device="cuda", generator=g) * 1.5 + 0.3).to(torch.bfloat16)
     w1 = torch.randn(Hd, K, device="cuda", generator=g) / K ** 0.5 * torch.linspace(0.5, 2.0, Hd, device="cuda")[:, None]

@@ -1,4 +1,4 @@
-// Shared device-side idioms of the kernels: the int8 MFMA register types, LDS-DMA issue, the wave-uniform LDS base and bf16 bit conversions.
+// Shared device-side idioms of the kernels: the int8 MFMA register types, LDS-DMA issue, the wave-uniform LDS base, the cursor of the constexpr LDS plans and bf16 bit conversions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,6 +67,18 @@ __device__ __forceinline__ uint32_t lds_offset(const void* p) {
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_offset(p));
 }
+
+// For a kernel's constexpr LDS plan (one function that kernel and host both evaluate): hands out consecutive regions,
+// each at its alignment; offsets are in bytes from the start of LDS and `at` ends as the size.
+struct LdsCursor {
+  uint32_t at;
+  __host__ __device__ constexpr uint32_t take(uint32_t bytes, uint32_t align = 4) {
+    at = (at + align - 1) / align * align;
+    const uint32_t off = at;
+    at += bytes;
+    return off;
+  }
+};
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
 

@@ -1,12 +1,23 @@
-// bf16 linear layer with fused epilogue for the DINOv2 blocks (the model behind reference
+// bf16 linear layers with fused epilogues for the DINOv2 blocks (the model behind reference
 // vit_colmap/features/vit_extractor.py:135-146):  out = epi(x W^T + b)  with
 //   epi = identity (qkv), exact-erf GELU (fc1), "+ residual" (attn.proj / fc2 — the residual
 //   stream update), or the SwiGLU gate of ViT-g (w12: silu(gate half) * value half, out half as wide),
 //   so the activation and the residual add never make their own pass over HBM.
+// x [M][K] bf16 (token rows), W [N][K] bf16 (torch Linear layout: one output feature per row), out [M][N] bf16.
 //
-// x [M][K] bf16 (token rows), W [N][K] bf16 (torch Linear layout: one output feature per row),
-// out [M][N] bf16.  M is arbitrary (76 550 at 50 images x 1531 tokens), N % 128 == 0, K % 64 == 0.
+// Four kernel families, in this order (each has its own comment):
+//   1. gemm_kernel<EPI>           128 x 128 staged tile, any K % 64 == 0, N % 128 == 0 (vc_linear_bf16, vc_patch_embed_bf16);
+//   2. gemm256_kernel<EPI, CONV>  256 x 256 persistent tile for the wide layers of ViT-B / L / g, also as an implicit-GEMM
+//                                 convolution (vc_linear_bf16, vc_conv_taps_bf16);
+//   -- shared section of the two K = 384 kernels: x-row load + LayerNorm, table GELU, the steps by which a 32 x 32 block
+//      leaves through the wave's transposer, bias as initial value, the 24-MFMA stage loop, the fc1 weight fold --
+//   3. xs_kernel<EPI, LN, GT>     x-stationary GEMM for K = 384: qkv, proj, fc1 of ViT-S (vc_linear_xs_bf16) + its prepare kernel;
+//   4. mlp2_kernel                the whole MLP of a 384-wide block in one kernel (vc_mlp_bf16) + its prepare kernel.
+// 3 and 4 take their LDS layout from one constexpr plan each (xs_lds, mlp_lds), which the host entry points read too.
+// Vector types, bf16 pair conversions, the GELU forms, the XCD-aware tile order and the swizzled fragment offset of the two
+// staged kernels come first; the host helpers and the C entry points are at the end.
 //
+// 1. gemm_kernel.  M is arbitrary (76 550 at 50 images x 1531 tokens), N % 128 == 0, K % 64 == 0.
 // One workgroup = 4 waves = one 128 (tokens) x 128 (features) output tile; two workgroups per CU
 // (64 KiB of LDS, <= 128 VGPRs each) so that one tile's epilogue VALU work runs under the other's
 // MFMAs.  Per 64-deep K step both operand tiles (128 rows x 128 B) go global -> LDS by LDS-DMA
@@ -27,7 +38,19 @@ namespace {
 
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
+typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+
+// Two floats -> one register of two bf16 (round to nearest even, lo in the low half) and back.
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+  const v2bf p = {(__bf16)lo, (__bf16)hi};
+  return *(const uint32_t*)&p;
+}
+__device__ __forceinline__ v2f unpack_bf16x2(uint32_t u) { return (v2f){__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; }
 
 constexpr int BM = 128;              // token rows per tile
 constexpr int BN = 128;              // output features per tile
@@ -58,22 +81,21 @@ __device__ __forceinline__ float gelu_erf(float x) {
 // The same on a pair of values with 2-wide packed float32 operations (v_pk_fma_f32 / v_pk_mul_f32):
 // beside a partner wave that owns the matrix pipe, a lone wave's VALU stream is issue-bound, and a packed
 // instruction does twice the work per issue slot.  Only rcp / exp2 / abs / max stay one value at a time.
-typedef float v2f_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2f_t gelu_erf2(v2f_t x) {
-  const v2f_t ax = {__builtin_fabsf(x[0]), __builtin_fabsf(x[1])};
-  const v2f_t one = {1.0f, 1.0f};
-  const v2f_t den = __builtin_elementwise_fma(ax, (v2f_t){0.3275911f * 0.70710678118654752f, 0.3275911f * 0.70710678118654752f}, one);
-  const v2f_t t = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  v2f_t p = __builtin_elementwise_fma(t, (v2f_t){1.061405429f, 1.061405429f}, (v2f_t){-1.453152027f, -1.453152027f});
-  p = __builtin_elementwise_fma(p, t, (v2f_t){1.421413741f, 1.421413741f});
-  p = __builtin_elementwise_fma(p, t, (v2f_t){-0.284496736f, -0.284496736f});
-  p = __builtin_elementwise_fma(p, t, (v2f_t){0.254829592f, 0.254829592f});
-  const v2f_t zl = x * (v2f_t){0.84932180028801907f, 0.84932180028801907f};
-  const v2f_t z2 = zl * zl;
-  const v2f_t e = {__builtin_amdgcn_exp2f(-z2[0]), __builtin_amdgcn_exp2f(-z2[1])};
-  const v2f_t q = p * t * e;
-  const v2f_t pos = {__builtin_fmaxf(x[0], 0.0f), __builtin_fmaxf(x[1], 0.0f)};
-  return __builtin_elementwise_fma(ax * (v2f_t){-0.5f, -0.5f}, q, pos);
+__device__ __forceinline__ v2f gelu_erf2(v2f x) {
+  const v2f ax = {__builtin_fabsf(x[0]), __builtin_fabsf(x[1])};
+  const v2f one = {1.0f, 1.0f};
+  const v2f den = __builtin_elementwise_fma(ax, (v2f){0.3275911f * 0.70710678118654752f, 0.3275911f * 0.70710678118654752f}, one);
+  const v2f t = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
+  v2f p = __builtin_elementwise_fma(t, (v2f){1.061405429f, 1.061405429f}, (v2f){-1.453152027f, -1.453152027f});
+  p = __builtin_elementwise_fma(p, t, (v2f){1.421413741f, 1.421413741f});
+  p = __builtin_elementwise_fma(p, t, (v2f){-0.284496736f, -0.284496736f});
+  p = __builtin_elementwise_fma(p, t, (v2f){0.254829592f, 0.254829592f});
+  const v2f zl = x * (v2f){0.84932180028801907f, 0.84932180028801907f};
+  const v2f z2 = zl * zl;
+  const v2f e = {__builtin_amdgcn_exp2f(-z2[0]), __builtin_amdgcn_exp2f(-z2[1])};
+  const v2f q = p * t * e;
+  const v2f pos = {__builtin_fmaxf(x[0], 0.0f), __builtin_fmaxf(x[1], 0.0f)};
+  return __builtin_elementwise_fma(ax * (v2f){-0.5f, -0.5f}, q, pos);
 }
 
 // EPI_SWIGLU: silu(a) b = a b / (1 + exp(-a)) on the two float32 pre-activations.  exp(-a) overflows to +inf below
@@ -81,6 +103,22 @@ __device__ __forceinline__ v2f_t gelu_erf2(v2f_t x) {
 __device__ __forceinline__ float swiglu_f32(float a, float b) {
   const float e = __builtin_amdgcn_exp2f(a * -1.4426950408889634f);
   return a * __builtin_amdgcn_rcpf(1.0f + e) * b;
+}
+
+// XCD-aware tile order of the two staged kernels: the 8 XCDs take workgroups round-robin, so give each XCD a contiguous
+// run of tiles (feature tiles fastest: the tiles an XCD works on at one time share x rows in its L2).
+__device__ __forceinline__ int xcd_tile(int slot, int n_tiles) {
+  const int xcd = slot & 7, idx = slot >> 3;
+  const int q = n_tiles >> 3, r = n_tiles & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// Fragment addressing of the two staged kernels in an image of 128-byte rows (64 k): for k-substep ks a lane reads row
+// row0 + (l & 15) of a 16-row block, 16-byte chunk 4 ks + (l >> 4), stored at chunk ^ (row & 7).  row0 % 8 == 0, so the rows
+// of all 16-row blocks below it share the swizzle: one offset per k-substep, the blocks are 2048 bytes apart.
+__device__ __forceinline__ uint32_t frag_off(int row0, int lane, int ks) {
+  const int fr = lane & 15, ch = ks * 4 + (lane >> 4);
+  return (uint32_t)(row0 + fr) * 128u + (uint32_t)((ch ^ (fr & 7)) << 4);
 }
 
 // EPI_SWIGLU (both tile forms): N is the width of the PRODUCT (2 H, DINOv2's w12: rows [0, H) of W make the gate, rows
@@ -101,14 +139,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;
 
-  // XCD-aware tile order: the 8 XCDs take workgroups round-robin, so give each XCD a contiguous
-  // run of tiles (feature tiles fastest: the tiles an XCD works on at one time share x rows in its L2)
-  int tile;
-  {
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    const int q = n_tiles >> 3, r = n_tiles & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int tile = xcd_tile(blockIdx.x, n_tiles);
   const int tm = tile / n_tiles_n, tn = tile - tm * n_tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   // EPI_SWIGLU: the tile makes output columns j0 .. j0 + 63; W image rows [64 wn, 64 wn + 32) are gate rows
@@ -144,15 +175,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
 #pragma unroll
     for (int b = 0; b < 4; ++b) acc[a][b] = (v4f){0.f, 0.f, 0.f, 0.f};
 
-  // fragment addressing: lane reads row (l & 15) of a 16-row block, 16-byte chunk 4 ks + (l >> 4)
   const int fr = lane & 15, fq = lane >> 4;
   uint32_t xoff[2], woff[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const int ch = ks * 4 + fq;
-    // rows of all 16-row blocks share (row & 7) == (fr & 7): one swizzled chunk offset per k-substep
-    xoff[ks] = (uint32_t)(wm * 64 + fr) * 128u + (uint32_t)((ch ^ (fr & 7)) << 4);
-    woff[ks] = (uint32_t)kImg + (uint32_t)(wn * 64 + fr) * 128u + (uint32_t)((ch ^ (fr & 7)) << 4);
+    xoff[ks] = frag_off(wm * 64, lane, ks);
+    woff[ks] = (uint32_t)kImg + frag_off(wn * 64, lane, ks);
   }
 
   const int nk = K / BK;
@@ -287,12 +315,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
   // that epilogues do not coincide — the output writes are not a shared-HBM burst problem; every start delay came back as
   // added time, 1268 -> 1344 us per ViT-B layer.)
   for (int slot = blockIdx.x; slot < n_tiles; slot += gridDim.x) {
-  int tile;
-  {
-    const int xcd = slot & 7, idx = slot >> 3;
-    const int q = n_tiles >> 3, r = n_tiles & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int tile = xcd_tile(slot, n_tiles);
   const int tm = tile / n_tiles_n, tn = tile - tm * n_tiles_n;
   const int m0 = tm * G2M, n0 = tn * G2N;
 
@@ -363,14 +386,13 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
 #pragma unroll
     for (int b = 0; b < 8; ++b) acc[a][b] = (v4f){0.f, 0.f, 0.f, 0.f};
 
-  // fragment addressing inside a unit: lane reads unit row (block * 16 + fr), 16-byte chunk (4 ks + fq) ^ (row & 7)
+  // fragment addressing inside a unit (frag_off)
   const int fr = lane & 15, fq = lane >> 4;
   uint32_t xoff[2], woff[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const int ch = ks * 4 + fq;
-    xoff[ks] = (uint32_t)(wr * 64 + fr) * 128u + (uint32_t)((ch ^ (fr & 7)) << 4);
-    woff[ks] = (uint32_t)(wc * 32 + fr) * 128u + (uint32_t)((ch ^ (fr & 7)) << 4);
+    xoff[ks] = frag_off(wr * 64, lane, ks);
+    woff[ks] = frag_off(wc * 32, lane, ks);
   }
   v8bf xf[2][4], wf[2][2][2];   // x fragments of the current token half [ks][block]; W fragments [feature half][ks][block]
 
@@ -453,9 +475,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
   // XORed with (row >> 1) & 7: the 16-byte reads are conflict-free in the hardware's lane groups ({0-3, 12-15, 20-27}, ...:
   // 16 distinct slots of the 256-byte bank row each); the 8-byte writes keep a 2-way conflict (rows 2k and 2k + 1 of a
   // 16-lane group share a slot), which a ds_write_b64's own issue time nearly covers.
-  typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
-  typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
-  typedef __bf16 v2bf16 __attribute__((ext_vector_type(2)));
   uint8_t* const ep = lds2 + (size_t)wave * 16384;
   const int lrow = lane >> 3, lslot = lane & 7;          // whole-line view: row 8 i + lrow, 16-byte slot lslot
   auto ep_at = [&](int row, int byte) { return ep + row * 128 + (byte ^ (((row >> 1) & 7) << 4)); };
@@ -476,28 +495,27 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = swiglu_f32(acc[a][b][j] + (float)bg[j], acc[a + 2][b][j] + (float)bv[j]);
-        const v2bf16 q0 = {(__bf16)v[0], (__bf16)v[1]}, q1 = {(__bf16)v[2], (__bf16)v[3]};
-        *(v2u32*)ep_at(row >> 1, 64 * (row & 1) + 32 * a + 8 * fq) = (v2u32){*(const unsigned int*)&q0, *(const unsigned int*)&q1};
+        *(v2u*)ep_at(row >> 1, 64 * (row & 1) + 32 * a + 8 * fq) = (v2u){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int m = m0 + wr * 128 + 16 * i + (lane >> 2);
-      const v4u32 o = *(const v4u32*)ep_at(8 * i + lrow, lslot * 16);
-      if (m < M) *(v4u32*)(out + (size_t)m * H + colh + (lane & 3) * 8) = o;
+      const v4u o = *(const v4u*)ep_at(8 * i + lrow, lslot * 16);
+      if (m < M) *(v4u*)(out + (size_t)m * H + colh + (lane & 3) * 8) = o;
     }
     asm volatile("s_barrier" ::: "memory");   // as below: the next tile's copies land in this buffer
     continue;
   }
   const size_t col0 = (size_t)n0 + wc * 64;
   if (EPI == EPI_RESIDUAL) {
-    v4u32 rr[16];
+    v4u rr[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      rr[i] = *(const v4u32*)(res + (size_t)min(m0 + wr * 128 + 8 * i + lrow, M - 1) * N + col0 + lslot * 8);
+      rr[i] = *(const v4u*)(res + (size_t)min(m0 + wr * 128 + 8 * i + lrow, M - 1) * N + col0 + lslot * 8);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) *(v4u32*)ep_at(8 * i + lrow, lslot * 16) = rr[i];
+    for (int i = 0; i < 16; ++i) *(v4u*)ep_at(8 * i + lrow, lslot * 16) = rr[i];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
 #pragma unroll
@@ -512,21 +530,21 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
       if (EPI == EPI_GELU) {
 #pragma unroll
         for (int j = 0; j < 4; j += 2) {
-          const v2f_t g = gelu_erf2((v2f_t){v[j], v[j + 1]});
+          const v2f g = gelu_erf2((v2f){v[j], v[j + 1]});
           v[j] = g[0];
           v[j + 1] = g[1];
         }
       }
       if (EPI == EPI_RESIDUAL) {
-        const v2u32 r8 = *(const v2u32*)pp;
+        const v2u r8 = *(const v2u*)pp;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          v[2 * j] += __uint_as_float(r8[j] << 16);
-          v[2 * j + 1] += __uint_as_float(r8[j] & 0xffff0000u);
+          const v2f rf = unpack_bf16x2(r8[j]);
+          v[2 * j] += rf[0];
+          v[2 * j + 1] += rf[1];
         }
       }
-      const v2bf16 q0 = {(__bf16)v[0], (__bf16)v[1]}, q1 = {(__bf16)v[2], (__bf16)v[3]};
-      *(v2u32*)pp = (v2u32){*(const unsigned int*)&q0, *(const unsigned int*)&q1};
+      *(v2u*)pp = (v2u){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -537,9 +555,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int row = 8 * i + lrow;
-      const v4u32 o = *(const v4u32*)ep_at(row, lslot * 16);
+      const v4u o = *(const v4u*)ep_at(row, lslot * 16);
       const size_t orow = ((size_t)pb * 2 * cH + 2 * py + (cpar >> 1)) * (2 * cW) + 2 * px + (cpar & 1);
-      if (mm < M) *(v4u32*)(out + orow * N + col0 + lslot * 8) = o;
+      if (mm < M) *(v4u*)(out + orow * N + col0 + lslot * 8) = o;
       mm += 8;
       px += 8;
       while (px >= cW) { px -= cW; if (++py == cH) { py = 0; ++pb; } }
@@ -548,8 +566,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int row = 8 * i + lrow, m = m0 + wr * 128 + row;
-      const v4u32 o = *(const v4u32*)ep_at(row, lslot * 16);
-      if (m < M) *(v4u32*)(out + (size_t)m * N + col0 + lslot * 8) = o;
+      const v4u o = *(const v4u*)ep_at(row, lslot * 16);
+      if (m < M) *(v4u*)(out + (size_t)m * N + col0 + lslot * 8) = o;
     }
   }
   asm volatile("s_barrier" ::: "memory");   // every wave is past its last fragment read of this tile before the next tile's copies land
@@ -587,15 +605,8 @@ constexpr int XKS = XK / 16;                 // 24 k-steps of v_mfma_f32_32x32x1
 constexpr int XStage = XKS * 1024;           // 24 KiB: one 32-feature block of W in fragment order
 constexpr int XNS = 3;                       // ring slots
 constexpr int XPF = XNS - 1;                 // stages in flight
-constexpr int XMaxN = 4096;                  // bias staging area (floats)
 constexpr int XRows = 256;                   // token rows per workgroup (8 waves x 32)
 constexpr int XChunk = 32 * 128;             // x staging: 32 rows x 64 k (128-byte rows), per wave, double buffered
-constexpr int XOffBias = XNS * XStage;
-constexpr int XOffStage = XOffBias + XMaxN * 4;
-constexpr int XLds = XOffStage + 8 * 2 * XChunk;   // 72 + 16 + 64 = 152 KiB
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 // GELU by table (EPI_GELU with a table pointer).  float32 VALU work does not overlap with the matrix pipe on
 // this part, integer VALU work and LDS reads do (tools/overlap_probe.hip), and the exact GELU is ~150 float
@@ -623,7 +634,281 @@ __global__ void gelu_table_kernel(uint16_t* __restrict__ tab) {
   tab[i] = (uint16_t)f32_to_bf16_rne(y);
 }
 
-constexpr int XReadAhead = 8;   // W fragments read ahead of the MFMA that uses them
+// =====================================================================================================
+// What xs_kernel and mlp2_kernel (below) share.  Everything is __forceinline__ and takes its register arrays by
+// reference; the step index `sl` / `ks` of a sliced function is a constant after unrolling, so a call leaves only the
+// instructions of that step.
+//
+// ---- LDS plans: one constexpr function per kernel, read by the kernel for its pointers and by the host for its limits.
+constexpr int kCuLds = 160 * 1024;                 // LDS of a CU
+constexpr int MStage = 2 * XStage;                 // fused MLP, 48 KiB: [W1 chunk | W2 chunk]
+constexpr int MNS = 2;                             // ... its ring slots
+
+// xs_kernel: [ring of XNS stages][bias area: float32 bias of the N features, behind it (GT) the GELU table]
+//            [per wave 8 KiB: the x transposer, later the out (+0) and residual (+2048) transposers of the epilogue]
+struct XsLds {
+  uint32_t ring, bias, bias_bytes, tr, end;
+  __host__ __device__ constexpr bool bias_fits(int n_out) const { return (uint32_t)n_out * 4 <= bias_bytes; }
+  __host__ __device__ constexpr uint32_t table(int n_out) const { return bias + (uint32_t)((n_out * 4 + 15) & ~15); }
+  __host__ __device__ constexpr bool table_fits(int n_out) const { return table(n_out) + kGtBytes <= bias + bias_bytes; }
+};
+__host__ __device__ constexpr XsLds xs_lds() {
+  vc::LdsCursor c{0};
+  XsLds l{};
+  l.ring = c.take(XNS * XStage, 1024);
+  l.bias_bytes = 16 * 1024;
+  l.bias = c.take(l.bias_bytes, 16);
+  l.tr = c.take(8 * 2 * XChunk, 16);
+  l.end = c.at;
+  return l;
+}
+static_assert(xs_lds().end == 152 * 1024, "xs_kernel: 72 + 16 + 64 KiB");
+static_assert(xs_lds().ring % 1024 == 0 && XStage % 1024 == 0, "xs_kernel: every LDS-DMA piece lands on a 1 KiB boundary");
+static_assert(xs_lds().bias % 16 == 0 && xs_lds().tr % 16 == 0 && XChunk % 16 == 0, "xs_kernel: table and transposers take 16-byte accesses");
+static_assert(xs_lds().table_fits(1920) && !xs_lds().table_fits(1952) && xs_lds().table_fits(1536) && xs_lds().bias_fits(4096),
+              "xs_kernel: ViT-S's fc1 has its table; bias and table share the area up to 1920 features, the bias alone fills it at 4096");
+
+// mlp2_kernel: [ring of MNS stages][fc1 bias][GELU table][fc2 bias][x transposers of the A waves, 4 x 4 KiB]
+//              [out (+0) / residual (+2048) transposers of the B waves, 4 x 4 KiB][activation hand-off: 2 parities x 4 pairs x 2 KiB]
+// The fc1 bias gets what the fixed regions leave of the CU's LDS: that is the limit on the hidden width.
+struct MlpLds {
+  uint32_t ring, b1, b1_bytes, gt, b2, tr_a, tr_b, hand, end;
+  __host__ __device__ constexpr int max_hidden() const { return (int)(b1_bytes / 4 / 32 * 32); }
+};
+__host__ __device__ constexpr MlpLds mlp_lds() {
+  constexpr uint32_t fixed = MNS * MStage + kGtBytes + XK * 4 + 2 * 4 * XChunk + 2 * 4 * 2048;
+  vc::LdsCursor c{0};
+  MlpLds l{};
+  l.ring = c.take(MNS * MStage, 1024);
+  l.b1_bytes = kCuLds - fixed;
+  l.b1 = c.take(l.b1_bytes, 16);
+  l.gt = c.take(kGtBytes, 16);
+  l.b2 = c.take(XK * 4, 16);
+  l.tr_a = c.take(4 * XChunk, 16);
+  l.tr_b = c.take(4 * XChunk, 16);
+  l.hand = c.take(2 * 4 * 2048, 16);
+  l.end = c.at;
+  return l;
+}
+static_assert(mlp_lds().end == kCuLds, "mlp2_kernel: 96 + 6 + 8.5 + 1.5 + 16 + 16 + 16 KiB, no padding between the regions");
+static_assert(mlp_lds().ring % 1024 == 0 && MStage % 1024 == 0 && XStage % 1024 == 0, "mlp2_kernel: every LDS-DMA piece lands on a 1 KiB boundary");
+static_assert(mlp_lds().gt % 16 == 0 && mlp_lds().tr_a % 16 == 0 && mlp_lds().tr_b % 16 == 0 && mlp_lds().hand % 16 == 0,
+              "mlp2_kernel: table, transposers and hand-off take 16-byte accesses");
+static_assert(mlp_lds().max_hidden() == 1536, "mlp2_kernel: the hidden width include/vitcolmap_hip.h documents");
+
+// ---- x rows of a wave as MFMA B fragments (+ LayerNorm) -----------------------------------------------------------
+// Fragment-shaped global loads (32 rows x 32 B per instruction) run at ~5 B/clk/CU, and a staged copy
+// through LDS-DMA is limited by the bytes the staging area lets a wave keep in flight.  So the 32 rows
+// are fetched in whole 128-byte lines straight into registers — 24 loads of 8 rows x 128 B, all in
+// flight at once (the registers that will hold the fragments are the landing zone) — and then turned
+// into fragments 64 k at a time through a 4 KiB wave-private LDS transposer `tp` ([32 rows][128 B], 16-byte
+// chunk ^ ((row >> 1) & 7): conflict free for the 8-row writes and the 32-row column-slice reads).
+// DS operations of one wave execute in order, so the transposer needs no waits between chunks.
+// Two halves, because xs_kernel runs the pending block's epilogue while the loads are in flight.
+__device__ __forceinline__ void x_rows_issue(v8bf (&xf)[XKS], const __bf16* X, int row0, int M, int lane) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int m = min(row0 + 8 * p + (lane >> 3), M - 1);
+    const uint8_t* src = (const uint8_t*)X + (size_t)m * (XK * 2) + (lane & 7) * 16;
+#pragma unroll
+    for (int c = 0; c < XK / 64; ++c) *(v4u*)&xf[4 * c + p] = *(const v4u*)(src + c * 128);   // raw lines land in xf itself
+  }
+}
+template <bool LN>
+__device__ __forceinline__ void x_rows_finish(v8bf (&xf)[XKS], uint8_t* tp, int lane, float eps) {
+  const int r = lane & 31, h = lane >> 5, prow = lane >> 3;
+  const int fsw = (r >> 1) & 7;
+#pragma unroll
+  for (int c = 0; c < XK / 64; ++c) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int row = 8 * p + prow;
+      *(v4u*)(tp + row * 128 + (((lane & 7) ^ ((row >> 1) & 7)) << 4)) = *(const v4u*)&xf[4 * c + p];
+    }
+#pragma unroll
+    for (int k4 = 0; k4 < 4; ++k4)
+      xf[4 * c + k4] = *(const v8bf*)(tp + r * 128 + (((2 * k4 + h) ^ fsw) << 4));
+  }
+  if (LN) {
+    // a lane and its partner (l ^ 32) hold one whole row: two-pass float32 statistics with packed (2-wide) VALU ops;
+    // the passes re-expand the bf16 pairs (shift / mask) instead of keeping 192 floats live
+    v2f s2 = {0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < XKS; ++ks) {
+      const v4u u = *(const v4u*)&xf[ks];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s2 += unpack_bf16x2(u[j]);
+    }
+    float sum = s2[0] + s2[1];
+    sum += __shfl_xor(sum, 32);
+    const float mean = sum * (1.0f / XK);
+    const v2f mean2 = {mean, mean};
+#pragma unroll
+    for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
+    v2f q2 = {0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < XKS; ++ks) {
+      const v4u u = *(const v4u*)&xf[ks];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const v2f d = unpack_bf16x2(u[j]) - mean2; q2 = __builtin_elementwise_fma(d, d, q2); }
+    }
+    float q = q2[0] + q2[1];
+    q += __shfl_xor(q, 32);
+    const float rstd = __builtin_amdgcn_rsqf(q * (1.0f / XK) + eps);
+    const v2f rstd2 = {rstd, rstd};
+#pragma unroll
+    for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
+#pragma unroll
+    for (int ks = 0; ks < XKS; ++ks) {
+      const v4u u = *(const v4u*)&xf[ks];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const v2f y = (unpack_bf16x2(u[j]) - mean2) * rstd2;
+        xf[ks][2 * j] = (__bf16)y[0];
+        xf[ks][2 * j + 1] = (__bf16)y[1];
+      }
+    }
+  }
+}
+
+// ---- table GELU of one 32 x 32 block, cut into slices 0-15 that ride between the MFMAs of the next block ---------------
+// MFMA layout: lane = token r, half h, accumulator register 4g + j = feature 8g + 4h + j; packed register 2g (2g + 1)
+// holds the bf16 pair j = 0, 1 (2, 3) of group g.
+struct BlockState {
+  uint32_t pb[8];    // pre-activations as bf16 pairs
+  uint32_t gq[8];    // looked-up halves in flight (ring of 4 packed registers)
+  uint32_t ep[8];    // the block's results as bf16 pairs
+  uint32_t gbad;     // largest table index seen (out-of-range detector)
+};
+__device__ __forceinline__ void pack_group(uint32_t (&dst)[8], int g, float v0, float v1, float v2, float v3) {
+  dst[2 * g] = pack_bf16x2(v0, v1);
+  dst[2 * g + 1] = pack_bf16x2(v2, v3);
+}
+// slices 0-3: pre-activations -> bf16 pairs (pb), the only float work; 4-11: table index + LDS gather of packed register
+// sl - 4; 7-14: results packed back (three slices, ~100+ cycles, after the gather was issued); 15: range check — a value
+// outside the table's range somewhere in the wave sends the block through the float path.  s.ep is complete after slice 15.
+__device__ __forceinline__ void gelu_table_slice(int sl, const v16f& pre, BlockState& s, const uint8_t* gt_l) {
+  if (sl < 4) {
+    pack_group(s.pb, sl, pre[4 * sl], pre[4 * sl + 1], pre[4 * sl + 2], pre[4 * sl + 3]);
+    if (sl == 0) s.gbad = 0;
+  }
+  if (sl >= 4 && sl < 12) {
+    const int qd = sl - 4;
+    const uint32_t b0 = s.pb[qd] & 0xffffu, b1 = s.pb[qd] >> 16;
+    const uint32_t k0 = (b0 & 0x7fffu) - kGtLo, k1 = (b1 & 0x7fffu) - kGtLo;   // wraps to a huge value below the range
+    s.gbad = max(s.gbad, max(k0, k1));
+    s.gq[2 * (qd & 3)] = *(const uint16_t*)(gt_l + min(k0, kGtN - 1) * 4 + ((b0 >> 15) << 1));
+    s.gq[2 * (qd & 3) + 1] = *(const uint16_t*)(gt_l + min(k1, kGtN - 1) * 4 + ((b1 >> 15) << 1));
+  }
+  if (sl >= 7 && sl < 15) {
+    const int qd = sl - 7;
+    s.ep[qd] = s.gq[2 * (qd & 3)] | (s.gq[2 * (qd & 3) + 1] << 16);
+  }
+  if (sl == 15) {
+    if (__any(s.gbad >= kGtN)) {
+#pragma unroll
+      for (int qd = 0; qd < 8; ++qd) {
+        const v2f y = gelu_erf2(unpack_bf16x2(s.pb[qd]));
+        s.ep[qd] = pack_bf16x2(y[0], y[1]);
+      }
+    }
+  }
+}
+
+// ---- a 32 (features) x 32 (tokens) D^T block leaves --------------------------------------------------------------------
+// A row-per-lane global access (32 rows per instruction) is issue-bound in the texture path, so both the residual read
+// and the result write go through wave-private transposers — [32 tokens][64 B], 16-byte chunk ^ ((token >> 2) & 3),
+// conflict free both ways — and touch memory as lane -> (token l >> 2 (+16 q), 16-byte chunk l & 3): 16 rows x 64
+// contiguous bytes per instruction.  DS operations of one wave execute in order, so no wait separates write and read.
+// Results leave through a raw buffer store: rows past M fall outside num_records and are dropped by the hardware, so
+// every block issues exactly two store instructions (xs_kernel's vmcnt bookkeeping counts them).
+// The steps, in order: pack_group x 4; half_swap; tr_write; tr_read x 2; block_store x 2.  Residual side: res_load x 2
+// (whole lines), res_write x 2, res_read per group (the lane's own 8 bytes back in the accumulator layout).
+__device__ __forceinline__ uint8_t* tr_line(uint8_t* tr, int lane, int q) {   // the lane's 16 bytes in the whole-line view
+  const int row = (lane >> 2) + 16 * q;
+  return tr + row * 64 + (((lane & 3) ^ ((row >> 2) & 3)) << 4);
+}
+// exchange with the partner lane (l ^ 32): h = 0 ends with features 0..15, h = 1 with 16..31
+__device__ __forceinline__ void half_swap(uint32_t (&ep)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {     // i = 0,1: group 0 <-> group 2;  i = 2,3: group 1 <-> group 3
+    const auto sw = __builtin_amdgcn_permlane32_swap(ep[i], ep[i + 4], false, false);
+    ep[i] = sw[0];
+    ep[i + 4] = sw[1];
+  }
+}
+__device__ __forceinline__ void tr_write(uint8_t* tr_out, const uint32_t (&ep)[8], int lane) {
+  const int r = lane & 31, h = lane >> 5, rsw = (r >> 2) & 3;
+  *(v4u*)(tr_out + r * 64 + (((2 * h) ^ rsw) << 4)) = (v4u){ep[0], ep[1], ep[4], ep[5]};
+  *(v4u*)(tr_out + r * 64 + (((2 * h + 1) ^ rsw) << 4)) = (v4u){ep[2], ep[3], ep[6], ep[7]};
+}
+__device__ __forceinline__ v4u tr_read(uint8_t* tr_out, int lane, int q) { return *(const v4u*)tr_line(tr_out, lane, q); }
+// rows row0 .. row0 + 31 of an [M][n_cols] output, columns col0 .. col0 + 31
+__device__ __forceinline__ void block_store(v4u v, __amdgpu_buffer_rsrc_t out_rs, int row0, int n_cols, int col0, int lane, int q) {
+  const int row = (lane >> 2) + 16 * q;
+  __builtin_amdgcn_raw_buffer_store_b128(v, out_rs, (int)(((size_t)(row0 + row) * n_cols + col0 + (lane & 3) * 8) * 2), 0, 0);
+}
+__device__ __forceinline__ v4u res_load(const __bf16* res, int row0, int M, int n_cols, int col0, int lane, int q) {
+  return *(const v4u*)(res + (size_t)min(row0 + (lane >> 2) + 16 * q, M - 1) * n_cols + col0 + (lane & 3) * 8);
+}
+__device__ __forceinline__ void res_write(uint8_t* tr_res, v4u v, int lane, int q) { *(v4u*)tr_line(tr_res, lane, q) = v; }
+__device__ __forceinline__ v4bf res_read(const uint8_t* tr_res, int lane, int g) {   // features 8g + 4h .. + 3 of token r
+  const int r = lane & 31, h = lane >> 5;
+  return *(const v4bf*)(tr_res + r * 64 + ((g ^ ((r >> 2) & 3)) << 4) + 8 * h);
+}
+
+// ---- one 32 x 32 x 384 product ----------------------------------------------------------------------------------------
+// The bias is the accumulator's initial value: register 4g + j <- bias32[8g + 4h + j] (bias32: the block's 32 floats in LDS).
+__device__ __forceinline__ void acc_from_bias(v16f& acc, const float* bias32, int lane) {
+  const float* bl = bias32 + 4 * (lane >> 5);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const v4f bv = *(const v4f*)(bl + 8 * g);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[4 * g + j] = bv[j];
+  }
+}
+// The 24 MFMAs of a stage (`st`: the lane's 16 bytes of piece 0; pieces are 1 KiB apart).  W fragments are read RD
+// k-steps ahead of the MFMA that consumes them (LDS latency ~ 4 MFMAs); then [MFMA, fragment read, behind(ks)] per
+// k-step — `behind` is the caller's epilogue slice and / or LDS-DMA piece — with a sched_barrier pinning each group; the
+// compiler places the waits.  (The fragment array lives in here: handed in by reference from a caller with two loops,
+// xs_kernel's LayerNorm instantiations gained 32-52 bytes of scratch.)
+template <int RD, typename F>
+__device__ __forceinline__ void stage_mfmas(v16f& acc, const uint8_t* st, const v8bf (&xf)[XKS], F&& behind) {
+  v8bf wf[XKS];
+#pragma unroll
+  for (int ks = 0; ks < RD; ++ks) wf[ks] = *(const v8bf*)(st + ks * 1024);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ks = 0; ks < XKS; ++ks) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], acc, 0, 0, 0);
+    if (ks + RD < XKS) wf[ks + RD] = *(const v8bf*)(st + (ks + RD) * 1024);
+    behind(ks);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- prepare side: one fc1-type weight row into fragment order ------------------------------------------------------------
+// Row `rr` of a 32-feature block `blk` (XStage / 2 elements): piece ks = k >> 4 is the 1 KiB A operand of k-step ks, lane
+// 32 hh + rr holds k = 16 ks + 8 hh .. + 7.  LayerNorm's gamma is folded into the weights; returns the wave's sum of
+// w[k] beta[k], the row's share of the folded bias.  One wave per row.
+__device__ __forceinline__ float fc1_row_to_fragments(const float* __restrict__ w, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, __bf16* __restrict__ blk, int rr, int lane) {
+  float dot = 0.f;
+  for (int k = lane; k < XK; k += 64) {
+    const float wk = w[k];
+    if (beta) dot += wk * beta[k];
+    const int ks = k >> 4, hh = (k >> 3) & 1, j = k & 7;
+    blk[((size_t)ks * 64 + hh * 32 + rr) * 8 + j] = (__bf16)(gamma ? wk * gamma[k] : wk);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+  return dot;
+}
+
+// =====================================================================================================
+// xs_kernel (described above the K = 384 constants).
+constexpr int XReadAhead = 8;  // W fragments read ahead of the MFMA that uses them
 constexpr int XIssue0 = 1;      // MFMA behind which the first piece of stage i + 2 is issued ...
 constexpr int XIssueStep = 8;   // ... and the distance to the next (the last one stays ahead of the result stores at slice 19)
 template <int EPI, bool LN, bool GT>
@@ -631,20 +916,19 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
                                                     const float* __restrict__ biasf, const __bf16* res,
                                                     __bf16* out, int M, int N, int n_nb, int n_stages, float eps,
                                                     const uint16_t* __restrict__ gelu_tab) {
-  __shared__ __attribute__((aligned(1024))) uint8_t lds[XLds];
+  constexpr XsLds L = xs_lds();
+  __shared__ __attribute__((aligned(1024))) uint8_t lds[L.end];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
 
   const int G = gridDim.x, bid = blockIdx.x;
   const int s0 = (int)((long long)n_stages * bid / G), s1 = (int)((long long)n_stages * (bid + 1) / G);
   const int n = s1 - s0;
   if (n <= 0) return;
 
-  float* bias_l = (float*)(lds + XOffBias);
+  float* bias_l = (float*)(lds + L.bias);
   for (int i = tid; i < N; i += 512) bias_l[i] = biasf[i];   // visible after the first stage barrier
-  // GELU table behind the bias (the host checks that both fit the 16 KiB area)
-  uint8_t* const gt_l = lds + XOffBias + ((N * 4 + 15) & ~15);
+  uint8_t* const gt_l = lds + L.table(N);   // (the host passes GT only where L.table_fits(N))
   if (GT)
     for (int i = tid; i < kGtBytes / 4; i += 512) ((uint32_t*)gt_l)[i] = ((const uint32_t*)gelu_tab)[i];
 
@@ -671,206 +955,55 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
 #pragma unroll
   for (int j = 0; j < XPF; ++j) issue();
 
-  // ---- x rows of this wave as B fragments ---------------------------------------------------------
-  // Fragment-shaped global loads (32 rows x 32 B per instruction) run at ~5 B/clk/CU, and a staged copy
-  // through LDS-DMA is limited by the bytes the staging area lets a wave keep in flight.  So the 32 rows
-  // are fetched in whole 128-byte lines straight into registers — 24 loads of 8 rows x 128 B, all in
-  // flight at once (the registers that will hold the fragments are the landing zone) — and then turned
-  // into fragments 64 k at a time through a 4 KiB wave-private LDS transposer ([32 rows][128 B], 16-byte
-  // chunk ^ ((row >> 1) & 7): conflict free for the 8-row writes and the 32-row column-slice reads).
-  // DS operations of one wave execute in order, so the transposer needs no waits between chunks.
+  // ---- x rows of this wave as B fragments (x_rows_issue / x_rows_finish) ----------------------------------------
   v8bf xf[XKS];
-  typedef float v2f __attribute__((ext_vector_type(2)));
-  const int prow = lane >> 3;
-  auto x_issue = [&](int mt) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int m = min(mt * XRows + wave * 32 + 8 * p + prow, M - 1);
-      const uint8_t* src = (const uint8_t*)X + (size_t)m * (XK * 2) + (lane & 7) * 16;
-#pragma unroll
-      for (int c = 0; c < XK / 64; ++c) *(v4u*)&xf[4 * c + p] = *(const v4u*)(src + c * 128);   // raw lines land in xf itself
-    }
-  };
-  auto x_finish = [&]() {
-    uint8_t* const tp = lds + XOffStage + wave * (2 * XChunk);
-    const int fsw = (r >> 1) & 7;
-#pragma unroll
-    for (int c = 0; c < XK / 64; ++c) {
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int row = 8 * p + prow;
-        *(v4u*)(tp + row * 128 + (((lane & 7) ^ ((row >> 1) & 7)) << 4)) = *(const v4u*)&xf[4 * c + p];
-      }
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4)
-        xf[4 * c + k4] = *(const v8bf*)(tp + r * 128 + (((2 * k4 + h) ^ fsw) << 4));
-    }
-    if (LN) {
-      // two-pass float32 statistics with packed (2-wide) VALU ops; the passes re-expand the bf16 pairs
-      // (shift / mask) instead of keeping 192 floats live
-      auto expand = [](uint32_t u) { return (v2f){__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; };
-      v2f s2 = {0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < XKS; ++ks) {
-        const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s2 += expand(u[j]);
-      }
-      float sum = s2[0] + s2[1];
-      sum += __shfl_xor(sum, 32);
-      const float mean = sum * (1.0f / XK);
-      const v2f mean2 = {mean, mean};
-#pragma unroll
-      for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
-      v2f q2 = {0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < XKS; ++ks) {
-        const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const v2f d = expand(u[j]) - mean2; q2 = __builtin_elementwise_fma(d, d, q2); }
-      }
-      float q = q2[0] + q2[1];
-      q += __shfl_xor(q, 32);
-      const float rstd = __builtin_amdgcn_rsqf(q * (1.0f / XK) + eps);
-      const v2f rstd2 = {rstd, rstd};
-#pragma unroll
-      for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
-#pragma unroll
-      for (int ks = 0; ks < XKS; ++ks) {
-        const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const v2f y = (expand(u[j]) - mean2) * rstd2;
-          xf[ks][2 * j] = (__bf16)y[0];
-          xf[ks][2 * j + 1] = (__bf16)y[1];
-        }
-      }
-    }
-  };
+  uint8_t* const tr_out = lds + L.tr + wave * (2 * XChunk);   // x transposer, then out / residual transposers (idle x staging)
+  uint8_t* const tr_res = tr_out + 2048;
 
-  // ---- epilogue of one 32 (features) x 32 (tokens) block.  MFMA side: lane = token r, half h, register
-  // 4g + j = feature 8g + 4h + j.  A row-per-lane global access (32 rows per instruction) is issue-bound in
-  // the texture path, so both the residual read and the result write go through a wave-private transposer
-  // in the (idle) x staging area — [32 tokens][64 B], 16-byte chunk ^ ((token >> 2) & 3), conflict free both
-  // ways — and touch memory as lane -> (token l >> 2 (+16), 16-byte chunk l & 3): 16 rows x 64 contiguous
-  // bytes per instruction.  DS operations of one wave execute in order, so no wait separates write and read.
-  // Results leave through a raw buffer store: rows past M fall outside num_records and are dropped by the
-  // hardware, so every epilogue issues exactly two store instructions (the vmcnt bookkeeping below counts them).
-  //
+  // ---- epilogue of one 32 (features) x 32 (tokens) block (the block-leaving steps above).
   // The epilogue of block i-1 is cut into 24 slices that are issued BETWEEN the 24 MFMAs of block i, in the
   // same wave (all 8 waves run the same stream, no wave roles).  tools/overlap_probe.hip: float32 VALU work does
   // not overlap with the matrix pipe on this part however it is arranged (integer VALU work does), so this
   // costs the same as running the epilogue as a cluster — time = MFMA time + float VALU time — and is kept
   // for its simplicity; the lever for this kernel is fewer float instructions per output.
   const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)M * N * 2), 0x00020000);
-  uint8_t* const tr_out = lds + XOffStage + wave * (2 * XChunk);
-  uint8_t* const tr_res = tr_out + 2048;
-  const int crow = lane >> 2, cch = lane & 3;
-  const int rsw = (r >> 2) & 3;
-  v4u resq[2];
+  constexpr bool TABLE = EPI == EPI_GELU && GT;
+  // the slices at which a finished block (s.ep) is exchanged, written to the transposer, read back and stored: behind the
+  // table's 16 slices, or behind 8 slices of float work (values 2 sl, 2 sl + 1) and 4 of packing
+  struct Leave { int swap, write, read, store; };
+  constexpr Leave at = TABLE ? Leave{16, 17, 19, 22} : Leave{12, 13, 15, 19};
+  // state that flows from slice to slice
+  v4u resq[2];      // the next block's residual lines
+  v16f pa;          // the pending block's accumulators
+  float ev[16];     // ... after GELU / residual
+  BlockState s;     // ... packed to bf16 pairs
+  v4u eo[2];        // ... transposed for the store
+  int pm_base = 0, pnb = 0;
   auto load_res = [&](int m_base, int nb) {
     if (EPI == EPI_RESIDUAL) {
 #pragma unroll
-      for (int q = 0; q < 2; ++q)
-        resq[q] = *(const v4u*)(res + (size_t)min(m_base + crow + 16 * q, M - 1) * N + nb * 32 + cch * 8);
+      for (int q = 0; q < 2; ++q) resq[q] = res_load(res, m_base, M, N, nb * 32, lane, q);
     }
   };
-  // state that flows from slice to slice
-  v16f pa;          // the pending block's accumulators
-  float ev[16];     // ... after GELU / residual
-  uint32_t ep[8];   // ... packed to bf16 pairs
-  v4u eo[2];        // ... transposed for the store
-  int pm_base = 0, pnb = 0;
   auto res_to_lds = [&]() {   // the pending block's residual (loaded an iteration ago) enters the transposer
     if (EPI == EPI_RESIDUAL) {
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int row = crow + 16 * q;
-        *(v4u*)(tr_res + row * 64 + ((cch ^ ((row >> 2) & 3)) << 4)) = resq[q];
-      }
+      for (int q = 0; q < 2; ++q) res_write(tr_res, resq[q], lane, q);
     }
   };
-  uint32_t gq[8];        // table GELU: looked-up halves in flight (ring of 4 packed registers)
-  uint32_t gres[8];      // ... results, packed bf16 pairs, parked until the range check
-  uint32_t gbad = 0;     // ... largest table index seen (out-of-range detector)
   auto slice = [&](int sl) {
-    if (EPI == EPI_GELU && GT) {
-      // slices 0-3: pre-activations -> bf16 pairs (ep), the only float work; 4-11: table index + LDS gather of
-      // packed register sl-4; 7-14: results packed back; 15: range check (+ float path); 16/17/19/22: exchange,
-      // transposer write / read, store
-      typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-      if (sl < 4) {
-        const int g = sl;
-        const v2bf lo = {(__bf16)pa[4 * g], (__bf16)pa[4 * g + 1]}, hi = {(__bf16)pa[4 * g + 2], (__bf16)pa[4 * g + 3]};
-        ep[2 * g] = *(const uint32_t*)&lo;
-        ep[2 * g + 1] = *(const uint32_t*)&hi;
-        if (sl == 0) gbad = 0;
-      }
-      if (sl >= 4 && sl < 12) {
-        const int qd = sl - 4;
-        const uint32_t b0 = ep[qd] & 0xffffu, b1 = ep[qd] >> 16;
-        const uint32_t k0 = (b0 & 0x7fffu) - kGtLo, k1 = (b1 & 0x7fffu) - kGtLo;   // wraps to a huge value below the range
-        gbad = max(gbad, max(k0, k1));
-        const uint32_t a0 = min(k0, kGtN - 1) * 4 + ((b0 >> 15) << 1), a1 = min(k1, kGtN - 1) * 4 + ((b1 >> 15) << 1);
-        gq[2 * (qd & 3)] = *(const uint16_t*)(gt_l + a0);
-        gq[2 * (qd & 3) + 1] = *(const uint16_t*)(gt_l + a1);
-      }
-      if (sl >= 7 && sl < 15) {        // three slices (~100+ cycles) after the gather was issued
-        const int qd = sl - 7;
-        gres[qd] = gq[2 * (qd & 3)] | (gq[2 * (qd & 3) + 1] << 16);
-      }
-      if (sl == 15) {
-        if (__any(gbad >= kGtN)) {       // a value outside the table's range somewhere in the wave: float path for the block
-#pragma unroll
-          for (int qd = 0; qd < 8; ++qd) {
-            const v2f_t xin = {__uint_as_float(ep[qd] << 16), __uint_as_float(ep[qd] & 0xffff0000u)};
-            const v2f_t y = gelu_erf2(xin);
-            const v2bf o = {(__bf16)y[0], (__bf16)y[1]};
-            ep[qd] = *(const uint32_t*)&o;
-          }
-        } else {
-#pragma unroll
-          for (int qd = 0; qd < 8; ++qd) ep[qd] = gres[qd];
-        }
-      }
-      if (sl == 16) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(ep[i], ep[i + 4], false, false);
-          ep[i] = sw[0];
-          ep[i + 4] = sw[1];
-        }
-      }
-      if (sl == 17) {
-        *(v4u*)(tr_out + r * 64 + (((2 * h) ^ rsw) << 4)) = (v4u){ep[0], ep[1], ep[4], ep[5]};
-        *(v4u*)(tr_out + r * 64 + (((2 * h + 1) ^ rsw) << 4)) = (v4u){ep[2], ep[3], ep[6], ep[7]};
-      }
-      if (sl == 19) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int row = crow + 16 * q;
-          eo[q] = *(const v4u*)(tr_out + row * 64 + ((cch ^ ((row >> 2) & 3)) << 4));
-        }
-      }
-      if (sl == 22) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int row = crow + 16 * q;
-          __builtin_amdgcn_raw_buffer_store_b128(eo[q], out_rs, (int)(((size_t)(pm_base + row) * N + pnb * 32 + cch * 8) * 2), 0, 0);
-        }
-      }
-      return;
-    }
-    if (sl < 8) {                       // values 2 sl, 2 sl + 1
+    if (TABLE) {
+      gelu_table_slice(sl, pa, s, gt_l);
+    } else if (sl < 8) {
       const int j0 = 2 * sl;
       if (EPI == EPI_GELU) {
-        const v2f_t y = gelu_erf2((v2f_t){pa[j0], pa[j0 + 1]});
+        const v2f y = gelu_erf2((v2f){pa[j0], pa[j0 + 1]});
         ev[j0] = y[0];
         ev[j0 + 1] = y[1];
       } else if (EPI == EPI_RESIDUAL) {
         if ((sl & 1) == 0) {            // one 8-byte read serves values 4g .. 4g + 3
           const int g = sl >> 1;
-          const v4bf rv = *(const v4bf*)(tr_res + r * 64 + ((g ^ rsw) << 4) + 8 * h);
+          const v4bf rv = res_read(tr_res, lane, g);
 #pragma unroll
           for (int j = 0; j < 4; ++j) ev[4 * g + j] = pa[4 * g + j] + (float)rv[j];
         }
@@ -878,35 +1011,19 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
         ev[j0] = pa[j0];
         ev[j0 + 1] = pa[j0 + 1];
       }
-    } else if (sl < 12) {               // pack group g
+    } else if (sl < 12) {
       const int g = sl - 8;
-      typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-      const v2bf lo = {(__bf16)ev[4 * g], (__bf16)ev[4 * g + 1]}, hi = {(__bf16)ev[4 * g + 2], (__bf16)ev[4 * g + 3]};
-      ep[2 * g] = *(const uint32_t*)&lo;
-      ep[2 * g + 1] = *(const uint32_t*)&hi;
-    } else if (sl == 12) {
-      // exchange with the partner lane (l ^ 32): h = 0 ends with features 0..15, h = 1 with 16..31
+      pack_group(s.ep, g, ev[4 * g], ev[4 * g + 1], ev[4 * g + 2], ev[4 * g + 3]);
+    }
+    if (sl == at.swap) half_swap(s.ep);
+    if (sl == at.write) tr_write(tr_out, s.ep, lane);
+    if (sl == at.read) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {     // i = 0,1: group 0 <-> group 2;  i = 2,3: group 1 <-> group 3
-        const auto sw = __builtin_amdgcn_permlane32_swap(ep[i], ep[i + 4], false, false);
-        ep[i] = sw[0];
-        ep[i + 4] = sw[1];
-      }
-    } else if (sl == 13) {
-      *(v4u*)(tr_out + r * 64 + (((2 * h) ^ rsw) << 4)) = (v4u){ep[0], ep[1], ep[4], ep[5]};
-      *(v4u*)(tr_out + r * 64 + (((2 * h + 1) ^ rsw) << 4)) = (v4u){ep[2], ep[3], ep[6], ep[7]};
-    } else if (sl == 15) {
+      for (int q = 0; q < 2; ++q) eo[q] = tr_read(tr_out, lane, q);
+    }
+    if (sl == at.store) {
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int row = crow + 16 * q;
-        eo[q] = *(const v4u*)(tr_out + row * 64 + ((cch ^ ((row >> 2) & 3)) << 4));
-      }
-    } else if (sl == 19) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int row = crow + 16 * q;
-        __builtin_amdgcn_raw_buffer_store_b128(eo[q], out_rs, (int)(((size_t)(pm_base + row) * N + pnb * 32 + cch * 8) * 2), 0, 0);
-      }
+      for (int q = 0; q < 2; ++q) block_store(eo[q], out_rs, pm_base, N, pnb * 32, lane, q);
     }
   };
 
@@ -935,54 +1052,27 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
     const int m_base = mt * XRows + wave * 32;
     if (reload) {
       // new row tile: the pending block cannot ride under this block's MFMAs (its x loads come first)
-      x_issue(mt);
+      x_rows_issue(xf, X, m_base, M, lane);
       if (pending) {
 #pragma unroll
         for (int sl = 0; sl < XKS; ++sl) slice(sl);
       }
-      x_finish();
+      x_rows_finish<LN>(xf, tr_out, lane, eps);
       mt_cur = mt;
     }
     load_res(m_base, nb);
     const uint8_t* st = lds + slot * XStage + lane * 16;
+    acc_from_bias(acc, bias_l + nb * 32, lane);
     {
-      // the bias is the accumulator's initial value: register 4g + j <- bias[32 nb + 8g + 4h + j]
-      const float* bl = bias_l + nb * 32 + 4 * h;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const v4f bv = *(const v4f*)(bl + 8 * g);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[4 * g + j] = bv[j];
-      }
-    }
-    {
-      // W fragments are read XRD k-steps ahead of the MFMA that consumes them (LDS latency ~ 4 MFMAs);
-      // sched_barrier pins [MFMA, fragment read, epilogue slice] per k-step, the compiler places the waits
-      constexpr int XRD = (EPI == EPI_GELU && GT) ? 6 : XReadAhead;   // the table epilogue needs the registers
-      v8bf wf[XKS];
-#pragma unroll
-      for (int ks = 0; ks < XRD; ++ks) wf[ks] = *(const v8bf*)(st + ks * 1024);
-      __builtin_amdgcn_sched_barrier(0);
-      if (pending && !reload) {
-#pragma unroll
-        for (int ks = 0; ks < XKS; ++ks) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], acc, 0, 0, 0);
-          if (ks + XRD < XKS) wf[ks + XRD] = *(const v8bf*)(st + (ks + XRD) * 1024);
-          slice(ks);
-          if (ks == XIssue0 || ks == XIssue0 + XIssueStep || ks == XIssue0 + 2 * XIssueStep)
-            issue_piece((ks - XIssue0) / XIssueStep);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
-#pragma unroll
-        for (int ks = 0; ks < XKS; ++ks) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], acc, 0, 0, 0);
-          if (ks + XRD < XKS) wf[ks + XRD] = *(const v8bf*)(st + (ks + XRD) * 1024);
-          if (ks == XIssue0 || ks == XIssue0 + XIssueStep || ks == XIssue0 + 2 * XIssueStep)
-            issue_piece((ks - XIssue0) / XIssueStep);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
+      constexpr int XRD = TABLE ? 6 : XReadAhead;   // the table epilogue needs the registers
+      auto piece_behind = [&](int ks) {
+        if (ks == XIssue0 || ks == XIssue0 + XIssueStep || ks == XIssue0 + 2 * XIssueStep)
+          issue_piece((ks - XIssue0) / XIssueStep);
+      };
+      if (pending && !reload)
+        stage_mfmas<XRD>(acc, st, xf, [&](int ks) { slice(ks); piece_behind(ks); });
+      else
+        stage_mfmas<XRD>(acc, st, xf, piece_behind);
     }
     pa = acc;
     pm_base = m_base;
@@ -1005,17 +1095,7 @@ __global__ __launch_bounds__(256) void xs_prepare_kernel(const float* __restrict
   const int lane = threadIdx.x & 63;
   const int nfeat = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (nfeat >= N) return;
-  const int nb = nfeat >> 5, rr = nfeat & 31;
-  float dot = 0.f;
-  for (int k = lane; k < XK; k += 64) {
-    const float w = W[(size_t)nfeat * XK + k];
-    const float wg = gamma ? w * gamma[k] : w;
-    if (beta) dot += w * beta[k];
-    const int ks = k >> 4, hh = (k >> 3) & 1, j = k & 7;
-    Wp[(((size_t)nb * XKS + ks) * 64 + hh * 32 + rr) * 8 + j] = (__bf16)wg;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+  const float dot = fc1_row_to_fragments(W + (size_t)nfeat * XK, gamma, beta, Wp + (size_t)(nfeat >> 5) * (XStage / 2), nfeat & 31, lane);
   if (lane == 0) biasf[nfeat] = (b ? b[nfeat] : 0.f) + dot;
 }
 
@@ -1032,8 +1112,6 @@ __global__ __launch_bounds__(256) void xs_prepare_kernel(const float* __restrict
 //     the next MFMA's operand: W2's k order is permuted by the prepare step to match the register order);
 //   * after the last chunk of a row tile: + fc2 bias + residual (the tile's own x rows, read back), stored in place.
 // Row tiles are dealt round-robin to one persistent workgroup per CU.
-constexpr int MStage = 2 * XStage;                 // 48 KiB: [W1 chunk | W2 chunk]
-constexpr int MNS = 2;
 
 // mlp2_kernel splits the work by role: 8 waves, two per SIMD.  Waves 0-3 ("A") keep the
 // normalised x rows and compute H^T chunk by chunk + the GELU; waves 4-7 ("B") keep the 384 x 32 output accumulators
@@ -1043,14 +1121,7 @@ constexpr int MNS = 2;
 // integer work runs beside the partner's MFMAs, and the LDS-DMA pieces of a stage are issued by 8 waves instead of 4
 // (a piece occupies its wave for ~180 cycles: with 12 pieces per wave the staging alone took 2170 cycles per stage).
 // Stage i in the ring = [W1 chunk c_i | W2 chunk c_{i-1}] so both halves are consumed in iteration i.
-constexpr int M2OffB1 = MNS * MStage;                // fc1 bias, 1536 floats
-constexpr int M2OffGt = M2OffB1 + 1536 * 4;          // GELU table (8704 B)
-constexpr int M2OffB2 = M2OffGt + 8704;              // fc2 bias (384 floats)
-constexpr int M2OffTrA = M2OffB2 + 1536;             // x transposers of the A waves, 4 x 4 KiB
-constexpr int M2OffTrB = M2OffTrA + 4 * XChunk;      // out / residual transposers of the B waves, 4 x 4 KiB
-constexpr int M2OffG = M2OffTrB + 4 * XChunk;        // activation hand-off: [2 parities][4 pairs][2 KiB]
-constexpr int M2Lds = M2OffG + 2 * 4 * 2048;         // 96 + 16 + 16 + 16 + 16 = 160 KiB
-static_assert(M2Lds <= 160 * 1024, "fused MLP: LDS budget");
+// The LDS layout is mlp_lds (shared section above).
 
 constexpr int M2ReadAhead = 6;    // weight fragments read ahead of the MFMA that uses them
 constexpr int M2PiecesA = 3;      // LDS-DMA pieces of a stage issued by each fc1 wave (each fc2 wave issues the other 9): the fc1 role is the longer one
@@ -1061,20 +1132,20 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
                                                       const float* __restrict__ b1f, const float* __restrict__ b2f,
                                                       int M, int n_chunks, int n_tiles, float eps,
                                                       const uint16_t* __restrict__ gelu_tab) {
-  __shared__ __attribute__((aligned(1024))) uint8_t lds[M2Lds];
+  constexpr MlpLds L = mlp_lds();
+  __shared__ __attribute__((aligned(1024))) uint8_t lds[L.end];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool roleB = wave >= 4;
   const int pairw = wave & 3;                       // row block of the pair inside the 128-row tile
-  const int r = lane & 31, h = lane >> 5;
   const int G = gridDim.x, bid = blockIdx.x;
   const int my_tiles = bid < n_tiles ? (n_tiles - bid + G - 1) / G : 0;
   const int n = my_tiles * n_chunks;                // fc1 stages; fc2 runs one iteration behind
   if (n <= 0) return;
 
-  float* const b1_l = (float*)(lds + M2OffB1);
-  float* const b2_l = (float*)(lds + M2OffB2);
-  uint8_t* const gt_l = lds + M2OffGt;
+  float* const b1_l = (float*)(lds + L.b1);
+  float* const b2_l = (float*)(lds + L.b2);
+  uint8_t* const gt_l = lds + L.gt;
   for (int i = tid; i < n_chunks * 32; i += 512) b1_l[i] = b1f[i];
   for (int i = tid; i < XK; i += 512) b2_l[i] = b2f[i];
   for (int i = tid; i < kGtBytes / 4; i += 512) ((uint32_t*)gt_l)[i] = ((const uint32_t*)gelu_tab)[i];
@@ -1100,8 +1171,6 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
 #pragma unroll
     for (int i = 0; i < (NA > NB ? NA : NB); ++i) issue_piece(c1, c2, slot, i);
   };
-  typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-  typedef float v2f __attribute__((ext_vector_type(2)));
 
   // Iteration i (0 .. n+1) works on ring stage i = [W1 chunk of fc1 stage i | W2 chunk of fc1 stage i-2]:
   //   A waves: MFMAs of fc1 stage i, with the GELU of stage i-1 (integer work + LDS gathers, which overlap with MFMAs
@@ -1117,44 +1186,15 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
   if (!roleB) {
     // =========================== A: x rows, fc1, GELU ======================================================
     v8bf xf[XKS];
-    uint8_t* const tp = lds + M2OffTrA + pairw * XChunk;
-    const int prow = lane >> 3;
+    uint8_t* const tp = lds + L.tr_a + pairw * XChunk;
     v16f hprev;                                      // pre-activations of stage i-1
-    uint32_t pb[8], gq[8], gres[8], gbad = 0;        // GELU state flowing from slice to slice
+    BlockState s;                                    // ... their GELU, flowing from slice to slice
     auto gelu_slice = [&](int sl, int parity) {
-      if (sl < 4) {                                  // bf16 pairs of the pre-activations (the only float work)
-        const int g = sl;
-        const v2bf lo = {(__bf16)hprev[4 * g], (__bf16)hprev[4 * g + 1]}, hi = {(__bf16)hprev[4 * g + 2], (__bf16)hprev[4 * g + 3]};
-        pb[2 * g] = *(const uint32_t*)&lo;
-        pb[2 * g + 1] = *(const uint32_t*)&hi;
-        if (sl == 0) gbad = 0;
-      }
-      if (sl >= 4 && sl < 12) {                      // table index + LDS gather of packed register sl-4
-        const int qd = sl - 4;
-        const uint32_t b0 = pb[qd] & 0xffffu, b1 = pb[qd] >> 16;
-        const uint32_t k0 = (b0 & 0x7fffu) - kGtLo, k1 = (b1 & 0x7fffu) - kGtLo;
-        gbad = max(gbad, max(k0, k1));
-        gq[2 * (qd & 3)] = *(const uint16_t*)(gt_l + min(k0, kGtN - 1) * 4 + ((b0 >> 15) << 1));
-        gq[2 * (qd & 3) + 1] = *(const uint16_t*)(gt_l + min(k1, kGtN - 1) * 4 + ((b1 >> 15) << 1));
-      }
-      if (sl >= 7 && sl < 15) {                      // three slices after the gather was issued
-        const int qd = sl - 7;
-        gres[qd] = gq[2 * (qd & 3)] | (gq[2 * (qd & 3) + 1] << 16);
-      }
-      if (sl == 15) {
-        if (__any(gbad >= kGtN)) {                   // a value outside the table somewhere in the wave: float path
-#pragma unroll
-          for (int qd = 0; qd < 8; ++qd) {
-            const v2f_t y = gelu_erf2((v2f_t){__uint_as_float(pb[qd] << 16), __uint_as_float(pb[qd] & 0xffff0000u)});
-            const v2bf o = {(__bf16)y[0], (__bf16)y[1]};
-            gres[qd] = *(const uint32_t*)&o;
-          }
-        }
-      }
+      gelu_table_slice(sl, hprev, s, gt_l);
       if (sl == 16) {                                // hand the activation tile to the partner (k-step 0, k-step 1)
-        uint8_t* const gb = lds + M2OffG + (parity * 4 + pairw) * 2048 + lane * 16;
-        *(v4u*)gb = (v4u){gres[0], gres[1], gres[2], gres[3]};
-        *(v4u*)(gb + 1024) = (v4u){gres[4], gres[5], gres[6], gres[7]};
+        uint8_t* const gb = lds + L.hand + (parity * 4 + pairw) * 2048 + lane * 16;
+        *(v4u*)gb = (v4u){s.ep[0], s.ep[1], s.ep[2], s.ep[3]};
+        *(v4u*)(gb + 1024) = (v4u){s.ep[4], s.ep[5], s.ep[6], s.ep[7]};
       }
     };
     for (int i = 0; i <= n + 1; ++i) {
@@ -1169,103 +1209,23 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
       if (do_issue && !(i < n && i > 0)) issue_stage(i + 1, slot ^ 1);
       if (i < n) {
         if (chunk == 0) {
-          const int m0w = tile * 128 + pairw * 32;
-#pragma unroll
-          for (int p = 0; p < 4; ++p) {
-            const int m = min(m0w + 8 * p + prow, M - 1);
-            const uint8_t* src = (const uint8_t*)X + (size_t)m * (XK * 2) + (lane & 7) * 16;
-#pragma unroll
-            for (int c = 0; c < XK / 64; ++c) *(v4u*)&xf[4 * c + p] = *(const v4u*)(src + c * 128);
-          }
-          const int fsw = (r >> 1) & 7;
-#pragma unroll
-          for (int c = 0; c < XK / 64; ++c) {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-              const int row = 8 * p + prow;
-              *(v4u*)(tp + row * 128 + (((lane & 7) ^ ((row >> 1) & 7)) << 4)) = *(const v4u*)&xf[4 * c + p];
-            }
-#pragma unroll
-            for (int k4 = 0; k4 < 4; ++k4)
-              xf[4 * c + k4] = *(const v8bf*)(tp + r * 128 + (((2 * k4 + h) ^ fsw) << 4));
-          }
-          auto expand = [](uint32_t u) { return (v2f){__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; };
-          v2f s2 = {0.f, 0.f};
-#pragma unroll
-          for (int ks = 0; ks < XKS; ++ks) {
-            const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s2 += expand(u[j]);
-          }
-          float sum = s2[0] + s2[1];
-          sum += __shfl_xor(sum, 32);
-          const float mean = sum * (1.0f / XK);
-          const v2f mean2 = {mean, mean};
-#pragma unroll
-          for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
-          v2f q2 = {0.f, 0.f};
-#pragma unroll
-          for (int ks = 0; ks < XKS; ++ks) {
-            const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const v2f d = expand(u[j]) - mean2; q2 = __builtin_elementwise_fma(d, d, q2); }
-          }
-          float q = q2[0] + q2[1];
-          q += __shfl_xor(q, 32);
-          const float rstd = __builtin_amdgcn_rsqf(q * (1.0f / XK) + eps);
-          const v2f rstd2 = {rstd, rstd};
-#pragma unroll
-          for (int ks = 0; ks < XKS; ++ks) asm volatile("" : "+v"(xf[ks]));
-#pragma unroll
-          for (int ks = 0; ks < XKS; ++ks) {
-            const v4u u = *(const v4u*)&xf[ks];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const v2f y = (expand(u[j]) - mean2) * rstd2;
-              xf[ks][2 * j] = (__bf16)y[0];
-              xf[ks][2 * j + 1] = (__bf16)y[1];
-            }
-          }
+          x_rows_issue(xf, X, tile * 128 + pairw * 32, M, lane);
+          x_rows_finish<true>(xf, tp, lane, eps);
         }
         const uint8_t* st = lds + slot * MStage + lane * 16;
         v16f hacc;
-        {
-          const float* bl = b1_l + chunk * 32 + 4 * h;
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const v4f bv = *(const v4f*)(bl + 8 * g);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hacc[4 * g + j] = bv[j];
-          }
-        }
-        {
-          constexpr int RD = M2ReadAhead;
-          v8bf wf[XKS];
-#pragma unroll
-          for (int ks = 0; ks < RD; ++ks) wf[ks] = *(const v8bf*)(st + ks * 1024);
-          __builtin_amdgcn_sched_barrier(0);
-          // the fc1 role is the longer one (its GELU slices and x load ride in this phase): it gets the issue priority on
-          // its SIMD — 238 -> 230 us per layer; raising the fc2 role instead loses
-          __builtin_amdgcn_s_setprio(1);
-          if (i > 0) {
-#pragma unroll
-            for (int ks = 0; ks < XKS; ++ks) {
-              hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], hacc, 0, 0, 0);
-              if (ks + RD < XKS) wf[ks + RD] = *(const v8bf*)(st + (ks + RD) * 1024);
-              gelu_slice(ks, (i - 1) & 1);
-              if (ks >= M2Issue0 && ks < M2Issue0 + NA * M2IssueStep && (ks - M2Issue0) % M2IssueStep == 0 && do_issue)
-                issue_piece(nc1, nc2, slot ^ 1, (ks - M2Issue0) / M2IssueStep);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          } else {
-#pragma unroll
-            for (int ks = 0; ks < XKS; ++ks) {
-              hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], xf[ks], hacc, 0, 0, 0);
-              if (ks + RD < XKS) wf[ks + RD] = *(const v8bf*)(st + (ks + RD) * 1024);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-        }
+        acc_from_bias(hacc, b1_l + chunk * 32, lane);
+        // the fc1 role is the longer one (its GELU slices and x load ride in this phase): it gets the issue priority on
+        // its SIMD — 238 -> 230 us per layer; raising the fc2 role instead loses
+        __builtin_amdgcn_s_setprio(1);
+        if (i > 0)
+          stage_mfmas<M2ReadAhead>(hacc, st, xf, [&](int ks) {
+            gelu_slice(ks, (i - 1) & 1);
+            if (ks >= M2Issue0 && ks < M2Issue0 + NA * M2IssueStep && (ks - M2Issue0) % M2IssueStep == 0 && do_issue)
+              issue_piece(nc1, nc2, slot ^ 1, (ks - M2Issue0) / M2IssueStep);
+          });
+        else
+          stage_mfmas<M2ReadAhead>(hacc, st, xf, [](int) {});
         __builtin_amdgcn_s_setprio(0);
         hprev = hacc;
         if (++chunk == n_chunks) { chunk = 0; tile += G; }
@@ -1280,9 +1240,7 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
     // =========================== B: fc2 accumulators, two stages behind, tile epilogue ==========================
     v16f oacc[12];
     const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(X, 0, (int)((size_t)M * XK * 2), 0x00020000);
-    const int crow = lane >> 2, cch = lane & 3;
-    const int rsw = (r >> 2) & 3;
-    uint8_t* const tr_out = lds + M2OffTrB + pairw * XChunk;
+    uint8_t* const tr_out = lds + L.tr_b + pairw * XChunk;
     uint8_t* const tr_res = tr_out + 2048;
     int pchunk = 0;                                  // chunk consumed in this iteration (that of fc1 stage i-2)
     for (int i = 0; i <= n + 1; ++i) {
@@ -1297,7 +1255,7 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
 #pragma unroll
             for (int j = 0; j < 16; ++j) oacc[ob][j] = 0.f;
         }
-        const uint8_t* gb = lds + M2OffG + ((i & 1) * 4 + pairw) * 2048 + lane * 16;   // parity of stage i-2
+        const uint8_t* gb = lds + L.hand + ((i & 1) * 4 + pairw) * 2048 + lane * 16;   // parity of stage i-2
         const v8bf g_s0 = *(const v8bf*)gb, g_s1 = *(const v8bf*)(gb + 1024);
         const uint8_t* st2 = lds + slot * MStage + XStage + lane * 16;
         {
@@ -1318,15 +1276,12 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
           const int m0w = tile * 128 + pairw * 32;
 #pragma unroll 1
           for (int ob = 0; ob < 12; ++ob) {
+            // the block-leaving steps of the shared section, as one cluster
             v4u resq[2];
 #pragma unroll
-            for (int q = 0; q < 2; ++q)
-              resq[q] = *(const v4u*)(X + (size_t)min(m0w + crow + 16 * q, M - 1) * XK + ob * 32 + cch * 8);
+            for (int q = 0; q < 2; ++q) resq[q] = res_load(X, m0w, M, XK, ob * 32, lane, q);
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              const int row = crow + 16 * q;
-              *(v4u*)(tr_res + row * 64 + ((cch ^ ((row >> 2) & 3)) << 4)) = resq[q];
-            }
+            for (int q = 0; q < 2; ++q) res_write(tr_res, resq[q], lane, q);
             v16f oa;
             switch (ob) {   // dynamic index into the register tiles
 #define VC_OB(k) case k: oa = oacc[k]; break;
@@ -1337,29 +1292,17 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
             uint32_t ep[8];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-              const v4bf rv = *(const v4bf*)(tr_res + r * 64 + ((g ^ rsw) << 4) + 8 * h);
-              const v4f bv = *(const v4f*)(b2_l + ob * 32 + 8 * g + 4 * h);
+              const v4bf rv = res_read(tr_res, lane, g);
+              const v4f bv = *(const v4f*)(b2_l + ob * 32 + 8 * g + 4 * (lane >> 5));
               float v[4];
 #pragma unroll
               for (int j = 0; j < 4; ++j) v[j] = oa[4 * g + j] + bv[j] + (float)rv[j];
-              const v2bf lo = {(__bf16)v[0], (__bf16)v[1]}, hi = {(__bf16)v[2], (__bf16)v[3]};
-              ep[2 * g] = *(const uint32_t*)&lo;
-              ep[2 * g + 1] = *(const uint32_t*)&hi;
+              pack_group(ep, g, v[0], v[1], v[2], v[3]);
             }
+            half_swap(ep);
+            tr_write(tr_out, ep, lane);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const auto sw = __builtin_amdgcn_permlane32_swap(ep[k], ep[k + 4], false, false);
-              ep[k] = sw[0];
-              ep[k + 4] = sw[1];
-            }
-            *(v4u*)(tr_out + r * 64 + (((2 * h) ^ rsw) << 4)) = (v4u){ep[0], ep[1], ep[4], ep[5]};
-            *(v4u*)(tr_out + r * 64 + (((2 * h + 1) ^ rsw) << 4)) = (v4u){ep[2], ep[3], ep[6], ep[7]};
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              const int row = crow + 16 * q;
-              const v4u o = *(const v4u*)(tr_out + row * 64 + ((cch ^ ((row >> 2) & 3)) << 4));
-              __builtin_amdgcn_raw_buffer_store_b128(o, out_rs, (int)(((size_t)(m0w + row) * XK + ob * 32 + cch * 8) * 2), 0, 0);
-            }
+            for (int q = 0; q < 2; ++q) block_store(tr_read(tr_out, lane, q), out_rs, m0w, XK, ob * 32, lane, q);
           }
           tile += G;
         }
@@ -1381,16 +1324,7 @@ __global__ __launch_bounds__(256) void mlp_prepare_kernel(const float* __restric
   const int lane = threadIdx.x & 63;
   const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);   // hidden feature (fc1 part), then output feature (fc2 part)
   if (unit < n_hid) {
-    const int c = unit >> 5, rr = unit & 31;
-    float dot = 0.f;
-    for (int k = lane; k < XK; k += 64) {
-      const float w = W1[(size_t)unit * XK + k];
-      if (beta) dot += w * beta[k];
-      const int ks = k >> 4, hh = (k >> 3) & 1, j = k & 7;
-      Wm[(size_t)c * (MStage / 2) + ((size_t)ks * 64 + hh * 32 + rr) * 8 + j] = (__bf16)(gamma ? w * gamma[k] : w);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+    const float dot = fc1_row_to_fragments(W1 + (size_t)unit * XK, gamma, beta, Wm + (size_t)(unit >> 5) * (MStage / 2), unit & 31, lane);
     if (lane == 0) b1f[unit] = (b1 ? b1[unit] : 0.f) + dot;
   } else if (unit < n_hid + XK) {
     const int f = unit - n_hid, ob = f >> 5, rr = f & 31;
@@ -1406,11 +1340,26 @@ __global__ __launch_bounds__(256) void mlp_prepare_kernel(const float* __restric
 
 }  // namespace
 
-// Rows per launch of a kernel whose result store addresses 32-bit byte offsets from the output base: the largest multiple of
-// `tile_rows` whose [rows][n_cols] bf16 output stays below 2 GiB.
-static int max_rows_below_2gib(int n_cols, int tile_rows) {
-  const long long r = ((1LL << 31) - 1) / ((long long)n_cols * 2);
-  return (int)(r / tile_rows * tile_rows);
+// ---- host helpers of the entry points -----------------------------------------------------------------------------------
+// Every pointer a kernel reads or writes with 16-byte accesses (a null optional pointer passes).
+template <typename... P>
+static bool aligned16(const P*... p) {
+  return ((uintptr_t)0 | ... | (uintptr_t)p) % 16 == 0;
+}
+
+// Grid of a persistent kernel: one workgroup per CU, fewer when there is less work.
+static unsigned persistent_grid(long long work_items, int cus) { return (unsigned)(work_items < cus ? work_items : cus); }
+
+// xs_kernel and mlp2_kernel store their results through a buffer resource with a 32-bit record count and 32-bit byte
+// offsets: one launch writes less than 2 GiB of output, so a call is split into launches over consecutive row ranges, each
+// the largest multiple of `tile_rows` whose [rows][n_cols] bf16 output stays below 2 GiB.  launch(first row, rows) -> status.
+template <typename F>
+static int for_row_ranges(long long rows, int n_cols, int tile_rows, F&& launch) {
+  const int chunk = (int)(((1LL << 31) - 1) / ((long long)n_cols * 2) / tile_rows * tile_rows);
+  for (long long r0 = 0; r0 < rows; r0 += chunk) {
+    if (int st = launch(r0, (int)(rows - r0 < chunk ? rows - r0 : chunk))) return st;
+  }
+  return VC_OK;
 }
 
 extern "C" {
@@ -1423,8 +1372,7 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
   if ((epilogue == EPI_RESIDUAL) != (residual_or_null != nullptr)) return VC_ERR_INVALID_ARG;
   // EPI_SWIGLU: a tile of either form holds the gate and the value half of its output columns, 128 product columns at least
   if (n_out % (epilogue == EPI_SWIGLU ? 2 * BN : BN) != 0 || k_in % BK != 0) return VC_ERR_UNSUPPORTED;
-  if ((((uintptr_t)x) | ((uintptr_t)weight) | ((uintptr_t)bias) | ((uintptr_t)residual_or_null) | ((uintptr_t)out)) % 16 != 0)
-    return VC_ERR_INVALID_ARG;
+  if (!aligned16(x, weight, bias, residual_or_null, out)) return VC_ERR_INVALID_ARG;
   if (rows == 0) return VC_OK;
   hipStream_t s = (hipStream_t)stream;
   const __bf16 *px = (const __bf16*)x, *pw = (const __bf16*)weight, *pb = (const __bf16*)bias,
@@ -1439,10 +1387,10 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
     const long long nt = (long long)tiles_m * tiles_n;
     if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
     static vc::PerDeviceOnce configured;
-    if (int st = vc::allow_dynamic_lds(configured, 160 * 1024, gemm256_kernel<EPI_BIAS, false>, gemm256_kernel<EPI_GELU, false>,
+    if (int st = vc::allow_dynamic_lds(configured, G256_LDS, gemm256_kernel<EPI_BIAS, false>, gemm256_kernel<EPI_GELU, false>,
                                        gemm256_kernel<EPI_RESIDUAL, false>, gemm256_kernel<EPI_SWIGLU, false>))
       return st;
-    const dim3 grid((unsigned)(nt < cus ? nt : cus)), block(512);
+    const dim3 grid(persistent_grid(nt, cus)), block(512);
     return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_SWIGLU>(epilogue, [&](auto epi) {
       hipLaunchKernelGGL((gemm256_kernel<epi, false>), grid, block, (size_t)G256_LDS, s, px, pw, pb, pr, po, rows, n_out, k_in,
                          tiles_n, (int)nt, 0, 0, 0, 1, 0, 0, -1);
@@ -1466,7 +1414,7 @@ int vc_conv_taps_bf16(void* x, const void* weight, const void* bias, void* out, 
   if (kh <= 0 || kw <= 0 || kh * kw > 16 || dy0 < -8 || dy0 > 8 || dx0 < -8 || dx0 > 8) return VC_ERR_INVALID_ARG;
   if (out_parity < -1 || out_parity > 3) return VC_ERR_INVALID_ARG;
   if (n_out % G2N != 0 || c_in % BK != 0) return VC_ERR_UNSUPPORTED;
-  if ((((uintptr_t)x) | ((uintptr_t)weight) | ((uintptr_t)bias) | ((uintptr_t)out)) % 16 != 0) return VC_ERR_INVALID_ARG;
+  if (!aligned16(x, weight, bias, out)) return VC_ERR_INVALID_ARG;
   const long long rows = (long long)batch * height * width;
   if (rows == 0) return VC_OK;
   // per-lane offsets are 32-bit: the image batch, its zero row and the largest tap shift must stay below 4 GiB
@@ -1478,11 +1426,11 @@ int vc_conv_taps_bf16(void* x, const void* weight, const void* bias, void* out, 
   const long long nt = (long long)tiles_m * tiles_n;
   if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;
   static vc::PerDeviceOnce configured;
-  if (int st = vc::allow_dynamic_lds(configured, 160 * 1024, gemm256_kernel<EPI_BIAS, true>, gemm256_kernel<EPI_GELU, true>))
+  if (int st = vc::allow_dynamic_lds(configured, G256_LDS, gemm256_kernel<EPI_BIAS, true>, gemm256_kernel<EPI_GELU, true>))
     return st;
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
-  const dim3 grid((unsigned)(nt < cus ? nt : cus)), block(512);
+  const dim3 grid(persistent_grid(nt, cus)), block(512);
   const __bf16 *px = (const __bf16*)x, *pw = (const __bf16*)weight, *pb = (const __bf16*)bias;
   __bf16* po = (__bf16*)out;
   return vc::dispatch<EPI_BIAS, EPI_GELU>(epilogue, [&](auto epi) {
@@ -1502,7 +1450,7 @@ int vc_linear_xs_prepare(const float* weight, const float* bias_or_null, const f
                          const float* ln_beta_or_null, int n_out, int k_in, void* weight_tiled, float* bias_folded,
                          vc_stream_t stream) {
   if (!weight || !weight_tiled || !bias_folded || n_out <= 0) return VC_ERR_INVALID_ARG;
-  if (k_in != XK || n_out % 32 != 0 || n_out > XMaxN) return VC_ERR_UNSUPPORTED;
+  if (k_in != XK || n_out % 32 != 0 || !xs_lds().bias_fits(n_out)) return VC_ERR_UNSUPPORTED;
   if ((ln_gamma_or_null == nullptr) != (ln_beta_or_null == nullptr)) return VC_ERR_INVALID_ARG;
   hipLaunchKernelGGL(xs_prepare_kernel, dim3((n_out + 3) / 4), dim3(256), 0, (hipStream_t)stream, weight, bias_or_null,
                      ln_gamma_or_null, ln_beta_or_null, n_out, (__bf16*)weight_tiled, bias_folded);
@@ -1512,7 +1460,7 @@ int vc_linear_xs_prepare(const float* weight, const float* bias_or_null, const f
 size_t vc_gelu_table_bytes(void) { return (size_t)kGtBytes; }
 
 int vc_gelu_table_bf16(void* table, vc_stream_t stream) {
-  if (!table || ((uintptr_t)table) % 16 != 0) return VC_ERR_INVALID_ARG;
+  if (!table || !aligned16(table)) return VC_ERR_INVALID_ARG;
   hipLaunchKernelGGL(gelu_table_kernel, dim3((kGtN * 2 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (uint16_t*)table);
   return vc::check_launch();
 }
@@ -1523,9 +1471,8 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
   if (!x || !weight_tiled || !bias_folded || !out || rows < 0 || n_out <= 0) return VC_ERR_INVALID_ARG;
   if (epilogue < EPI_BIAS || epilogue > EPI_RESIDUAL) return VC_ERR_INVALID_ARG;
   if ((epilogue == EPI_RESIDUAL) != (residual_or_null != nullptr)) return VC_ERR_INVALID_ARG;
-  if (k_in != XK || n_out % 32 != 0 || n_out > XMaxN) return VC_ERR_UNSUPPORTED;
-  if ((((uintptr_t)x) | ((uintptr_t)weight_tiled) | ((uintptr_t)bias_folded) | ((uintptr_t)residual_or_null) | ((uintptr_t)out)) % 16 != 0)
-    return VC_ERR_INVALID_ARG;
+  if (k_in != XK || n_out % 32 != 0 || !xs_lds().bias_fits(n_out)) return VC_ERR_UNSUPPORTED;
+  if (!aligned16(x, weight_tiled, bias_folded, residual_or_null, out)) return VC_ERR_INVALID_ARG;
   if (rows == 0) return VC_OK;
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
@@ -1533,16 +1480,11 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
   hipStream_t s = (hipStream_t)stream;
   const uint8_t* pw = (const uint8_t*)weight_tiled;
   const uint16_t* gt = (const uint16_t*)gelu_table_or_null;
-  if (gt && (((uintptr_t)gt) % 16 != 0)) return VC_ERR_INVALID_ARG;
-  // the table shares the 16 KiB staging area with the bias
-  const bool use_gt = gt && epilogue == EPI_GELU && ((n_out * 4 + 15) & ~15) + kGtBytes <= XMaxN * 4;
-  // The kernel stores its results through a buffer resource with a 32-bit record count and 32-bit byte offsets: one launch
-  // writes less than 2 GiB of output, a longer call is split into launches over consecutive row ranges.
-  const int chunk = max_rows_below_2gib(n_out, XRows);
-  for (long long r0 = 0; r0 < rows; r0 += chunk) {
-    const int m = (int)(rows - r0 < chunk ? rows - r0 : chunk);
+  if (!aligned16(gt)) return VC_ERR_INVALID_ARG;
+  const bool use_gt = gt && epilogue == EPI_GELU && xs_lds().table_fits(n_out);   // (the table shares an LDS area with the bias)
+  return for_row_ranges(rows, n_out, XRows, [&](long long r0, int m) {
     const int stages = (m + XRows - 1) / XRows * n_nb;
-    const dim3 grid((unsigned)(stages < cus ? stages : cus)), block(512);
+    const dim3 grid(persistent_grid(stages, cus)), block(512);
     const __bf16* px = (const __bf16*)x + (size_t)r0 * XK;
     const __bf16* pr = residual_or_null ? (const __bf16*)residual_or_null + (size_t)r0 * n_out : nullptr;
     __bf16* po = (__bf16*)out + (size_t)r0 * n_out;
@@ -1551,7 +1493,7 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
                          ln_eps, gt);
       return vc::check_launch();
     };
-    const int st = vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
+    return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
       return vc::dispatch<true, false>(fuse_layernorm != 0, [&](auto ln) {
         if constexpr (epi == EPI_GELU) {   // only the GELU epilogue has a table variant
           if (use_gt) return launch(epi, ln, std::true_type{});
@@ -1559,9 +1501,7 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
         return launch(epi, ln, std::false_type{});
       });
     });
-    if (st != VC_OK) return st;
-  }
-  return VC_OK;
+  });
 }
 
 
@@ -1570,8 +1510,7 @@ int vc_patch_embed_bf16(const void* patches, const void* weight, const void* bia
   if (!patches || !weight || !bias || !pos_embed || !out || n_images < 0 || tokens <= 0 || n_out <= 0 || k_in <= 0)
     return VC_ERR_INVALID_ARG;
   if (n_out % BN != 0 || k_in % BK != 0) return VC_ERR_UNSUPPORTED;
-  if ((((uintptr_t)patches) | ((uintptr_t)weight) | ((uintptr_t)bias) | ((uintptr_t)pos_embed) | ((uintptr_t)out)) % 16 != 0)
-    return VC_ERR_INVALID_ARG;
+  if (!aligned16(patches, weight, bias, pos_embed, out)) return VC_ERR_INVALID_ARG;
   if (n_images == 0) return VC_OK;
   const long long rows = (long long)n_images * tokens;
   const long long nt = ((rows + BM - 1) / BM) * (n_out / BN);
@@ -1584,7 +1523,7 @@ int vc_patch_embed_bf16(const void* patches, const void* weight, const void* bia
 
 
 size_t vc_mlp_weight_bytes(int n_hidden, int dim) {
-  if (dim != XK || n_hidden <= 0 || n_hidden % 32 != 0 || n_hidden > 1536) return 0;
+  if (dim != XK || n_hidden <= 0 || n_hidden % 32 != 0 || n_hidden > mlp_lds().max_hidden()) return 0;
   return (size_t)(n_hidden / 32) * MStage;
 }
 
@@ -1603,22 +1542,16 @@ int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded
                 int rows, int n_hidden, int dim, float ln_eps, vc_stream_t stream) {
   if (!x_inout || !weights_tiled || !b1_folded || !b2 || !gelu_table || rows < 0) return VC_ERR_INVALID_ARG;
   if (vc_mlp_weight_bytes(n_hidden, dim) == 0) return VC_ERR_UNSUPPORTED;
-  if ((((uintptr_t)x_inout) | ((uintptr_t)weights_tiled) | ((uintptr_t)b1_folded) | ((uintptr_t)b2) | ((uintptr_t)gelu_table)) % 16 != 0)
-    return VC_ERR_INVALID_ARG;
+  if (!aligned16(x_inout, weights_tiled, b1_folded, b2, gelu_table)) return VC_ERR_INVALID_ARG;
   if (rows == 0) return VC_OK;
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
-  // 32-bit buffer offsets in the result store, as in vc_linear_xs_bf16: launches of less than 2 GiB of rows each
-  const int chunk = max_rows_below_2gib(XK, 128);
-  for (long long r0 = 0; r0 < rows; r0 += chunk) {
-    const int m = (int)(rows - r0 < chunk ? rows - r0 : chunk);
+  return for_row_ranges(rows, XK, 128, [&](long long r0, int m) {
     const int n_tiles = (m + 127) / 128;
-    const dim3 grid((unsigned)(n_tiles < cus ? n_tiles : cus));
-    hipLaunchKernelGGL(mlp2_kernel, grid, dim3(512), 0, (hipStream_t)stream, (__bf16*)x_inout + (size_t)r0 * XK,
+    hipLaunchKernelGGL(mlp2_kernel, dim3(persistent_grid(n_tiles, cus)), dim3(512), 0, (hipStream_t)stream, (__bf16*)x_inout + (size_t)r0 * XK,
                        (const uint8_t*)weights_tiled, b1_folded, b2, m, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
-    if (int st = vc::check_launch()) return st;
-  }
-  return VC_OK;
+    return vc::check_launch();
+  });
 }
 
 }  // extern "C"

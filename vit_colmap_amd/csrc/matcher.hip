@@ -255,16 +255,8 @@ constexpr int kMaxPad = tiles_of(VC_MAX_KEYPOINTS) * kTile;   // rows of the lar
 
 // The dynamic LDS of a pair kernel is laid out ONCE, by a constexpr plan that both sides use: the kernel takes every
 // pointer from it, the host the fixed size (the plan with an empty ring), from that the number of ring slots, and the
-// launch's LDS size (`end`).  LdsCursor hands out consecutive regions; all offsets are in bytes from the start of LDS.
-struct LdsCursor {
-  u32 at;
-  __host__ __device__ constexpr u32 take(u32 bytes, u32 align = 4) {
-    at = (at + align - 1) / align * align;
-    const u32 off = at;
-    at += bytes;
-    return off;
-  }
-};
+// launch's LDS size (`end`).  vc::LdsCursor hands out consecutive regions; all offsets are in bytes from the start of LDS.
+using vc::LdsCursor;
 // pair_kernel:      [ring NS x KS KiB][colbest u64 x n_pad][colsecond u32 x n_pad]
 //                   [cterm i32 x n_pad][m21 i32 x n_pad][rbest, rsecond, ridx i32 x n_pad]
 //                   [crow6 i32 x 8 waves x 64 rows][row-reduce scratch 8 waves x 4224 B][wave_count 8 ints]
