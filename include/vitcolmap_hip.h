@@ -251,6 +251,44 @@ int vc_absolute_pose_inliers(const float* obs, const float* xyz4, const int32_t*
                              float max_error, uint8_t* out_mask, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Track triangulation: one 3D point per track of observations under known camera poses, every
+ * track in one launch, one track per lane, float64 in single operations in the specification's order
+ * (tests/util_mapper.py; the only library call is sqrt).  This build's own published rule: parity with COLMAP's triangulator
+ * is unpinned.
+ *   obs_xy     [total][2] float64 pixels
+ *   obs_cam    [total] int32: the observation's slot into cams
+ *   offsets    [n_tracks + 1] int32: track t owns rows offsets[t] .. offsets[t+1]) of the per-observation arrays, in any
+ *              order and of any length; a negative or descending pair of offsets rejects the track and nothing of it is read
+ *   cams       [n_cams][16] float64: R row-major (9), t (3), fx, fy, cx, cy; X_cam = R X + t.  A row with a non-finite entry is
+ *              an image that is not registered.  NULL only with n_cams 0
+ *   seeds      [n_tracks] int32, read as 32 unsigned bits: the sampler's seed of a track of 12 or more observations
+ *   max_error_px, min_tri_angle_tan2   the inlier threshold and tan^2 of the least angle between two rays at the point
+ *   out_xyz    [n_tracks][3] float64, NaN where the track is rejected
+ *   out_mask   [total] uint8: the inlier observations; a track writes its own rows only, 0 where it is rejected
+ *   out_count  [n_tracks] int32: the inliers, 0 where rejected
+ *   out_error  [n_tracks] float64: the mean pixel error of the inliers, NaN where rejected
+ * The rule for a track of n observations:
+ *   usable      an observation whose slot is in [0, n_cams), whose camera row and pixel are finite; any other is never an
+ *               inlier and never part of a hypothesis
+ *   hypotheses  pairs (p, q), p < q, of observation indices: all in lexicographic order while n (n - 1) / 2 <= 64; otherwise
+ *               64 pairs, p = lowbias32(seed * 0x9E3779B1 + h * 0x85EBCA6B + 0xC3C3C3C3) mod n,
+ *               q = (p + 1 + lowbias32(the same argument + 0xC2B2AE35) mod (n - 1)) mod n, swapped so that p < q (32-bit)
+ *   one of them the midpoint of the rays c + s d, d = R' ((u - cx) / fx, (v - cy) / fy, 1), c = -R' t, valid iff both depths
+ *               s, r are finite and positive and the parallax test passes at X for the two centres: with g = X - c_p,
+ *               h = X - c_q, g.h <= 0 or |g x h|^2 >= min_tri_angle_tan2 (g.h)^2
+ *   inlier      Xc = R X + t; Xc_z > 0 and (fx Xc_x + cx Xc_z - u Xc_z)^2 + (fy Xc_y + cy Xc_z - v Xc_z)^2 <= e^2 Xc_z^2; a
+ *               hypothesis counts only if p and q are inliers; most inliers win, the lowest index on ties
+ *   refit       at most 10 Gauss-Newton steps on X over the winner's inliers (3x3 normal equations by the adjugate), a step
+ *               kept only if it lowers the cost, the first one not kept ends it; taken iff finite with no fewer inliers
+ *   accepted    at least two inliers, some pair of which passes the parallax test at the final X
+ * n_tracks == 0: VC_OK whatever the pointers are.  A null pointer, a negative size, a threshold that is negative or not
+ * finite: VC_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------------------------ */
+int vc_triangulate_tracks(const double* obs_xy, const int32_t* obs_cam, const int32_t* offsets, int n_tracks, const double* cams,
+                          int n_cams, const int32_t* seeds, double max_error_px, double min_tri_angle_tan2, double* out_xyz,
+                          uint8_t* out_mask, int32_t* out_count, double* out_error, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

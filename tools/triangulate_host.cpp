@@ -1,0 +1,78 @@
+// The track triangulation of vit_colmap_amd/csrc/triangulate.hip on the CPU: triangulate_track is __host__ __device__, so
+// this program includes the kernel source and calls it on one track after another.  It is how the kernel's arithmetic is
+// compared with the specification without a GPU (tests/test_mapper_spec.py; TOL_X of tests/util_mapper.py was measured with
+// it), how it is run under a host sanitizer and where a fault in it is looked for with a host debugger.  tools/p3p_host.cpp
+// is its counterpart for csrc/absolute_pose.hip.
+//
+//   hipcc -x hip --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -o triangulate_host tools/triangulate_host.cpp
+//   ./triangulate_host tracks.bin points.bin
+// tracks.bin: int32 n_tracks, n_cams, total; float64 max_error_px, min_tri_angle_tan2; int32 offsets (n_tracks + 1), seeds
+// (n_tracks), obs_cam (total); float64 obs_xy (total, 2), cams (n_cams, 16).  points.bin: float64 xyz (n_tracks, 3), error
+// (n_tracks); int32 count (n_tracks); uint8 mask (total).  Offsets that do not ascend from 0 to total are refused.
+#include <cstdio>
+#include <vector>
+
+#include "../vit_colmap_amd/csrc/triangulate.hip"
+
+template <typename T>
+static bool read_all(std::FILE* f, std::vector<T>& v) {
+  return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
+}
+
+int main(int argc, char** argv) {
+  if (argc != 3) {
+    std::fprintf(stderr, "usage: %s tracks.bin points.bin\n", argv[0]);
+    return 2;
+  }
+  std::FILE* in = std::fopen(argv[1], "rb");
+  if (!in) {
+    std::fprintf(stderr, "cannot open %s\n", argv[1]);
+    return 2;
+  }
+  int32_t head[3];
+  double thr[2];
+  if (std::fread(head, sizeof(int32_t), 3, in) != 3 || std::fread(thr, sizeof(double), 2, in) != 2 || head[0] < 0 || head[1] < 0 ||
+      head[2] < 0) {
+    std::fprintf(stderr, "%s: no header\n", argv[1]);
+    return 2;
+  }
+  const int n_tracks = head[0], n_cams = head[1], total = head[2];
+  std::vector<int32_t> offsets(n_tracks + 1), seeds(n_tracks), obs_cam(total);
+  std::vector<double> obs_xy(2 * (size_t)total), cams(16 * (size_t)n_cams);
+  const bool ok = read_all(in, offsets) && read_all(in, seeds) && read_all(in, obs_cam) && read_all(in, obs_xy) && read_all(in, cams);
+  std::fclose(in);
+  if (!ok) {
+    std::fprintf(stderr, "%s: shorter than its header says\n", argv[1]);
+    return 2;
+  }
+  bool ascending = offsets[0] == 0 && offsets[n_tracks] == total;
+  for (int t = 0; t < n_tracks; ++t) ascending = ascending && offsets[t] <= offsets[t + 1];
+  if (!ascending) {
+    std::fprintf(stderr, "%s: the offsets do not ascend from 0 to %d\n", argv[1], total);
+    return 2;
+  }
+  std::vector<double> xyz(3 * (size_t)n_tracks), error(n_tracks);
+  std::vector<int32_t> count(n_tracks);
+  std::vector<uint8_t> mask(total);
+  const Tracks d{obs_xy.data(), obs_cam.data(), cams.data(), n_cams};
+  long accepted = 0;
+  for (int t = 0; t < n_tracks; ++t) {
+    double X[3];
+    count[t] = triangulate_track(d, offsets[t], offsets[t + 1] - offsets[t], (uint32_t)seeds[t], thr[0], thr[1], X,
+                                 mask.data() + offsets[t], error[t]);
+    xyz[3 * t] = X[0], xyz[3 * t + 1] = X[1], xyz[3 * t + 2] = X[2];
+    accepted += count[t] > 0;
+  }
+  std::FILE* out = std::fopen(argv[2], "wb");
+  if (!out) {
+    std::fprintf(stderr, "cannot open %s\n", argv[2]);
+    return 2;
+  }
+  std::fwrite(xyz.data(), sizeof(double), xyz.size(), out);
+  std::fwrite(error.data(), sizeof(double), error.size(), out);
+  std::fwrite(count.data(), sizeof(int32_t), count.size(), out);
+  std::fwrite(mask.data(), 1, mask.size(), out);
+  std::fclose(out);
+  std::printf("%d tracks, %ld accepted\n", n_tracks, accepted);
+  return 0;
+}

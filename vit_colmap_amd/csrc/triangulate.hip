@@ -1,0 +1,325 @@
+// Track triangulation (gfx950): one 3D point per track of observations under known camera poses, every
+// track of a call in one launch.  vc_triangulate_tracks is what a mapper repeats after every registration round
+// (vit_colmap_amd/mapping/grow.py).  Specification: tests/util_mapper.py (`triangulate_track`).  This build's own published
+// rule; parity with COLMAP's triangulator is unpinned.
+//
+// float64, one track per lane, one wave per workgroup, no LDS, no barrier, no atomics.  Per track of n observations:
+//   1. hypotheses   pairs (p, q), p < q, of observation indices: every pair in lexicographic order while n (n - 1) / 2 <= 64,
+//                   otherwise 64 pairs drawn by the published hash (lowbias32, the sampler's constants, SALT_T)
+//   2. one of them  the midpoint of the two rays (§4.2g between two arbitrary cameras) with positive depths on both and
+//                   enough parallax at the point; counted over every usable observation by the division-free pixel test of
+//                   §4.2i in float64; it counts only if p and q are inliers themselves; most inliers win, the lowest index on ties
+//   3. refit        at most kRefitSteps Gauss-Newton steps on X over the winner's inliers, 3x3 normal equations accumulated in
+//                   observation order and solved by the adjugate; a step is kept only if it lowers the cost, the first one
+//                   not kept ends it; the refit is taken iff it is finite and has no fewer inliers
+//   4. acceptance   at least two inliers, of which some pair passes the parallax test at the final X
+// Nothing is kept per observation: an observation and its camera row are read again wherever they are needed (a track is
+// short and its rows stay in cache), so a lane holds three observations at most and no array has a run-time index.  Every
+// loop but those over observations, hypotheses and refit steps is fully unrolled.  Angles are tested without trigonometry
+// and the only library call is sqrt, so the host build of triangulate_track (tools/triangulate_host.cpp includes this file)
+// and the device agree; what a lane computes is sequential, so two launches return the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/vitcolmap_hip.h"
+#include "common.h"
+
+namespace {
+
+constexpr int kTriWave = 64;
+constexpr int kTriMaxHypotheses = 64;
+constexpr int kRefitSteps = 10;                 // TRI_REFIT_STEPS
+constexpr uint32_t kSaltT = 0xC3C3C3C3u;        // SALT["T"] of matching/_common.py
+
+struct Tracks {
+  const double* __restrict__ obs_xy;
+  const int32_t* __restrict__ obs_cam;
+  const double* __restrict__ cams;
+  int n_cams;
+};
+
+// One observation with its camera: R row-major, t, fx, fy, cx, cy (X_cam = R X + t), the pixel (u, v).
+struct View {
+  double R[9], t[3], fx, fy, cx, cy, u, v;
+  bool ok;
+};
+
+__host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
+__host__ __device__ __forceinline__ bool is_finite(double x) { return fabs(x) < INFINITY; }   // false for NaN
+
+// Observation i of the call.  Unusable (ok = false): a slot outside [0, n_cams), a camera row or a pixel that is not finite.
+__host__ __device__ __forceinline__ void load_view(const Tracks& d, long long i, View& w) {
+  const int slot = d.obs_cam[i];
+  w.ok = slot >= 0 && slot < d.n_cams;
+  const double* c = d.cams + (long long)(w.ok ? slot : 0) * 16;
+  double row[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    row[k] = w.ok ? c[k] : NAN;
+    w.ok = w.ok && is_finite(row[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) w.R[k] = row[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) w.t[k] = row[9 + k];
+  w.fx = row[12], w.fy = row[13], w.cx = row[14], w.cy = row[15];
+  w.u = d.obs_xy[2 * i], w.v = d.obs_xy[2 * i + 1];
+  w.ok = w.ok && is_finite(w.u) && is_finite(w.v);
+}
+
+__host__ __device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) {
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+
+__host__ __device__ __forceinline__ void centre_of(const View& w, double (&c)[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) c[k] = -(w.R[k] * w.t[0] + w.R[3 + k] * w.t[1] + w.R[6 + k] * w.t[2]);
+}
+
+// The ray of a view in the world: direction d = R' x with x = ((u - cx) / fx, (v - cy) / fy, 1), centre c = -R' t.
+__host__ __device__ __forceinline__ void ray_of(const View& w, double (&d)[3], double (&c)[3]) {
+  const double x = (w.u - w.cx) / w.fx, y = (w.v - w.cy) / w.fy;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[k] = w.R[k] * x + w.R[3 + k] * y + w.R[6 + k];
+  centre_of(w, c);
+}
+
+// The parallax at X between the centres cp and cq: the angle between X - cp and X - cq is obtuse, or tan^2 of it reaches tan2.
+__host__ __device__ __forceinline__ bool parallax(const double (&X)[3], const double (&cp)[3], const double (&cq)[3], double tan2) {
+  const double g[3] = {X[0] - cp[0], X[1] - cp[1], X[2] - cp[2]}, h[3] = {X[0] - cq[0], X[1] - cq[1], X[2] - cq[2]};
+  const double gh = dot3(g, h);
+  const double k[3] = {g[1] * h[2] - g[2] * h[1], g[2] * h[0] - g[0] * h[2], g[0] * h[1] - g[1] * h[0]};
+  return gh <= 0.0 || dot3(k, k) >= tan2 * (gh * gh);       // false for NaN
+}
+
+__host__ __device__ __forceinline__ void to_camera(const View& w, const double (&X)[3], double (&Xc)[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Xc[i] = w.R[3 * i] * X[0] + w.R[3 * i + 1] * X[1] + w.R[3 * i + 2] * X[2] + w.t[i];
+}
+
+// The division-free pixel test; sq: the squared pixel error times Xc_z^2.
+__host__ __device__ __forceinline__ bool inlier(const View& w, const double (&X)[3], double e2, double& sq, double& z) {
+  double Xc[3];
+  to_camera(w, X, Xc);
+  z = Xc[2];
+  const double a = w.fx * Xc[0] + w.cx * z - w.u * z;
+  const double b = w.fy * Xc[1] + w.cy * z - w.v * z;
+  sq = a * a + b * b;
+  return w.ok && z > 0.0 && sq <= e2 * (z * z);              // false for NaN
+}
+
+__host__ __device__ __forceinline__ int count_inliers(const Tracks& d, long long lo, int n, const double (&X)[3], double e2) {
+  int count = 0;
+  for (int i = 0; i < n; ++i) {
+    View w;
+    double sq, z;
+    load_view(d, lo + i, w);
+    count += inlier(w, X, e2, sq, z) ? 1 : 0;
+  }
+  return count;
+}
+
+// The midpoint of the rays of p and q -> X; false when a depth is not finite and positive or the parallax is too small.
+__host__ __device__ __forceinline__ bool midpoint(const View& p, const View& q, double tan2, double (&X)[3]) {
+  double dp[3], cp[3], dq[3], cq[3];
+  ray_of(p, dp, cp);
+  ray_of(q, dq, cq);
+  const double e[3] = {cq[0] - cp[0], cq[1] - cp[1], cq[2] - cp[2]};
+  const double aa = dot3(dp, dp), ab = dot3(dp, dq), bb = dot3(dq, dq), ae = dot3(dp, e), be = dot3(dq, e);
+  const double det = aa * bb - ab * ab;
+  const double s = (bb * ae - ab * be) / det, r = (ab * ae - aa * be) / det;
+  if (!(s > 0.0 && r > 0.0 && s < INFINITY && r < INFINITY)) return false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) X[k] = 0.5 * (cp[k] + s * dp[k] + cq[k] + r * dq[k]);
+  return parallax(X, cp, cq, tan2);
+}
+
+// Sum over the observations that are inliers of X0 of the squared pixel error at X (the set does not move with X).
+__host__ __device__ __forceinline__ double refit_cost(const Tracks& d, long long lo, int n, const double (&X0)[3], double e2,
+                                                      const double (&X)[3]) {
+  double cost = 0.0;
+  for (int i = 0; i < n; ++i) {
+    View w;
+    double sq, z, Xc[3];
+    load_view(d, lo + i, w);
+    if (!inlier(w, X0, e2, sq, z)) continue;
+    to_camera(w, X, Xc);
+    const double iz = 1.0 / Xc[2];
+    const double ru = w.fx * Xc[0] * iz + w.cx - w.u, rv = w.fy * Xc[1] * iz + w.cy - w.v;
+    cost += ru * ru + rv * rv;
+  }
+  return cost;
+}
+
+// Gauss-Newton on X over the inliers of X0, from X0.
+__host__ __device__ __forceinline__ void refit(const Tracks& d, long long lo, int n, const double (&X0)[3], double e2, double (&X)[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) X[k] = X0[k];
+  double cost = refit_cost(d, lo, n, X0, e2, X);
+  for (int it = 0; it < kRefitSteps; ++it) {
+    double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
+    for (int i = 0; i < n; ++i) {
+      View w;
+      double sq, z, Xc[3];
+      load_view(d, lo + i, w);
+      if (!inlier(w, X0, e2, sq, z)) continue;
+      to_camera(w, X, Xc);
+      const double iz = 1.0 / Xc[2];
+      const double ru = w.fx * Xc[0] * iz + w.cx - w.u, rv = w.fy * Xc[1] * iz + w.cy - w.v;
+      const double xu = Xc[0] * iz, xv = Xc[1] * iz, fu = w.fx * iz, fv = w.fy * iz;
+      // d ru / d X = fx / z (R row 0 - x / z R row 2), d rv / d X = fy / z (R row 1 - y / z R row 2)
+      const double ju[3] = {fu * (w.R[0] - xu * w.R[6]), fu * (w.R[1] - xu * w.R[7]), fu * (w.R[2] - xu * w.R[8])};
+      const double jv[3] = {fv * (w.R[3] - xv * w.R[6]), fv * (w.R[4] - xv * w.R[7]), fv * (w.R[5] - xv * w.R[8])};
+      A00 += ju[0] * ju[0] + jv[0] * jv[0], A01 += ju[0] * ju[1] + jv[0] * jv[1], A02 += ju[0] * ju[2] + jv[0] * jv[2];
+      A11 += ju[1] * ju[1] + jv[1] * jv[1], A12 += ju[1] * ju[2] + jv[1] * jv[2], A22 += ju[2] * ju[2] + jv[2] * jv[2];
+      b0 += ju[0] * ru + jv[0] * rv, b1 += ju[1] * ru + jv[1] * rv, b2 += ju[2] * ru + jv[2] * rv;
+    }
+    // the adjugate of the symmetric A
+    const double c00 = A11 * A22 - A12 * A12, c01 = A02 * A12 - A01 * A22, c02 = A01 * A12 - A02 * A11;
+    const double c11 = A00 * A22 - A02 * A02, c12 = A01 * A02 - A00 * A12, c22 = A00 * A11 - A01 * A01;
+    const double inv = -1.0 / (A00 * c00 + A01 * c01 + A02 * c02);
+    const double Xn[3] = {X[0] + inv * (c00 * b0 + c01 * b1 + c02 * b2), X[1] + inv * (c01 * b0 + c11 * b1 + c12 * b2),
+                          X[2] + inv * (c02 * b0 + c12 * b1 + c22 * b2)};
+    const double costn = refit_cost(d, lo, n, X0, e2, Xn);
+    if (!(costn < cost)) break;                              // also for a NaN step
+#pragma unroll
+    for (int k = 0; k < 3; ++k) X[k] = Xn[k];
+    cost = costn;
+  }
+}
+
+// Hypothesis h of a track of n >= 12 observations, which has more than kTriMaxHypotheses pairs -> (p, q), p < q, by the hash.
+__host__ __device__ __forceinline__ void sampled_pair(uint32_t seed, int h, int n, int& p, int& q) {
+  const uint32_t x = seed * 0x9E3779B1u + (uint32_t)h * 0x85EBCA6Bu + kSaltT;
+  const int a = (int)(lowbias32(x) % (uint32_t)n);
+  const int b = (int)(((uint32_t)a + 1u + lowbias32(x + 0xC2B2AE35u) % (uint32_t)(n - 1)) % (uint32_t)n);
+  p = a < b ? a : b, q = a < b ? b : a;
+}
+
+// One track: observations lo .. lo + n of the call.  -> the number of inliers (0: rejected); X, the mean pixel error of the
+// inliers and mask[0 .. n) (the track's own slots) are written either way, NaN and 0 for a rejected track.
+__host__ __device__ __forceinline__ int triangulate_track(const Tracks& d, long long lo, int n, uint32_t seed, double max_error,
+                                                          double tan2, double (&X)[3], uint8_t* mask, double& error) {
+  const double e2 = max_error * max_error;
+  double best[3] = {NAN, NAN, NAN};
+  int best_count = 0;
+  const bool all_pairs = (long long)n * (n - 1) / 2 <= kTriMaxHypotheses;
+  const int n_hyp = n < 2 ? 0 : all_pairs ? n * (n - 1) / 2 : kTriMaxHypotheses;
+  int p = 0, q = 0;                                          // all pairs: (0, 1), (0, 2), ...
+  for (int h = 0; h < n_hyp; ++h) {
+    if (all_pairs) {
+      if (++q >= n) ++p, q = p + 1;
+    } else {
+      sampled_pair(seed, h, n, p, q);
+    }
+    View vp, vq;
+    load_view(d, lo + p, vp);
+    load_view(d, lo + q, vq);
+    double Xh[3], sq, z;
+    if (!(vp.ok && vq.ok && midpoint(vp, vq, tan2, Xh))) continue;
+    if (!(inlier(vp, Xh, e2, sq, z) && inlier(vq, Xh, e2, sq, z))) continue;
+    const int count = count_inliers(d, lo, n, Xh, e2);
+    if (count > best_count) {                                // the lowest h on ties
+      best_count = count;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) best[k] = Xh[k];
+    }
+  }
+  int count = best_count;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) X[k] = best[k];
+  if (best_count > 0) {
+    double Xr[3];
+    refit(d, lo, n, best, e2, Xr);
+    if (is_finite(Xr[0]) && is_finite(Xr[1]) && is_finite(Xr[2])) {
+      const int rcount = count_inliers(d, lo, n, Xr, e2);
+      if (rcount >= best_count) {
+        count = rcount;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[k] = Xr[k];
+      }
+    }
+  }
+  // acceptance: some pair of inliers with enough parallax at X
+  bool wide = false;
+  if (count >= 2) {
+    for (int i = 0; i < n && !wide; ++i) {
+      View wi;
+      double sq, z, ci[3];
+      load_view(d, lo + i, wi);
+      if (!inlier(wi, X, e2, sq, z)) continue;
+      centre_of(wi, ci);
+      for (int j = i + 1; j < n && !wide; ++j) {
+        View wj;
+        double cj[3];
+        load_view(d, lo + j, wj);
+        if (!inlier(wj, X, e2, sq, z)) continue;
+        centre_of(wj, cj);
+        wide = parallax(X, ci, cj, tan2);
+      }
+    }
+  }
+  double sum = 0.0;
+  for (int i = 0; i < n; ++i) {
+    View w;
+    double sq, z;
+    load_view(d, lo + i, w);
+    const bool in = wide && inlier(w, X, e2, sq, z);
+    mask[i] = in ? 1 : 0;
+    if (in) sum += sqrt(sq / (z * z));
+  }
+  if (!wide) {
+    X[0] = X[1] = X[2] = NAN;
+    error = NAN;
+    return 0;
+  }
+  error = sum / (double)count;
+  return count;
+}
+
+__global__ __launch_bounds__(kTriWave) void triangulate_tracks_kernel(Tracks d, const int32_t* __restrict__ offsets, int n_tracks,
+                                                                      const int32_t* __restrict__ seeds, double max_error, double tan2,
+                                                                      double* __restrict__ out_xyz, uint8_t* __restrict__ out_mask,
+                                                                      int32_t* __restrict__ out_count, double* __restrict__ out_error) {
+  const long long t = (long long)blockIdx.x * kTriWave + threadIdx.x;
+  if (t >= n_tracks) return;
+  const long long lo = offsets[t], hi = offsets[t + 1];
+  double X[3] = {NAN, NAN, NAN}, error = NAN;
+  int count = 0;
+  if (lo >= 0 && hi >= lo)                                   // a track whose offsets do not delimit a list is rejected, nothing of it read
+    count = triangulate_track(d, lo, (int)(hi - lo), (uint32_t)seeds[t], max_error, tan2, X, out_mask + lo, error);
+  out_xyz[3 * t] = X[0], out_xyz[3 * t + 1] = X[1], out_xyz[3 * t + 2] = X[2];
+  out_count[t] = count;
+  out_error[t] = error;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vc_triangulate_tracks(const double* obs_xy, const int32_t* obs_cam, const int32_t* offsets, int n_tracks, const double* cams,
+                          int n_cams, const int32_t* seeds, double max_error_px, double min_tri_angle_tan2, double* out_xyz,
+                          uint8_t* out_mask, int32_t* out_count, double* out_error, vc_stream_t stream) {
+  if (n_tracks < 0 || n_cams < 0) return VC_ERR_INVALID_ARG;
+  if (n_tracks == 0) return VC_OK;
+  if (!obs_xy || !obs_cam || !offsets || !seeds || !out_xyz || !out_mask || !out_count || !out_error) return VC_ERR_INVALID_ARG;
+  if (!cams && n_cams > 0) return VC_ERR_INVALID_ARG;
+  if (!(max_error_px >= 0.0 && max_error_px < INFINITY && min_tri_angle_tan2 >= 0.0 && min_tri_angle_tan2 < INFINITY))
+    return VC_ERR_INVALID_ARG;
+  const int blocks = (n_tracks + kTriWave - 1) / kTriWave;
+  hipLaunchKernelGGL(triangulate_tracks_kernel, dim3((unsigned)blocks), dim3(kTriWave), 0, (hipStream_t)stream,
+                     Tracks{obs_xy, obs_cam, cams, n_cams}, offsets, n_tracks, seeds, max_error_px, min_tri_angle_tan2, out_xyz, out_mask,
+                     out_count, out_error);
+  return vc::check_launch();
+}
+
+}  // extern "C"

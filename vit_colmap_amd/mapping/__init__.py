@@ -1,4 +1,5 @@
-"""Image registration and the seed model.  Imported only when `ReconstructionConfig.seed_model` is set."""
+"""Image registration and the seed model, imported only when `ReconstructionConfig.seed_model` or
+`sparse_model` is set; the growth of the seed model (§4.2j: `mapping.grow`, `mapping.triangulate`) is imported only with the latter."""
 from .absolute_pose import estimate_absolute_poses, score_poses, solve_p3p
 from .seed import SparseModel, build_seed_model
 

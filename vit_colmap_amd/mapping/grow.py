@@ -1,0 +1,165 @@
+"""Growth of the seed model: the tracks of the match graph are triangulated under the registered poses
+and the remaining images registered against the new points, in rounds, until a round adds neither a point nor an image.
+It is still not a mapper: no bundle adjustment, no re-triangulation or merging of existing points, no point filtering after
+the rounds, no distortion models.  Specification: tests/util_mapper.py (`grow_model`).  This build's own published rule;
+parity with COLMAP's mapper is unpinned.
+
+Where the work runs
+  HIP     the seed model's two steps (mapping/seed.py); per round one launch of vc_triangulate_tracks over every track that
+          is tried (mapping/triangulate.py) and one registration batch over every image that is tried
+          (mapping/absolute_pose.py)
+  host    Python / numpy: the database rows, the union-find over (image, keypoint) nodes, which tracks and images a round
+          tries, the point ids and tracks, the final reprojection errors
+"""
+import logging
+
+import numpy as np
+
+from ..database.colmap_db import _quat_to_rot
+from .absolute_pose import ABS_POSE_MIN_NUM_INLIERS, estimate_absolute_poses
+from .seed import SparseModel, _pixel_errors, _read_database, _seed_model
+
+logger = logging.getLogger(__name__)
+
+
+def _gpu_triangulate(obs_xy, obs_cam, offsets, cams, seeds, device):
+    import torch
+
+    from .triangulate import triangulate_tracks
+
+    xyz, mask, count, error = triangulate_tracks(*(torch.from_numpy(np.ascontiguousarray(a)).to(device)
+                                                   for a in (obs_xy, obs_cam, offsets, cams, seeds)))
+    return xyz.cpu().numpy(), mask.cpu().numpy(), count.cpu().numpy(), error.cpu().numpy()
+
+
+def _components(kps, K, rows):
+    """Union-find over the nodes (image id, keypoint index), numbered image by image; the edges are the inlier matches of the
+    rows between images with a usable camera -> the consistent components (no two nodes in one image) as int64 arrays
+    (m, 2) of (image id, keypoint) in ascending order, themselves ascending in their first node."""
+    ids = sorted(kps)
+    base = dict(zip(ids, np.concatenate([[0], np.cumsum([len(kps[i]) for i in ids])])))
+    total = int(sum(len(kps[i]) for i in ids))
+    parent = np.arange(total)
+    edges = [np.stack([base[i] + g["inlier_matches"][:, 0].astype(np.int64), base[j] + g["inlier_matches"][:, 1].astype(np.int64)], axis=1)
+             for (i, j), g in sorted(rows.items()) if K[i] is not None and K[j] is not None]
+    touched = np.zeros(total, bool)
+    for a, b in (np.concatenate(edges) if edges else np.zeros((0, 2), np.int64)):
+        touched[a] = touched[b] = True
+        while parent[a] != a:                                  # path halving
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        while parent[b] != b:
+            parent[b] = parent[parent[b]]
+            b = parent[b]
+        if a != b:
+            parent[max(a, b)] = min(a, b)                      # the root of a component is its first node
+    nodes = np.nonzero(touched)[0]
+    root = nodes.copy()
+    while True:
+        up = parent[root]
+        if np.array_equal(up, root):
+            break
+        root = up
+    image_of = np.repeat(np.array(ids, np.int64), [len(kps[i]) for i in ids])
+    first = np.array([base[i] for i in ids], np.int64)
+    comps = []
+    order = np.argsort(root, kind="stable")                    # nodes ascend inside a component, components by their root
+    for members in np.split(nodes[order], np.nonzero(np.diff(root[order]))[0] + 1) if len(nodes) else []:
+        im = image_of[members]
+        if len(np.unique(im)) == len(im):
+            comps.append(np.stack([im, members - first[np.searchsorted(ids, im)]], axis=1))
+    return comps
+
+
+def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None) -> SparseModel:
+    """Read a matched database -> the seed model grown by rounds.  Raises the seed model's ValueErrors unchanged.
+    `two_view_pose_fn` and `estimate_fn` as in build_seed_model; `triangulate_fn(obs_xy, obs_cam, offsets, cams, seeds,
+    device) -> (xyz, mask, count, error)` on numpy arrays replaces the triangulation launch (tests)."""
+    estimate_fn = estimate_fn or estimate_absolute_poses
+    triangulate_fn = triangulate_fn or _gpu_triangulate
+    database = _read_database(database_path)
+    images, cameras, K, kps, rows = database
+    seed = _seed_model(database, device, two_view_pose_fn, estimate_fn)
+
+    poses = {i: (_quat_to_rot(im["qvec"]), np.asarray(im["tvec"], np.float64), im["qvec"]) for i, im in seed.images.items()}
+    xyz = {pid: p["xyz"] for pid, p in seed.points3D.items()}
+    tracks = {pid: list(p["track"]) for pid, p in seed.points3D.items()}
+    comps = _components(kps, K, rows)
+    comp_at = {i: {} for i in images}                          # image -> keypoint -> component
+    for c, nodes in enumerate(comps):
+        for i, kp in nodes:
+            comp_at[int(i)][int(kp)] = c
+    point_of = {}                                              # component -> point id
+    for pid, track in tracks.items():
+        c = comp_at[track[0][0]].get(track[0][1])
+        if c is not None:
+            point_of[c] = pid
+    ids = sorted(images)
+    slot = {i: s for s, i in enumerate(ids)}
+    slots = [np.array([slot[int(i)] for i in nodes[:, 0]], np.int32) for nodes in comps]
+    next_id = max(xyz, default=0) + 1
+    tried_t, tried_r, rounds = np.zeros(len(comps), np.int64), {}, 0
+    while True:
+        # T-step: every track without a point that two registered images see, in one launch
+        cams = np.full((len(ids), 16), np.nan)
+        for i, (R, t, _) in poses.items():
+            cams[slot[i]] = np.concatenate([R.reshape(9), t, [K[i][0, 0], K[i][1, 1], K[i][0, 2], K[i][1, 2]]])
+        registered = np.isfinite(cams[:, 0])
+        batch = []
+        for c, s in enumerate(slots):
+            seen = int(registered[s].sum())
+            if c not in point_of and seen >= 2 and seen > tried_t[c]:
+                tried_t[c] = seen
+                batch.append(c)
+        new_points = 0
+        if batch:
+            obs = np.concatenate([np.stack([kps[int(i)][int(kp)] for i, kp in comps[c]]) for c in batch]).astype(np.float64)
+            offsets = np.concatenate([[0], np.cumsum([len(comps[c]) for c in batch])]).astype(np.int32)
+            seeds = np.array([((int(comps[c][0, 0]) << 16) ^ int(comps[c][0, 1])) & 0xFFFFFFFF for c in batch], np.uint32).view(np.int32)
+            X, mask, count, _ = triangulate_fn(obs, np.concatenate([slots[c] for c in batch]), offsets, cams, seeds, device)
+            for b, c in enumerate(batch):
+                if count[b] > 0:
+                    point_of[c] = next_id
+                    xyz[next_id] = np.asarray(X[b], np.float64).copy()
+                    tracks[next_id] = [(int(i), int(kp)) for (i, kp), m in zip(comps[c], mask[offsets[b]:offsets[b + 1]]) if m]
+                    next_id += 1
+                    new_points += 1
+        # R-step: every unregistered image against the points its keypoints' tracks have, in one batch
+        problems, meta = [], []
+        for i in ids:
+            if i in poses or K[i] is None:
+                continue
+            pairs = sorted((kp, point_of[c]) for kp, c in comp_at[i].items() if c in point_of)
+            if len(pairs) >= ABS_POSE_MIN_NUM_INLIERS and len(pairs) > tried_r.get(i, 0):
+                tried_r[i] = len(pairs)
+                kp_idx, pids = [kp for kp, _ in pairs], [pid for _, pid in pairs]
+                problems.append(dict(obs=kps[i][kp_idx], xyz=np.stack([xyz[pid] for pid in pids]), K=K[i], seed=i))
+                meta.append((i, kp_idx, pids))
+        new_images = 0
+        for (i, kp_idx, pids), r in zip(meta, estimate_fn(problems, device) if problems else []):
+            if not r["success"]:
+                continue
+            q = np.asarray(r["qvec"], np.float64)
+            poses[i] = (_quat_to_rot(q), np.asarray(r["tvec"], np.float64), q)
+            for kp, pid, ok in zip(kp_idx, pids, r["inlier_mask"]):
+                if ok:
+                    tracks[pid].append((i, kp))
+            new_images += 1
+        if not new_points and not new_images:
+            break
+        rounds += 1
+        logger.info("Growth round %d: %d new points, %d new images", rounds, new_points, new_images)
+
+    model = SparseModel(initial_pair=seed.initial_pair, rounds=rounds)
+    for i, (_, t, q) in sorted(poses.items()):
+        cid = images[i].camera_id
+        model.cameras[cid] = cameras[cid]
+        model.images[i] = dict(qvec=q, tvec=t, camera_id=cid, name=images[i].name, xys=kps[i].astype(np.float64),
+                               point3D_ids=np.full(len(kps[i]), -1, np.int64))
+    for pid in sorted(xyz):
+        errs = []
+        for i, kp in tracks[pid]:
+            model.images[i]["point3D_ids"][kp] = pid
+            errs.append(_pixel_errors(K[i], poses[i][0], poses[i][1], xyz[pid][None], kps[i][kp][None].astype(np.float64))[0])
+        model.points3D[pid] = dict(xyz=xyz[pid].copy(), rgb=(0, 0, 0), error=float(np.mean(errs)), track=list(tracks[pid]))
+    return model

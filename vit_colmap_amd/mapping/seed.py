@@ -1,7 +1,8 @@
 """The seed model: an initial pair, that pair's triangulated points, every other image registered against
-those points in one batched launch, written as a COLMAP text model.  It is NOT a mapper: no point is triangulated after the
-seed, there is no bundle adjustment and no second registration round.  Specification: tests/util_absolute_pose.py
-(`seed_model`).  This build's own published rule; parity with COLMAP's mapper is unpinned.
+those points in one batched launch, written as a COLMAP text model.  The seed model itself triangulates no point after the
+seed and registers once; mapping/grow.py (§4.2j) grows it by rounds of triangulation and registration.  Neither is a mapper:
+there is no bundle adjustment.  Specification: tests/util_absolute_pose.py (`seed_model`).  This build's own published rule;
+parity with COLMAP's mapper is unpinned.
 
 Where the work runs
   HIP     the triangulation of every candidate pair's inliers (vc_two_view_pose, one launch over all candidates) and the
@@ -15,7 +16,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ..database.colmap_db import Camera, ColmapDatabase, _quat_to_rot
-from ..matching._common import CONFIG_CALIBRATED, MAX_ERROR
+from ..matching._common import CONFIG_CALIBRATED, CONFIG_PLANAR, MAX_ERROR
 from ..matching.essential import camera_prior
 from .absolute_pose import (ABS_POSE_MIN_NUM_INLIERS, FILTER_MIN_TRI_ANGLE, INIT_MIN_NUM_INLIERS, INIT_MIN_TRI_ANGLE,
                             estimate_absolute_poses)
@@ -35,13 +36,15 @@ class SparseModel:
     images: dict = field(default_factory=dict)
     points3D: dict = field(default_factory=dict)
     initial_pair: tuple = None
+    rounds: int = None                   # growth rounds that added a point or an image (§4.2j); None: a seed model
 
     def mean_track_length(self):
         return float(np.mean([len(p["track"]) for p in self.points3D.values()])) if self.points3D else 0.0
 
     def stats(self):
-        return dict(initial_pair=list(self.initial_pair) if self.initial_pair else None, registered_images=len(self.images),
-                    num_points3D=len(self.points3D), mean_track_length=self.mean_track_length())
+        s = dict(initial_pair=list(self.initial_pair) if self.initial_pair else None, registered_images=len(self.images),
+                 num_points3D=len(self.points3D), mean_track_length=self.mean_track_length())
+        return s if self.rounds is None else dict(s, rounds=self.rounds)
 
     # COLMAP's text layout [recalled: colmap/src/colmap/scene/reconstruction_io.cc]; floats are written with repr, so a model
     # reads back equal
@@ -160,11 +163,10 @@ def _pixel_errors(K, R, t, xyz, obs):
     return np.where(Xc[:, 2] > 0, err, np.inf)
 
 
-def build_seed_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None) -> SparseModel:
-    """Read a matched database -> the seed model.  Raises ValueError, naming the condition, when no pair can start it.
-    `two_view_pose_fn(xn_rows, cand, device)` and `estimate_fn(problems, device)` replace the two GPU steps (tests)."""
-    two_view_pose_fn = two_view_pose_fn or _gpu_two_view_pose
-    estimate_fn = estimate_fn or estimate_absolute_poses
+def _read_database(database_path):
+    """The rows the seed model and its growth read -> images {image_id: Image}, cameras {camera_id: Camera}, K {image_id: (3, 3)
+    or None where the camera has no usable prior or another model}, kps {image_id: float32 (n, 2)}, rows {(i, j), i < j: the
+    two_view_geometries row} of every CALIBRATED or PLANAR row with inliers."""
     with ColmapDatabase.open_database(str(database_path)) as db:
         images = {im.image_id: im for im in db.read_all_images()}
         cameras, K, kps = {}, {}, {}
@@ -176,10 +178,24 @@ def build_seed_model(database_path, device="cuda", two_view_pose_fn=None, estima
             K[iid] = Kc if ok and cam.model in SEED_CAMERA_MODELS else None
             kp = db.read_keypoints(iid)
             kps[iid] = np.zeros((0, 2), np.float32) if kp is None else kp[:, :2]
-        geoms = {}
-        for i, j, rows, config in db.read_two_view_geometry_pairs():
-            if rows > 0 and config == CONFIG_CALIBRATED and i in images and j in images:
-                geoms[(i, j)] = db.read_two_view_geometry(i, j)
+        rows = {}
+        for i, j, n, config in db.read_two_view_geometry_pairs():
+            if n > 0 and config in (CONFIG_CALIBRATED, CONFIG_PLANAR) and i in images and j in images:
+                rows[(i, j)] = db.read_two_view_geometry(i, j)
+    return images, cameras, K, kps, rows
+
+
+def build_seed_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None) -> SparseModel:
+    """Read a matched database -> the seed model.  Raises ValueError, naming the condition, when no pair can start it.
+    `two_view_pose_fn(xn_rows, cand, device)` and `estimate_fn(problems, device)` replace the two GPU steps (tests)."""
+    return _seed_model(_read_database(database_path), device, two_view_pose_fn, estimate_fn)
+
+
+def _seed_model(database, device, two_view_pose_fn, estimate_fn):
+    two_view_pose_fn = two_view_pose_fn or _gpu_two_view_pose
+    estimate_fn = estimate_fn or estimate_absolute_poses
+    images, cameras, K, kps, rows = database
+    geoms = {pair: g for pair, g in rows.items() if g["config"] == CONFIG_CALIBRATED}
 
     def directed(i, j):
         """The CALIBRATED geometry of (i -> j): match columns (i, j), X_j = R X_i + t; None where there is no such row."""

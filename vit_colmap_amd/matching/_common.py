@@ -15,7 +15,7 @@ MAX_H_INLIER_RATIO = 0.8
 MIN_INLIER_RATIO = 0.25
 NUM_HYP_F, NUM_HYP_H = 512, 128
 NUM_CANDIDATES = 32
-SALT = {"F": 0x0F0F0F0F, "H": 0x3C3C3C3C, "E": 0x5A5A5A5A, "P": 0x96969696}
+SALT = {"F": 0x0F0F0F0F, "H": 0x3C3C3C3C, "E": 0x5A5A5A5A, "P": 0x96969696, "T": 0xC3C3C3C3}
 MODEL_CODE = {"F": 0, "H": 1}
 _M32 = 0xFFFFFFFF
 

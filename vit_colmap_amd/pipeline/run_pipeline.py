@@ -71,12 +71,15 @@ class Pipeline:
         if matcher_type == "retrieval" and int(num_neighbors) < 1:
             raise ValueError(f"num_neighbors must be at least 1 (got {num_neighbors})")
         seed_model = bool(getattr(self.config.reconstruction, "seed_model", False))
-        if seed_model:                                          # the seed model reads calibrated rows with a pose (§4.2i)
+        sparse_model = bool(getattr(self.config.reconstruction, "sparse_model", False))
+        for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
+            if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
+                continue
             for on, flag in ((self.config.camera.prior_focal_length, "camera.prior_focal_length (--prior-focal-length)"),
                              (self.config.matching.compute_relative_pose, "matching.compute_relative_pose (--relative-pose)"),
                              (self.config.do_matching, "do_matching (no --skip-matching)")):
                 if not on:
-                    raise ValueError(f"seed_model needs {flag}")
+                    raise ValueError(f"{name} needs {flag}")
 
         extractor = self._make_extractor()
         extractor.prior_focal_length = bool(self.config.camera.prior_focal_length)
@@ -124,6 +127,8 @@ class Pipeline:
 
         if seed_model:                                          # under torchrun only rank 0 arrives here
             self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
+        if sparse_model:
+            self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
 
         reconstructions = None
         if self.config.do_reconstruction:
@@ -162,6 +167,20 @@ class Pipeline:
         self.last_stats = dict(self.last_stats or {}, seed_model=model.stats())
         logger.info("Seed model: pair %s, %d images, %d points", *[model.stats()[k] for k in
                                                                     ("initial_pair", "registered_images", "num_points3D")])
+
+    def _write_sparse_model(self, db_path, output_dir, device):
+        """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing."""
+        from ..mapping.grow import build_sparse_model
+
+        try:
+            model = build_sparse_model(str(db_path), device=device)
+        except ValueError as e:
+            logger.warning("no sparse model written: %s", e)
+            return
+        model.write_text(str(Path(output_dir) / "sparse" / "grown"))
+        self.last_stats = dict(self.last_stats or {}, sparse_model=model.stats())
+        logger.info("Sparse model: pair %s, %d images, %d points, %d rounds", *[model.stats()[k] for k in
+                                                                                 ("initial_pair", "registered_images", "num_points3D", "rounds")])
 
     def extract_and_export_metrics(self, db_path, output_dir, reconstructions, dataset, scene, results_dir=None):
         """Database metrics -> `{results_dir}/{dataset}/{scene}/{extractor}.json` + summary.csv row
@@ -204,6 +223,9 @@ def main() -> None:
     ap.add_argument("--seed-model", dest="seed_model", action="store_true",
                     help="write output/sparse/seed: an initial pair, its triangulated points and every other image registered "
                          "against them (needs --prior-focal-length and --relative-pose)")
+    ap.add_argument("--sparse-model", dest="sparse_model", action="store_true",
+                    help="write output/sparse/grown: the seed model grown by rounds of track triangulation and registration "
+                         "(needs --prior-focal-length and --relative-pose)")
     ap.add_argument("--matcher", choices=list(MATCHER_TYPES), default="exhaustive",
                     help="exhaustive: every image pair; retrieval: each image against its --num-neighbors nearest images")
     ap.add_argument("--num-neighbors", dest="num_neighbors", type=int, default=20,

@@ -106,6 +106,7 @@ class ReconstructionConfig:
     min_num_matches: int = 15
     multiple_models: bool = True
     seed_model: bool = False     # write output_dir/sparse/seed: an initial pair, its points, every other image registered (§4.2i)
+    sparse_model: bool = False   # write output_dir/sparse/grown: the seed model grown by rounds of triangulation and registration (§4.2j)
 
     def to_mapper_options(self):
         import pycolmap  # noqa: PLC0415 - optional, third party
@@ -165,6 +166,8 @@ class Config:
             config.matching.compute_relative_pose = True
         if getattr(args, "seed_model", False):
             config.reconstruction.seed_model = True
+        if getattr(args, "sparse_model", False):
+            config.reconstruction.sparse_model = True
         if getattr(args, "matcher", None):
             config.matching.matcher_type = args.matcher
         if getattr(args, "num_neighbors", None) is not None:
