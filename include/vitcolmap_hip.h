@@ -289,6 +289,60 @@ int vc_triangulate_tracks(const double* obs_xy, const int32_t* obs_cam, const in
                           uint8_t* out_mask, int32_t* out_count, double* out_error, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bundle adjustment: the three steps of one Levenberg-Marquardt iteration over every pose and
+ * every point, by the Schur complement of the points; float64 in single operations in the written order, the only library
+ * call is sqrt, no atomics: two calls return the same bytes.  The caller solves S dc = -g between the last two and runs the
+ * loop (vit_colmap_amd/mapping/bundle.py).  Specification: tests/util_bundle.py.  This build's own published rule: parity
+ * with COLMAP / Ceres is unpinned.  Intrinsics are never refined; the loss is the plain squared pixel error.
+ *   cams        [n_cams][16] float64 as vc_triangulate_tracks has them: R row-major, t, fx, fy, cx, cy
+ *   const_mask  [n_cams] uint8: bit i set = pose parameter i is held (0-2 the rotation w, 3-5 the translation)
+ *   points      [n_points][3] float64
+ *   offsets     [n_points + 1] int32, obs_cam [total] int32, obs_xy [total][2] float64: the point-major tracks of
+ *               vc_triangulate_tracks.  Offsets that are negative, descend or pass total: the point is skipped, nothing of it
+ *               is read, its outputs are 0 (its candidate is the point itself)
+ *   cam_offsets [n_cams + 1] int32, cam_obs [total] int32: per camera the indices of its observations in ascending order;
+ *               obs_point [total] int32: the point of each observation.  Offsets that are negative, descend or pass total:
+ *               the camera is skipped (its block is that of a camera without observations).  An entry of cam_obs that is no
+ *               usable observation of that camera inside its point's track is passed over
+ *   lambda      the damping, finite and not negative
+ * The rule, per observation of point X in camera (R, t):
+ *   usable      rule 1 of vc_triangulate_tracks (slot in [0, n_cams), finite row and pixel) and Xc_z > 0; any other observation
+ *               contributes nothing anywhere (obs_ok 0, obs_lin 0)
+ *   residual    Y = R X, Xc = Y + t, r = (fx Xc_x / Xc_z + cx - u, fy Xc_y / Xc_z + cy - v)
+ *   J_p         fu (R_0k - xu R_2k), fv (R_1k - xv R_2k) with fu = fx / z, fv = fy / z, xu = Xc_x / z, xv = Xc_y / z
+ *   J_c         the pose perturbed on the left, Xc(w, dt) = Rot(w) Y + t + dt: J_pi [ -[Y]x | I ], row u = (-(au Y_1),
+ *               fu Y_2 + au Y_0, -(fu Y_1), fu, 0, -au), row v = (-(fv Y_2 + av Y_1), av Y_0, fv Y_0, 0, fv, -av), au = fu xu,
+ *               av = fv xv; the columns of held parameters are 0
+ *   obs_lin     [total][32]: J_c row u (6), row v (6), r (2), W = J_c' J_p row-major (18)
+ * vc_ba_linearize_points: per point in track order V = sum J_p' J_p, g_p = sum J_p' r, cost = 0.5 sum |r|^2; V_ii += lambda
+ * V_ii; V^-1 by the adjugate, stored 00 01 02 11 12 22.  A point with fewer than two usable observations, or whose damped V
+ * has a determinant that is not finite and positive, is constant for this linearisation: V^-1 = 0.  out_total_cost [1]: the
+ * costs added in point order (a second launch of one wave).
+ * vc_ba_reduce_cameras: out_S [6 n_cams][6 n_cams] row-major, out_g [6 n_cams].  Per camera a over its observations in
+ * ascending order: U_a = sum J_c' J_c; Y = W V^-1; g_a = sum J_c' r - sum Y g_p; S_ab = delta_ab U_a - sum Y W_b' over the
+ * track of the observation's point in track order (b = a and a camera twice in a track included); U_ii += lambda U_ii.  A held
+ * parameter, or one with U_ii = 0 (no usable observation moves it), has the diagonal 1 and zero rows and columns.  One
+ * workgroup per camera, entry e of block b owned by lane (36 b + e) mod 64, the row block in LDS: n_cams <= VC_BA_MAX_CAMS
+ * (the CU's 160 KiB of LDS bind before the dense S does), VC_ERR_UNSUPPORTED above.
+ * vc_ba_step: dc [6 n_cams] the solution of S dc = -g.  out_dx = -V^-1 (g_p + sum W' dc) over the track in track order,
+ * out_points = points + out_dx; out_cams: q = (1, w / 2) / |(1, w / 2)|, R(q) R, t + dt, the intrinsics copied.
+ * A size of 0 (n_points for the first, n_cams for the second, both for the third): VC_OK whatever the pointers are.  A null
+ * pointer that a size needs, a negative size, a lambda that is negative or not finite: VC_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_BA_MAX_CAMS 512
+int vc_ba_linearize_points(const double* cams, int n_cams, const uint8_t* const_mask, const double* points, int n_points,
+                           const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                           double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count, uint8_t* out_obs_ok,
+                           double* out_obs_lin, double* out_total_cost, vc_stream_t stream);
+int vc_ba_reduce_cameras(int n_cams, const uint8_t* const_mask, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                         const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point, double lambda,
+                         const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_S,
+                         double* out_g, vc_stream_t stream);
+int vc_ba_step(const double* cams, int n_cams, const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam,
+               int total, const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* dc,
+               double* out_cams, double* out_points, double* out_dx, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Bundle adjustment (developer tool, bench.py is the judged entry).  Times the three entry points of
+csrc/bundle.hip, the solve of the reduced system and the whole loop of mapping/bundle.py on two problems: the grown model of
+the 12-view windowed scene (tests/util_mapper.py, truth_pairs rows: 12 cameras, 1161 points, 4283 observations) and a
+synthetic arc of --cams cameras (default 200) 0.5 degrees apart with --points points (default 20 000), each seen by 3-8
+neighbouring cameras, 0.5 px noise, poses and points moved off the truth.  A kernel's time is the median over --iters launches
+after 3 warm-up launches, by device events; the loop's is wall clock around bundle_adjust, synchronised, the median of --loops
+runs.  Prints one JSON line.  Needs a GPU."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from vit_colmap_amd import _lib  # noqa: E402
+from vit_colmap_amd.mapping import bundle  # noqa: E402
+
+K = np.array([[600.0, 0, 320.0], [0, 600.0, 240.0], [0, 0, 1]])
+
+
+def windowed_problem():
+    import util_bundle as ub
+    import util_mapper as um
+    from test_absolute_pose_spec import scene_images, truth_pairs
+
+    scene = um.windowed_scene()
+    images = scene_images(scene)
+    grown = um.grow_model(images, truth_pairs(scene))
+    ids, cams, points, offsets, obs_cam, obs_xy = ub.model_problem(images, grown)
+    a, b = (ids.index(i) for i in grown["initial_pair"])
+    return cams, points, offsets, obs_cam, obs_xy, ub.gauge_mask(cams, a, b)
+
+
+def arc_problem(n_cams, n_points, seed=1, noise=0.5):
+    rs = np.random.RandomState(seed)
+    rows = []
+    for a in np.radians(0.5 * (np.arange(n_cams) - n_cams / 2)):
+        c = np.array([8.0 * np.sin(a), 0.2 * np.cos(5 * a), -8.0 * np.cos(a)])
+        z = -c / np.linalg.norm(c)
+        x = np.cross([0.0, 1.0, 0.0], z)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])
+        rows.append(np.concatenate([R.reshape(9), -R @ c, [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]]))
+    cams = np.stack(rows)
+    lengths = rs.randint(3, 9, n_points)
+    offsets = np.concatenate([[0], np.cumsum(lengths)])
+    point_of = np.repeat(np.arange(n_points), lengths)
+    # a point's cameras: a random start and every fourth camera after it, so that a track spans up to 14 degrees
+    first = rs.randint(0, n_cams - 4 * 8, n_points)
+    obs_cam = (first[point_of] + 4 * (np.arange(offsets[-1]) - offsets[:-1][point_of])).astype(np.int32)
+    X = np.stack([rs.uniform(-2, 2, n_points), rs.uniform(-1.5, 1.5, n_points), rs.uniform(-1.5, 1.5, n_points)], axis=1)
+    Xc = np.einsum("nij,nj->ni", cams[obs_cam, :9].reshape(-1, 3, 3), X[point_of]) + cams[obs_cam, 9:12]
+    obs_xy = np.stack([K[0, 0] * Xc[:, 0] / Xc[:, 2] + K[0, 2], K[1, 1] * Xc[:, 1] / Xc[:, 2] + K[1, 2]], axis=1) + rs.normal(0, noise, (len(obs_cam), 2))
+    moved = cams.copy()
+    moved[1:, 9:12] += rs.normal(0, 5e-3, (n_cams - 1, 3))
+    mask = np.zeros(n_cams, np.uint8)
+    mask[0], mask[1] = bundle.HELD_ALL, 1 << (3 + int(np.argmax(np.abs(cams[1, 9:12]))))
+    return moved, X + rs.normal(0, 1e-2, X.shape), offsets.astype(np.int32), obs_cam, obs_xy, mask
+
+
+def device_ms(fn, iters):
+    for _ in range(3):
+        fn()
+    times = []
+    for _ in range(iters):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        fn()
+        stop.record()
+        stop.synchronize()
+        times.append(start.elapsed_time(stop))
+    return float(np.median(times))
+
+
+def measure(problem, iters, loops):
+    cams, points, offsets, obs_cam, obs_xy, mask = problem
+    c, n, t = len(cams), len(points), len(obs_cam)
+    lib = _lib.load()
+    dev = torch.device("cuda")
+    d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (cams, mask, points, offsets, obs_cam, obs_xy)]
+    x = [torch.from_numpy(a).to(dev) for a in bundle.camera_index(obs_cam, offsets, c)]
+    b = bundle._Buffers(torch, c, n, t, dev)
+    S = torch.zeros((6 * c, 6 * c), dtype=torch.float64, device=dev)
+    g, dc = torch.zeros(6 * c, dtype=torch.float64, device=dev), torch.zeros(6 * c, dtype=torch.float64, device=dev)
+    out_cams, out_points, dx = torch.zeros_like(d[0]), torch.zeros_like(d[2]), torch.zeros_like(d[2])
+    p, stream, lam = _lib.ptr, _lib.stream_ptr(), bundle.BA_LAMBDA0
+
+    def linearize():
+        _lib.check(lib.vc_ba_linearize_points(p(d[0]), c, p(d[1]), p(d[2]), n, p(d[3]), p(d[4]), p(d[5]), t, lam, p(b.vinv), p(b.gp), p(b.cost),
+                                              p(b.count), p(b.obs_ok), p(b.obs_lin), p(b.total_cost), stream), "vc_ba_linearize_points")
+
+    def reduce():
+        _lib.check(lib.vc_ba_reduce_cameras(c, p(d[1]), n, p(d[3]), p(d[4]), t, p(x[0]), p(x[1]), p(x[2]), lam, p(b.vinv), p(b.gp), p(b.obs_ok),
+                                            p(b.obs_lin), p(S), p(g), stream), "vc_ba_reduce_cameras")
+
+    def solve():
+        L, _ = torch.linalg.cholesky_ex(S)
+        dc.copy_(torch.cholesky_solve(-g[:, None], L)[:, 0])
+
+    def step():
+        _lib.check(lib.vc_ba_step(p(d[0]), c, p(d[2]), n, p(d[3]), p(d[4]), t, p(b.vinv), p(b.gp), p(b.obs_ok), p(b.obs_lin), p(dc), p(out_cams),
+                                  p(out_points), p(dx), stream), "vc_ba_step")
+
+    out = dict(cameras=c, points=n, observations=t)
+    for name, fn in (("linearize_ms", linearize), ("reduce_ms", reduce), ("solve_ms", solve), ("step_ms", step)):
+        out[name] = round(device_ms(fn, iters), 4)
+    walls, report = [], None
+    for _ in range(loops + 1):                                        # the first run warms up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, _, report = bundle.bundle_adjust(cams, points, offsets, obs_cam, obs_xy, mask, "cuda")
+        torch.cuda.synchronize()
+        walls.append(1e3 * (time.perf_counter() - t0))
+    out.update(loop_ms=round(float(np.median(walls[1:])), 3), iterations=report["iterations"], accepted_steps=report["accepted_steps"],
+               initial_cost=report["initial_cost"], final_cost=report["final_cost"])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cams", type=int, default=200)
+    ap.add_argument("--points", type=int, default=20000)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--loops", type=int, default=5)
+    args = ap.parse_args()
+    print(json.dumps(dict(tool="bench_bundle", iters=args.iters, loops=args.loops, windowed=measure(windowed_problem(), args.iters, args.loops),
+                          arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops))))
+
+
+if __name__ == "__main__":
+    main()

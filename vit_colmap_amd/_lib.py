@@ -16,6 +16,7 @@ ABI_VERSION = 1
 VC_MAX_KEYPOINTS = 2048
 VC_MAX_DESC_DIM = 1024
 VC_MAX_NEIGHBOURS = 64
+VC_BA_MAX_CAMS = 512
 VC_ERR_INVALID_ARG, VC_ERR_UNSUPPORTED, VC_ERR_LAUNCH, VC_ERR_WORKSPACE = -1, -2, -3, -4
 
 
@@ -57,6 +58,12 @@ SIGNATURES = {
     "vc_absolute_pose_inliers": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p]),
     "vc_triangulate_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_ba_linearize_points": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_ba_reduce_cameras": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_ba_step": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vc_structure_tensor": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vc_score_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vc_select_keypoints": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,

@@ -1,0 +1,414 @@
+// Bundle adjustment (gfx950): the three kernels of one Levenberg-Marquardt iteration over every pose and
+// every point of a sparse model, by the Schur complement of the points.  vc_ba_linearize_points, vc_ba_reduce_cameras and
+// vc_ba_step are what vit_colmap_amd/mapping/bundle.py repeats; the reduced system between the last two is solved by the
+// caller.  Specification: tests/util_bundle.py.  This build's own published rule; parity with COLMAP / Ceres is unpinned.
+//
+// float64 in single operations in the written order (-ffp-contract=off), the only library call is sqrt, no atomics.
+//   linearize  one point per lane, one wave per workgroup, no LDS: every observation of the point's track is linearised
+//              (residual r, J_c 2x6, W = J_c' J_p 6x3, written per observation: 32 numbers), V = sum J_p' J_p, g_p and the
+//              cost are accumulated in track order, V is damped and inverted by the adjugate.  A second launch of one wave
+//              adds the costs in point order.
+//   reduce     one workgroup of one wave per camera a, the row block [6][6 n_cams] of sum Y W' in LDS.  Entry e = 6 r + c of
+//              block b belongs to lane (36 b + e) mod 64 for the whole launch; nobody else reads or writes it, so there is no
+//              atomic and the order of a lane's additions is the rule's: camera a's observations in ascending order and,
+//              inside each, the track of its point in track order.  What lanes share is prepared 64 observations at a time,
+//              one per lane (the list's entry resolved, Y = W V^-1), and left in LDS between two barriers; every lane then
+//              walks the batch in order, so the chain of dependent loads that resolves an entry is paid once per batch; along
+//              a track it loads the next element's flag and camera while the current element's W is on its way.
+//   step       one point per lane: dX = -V^-1 (g_p + sum W' dc) in track order, X + dX; one camera per lane: q = (1, w / 2)
+//              normalised, R(q) R, t + dt.
+// What a lane computes is sequential and nothing depends on the order in which lanes or workgroups run, so two launches
+// return the same bits, and the same routines compiled for the host (tools/bundle_host.cpp includes this file) return the
+// device's.  Every index read from an input array is checked against the array it indexes before it is used.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/vitcolmap_hip.h"
+#include "common.h"
+
+namespace {
+
+constexpr int kBaWave = 64;
+constexpr int kBaLin = 32;                     // numbers per observation: J_c row u (6), row v (6), r (2), W row-major (18)
+constexpr int kBaLinR = 12, kBaLinW = 14;
+
+struct BaProblem {
+  const double* __restrict__ cams;             // [n_cams][16]
+  const uint8_t* __restrict__ const_mask;      // [n_cams]
+  const double* __restrict__ points;           // [n_points][3]
+  const int32_t* __restrict__ offsets;         // [n_points + 1]
+  const int32_t* __restrict__ obs_cam;         // [total]
+  const double* __restrict__ obs_xy;           // [total][2]
+  int n_cams, n_points, total;
+};
+
+// What the points pass leaves for the other two.
+struct BaLinear {
+  const double* __restrict__ vinv;             // [n_points][6]: 00 01 02 11 12 22
+  const double* __restrict__ gp;               // [n_points][3]
+  const uint8_t* __restrict__ obs_ok;          // [total]
+  const double* __restrict__ obs_lin;          // [total][32]
+};
+
+__host__ __device__ __forceinline__ bool ba_finite(double x) { return fabs(x) < INFINITY; }   // false for NaN
+
+// Point j's rows of the per-observation arrays -> false when its offsets do not delimit a list inside them.
+__host__ __device__ __forceinline__ bool ba_track(const int32_t* __restrict__ offsets, int j, int total, int& lo, int& hi) {
+  lo = offsets[j], hi = offsets[j + 1];
+  return lo >= 0 && hi >= lo && hi <= total;
+}
+
+// Observation o of point X: usable -> lin[32] (zeros otherwise) and J_p (2x3).
+__host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, int o, const double (&X)[3], double* __restrict__ lin,
+                                                    double (&ju)[3], double (&jv)[3]) {
+  const int slot = d.obs_cam[o];
+  bool ok = slot >= 0 && slot < d.n_cams;
+  const double* c = d.cams + (long long)(ok ? slot : 0) * 16;
+  double row[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    row[k] = ok ? c[k] : NAN;
+    ok = ok && ba_finite(row[k]);
+  }
+  const double u = d.obs_xy[2 * (long long)o], v = d.obs_xy[2 * (long long)o + 1];
+  ok = ok && ba_finite(u) && ba_finite(v);
+  const unsigned held = ok ? d.const_mask[slot] : 0u;
+  double Y[3], Xc[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    Y[i] = row[3 * i] * X[0] + row[3 * i + 1] * X[1] + row[3 * i + 2] * X[2];
+    Xc[i] = Y[i] + row[9 + i];
+  }
+  const double z = Xc[2];
+  ok = ok && z > 0.0;                                        // false for NaN
+  const double fx = row[12], fy = row[13], cx = row[14], cy = row[15];
+  const double ru = fx * Xc[0] / z + cx - u, rv = fy * Xc[1] / z + cy - v;
+  const double fu = fx / z, fv = fy / z, xu = Xc[0] / z, xv = Xc[1] / z;
+  const double au = fu * xu, av = fv * xv;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    ju[k] = fu * (row[k] - xu * row[6 + k]);
+    jv[k] = fv * (row[3 + k] - xv * row[6 + k]);
+  }
+  // J_c = J_pi [ -[R X]x | I ]: the pose is perturbed on the left, Xc(w, dt) = Rot(w) (R X) + t + dt
+  double cu[6] = {-(au * Y[1]), fu * Y[2] + au * Y[0], -(fu * Y[1]), fu, 0.0, -au};
+  double cv[6] = {-(fv * Y[2] + av * Y[1]), av * Y[0], fv * Y[0], 0.0, fv, -av};
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const bool off = !ok || ((held >> i) & 1u);
+    cu[i] = off ? 0.0 : cu[i];
+    cv[i] = off ? 0.0 : cv[i];
+    lin[i] = cu[i], lin[6 + i] = cv[i];
+  }
+  lin[kBaLinR] = ok ? ru : 0.0, lin[kBaLinR + 1] = ok ? rv : 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lin[kBaLinW + 3 * i + k] = ok ? cu[i] * ju[k] + cv[i] * jv[k] : 0.0;
+  return ok;
+}
+
+// One point: its track linearised -> V^-1 (damped, 0 where the point is constant), g_p, cost, the usable count; per
+// observation of the track obs_ok and obs_lin.
+__host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, int j, double lambda, double (&vinv)[6], double (&gp)[3],
+                                                           double& cost, uint8_t* __restrict__ obs_ok, double* __restrict__ obs_lin) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) vinv[k] = 0.0;
+  gp[0] = gp[1] = gp[2] = 0.0;
+  cost = 0.0;
+  int lo, hi, count = 0;
+  if (!ba_track(d.offsets, j, d.total, lo, hi)) return 0;   // nothing of the point is read or written
+  const double X[3] = {d.points[3 * (long long)j], d.points[3 * (long long)j + 1], d.points[3 * (long long)j + 2]};
+  double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, sq = 0.0;
+  for (int o = lo; o < hi; ++o) {
+    double* lin = obs_lin + (long long)o * kBaLin;
+    double ju[3], jv[3];
+    const bool ok = ba_observe(d, o, X, lin, ju, jv);
+    obs_ok[o] = ok ? 1 : 0;
+    if (!ok) continue;
+    const double ru = lin[kBaLinR], rv = lin[kBaLinR + 1];
+    A00 += ju[0] * ju[0] + jv[0] * jv[0], A01 += ju[0] * ju[1] + jv[0] * jv[1], A02 += ju[0] * ju[2] + jv[0] * jv[2];
+    A11 += ju[1] * ju[1] + jv[1] * jv[1], A12 += ju[1] * ju[2] + jv[1] * jv[2], A22 += ju[2] * ju[2] + jv[2] * jv[2];
+    gp[0] += ju[0] * ru + jv[0] * rv, gp[1] += ju[1] * ru + jv[1] * rv, gp[2] += ju[2] * ru + jv[2] * rv;
+    sq += ru * ru + rv * rv;
+    ++count;
+  }
+  cost = 0.5 * sq;
+  A00 += lambda * A00, A11 += lambda * A11, A22 += lambda * A22;
+  // the adjugate of the symmetric V
+  const double c00 = A11 * A22 - A12 * A12, c01 = A02 * A12 - A01 * A22, c02 = A01 * A12 - A02 * A11;
+  const double c11 = A00 * A22 - A02 * A02, c12 = A01 * A02 - A00 * A12, c22 = A00 * A11 - A01 * A01;
+  const double det = A00 * c00 + A01 * c01 + A02 * c02;
+  if (count >= 2 && det > 0.0 && det < INFINITY) {          // otherwise the point is constant for this linearisation
+    const double inv = 1.0 / det;
+    vinv[0] = c00 * inv, vinv[1] = c01 * inv, vinv[2] = c02 * inv, vinv[3] = c11 * inv, vinv[4] = c12 * inv, vinv[5] = c22 * inv;
+  }
+  return count;
+}
+
+// Entry idx of camera a's list -> the observation and its point's track; false where the entry names no usable
+// observation of camera a (the point's offsets, the observation's owner and its slot are checked here).
+__host__ __device__ __forceinline__ bool ba_camera_obs(const BaProblem& d, const BaLinear& l, const int32_t* __restrict__ cam_obs,
+                                                       const int32_t* __restrict__ obs_point, int a, int idx, int& o, int& j,
+                                                       int& lo, int& hi) {
+  o = cam_obs[idx];
+  if (o < 0 || o >= d.total) return false;
+  j = obs_point[o];
+  if (j < 0 || j >= d.n_points || !ba_track(d.offsets, j, d.total, lo, hi) || o < lo || o >= hi) return false;
+  return d.obs_cam[o] == a && l.obs_ok[o] != 0;
+}
+
+// The registers of one lane of the camera pass: its entry of U_a (the lanes that own block a), of sum J_c' r and of sum Y g_p
+// (lanes 0 .. 5).
+struct BaLane {
+  double u, gr, gy;
+};
+
+// What one lane prepares for the others: entry base + lane of camera a's list resolved (o < 0: passed over) and, for a usable
+// observation, Y = W V^-1 (6x3, 18 numbers).  A batch of 64 entries is prepared at once, then every lane walks it in order.
+struct BaBatch {
+  int o[kBaWave], j[kBaWave], lo[kBaWave], hi[kBaWave];
+  double y[kBaWave][18];
+};
+
+__host__ __device__ __forceinline__ void ba_prepare(const BaProblem& d, const BaLinear& l, const int32_t* __restrict__ cam_obs,
+                                                    const int32_t* __restrict__ obs_point, int a, int idx, int last, int lane,
+                                                    BaBatch& batch) {
+  int o = -1, j = 0, lo = 0, hi = 0;
+  if (idx >= last || !ba_camera_obs(d, l, cam_obs, obs_point, a, idx, o, j, lo, hi)) o = -1;
+  batch.o[lane] = o, batch.j[lane] = j, batch.lo[lane] = lo, batch.hi[lane] = hi;
+  if (o < 0) return;
+  const double* w = l.obs_lin + (long long)o * kBaLin + kBaLinW;
+  const double* v = l.vinv + (long long)j * 6;
+  const double v00 = v[0], v01 = v[1], v02 = v[2], v11 = v[3], v12 = v[4], v22 = v[5];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double w0 = w[3 * r], w1 = w[3 * r + 1], w2 = w[3 * r + 2];
+    batch.y[lane][3 * r] = w0 * v00 + w1 * v01 + w2 * v02;
+    batch.y[lane][3 * r + 1] = w0 * v01 + w1 * v11 + w2 * v12;
+    batch.y[lane][3 * r + 2] = w0 * v02 + w1 * v12 + w2 * v22;
+  }
+}
+
+// One lane's additions for observation o of camera a (point j, track lo .. hi): its entry of U_a, of the two sums of g_a and,
+// along the track, of the blocks of sum Y W' it owns.  acc: the row block [n_cams][36]; y: the observation's 18 numbers of ba_prepare.
+__host__ __device__ __forceinline__ void ba_lane_update(const BaProblem& d, const BaLinear& l, int a, int o, int j, int lo, int hi,
+                                                        int lane, const double* y, double* acc, BaLane& s) {
+  const double* lin = l.obs_lin + (long long)o * kBaLin;
+  const int ea = ((lane - 36 * a) % kBaWave + kBaWave) % kBaWave;             // the entry of block a this lane owns, if < 36
+  if (ea < 36) s.u += lin[ea / 6] * lin[ea % 6] + lin[6 + ea / 6] * lin[6 + ea % 6];
+  if (lane < 6) {
+    const double* gp = l.gp + (long long)j * 3;
+    s.gr += lin[lane] * lin[kBaLinR] + lin[6 + lane] * lin[kBaLinR + 1];
+    s.gy += y[3 * lane] * gp[0] + y[3 * lane + 1] * gp[1] + y[3 * lane + 2] * gp[2];
+  }
+  // the flag and the camera of the next track element are loaded while this one's W is on its way
+  bool ok_next = lo < hi && l.obs_ok[lo] != 0;
+  int b_next = lo < hi ? d.obs_cam[lo] : 0;
+  for (int o2 = lo; o2 < hi; ++o2) {
+    const bool ok = ok_next;
+    const int b = b_next;
+    if (o2 + 1 < hi) ok_next = l.obs_ok[o2 + 1] != 0, b_next = d.obs_cam[o2 + 1];
+    if (!ok || b < 0 || b >= d.n_cams) continue;
+    const int e = ((lane - 36 * b) % kBaWave + kBaWave) % kBaWave;
+    if (e >= 36) continue;
+    const double* w = l.obs_lin + (long long)o2 * kBaLin + kBaLinW + 3 * (e % 6);
+    const double* yr = y + 3 * (e / 6);
+    acc[36 * b + e] += yr[0] * w[0] + yr[1] * w[1] + yr[2] * w[2];
+  }
+}
+
+// What a lane writes when camera a's list is through: its entries of S's row block and of g.
+__host__ __device__ __forceinline__ void ba_lane_finish(int n_cams, unsigned held, double lambda, int a, int lane, const double* acc,
+                                                        const BaLane& s, double* __restrict__ S, double* __restrict__ g) {
+  for (int idx = lane; idx < 36 * n_cams; idx += kBaWave) {
+    const int b = idx / 36, r = idx % 36 / 6, c = idx % 6;
+    double u = 0.0;
+    if (b == a) {
+      u = s.u;
+      // a held parameter, or one that no usable observation moves, has the diagonal 1 and zero rows and columns
+      if (r == c) u = ((held >> r) & 1u) || u == 0.0 ? 1.0 : u + lambda * u;
+    }
+    S[(long long)(6 * a + r) * (6 * n_cams) + 6 * b + c] = u - acc[idx];
+  }
+  if (lane < 6) g[6 * a + lane] = s.gr - s.gy;
+}
+
+// One point's step: dX = -V^-1 (g_p + sum W' dc) over the track in track order.
+__host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const BaLinear& l, const double* __restrict__ dc, int j,
+                                                       double (&dX)[3]) {
+  dX[0] = dX[1] = dX[2] = 0.0;
+  int lo, hi;
+  if (!ba_track(d.offsets, j, d.total, lo, hi)) return;
+  double s[3] = {l.gp[3 * (long long)j], l.gp[3 * (long long)j + 1], l.gp[3 * (long long)j + 2]};
+  for (int o = lo; o < hi; ++o) {
+    if (!l.obs_ok[o]) continue;
+    const int b = d.obs_cam[o];
+    if (b < 0 || b >= d.n_cams) continue;
+    const double* w = l.obs_lin + (long long)o * kBaLin + kBaLinW;
+    const double* e = dc + 6 * (long long)b;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      s[k] += w[k] * e[0] + w[3 + k] * e[1] + w[6 + k] * e[2] + w[9 + k] * e[3] + w[12 + k] * e[4] + w[15 + k] * e[5];
+  }
+  const double* v = l.vinv + (long long)j * 6;
+  dX[0] = -(v[0] * s[0] + v[1] * s[1] + v[2] * s[2]);
+  dX[1] = -(v[1] * s[0] + v[3] * s[1] + v[4] * s[2]);
+  dX[2] = -(v[2] * s[0] + v[4] * s[1] + v[5] * s[2]);
+}
+
+// One camera's update without trigonometry: q = (1, w / 2) / |(1, w / 2)|, R <- R(q) R, t <- t + dt; the intrinsics are copied.
+__host__ __device__ __forceinline__ void ba_camera_step(const double* __restrict__ cam, const double* __restrict__ e,
+                                                        double* __restrict__ out) {
+  const double hx = 0.5 * e[0], hy = 0.5 * e[1], hz = 0.5 * e[2];
+  const double n = sqrt(1.0 + hx * hx + hy * hy + hz * hz);
+  const double w = 1.0 / n, x = hx / n, y = hy / n, z = hz / n;
+  const double Q[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                       2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                       2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[3 * i + k] = Q[3 * i] * cam[k] + Q[3 * i + 1] * cam[3 + k] + Q[3 * i + 2] * cam[6 + k];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) out[9 + i] = cam[9 + i] + e[3 + i];
+#pragma unroll
+  for (int i = 12; i < 16; ++i) out[i] = cam[i];
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_linearize_points_kernel(BaProblem d, double lambda, double* __restrict__ out_vinv,
+                                                                      double* __restrict__ out_gp, double* __restrict__ out_cost,
+                                                                      int32_t* __restrict__ out_count, uint8_t* __restrict__ out_obs_ok,
+                                                                      double* __restrict__ out_obs_lin) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j >= d.n_points) return;
+  double vinv[6], gp[3], cost;
+  const int count = ba_linearize_point(d, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) out_vinv[6 * j + k] = vinv[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out_gp[3 * j + k] = gp[k];
+  out_cost[j] = cost;
+  out_count[j] = count;
+}
+
+// The total cost: the costs added in point order.  One wave; a lane loads, every lane adds the 64 values in order.
+__global__ __launch_bounds__(kBaWave) void ba_total_cost_kernel(const double* __restrict__ cost, int n, double* __restrict__ out_total) {
+  double sum = 0.0;
+  for (int base = 0; base < n; base += kBaWave) {
+    const double v = base + (int)threadIdx.x < n ? cost[base + threadIdx.x] : 0.0;
+    const int m = n - base < kBaWave ? n - base : kBaWave;
+    for (int k = 0; k < m; ++k) sum += __shfl(v, k, kBaWave);
+  }
+  if (threadIdx.x == 0) out_total[0] = sum;
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_reduce_cameras_kernel(BaProblem d, BaLinear l, const int32_t* __restrict__ cam_offsets,
+                                                                    const int32_t* __restrict__ cam_obs,
+                                                                    const int32_t* __restrict__ obs_point, double lambda,
+                                                                    double* __restrict__ out_S, double* __restrict__ out_g) {
+  extern __shared__ __attribute__((aligned(16))) double ba_lds[];             // the row block [n_cams][36]
+  __shared__ BaBatch batch;
+  double* acc = ba_lds;
+  const int a = blockIdx.x, lane = threadIdx.x;
+  for (int idx = lane; idx < 36 * d.n_cams; idx += kBaWave) acc[idx] = 0.0;  // a lane's own entries: no barrier needed
+  BaLane s{0.0, 0.0, 0.0};
+  const int first = cam_offsets[a], last = cam_offsets[a + 1];
+  if (first >= 0 && last >= first && last <= d.total) {     // otherwise the camera is skipped, nothing of it read
+    for (int base = first; base < last; base += kBaWave) {
+      ba_prepare(d, l, cam_obs, obs_point, a, base + lane, last, lane, batch);
+      __syncthreads();
+      const int m = last - base < kBaWave ? last - base : kBaWave;
+      for (int k = 0; k < m; ++k)
+        if (batch.o[k] >= 0) ba_lane_update(d, l, a, batch.o[k], batch.j[k], batch.lo[k], batch.hi[k], lane, batch.y[k], acc, s);
+      __syncthreads();
+    }
+  }
+  ba_lane_finish(d.n_cams, d.const_mask[a], lambda, a, lane, acc, s, out_S, out_g);
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_step_points_kernel(BaProblem d, BaLinear l, const double* __restrict__ dc,
+                                                                 double* __restrict__ out_points, double* __restrict__ out_dx) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j >= d.n_points) return;
+  double dX[3];
+  ba_point_step(d, l, dc, (int)j, dX);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    out_dx[3 * j + k] = dX[k];
+    out_points[3 * j + k] = d.points[3 * j + k] + dX[k];
+  }
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(const double* __restrict__ cams, int n_cams, const double* __restrict__ dc,
+                                                                  double* __restrict__ out_cams) {
+  const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (a >= n_cams) return;
+  ba_camera_step(cams + 16 * a, dc + 6 * a, out_cams + 16 * a);
+}
+
+constexpr int ba_reduce_lds_bytes(int n_cams) { return 36 * n_cams * (int)sizeof(double); }
+static_assert(ba_reduce_lds_bytes(VC_BA_MAX_CAMS) + (int)sizeof(BaBatch) <= 160 * 1024, "the row block of VC_BA_MAX_CAMS cameras must fit the CU's LDS");
+
+}  // namespace
+
+extern "C" {
+
+int vc_ba_linearize_points(const double* cams, int n_cams, const uint8_t* const_mask, const double* points, int n_points,
+                           const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                           double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count, uint8_t* out_obs_ok,
+                           double* out_obs_lin, double* out_total_cost, vc_stream_t stream) {
+  if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_points == 0) return VC_OK;
+  if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !const_mask)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
+  const int blocks = (n_points + kBaWave - 1) / kBaWave;
+  hipLaunchKernelGGL(ba_linearize_points_kernel, dim3((unsigned)blocks), dim3(kBaWave), 0, (hipStream_t)stream, d, lambda, out_vinv,
+                     out_gp, out_cost, out_count, out_obs_ok, out_obs_lin);
+  hipLaunchKernelGGL(ba_total_cost_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
+  return vc::check_launch();
+}
+
+int vc_ba_reduce_cameras(int n_cams, const uint8_t* const_mask, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                         const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point, double lambda,
+                         const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_S,
+                         double* out_g, vc_stream_t stream) {
+  if (n_cams < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_cams == 0) return VC_OK;
+  if (n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
+  if (!const_mask || !cam_offsets || !out_S || !out_g) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!offsets || !vinv || !gp)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  static vc::PerDeviceOnce configured;
+  if (int st = vc::allow_dynamic_lds(configured, ba_reduce_lds_bytes(VC_BA_MAX_CAMS), ba_reduce_cameras_kernel)) return st;
+  const BaProblem d{nullptr, const_mask, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_reduce_cameras_kernel, dim3((unsigned)n_cams), dim3(kBaWave), (size_t)ba_reduce_lds_bytes(n_cams),
+                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, cam_offsets, cam_obs, obs_point, lambda, out_S, out_g);
+  return vc::check_launch();
+}
+
+int vc_ba_step(const double* cams, int n_cams, const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam,
+               int total, const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* dc,
+               double* out_cams, double* out_points, double* out_dx, vc_stream_t stream) {
+  if (n_cams < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_cams == 0 && n_points == 0) return VC_OK;
+  if (n_cams > 0 && (!cams || !dc || !out_cams)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0) {
+    const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+    hipLaunchKernelGGL(ba_step_points_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       d, BaLinear{vinv, gp, obs_ok, obs_lin}, dc, out_points, out_dx);
+  }
+  if (n_cams > 0)
+    hipLaunchKernelGGL(ba_step_cameras_kernel, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       cams, n_cams, dc, out_cams);
+  return vc::check_launch();
+}
+
+}  // extern "C"

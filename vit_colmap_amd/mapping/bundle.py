@@ -1,0 +1,226 @@
+"""Bundle adjustment of the grown model: one global Levenberg-Marquardt over every pose and every point
+by the Schur complement of the points, on the three kernels of csrc/bundle.hip, whose header (include/vitcolmap_hip.h) states
+the rule; then the rescale to a unit baseline and the filter of observations and points.  Specification:
+tests/util_bundle.py.  This build's own published rule; parity with COLMAP's bundle adjuster and with Ceres is unpinned.
+Still missing on the way to a mapper: adjustment per round and local adjustment, re-triangulation, merging of points, a robust
+loss, refined intrinsics, distortion models.
+
+Where the work runs
+  HIP     per iteration vc_ba_linearize_points (one point per lane: residuals, Jacobians, V^-1, the cost), vc_ba_reduce_cameras
+          (one workgroup per camera: the reduced system S, g) and vc_ba_step (back-substitution, the trig-free pose update)
+  torch   the solve of S dc = -g in float64 on the device (cholesky_ex + cholesky_solve) and the loop's scalars; the accept /
+          reject decision is the only host read of an iteration: one number, the candidate's cost (NaN where S did not factor)
+  host    Python / numpy: the model's arrays, the camera-major index, the gauge, the rescale, the filter
+"""
+import copy
+import logging
+
+import numpy as np
+
+from ..database.colmap_db import _quat_to_rot
+from ..matching._common import MAX_ERROR
+from ..matching.essential import rot_to_quat
+from .absolute_pose import FILTER_MIN_TRI_ANGLE
+from .grow import build_sparse_model
+from .seed import SparseModel, _pixel_errors, _read_database
+
+logger = logging.getLogger(__name__)
+
+BA_LAMBDA0 = 1e-4
+BA_LAMBDA_MIN, BA_LAMBDA_MAX = 1e-12, 1e12
+BA_MAX_ITERATIONS = 25               # linearisations
+BA_REL_DECREASE = 1e-8
+HELD_ALL = 63                        # bits 0-2: the rotation, bits 3-5: the translation
+MIN_TRI_ANGLE_TAN2 = float(np.tan(FILTER_MIN_TRI_ANGLE) ** 2)
+
+
+def camera_index(obs_cam, offsets, n_cams):
+    """-> cam_offsets int32 (n_cams + 1,), cam_obs int32 (total,): per camera its observations in ascending order (one whose
+    slot is outside [0, n_cams) belongs to none, the tail of cam_obs is then -1), obs_point int32 (total,)."""
+    obs_cam, offsets = np.asarray(obs_cam, np.int64), np.asarray(offsets, np.int64)
+    total = len(obs_cam)
+    inside = (obs_cam >= 0) & (obs_cam < n_cams)
+    order = np.argsort(np.where(inside, obs_cam, n_cams), kind="stable")[:int(inside.sum())]
+    cam_obs = np.full(total, -1, np.int32)
+    cam_obs[:len(order)] = order
+    cam_offsets = np.concatenate([[0], np.cumsum(np.bincount(obs_cam[inside], minlength=n_cams))]).astype(np.int32)
+    lo, hi = offsets[:-1], offsets[1:]
+    valid = (lo >= 0) & (hi >= lo) & (hi <= total)
+    obs_point = np.full(total, -1, np.int32)
+    if valid.all() and len(lo) and lo[0] == 0 and hi[-1] == total and np.array_equal(lo[1:], hi[:-1]):
+        obs_point[:] = np.repeat(np.arange(len(lo), dtype=np.int32), hi - lo)
+    else:
+        for j in np.nonzero(valid)[0]:
+            obs_point[lo[j]:hi[j]] = j
+    return cam_offsets, cam_obs, obs_point
+
+
+class _Buffers:
+    """The outputs of one vc_ba_linearize_points call; two of them alternate between the current parameters and the candidate."""
+
+    def __init__(self, torch, n_cams, n_points, total, device):
+        f64 = dict(dtype=torch.float64, device=device)
+        self.cams, self.points = torch.zeros((n_cams, 16), **f64), torch.zeros((n_points, 3), **f64)
+        self.vinv, self.gp, self.cost = torch.zeros((n_points, 6), **f64), torch.zeros((n_points, 3), **f64), torch.zeros(n_points, **f64)
+        self.count = torch.zeros(n_points, dtype=torch.int32, device=device)
+        self.obs_ok = torch.zeros(total, dtype=torch.uint8, device=device)
+        self.obs_lin = torch.zeros((total, 32), **f64)
+        self.total_cost = torch.zeros(1, **f64)
+
+
+def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cuda", max_iterations=BA_MAX_ITERATIONS):
+    """cams float64 (n_cams, 16) as vc_triangulate_tracks has them, points float64 (n_points, 3), offsets int32 (n_points + 1,),
+    obs_cam int32 (total,), obs_xy float64 (total, 2), const_mask uint8 (n_cams,) (bit i: pose parameter i is held), numpy
+    -> cams, points (numpy, adjusted) and the report dict(iterations, accepted_steps, initial_cost, final_cost, final_lambda,
+    decisions).  Raises ValueError above VC_BA_MAX_CAMS cameras."""
+    import torch
+
+    from .. import _lib
+
+    cams = np.ascontiguousarray(cams, np.float64).reshape(-1, 16)
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    offsets, obs_cam = np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(obs_cam, np.int32)
+    obs_xy, const_mask = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2), np.ascontiguousarray(const_mask, np.uint8)
+    n_cams, n_points, total = len(cams), len(points), len(obs_cam)
+    if n_cams > _lib.VC_BA_MAX_CAMS:
+        raise ValueError(f"bundle_adjust: {n_cams} cameras, the reduction kernel holds at most {_lib.VC_BA_MAX_CAMS} (VC_BA_MAX_CAMS)")
+    if offsets.shape != (n_points + 1,) or obs_xy.shape != (total, 2) or const_mask.shape != (n_cams,):
+        raise ValueError("bundle_adjust needs offsets (n_points + 1,), obs_cam (total,), obs_xy (total, 2), const_mask (n_cams,)")
+    report = dict(iterations=0, accepted_steps=0, initial_cost=0.0, final_cost=0.0, final_lambda=BA_LAMBDA0, decisions=[])
+    if n_cams == 0 or n_points == 0:
+        return cams.copy(), points.copy(), report
+    lib = _lib.load()
+    dev = torch.device(device)
+
+    def on_device(a):
+        return torch.from_numpy(a).to(dev)
+
+    cam_offsets, cam_obs, obs_point = (on_device(a) for a in camera_index(obs_cam, offsets, n_cams))
+    d_offsets, d_obs_cam, d_obs_xy, d_mask = on_device(offsets), on_device(obs_cam), on_device(obs_xy), on_device(const_mask)
+    free = on_device(np.array([[not (int(m) >> i) & 1 for i in range(6)] for m in const_mask], bool).reshape(-1))
+    cur, cand = _Buffers(torch, n_cams, n_points, total, dev), _Buffers(torch, n_cams, n_points, total, dev)
+    cur.cams.copy_(on_device(cams)), cur.points.copy_(on_device(points))
+    S = torch.zeros((6 * n_cams, 6 * n_cams), dtype=torch.float64, device=dev)
+    g = torch.zeros(6 * n_cams, dtype=torch.float64, device=dev)
+    dx = torch.zeros((n_points, 3), dtype=torch.float64, device=dev)
+    p, stream = _lib.ptr, _lib.stream_ptr()
+
+    def linearize(b, lam):
+        _lib.check(lib.vc_ba_linearize_points(p(b.cams), n_cams, p(d_mask), p(b.points), n_points, p(d_offsets), p(d_obs_cam), p(d_obs_xy),
+                                              total, float(lam), p(b.vinv), p(b.gp), p(b.cost), p(b.count), p(b.obs_ok), p(b.obs_lin),
+                                              p(b.total_cost), stream), "vc_ba_linearize_points")
+
+    lam = BA_LAMBDA0
+    linearize(cur, lam)
+    cost = initial = float(cur.total_cost.item())
+    iterations, decisions = 1, []
+    while iterations < max_iterations:
+        _lib.check(lib.vc_ba_reduce_cameras(n_cams, p(d_mask), n_points, p(d_offsets), p(d_obs_cam), total, p(cam_offsets), p(cam_obs),
+                                            p(obs_point), float(lam), p(cur.vinv), p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(S), p(g),
+                                            stream), "vc_ba_reduce_cameras")
+        L, info = torch.linalg.cholesky_ex(S)
+        dc = torch.cholesky_solve(-g[:, None], L)[:, 0]
+        factored = (info == 0) & torch.isfinite(dc).all()
+        # a held parameter's step is exactly 0; a system that did not factor still takes a (finite, zero) step through the
+        # kernels, whose cost is then replaced by NaN: the decision stays one scalar read
+        dc = torch.where(free & factored, dc, torch.zeros_like(dc)).contiguous()
+        _lib.check(lib.vc_ba_step(p(cur.cams), n_cams, p(cur.points), n_points, p(d_offsets), p(d_obs_cam), total, p(cur.vinv), p(cur.gp),
+                                  p(cur.obs_ok), p(cur.obs_lin), p(dc), p(cand.cams), p(cand.points), p(dx), stream), "vc_ba_step")
+        lower = max(lam / 10, BA_LAMBDA_MIN)
+        linearize(cand, lower)
+        iterations += 1
+        c = float(torch.where(factored, cand.total_cost[0], torch.full_like(cand.total_cost[0], float("nan"))).item())
+        accepted = bool(np.isfinite(c) and c < cost)
+        decisions.append(accepted)
+        if accepted:
+            decrease = (cost - c) / cost
+            cur, cand, cost, lam = cand, cur, c, lower
+            if decrease < BA_REL_DECREASE:
+                break
+        else:
+            lam = lam * 10
+            if lam > BA_LAMBDA_MAX or iterations >= max_iterations:
+                break
+            linearize(cur, lam)
+            iterations += 1
+    report = dict(iterations=iterations, accepted_steps=int(sum(decisions)), initial_cost=initial, final_cost=cost, final_lambda=lam,
+                  decisions=decisions)
+    return cur.cams.cpu().numpy(), cur.points.cpu().numpy(), report
+
+
+def _gpu_bundle(cams, points, offsets, obs_cam, obs_xy, const_mask, device):
+    return bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device)
+
+
+def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
+    """Some pair of the centres sees X under enough parallax (the test of §4.2j)."""
+    gq = X - centres
+    dots = gq @ gq.T
+    cross2 = (np.cross(gq[:, None, :], gq[None, :, :]) ** 2).sum(axis=2)
+    return bool(np.any(np.triu(np.ones_like(dots, bool), 1) & ((dots <= 0) | (cross2 >= tan2 * dots * dots))))
+
+
+def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
+                         grown=None) -> SparseModel:
+    """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
+    is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
+    Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
+    (cams, points, report)` on numpy arrays replaces the adjustment (tests), the other three as in build_sparse_model."""
+    bundle_fn = bundle_fn or _gpu_bundle
+    if grown is None:
+        grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn)
+    _, _, K, _, _ = _read_database(database_path)
+    ids, pids = sorted(grown.images), sorted(grown.points3D)
+    slot = {i: s for s, i in enumerate(ids)}
+    cams = np.stack([np.concatenate([_quat_to_rot(grown.images[i]["qvec"]).reshape(9), np.asarray(grown.images[i]["tvec"], np.float64),
+                                     [K[i][0, 0], K[i][1, 1], K[i][0, 2], K[i][1, 2]]]) for i in ids])
+    points = np.array([grown.points3D[pid]["xyz"] for pid in pids], np.float64).reshape(-1, 3)
+    tracks = [grown.points3D[pid]["track"] for pid in pids]
+    offsets = np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.int32)
+    obs_cam = np.array([slot[i] for t in tracks for i, _ in t], np.int32)
+    obs_xy = np.array([grown.images[i]["xys"][kp] for t in tracks for i, kp in t], np.float64).reshape(-1, 2)
+
+    # the gauge: the pair's first image held, of the second the translation coordinate of largest magnitude
+    # [recalled: COLMAP holds one coordinate of the second image]
+    a, b = (slot[i] for i in grown.initial_pair)
+    mask = np.zeros(len(ids), np.uint8)
+    mask[a] = HELD_ALL
+    mask[b] = 1 << (3 + int(np.argmax(np.abs(cams[b, 9:12]))))
+    cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device)
+    cams, points = np.array(cams, np.float64), np.array(points, np.float64)
+
+    # every t and X rescaled so that the pair's baseline is 1 again (§4.2i)
+    centre = [-(cams[s, :9].reshape(3, 3).T @ cams[s, 9:12]) for s in (a, b)]
+    scale = 1.0 / np.linalg.norm(centre[1] - centre[0])
+    cams[:, 9:12] = cams[:, 9:12] * scale
+    points = points * scale
+
+    model = SparseModel(initial_pair=grown.initial_pair, rounds=grown.rounds,
+                        bundle_adjustment={k: v for k, v in report.items() if k != "decisions"})
+    model.cameras = copy.deepcopy(grown.cameras)
+    for i in ids:
+        im, R = grown.images[i], cams[slot[i], :9].reshape(3, 3)
+        model.images[i] = dict(qvec=rot_to_quat(R), tvec=cams[slot[i], 9:12].copy(), camera_id=im["camera_id"], name=im["name"],
+                               xys=np.array(im["xys"], np.float64), point3D_ids=np.full(len(im["xys"]), -1, np.int64))
+    # the filter: observations beyond MAX_ERROR px under the final poses, then points left with fewer than two observations or
+    # without a pair of enough parallax
+    dropped_obs = 0
+    for j, pid in enumerate(pids):
+        rows = cams[obs_cam[offsets[j]:offsets[j + 1]]]
+        err = np.array([_pixel_errors(K[i], row[:9].reshape(3, 3), row[9:12], points[j][None], obs_xy[o][None])[0]
+                        for o, row, (i, _) in zip(range(offsets[j], offsets[j + 1]), rows, tracks[j])])
+        keep = err <= MAX_ERROR
+        dropped_obs += int((~keep).sum())
+        if keep.sum() < 2:
+            continue
+        centres = -np.einsum("nji,nj->ni", rows[keep, :9].reshape(-1, 3, 3), rows[keep, 9:12])
+        if not _wide(points[j], centres):
+            continue
+        track = [node for node, k in zip(tracks[j], keep) if k]
+        for i, kp in track:
+            model.images[i]["point3D_ids"][kp] = pid
+        model.points3D[pid] = dict(xyz=points[j].copy(), rgb=(0, 0, 0), error=float(err[keep].mean()), track=[(int(i), int(kp)) for i, kp in track])
+    model.bundle_adjustment.update(filtered_observations=dropped_obs, filtered_points=len(pids) - len(model.points3D))
+    logger.info("Bundle adjustment: %d linearisations, %d accepted steps, cost %.6g -> %.6g", report["iterations"],
+                report["accepted_steps"], report["initial_cost"], report["final_cost"])
+    return model

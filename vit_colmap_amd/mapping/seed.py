@@ -1,7 +1,7 @@
 """The seed model: an initial pair, that pair's triangulated points, every other image registered against
 those points in one batched launch, written as a COLMAP text model.  The seed model itself triangulates no point after the
-seed and registers once; mapping/grow.py (§4.2j) grows it by rounds of triangulation and registration.  Neither is a mapper:
-there is no bundle adjustment.  Specification: tests/util_absolute_pose.py (`seed_model`).  This build's own published rule;
+seed and registers once; mapping/grow.py (§4.2j) grows it by rounds of triangulation and registration and mapping/bundle.py
+(§4.2k) adjusts the grown model once.  None of them is a mapper.  Specification: tests/util_absolute_pose.py (`seed_model`).  This build's own published rule;
 parity with COLMAP's mapper is unpinned.
 
 Where the work runs
@@ -37,6 +37,7 @@ class SparseModel:
     points3D: dict = field(default_factory=dict)
     initial_pair: tuple = None
     rounds: int = None                   # growth rounds that added a point or an image (§4.2j); None: a seed model
+    bundle_adjustment: dict = None       # the report of the adjustment (§4.2k); None: a model that was not adjusted
 
     def mean_track_length(self):
         return float(np.mean([len(p["track"]) for p in self.points3D.values()])) if self.points3D else 0.0
@@ -44,7 +45,8 @@ class SparseModel:
     def stats(self):
         s = dict(initial_pair=list(self.initial_pair) if self.initial_pair else None, registered_images=len(self.images),
                  num_points3D=len(self.points3D), mean_track_length=self.mean_track_length())
-        return s if self.rounds is None else dict(s, rounds=self.rounds)
+        s = s if self.rounds is None else dict(s, rounds=self.rounds)
+        return s if self.bundle_adjustment is None else dict(s, bundle_adjustment=dict(self.bundle_adjustment))
 
     # COLMAP's text layout [recalled: colmap/src/colmap/scene/reconstruction_io.cc]; floats are written with repr, so a model
     # reads back equal

@@ -72,6 +72,9 @@ class Pipeline:
             raise ValueError(f"num_neighbors must be at least 1 (got {num_neighbors})")
         seed_model = bool(getattr(self.config.reconstruction, "seed_model", False))
         sparse_model = bool(getattr(self.config.reconstruction, "sparse_model", False))
+        bundle_adjustment = bool(getattr(self.config.reconstruction, "bundle_adjustment", False))
+        if bundle_adjustment and not sparse_model:              # it adjusts the grown model (§4.2k)
+            raise ValueError("bundle_adjustment needs reconstruction.sparse_model (--sparse-model)")
         for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
             if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
                 continue
@@ -128,7 +131,7 @@ class Pipeline:
         if seed_model:                                          # under torchrun only rank 0 arrives here
             self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
         if sparse_model:
-            self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
+            self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment)
 
         reconstructions = None
         if self.config.do_reconstruction:
@@ -168,8 +171,9 @@ class Pipeline:
         logger.info("Seed model: pair %s, %d images, %d points", *[model.stats()[k] for k in
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
-    def _write_sparse_model(self, db_path, output_dir, device):
-        """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing."""
+    def _write_sparse_model(self, db_path, output_dir, device, adjust=False):
+        """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
+        `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted."""
         from ..mapping.grow import build_sparse_model
 
         try:
@@ -181,6 +185,14 @@ class Pipeline:
         self.last_stats = dict(self.last_stats or {}, sparse_model=model.stats())
         logger.info("Sparse model: pair %s, %d images, %d points, %d rounds", *[model.stats()[k] for k in
                                                                                  ("initial_pair", "registered_images", "num_points3D", "rounds")])
+        if adjust:
+            from ..mapping.bundle import build_adjusted_model
+
+            adjusted = build_adjusted_model(str(db_path), device=device, grown=model)
+            adjusted.write_text(str(Path(output_dir) / "sparse" / "adjusted"))
+            self.last_stats = dict(self.last_stats, bundle_adjustment=adjusted.stats())
+            logger.info("Adjusted model: %d images, %d points, cost %.6g -> %.6g", len(adjusted.images), len(adjusted.points3D),
+                        adjusted.bundle_adjustment["initial_cost"], adjusted.bundle_adjustment["final_cost"])
 
     def extract_and_export_metrics(self, db_path, output_dir, reconstructions, dataset, scene, results_dir=None):
         """Database metrics -> `{results_dir}/{dataset}/{scene}/{extractor}.json` + summary.csv row
@@ -226,6 +238,9 @@ def main() -> None:
     ap.add_argument("--sparse-model", dest="sparse_model", action="store_true",
                     help="write output/sparse/grown: the seed model grown by rounds of track triangulation and registration "
                          "(needs --prior-focal-length and --relative-pose)")
+    ap.add_argument("--bundle-adjustment", dest="bundle_adjustment", action="store_true",
+                    help="with --sparse-model: also write output/sparse/adjusted, the grown model after one global bundle "
+                         "adjustment, rescaled to a unit baseline and filtered")
     ap.add_argument("--matcher", choices=list(MATCHER_TYPES), default="exhaustive",
                     help="exhaustive: every image pair; retrieval: each image against its --num-neighbors nearest images")
     ap.add_argument("--num-neighbors", dest="num_neighbors", type=int, default=20,
