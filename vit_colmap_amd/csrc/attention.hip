@@ -7,6 +7,9 @@
 // output out [B][N][H*64] bf16   — exactly what the projection GEMM reads.
 //
 // One workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 queries.
+//   * units (128 QT query rows of one (batch, head)) are numbered (batch, head)-major and dealt to the launch slots by
+//     vc::xcd_tile, so that every XCD works through a contiguous run of units: the units that stream the same K / V run on
+//     one XCD at about the same time, and its L2 serves K / V to all of them for one fetch from beyond it;
 //   * swapped product: S^T = K Q^T (v_mfma_f32_32x32x16_bf16, A = K fragment from LDS, B = Q
 //     fragment kept in registers), so a lane holds 32 scores of ONE query (its partner lane,
 //     l ^ 32, the other 32 of the 64-key block): the row max / row sum are lane-local plus one
@@ -85,12 +88,14 @@ constexpr float kLMaxPerKey = 64.0f;   // 2^kLazyTh: the fast pass is final for 
 template <int QT, bool LAZY>
 __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const __bf16* __restrict__ qkv,
                                                                            __bf16* __restrict__ out, int N, int H,
-                                                                           float scale_log2e, int unit0, int nqb) {
+                                                                           float scale_log2e, int n_units, int nqb) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[3][2][kTileBytes];  // ring slot x [K | V]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
-  // work unit = (batch * head, block of 128 QT query rows), numbered bh-major so that neighbouring workgroups share K / V
-  const int unit = unit0 + (int)blockIdx.x;
+  // work unit = (batch * head, block of 128 QT query rows), numbered bh-major: the units of one (batch, head) read the same
+  // K / V.  Launch slots b and b + 8 share an XCD (and its L2), b and b + 1 never do, so the slot -> unit map gives every XCD
+  // a contiguous run of units: the workgroups resident on an XCD at one time then cover a few whole (batch, head) runs.
+  const int unit = vc::xcd_tile((int)blockIdx.x, n_units);
   const int bh = unit / nqb, b = bh / H, h = bh - b * H;
   const int q_base = (unit - bh * nqb) * (kQB * QT);
   if (q_base >= N) return;   // (the second half of a ragged last block when the tail runs as 128-row units)
@@ -202,6 +207,8 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       // LAZY: the running maximum of the lane's query (log2 units) is subtracted by the MFMA itself
+      // (the 30 v_mov_b32 + 2 v_cndmask_b32 per block this costs can be had from a lane-private LDS slot with the bits
+      // unchanged: -3.8 % of the kernel alone, but its step times did not separate from this form's.  DESIGN.md §8.1)
       float c0 = (LAZY && blk > 0) ? -m_run[qt] : 0.f;
       asm volatile("" : "+v"(c0));   // one select, then plain moves (left alone the compiler emits a v_cndmask per register)
 #pragma unroll
@@ -363,7 +370,7 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
   // and writes whole rows: 8 queries x 128 contiguous bytes (one head's 64 d) per store instruction, 4 QT per lane.
   typedef uint32_t v4u32a __attribute__((ext_vector_type(4)));
   __syncthreads();
-  uint8_t* const stg = (uint8_t*)lds + wave * (QT * 4096);
+  uint8_t* const stg = (uint8_t*)lds + wave_u * (QT * 4096);   // (the scalar copy: no VGPR holds the wave index across the passes)
   auto stg_at = [&](int row, int slot16) { return stg + row * 128 + ((slot16 ^ ((row >> 1) & 7)) << 4); };
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
@@ -392,7 +399,7 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
   }
   {
     const int lrow = lane >> 3, lslot = lane & 7;
-    const int q_wave0 = q_base + wave * (kQW * QT);
+    const int q_wave0 = q_base + wave_u * (kQW * QT);
 #pragma unroll
     for (int i = 0; i < 4 * QT; ++i) {
       const int row = 8 * i + lrow;
@@ -421,17 +428,17 @@ int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int
   __bf16* po = (__bf16*)out;
   hipStream_t st = (hipStream_t)stream;
   const int bh = batch * n_heads;
-#define VC_ATT(Q, L, UNITS, UNIT0, NQB) \
-  hipLaunchKernelGGL((attention_kernel<Q, L>), dim3(UNITS), dim3(256), 0, st, pq, po, n_tokens, n_heads, scale_log2e, UNIT0, NQB)
+#define VC_ATT(Q, L, UNITS, NQB) \
+  hipLaunchKernelGGL((attention_kernel<Q, L>), dim3(UNITS), dim3(256), 0, st, pq, po, n_tokens, n_heads, scale_log2e, UNITS, NQB)
   if (qt == 1) {
     const int nqb = (n_tokens + kQB - 1) / kQB;
-    if (q_prescaled) VC_ATT(1, true, nqb * bh, 0, nqb); else VC_ATT(1, false, nqb * bh, 0, nqb);
+    if (q_prescaled) VC_ATT(1, true, nqb * bh, nqb); else VC_ATT(1, false, nqb * bh, nqb);
     return vc::check_launch();
   }
   // (Running the units of the last, partial "round" — 1800 units over 512 resident workgroups — as half-size QT = 1 units was
   // measured: 241.5 vs 239.0 us, no gain; workgroups do not advance in lockstep rounds.  One launch.)
   const int nqb2 = (n_tokens + 2 * kQB - 1) / (2 * kQB);
-  if (q_prescaled) VC_ATT(2, true, nqb2 * bh, 0, nqb2); else VC_ATT(2, false, nqb2 * bh, 0, nqb2);
+  if (q_prescaled) VC_ATT(2, true, nqb2 * bh, nqb2); else VC_ATT(2, false, nqb2 * bh, nqb2);
 #undef VC_ATT
   return vc::check_launch();
 }

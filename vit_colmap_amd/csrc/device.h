@@ -1,4 +1,4 @@
-// Shared device-side idioms of the kernels: the int8 MFMA register types, LDS-DMA issue, the wave-uniform LDS base, the cursor of the constexpr LDS plans and bf16 bit conversions.
+// Shared device-side idioms of the kernels: the int8 MFMA register types, LDS-DMA issue, the wave-uniform LDS base, the cursor of the constexpr LDS plans, the XCD-aware work order and bf16 bit conversions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,6 +79,16 @@ struct LdsCursor {
     return off;
   }
 };
+
+// XCD-aware work order: the 8 XCDs take workgroups round-robin (blocks b and b + 8 share an L2, b and b + 1 never do), so
+// launch slot `slot` of `n_tiles` gets the tile that gives each XCD a contiguous run of tiles: what an XCD works on at one
+// time is then neighbouring tiles, whose common operand (the staged GEMMs' x rows, the attention units' K / V) is in its L2.
+// A bijection of [0, n_tiles) for every n_tiles; placement is not a contract, so this may change speed only.
+__device__ __forceinline__ int xcd_tile(int slot, int n_tiles) {
+  const int xcd = slot & 7, idx = slot >> 3;
+  const int q = n_tiles >> 3, r = n_tiles & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
 

@@ -105,14 +105,6 @@ __device__ __forceinline__ float swiglu_f32(float a, float b) {
   return a * __builtin_amdgcn_rcpf(1.0f + e) * b;
 }
 
-// XCD-aware tile order of the two staged kernels: the 8 XCDs take workgroups round-robin, so give each XCD a contiguous
-// run of tiles (feature tiles fastest: the tiles an XCD works on at one time share x rows in its L2).
-__device__ __forceinline__ int xcd_tile(int slot, int n_tiles) {
-  const int xcd = slot & 7, idx = slot >> 3;
-  const int q = n_tiles >> 3, r = n_tiles & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 // Fragment addressing of the two staged kernels in an image of 128-byte rows (64 k): for k-substep ks a lane reads row
 // row0 + (l & 15) of a 16-row block, 16-byte chunk 4 ks + (l >> 4), stored at chunk ^ (row & 7).  row0 % 8 == 0, so the rows
 // of all 16-row blocks below it share the swizzle: one offset per k-substep, the blocks are 2048 bytes apart.
@@ -139,7 +131,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const __bf16* __restrict__
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;
 
-  const int tile = xcd_tile(blockIdx.x, n_tiles);
+  // XCD-aware tile order of the two staged kernels (vc::xcd_tile), feature tiles fastest: the tiles an XCD works on at one
+  // time share x rows in its L2
+  const int tile = vc::xcd_tile(blockIdx.x, n_tiles);
   const int tm = tile / n_tiles_n, tn = tile - tm * n_tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   // EPI_SWIGLU: the tile makes output columns j0 .. j0 + 63; W image rows [64 wn, 64 wn + 32) are gate rows
@@ -315,7 +309,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const __bf16* __restric
   // that epilogues do not coincide — the output writes are not a shared-HBM burst problem; every start delay came back as
   // added time, 1268 -> 1344 us per ViT-B layer.)
   for (int slot = blockIdx.x; slot < n_tiles; slot += gridDim.x) {
-  const int tile = xcd_tile(slot, n_tiles);
+  const int tile = vc::xcd_tile(slot, n_tiles);
   const int tm = tile / n_tiles_n, tn = tile - tm * n_tiles_n;
   const int m0 = tm * G2M, n0 = tn * G2N;
 
