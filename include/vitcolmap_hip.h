@@ -293,7 +293,8 @@ int vc_triangulate_tracks(const double* obs_xy, const int32_t* obs_cam, const in
  * every point, by the Schur complement of the points; float64 in single operations in the written order, the only library
  * call is sqrt, no atomics: two calls return the same bytes.  The caller solves S dc = -g between the last two and runs the
  * loop (vit_colmap_amd/mapping/bundle.py).  Specification: tests/util_bundle.py.  This build's own published rule: parity
- * with COLMAP / Ceres is unpinned.  Intrinsics are never refined; the loss is the plain squared pixel error.
+ * with COLMAP / Ceres is unpinned.  These three never refine an intrinsic (the border below does); the loss is the plain
+ * squared pixel error.
  *   cams        [n_cams][16] float64 as vc_triangulate_tracks has them: R row-major, t, fx, fy, cx, cy
  *   const_mask  [n_cams] uint8: bit i set = pose parameter i is held (0-2 the rotation w, 3-5 the translation)
  *   points      [n_points][3] float64
@@ -341,6 +342,58 @@ int vc_ba_reduce_cameras(int n_cams, const uint8_t* const_mask, int n_points, co
 int vc_ba_step(const double* cams, int n_cams, const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam,
                int total, const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* dc,
                double* out_cams, double* out_points, double* out_dx, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Bundle adjustment with refined intrinsics ("The border"): the three entry points above never move
+ * an intrinsic; these three add theta_g = (fx, fy, cx, cy) of every group of cameras as a border of the reduced system,
+ *   [[S, B], [B', C]] (dc, dtheta) = -(g, h),  S and g from vc_ba_reduce_cameras unchanged,
+ * which the caller assembles and solves.  Same arithmetic conventions; no atomics, every sum has one owner and the written
+ * order, two calls return the same bytes.  Specification: tests/util_bundle_intr.py.  This build's own rule, parity unpinned.
+ *   cam_group   [n_cams] int32: the group of each camera slot; outside [0, n_groups): the slot's intrinsics are held
+ *   intr_mask   [n_groups] uint8: bits 0-3 set = fx, fy, cx, cy held; bit 4 = tied: fx and fy are one parameter, column 0 of
+ *               J_theta is d r / d fx + d r / d fy, parameter 1 counts as held, the step of parameter 0 goes to both
+ *   vinv, gp, obs_ok, obs_lin: what vc_ba_linearize_points wrote for the same parameters and damping
+ * Per usable observation (obs_ok set, slot in the table): x = Xc_x / Xc_z, y = Xc_y / Xc_z, J_theta = [[x, 0, 1, 0],
+ * [0, y, 0, 1]], held columns 0; tied: column 0 = (x, y), column 1 = 0.
+ * vc_ba_linearize_intrinsics (one point per lane, the groups outside, the track inside):
+ *   out_obs_xn [total][2]   (x, y) of a usable observation, 0 otherwise
+ *   out_T      [n_points][n_groups][12]   T_jg = sum J_theta' J_p (4x3 row-major) over the group's observations in track order
+ *   out_terms  [24 G + 16 G^2][n_points], G = n_groups, entry-major: rows 16 g + 4 i + k: q_jg = sum J_theta' J_theta; 16 G + 4 g
+ *              + i: hq_jg = sum J_theta' r; 20 G + 4 g + i: T_jg V_j^-1 g_pj; 24 G + 16 (g G + g') + 4 i + k: T_jg V_j^-1 T_jg''
+ *              (T V^-1 formed first, as Y = W V^-1 is).  A skipped point has T and its terms 0.
+ * vc_ba_reduce_border:
+ *   out_sums   [24 G + 16 G^2]: every row of the terms added over the points in ascending order (one wave per row, the total
+ *              cost's scheme)
+ *   out_C      [4 G][4 G], out_h [4 G]: Q_g = sum_j q_jg with Q_ii += lambda Q_ii; C_gg' = delta_gg' Q_g - sum_j T V^-1 T';
+ *              h_g = sum_j hq_jg - sum_j T V^-1 g_p (the two sums kept apart).  A held parameter, parameter 1 of a tied group
+ *              and one with Q_ii = 0 have the diagonal 1, zero rows and columns, h = 0 and out_free [4 G] uint8 = 0
+ *   out_B      [6 n_cams][4 G]: per camera a over cam_obs in ascending order B_ag = sum [g = g(a)] J_c' J_theta - sum Y T_j(o)g',
+ *              Y = W V^-1 as vc_ba_reduce_cameras forms it, the two sums kept apart; one wave per camera, entry 24 g + 4 r + i
+ *              of the row block owned by lane (24 g + 4 r + i) mod 64 in a register
+ * vc_ba_step_intrinsics: dtheta [4 G] (a parameter that does not move: 0).  out_dx = -V^-1 (g_p + sum W' dc + sum_g T_jg'
+ * dtheta_g), the cameras in track order, then the groups ascending; out_cams: vc_ba_step's pose update, then (fx, fy, cx, cy)
+ * += dtheta of the slot's group (tied: dtheta_0 to fx and fy); out_valid [n_cams] uint8: 0 where the slot's group is in
+ * [0, n_groups) and its new fx or fy is not finite or not positive (the loop rejects such a candidate).
+ * n_groups <= VC_BA_MAX_GROUPS (a lane of the B pass keeps ceil(24 G / 64) = 3 entries in registers and the terms grow with
+ * 16 G^2 numbers per point), VC_ERR_UNSUPPORTED above; vc_ba_reduce_border also above VC_BA_MAX_CAMS.  A size of 0 (n_points or
+ * n_groups for the first, n_groups for the second, n_cams and n_points for the third): VC_OK.  A null pointer that a size
+ * needs, a negative size, a bad lambda: VC_ERR_INVALID_ARG without a launch.  Offsets as above; every index is checked.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_BA_MAX_GROUPS 8
+int vc_ba_linearize_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                               const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                               const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_obs_xn,
+                               double* out_T, double* out_terms, vc_stream_t stream);
+int vc_ba_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
+                        const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
+                        double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
+                        const double* T, const double* terms, double* out_sums, double* out_B, double* out_C, double* out_h,
+                        uint8_t* out_free, vc_stream_t stream);
+int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                          const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
+                          const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc,
+                          const double* dtheta, double* out_cams, double* out_points, double* out_dx, uint8_t* out_valid,
+                          vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces

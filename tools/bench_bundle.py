@@ -5,7 +5,9 @@ the 12-view windowed scene (tests/util_mapper.py, truth_pairs rows: 12 cameras, 
 synthetic arc of --cams cameras (default 200) 0.5 degrees apart with --points points (default 20 000), each seen by 3-8
 neighbouring cameras, 0.5 px noise, poses and points moved off the truth.  A kernel's time is the median over --iters launches
 after 3 warm-up launches, by device events; the loop's is wall clock around bundle_adjust, synchronised, the median of --loops
-runs.  Prints one JSON line.  Needs a GPU."""
+runs.  --refine-focal: the same two problems with every focal 3 % off and one tied group of intrinsics refined (§4.2k, "The
+border"): also the three entry points of the border and the bordered solve, and the refined loop beside the plain loop of the
+same build, the two alternating.  Prints one JSON line.  Needs a GPU."""
 import argparse
 import json
 import os
@@ -78,8 +80,11 @@ def device_ms(fn, iters):
     return float(np.median(times))
 
 
-def measure(problem, iters, loops):
+def measure(problem, iters, loops, refine=False):
     cams, points, offsets, obs_cam, obs_xy, mask = problem
+    if refine:
+        cams = cams.copy()
+        cams[:, 12:14] *= 1.03
     c, n, t = len(cams), len(points), len(obs_cam)
     lib = _lib.load()
     dev = torch.device("cuda")
@@ -108,17 +113,61 @@ def measure(problem, iters, loops):
                                   p(out_points), p(dx), stream), "vc_ba_step")
 
     out = dict(cameras=c, points=n, observations=t)
-    for name, fn in (("linearize_ms", linearize), ("reduce_ms", reduce), ("solve_ms", solve), ("step_ms", step)):
+    stages = [("linearize_ms", linearize), ("reduce_ms", reduce), ("solve_ms", solve), ("step_ms", step)]
+    groups = {}
+    if refine:                                                        # one tied group, the principal point held
+        f64 = dict(dtype=torch.float64, device=dev)
+        groups = dict(cam_group=np.zeros(c, np.int32), intr_mask=np.array([16 | 4 | 8], np.uint8))
+        dg, di = torch.from_numpy(groups["cam_group"]).to(dev), torch.from_numpy(groups["intr_mask"]).to(dev)
+        xn, T, terms, sums = torch.zeros((t, 2), **f64), torch.zeros((n, 1, 12), **f64), torch.zeros((40, n), **f64), torch.zeros(40, **f64)
+        B, C, h, free = torch.zeros((6 * c, 4), **f64), torch.zeros((4, 4), **f64), torch.zeros(4, **f64), torch.zeros(4, dtype=torch.uint8, device=dev)
+        M, rhs, dtheta = torch.zeros((6 * c + 4, 6 * c + 4), **f64), torch.zeros(6 * c + 4, **f64), torch.zeros(4, **f64)
+        valid = torch.zeros(c, dtype=torch.uint8, device=dev)
+
+        def linearize_intrinsics():
+            _lib.check(lib.vc_ba_linearize_intrinsics(p(d[0]), c, p(dg), 1, p(di), p(d[2]), n, p(d[3]), p(d[4]), t, p(b.vinv), p(b.gp), p(b.obs_ok),
+                                                      p(b.obs_lin), p(xn), p(T), p(terms), stream), "vc_ba_linearize_intrinsics")
+
+        def reduce_border():
+            _lib.check(lib.vc_ba_reduce_border(c, p(dg), 1, p(di), n, p(d[3]), p(d[4]), t, p(x[0]), p(x[1]), p(x[2]), lam, p(b.vinv), p(b.obs_ok),
+                                               p(b.obs_lin), p(xn), p(T), p(terms), p(sums), p(B), p(C), p(h), p(free), stream), "vc_ba_reduce_border")
+
+        def solve_bordered():
+            M[:6 * c, :6 * c], M[:6 * c, 6 * c:], M[6 * c:, :6 * c], M[6 * c:, 6 * c:] = S, B, B.T, C
+            rhs[:6 * c], rhs[6 * c:] = g, h
+            L, _ = torch.linalg.cholesky_ex(M)
+            sol = torch.cholesky_solve(-rhs[:, None], L)[:, 0]
+            dc.copy_(sol[:6 * c]), dtheta.copy_(sol[6 * c:])
+
+        def step_intrinsics():
+            _lib.check(lib.vc_ba_step_intrinsics(p(d[0]), c, p(dg), 1, p(di), p(d[2]), n, p(d[3]), p(d[4]), t, p(b.vinv), p(b.gp), p(b.obs_ok),
+                                                 p(b.obs_lin), p(T), p(dc), p(dtheta), p(out_cams), p(out_points), p(dx), p(valid), stream),
+                       "vc_ba_step_intrinsics")
+
+        stages += [("linearize_intrinsics_ms", linearize_intrinsics), ("reduce_border_ms", reduce_border), ("solve_bordered_ms", solve_bordered),
+                   ("step_intrinsics_ms", step_intrinsics)]
+    for name, fn in stages:
         out[name] = round(device_ms(fn, iters), 4)
-    walls, report = [], None
-    for _ in range(loops + 1):                                        # the first run warms up
+
+    def loop(**kw):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        _, _, report = bundle.bundle_adjust(cams, points, offsets, obs_cam, obs_xy, mask, "cuda")
+        cams_out, _, report = bundle.bundle_adjust(cams, points, offsets, obs_cam, obs_xy, mask, "cuda", **kw)
         torch.cuda.synchronize()
-        walls.append(1e3 * (time.perf_counter() - t0))
+        return 1e3 * (time.perf_counter() - t0), report, cams_out
+
+    walls, refined_walls = [], []
+    for _ in range(loops + 1):                                        # the first run warms up; plain and refined alternate
+        wall, report, _ = loop()
+        walls.append(wall)
+        if refine:
+            wall, refined, cams_out = loop(**groups)
+            refined_walls.append(wall)
     out.update(loop_ms=round(float(np.median(walls[1:])), 3), iterations=report["iterations"], accepted_steps=report["accepted_steps"],
                initial_cost=report["initial_cost"], final_cost=report["final_cost"])
+    if refine:
+        out.update(refined_loop_ms=round(float(np.median(refined_walls[1:])), 3), refined_iterations=refined["iterations"],
+                   refined_accepted_steps=refined["accepted_steps"], refined_final_cost=refined["final_cost"], refined_focal=float(cams_out[0, 12]))
     return out
 
 
@@ -128,9 +177,12 @@ def main():
     ap.add_argument("--points", type=int, default=20000)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--loops", type=int, default=5)
+    ap.add_argument("--refine-focal", dest="refine_focal", action="store_true",
+                    help="every focal 3 %% off; also time the border's entry points and the loop that refines one tied focal")
     args = ap.parse_args()
-    print(json.dumps(dict(tool="bench_bundle", iters=args.iters, loops=args.loops, windowed=measure(windowed_problem(), args.iters, args.loops),
-                          arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops))))
+    print(json.dumps(dict(tool="bench_bundle", iters=args.iters, loops=args.loops, refine_focal=args.refine_focal,
+                          windowed=measure(windowed_problem(), args.iters, args.loops, args.refine_focal),
+                          arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops, args.refine_focal))))
 
 
 if __name__ == "__main__":

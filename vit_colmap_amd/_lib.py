@@ -17,6 +17,7 @@ VC_MAX_KEYPOINTS = 2048
 VC_MAX_DESC_DIM = 1024
 VC_MAX_NEIGHBOURS = 64
 VC_BA_MAX_CAMS = 512
+VC_BA_MAX_GROUPS = 8
 VC_ERR_INVALID_ARG, VC_ERR_UNSUPPORTED, VC_ERR_LAUNCH, VC_ERR_WORKSPACE = -1, -2, -3, -4
 
 
@@ -64,6 +65,12 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vc_ba_step": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_ba_linearize_intrinsics": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]
+                                   + [c_void_p] * 8),
+    "vc_ba_reduce_border": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_double] + [c_void_p] * 12),
+    "vc_ba_step_intrinsics": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]
+                              + [c_void_p] * 12),
     "vc_structure_tensor": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vc_score_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vc_select_keypoints": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,

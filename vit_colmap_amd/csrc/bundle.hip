@@ -17,6 +17,13 @@
 //              a track it loads the next element's flag and camera while the current element's W is on its way.
 //   step       one point per lane: dX = -V^-1 (g_p + sum W' dc) in track order, X + dX; one camera per lane: q = (1, w / 2)
 //              normalised, R(q) R, t + dt.
+// The border of the intrinsics (vc_ba_linearize_intrinsics, vc_ba_reduce_border, vc_ba_step_intrinsics; tools/bundle_intr_host.cpp,
+// tests/util_bundle_intr.py) adds (fx, fy, cx, cy) of every group of cameras to that iteration:
+//   linearize  one point per lane, the groups outside and the track inside: T = sum J_theta' J_p, q, hq and the point's products
+//              T V^-1 T', T V^-1 g_p; nothing is a register array indexed by a runtime value
+//   reduce     one wave per ordered sum over the points (the total cost's scheme) -> C, h; one wave per camera over its list in
+//              the camera pass' batches, a lane's entries of B_a [6][4 G] in its registers
+//   step       the point's and the camera's step with the groups' terms; whether the candidate's focal lengths are positive
 // What a lane computes is sequential and nothing depends on the order in which lanes or workgroups run, so two launches
 // return the same bits, and the same routines compiled for the host (tools/bundle_host.cpp includes this file) return the
 // device's.  Every index read from an input array is checked against the array it indexes before it is used.
@@ -235,13 +242,13 @@ __host__ __device__ __forceinline__ void ba_lane_finish(int n_cams, unsigned hel
   if (lane < 6) g[6 * a + lane] = s.gr - s.gy;
 }
 
-// One point's step: dX = -V^-1 (g_p + sum W' dc) over the track in track order.
-__host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const BaLinear& l, const double* __restrict__ dc, int j,
-                                                       double (&dX)[3]) {
-  dX[0] = dX[1] = dX[2] = 0.0;
+// One point's right-hand side s = g_p + sum W' dc over the track in track order -> false where the point's offsets delimit
+// nothing (s is then not written).
+__host__ __device__ __forceinline__ bool ba_point_rhs(const BaProblem& d, const BaLinear& l, const double* __restrict__ dc, int j,
+                                                      double (&s)[3]) {
   int lo, hi;
-  if (!ba_track(d.offsets, j, d.total, lo, hi)) return;
-  double s[3] = {l.gp[3 * (long long)j], l.gp[3 * (long long)j + 1], l.gp[3 * (long long)j + 2]};
+  if (!ba_track(d.offsets, j, d.total, lo, hi)) return false;
+  s[0] = l.gp[3 * (long long)j], s[1] = l.gp[3 * (long long)j + 1], s[2] = l.gp[3 * (long long)j + 2];
   for (int o = lo; o < hi; ++o) {
     if (!l.obs_ok[o]) continue;
     const int b = d.obs_cam[o];
@@ -252,10 +259,23 @@ __host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const
     for (int k = 0; k < 3; ++k)
       s[k] += w[k] * e[0] + w[3 + k] * e[1] + w[6 + k] * e[2] + w[9 + k] * e[3] + w[12 + k] * e[4] + w[15 + k] * e[5];
   }
+  return true;
+}
+
+// dX = -V^-1 s
+__host__ __device__ __forceinline__ void ba_point_solve(const BaLinear& l, int j, const double (&s)[3], double (&dX)[3]) {
   const double* v = l.vinv + (long long)j * 6;
   dX[0] = -(v[0] * s[0] + v[1] * s[1] + v[2] * s[2]);
   dX[1] = -(v[1] * s[0] + v[3] * s[1] + v[4] * s[2]);
   dX[2] = -(v[2] * s[0] + v[4] * s[1] + v[5] * s[2]);
+}
+
+// One point's step: dX = -V^-1 (g_p + sum W' dc) over the track in track order.
+__host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const BaLinear& l, const double* __restrict__ dc, int j,
+                                                       double (&dX)[3]) {
+  dX[0] = dX[1] = dX[2] = 0.0;
+  double s[3];
+  if (ba_point_rhs(d, l, dc, j, s)) ba_point_solve(l, j, s, dX);
 }
 
 // One camera's update without trigonometry: q = (1, w / 2) / |(1, w / 2)|, R <- R(q) R, t <- t + dt; the intrinsics are copied.
@@ -275,6 +295,221 @@ __host__ __device__ __forceinline__ void ba_camera_step(const double* __restrict
   for (int i = 0; i < 3; ++i) out[9 + i] = cam[9 + i] + e[3 + i];
 #pragma unroll
   for (int i = 12; i < 16; ++i) out[i] = cam[i];
+}
+
+// ---- the border of the intrinsics (vc_ba_linearize_intrinsics, vc_ba_reduce_border, vc_ba_step_intrinsics) ----------------------
+// The unknowns theta_g = (fx, fy, cx, cy) of every group of cameras join the reduced system as a border [[S, B], [B', C]];
+// S and g stay vc_ba_reduce_cameras'.
+constexpr int kBaT = 12;                                                      // T_{j,g} = sum J_theta' J_p, 4x3 row-major
+constexpr int kBaBorderSlots = (24 * VC_BA_MAX_GROUPS + kBaWave - 1) / kBaWave;   // entries of a camera's B row block per lane
+
+struct BaGroups {
+  const int32_t* __restrict__ cam_group;       // [n_cams]
+  const uint8_t* __restrict__ intr_mask;       // [n_groups]: bits 0-3 fx fy cx cy held, bit 4 fx and fy tied
+  int n_groups;
+};
+
+// The rows of the per-point terms [ba_term_rows(G)][n_points] (entry-major: a point per lane writes a row and a wave per row
+// reads it, both coalesced): q_{j,g} 4x4, hq_{j,g}, p_{j,g} = T V^-1 g_p, P_{j,g,g'} = T_g V^-1 T_g'' 4x4.
+__host__ __device__ constexpr int ba_term_q(int G, int g) { return 16 * g; }
+__host__ __device__ constexpr int ba_term_hq(int G, int g) { return 16 * G + 4 * g; }
+__host__ __device__ constexpr int ba_term_p(int G, int g) { return 20 * G + 4 * g; }
+__host__ __device__ constexpr int ba_term_P(int G, int g, int g2) { return 24 * G + 16 * (g * G + g2); }
+__host__ __device__ constexpr int ba_term_rows(int G) { return 24 * G + 16 * G * G; }
+
+// Camera slot -> its group, -1 where the slot's group is outside [0, n_groups): its intrinsics are held.
+__host__ __device__ __forceinline__ int ba_group_of(const BaGroups& gr, int slot) {
+  const int g = gr.cam_group[slot];
+  return g >= 0 && g < gr.n_groups ? g : -1;
+}
+
+__host__ __device__ __forceinline__ bool ba_theta_held(unsigned mask, int i) { return ((mask >> i) & 1u) || (((mask >> 4) & 1u) && i == 1); }
+
+// Column i of J_theta = [[x, 0, 1, 0], [0, y, 0, 1]] at the normalised point (x, y); tied: column 0 is (x, y); a held column is 0.
+__host__ __device__ __forceinline__ void ba_jtheta(unsigned mask, double x, double y, int i, double& tu, double& tv) {
+  const bool tied = (mask >> 4) & 1u;
+  tu = i == 0 ? x : i == 2 ? 1.0 : 0.0;
+  tv = i == 0 ? (tied ? y : 0.0) : i == 1 ? y : i == 3 ? 1.0 : 0.0;
+  if (ba_theta_held(mask, i)) tu = tv = 0.0;
+}
+
+// A usable observation of X in camera row c again: x = Xc_x / Xc_z, y = Xc_y / Xc_z and J_p, the operations of ba_observe.
+__host__ __device__ __forceinline__ void ba_observe_point(const double* __restrict__ c, const double (&X)[3], double& xu, double& xv,
+                                                          double (&ju)[3], double (&jv)[3]) {
+  double Xc[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Xc[i] = (c[3 * i] * X[0] + c[3 * i + 1] * X[1] + c[3 * i + 2] * X[2]) + c[9 + i];
+  const double z = Xc[2], fu = c[12] / z, fv = c[13] / z;
+  xu = Xc[0] / z, xv = Xc[1] / z;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    ju[k] = fu * (c[k] - xu * c[6 + k]);
+    jv[k] = fv * (c[3 + k] - xv * c[6 + k]);
+  }
+}
+
+// One point: obs_xn of its track; per group (outside) over the track (inside) T, q, hq; then the point's products with V^-1.
+// A point whose offsets delimit nothing has T and its terms 0 and nothing of its track read or written.
+__host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaProblem& d, const BaLinear& l, const BaGroups& gr, int j,
+                                                                       double* __restrict__ obs_xn, double* T, double* __restrict__ terms) {
+  const int G = gr.n_groups;
+  const long long n = d.n_points;
+  int lo, hi;
+  if (!ba_track(d.offsets, j, d.total, lo, hi)) lo = hi = 0;
+  double X[3] = {0.0, 0.0, 0.0};
+  if (lo < hi) X[0] = d.points[3 * (long long)j], X[1] = d.points[3 * (long long)j + 1], X[2] = d.points[3 * (long long)j + 2];
+  for (int o = lo; o < hi; ++o) {
+    const int slot = d.obs_cam[o];
+    double x = 0.0, y = 0.0, ju[3], jv[3];
+    if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
+    obs_xn[2 * (long long)o] = x, obs_xn[2 * (long long)o + 1] = y;
+  }
+  double* Tj = T + (long long)j * G * kBaT;
+  for (int g = 0; g < G; ++g) {
+    const unsigned mask = gr.intr_mask[g];
+    double t[kBaT], q[16], hq[4];
+#pragma unroll
+    for (int k = 0; k < kBaT; ++k) t[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) q[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hq[k] = 0.0;
+    for (int o = lo; o < hi; ++o) {
+      const int slot = d.obs_cam[o];
+      if (!l.obs_ok[o] || slot < 0 || slot >= d.n_cams || ba_group_of(gr, slot) != g) continue;
+      double x, y, ju[3], jv[3], tu[4], tv[4];
+      ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ba_jtheta(mask, x, y, i, tu[i], tv[i]);
+      const double ru = l.obs_lin[(long long)o * kBaLin + kBaLinR], rv = l.obs_lin[(long long)o * kBaLin + kBaLinR + 1];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[3 * i + k] += tu[i] * ju[k] + tv[i] * jv[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[4 * i + k] += tu[i] * tu[k] + tv[i] * tv[k];
+        hq[i] += tu[i] * ru + tv[i] * rv;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kBaT; ++k) Tj[g * kBaT + k] = t[k];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) terms[(ba_term_q(G, g) + k) * n + j] = q[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) terms[(ba_term_hq(G, g) + k) * n + j] = hq[k];
+  }
+  const double* v = l.vinv + (long long)j * 6;
+  const double v00 = v[0], v01 = v[1], v02 = v[2], v11 = v[3], v12 = v[4], v22 = v[5];
+  const double g0 = l.gp[3 * (long long)j], g1 = l.gp[3 * (long long)j + 1], g2 = l.gp[3 * (long long)j + 2];
+  for (int g = 0; g < G; ++g) {
+    double tv[kBaT];                                                          // T_g V^-1, as Y = W V^-1 is formed
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const double t0 = Tj[g * kBaT + 3 * i], t1 = Tj[g * kBaT + 3 * i + 1], t2 = Tj[g * kBaT + 3 * i + 2];
+      tv[3 * i] = t0 * v00 + t1 * v01 + t2 * v02;
+      tv[3 * i + 1] = t0 * v01 + t1 * v11 + t2 * v12;
+      tv[3 * i + 2] = t0 * v02 + t1 * v12 + t2 * v22;
+      terms[(ba_term_p(G, g) + i) * n + j] = tv[3 * i] * g0 + tv[3 * i + 1] * g1 + tv[3 * i + 2] * g2;
+    }
+    for (int h = 0; h < G; ++h) {
+      const double* th = Tj + h * kBaT;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          terms[(ba_term_P(G, g, h) + 4 * i + k) * n + j] = tv[3 * i] * th[3 * k] + tv[3 * i + 1] * th[3 * k + 1] + tv[3 * i + 2] * th[3 * k + 2];
+    }
+  }
+}
+
+// Parameter i of group g moves: not held, not parameter 1 of a tied group, and some usable observation moves it (Q_ii != 0).
+__host__ __device__ __forceinline__ bool ba_theta_free(const double* __restrict__ sums, const BaGroups& gr, int g, int i) {
+  return !ba_theta_held(gr.intr_mask[g], i) && sums[ba_term_q(gr.n_groups, g) + 5 * i] != 0.0;
+}
+
+// Entry (row, col) of C from the ordered sums: delta Q (its diagonal damped) - sum P; the identity where a parameter does not move.
+__host__ __device__ __forceinline__ double ba_border_c(const double* __restrict__ sums, const BaGroups& gr, double lambda, int row, int col) {
+  const int G = gr.n_groups, g = row / 4, i = row % 4, h = col / 4, k = col % 4;
+  if (!ba_theta_free(sums, gr, g, i) || !ba_theta_free(sums, gr, h, k)) return row == col ? 1.0 : 0.0;
+  double q = 0.0;
+  if (g == h) {
+    q = sums[ba_term_q(G, g) + 4 * i + k];
+    if (i == k) q += lambda * q;
+  }
+  return q - sums[ba_term_P(G, g, h) + 4 * i + k];
+}
+
+__host__ __device__ __forceinline__ double ba_border_h(const double* __restrict__ sums, const BaGroups& gr, int row) {
+  const int G = gr.n_groups, g = row / 4, i = row % 4;
+  return ba_theta_free(sums, gr, g, i) ? sums[ba_term_hq(G, g) + i] - sums[ba_term_p(G, g) + i] : 0.0;
+}
+
+// The registers of one lane of the border's camera pass: entry idx = lane + 64 k of the row block B_a [6][4 G], as g = idx / 24,
+// r = idx % 24 / 4, i = idx % 4, and its two sums.
+struct BaBorderLane {
+  double jt[kBaBorderSlots], yt[kBaBorderSlots];
+};
+
+// One lane's additions for the usable observation o of camera a (its group ga or -1, its point j, y as ba_prepare left it).
+__host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, const BaGroups& gr, const double* __restrict__ obs_xn,
+                                                          const double* __restrict__ T, int ga, int o, int j, int lane, const double* y,
+                                                          BaBorderLane& s) {
+  const int G = gr.n_groups;
+  const double* lin = l.obs_lin + (long long)o * kBaLin;
+  const unsigned mask = ga >= 0 ? gr.intr_mask[ga] : 0u;
+  const double x = obs_xn[2 * (long long)o], yn = obs_xn[2 * (long long)o + 1];
+#pragma unroll
+  for (int k = 0; k < kBaBorderSlots; ++k) {
+    const int idx = lane + kBaWave * k;
+    if (idx >= 24 * G) continue;
+    const int g = idx / 24, r = idx % 24 / 4, i = idx % 4;
+    if (g == ga) {
+      double tu, tv;
+      ba_jtheta(mask, x, yn, i, tu, tv);
+      s.jt[k] += lin[r] * tu + lin[6 + r] * tv;
+    }
+    const double* t = T + ((long long)j * G + g) * kBaT + 3 * i;
+    s.yt[k] += y[3 * r] * t[0] + y[3 * r + 1] * t[1] + y[3 * r + 2] * t[2];
+  }
+}
+
+__host__ __device__ __forceinline__ void ba_border_finish(int G, int a, int lane, const BaBorderLane& s, double* __restrict__ B) {
+#pragma unroll
+  for (int k = 0; k < kBaBorderSlots; ++k) {
+    const int idx = lane + kBaWave * k;
+    if (idx < 24 * G) B[(long long)(6 * a + idx % 24 / 4) * (4 * G) + 4 * (idx / 24) + idx % 4] = s.jt[k] - s.yt[k];
+  }
+}
+
+// One point's step with the border: dX = -V^-1 (g_p + sum W' dc + sum_g T_g' dtheta_g), the groups in ascending order.
+__host__ __device__ __forceinline__ void ba_point_step_intrinsics(const BaProblem& d, const BaLinear& l, const double* __restrict__ T, int G,
+                                                                  const double* __restrict__ dc, const double* __restrict__ dtheta, int j,
+                                                                  double (&dX)[3]) {
+  dX[0] = dX[1] = dX[2] = 0.0;
+  double s[3];
+  if (!ba_point_rhs(d, l, dc, j, s)) return;
+  for (int g = 0; g < G; ++g) {
+    const double* t = T + ((long long)j * G + g) * kBaT;
+    const double* e = dtheta + 4 * g;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3];
+  }
+  ba_point_solve(l, j, s, dX);
+}
+
+// One camera's update with the border: ba_camera_step, then (fx, fy, cx, cy) += dtheta of its group (tied: dtheta_0 to both
+// focal lengths) -> whether the candidate's focal lengths are finite and positive (true where the group holds the intrinsics).
+__host__ __device__ __forceinline__ bool ba_camera_step_intrinsics(const double* __restrict__ cam, const double* __restrict__ e,
+                                                                   const BaGroups& gr, int a, const double* __restrict__ dtheta,
+                                                                   double* __restrict__ out) {
+  ba_camera_step(cam, e, out);
+  const int g = ba_group_of(gr, a);
+  if (g < 0) return true;
+  const double* th = dtheta + 4 * g;
+  const bool tied = (gr.intr_mask[g] >> 4) & 1u;
+  const double fx = cam[12] + th[0], fy = cam[13] + (tied ? th[0] : th[1]);
+  out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
+  return ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0;
 }
 
 __global__ __launch_bounds__(kBaWave) void ba_linearize_points_kernel(BaProblem d, double lambda, double* __restrict__ out_vinv,
@@ -348,6 +583,84 @@ __global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(const double* 
   ba_camera_step(cams + 16 * a, dc + 6 * a, out_cams + 16 * a);
 }
 
+__global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_kernel(BaProblem d, BaLinear l, BaGroups gr, double* __restrict__ out_obs_xn,
+                                                                          double* out_T, double* __restrict__ out_terms) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j < d.n_points) ba_linearize_point_intrinsics(d, l, gr, (int)j, out_obs_xn, out_T, out_terms);
+}
+
+// Row blockIdx.x of the terms added in point order by ba_total_cost_kernel's scheme: one wave per output entry.  (That kernel
+// keeps its own copy of the loop: routed through a shared routine the compiler schedules it differently, and its code is pinned.)
+__global__ __launch_bounds__(kBaWave) void ba_border_sums_kernel(const double* __restrict__ terms, int n_points, double* __restrict__ out_sums) {
+  const double* row = terms + (long long)blockIdx.x * n_points;
+  double sum = 0.0;
+  for (int base = 0; base < n_points; base += kBaWave) {
+    const double v = base + (int)threadIdx.x < n_points ? row[base + threadIdx.x] : 0.0;
+    const int m = n_points - base < kBaWave ? n_points - base : kBaWave;
+    for (int k = 0; k < m; ++k) sum += __shfl(v, k, kBaWave);
+  }
+  if (threadIdx.x == 0) out_sums[blockIdx.x] = sum;
+}
+
+// C, h and which parameters move, from the ordered sums: one entry per lane.
+__global__ __launch_bounds__(kBaWave) void ba_border_system_kernel(const double* __restrict__ sums, BaGroups gr, double lambda,
+                                                                   double* __restrict__ out_C, double* __restrict__ out_h,
+                                                                   uint8_t* __restrict__ out_free) {
+  const int m = 4 * gr.n_groups;
+  for (int idx = threadIdx.x; idx < m * m; idx += kBaWave) out_C[idx] = ba_border_c(sums, gr, lambda, idx / m, idx % m);
+  for (int row = threadIdx.x; row < m; row += kBaWave) {
+    out_h[row] = ba_border_h(sums, gr, row);
+    out_free[row] = ba_theta_free(sums, gr, row / 4, row % 4) ? 1 : 0;
+  }
+}
+
+// B_a: one wave per camera over its list, the batches of ba_reduce_cameras_kernel, a lane's entries in its registers.
+__global__ __launch_bounds__(kBaWave) void ba_reduce_border_kernel(BaProblem d, BaLinear l, BaGroups gr, const int32_t* __restrict__ cam_offsets,
+                                                                   const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
+                                                                   const double* __restrict__ obs_xn, const double* __restrict__ T,
+                                                                   double* __restrict__ out_B) {
+  __shared__ BaBatch batch;
+  const int a = blockIdx.x, lane = threadIdx.x;
+  const int ga = ba_group_of(gr, a);
+  BaBorderLane s;
+#pragma unroll
+  for (int k = 0; k < kBaBorderSlots; ++k) s.jt[k] = s.yt[k] = 0.0;
+  const int first = cam_offsets[a], last = cam_offsets[a + 1];
+  if (first >= 0 && last >= first && last <= d.total) {     // otherwise the camera is skipped, nothing of it read
+    for (int base = first; base < last; base += kBaWave) {
+      ba_prepare(d, l, cam_obs, obs_point, a, base + lane, last, lane, batch);
+      __syncthreads();
+      const int m = last - base < kBaWave ? last - base : kBaWave;
+      for (int k = 0; k < m; ++k)
+        if (batch.o[k] >= 0) ba_border_update(l, gr, obs_xn, T, ga, batch.o[k], batch.j[k], lane, batch.y[k], s);
+      __syncthreads();
+    }
+  }
+  ba_border_finish(gr.n_groups, a, lane, s, out_B);
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_step_points_intrinsics_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
+                                                                            const double* __restrict__ dc, const double* __restrict__ dtheta,
+                                                                            double* __restrict__ out_points, double* __restrict__ out_dx) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j >= d.n_points) return;
+  double dX[3];
+  ba_point_step_intrinsics(d, l, T, n_groups, dc, dtheta, (int)j, dX);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    out_dx[3 * j + k] = dX[k];
+    out_points[3 * j + k] = d.points[3 * j + k] + dX[k];
+  }
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_step_cameras_intrinsics_kernel(const double* __restrict__ cams, int n_cams, BaGroups gr,
+                                                                             const double* __restrict__ dc, const double* __restrict__ dtheta,
+                                                                             double* __restrict__ out_cams, uint8_t* __restrict__ out_valid) {
+  const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (a >= n_cams) return;
+  out_valid[a] = ba_camera_step_intrinsics(cams + 16 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a) ? 1 : 0;
+}
+
 constexpr int ba_reduce_lds_bytes(int n_cams) { return 36 * n_cams * (int)sizeof(double); }
 static_assert(ba_reduce_lds_bytes(VC_BA_MAX_CAMS) + (int)sizeof(BaBatch) <= 160 * 1024, "the row block of VC_BA_MAX_CAMS cameras must fit the CU's LDS");
 
@@ -408,6 +721,71 @@ int vc_ba_step(const double* cams, int n_cams, const double* points, int n_point
   if (n_cams > 0)
     hipLaunchKernelGGL(ba_step_cameras_kernel, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
                        cams, n_cams, dc, out_cams);
+  return vc::check_launch();
+}
+
+int vc_ba_linearize_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                               const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                               const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_obs_xn,
+                               double* out_T, double* out_terms, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_points == 0 || n_groups == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_group)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !out_obs_xn)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_linearize_intrinsics_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, out_obs_xn, out_T,
+                     out_terms);
+  return vc::check_launch();
+}
+
+int vc_ba_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
+                        const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
+                        double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
+                        const double* T, const double* terms, double* out_sums, double* out_B, double* out_C, double* out_h,
+                        uint8_t* out_free, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_groups == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_xn)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaGroups gr{cam_group, intr_mask, n_groups};
+  hipLaunchKernelGGL(ba_border_sums_kernel, dim3((unsigned)ba_term_rows(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
+                     out_sums);
+  hipLaunchKernelGGL(ba_border_system_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h, out_free);
+  if (n_cams > 0) {
+    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
+    hipLaunchKernelGGL(ba_reduce_border_kernel, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
+                       BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_xn, T, out_B);
+  }
+  return vc::check_launch();
+}
+
+int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                          const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
+                          const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc,
+                          const double* dtheta, double* out_cams, double* out_points, double* out_dx, uint8_t* out_valid,
+                          vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_cams == 0 && n_points == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS) return VC_ERR_UNSUPPORTED;
+  if (n_groups > 0 && (!intr_mask || !dtheta)) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_group || !dc || !out_cams || !out_valid)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx || (n_groups > 0 && !T))) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0) {
+    const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+    hipLaunchKernelGGL(ba_step_points_intrinsics_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                       (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, T, n_groups, dc, dtheta, out_points, out_dx);
+  }
+  if (n_cams > 0)
+    hipLaunchKernelGGL(ba_step_cameras_intrinsics_kernel, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                       (hipStream_t)stream, cams, n_cams, BaGroups{cam_group, intr_mask, n_groups}, dc, dtheta, out_cams, out_valid);
   return vc::check_launch();
 }
 

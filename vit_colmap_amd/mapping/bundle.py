@@ -2,8 +2,10 @@
 by the Schur complement of the points, on the three kernels of csrc/bundle.hip, whose header (include/vitcolmap_hip.h) states
 the rule; then the rescale to a unit baseline and the filter of observations and points.  Specification:
 tests/util_bundle.py.  This build's own published rule; parity with COLMAP's bundle adjuster and with Ceres is unpinned.
-Still missing on the way to a mapper: adjustment per round and local adjustment, re-triangulation, merging of points, a robust
-loss, refined intrinsics, distortion models.
+With `refine_focal_length` the adjustment also refines the focal length(s) of every camera (one group of intrinsics per
+camera_id, a border of the reduced system: mapping/bundle_intr.py, imported only then; specification:
+tests/util_bundle_intr.py).  Still missing on the way to a mapper: adjustment per round and local adjustment,
+re-triangulation, merging of points, a robust loss, the principal point and distortion among the refined intrinsics.
 
 Where the work runs
   HIP     per iteration vc_ba_linearize_points (one point per lane: residuals, Jacobians, V^-1, the cost), vc_ba_reduce_cameras
@@ -68,11 +70,16 @@ class _Buffers:
         self.total_cost = torch.zeros(1, **f64)
 
 
-def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cuda", max_iterations=BA_MAX_ITERATIONS):
+def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cuda", max_iterations=BA_MAX_ITERATIONS, cam_group=None,
+                  intr_mask=None):
     """cams float64 (n_cams, 16) as vc_triangulate_tracks has them, points float64 (n_points, 3), offsets int32 (n_points + 1,),
     obs_cam int32 (total,), obs_xy float64 (total, 2), const_mask uint8 (n_cams,) (bit i: pose parameter i is held), numpy
     -> cams, points (numpy, adjusted) and the report dict(iterations, accepted_steps, initial_cost, final_cost, final_lambda,
-    decisions).  Raises ValueError above VC_BA_MAX_CAMS cameras."""
+    decisions).  Raises ValueError above VC_BA_MAX_CAMS cameras.
+    cam_group int32 (n_cams,) and intr_mask uint8 (n_groups,), both or neither: the intrinsics of every group of cameras are
+    refined too (mapping/bundle_intr.py; bits 0-3 of a group's mask: fx, fy, cx, cy held, bit 4: fx and fy tied; a slot whose
+    group is outside [0, n_groups) keeps its intrinsics), the report gains `intrinsics` = dict(before, after), (n_groups, 4)
+    each.  Raises ValueError above VC_BA_MAX_GROUPS groups."""
     import torch
 
     from .. import _lib
@@ -86,6 +93,12 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
         raise ValueError(f"bundle_adjust: {n_cams} cameras, the reduction kernel holds at most {_lib.VC_BA_MAX_CAMS} (VC_BA_MAX_CAMS)")
     if offsets.shape != (n_points + 1,) or obs_xy.shape != (total, 2) or const_mask.shape != (n_cams,):
         raise ValueError("bundle_adjust needs offsets (n_points + 1,), obs_cam (total,), obs_xy (total, 2), const_mask (n_cams,)")
+    if cam_group is not None or intr_mask is not None:
+        if cam_group is None or intr_mask is None:
+            raise ValueError("bundle_adjust needs cam_group and intr_mask together")
+        from .bundle_intr import bundle_adjust_intrinsics
+
+        return bundle_adjust_intrinsics(cams, points, offsets, obs_cam, obs_xy, const_mask, cam_group, intr_mask, device, max_iterations)
     report = dict(iterations=0, accepted_steps=0, initial_cost=0.0, final_cost=0.0, final_lambda=BA_LAMBDA0, decisions=[])
     if n_cams == 0 or n_points == 0:
         return cams.copy(), points.copy(), report
@@ -148,8 +161,8 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     return cur.cams.cpu().numpy(), cur.points.cpu().numpy(), report
 
 
-def _gpu_bundle(cams, points, offsets, obs_cam, obs_xy, const_mask, device):
-    return bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device)
+def _gpu_bundle(cams, points, offsets, obs_cam, obs_xy, const_mask, device, cam_group=None, intr_mask=None, max_iterations=BA_MAX_ITERATIONS):
+    return bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device, max_iterations, cam_group=cam_group, intr_mask=intr_mask)
 
 
 def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
@@ -161,11 +174,17 @@ def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
 
 
 def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
-                         grown=None) -> SparseModel:
+                         grown=None, refine_focal_length=False) -> SparseModel:
     """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
     is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
     Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
-    (cams, points, report)` on numpy arrays replaces the adjustment (tests), the other three as in build_sparse_model."""
+    (cams, points, report)` on numpy arrays replaces the adjustment (tests), the other three as in build_sparse_model.
+    `refine_focal_length`: the adjustment also refines the focal length(s) of every camera of the registered images (one
+    group per camera_id: one parameter where the model has one focal length, fx and fy for PINHOLE and OPENCV; the principal
+    point is held); bundle_fn is then also given cam_group=, intr_mask= and max_iterations=REFINE_MAX_ITERATIONS (the same
+    loop under a higher cap: a model grown under a wrong focal starts far from a minimum), the model's cameras carry the refined values, the
+    filter and `error` use them and the report gains `intrinsics` {camera_id: dict(before, after)}.  Raises ValueError above
+    VC_BA_MAX_GROUPS cameras."""
     bundle_fn = bundle_fn or _gpu_bundle
     if grown is None:
         grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn)
@@ -186,7 +205,20 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     mask = np.zeros(len(ids), np.uint8)
     mask[a] = HELD_ALL
     mask[b] = 1 << (3 + int(np.argmax(np.abs(cams[b, 9:12]))))
-    cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device)
+    if refine_focal_length:
+        from .. import _lib
+        from .bundle_intr import HOLD_CX, HOLD_CY, REFINE_MAX_ITERATIONS, TIED, has_one_focal
+
+        cids = sorted({grown.images[i]["camera_id"] for i in ids})
+        if len(cids) > _lib.VC_BA_MAX_GROUPS:
+            raise ValueError(f"refine_focal_length: the registered images have {len(cids)} cameras, the border kernels hold at most "
+                             f"{_lib.VC_BA_MAX_GROUPS} groups of intrinsics (VC_BA_MAX_GROUPS)")
+        cam_group = np.array([cids.index(grown.images[i]["camera_id"]) for i in ids], np.int32)
+        intr_mask = np.array([HOLD_CX | HOLD_CY | (TIED if has_one_focal(grown.cameras[c]) else 0) for c in cids], np.uint8)
+        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group, intr_mask=intr_mask,
+                                         max_iterations=REFINE_MAX_ITERATIONS)
+    else:
+        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device)
     cams, points = np.array(cams, np.float64), np.array(points, np.float64)
 
     # every t and X rescaled so that the pair's baseline is 1 again (§4.2i)
@@ -196,8 +228,18 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     points = points * scale
 
     model = SparseModel(initial_pair=grown.initial_pair, rounds=grown.rounds,
-                        bundle_adjustment={k: v for k, v in report.items() if k != "decisions"})
+                        bundle_adjustment={k: v for k, v in report.items() if k not in ("decisions", "intrinsics")})
     model.cameras = copy.deepcopy(grown.cameras)
+    if refine_focal_length:
+        # the cameras carry the refined focal length(s); the filter below and `error` use the refined K
+        for g, cid in enumerate(cids):
+            fx, fy = (float(v) for v in report["intrinsics"]["after"][g][:2])
+            cam = model.cameras[cid]
+            cam.params = [fx] + list(cam.params[1:]) if has_one_focal(cam) else [fx, fy] + list(cam.params[2:])
+        K = {i: np.array([[cams[slot[i], 12], 0.0, cams[slot[i], 14]], [0.0, cams[slot[i], 13], cams[slot[i], 15]], [0.0, 0.0, 1.0]]) for i in ids}
+        model.bundle_adjustment["intrinsics"] = {cid: dict(before=[float(v) for v in report["intrinsics"]["before"][g]],
+                                                           after=[float(v) for v in report["intrinsics"]["after"][g]])
+                                                 for g, cid in enumerate(cids)}
     for i in ids:
         im, R = grown.images[i], cams[slot[i], :9].reshape(3, 3)
         model.images[i] = dict(qvec=rot_to_quat(R), tvec=cams[slot[i], 9:12].copy(), camera_id=im["camera_id"], name=im["name"],

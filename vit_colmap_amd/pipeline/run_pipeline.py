@@ -75,6 +75,9 @@ class Pipeline:
         bundle_adjustment = bool(getattr(self.config.reconstruction, "bundle_adjustment", False))
         if bundle_adjustment and not sparse_model:              # it adjusts the grown model (§4.2k)
             raise ValueError("bundle_adjustment needs reconstruction.sparse_model (--sparse-model)")
+        refine_focal_length = bool(getattr(self.config.reconstruction, "refine_focal_length", False))
+        if refine_focal_length and not bundle_adjustment:       # it is one more unknown of that adjustment (§4.2k)
+            raise ValueError("refine_focal_length needs reconstruction.bundle_adjustment (--bundle-adjustment)")
         for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
             if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
                 continue
@@ -131,7 +134,10 @@ class Pipeline:
         if seed_model:                                          # under torchrun only rank 0 arrives here
             self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
         if sparse_model:
-            self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment)
+            if refine_focal_length:
+                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True, refine_focal_length=True)
+            else:
+                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment)
 
         reconstructions = None
         if self.config.do_reconstruction:
@@ -171,9 +177,10 @@ class Pipeline:
         logger.info("Seed model: pair %s, %d images, %d points", *[model.stats()[k] for k in
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
-    def _write_sparse_model(self, db_path, output_dir, device, adjust=False):
+    def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
-        `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted."""
+        `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
+        `refine_focal_length`: that adjustment also refines the cameras' focal lengths."""
         from ..mapping.grow import build_sparse_model
 
         try:
@@ -188,7 +195,10 @@ class Pipeline:
         if adjust:
             from ..mapping.bundle import build_adjusted_model
 
-            adjusted = build_adjusted_model(str(db_path), device=device, grown=model)
+            if refine_focal_length:
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=True)
+            else:
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model)
             adjusted.write_text(str(Path(output_dir) / "sparse" / "adjusted"))
             self.last_stats = dict(self.last_stats, bundle_adjustment=adjusted.stats())
             logger.info("Adjusted model: %d images, %d points, cost %.6g -> %.6g", len(adjusted.images), len(adjusted.points3D),
@@ -241,6 +251,9 @@ def main() -> None:
     ap.add_argument("--bundle-adjustment", dest="bundle_adjustment", action="store_true",
                     help="with --sparse-model: also write output/sparse/adjusted, the grown model after one global bundle "
                          "adjustment, rescaled to a unit baseline and filtered")
+    ap.add_argument("--refine-focal-length", dest="refine_focal_length", action="store_true",
+                    help="with --bundle-adjustment: the adjustment also refines the focal length(s) of every camera; the "
+                         "adjusted model's cameras.txt carries the refined values")
     ap.add_argument("--matcher", choices=list(MATCHER_TYPES), default="exhaustive",
                     help="exhaustive: every image pair; retrieval: each image against its --num-neighbors nearest images")
     ap.add_argument("--num-neighbors", dest="num_neighbors", type=int, default=20,

@@ -108,6 +108,7 @@ class ReconstructionConfig:
     seed_model: bool = False     # write output_dir/sparse/seed: an initial pair, its points, every other image registered (§4.2i)
     sparse_model: bool = False   # write output_dir/sparse/grown: the seed model grown by rounds of triangulation and registration (§4.2j)
     bundle_adjustment: bool = False   # with sparse_model: write output_dir/sparse/adjusted, the grown model bundle-adjusted once (§4.2k)
+    refine_focal_length: bool = False   # with bundle_adjustment: the adjustment also refines every camera's focal length(s) (§4.2k)
 
     def to_mapper_options(self):
         import pycolmap  # noqa: PLC0415 - optional, third party
@@ -171,6 +172,8 @@ class Config:
             config.reconstruction.sparse_model = True
         if getattr(args, "bundle_adjustment", False):
             config.reconstruction.bundle_adjustment = True
+        if getattr(args, "refine_focal_length", False):
+            config.reconstruction.refine_focal_length = True
         if getattr(args, "matcher", None):
             config.matching.matcher_type = args.matcher
         if getattr(args, "num_neighbors", None) is not None:
