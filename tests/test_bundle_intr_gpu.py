@@ -1,5 +1,5 @@
 """GPU tests of bundle adjustment with refined intrinsics ("The border"): vc_ba_linearize_intrinsics,
-vc_ba_reduce_border and vc_ba_step_intrinsics against the same routines compiled for the host (tools/bundle_intr_host.cpp), byte
+vc_ba_reduce_border and vc_ba_step_intrinsics against the same routines compiled for the host (tools/bundle_host.cpp), byte
 for byte, on the problems of tests/test_bundle_gpu.py under groups of every kind, inside sentinel-filled buffers; two launches;
 the argument checks; the front end's loop against the specification of tests/util_bundle_intr.py on the windowed problem from
 a focal 3 % off; matching, growth and the adjustment end to end from a database whose camera is 3 % off, and the pipeline's flags."""
@@ -14,7 +14,8 @@ import util_essential as ue
 import util_mapper as um
 from test_absolute_pose_gpu import _two_view_bytes
 from test_bundle_gpu import PAD, dev, problem_of, step_of
-from test_bundle_intr_spec import bundle_intr_host, grown_runs, result_shapes, run_host, tied_groups, windowed_problem, with_focal  # noqa: F401
+from test_bundle_intr_spec import grown_runs, tied_groups, windowed_problem, with_focal
+from test_bundle_spec import bundle_host, result_shapes, run_host  # noqa: F401 - the fixture
 from test_mapper_gpu import write_windowed_db
 
 pytestmark = pytest.mark.gpu
@@ -95,12 +96,12 @@ def assert_bytes_equal(got, host, what, skip=()):
 
 
 @pytest.mark.parametrize("n_points,n_cams,n_groups", SHAPES)
-def test_kernels_return_the_host_builds_bytes(n_points, n_cams, n_groups, bundle_intr_host, tmp_path):  # noqa: F811
+def test_kernels_return_the_host_builds_bytes(n_points, n_cams, n_groups, bundle_host, tmp_path):  # noqa: F811
     problem, groups = problem_of(n_points, n_cams), groups_of(n_cams, n_groups)
     # at 65 points the step takes group 0's focal below zero: its slots are not valid
     dc, dtheta = step_of(problem), theta_step(groups, first=-700.0 if n_points == 65 else None)
     got, raw = launch(problem, groups, ub.BA_LAMBDA0, dc, dtheta)
-    host, _ = run_host(bundle_intr_host, tmp_path, problem, groups, ub.BA_LAMBDA0, dc, dtheta)
+    host, _ = run_host(bundle_host, tmp_path, problem, ub.BA_LAMBDA0, dc, groups=groups, dtheta=dtheta)
     assert_bytes_equal(got, host, f"{n_points} points, {n_cams} cameras, {n_groups} groups")
     again, raw2 = launch(problem, groups, ub.BA_LAMBDA0, dc, dtheta)
     assert raw == raw2                                                # two launches, identical bytes
@@ -126,7 +127,48 @@ def test_kernels_return_the_host_builds_bytes(n_points, n_cams, n_groups, bundle
         assert valid.all()
 
 
-def test_the_largest_camera_count_with_two_groups(bundle_intr_host, tmp_path):  # noqa: F811
+def test_step_without_groups_is_vc_ba_steps_through_either_entry_point():
+    """One points-step and one cameras-step kernel serve both entry points: vc_ba_step_intrinsics with n_groups = 0, whatever
+    cam_group holds, writes vc_ba_step's bytes and calls every candidate valid.  65 points span the wave seam."""
+    from vit_colmap_amd import _lib
+
+    lib = _lib.load()
+    problem = problem_of(65, 12)
+    cams, points, offsets, obs_cam, obs_xy, mask = problem
+    c, n, t = len(cams), len(points), len(obs_cam)
+    d_cams, d_points, d_offsets, d_obs_cam, d_obs_xy, d_mask, d_dc = (dev(a) for a in (cams, points, offsets, obs_cam, obs_xy, mask, step_of(problem)))
+    d_group = dev(np.array([0, 3, -1, 2 ** 31 - 1, -2 ** 31, 1, 7, 0, 0, -5, 2, 1], np.int32))       # read by nobody: there is no table
+    f64 = dict(dtype=torch.float64, device="cuda")
+    vinv, gp, cost, total_cost = torch.zeros(6 * n, **f64), torch.zeros(3 * n, **f64), torch.zeros(n, **f64), torch.zeros(1, **f64)
+    count, obs_ok, obs_lin = torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(t, dtype=torch.uint8, device="cuda"), torch.zeros(32 * t, **f64)
+    p, stream = _lib.ptr, _lib.stream_ptr()
+    _lib.check(lib.vc_ba_linearize_points(p(d_cams), c, p(d_mask), p(d_points), n, p(d_offsets), p(d_obs_cam), p(d_obs_xy), t, ub.BA_LAMBDA0,
+                                          p(vinv), p(gp), p(cost), p(count), p(obs_ok), p(obs_lin), p(total_cost), stream), "vc_ba_linearize_points")
+    runs = []
+    for with_groups in (False, True):
+        bufs = {k: torch.full((2 * PAD + size,), 7, **f64) for k, size in (("cams", 16 * c), ("points", 3 * n), ("dx", 3 * n))}
+        bufs["valid"] = torch.full((2 * PAD + c,), 7, dtype=torch.uint8, device="cuda")
+        o = {k: p(b[PAD:len(b) - PAD]) for k, b in bufs.items()}
+        if with_groups:
+            _lib.check(lib.vc_ba_step_intrinsics(p(d_cams), c, p(d_group), 0, None, p(d_points), n, p(d_offsets), p(d_obs_cam), t, p(vinv), p(gp),
+                                                 p(obs_ok), p(obs_lin), None, p(d_dc), None, o["cams"], o["points"], o["dx"], o["valid"], stream),
+                       "vc_ba_step_intrinsics")
+        else:
+            _lib.check(lib.vc_ba_step(p(d_cams), c, p(d_points), n, p(d_offsets), p(d_obs_cam), t, p(vinv), p(gp), p(obs_ok), p(obs_lin), p(d_dc),
+                                      o["cams"], o["points"], o["dx"], stream), "vc_ba_step")
+        torch.cuda.synchronize()
+        host = {k: b.cpu().numpy() for k, b in bufs.items()}
+        for k, b in host.items():
+            assert (b[:PAD] == 7).all() and (b[len(b) - PAD:] == 7).all(), f"{k}: written outside the output"
+        runs.append({k: b[PAD:len(b) - PAD] for k, b in host.items()})
+    plain, grouped = runs
+    for k in ("cams", "points", "dx"):
+        assert plain[k].tobytes() == grouped[k].tobytes(), k
+    assert (plain["valid"] == 7).all() and (grouped["valid"] == 1).all()       # vc_ba_step has no such output
+    assert np.isfinite(plain["dx"]).all() and plain["dx"].any() and plain["cams"].tobytes() != cams.tobytes()
+
+
+def test_the_largest_camera_count_with_two_groups(bundle_host, tmp_path):  # noqa: F811
     from vit_colmap_amd import _lib
 
     n_cams = _lib.VC_BA_MAX_CAMS
@@ -144,13 +186,13 @@ def test_the_largest_camera_count_with_two_groups(bundle_intr_host, tmp_path):  
     groups = tied_groups(n_cams, 2)
     dc, dtheta = step_of(problem), theta_step(groups)
     got, _ = launch(problem, groups, ub.BA_LAMBDA0, dc, dtheta)
-    host, _ = run_host(bundle_intr_host, tmp_path, problem, groups, ub.BA_LAMBDA0, dc, dtheta)
+    host, _ = run_host(bundle_host, tmp_path, problem, ub.BA_LAMBDA0, dc, groups=groups, dtheta=dtheta)
     assert_bytes_equal(got, host, f"{n_cams} cameras")
     B = got["B"].reshape(6 * n_cams, 8)
     assert not B[:6].any() and B[6 * (n_cams - 1):, 4].any() and got["free"].tolist() == [1, 0, 0, 0, 1, 0, 0, 0] and got["valid"].all()
 
 
-def test_offsets_that_delimit_nothing_skip_their_point_or_camera(bundle_intr_host, tmp_path):  # noqa: F811
+def test_offsets_that_delimit_nothing_skip_their_point_or_camera(bundle_host, tmp_path):  # noqa: F811
     cams, points, offsets, obs_cam, obs_xy, mask = problem_of(65, 12)
     offsets = offsets.copy()
     total = len(obs_cam)
@@ -161,7 +203,7 @@ def test_offsets_that_delimit_nothing_skip_their_point_or_camera(bundle_intr_hos
     index[1][index[0][7]] = total + 100                               # an entry of camera 7's list names no observation
     dc, dtheta = step_of(problem), theta_step(groups)
     got, _ = launch(problem, groups, ub.BA_LAMBDA0, dc, dtheta, index)
-    host, _ = run_host(bundle_intr_host, tmp_path, problem, groups, ub.BA_LAMBDA0, dc, dtheta, index)
+    host, _ = run_host(bundle_host, tmp_path, problem, ub.BA_LAMBDA0, dc, index, groups, dtheta)
     # the rows of a skipped point are not written: there the buffer keeps its fill, the host program's array its zeros
     assert_bytes_equal(got, host, "bad offsets", skip=("xn",))
     written = np.zeros(total, bool)

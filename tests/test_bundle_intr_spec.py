@@ -1,10 +1,9 @@
 """CPU tests of bundle adjustment with refined intrinsics ("The border"): the numpy specification of
 tests/util_bundle_intr.py (the derivative, the border against the dense normal equations, the all-held case against
 tests/util_bundle.py bit for bit, recovery of a wrong focal length on the exact scene and on the grown model, the rejection of a
-focal length that is not positive), the kernels' routines compiled for the host (tools/bundle_intr_host.cpp) against it, plain
+focal length that is not positive), the kernels' routines compiled for the host (tools/bundle_host.cpp) against it, plain
 and under the host sanitizers, the product's host logic with the specification in its seams, and the pipeline's flag.  No GPU."""
 import copy
-import os
 import subprocess
 import sys
 from functools import lru_cache
@@ -16,10 +15,10 @@ import util_absolute_pose as ua
 import util_bundle as ub
 import util_bundle_intr as ui
 from test_absolute_pose_spec import spec_estimate, spec_two_view_pose, write_scene_db
-from test_bundle_spec import (BA_POS_BOUND, BA_ROT_BOUND, HIPCC, HOST_BUILD, ROOT, adjusted, exact_problem, spec_bundle, spec_pass)
+from test_bundle_spec import (BA_POS_BOUND, BA_ROT_BOUND, ROOT, SANITIZE, _build, adjusted, bundle_host, exact_problem, run_host,  # noqa: F401
+                              spec_bundle, spec_pass)
 from test_mapper_spec import spec_triangulate, windowed
 
-SOURCE = os.path.join(ROOT, "tools", "bundle_intr_host.cpp")
 # central differences of the specification's own residual in fx, fy, cx, cy and in the tied parameter with step 1e-3 px (the
 # residual is linear in all of them, so the step only has to be large against the rounding of a residual, 640 * 2^-52 ~ 1e-13 px)
 # against J_theta on 20 observations, measured: worst |difference| 3.4e-11 where the largest entry of J_theta is 1; the bound is
@@ -249,47 +248,6 @@ def test_a_step_to_a_focal_that_is_not_positive_is_rejected_and_lambda_grows():
 
 
 # ---- the kernels' routines on the host ---------------------------------------------------------------------------------------------------
-def write_problem_file(path, problem, groups, lam, dc, dtheta, index=None):
-    """The input of tools/bundle_intr_host.cpp."""
-    cams, points, offsets, obs_cam, obs_xy, mask = problem
-    cam_group, intr_mask = groups
-    cam_offsets, cam_obs, obs_point = index or ub.camera_index(obs_cam, offsets, len(cams))
-    with open(path, "wb") as f:
-        f.write(np.array([len(cams), len(points), len(obs_cam), len(intr_mask)], np.int32).tobytes())
-        f.write(np.array([lam], np.float64).tobytes())
-        for a in (offsets, obs_cam, cam_offsets, cam_obs, obs_point, mask, cam_group, intr_mask):
-            f.write(np.ascontiguousarray(a).astype(np.int32).tobytes())
-        for a in (cams, points, obs_xy, dc, dtheta):
-            f.write(np.ascontiguousarray(a, np.float64).tobytes())
-
-
-def result_shapes(n_cams, n_points, total, G):
-    rows = 24 * G + 16 * G * G
-    return [("xn", (total, 2)), ("T", (n_points, G, 12)), ("terms", (rows, n_points)), ("sums", (rows,)), ("B", (6 * n_cams, 4 * G)),
-            ("C", (4 * G, 4 * G)), ("h", (4 * G,)), ("cams", (n_cams, 16)), ("points", (n_points, 3)), ("dx", (n_points, 3))]
-
-
-def read_result_file(path, n_cams, n_points, total, G):
-    raw = open(path, "rb").read()
-    out, at = {}, 0
-    for name, shape in result_shapes(n_cams, n_points, total, G):
-        n = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, np.float64, n, at).reshape(shape)
-        at += 8 * n
-    out["free"] = np.frombuffer(raw, np.uint8, 4 * G, at)
-    out["valid"] = np.frombuffer(raw, np.uint8, n_cams, at + 4 * G)
-    assert at + 4 * G + n_cams == len(raw)
-    return out
-
-
-def run_host(program, tmp_path, problem, groups, lam, dc, dtheta, index=None):
-    write_problem_file(tmp_path / "problem.bin", problem, groups, lam, dc, dtheta, index)
-    done = subprocess.run([program, str(tmp_path / "problem.bin"), str(tmp_path / "result.bin")], stdout=subprocess.PIPE,
-                          stderr=subprocess.PIPE, text=True)
-    assert done.returncode == 0, done.stderr
-    return read_result_file(tmp_path / "result.bin", len(problem[0]), len(problem[1]), len(problem[3]), len(groups[1])), done.stderr
-
-
 def spec_layout(problem, groups, lam=ub.BA_LAMBDA0):
     """`one_pass` in the host program's layout."""
     s = one_pass(problem, groups, lam)
@@ -314,25 +272,6 @@ def relative_differences(host, spec, what):
     return out
 
 
-_BUILT = {}
-
-
-def _build(out, extra):
-    proc = subprocess.run(HOST_BUILD + extra + ["-o", str(out), SOURCE], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert proc.returncode == 0, f"{out.name} does not build:\n{proc.stdout}"
-    return str(out)
-
-
-@pytest.fixture(scope="session")
-def bundle_intr_host(tmp_path_factory):
-    """tools/bundle_intr_host.cpp built with the line its source gives (once per session, test_bundle_intr_gpu.py shares it)."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc to build the host program with")
-    if "plain" not in _BUILT:
-        _BUILT["plain"] = _build(tmp_path_factory.mktemp("bundle_intr_host") / "bundle_intr_host", [])
-    return _BUILT["plain"]
-
-
 def host_problems():
     """The windowed problem from 1.03 f with one tied group, the 300 random ones with random groups, the edge cases of
     util_bundle under two groups, and random problem 7 with a slot in a group outside the table -> [(name, problem, groups)]."""
@@ -351,10 +290,10 @@ def spec_layouts():
     return [(name, problem, groups, spec_layout(problem, groups)) for name, problem, groups in host_problems()]
 
 
-def test_host_build_matches_the_spec_on_the_windowed_the_random_and_the_edge_problems(bundle_intr_host, tmp_path):
+def test_host_build_matches_the_spec_on_the_windowed_the_random_and_the_edge_problems(bundle_host, tmp_path):  # noqa: F811
     worst = {}
     for name, problem, groups, spec in spec_layouts():
-        host, _ = run_host(bundle_intr_host, tmp_path, problem, groups, ub.BA_LAMBDA0, spec["dc"], spec["dtheta"])
+        host, _ = run_host(bundle_host, tmp_path, problem, ub.BA_LAMBDA0, spec["dc"], groups=groups, dtheta=spec["dtheta"])
         for k, v in relative_differences(host, spec, name).items():
             if v > worst.get(k, (-1.0, ""))[0]:
                 worst[k] = (v, name)
@@ -365,15 +304,12 @@ def test_host_build_matches_the_spec_on_the_windowed_the_random_and_the_edge_pro
     assert len(masks) >= 24 and {len(groups[1]) for _, _, groups, _ in spec_layouts()} == {1, 2, 3}
 
 
-def test_host_build_under_the_sanitizers_reports_nothing(tmp_path):
+def test_host_build_under_the_sanitizers_reports_nothing(tmp_path, tmp_path_factory):
     """The same program with the host half built -fsanitize=address,undefined, run on its own over the same problems and over
     offsets and indices that name nothing."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc to build the host program with")
-    program = _build(tmp_path / "bundle_intr_host_san", ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                                                         "-Xarch_host", "-g"])
+    program = _build(tmp_path_factory, "bundle_host_san", SANITIZE)
     for name, problem, groups, spec in spec_layouts():
-        host, stderr = run_host(program, tmp_path, problem, groups, ub.BA_LAMBDA0, spec["dc"], spec["dtheta"])
+        host, stderr = run_host(program, tmp_path, problem, ub.BA_LAMBDA0, spec["dc"], groups=groups, dtheta=spec["dtheta"])
         assert stderr == "" and np.array_equal(host["free"], spec["free"]), name
     cams, points, offsets, obs_cam, obs_xy, mask = ub.random_problem(7)
     bad = offsets.copy()
@@ -382,8 +318,8 @@ def test_host_build_under_the_sanitizers_reports_nothing(tmp_path):
     index[0][2] = index[0][3] + 1
     index[1][index[0][4]] = len(obs_cam) + 100
     groups = (np.array([0, 1, 2 ** 31 - 1, -2 ** 31] + [1] * (len(cams) - 4), np.int32), np.array([0, ui.TIED], np.uint8))
-    host, stderr = run_host(program, tmp_path, (cams, points, bad, obs_cam, obs_xy, mask), groups, ub.BA_LAMBDA0, np.zeros(6 * len(cams)),
-                            np.zeros(8), index)
+    host, stderr = run_host(program, tmp_path, (cams, points, bad, obs_cam, obs_xy, mask), ub.BA_LAMBDA0, np.zeros(6 * len(cams)), index, groups,
+                            np.zeros(8))
     assert stderr == "" and not host["T"][3].any() and not host["T"][-1].any() and not host["terms"][:, [3, -1]].any()
     assert np.isfinite(host["B"]).all() and np.isfinite(host["C"]).all() and host["valid"].all()
 
@@ -523,7 +459,7 @@ def test_pipeline_passes_the_flag_and_leaves_the_grown_model_alone(tmp_path, mon
     real = grow.build_sparse_model
     monkeypatch.setattr(grow, "build_sparse_model", lambda path, device="cuda": real(path, device="cpu", two_view_pose_fn=spec_two_view_pose,
                                                                                      estimate_fn=spec_estimate, triangulate_fn=spec_triangulate))
-    monkeypatch.setattr(bundle, "_gpu_bundle", spec_bundle_intr)
+    monkeypatch.setattr(bundle, "bundle_adjust", spec_bundle_intr)
     texts = {}
     for name, refine in (("held", False), ("refined", True)):
         p = rp.Pipeline(Config())

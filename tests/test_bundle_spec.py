@@ -1,7 +1,7 @@
 """CPU tests of bundle adjustment: the numpy specification of tests/util_bundle.py (derivatives, the exact
 scene, held parameters, the drift it removes from the grown model of the windowed scene), the kernels' routines compiled for
-the host (tools/bundle_host.cpp) against it, plain and under the host sanitizers, the product's host logic with the
-specification in its four GPU seams, and the pipeline's flag.  No GPU."""
+the host (tools/bundle_host.cpp, whose helpers here the other bundle tests share) against it, plain and under the host
+sanitizers, the product's host logic with the specification in its four GPU seams, and the pipeline's flag.  No GPU."""
 import os
 import shutil
 import subprocess
@@ -13,6 +13,7 @@ import pytest
 
 import util_absolute_pose as ua
 import util_bundle as ub
+import util_bundle_intr as ui
 import util_mapper as um
 from test_absolute_pose_spec import scene_images, spec_estimate, spec_two_view_pose, write_scene_db
 from test_mapper_spec import spec_triangulate, windowed
@@ -175,41 +176,58 @@ def test_filter_drops_a_gross_observation_and_a_point_without_parallax():
 
 
 # ---- the kernels' routines on the host ---------------------------------------------------------------------------------------------------
-def write_problem_file(path, problem, lam, dc, index=None):
-    """The input of tools/bundle_host.cpp; `index`: cam_offsets, cam_obs, obs_point where they are not ub.camera_index's."""
+def write_problem_file(path, problem, lam, dc, index=None, groups=None, dtheta=()):
+    """The input of tools/bundle_host.cpp; `index`: cam_offsets, cam_obs, obs_point where they are not ub.camera_index's;
+    `groups`: cam_group, intr_mask and with them `dtheta` for the border's section."""
     cams, points, offsets, obs_cam, obs_xy, mask = problem
+    cam_group, intr_mask = groups or ((), ())
     cam_offsets, cam_obs, obs_point = index or ub.camera_index(obs_cam, offsets, len(cams))
     with open(path, "wb") as f:
-        f.write(np.array([len(cams), len(points), len(obs_cam)], np.int32).tobytes())
+        f.write(np.array([len(cams), len(points), len(obs_cam), len(intr_mask)], np.int32).tobytes())
         f.write(np.array([lam], np.float64).tobytes())
-        for a in (offsets, obs_cam, cam_offsets, cam_obs, obs_point, mask):
+        for a in (offsets, obs_cam, cam_offsets, cam_obs, obs_point, mask, cam_group, intr_mask):
             f.write(np.ascontiguousarray(a).astype(np.int32).tobytes())
-        for a in (cams, points, obs_xy, dc):
+        for a in (cams, points, obs_xy, dc, dtheta):
             f.write(np.ascontiguousarray(a, np.float64).tobytes())
 
 
-def read_result_file(path, n_cams, n_points, total):
+def result_shapes(n_cams, n_points, total, G):
+    """The float64 arrays of the border's section."""
+    rows = 24 * G + 16 * G * G
+    return [("xn", (total, 2)), ("T", (n_points, G, 12)), ("terms", (rows, n_points)), ("sums", (rows,)), ("B", (6 * n_cams, 4 * G)),
+            ("C", (4 * G, 4 * G)), ("h", (4 * G,)), ("cams", (n_cams, 16)), ("points", (n_points, 3)), ("dx", (n_points, 3))]
+
+
+def read_result_file(path, n_cams, n_points, total, G=0):
+    """-> the plain section; with groups the border's section, the plain one under "plain"."""
     raw = open(path, "rb").read()
+    at = 0
+
+    def take(dtype, shape):
+        nonlocal at
+        n = int(np.prod(shape))
+        a = np.frombuffer(raw, dtype, n, at).reshape(shape)
+        at += a.nbytes
+        return a
+
     shapes = [("vinv", (n_points, 6)), ("gp", (n_points, 3)), ("cost", (n_points,)), ("total_cost", (1,)), ("S", (6 * n_cams, 6 * n_cams)),
               ("g", (6 * n_cams,)), ("cams", (n_cams, 16)), ("points", (n_points, 3)), ("dx", (n_points, 3)), ("obs_lin", (total, 32))]
-    out, at = {}, 0
-    for name, shape in shapes:
-        n = int(np.prod(shape))
-        out[name] = np.frombuffer(raw, np.float64, n, at).reshape(shape)
-        at += 8 * n
-    out["count"] = np.frombuffer(raw, np.int32, n_points, at)
-    at += 4 * n_points
-    out["obs_ok"] = np.frombuffer(raw, np.uint8, total, at)
-    assert at + total == len(raw)
+    out = {name: take(np.float64, shape) for name, shape in shapes}
+    out["count"], out["obs_ok"] = take(np.int32, (n_points,)), take(np.uint8, (total,))
+    if G:
+        out = dict({name: take(np.float64, shape) for name, shape in result_shapes(n_cams, n_points, total, G)}, plain=out)
+        out["free"], out["valid"] = take(np.uint8, (4 * G,)), take(np.uint8, (n_cams,))
+    assert at == len(raw)
     return out
 
 
-def run_host(program, tmp_path, problem, lam, dc, index=None):
-    write_problem_file(tmp_path / "problem.bin", problem, lam, dc, index)
+def run_host(program, tmp_path, problem, lam, dc, index=None, groups=None, dtheta=()):
+    write_problem_file(tmp_path / "problem.bin", problem, lam, dc, index, groups, dtheta)
     done = subprocess.run([program, str(tmp_path / "problem.bin"), str(tmp_path / "result.bin")], stdout=subprocess.PIPE,
                           stderr=subprocess.PIPE, text=True)
     assert done.returncode == 0, done.stderr
-    return read_result_file(tmp_path / "result.bin", len(problem[0]), len(problem[1]), len(problem[3])), done.stderr
+    G = len(groups[1]) if groups else 0
+    return read_result_file(tmp_path / "result.bin", len(problem[0]), len(problem[1]), len(problem[3]), G), done.stderr
 
 
 def spec_pass(problem, lam=ub.BA_LAMBDA0):
@@ -239,23 +257,26 @@ def relative_differences(host, spec, what):
     return out
 
 
+SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-Xarch_host", "-g"]
 _BUILT = {}
 
 
-def _build(out, extra):
-    proc = subprocess.run(HOST_BUILD + extra + ["-o", str(out), SOURCE], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert proc.returncode == 0, f"{out.name} does not build:\n{proc.stdout}"
-    return str(out)
+def _build(tmp_path_factory, name, extra=()):
+    """tools/bundle_host.cpp built with the line its source gives and `extra`, once per session and name."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc to build the host program with")
+    if name not in _BUILT:
+        out = tmp_path_factory.mktemp(name) / name
+        proc = subprocess.run(HOST_BUILD + list(extra) + ["-o", str(out), SOURCE], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert proc.returncode == 0, f"{name} does not build:\n{proc.stdout}"
+        _BUILT[name] = str(out)
+    return _BUILT[name]
 
 
 @pytest.fixture(scope="session")
 def bundle_host(tmp_path_factory):
-    """tools/bundle_host.cpp built with the line its source gives (once per session, test_bundle_gpu.py shares it)."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc to build the host program with")
-    if "plain" not in _BUILT:
-        _BUILT["plain"] = _build(tmp_path_factory.mktemp("bundle_host") / "bundle_host", [])
-    return _BUILT["plain"]
+    """The host program (the other bundle tests share it)."""
+    return _build(tmp_path_factory, "bundle_host")
 
 
 def host_problems():
@@ -303,12 +324,9 @@ def test_host_build_matches_the_spec_on_the_windowed_the_random_and_the_edge_pro
     assert max(v for v, _ in worst.values()) <= ub.TOL_REL
 
 
-def test_host_build_under_the_sanitizers_reports_nothing(tmp_path):
+def test_host_build_under_the_sanitizers_reports_nothing(tmp_path, tmp_path_factory):
     """The same program with the host half built -fsanitize=address,undefined, run on its own over the same problems."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc to build the host program with")
-    program = _build(tmp_path / "bundle_host_san", ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                                                    "-Xarch_host", "-g"])
+    program = _build(tmp_path_factory, "bundle_host_san", SANITIZE)
     for name, problem, spec in spec_passes():
         host, stderr = run_host(program, tmp_path, problem, ub.BA_LAMBDA0, spec["dc"])
         assert stderr == "" and np.array_equal(host["count"], spec["count"]), name
@@ -318,6 +336,19 @@ def test_host_build_under_the_sanitizers_reports_nothing(tmp_path):
     bad[3], bad[-1] = bad[4] + 1, len(obs_cam) + 5
     host, stderr = run_host(program, tmp_path, (cams, points, bad, obs_cam, obs_xy, mask), ub.BA_LAMBDA0, np.zeros(6 * len(cams)))
     assert stderr == "" and host["count"][3] == 0 and host["count"][-1] == 0 and np.isfinite(host["S"]).all()
+
+
+def test_groups_leave_every_byte_of_the_plain_section(bundle_host, tmp_path):
+    """The plain arrays are computed before and apart from the border: with groups the program writes the same bytes."""
+    for seed, problem in ((7, ub.random_problem(7)), (8, ub.edge_problems()["short_tracks"])):
+        groups = ui.random_groups(seed, len(problem[0]))
+        dc = np.random.RandomState(seed).normal(0, 2e-3, 6 * len(problem[0]))
+        dtheta = np.random.RandomState(seed).normal(0, 0.5, 4 * len(groups[1]))
+        plain, _ = run_host(bundle_host, tmp_path, problem, ub.BA_LAMBDA0, dc)
+        both, _ = run_host(bundle_host, tmp_path, problem, ub.BA_LAMBDA0, dc, groups=groups, dtheta=dtheta)
+        assert len(groups[1]) >= 1 and sorted(both["plain"]) == sorted(plain) and len(plain) == 12
+        for k, a in plain.items():
+            assert both["plain"][k].tobytes() == a.tobytes(), (seed, k)
 
 
 # ---- the product's host logic with the specification in its seams -----------------------------------------------------------------------
@@ -462,7 +493,7 @@ def test_pipeline_writes_the_adjusted_model_beside_an_unchanged_grown_one(tmp_pa
 
     import vit_colmap_amd.mapping.bundle as bundle
 
-    monkeypatch.setattr(bundle, "_gpu_bundle", spec_bundle)
+    monkeypatch.setattr(bundle, "bundle_adjust", spec_bundle)
     on = rp.Pipeline(Config())
     on.last_stats = {"verified_pairs": 10}
     on._write_sparse_model(tmp_path / "w.db", tmp_path / "on", "cpu", adjust=True)

@@ -1,63 +1,88 @@
-// The three steps of vit_colmap_amd/csrc/bundle.hip on the CPU: its per-point and per-entry routines are __host__ __device__,
-// so this program includes the kernel source and calls them point after point and, for the camera pass, lane after lane
-// between the places where the kernel has its barriers.  It is how the kernels' arithmetic is compared with the specification
-// without a GPU (tests/test_bundle_spec.py; HOST_SPEC_REL of tests/util_bundle.py was measured with it), what the GPU tests
-// expect the kernels' bytes to equal, how the routines are run under a host sanitizer and where a fault in them is looked
-// for with a host debugger.  tools/triangulate_host.cpp is its counterpart for csrc/triangulate.hip.
+// The kernels of vit_colmap_amd/csrc/bundle.hip on the CPU, the plain adjustment and the border of the intrinsics: its per-point
+// and per-entry routines are __host__ __device__, so this program includes the kernel source and calls them point after point,
+// row after row and, for the two camera passes, lane after lane between the places where the kernel has its barriers.  It is how
+// the kernels' arithmetic is compared with the specification without a GPU (tests/test_bundle_spec.py,
+// tests/test_bundle_intr_spec.py; HOST_SPEC_REL of tests/util_bundle.py and tests/util_bundle_intr.py was measured with it), what
+// the GPU tests expect the kernels' bytes to equal, how the routines are run under a host sanitizer and where a fault in them is
+// looked for with a host debugger.  tools/triangulate_host.cpp is its counterpart for csrc/triangulate.hip.
 //
 //   hipcc -x hip --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -o bundle_host tools/bundle_host.cpp
 //   ./bundle_host problem.bin result.bin
-// problem.bin: int32 n_cams, n_points, total; float64 lambda; int32 offsets (n_points + 1), obs_cam (total), cam_offsets
-// (n_cams + 1), cam_obs (total), obs_point (total), const_mask (n_cams, one int32 each); float64 cams (n_cams, 16), points
-// (n_points, 3), obs_xy (total, 2), dc (n_cams, 6): the step is taken with the caller's dc, no system is solved here.
-// result.bin: float64 vinv (n_points, 6), gp (n_points, 3), cost (n_points), total_cost (1), S (6 n_cams, 6 n_cams), g
-// (6 n_cams), out_cams (n_cams, 16), out_points (n_points, 3), dx (n_points, 3), obs_lin (total, 32); int32 count (n_points);
-// uint8 obs_ok (total).  Offsets of any kind are passed on as they are: the routines check them.
-#include <cstdio>
-#include <vector>
-
+// problem.bin: int32 n_cams, n_points, total, n_groups (>= 0); float64 lambda; int32 offsets (n_points + 1), obs_cam (total),
+// cam_offsets (n_cams + 1), cam_obs (total), obs_point (total), const_mask (n_cams), cam_group (n_cams; none without groups),
+// intr_mask (n_groups); float64 cams (n_cams, 16), points (n_points, 3), obs_xy (total, 2), dc (n_cams, 6), dtheta (n_groups, 4):
+// the steps are taken with the caller's dc and dtheta, no system is solved here.
+// result.bin, the plain section: float64 vinv (n_points, 6), gp (n_points, 3), cost (n_points), total_cost (1), S (6 n_cams,
+// 6 n_cams), g (6 n_cams), out_cams (n_cams, 16), out_points (n_points, 3), dx (n_points, 3) (the step under dc alone), obs_lin
+// (total, 32); int32 count (n_points); uint8 obs_ok (total).  With n_groups = G >= 1 the border's section follows: float64 obs_xn
+// (total, 2), T (n_points, G, 12), terms (24 G + 16 G^2, n_points), sums (24 G + 16 G^2), B (6 n_cams, 4 G), C (4 G, 4 G), h (4 G),
+// out_cams, out_points, dx (the step under dc and dtheta); uint8 free (4 G), valid (n_cams).
+// Offsets of any kind are passed on as they are: the routines check them.
 #include "../vit_colmap_amd/csrc/bundle.hip"
+#include "host_io.h"
 
-template <typename T>
-static bool read_all(std::FILE* f, std::vector<T>& v) {
-  return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
+// The camera pass of one wave (ba_camera_walk) lane after lane: every batch of camera a's list is prepared by all lanes, then
+// visit(lane, o, j, lo, hi, y) is called for every lane in turn over the batch's usable observations in order.
+template <typename Visit>
+static void camera_walk(const BaProblem& d, const BaLinear& l, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
+                        int a, Visit visit) {
+  BaBatch batch;
+  int first, last;
+  if (!ba_camera_list(cam_offsets, a, d.total, first, last)) return;
+  for (int base = first; base < last; base += kBaWave) {
+    for (int lane = 0; lane < kBaWave; ++lane) ba_prepare(d, l, cam_obs, obs_point, a, base + lane, last, lane, batch);
+    const int m = last - base < kBaWave ? last - base : kBaWave;
+    for (int lane = 0; lane < kBaWave; ++lane)
+      for (int k = 0; k < m; ++k)
+        if (batch.o[k] >= 0) visit(lane, batch.o[k], batch.j[k], batch.lo[k], batch.hi[k], batch.y[k]);
+  }
 }
 
-template <typename T>
-static void write_all(std::FILE* f, const std::vector<T>& v) {
-  if (!v.empty()) std::fwrite(v.data(), sizeof(T), v.size(), f);
+// The two step kernels -> out_cams, out_points, dx, valid.
+struct Step {
+  std::vector<double> cams, points, dx;
+  std::vector<uint8_t> valid;
+};
+
+static Step take_step(const BaProblem& d, const BaLinear& l, const BaGroups& gr, const double* T, const double* dc, const double* dtheta) {
+  Step s{std::vector<double>(16 * (size_t)d.n_cams), std::vector<double>(3 * (size_t)d.n_points), std::vector<double>(3 * (size_t)d.n_points),
+         std::vector<uint8_t>(d.n_cams)};
+  for (int j = 0; j < d.n_points; ++j) {
+    double dX[3];
+    ba_point_step(d, l, T, gr.n_groups, dc, dtheta, j, dX);
+    for (int k = 0; k < 3; ++k) s.dx[3 * (size_t)j + k] = dX[k], s.points[3 * (size_t)j + k] = d.points[3 * (size_t)j + k] + dX[k];
+  }
+  for (int a = 0; a < d.n_cams; ++a)
+    s.valid[a] = ba_camera_step(d.cams + 16 * (size_t)a, dc + 6 * (size_t)a, gr, a, dtheta, s.cams.data() + 16 * (size_t)a) ? 1 : 0;
+  return s;
 }
 
 int main(int argc, char** argv) {
-  if (argc != 3) {
-    std::fprintf(stderr, "usage: %s problem.bin result.bin\n", argv[0]);
-    return 2;
-  }
-  std::FILE* in = std::fopen(argv[1], "rb");
-  if (!in) {
-    std::fprintf(stderr, "cannot open %s\n", argv[1]);
-    return 2;
-  }
-  int32_t head[3];
+  std::FILE* in = open_input(argc, argv, "problem.bin result.bin");
+  if (!in) return 2;
+  int32_t head[4];
   double lambda;
-  if (std::fread(head, sizeof(int32_t), 3, in) != 3 || std::fread(&lambda, sizeof(double), 1, in) != 1 || head[0] < 0 || head[1] < 0 ||
-      head[2] < 0 || head[0] > VC_BA_MAX_CAMS) {
+  if (std::fread(head, sizeof(int32_t), 4, in) != 4 || std::fread(&lambda, sizeof(double), 1, in) != 1 || head[0] < 0 || head[1] < 0 ||
+      head[2] < 0 || head[3] < 0 || head[0] > VC_BA_MAX_CAMS || head[3] > VC_BA_MAX_GROUPS) {
     std::fprintf(stderr, "%s: no header\n", argv[1]);
     return 2;
   }
-  const int n_cams = head[0], n_points = head[1], total = head[2];
+  const int n_cams = head[0], n_points = head[1], total = head[2], G = head[3];
   std::vector<int32_t> offsets(n_points + 1), obs_cam(total), cam_offsets(n_cams + 1), cam_obs(total), obs_point(total), mask32(n_cams);
+  std::vector<int32_t> cam_group(G > 0 ? n_cams : 0), intr32(G);
   std::vector<double> cams(16 * (size_t)n_cams), points(3 * (size_t)n_points), obs_xy(2 * (size_t)total), dc(6 * (size_t)n_cams);
+  std::vector<double> dtheta(4 * (size_t)G);
   const bool ok = read_all(in, offsets) && read_all(in, obs_cam) && read_all(in, cam_offsets) && read_all(in, cam_obs) &&
-                  read_all(in, obs_point) && read_all(in, mask32) && read_all(in, cams) && read_all(in, points) && read_all(in, obs_xy) &&
-                  read_all(in, dc);
+                  read_all(in, obs_point) && read_all(in, mask32) && read_all(in, cam_group) && read_all(in, intr32) && read_all(in, cams) &&
+                  read_all(in, points) && read_all(in, obs_xy) && read_all(in, dc) && read_all(in, dtheta);
   std::fclose(in);
   if (!ok) {
     std::fprintf(stderr, "%s: shorter than its header says\n", argv[1]);
     return 2;
   }
-  std::vector<uint8_t> const_mask(n_cams);
+  std::vector<uint8_t> const_mask(n_cams), intr_mask(G);
   for (int a = 0; a < n_cams; ++a) const_mask[a] = (uint8_t)mask32[a];
+  for (int g = 0; g < G; ++g) intr_mask[g] = (uint8_t)intr32[g];
 
   // 1. the points pass and the total cost
   std::vector<double> vinv(6 * (size_t)n_points), gp(3 * (size_t)n_points), cost(n_points), total_cost(1, 0.0);
@@ -77,43 +102,60 @@ int main(int argc, char** argv) {
   const BaLinear l{vinv.data(), gp.data(), obs_ok.data(), obs_lin.data()};
   std::vector<double> S(36 * (size_t)n_cams * n_cams), g(6 * (size_t)n_cams), acc(36 * (size_t)n_cams);
   for (int a = 0; a < n_cams; ++a) {
-    BaBatch batch;
     BaLane lanes[kBaWave];
     for (int lane = 0; lane < kBaWave; ++lane) lanes[lane] = BaLane{0.0, 0.0, 0.0};
     for (double& v : acc) v = 0.0;
-    const int first = cam_offsets[a], last = cam_offsets[a + 1];
-    if (first >= 0 && last >= first && last <= total) {
-      for (int base = first; base < last; base += kBaWave) {
-        for (int lane = 0; lane < kBaWave; ++lane) ba_prepare(d, l, cam_obs.data(), obs_point.data(), a, base + lane, last, lane, batch);
-        const int m = last - base < kBaWave ? last - base : kBaWave;
-        for (int lane = 0; lane < kBaWave; ++lane)
-          for (int k = 0; k < m; ++k)
-            if (batch.o[k] >= 0)
-              ba_lane_update(d, l, a, batch.o[k], batch.j[k], batch.lo[k], batch.hi[k], lane, batch.y[k], acc.data(), lanes[lane]);
-      }
-    }
+    camera_walk(d, l, cam_offsets.data(), cam_obs.data(), obs_point.data(), a, [&](int lane, int o, int j, int lo, int hi, const double* y) {
+      ba_lane_update(d, l, a, o, j, lo, hi, lane, y, acc.data(), lanes[lane]);
+    });
     for (int lane = 0; lane < kBaWave; ++lane)
       ba_lane_finish(n_cams, const_mask[a], lambda, a, lane, acc.data(), lanes[lane], S.data(), g.data());
   }
 
   // 3. the step under the caller's dc
-  std::vector<double> out_cams(16 * (size_t)n_cams), out_points(3 * (size_t)n_points), dx(3 * (size_t)n_points);
-  for (int j = 0; j < n_points; ++j) {
-    double dX[3];
-    ba_point_step(d, l, dc.data(), j, dX);
-    for (int k = 0; k < 3; ++k) dx[3 * (size_t)j + k] = dX[k], out_points[3 * (size_t)j + k] = points[3 * (size_t)j + k] + dX[k];
-  }
-  for (int a = 0; a < n_cams; ++a) ba_camera_step(cams.data() + 16 * (size_t)a, dc.data() + 6 * (size_t)a, out_cams.data() + 16 * (size_t)a);
+  const Step plain = take_step(d, l, BaGroups{nullptr, nullptr, 0}, nullptr, dc.data(), nullptr);
 
-  std::FILE* out = std::fopen(argv[2], "wb");
-  if (!out) {
-    std::fprintf(stderr, "cannot open %s\n", argv[2]);
-    return 2;
-  }
+  std::FILE* out = open_output(argv[2]);
+  if (!out) return 2;
   write_all(out, vinv), write_all(out, gp), write_all(out, cost), write_all(out, total_cost), write_all(out, S), write_all(out, g);
-  write_all(out, out_cams), write_all(out, out_points), write_all(out, dx), write_all(out, obs_lin), write_all(out, count);
+  write_all(out, plain.cams), write_all(out, plain.points), write_all(out, plain.dx), write_all(out, obs_lin), write_all(out, count);
   write_all(out, obs_ok);
+
+  if (G >= 1) {
+    // 4. the intrinsics' terms of every point, their ordered sums, C and h
+    const BaGroups gr{cam_group.data(), intr_mask.data(), G};
+    const int rows = ba_term_rows(G), m = 4 * G;
+    std::vector<double> obs_xn(2 * (size_t)total), T((size_t)n_points * G * kBaT), terms((size_t)rows * n_points), sums(rows);
+    for (int j = 0; j < n_points; ++j) ba_linearize_point_intrinsics(d, l, gr, j, obs_xn.data(), T.data(), terms.data());
+    for (int r = 0; r < rows; ++r) {
+      double sum = 0.0;
+      for (int j = 0; j < n_points; ++j) sum += terms[(size_t)r * n_points + j];
+      sums[r] = sum;
+    }
+    std::vector<double> B(6 * (size_t)n_cams * m), C((size_t)m * m), h(m);
+    std::vector<uint8_t> free_(m);
+    for (int idx = 0; idx < m * m; ++idx) C[idx] = ba_border_c(sums.data(), gr, lambda, idx / m, idx % m);
+    for (int row = 0; row < m; ++row) h[row] = ba_border_h(sums.data(), gr, row), free_[row] = ba_theta_free(sums.data(), gr, row / 4, row % 4) ? 1 : 0;
+
+    // 5. the border's camera pass
+    for (int a = 0; a < n_cams; ++a) {
+      BaBorderLane lanes[kBaWave];
+      for (int lane = 0; lane < kBaWave; ++lane)
+        for (int k = 0; k < kBaBorderSlots; ++k) lanes[lane].jt[k] = lanes[lane].yt[k] = 0.0;
+      const int ga = ba_group_of(gr, a);
+      camera_walk(d, l, cam_offsets.data(), cam_obs.data(), obs_point.data(), a, [&](int lane, int o, int j, int, int, const double* y) {
+        ba_border_update(l, gr, obs_xn.data(), T.data(), ga, o, j, lane, y, lanes[lane]);
+      });
+      for (int lane = 0; lane < kBaWave; ++lane) ba_border_finish(G, a, lane, lanes[lane], B.data());
+    }
+
+    // 6. the step under the caller's dc and dtheta
+    const Step step = take_step(d, l, gr, T.data(), dc.data(), dtheta.data());
+    write_all(out, obs_xn), write_all(out, T), write_all(out, terms), write_all(out, sums), write_all(out, B), write_all(out, C);
+    write_all(out, h), write_all(out, step.cams), write_all(out, step.points), write_all(out, step.dx), write_all(out, free_);
+    write_all(out, step.valid);
+  }
   std::fclose(out);
-  std::printf("%d cameras, %d points, %d observations, cost %.17g\n", n_cams, n_points, total, total_cost[0]);
+  std::printf("%d cameras, %d points, %d observations, %d groups, cost %.17g\n", n_cams, n_points, total, G, total_cost[0]);
   return 0;
 }

@@ -9,26 +9,12 @@
 // tracks.bin: int32 n_tracks, n_cams, total; float64 max_error_px, min_tri_angle_tan2; int32 offsets (n_tracks + 1), seeds
 // (n_tracks), obs_cam (total); float64 obs_xy (total, 2), cams (n_cams, 16).  points.bin: float64 xyz (n_tracks, 3), error
 // (n_tracks); int32 count (n_tracks); uint8 mask (total).  Offsets that do not ascend from 0 to total are refused.
-#include <cstdio>
-#include <vector>
-
 #include "../vit_colmap_amd/csrc/triangulate.hip"
-
-template <typename T>
-static bool read_all(std::FILE* f, std::vector<T>& v) {
-  return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
-}
+#include "host_io.h"
 
 int main(int argc, char** argv) {
-  if (argc != 3) {
-    std::fprintf(stderr, "usage: %s tracks.bin points.bin\n", argv[0]);
-    return 2;
-  }
-  std::FILE* in = std::fopen(argv[1], "rb");
-  if (!in) {
-    std::fprintf(stderr, "cannot open %s\n", argv[1]);
-    return 2;
-  }
+  std::FILE* in = open_input(argc, argv, "tracks.bin points.bin");
+  if (!in) return 2;
   int32_t head[3];
   double thr[2];
   if (std::fread(head, sizeof(int32_t), 3, in) != 3 || std::fread(thr, sizeof(double), 2, in) != 2 || head[0] < 0 || head[1] < 0 ||
@@ -63,15 +49,9 @@ int main(int argc, char** argv) {
     xyz[3 * t] = X[0], xyz[3 * t + 1] = X[1], xyz[3 * t + 2] = X[2];
     accepted += count[t] > 0;
   }
-  std::FILE* out = std::fopen(argv[2], "wb");
-  if (!out) {
-    std::fprintf(stderr, "cannot open %s\n", argv[2]);
-    return 2;
-  }
-  std::fwrite(xyz.data(), sizeof(double), xyz.size(), out);
-  std::fwrite(error.data(), sizeof(double), error.size(), out);
-  std::fwrite(count.data(), sizeof(int32_t), count.size(), out);
-  std::fwrite(mask.data(), 1, mask.size(), out);
+  std::FILE* out = open_output(argv[2]);
+  if (!out) return 2;
+  write_all(out, xyz), write_all(out, error), write_all(out, count), write_all(out, mask);
   std::fclose(out);
   std::printf("%d tracks, %ld accepted\n", n_tracks, accepted);
   return 0;

@@ -1,29 +1,32 @@
-// Bundle adjustment (gfx950): the three kernels of one Levenberg-Marquardt iteration over every pose and
-// every point of a sparse model, by the Schur complement of the points.  vc_ba_linearize_points, vc_ba_reduce_cameras and
-// vc_ba_step are what vit_colmap_amd/mapping/bundle.py repeats; the reduced system between the last two is solved by the
-// caller.  Specification: tests/util_bundle.py.  This build's own published rule; parity with COLMAP / Ceres is unpinned.
+// Bundle adjustment (gfx950): the kernels of one Levenberg-Marquardt iteration over every pose and every point
+// of a sparse model and, where groups of cameras are given, over their intrinsics (fx, fy, cx, cy), by the Schur complement of
+// the points.  vit_colmap_amd/mapping/bundle.py repeats vc_ba_linearize_points, vc_ba_reduce_cameras and vc_ba_step; with groups
+// (mapping/bundle_intr.py) vc_ba_linearize_intrinsics and vc_ba_reduce_border follow the reduction and vc_ba_step_intrinsics takes
+// the step: the groups' unknowns border the reduced system, [[S, B], [B', C]] (dc, dtheta) = -(g, h).  The system is solved by
+// the caller.  Specification: tests/util_bundle.py, tests/util_bundle_intr.py.  This build's own published rule; parity with
+// COLMAP / Ceres is unpinned.
 //
 // float64 in single operations in the written order (-ffp-contract=off), the only library call is sqrt, no atomics.
-//   linearize  one point per lane, one wave per workgroup, no LDS: every observation of the point's track is linearised
-//              (residual r, J_c 2x6, W = J_c' J_p 6x3, written per observation: 32 numbers), V = sum J_p' J_p, g_p and the
-//              cost are accumulated in track order, V is damped and inverted by the adjugate.  A second launch of one wave
-//              adds the costs in point order.
-//   reduce     one workgroup of one wave per camera a, the row block [6][6 n_cams] of sum Y W' in LDS.  Entry e = 6 r + c of
-//              block b belongs to lane (36 b + e) mod 64 for the whole launch; nobody else reads or writes it, so there is no
-//              atomic and the order of a lane's additions is the rule's: camera a's observations in ascending order and,
-//              inside each, the track of its point in track order.  What lanes share is prepared 64 observations at a time,
-//              one per lane (the list's entry resolved, Y = W V^-1), and left in LDS between two barriers; every lane then
-//              walks the batch in order, so the chain of dependent loads that resolves an entry is paid once per batch; along
-//              a track it loads the next element's flag and camera while the current element's W is on its way.
-//   step       one point per lane: dX = -V^-1 (g_p + sum W' dc) in track order, X + dX; one camera per lane: q = (1, w / 2)
-//              normalised, R(q) R, t + dt.
-// The border of the intrinsics (vc_ba_linearize_intrinsics, vc_ba_reduce_border, vc_ba_step_intrinsics; tools/bundle_intr_host.cpp,
-// tests/util_bundle_intr.py) adds (fx, fy, cx, cy) of every group of cameras to that iteration:
-//   linearize  one point per lane, the groups outside and the track inside: T = sum J_theta' J_p, q, hq and the point's products
-//              T V^-1 T', T V^-1 g_p; nothing is a register array indexed by a runtime value
-//   reduce     one wave per ordered sum over the points (the total cost's scheme) -> C, h; one wave per camera over its list in
-//              the camera pass' batches, a lane's entries of B_a [6][4 G] in its registers
-//   step       the point's and the camera's step with the groups' terms; whether the candidate's focal lengths are positive
+//   points pass  one point per lane, one wave per workgroup, no LDS.  ba_linearize_points_kernel: every observation of the point's
+//                track is linearised (ba_project; residual r, J_c 2x6, W = J_c' J_p 6x3, written per observation: 32 numbers),
+//                V = sum J_p' J_p, g_p and the cost are accumulated in track order, V is damped and inverted by the adjugate.
+//                ba_linearize_intrinsics_kernel: the groups outside and the track inside, T = sum J_theta' J_p, q, hq (ba_project
+//                again for x, y and J_p) and the point's products T V^-1 T', T V^-1 g_p; nothing is a register array indexed by a
+//                runtime value.
+//   ordered sums ba_ordered_sums_kernel, one wave per row of [rows][n], adds the row in ascending order: the total cost is the one
+//                row of the points' costs, the border's C and h come from the rows of its terms (ba_border_system_kernel).
+//   camera pass  one workgroup of one wave per camera a.  ba_camera_walk: what lanes share is prepared 64 entries of the camera's
+//                list at a time, one per lane (the entry resolved, Y = W V^-1), and left in LDS between two barriers; every lane
+//                then walks the batch in order, so the chain of dependent loads that resolves an entry is paid once per batch.
+//                ba_reduce_cameras_kernel keeps the row block [6][6 n_cams] of sum Y W' in LDS: entry e = 6 r + c of block b
+//                belongs to lane (36 b + e) mod 64 for the whole launch; nobody else reads or writes it, so there is no atomic and
+//                the order of a lane's additions is the rule's: camera a's observations in ascending order and, inside each, the
+//                track of its point in track order (the next element's flag and camera are loaded while the current element's W
+//                is on its way).  ba_reduce_border_kernel keeps a lane's entries of B_a [6][4 G] in its registers.
+//   step         ba_step_points_kernel, one point per lane: dX = -V^-1 (g_p + sum W' dc + sum T_g' dtheta_g) in track order, then
+//                group order, X + dX; ba_step_cameras_kernel, one camera per lane: q = (1, w / 2) normalised, R(q) R, t + dt, its
+//                group's dtheta added, whether the focal lengths stay positive.  vc_ba_step launches both without groups: T,
+//                dtheta, cam_group and the valid flags are then absent and not read.
 // What a lane computes is sequential and nothing depends on the order in which lanes or workgroups run, so two launches
 // return the same bits, and the same routines compiled for the host (tools/bundle_host.cpp includes this file) return the
 // device's.  Every index read from an input array is checked against the array it indexes before it is used.
@@ -66,6 +69,23 @@ __host__ __device__ __forceinline__ bool ba_track(const int32_t* __restrict__ of
   return lo >= 0 && hi >= lo && hi <= total;
 }
 
+// X in the camera of row c[16]: Y = R X, Xc = Y + t, (xu, xv) = (Xc_x, Xc_y) / Xc_z, (fu, fv) = (fx, fy) / Xc_z and J_p (2x3).
+__host__ __device__ __forceinline__ void ba_project(const double* c, const double (&X)[3], double (&Y)[3], double (&Xc)[3], double& fu,
+                                                    double& fv, double& xu, double& xv, double (&ju)[3], double (&jv)[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    Y[i] = c[3 * i] * X[0] + c[3 * i + 1] * X[1] + c[3 * i + 2] * X[2];
+    Xc[i] = Y[i] + c[9 + i];
+  }
+  const double z = Xc[2];
+  fu = c[12] / z, fv = c[13] / z, xu = Xc[0] / z, xv = Xc[1] / z;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    ju[k] = fu * (c[k] - xu * c[6 + k]);
+    jv[k] = fv * (c[3 + k] - xv * c[6 + k]);
+  }
+}
+
 // Observation o of point X: usable -> lin[32] (zeros otherwise) and J_p (2x3).
 __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, int o, const double (&X)[3], double* __restrict__ lin,
                                                     double (&ju)[3], double (&jv)[3]) {
@@ -81,23 +101,13 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, int o, c
   const double u = d.obs_xy[2 * (long long)o], v = d.obs_xy[2 * (long long)o + 1];
   ok = ok && ba_finite(u) && ba_finite(v);
   const unsigned held = ok ? d.const_mask[slot] : 0u;
-  double Y[3], Xc[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    Y[i] = row[3 * i] * X[0] + row[3 * i + 1] * X[1] + row[3 * i + 2] * X[2];
-    Xc[i] = Y[i] + row[9 + i];
-  }
+  double Y[3], Xc[3], fu, fv, xu, xv;
+  ba_project(row, X, Y, Xc, fu, fv, xu, xv, ju, jv);
   const double z = Xc[2];
   ok = ok && z > 0.0;                                        // false for NaN
   const double fx = row[12], fy = row[13], cx = row[14], cy = row[15];
   const double ru = fx * Xc[0] / z + cx - u, rv = fy * Xc[1] / z + cy - v;
-  const double fu = fx / z, fv = fy / z, xu = Xc[0] / z, xv = Xc[1] / z;
   const double au = fu * xu, av = fv * xv;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    ju[k] = fu * (row[k] - xu * row[6 + k]);
-    jv[k] = fv * (row[3 + k] - xv * row[6 + k]);
-  }
   // J_c = J_pi [ -[R X]x | I ]: the pose is perturbed on the left, Xc(w, dt) = Rot(w) (R X) + t + dt
   double cu[6] = {-(au * Y[1]), fu * Y[2] + au * Y[0], -(fu * Y[1]), fu, 0.0, -au};
   double cv[6] = {-(fv * Y[2] + av * Y[1]), av * Y[0], fv * Y[0], 0.0, fv, -av};
@@ -198,6 +208,30 @@ __host__ __device__ __forceinline__ void ba_prepare(const BaProblem& d, const Ba
   }
 }
 
+// Camera a's list of cam_obs -> false where its offsets delimit nothing: the camera is skipped, nothing of it read.
+__host__ __device__ __forceinline__ bool ba_camera_list(const int32_t* __restrict__ cam_offsets, int a, int total, int& first, int& last) {
+  first = cam_offsets[a], last = cam_offsets[a + 1];
+  return first >= 0 && last >= first && last <= total;
+}
+
+// The camera pass of one wave: camera a's list 64 entries at a time, one prepared per lane and left in LDS between two barriers
+// (at trip counts the whole wave shares), then every lane calls visit(o, j, lo, hi, y) for the batch's usable observations in order.
+template <typename Visit>
+__device__ __forceinline__ void ba_camera_walk(const BaProblem& d, const BaLinear& l, const int32_t* __restrict__ cam_offsets,
+                                               const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point, int a, int lane,
+                                               BaBatch& batch, Visit visit) {
+  int first, last;
+  if (!ba_camera_list(cam_offsets, a, d.total, first, last)) return;
+  for (int base = first; base < last; base += kBaWave) {
+    ba_prepare(d, l, cam_obs, obs_point, a, base + lane, last, lane, batch);
+    __syncthreads();
+    const int m = last - base < kBaWave ? last - base : kBaWave;
+    for (int k = 0; k < m; ++k)
+      if (batch.o[k] >= 0) visit(batch.o[k], batch.j[k], batch.lo[k], batch.hi[k], batch.y[k]);
+    __syncthreads();
+  }
+}
+
 // One lane's additions for observation o of camera a (point j, track lo .. hi): its entry of U_a, of the two sums of g_a and,
 // along the track, of the blocks of sum Y W' it owns.  acc: the row block [n_cams][36]; y: the observation's 18 numbers of ba_prepare.
 __host__ __device__ __forceinline__ void ba_lane_update(const BaProblem& d, const BaLinear& l, int a, int o, int j, int lo, int hi,
@@ -242,45 +276,9 @@ __host__ __device__ __forceinline__ void ba_lane_finish(int n_cams, unsigned hel
   if (lane < 6) g[6 * a + lane] = s.gr - s.gy;
 }
 
-// One point's right-hand side s = g_p + sum W' dc over the track in track order -> false where the point's offsets delimit
-// nothing (s is then not written).
-__host__ __device__ __forceinline__ bool ba_point_rhs(const BaProblem& d, const BaLinear& l, const double* __restrict__ dc, int j,
-                                                      double (&s)[3]) {
-  int lo, hi;
-  if (!ba_track(d.offsets, j, d.total, lo, hi)) return false;
-  s[0] = l.gp[3 * (long long)j], s[1] = l.gp[3 * (long long)j + 1], s[2] = l.gp[3 * (long long)j + 2];
-  for (int o = lo; o < hi; ++o) {
-    if (!l.obs_ok[o]) continue;
-    const int b = d.obs_cam[o];
-    if (b < 0 || b >= d.n_cams) continue;
-    const double* w = l.obs_lin + (long long)o * kBaLin + kBaLinW;
-    const double* e = dc + 6 * (long long)b;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      s[k] += w[k] * e[0] + w[3 + k] * e[1] + w[6 + k] * e[2] + w[9 + k] * e[3] + w[12 + k] * e[4] + w[15 + k] * e[5];
-  }
-  return true;
-}
-
-// dX = -V^-1 s
-__host__ __device__ __forceinline__ void ba_point_solve(const BaLinear& l, int j, const double (&s)[3], double (&dX)[3]) {
-  const double* v = l.vinv + (long long)j * 6;
-  dX[0] = -(v[0] * s[0] + v[1] * s[1] + v[2] * s[2]);
-  dX[1] = -(v[1] * s[0] + v[3] * s[1] + v[4] * s[2]);
-  dX[2] = -(v[2] * s[0] + v[4] * s[1] + v[5] * s[2]);
-}
-
-// One point's step: dX = -V^-1 (g_p + sum W' dc) over the track in track order.
-__host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const BaLinear& l, const double* __restrict__ dc, int j,
-                                                       double (&dX)[3]) {
-  dX[0] = dX[1] = dX[2] = 0.0;
-  double s[3];
-  if (ba_point_rhs(d, l, dc, j, s)) ba_point_solve(l, j, s, dX);
-}
-
-// One camera's update without trigonometry: q = (1, w / 2) / |(1, w / 2)|, R <- R(q) R, t <- t + dt; the intrinsics are copied.
-__host__ __device__ __forceinline__ void ba_camera_step(const double* __restrict__ cam, const double* __restrict__ e,
-                                                        double* __restrict__ out) {
+// One camera's pose update without trigonometry: q = (1, w / 2) / |(1, w / 2)|, R <- R(q) R, t <- t + dt; the intrinsics are copied.
+__host__ __device__ __forceinline__ void ba_pose_step(const double* __restrict__ cam, const double* __restrict__ e,
+                                                      double* __restrict__ out) {
   const double hx = 0.5 * e[0], hy = 0.5 * e[1], hz = 0.5 * e[2];
   const double n = sqrt(1.0 + hx * hx + hy * hy + hz * hz);
   const double w = 1.0 / n, x = hx / n, y = hy / n, z = hz / n;
@@ -317,8 +315,10 @@ __host__ __device__ constexpr int ba_term_p(int G, int g) { return 20 * G + 4 * 
 __host__ __device__ constexpr int ba_term_P(int G, int g, int g2) { return 24 * G + 16 * (g * G + g2); }
 __host__ __device__ constexpr int ba_term_rows(int G) { return 24 * G + 16 * G * G; }
 
-// Camera slot -> its group, -1 where the slot's group is outside [0, n_groups): its intrinsics are held.
+// Camera slot -> its group, -1 where the slot's group is outside [0, n_groups): its intrinsics are held.  Without groups
+// cam_group is not read.
 __host__ __device__ __forceinline__ int ba_group_of(const BaGroups& gr, int slot) {
+  if (gr.n_groups <= 0) return -1;
   const int g = gr.cam_group[slot];
   return g >= 0 && g < gr.n_groups ? g : -1;
 }
@@ -333,19 +333,11 @@ __host__ __device__ __forceinline__ void ba_jtheta(unsigned mask, double x, doub
   if (ba_theta_held(mask, i)) tu = tv = 0.0;
 }
 
-// A usable observation of X in camera row c again: x = Xc_x / Xc_z, y = Xc_y / Xc_z and J_p, the operations of ba_observe.
+// A usable observation of X in camera row c again: x = Xc_x / Xc_z, y = Xc_y / Xc_z and J_p.
 __host__ __device__ __forceinline__ void ba_observe_point(const double* __restrict__ c, const double (&X)[3], double& xu, double& xv,
                                                           double (&ju)[3], double (&jv)[3]) {
-  double Xc[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Xc[i] = (c[3 * i] * X[0] + c[3 * i + 1] * X[1] + c[3 * i + 2] * X[2]) + c[9 + i];
-  const double z = Xc[2], fu = c[12] / z, fv = c[13] / z;
-  xu = Xc[0] / z, xv = Xc[1] / z;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    ju[k] = fu * (c[k] - xu * c[6 + k]);
-    jv[k] = fv * (c[3 + k] - xv * c[6 + k]);
-  }
+  double Y[3], Xc[3], fu, fv;
+  ba_project(c, X, Y, Xc, fu, fv, xu, xv, ju, jv);
 }
 
 // One point: obs_xn of its track; per group (outside) over the track (inside) T, q, hq; then the point's products with V^-1.
@@ -481,28 +473,42 @@ __host__ __device__ __forceinline__ void ba_border_finish(int G, int a, int lane
   }
 }
 
-// One point's step with the border: dX = -V^-1 (g_p + sum W' dc + sum_g T_g' dtheta_g), the groups in ascending order.
-__host__ __device__ __forceinline__ void ba_point_step_intrinsics(const BaProblem& d, const BaLinear& l, const double* __restrict__ T, int G,
-                                                                  const double* __restrict__ dc, const double* __restrict__ dtheta, int j,
-                                                                  double (&dX)[3]) {
+// One point's step: dX = -V^-1 (g_p + sum W' dc + sum_g T_g' dtheta_g), the track in track order, then the groups in ascending
+// order; 0 where the point's offsets delimit nothing.  Without groups T and dtheta are not read.
+__host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const BaLinear& l, const double* __restrict__ T, int G,
+                                                       const double* __restrict__ dc, const double* __restrict__ dtheta, int j,
+                                                       double (&dX)[3]) {
   dX[0] = dX[1] = dX[2] = 0.0;
-  double s[3];
-  if (!ba_point_rhs(d, l, dc, j, s)) return;
+  int lo, hi;
+  if (!ba_track(d.offsets, j, d.total, lo, hi)) return;
+  double s[3] = {l.gp[3 * (long long)j], l.gp[3 * (long long)j + 1], l.gp[3 * (long long)j + 2]};
+  for (int o = lo; o < hi; ++o) {
+    if (!l.obs_ok[o]) continue;
+    const int b = d.obs_cam[o];
+    if (b < 0 || b >= d.n_cams) continue;
+    const double* w = l.obs_lin + (long long)o * kBaLin + kBaLinW;
+    const double* e = dc + 6 * (long long)b;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      s[k] += w[k] * e[0] + w[3 + k] * e[1] + w[6 + k] * e[2] + w[9 + k] * e[3] + w[12 + k] * e[4] + w[15 + k] * e[5];
+  }
   for (int g = 0; g < G; ++g) {
     const double* t = T + ((long long)j * G + g) * kBaT;
     const double* e = dtheta + 4 * g;
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3];
   }
-  ba_point_solve(l, j, s, dX);
+  const double* v = l.vinv + (long long)j * 6;
+  dX[0] = -(v[0] * s[0] + v[1] * s[1] + v[2] * s[2]);
+  dX[1] = -(v[1] * s[0] + v[3] * s[1] + v[4] * s[2]);
+  dX[2] = -(v[2] * s[0] + v[4] * s[1] + v[5] * s[2]);
 }
 
-// One camera's update with the border: ba_camera_step, then (fx, fy, cx, cy) += dtheta of its group (tied: dtheta_0 to both
-// focal lengths) -> whether the candidate's focal lengths are finite and positive (true where the group holds the intrinsics).
-__host__ __device__ __forceinline__ bool ba_camera_step_intrinsics(const double* __restrict__ cam, const double* __restrict__ e,
-                                                                   const BaGroups& gr, int a, const double* __restrict__ dtheta,
-                                                                   double* __restrict__ out) {
-  ba_camera_step(cam, e, out);
+// One camera's step: ba_pose_step, then (fx, fy, cx, cy) += dtheta of its group (tied: dtheta_0 to both focal lengths) -> whether
+// the candidate's focal lengths are finite and positive (true where the intrinsics are held: no group, or one outside the table).
+__host__ __device__ __forceinline__ bool ba_camera_step(const double* __restrict__ cam, const double* __restrict__ e, const BaGroups& gr,
+                                                        int a, const double* __restrict__ dtheta, double* __restrict__ out) {
+  ba_pose_step(cam, e, out);
   const int g = ba_group_of(gr, a);
   if (g < 0) return true;
   const double* th = dtheta + 4 * g;
@@ -528,15 +534,17 @@ __global__ __launch_bounds__(kBaWave) void ba_linearize_points_kernel(BaProblem 
   out_count[j] = count;
 }
 
-// The total cost: the costs added in point order.  One wave; a lane loads, every lane adds the 64 values in order.
-__global__ __launch_bounds__(kBaWave) void ba_total_cost_kernel(const double* __restrict__ cost, int n, double* __restrict__ out_total) {
+// Row blockIdx.x of [rows][n] added in ascending order, one wave per row: a lane loads, every lane adds the 64 values in order.
+// The total cost is the one row of the points' costs; the border's sums are the rows of its terms.
+__global__ __launch_bounds__(kBaWave) void ba_ordered_sums_kernel(const double* __restrict__ terms, int n, double* __restrict__ out_sums) {
+  const double* row = terms + (long long)blockIdx.x * n;
   double sum = 0.0;
   for (int base = 0; base < n; base += kBaWave) {
-    const double v = base + (int)threadIdx.x < n ? cost[base + threadIdx.x] : 0.0;
+    const double v = base + (int)threadIdx.x < n ? row[base + threadIdx.x] : 0.0;
     const int m = n - base < kBaWave ? n - base : kBaWave;
     for (int k = 0; k < m; ++k) sum += __shfl(v, k, kBaWave);
   }
-  if (threadIdx.x == 0) out_total[0] = sum;
+  if (threadIdx.x == 0) out_sums[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kBaWave) void ba_reduce_cameras_kernel(BaProblem d, BaLinear l, const int32_t* __restrict__ cam_offsets,
@@ -549,57 +557,15 @@ __global__ __launch_bounds__(kBaWave) void ba_reduce_cameras_kernel(BaProblem d,
   const int a = blockIdx.x, lane = threadIdx.x;
   for (int idx = lane; idx < 36 * d.n_cams; idx += kBaWave) acc[idx] = 0.0;  // a lane's own entries: no barrier needed
   BaLane s{0.0, 0.0, 0.0};
-  const int first = cam_offsets[a], last = cam_offsets[a + 1];
-  if (first >= 0 && last >= first && last <= d.total) {     // otherwise the camera is skipped, nothing of it read
-    for (int base = first; base < last; base += kBaWave) {
-      ba_prepare(d, l, cam_obs, obs_point, a, base + lane, last, lane, batch);
-      __syncthreads();
-      const int m = last - base < kBaWave ? last - base : kBaWave;
-      for (int k = 0; k < m; ++k)
-        if (batch.o[k] >= 0) ba_lane_update(d, l, a, batch.o[k], batch.j[k], batch.lo[k], batch.hi[k], lane, batch.y[k], acc, s);
-      __syncthreads();
-    }
-  }
+  ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
+                 [&](int o, int j, int lo, int hi, const double* y) { ba_lane_update(d, l, a, o, j, lo, hi, lane, y, acc, s); });
   ba_lane_finish(d.n_cams, d.const_mask[a], lambda, a, lane, acc, s, out_S, out_g);
-}
-
-__global__ __launch_bounds__(kBaWave) void ba_step_points_kernel(BaProblem d, BaLinear l, const double* __restrict__ dc,
-                                                                 double* __restrict__ out_points, double* __restrict__ out_dx) {
-  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (j >= d.n_points) return;
-  double dX[3];
-  ba_point_step(d, l, dc, (int)j, dX);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    out_dx[3 * j + k] = dX[k];
-    out_points[3 * j + k] = d.points[3 * j + k] + dX[k];
-  }
-}
-
-__global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(const double* __restrict__ cams, int n_cams, const double* __restrict__ dc,
-                                                                  double* __restrict__ out_cams) {
-  const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (a >= n_cams) return;
-  ba_camera_step(cams + 16 * a, dc + 6 * a, out_cams + 16 * a);
 }
 
 __global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_kernel(BaProblem d, BaLinear l, BaGroups gr, double* __restrict__ out_obs_xn,
                                                                           double* out_T, double* __restrict__ out_terms) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (j < d.n_points) ba_linearize_point_intrinsics(d, l, gr, (int)j, out_obs_xn, out_T, out_terms);
-}
-
-// Row blockIdx.x of the terms added in point order by ba_total_cost_kernel's scheme: one wave per output entry.  (That kernel
-// keeps its own copy of the loop: routed through a shared routine the compiler schedules it differently, and its code is pinned.)
-__global__ __launch_bounds__(kBaWave) void ba_border_sums_kernel(const double* __restrict__ terms, int n_points, double* __restrict__ out_sums) {
-  const double* row = terms + (long long)blockIdx.x * n_points;
-  double sum = 0.0;
-  for (int base = 0; base < n_points; base += kBaWave) {
-    const double v = base + (int)threadIdx.x < n_points ? row[base + threadIdx.x] : 0.0;
-    const int m = n_points - base < kBaWave ? n_points - base : kBaWave;
-    for (int k = 0; k < m; ++k) sum += __shfl(v, k, kBaWave);
-  }
-  if (threadIdx.x == 0) out_sums[blockIdx.x] = sum;
 }
 
 // C, h and which parameters move, from the ordered sums: one entry per lane.
@@ -614,7 +580,7 @@ __global__ __launch_bounds__(kBaWave) void ba_border_system_kernel(const double*
   }
 }
 
-// B_a: one wave per camera over its list, the batches of ba_reduce_cameras_kernel, a lane's entries in its registers.
+// B_a: one wave per camera over its list, a lane's entries in its registers.
 __global__ __launch_bounds__(kBaWave) void ba_reduce_border_kernel(BaProblem d, BaLinear l, BaGroups gr, const int32_t* __restrict__ cam_offsets,
                                                                    const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
                                                                    const double* __restrict__ obs_xn, const double* __restrict__ T,
@@ -625,27 +591,18 @@ __global__ __launch_bounds__(kBaWave) void ba_reduce_border_kernel(BaProblem d, 
   BaBorderLane s;
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) s.jt[k] = s.yt[k] = 0.0;
-  const int first = cam_offsets[a], last = cam_offsets[a + 1];
-  if (first >= 0 && last >= first && last <= d.total) {     // otherwise the camera is skipped, nothing of it read
-    for (int base = first; base < last; base += kBaWave) {
-      ba_prepare(d, l, cam_obs, obs_point, a, base + lane, last, lane, batch);
-      __syncthreads();
-      const int m = last - base < kBaWave ? last - base : kBaWave;
-      for (int k = 0; k < m; ++k)
-        if (batch.o[k] >= 0) ba_border_update(l, gr, obs_xn, T, ga, batch.o[k], batch.j[k], lane, batch.y[k], s);
-      __syncthreads();
-    }
-  }
+  ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
+                 [&](int o, int j, int, int, const double* y) { ba_border_update(l, gr, obs_xn, T, ga, o, j, lane, y, s); });
   ba_border_finish(gr.n_groups, a, lane, s, out_B);
 }
 
-__global__ __launch_bounds__(kBaWave) void ba_step_points_intrinsics_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
-                                                                            const double* __restrict__ dc, const double* __restrict__ dtheta,
-                                                                            double* __restrict__ out_points, double* __restrict__ out_dx) {
+__global__ __launch_bounds__(kBaWave) void ba_step_points_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
+                                                                 const double* __restrict__ dc, const double* __restrict__ dtheta,
+                                                                 double* __restrict__ out_points, double* __restrict__ out_dx) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (j >= d.n_points) return;
   double dX[3];
-  ba_point_step_intrinsics(d, l, T, n_groups, dc, dtheta, (int)j, dX);
+  ba_point_step(d, l, T, n_groups, dc, dtheta, (int)j, dX);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     out_dx[3 * j + k] = dX[k];
@@ -653,12 +610,26 @@ __global__ __launch_bounds__(kBaWave) void ba_step_points_intrinsics_kernel(BaPr
   }
 }
 
-__global__ __launch_bounds__(kBaWave) void ba_step_cameras_intrinsics_kernel(const double* __restrict__ cams, int n_cams, BaGroups gr,
-                                                                             const double* __restrict__ dc, const double* __restrict__ dtheta,
-                                                                             double* __restrict__ out_cams, uint8_t* __restrict__ out_valid) {
+// out_valid may be absent (vc_ba_step: no intrinsics move, every candidate is valid).
+__global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(const double* __restrict__ cams, int n_cams, BaGroups gr,
+                                                                  const double* __restrict__ dc, const double* __restrict__ dtheta,
+                                                                  double* __restrict__ out_cams, uint8_t* __restrict__ out_valid) {
   const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (a >= n_cams) return;
-  out_valid[a] = ba_camera_step_intrinsics(cams + 16 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a) ? 1 : 0;
+  const bool valid = ba_camera_step(cams + 16 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a);
+  if (out_valid) out_valid[a] = valid ? 1 : 0;
+}
+
+// The two kernels of a step; vc_ba_step has no groups: then T, dtheta, cam_group and out_valid are absent and none is read.
+int ba_launch_step(const BaProblem& d, const BaLinear& l, const BaGroups& gr, const double* T, const double* dc, const double* dtheta,
+                   double* out_cams, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
+  if (d.n_points > 0)
+    hipLaunchKernelGGL(ba_step_points_kernel, dim3((unsigned)((d.n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       d, l, T, gr.n_groups, dc, dtheta, out_points, out_dx);
+  if (d.n_cams > 0)
+    hipLaunchKernelGGL(ba_step_cameras_kernel, dim3((unsigned)((d.n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       d.cams, d.n_cams, gr, dc, dtheta, out_cams, out_valid);
+  return vc::check_launch();
 }
 
 constexpr int ba_reduce_lds_bytes(int n_cams) { return 36 * n_cams * (int)sizeof(double); }
@@ -682,7 +653,7 @@ int vc_ba_linearize_points(const double* cams, int n_cams, const uint8_t* const_
   const int blocks = (n_points + kBaWave - 1) / kBaWave;
   hipLaunchKernelGGL(ba_linearize_points_kernel, dim3((unsigned)blocks), dim3(kBaWave), 0, (hipStream_t)stream, d, lambda, out_vinv,
                      out_gp, out_cost, out_count, out_obs_ok, out_obs_lin);
-  hipLaunchKernelGGL(ba_total_cost_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
   return vc::check_launch();
 }
 
@@ -713,15 +684,8 @@ int vc_ba_step(const double* cams, int n_cams, const double* points, int n_point
   if (n_cams > 0 && (!cams || !dc || !out_cams)) return VC_ERR_INVALID_ARG;
   if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx)) return VC_ERR_INVALID_ARG;
   if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0) {
-    const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
-    hipLaunchKernelGGL(ba_step_points_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       d, BaLinear{vinv, gp, obs_ok, obs_lin}, dc, out_points, out_dx);
-  }
-  if (n_cams > 0)
-    hipLaunchKernelGGL(ba_step_cameras_kernel, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       cams, n_cams, dc, out_cams);
-  return vc::check_launch();
+  return ba_launch_step(BaProblem{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total}, BaLinear{vinv, gp, obs_ok, obs_lin},
+                        BaGroups{nullptr, nullptr, 0}, nullptr, dc, nullptr, out_cams, out_points, out_dx, nullptr, stream);
 }
 
 int vc_ba_linearize_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
@@ -755,7 +719,7 @@ int vc_ba_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, cons
   if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_xn)) return VC_ERR_INVALID_ARG;
   if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
   const BaGroups gr{cam_group, intr_mask, n_groups};
-  hipLaunchKernelGGL(ba_border_sums_kernel, dim3((unsigned)ba_term_rows(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
                      out_sums);
   hipLaunchKernelGGL(ba_border_system_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h, out_free);
   if (n_cams > 0) {
@@ -778,15 +742,8 @@ int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_gro
   if (n_cams > 0 && (!cams || !cam_group || !dc || !out_cams || !out_valid)) return VC_ERR_INVALID_ARG;
   if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx || (n_groups > 0 && !T))) return VC_ERR_INVALID_ARG;
   if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0) {
-    const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
-    hipLaunchKernelGGL(ba_step_points_intrinsics_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                       (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, T, n_groups, dc, dtheta, out_points, out_dx);
-  }
-  if (n_cams > 0)
-    hipLaunchKernelGGL(ba_step_cameras_intrinsics_kernel, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                       (hipStream_t)stream, cams, n_cams, BaGroups{cam_group, intr_mask, n_groups}, dc, dtheta, out_cams, out_valid);
-  return vc::check_launch();
+  return ba_launch_step(BaProblem{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total}, BaLinear{vinv, gp, obs_ok, obs_lin},
+                        BaGroups{cam_group, intr_mask, n_groups}, T, dc, dtheta, out_cams, out_points, out_dx, out_valid, stream);
 }
 
 }  // extern "C"

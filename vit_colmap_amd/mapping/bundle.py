@@ -1,17 +1,18 @@
 """Bundle adjustment of the grown model: one global Levenberg-Marquardt over every pose and every point
-by the Schur complement of the points, on the three kernels of csrc/bundle.hip, whose header (include/vitcolmap_hip.h) states
+by the Schur complement of the points, on the kernels of csrc/bundle.hip, whose header (include/vitcolmap_hip.h) states
 the rule; then the rescale to a unit baseline and the filter of observations and points.  Specification:
 tests/util_bundle.py.  This build's own published rule; parity with COLMAP's bundle adjuster and with Ceres is unpinned.
 With `refine_focal_length` the adjustment also refines the focal length(s) of every camera (one group of intrinsics per
-camera_id, a border of the reduced system: mapping/bundle_intr.py, imported only then; specification:
-tests/util_bundle_intr.py).  Still missing on the way to a mapper: adjustment per round and local adjustment,
+camera_id, a border of the reduced system, which mapping/bundle_intr.py, imported only then, supplies to the one loop here;
+specification: tests/util_bundle_intr.py).  Still missing on the way to a mapper: adjustment per round and local adjustment,
 re-triangulation, merging of points, a robust loss, the principal point and distortion among the refined intrinsics.
 
 Where the work runs
   HIP     per iteration vc_ba_linearize_points (one point per lane: residuals, Jacobians, V^-1, the cost), vc_ba_reduce_cameras
           (one workgroup per camera: the reduced system S, g) and vc_ba_step (back-substitution, the trig-free pose update)
-  torch   the solve of S dc = -g in float64 on the device (cholesky_ex + cholesky_solve) and the loop's scalars; the accept /
-          reject decision is the only host read of an iteration: one number, the candidate's cost (NaN where S did not factor)
+  torch   the solve of S dc = -g (with a border: of the bordered system) in float64 on the device (cholesky_ex +
+          cholesky_solve) and the loop's scalars; the accept / reject decision is the only host read of an iteration: one
+          number, the candidate's cost (NaN where the system did not factor)
   host    Python / numpy: the model's arrays, the camera-major index, the gauge, the rescale, the filter
 """
 import copy
@@ -93,15 +94,16 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
         raise ValueError(f"bundle_adjust: {n_cams} cameras, the reduction kernel holds at most {_lib.VC_BA_MAX_CAMS} (VC_BA_MAX_CAMS)")
     if offsets.shape != (n_points + 1,) or obs_xy.shape != (total, 2) or const_mask.shape != (n_cams,):
         raise ValueError("bundle_adjust needs offsets (n_points + 1,), obs_cam (total,), obs_xy (total, 2), const_mask (n_cams,)")
+    border = None
     if cam_group is not None or intr_mask is not None:
         if cam_group is None or intr_mask is None:
             raise ValueError("bundle_adjust needs cam_group and intr_mask together")
-        from .bundle_intr import bundle_adjust_intrinsics
+        from .bundle_intr import Border
 
-        return bundle_adjust_intrinsics(cams, points, offsets, obs_cam, obs_xy, const_mask, cam_group, intr_mask, device, max_iterations)
+        border = Border(cams, cam_group, intr_mask)
     report = dict(iterations=0, accepted_steps=0, initial_cost=0.0, final_cost=0.0, final_lambda=BA_LAMBDA0, decisions=[])
     if n_cams == 0 or n_points == 0:
-        return cams.copy(), points.copy(), report
+        return cams.copy(), points.copy(), report if border is None else border.report(report, cams)
     lib = _lib.load()
     dev = torch.device(device)
 
@@ -117,6 +119,8 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     g = torch.zeros(6 * n_cams, dtype=torch.float64, device=dev)
     dx = torch.zeros((n_points, 3), dtype=torch.float64, device=dev)
     p, stream = _lib.ptr, _lib.stream_ptr()
+    if border is not None:
+        border.upload(on_device, d_offsets, d_obs_cam, (cam_offsets, cam_obs, obs_point))
 
     def linearize(b, lam):
         _lib.check(lib.vc_ba_linearize_points(p(b.cams), n_cams, p(d_mask), p(b.points), n_points, p(d_offsets), p(d_obs_cam), p(d_obs_xy),
@@ -131,18 +135,24 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
         _lib.check(lib.vc_ba_reduce_cameras(n_cams, p(d_mask), n_points, p(d_offsets), p(d_obs_cam), total, p(cam_offsets), p(cam_obs),
                                             p(obs_point), float(lam), p(cur.vinv), p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(S), p(g),
                                             stream), "vc_ba_reduce_cameras")
-        L, info = torch.linalg.cholesky_ex(S)
-        dc = torch.cholesky_solve(-g[:, None], L)[:, 0]
-        factored = (info == 0) & torch.isfinite(dc).all()
-        # a held parameter's step is exactly 0; a system that did not factor still takes a (finite, zero) step through the
-        # kernels, whose cost is then replaced by NaN: the decision stays one scalar read
-        dc = torch.where(free & factored, dc, torch.zeros_like(dc)).contiguous()
-        _lib.check(lib.vc_ba_step(p(cur.cams), n_cams, p(cur.points), n_points, p(d_offsets), p(d_obs_cam), total, p(cur.vinv), p(cur.gp),
-                                  p(cur.obs_ok), p(cur.obs_lin), p(dc), p(cand.cams), p(cand.points), p(dx), stream), "vc_ba_step")
+        # the system A x = -rhs and which of its unknowns move: the cameras', or with a border the cameras' and the intrinsics'
+        A, rhs, moves = (S, g, free) if border is None else border.system(cur, lam, S, g, free)
+        L, info = torch.linalg.cholesky_ex(A)
+        x = torch.cholesky_solve(-rhs[:, None], L)[:, 0]
+        factored = (info == 0) & torch.isfinite(x).all()
+        # a parameter that does not move steps by exactly 0; a system that did not factor still takes a (finite, zero) step
+        # through the kernels, whose cost is then replaced by NaN: the decision stays one scalar read
+        x = torch.where(moves & factored, x, torch.zeros_like(x)).contiguous()
+        if border is None:
+            _lib.check(lib.vc_ba_step(p(cur.cams), n_cams, p(cur.points), n_points, p(d_offsets), p(d_obs_cam), total, p(cur.vinv), p(cur.gp),
+                                      p(cur.obs_ok), p(cur.obs_lin), p(x), p(cand.cams), p(cand.points), p(dx), stream), "vc_ba_step")
+            usable = factored
+        else:
+            usable = factored & border.step(cur, cand, x, dx)
         lower = max(lam / 10, BA_LAMBDA_MIN)
         linearize(cand, lower)
         iterations += 1
-        c = float(torch.where(factored, cand.total_cost[0], torch.full_like(cand.total_cost[0], float("nan"))).item())
+        c = float(torch.where(usable, cand.total_cost[0], torch.full_like(cand.total_cost[0], float("nan"))).item())
         accepted = bool(np.isfinite(c) and c < cost)
         decisions.append(accepted)
         if accepted:
@@ -156,13 +166,10 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
                 break
             linearize(cur, lam)
             iterations += 1
+    out_cams = cur.cams.cpu().numpy()
     report = dict(iterations=iterations, accepted_steps=int(sum(decisions)), initial_cost=initial, final_cost=cost, final_lambda=lam,
                   decisions=decisions)
-    return cur.cams.cpu().numpy(), cur.points.cpu().numpy(), report
-
-
-def _gpu_bundle(cams, points, offsets, obs_cam, obs_xy, const_mask, device, cam_group=None, intr_mask=None, max_iterations=BA_MAX_ITERATIONS):
-    return bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device, max_iterations, cam_group=cam_group, intr_mask=intr_mask)
+    return out_cams, cur.points.cpu().numpy(), report if border is None else border.report(report, out_cams)
 
 
 def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
@@ -185,7 +192,7 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     loop under a higher cap: a model grown under a wrong focal starts far from a minimum), the model's cameras carry the refined values, the
     filter and `error` use them and the report gains `intrinsics` {camera_id: dict(before, after)}.  Raises ValueError above
     VC_BA_MAX_GROUPS cameras."""
-    bundle_fn = bundle_fn or _gpu_bundle
+    bundle_fn = bundle_fn or bundle_adjust
     if grown is None:
         grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn)
     _, _, K, _, _ = _read_database(database_path)
