@@ -396,6 +396,47 @@ int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_gro
                           vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bundle adjustment under a robust loss ("The loss"): iteratively reweighted Gauss-Newton.  This
+ * build's own published rule; parity with Ceres' loss functions is unpinned.  For a usable observation with the unweighted
+ * residual r = (ru, rv) let s = ru ru + rv rv and c = loss_scale (px); float64, single operations in the written order, sqrt the
+ * only library call:
+ *   VC_BA_LOSS_TRIVIAL   rho = s, w = 1
+ *   VC_BA_LOSS_HUBER     s <= c c: rho = s, w = 1; otherwise q = sqrt(s), rho = (2 c) q - c c, w = c / q
+ *   VC_BA_LOSS_SOFT_L1   q = sqrt(1 + s / (c c)), rho = 2 s / (1 + q), w = 1 / q   (= 2 c^2 (q - 1) without its cancellation)
+ * sw = sqrt(w).  The observation's rows of J_c and of J_p and r are each multiplied by sw (a held column of J_c stays exactly 0)
+ * before anything is formed from them; W, V, g_p, U, S, g, the border's T, q, hq, B, C, h and the steps are the arithmetic
+ * above on the scaled values, so the gradient (sw J)' (sw r) = rho' J' r is exact and the loss' second-order term is dropped
+ * (the system stays positive semidefinite).  cost_j = 0.5 sum rho in track order.  With w = 1 every product is exact: the
+ * trivial loss returns the bytes of the entry point without a loss.  A residual whose s overflows takes what this arithmetic
+ * gives (w = 0, a cost that is not finite: the loop rejects the candidate); Cauchy is not offered: its cost needs log.
+ *
+ * vc_ba_linearize_points_loss: vc_ba_linearize_points with loss, loss_scale and out_obs_w [total]: sw of a usable observation, 0
+ * of any other of a track (observations outside every track are not written).  out_obs_lin holds the scaled J_c, r and W, so
+ * vc_ba_reduce_cameras, vc_ba_step and vc_ba_step_intrinsics are called on its outputs as they are.
+ * vc_ba_linearize_intrinsics_loss, vc_ba_reduce_border_loss: the two entry points above with obs_w [total] as the points pass
+ * wrote it; the recomputed J_p and every column of J_theta (the constant 1 of cx, cy too) are multiplied by obs_w[o];
+ * out_obs_xn stays the unscaled (x, y).
+ * A loss outside 0-2, a loss_scale that is not finite or not positive, a null out_obs_w / obs_w that total needs:
+ * VC_ERR_INVALID_ARG without a launch; everything else as the entry points without a loss.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_BA_LOSS_TRIVIAL 0
+#define VC_BA_LOSS_HUBER 1
+#define VC_BA_LOSS_SOFT_L1 2
+int vc_ba_linearize_points_loss(const double* cams, int n_cams, const uint8_t* const_mask, const double* points, int n_points,
+                                const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda, int loss,
+                                double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
+                                uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream);
+int vc_ba_linearize_intrinsics_loss(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                                    const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                                    const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* obs_w,
+                                    double* out_obs_xn, double* out_T, double* out_terms, vc_stream_t stream);
+int vc_ba_reduce_border_loss(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
+                             const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
+                             double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
+                             const double* obs_w, const double* T, const double* terms, double* out_sums, double* out_B, double* out_C,
+                             double* out_h, uint8_t* out_free, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

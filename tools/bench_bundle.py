@@ -7,7 +7,10 @@ neighbouring cameras, 0.5 px noise, poses and points moved off the truth.  A ker
 after 3 warm-up launches, by device events; the loop's is wall clock around bundle_adjust, synchronised, the median of --loops
 runs.  --refine-focal: the same two problems with every focal 3 % off and one tied group of intrinsics refined (§4.2k, "The
 border"): also the three entry points of the border and the bordered solve, and the refined loop beside the plain loop of the
-same build, the two alternating.  Prints one JSON line.  Needs a GPU."""
+same build, the two alternating.  --loss huber|soft_l1 (--loss-scale PX, default 1): after those columns also the points pass
+under the loss (vc_ba_linearize_points_loss) and, with --refine-focal, the border's two passes with obs_w, on the same buffers;
+and the loop under the loss beside the plain loop, alternating (with --refine-focal the refined loop under the loss too).
+Prints one JSON line.  Needs a GPU."""
 import argparse
 import json
 import os
@@ -80,7 +83,7 @@ def device_ms(fn, iters):
     return float(np.median(times))
 
 
-def measure(problem, iters, loops, refine=False):
+def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0):
     cams, points, offsets, obs_cam, obs_xy, mask = problem
     if refine:
         cams = cams.copy()
@@ -90,7 +93,7 @@ def measure(problem, iters, loops, refine=False):
     dev = torch.device("cuda")
     d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (cams, mask, points, offsets, obs_cam, obs_xy)]
     x = [torch.from_numpy(a).to(dev) for a in bundle.camera_index(obs_cam, offsets, c)]
-    b = bundle._Buffers(torch, c, n, t, dev)
+    b = bundle._Buffers(torch, c, n, t, dev, with_loss=loss is not None)
     S = torch.zeros((6 * c, 6 * c), dtype=torch.float64, device=dev)
     g, dc = torch.zeros(6 * c, dtype=torch.float64, device=dev), torch.zeros(6 * c, dtype=torch.float64, device=dev)
     out_cams, out_points, dx = torch.zeros_like(d[0]), torch.zeros_like(d[2]), torch.zeros_like(d[2])
@@ -146,6 +149,27 @@ def measure(problem, iters, loops, refine=False):
 
         stages += [("linearize_intrinsics_ms", linearize_intrinsics), ("reduce_border_ms", reduce_border), ("solve_bordered_ms", solve_bordered),
                    ("step_intrinsics_ms", step_intrinsics)]
+    if loss is not None:                                              # after the columns without a loss, on the same buffers
+        kind = bundle.LOSSES[loss]
+
+        def linearize_loss():
+            _lib.check(lib.vc_ba_linearize_points_loss(p(d[0]), c, p(d[1]), p(d[2]), n, p(d[3]), p(d[4]), p(d[5]), t, lam, kind, loss_scale,
+                                                       p(b.vinv), p(b.gp), p(b.cost), p(b.count), p(b.obs_ok), p(b.obs_lin), p(b.obs_w),
+                                                       p(b.total_cost), stream), "vc_ba_linearize_points_loss")
+
+        stages.append(("linearize_loss_ms", linearize_loss))
+        if refine:
+            def linearize_intrinsics_loss():
+                _lib.check(lib.vc_ba_linearize_intrinsics_loss(p(d[0]), c, p(dg), 1, p(di), p(d[2]), n, p(d[3]), p(d[4]), t, p(b.vinv), p(b.gp),
+                                                               p(b.obs_ok), p(b.obs_lin), p(b.obs_w), p(xn), p(T), p(terms), stream),
+                           "vc_ba_linearize_intrinsics_loss")
+
+            def reduce_border_loss():
+                _lib.check(lib.vc_ba_reduce_border_loss(c, p(dg), 1, p(di), n, p(d[3]), p(d[4]), t, p(x[0]), p(x[1]), p(x[2]), lam, p(b.vinv),
+                                                        p(b.obs_ok), p(b.obs_lin), p(xn), p(b.obs_w), p(T), p(terms), p(sums), p(B), p(C), p(h),
+                                                        p(free), stream), "vc_ba_reduce_border_loss")
+
+            stages += [("linearize_intrinsics_loss_ms", linearize_intrinsics_loss), ("reduce_border_loss_ms", reduce_border_loss)]
     for name, fn in stages:
         out[name] = round(device_ms(fn, iters), 4)
 
@@ -156,18 +180,31 @@ def measure(problem, iters, loops, refine=False):
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0), report, cams_out
 
-    walls, refined_walls = [], []
-    for _ in range(loops + 1):                                        # the first run warms up; plain and refined alternate
+    walls, refined_walls, loss_walls, refined_loss_walls = [], [], [], []
+    loss_args = {} if loss is None else dict(loss=loss, loss_scale=loss_scale)
+    for _ in range(loops + 1):                                        # the first run warms up; the loops alternate
         wall, report, _ = loop()
         walls.append(wall)
         if refine:
             wall, refined, cams_out = loop(**groups)
             refined_walls.append(wall)
+        if loss is not None:
+            wall, robust, _ = loop(**loss_args)
+            loss_walls.append(wall)
+            if refine:
+                wall, refined_robust, robust_cams = loop(**groups, **loss_args)
+                refined_loss_walls.append(wall)
     out.update(loop_ms=round(float(np.median(walls[1:])), 3), iterations=report["iterations"], accepted_steps=report["accepted_steps"],
                initial_cost=report["initial_cost"], final_cost=report["final_cost"])
     if refine:
         out.update(refined_loop_ms=round(float(np.median(refined_walls[1:])), 3), refined_iterations=refined["iterations"],
                    refined_accepted_steps=refined["accepted_steps"], refined_final_cost=refined["final_cost"], refined_focal=float(cams_out[0, 12]))
+    if loss is not None:
+        out.update(loss_loop_ms=round(float(np.median(loss_walls[1:])), 3), loss_iterations=robust["iterations"],
+                   loss_accepted_steps=robust["accepted_steps"], loss_initial_cost=robust["initial_cost"], loss_final_cost=robust["final_cost"])
+        if refine:
+            out.update(refined_loss_loop_ms=round(float(np.median(refined_loss_walls[1:])), 3), refined_loss_iterations=refined_robust["iterations"],
+                       refined_loss_final_cost=refined_robust["final_cost"], refined_loss_focal=float(robust_cams[0, 12]))
     return out
 
 
@@ -179,10 +216,14 @@ def main():
     ap.add_argument("--loops", type=int, default=5)
     ap.add_argument("--refine-focal", dest="refine_focal", action="store_true",
                     help="every focal 3 %% off; also time the border's entry points and the loop that refines one tied focal")
+    ap.add_argument("--loss", choices=[k for k in bundle.LOSSES if k != "trivial"], default=None,
+                    help="also time the entry points that take a loss and the loop under it (DESIGN.md §4.2k, \"The loss\")")
+    ap.add_argument("--loss-scale", dest="loss_scale", type=float, default=1.0, metavar="PX")
     args = ap.parse_args()
-    print(json.dumps(dict(tool="bench_bundle", iters=args.iters, loops=args.loops, refine_focal=args.refine_focal,
-                          windowed=measure(windowed_problem(), args.iters, args.loops, args.refine_focal),
-                          arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops, args.refine_focal))))
+    extra = (args.refine_focal, args.loss, args.loss_scale)
+    print(json.dumps(dict(tool="bench_bundle", iters=args.iters, loops=args.loops, refine_focal=args.refine_focal, loss=args.loss,
+                          loss_scale=args.loss_scale, windowed=measure(windowed_problem(), args.iters, args.loops, *extra),
+                          arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops, *extra))))
 
 
 if __name__ == "__main__":

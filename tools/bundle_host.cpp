@@ -18,6 +18,10 @@
 // (total, 2), T (n_points, G, 12), terms (24 G + 16 G^2, n_points), sums (24 G + 16 G^2), B (6 n_cams, 4 G), C (4 G, 4 G), h (4 G),
 // out_cams, out_points, dx (the step under dc and dtheta); uint8 free (4 G), valid (n_cams).
 // Offsets of any kind are passed on as they are: the routines check them.
+// A loss ("The loss" in DESIGN.md §4.2k) is an optional extension: where problem.bin goes on after dtheta with int32 loss, float64
+// loss_scale, every routine that has a loss variant runs it (vc_ba_linearize_points_loss, vc_ba_linearize_intrinsics_loss,
+// vc_ba_reduce_border_loss) and result.bin ends with one more array, float64 obs_w (total).  A loss that the entry point refuses
+// (ba_loss_valid) is refused here: one line on stderr, exit status 3, no result.  Without the extension nothing changes.
 #include "../vit_colmap_amd/csrc/bundle.hip"
 #include "host_io.h"
 
@@ -75,10 +79,20 @@ int main(int argc, char** argv) {
   const bool ok = read_all(in, offsets) && read_all(in, obs_cam) && read_all(in, cam_offsets) && read_all(in, cam_obs) &&
                   read_all(in, obs_point) && read_all(in, mask32) && read_all(in, cam_group) && read_all(in, intr32) && read_all(in, cams) &&
                   read_all(in, points) && read_all(in, obs_xy) && read_all(in, dc) && read_all(in, dtheta);
+  // the optional loss: nothing after dtheta, or both of its numbers
+  int32_t loss_kind = 0;
+  BaLoss loss{VC_BA_LOSS_TRIVIAL, 1.0};
+  const bool with_loss = ok && std::fread(&loss_kind, sizeof(int32_t), 1, in) == 1;
+  const bool loss_read = !with_loss || std::fread(&loss.scale, sizeof(double), 1, in) == 1;
+  loss.kind = loss_kind;
   std::fclose(in);
-  if (!ok) {
+  if (!ok || !loss_read) {
     std::fprintf(stderr, "%s: shorter than its header says\n", argv[1]);
     return 2;
+  }
+  if (with_loss && !ba_loss_valid(loss)) {
+    std::fprintf(stderr, "%s: loss %d with scale %g is refused\n", argv[1], loss.kind, loss.scale);
+    return 3;
   }
   std::vector<uint8_t> const_mask(n_cams), intr_mask(G);
   for (int a = 0; a < n_cams; ++a) const_mask[a] = (uint8_t)mask32[a];
@@ -89,10 +103,12 @@ int main(int argc, char** argv) {
   std::vector<double> obs_lin((size_t)kBaLin * total);
   std::vector<int32_t> count(n_points);
   std::vector<uint8_t> obs_ok(total);
+  std::vector<double> obs_w(with_loss ? total : 0);
   const BaProblem d{cams.data(), const_mask.data(), points.data(), offsets.data(), obs_cam.data(), obs_xy.data(), n_cams, n_points, total};
   for (int j = 0; j < n_points; ++j) {
     double v[6], g[3];
-    count[j] = ba_linearize_point(d, j, lambda, v, g, cost[j], obs_ok.data(), obs_lin.data());
+    count[j] = with_loss ? ba_linearize_point<true>(d, loss, j, lambda, v, g, cost[j], obs_ok.data(), obs_lin.data(), obs_w.data())
+                         : ba_linearize_point<false>(d, loss, j, lambda, v, g, cost[j], obs_ok.data(), obs_lin.data(), nullptr);
     for (int k = 0; k < 6; ++k) vinv[6 * (size_t)j + k] = v[k];
     for (int k = 0; k < 3; ++k) gp[3 * (size_t)j + k] = g[k];
     total_cost[0] += cost[j];
@@ -126,7 +142,10 @@ int main(int argc, char** argv) {
     const BaGroups gr{cam_group.data(), intr_mask.data(), G};
     const int rows = ba_term_rows(G), m = 4 * G;
     std::vector<double> obs_xn(2 * (size_t)total), T((size_t)n_points * G * kBaT), terms((size_t)rows * n_points), sums(rows);
-    for (int j = 0; j < n_points; ++j) ba_linearize_point_intrinsics(d, l, gr, j, obs_xn.data(), T.data(), terms.data());
+    for (int j = 0; j < n_points; ++j) {
+      if (with_loss) ba_linearize_point_intrinsics<true>(d, l, gr, obs_w.data(), j, obs_xn.data(), T.data(), terms.data());
+      else ba_linearize_point_intrinsics<false>(d, l, gr, nullptr, j, obs_xn.data(), T.data(), terms.data());
+    }
     for (int r = 0; r < rows; ++r) {
       double sum = 0.0;
       for (int j = 0; j < n_points; ++j) sum += terms[(size_t)r * n_points + j];
@@ -144,7 +163,8 @@ int main(int argc, char** argv) {
         for (int k = 0; k < kBaBorderSlots; ++k) lanes[lane].jt[k] = lanes[lane].yt[k] = 0.0;
       const int ga = ba_group_of(gr, a);
       camera_walk(d, l, cam_offsets.data(), cam_obs.data(), obs_point.data(), a, [&](int lane, int o, int j, int, int, const double* y) {
-        ba_border_update(l, gr, obs_xn.data(), T.data(), ga, o, j, lane, y, lanes[lane]);
+        if (with_loss) ba_border_update<true>(l, gr, obs_xn.data(), obs_w.data(), T.data(), ga, o, j, lane, y, lanes[lane]);
+        else ba_border_update<false>(l, gr, obs_xn.data(), nullptr, T.data(), ga, o, j, lane, y, lanes[lane]);
       });
       for (int lane = 0; lane < kBaWave; ++lane) ba_border_finish(G, a, lane, lanes[lane], B.data());
     }
@@ -155,6 +175,7 @@ int main(int argc, char** argv) {
     write_all(out, h), write_all(out, step.cams), write_all(out, step.points), write_all(out, step.dx), write_all(out, free_);
     write_all(out, step.valid);
   }
+  write_all(out, obs_w);
   std::fclose(out);
   std::printf("%d cameras, %d points, %d observations, %d groups, cost %.17g\n", n_cams, n_points, total, G, total_cost[0]);
   return 0;

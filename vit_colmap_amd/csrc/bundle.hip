@@ -3,8 +3,11 @@
 // the points.  vit_colmap_amd/mapping/bundle.py repeats vc_ba_linearize_points, vc_ba_reduce_cameras and vc_ba_step; with groups
 // (mapping/bundle_intr.py) vc_ba_linearize_intrinsics and vc_ba_reduce_border follow the reduction and vc_ba_step_intrinsics takes
 // the step: the groups' unknowns border the reduced system, [[S, B], [B', C]] (dc, dtheta) = -(g, h).  The system is solved by
-// the caller.  Specification: tests/util_bundle.py, tests/util_bundle_intr.py.  This build's own published rule; parity with
-// COLMAP / Ceres is unpinned.
+// the caller.  Under a loss (Huber, soft L1: vc_ba_linearize_points_loss, vc_ba_linearize_intrinsics_loss,
+// vc_ba_reduce_border_loss) every observation's J_c, J_p, r and J_theta are multiplied by the square root of its weight before
+// anything is formed from them, and the other three entry points run unchanged on the result; the routines take the loss as a
+// template argument, and without it return the bytes they returned.  Specification: tests/util_bundle.py, tests/util_bundle_intr.py,
+// tests/util_bundle_loss.py.  This build's own published rule; parity with COLMAP / Ceres is unpinned.
 //
 // float64 in single operations in the written order (-ffp-contract=off), the only library call is sqrt, no atomics.
 //   points pass  one point per lane, one wave per workgroup, no LDS.  ba_linearize_points_kernel: every observation of the point's
@@ -86,9 +89,38 @@ __host__ __device__ __forceinline__ void ba_project(const double* c, const doubl
   }
 }
 
-// Observation o of point X: usable -> lin[32] (zeros otherwise) and J_p (2x3).
-__host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, int o, const double (&X)[3], double* __restrict__ lin,
-                                                    double (&ju)[3], double (&jv)[3]) {
+// The loss of an observation ("The loss" in DESIGN.md §4.2k): kind VC_BA_LOSS_*, scale c in px.
+struct BaLoss {
+  int kind;
+  double scale;
+};
+
+// A loss the entry points accept: a kind of the header's, a finite positive scale (false for NaN).
+__host__ __device__ __forceinline__ bool ba_loss_valid(const BaLoss& loss) {
+  return loss.kind >= VC_BA_LOSS_TRIVIAL && loss.kind <= VC_BA_LOSS_SOFT_L1 && loss.scale > 0.0 && loss.scale < INFINITY;
+}
+
+// s = |r|^2 of the unweighted residual -> rho(s) and the weight w = rho'(s).
+__host__ __device__ __forceinline__ void ba_loss(const BaLoss& loss, double s, double& rho, double& w) {
+  const double c = loss.scale;
+  rho = s, w = 1.0;
+  if (loss.kind == VC_BA_LOSS_HUBER) {
+    if (!(s <= c * c)) {
+      const double q = sqrt(s);
+      rho = (2.0 * c) * q - c * c, w = c / q;
+    }
+  } else if (loss.kind == VC_BA_LOSS_SOFT_L1) {
+    const double q = sqrt(1.0 + s / (c * c));
+    rho = 2.0 * s / (1.0 + q), w = 1.0 / q;
+  }
+}
+
+// Observation o of point X: usable -> lin[32] (zeros otherwise) and J_p (2x3).  With a loss the rows of J_c and J_p and r are
+// multiplied by sw = sqrt(w) before anything is formed from them, and rho is the loss of the unweighted residual, the
+// observation's term of the cost.
+template <bool kLoss>
+__host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const BaLoss& loss, int o, const double (&X)[3],
+                                                    double* __restrict__ lin, double (&ju)[3], double (&jv)[3], double& rho, double& sw) {
   const int slot = d.obs_cam[o];
   bool ok = slot >= 0 && slot < d.n_cams;
   const double* c = d.cams + (long long)(ok ? slot : 0) * 16;
@@ -106,14 +138,25 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, int o, c
   const double z = Xc[2];
   ok = ok && z > 0.0;                                        // false for NaN
   const double fx = row[12], fy = row[13], cx = row[14], cy = row[15];
-  const double ru = fx * Xc[0] / z + cx - u, rv = fy * Xc[1] / z + cy - v;
+  double ru = fx * Xc[0] / z + cx - u, rv = fy * Xc[1] / z + cy - v;
   const double au = fu * xu, av = fv * xv;
   // J_c = J_pi [ -[R X]x | I ]: the pose is perturbed on the left, Xc(w, dt) = Rot(w) (R X) + t + dt
   double cu[6] = {-(au * Y[1]), fu * Y[2] + au * Y[0], -(fu * Y[1]), fu, 0.0, -au};
   double cv[6] = {-(fv * Y[2] + av * Y[1]), av * Y[0], fv * Y[0], 0.0, fv, -av};
+  rho = 0.0, sw = 1.0;                                       // without a loss the caller forms |r|^2 itself, as it always did
+  if (kLoss) {
+    double w;
+    ba_loss(loss, ru * ru + rv * rv, rho, w);
+    sw = sqrt(w);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ju[k] = sw * ju[k], jv[k] = sw * jv[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) cu[i] = sw * cu[i], cv[i] = sw * cv[i];
+    ru = sw * ru, rv = sw * rv;
+  }
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    const bool off = !ok || ((held >> i) & 1u);
+    const bool off = !ok || ((held >> i) & 1u);          // after the weight: a held column and an unusable observation are exactly 0
     cu[i] = off ? 0.0 : cu[i];
     cv[i] = off ? 0.0 : cv[i];
     lin[i] = cu[i], lin[6 + i] = cv[i];
@@ -127,9 +170,11 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, int o, c
 }
 
 // One point: its track linearised -> V^-1 (damped, 0 where the point is constant), g_p, cost, the usable count; per
-// observation of the track obs_ok and obs_lin.
-__host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, int j, double lambda, double (&vinv)[6], double (&gp)[3],
-                                                           double& cost, uint8_t* __restrict__ obs_ok, double* __restrict__ obs_lin) {
+// observation of the track obs_ok and obs_lin and, with a loss, obs_w: sw of a usable observation, 0 of any other.
+template <bool kLoss>
+__host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, const BaLoss& loss, int j, double lambda, double (&vinv)[6],
+                                                           double (&gp)[3], double& cost, uint8_t* __restrict__ obs_ok,
+                                                           double* __restrict__ obs_lin, double* __restrict__ obs_w) {
 #pragma unroll
   for (int k = 0; k < 6; ++k) vinv[k] = 0.0;
   gp[0] = gp[1] = gp[2] = 0.0;
@@ -140,15 +185,16 @@ __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, i
   double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0, sq = 0.0;
   for (int o = lo; o < hi; ++o) {
     double* lin = obs_lin + (long long)o * kBaLin;
-    double ju[3], jv[3];
-    const bool ok = ba_observe(d, o, X, lin, ju, jv);
+    double ju[3], jv[3], rho, sw;
+    const bool ok = ba_observe<kLoss>(d, loss, o, X, lin, ju, jv, rho, sw);
     obs_ok[o] = ok ? 1 : 0;
+    if (kLoss) obs_w[o] = ok ? sw : 0.0;
     if (!ok) continue;
     const double ru = lin[kBaLinR], rv = lin[kBaLinR + 1];
     A00 += ju[0] * ju[0] + jv[0] * jv[0], A01 += ju[0] * ju[1] + jv[0] * jv[1], A02 += ju[0] * ju[2] + jv[0] * jv[2];
     A11 += ju[1] * ju[1] + jv[1] * jv[1], A12 += ju[1] * ju[2] + jv[1] * jv[2], A22 += ju[2] * ju[2] + jv[2] * jv[2];
     gp[0] += ju[0] * ru + jv[0] * rv, gp[1] += ju[1] * ru + jv[1] * rv, gp[2] += ju[2] * ru + jv[2] * rv;
-    sq += ru * ru + rv * rv;
+    sq += kLoss ? rho : ru * ru + rv * rv;
     ++count;
   }
   cost = 0.5 * sq;
@@ -341,9 +387,13 @@ __host__ __device__ __forceinline__ void ba_observe_point(const double* __restri
 }
 
 // One point: obs_xn of its track; per group (outside) over the track (inside) T, q, hq; then the point's products with V^-1.
-// A point whose offsets delimit nothing has T and its terms 0 and nothing of its track read or written.
-__host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaProblem& d, const BaLinear& l, const BaGroups& gr, int j,
-                                                                       double* __restrict__ obs_xn, double* T, double* __restrict__ terms) {
+// A point whose offsets delimit nothing has T and its terms 0 and nothing of its track read or written.  With a loss J_p and
+// J_theta (its constant columns too) are multiplied by obs_w[o], as the points pass multiplied what it left in obs_lin; obs_xn
+// stays the unscaled (x, y).
+template <bool kLoss>
+__host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaProblem& d, const BaLinear& l, const BaGroups& gr,
+                                                                       const double* __restrict__ obs_w, int j, double* __restrict__ obs_xn,
+                                                                       double* T, double* __restrict__ terms) {
   const int G = gr.n_groups;
   const long long n = d.n_points;
   int lo, hi;
@@ -373,6 +423,13 @@ __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaP
       ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
 #pragma unroll
       for (int i = 0; i < 4; ++i) ba_jtheta(mask, x, y, i, tu[i], tv[i]);
+      if (kLoss) {
+        const double sw = obs_w[o];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ju[k] = sw * ju[k], jv[k] = sw * jv[k];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tu[i] = sw * tu[i], tv[i] = sw * tv[i];
+      }
       const double ru = l.obs_lin[(long long)o * kBaLin + kBaLinR], rv = l.obs_lin[(long long)o * kBaLin + kBaLinR + 1];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -443,10 +500,13 @@ struct BaBorderLane {
 };
 
 // One lane's additions for the usable observation o of camera a (its group ga or -1, its point j, y as ba_prepare left it).
+// With a loss the column of J_theta is multiplied by obs_w[o]; obs_lin and T carry the weight already.
+template <bool kLoss>
 __host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, const BaGroups& gr, const double* __restrict__ obs_xn,
-                                                          const double* __restrict__ T, int ga, int o, int j, int lane, const double* y,
-                                                          BaBorderLane& s) {
+                                                          const double* __restrict__ obs_w, const double* __restrict__ T, int ga, int o,
+                                                          int j, int lane, const double* y, BaBorderLane& s) {
   const int G = gr.n_groups;
+  const double sw = kLoss ? obs_w[o] : 1.0;
   const double* lin = l.obs_lin + (long long)o * kBaLin;
   const unsigned mask = ga >= 0 ? gr.intr_mask[ga] : 0u;
   const double x = obs_xn[2 * (long long)o], yn = obs_xn[2 * (long long)o + 1];
@@ -458,6 +518,7 @@ __host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, con
     if (g == ga) {
       double tu, tv;
       ba_jtheta(mask, x, yn, i, tu, tv);
+      if (kLoss) tu = sw * tu, tv = sw * tv;
       s.jt[k] += lin[r] * tu + lin[6 + r] * tv;
     }
     const double* t = T + ((long long)j * G + g) * kBaT + 3 * i;
@@ -518,14 +579,18 @@ __host__ __device__ __forceinline__ bool ba_camera_step(const double* __restrict
   return ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0;
 }
 
+// kLoss = false: loss and out_obs_w are absent and not read (vc_ba_linearize_points).  What a loss adds comes last in the three
+// kernels' arguments, so that without it the others sit where they sat.
+template <bool kLoss>
 __global__ __launch_bounds__(kBaWave) void ba_linearize_points_kernel(BaProblem d, double lambda, double* __restrict__ out_vinv,
                                                                       double* __restrict__ out_gp, double* __restrict__ out_cost,
                                                                       int32_t* __restrict__ out_count, uint8_t* __restrict__ out_obs_ok,
-                                                                      double* __restrict__ out_obs_lin) {
+                                                                      double* __restrict__ out_obs_lin, BaLoss loss,
+                                                                      double* __restrict__ out_obs_w) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (j >= d.n_points) return;
   double vinv[6], gp[3], cost;
-  const int count = ba_linearize_point(d, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin);
+  const int count = ba_linearize_point<kLoss>(d, loss, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin, out_obs_w);
 #pragma unroll
   for (int k = 0; k < 6; ++k) out_vinv[6 * j + k] = vinv[k];
 #pragma unroll
@@ -562,10 +627,12 @@ __global__ __launch_bounds__(kBaWave) void ba_reduce_cameras_kernel(BaProblem d,
   ba_lane_finish(d.n_cams, d.const_mask[a], lambda, a, lane, acc, s, out_S, out_g);
 }
 
+template <bool kLoss>
 __global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_kernel(BaProblem d, BaLinear l, BaGroups gr, double* __restrict__ out_obs_xn,
-                                                                          double* out_T, double* __restrict__ out_terms) {
+                                                                          double* out_T, double* __restrict__ out_terms,
+                                                                          const double* __restrict__ obs_w) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (j < d.n_points) ba_linearize_point_intrinsics(d, l, gr, (int)j, out_obs_xn, out_T, out_terms);
+  if (j < d.n_points) ba_linearize_point_intrinsics<kLoss>(d, l, gr, obs_w, (int)j, out_obs_xn, out_T, out_terms);
 }
 
 // C, h and which parameters move, from the ordered sums: one entry per lane.
@@ -581,10 +648,11 @@ __global__ __launch_bounds__(kBaWave) void ba_border_system_kernel(const double*
 }
 
 // B_a: one wave per camera over its list, a lane's entries in its registers.
+template <bool kLoss>
 __global__ __launch_bounds__(kBaWave) void ba_reduce_border_kernel(BaProblem d, BaLinear l, BaGroups gr, const int32_t* __restrict__ cam_offsets,
                                                                    const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
                                                                    const double* __restrict__ obs_xn, const double* __restrict__ T,
-                                                                   double* __restrict__ out_B) {
+                                                                   double* __restrict__ out_B, const double* __restrict__ obs_w) {
   __shared__ BaBatch batch;
   const int a = blockIdx.x, lane = threadIdx.x;
   const int ga = ba_group_of(gr, a);
@@ -592,7 +660,7 @@ __global__ __launch_bounds__(kBaWave) void ba_reduce_border_kernel(BaProblem d, 
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) s.jt[k] = s.yt[k] = 0.0;
   ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
-                 [&](int o, int j, int, int, const double* y) { ba_border_update(l, gr, obs_xn, T, ga, o, j, lane, y, s); });
+                 [&](int o, int j, int, int, const double* y) { ba_border_update<kLoss>(l, gr, obs_xn, obs_w, T, ga, o, j, lane, y, s); });
   ba_border_finish(gr.n_groups, a, lane, s, out_B);
 }
 
@@ -632,6 +700,72 @@ int ba_launch_step(const BaProblem& d, const BaLinear& l, const BaGroups& gr, co
   return vc::check_launch();
 }
 
+// The three entry points that exist with and without a loss: the checks and the launches of both, once.  kLoss = false: loss,
+// out_obs_w and obs_w are absent and none is read.
+template <bool kLoss>
+int ba_launch_linearize_points(const double* cams, int n_cams, const uint8_t* const_mask, const double* points, int n_points,
+                               const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda, BaLoss loss,
+                               double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count, uint8_t* out_obs_ok,
+                               double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
+  if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (kLoss && !ba_loss_valid(loss)) return VC_ERR_INVALID_ARG;
+  if (n_points == 0) return VC_OK;
+  if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !const_mask)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin || (kLoss && !out_obs_w))) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
+  const int blocks = (n_points + kBaWave - 1) / kBaWave;
+  hipLaunchKernelGGL(ba_linearize_points_kernel<kLoss>, dim3((unsigned)blocks), dim3(kBaWave), 0, (hipStream_t)stream, d, lambda, out_vinv,
+                     out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, loss, out_obs_w);
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
+  return vc::check_launch();
+}
+
+template <bool kLoss>
+int ba_launch_linearize_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                                   const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                                   const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* obs_w,
+                                   double* out_obs_xn, double* out_T, double* out_terms, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_points == 0 || n_groups == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_group)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !out_obs_xn || (kLoss && !obs_w))) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_linearize_intrinsics_kernel<kLoss>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, out_obs_xn, out_T,
+                     out_terms, obs_w);
+  return vc::check_launch();
+}
+
+template <bool kLoss>
+int ba_launch_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
+                            const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
+                            double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
+                            const double* obs_w, const double* T, const double* terms, double* out_sums, double* out_B, double* out_C,
+                            double* out_h, uint8_t* out_free, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_groups == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_xn || (kLoss && !obs_w))) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaGroups gr{cam_group, intr_mask, n_groups};
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
+                     out_sums);
+  hipLaunchKernelGGL(ba_border_system_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h, out_free);
+  if (n_cams > 0) {
+    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
+    hipLaunchKernelGGL(ba_reduce_border_kernel<kLoss>, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
+                       BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_xn, T, out_B, obs_w);
+  }
+  return vc::check_launch();
+}
+
 constexpr int ba_reduce_lds_bytes(int n_cams) { return 36 * n_cams * (int)sizeof(double); }
 static_assert(ba_reduce_lds_bytes(VC_BA_MAX_CAMS) + (int)sizeof(BaBatch) <= 160 * 1024, "the row block of VC_BA_MAX_CAMS cameras must fit the CU's LDS");
 
@@ -643,18 +777,17 @@ int vc_ba_linearize_points(const double* cams, int n_cams, const uint8_t* const_
                            const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
                            double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count, uint8_t* out_obs_ok,
                            double* out_obs_lin, double* out_total_cost, vc_stream_t stream) {
-  if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_points == 0) return VC_OK;
-  if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !const_mask)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin)) return VC_ERR_INVALID_ARG;
-  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
-  const int blocks = (n_points + kBaWave - 1) / kBaWave;
-  hipLaunchKernelGGL(ba_linearize_points_kernel, dim3((unsigned)blocks), dim3(kBaWave), 0, (hipStream_t)stream, d, lambda, out_vinv,
-                     out_gp, out_cost, out_count, out_obs_ok, out_obs_lin);
-  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
-  return vc::check_launch();
+  return ba_launch_linearize_points<false>(cams, n_cams, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda, BaLoss{0, 1.0},
+                                           out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, nullptr, out_total_cost, stream);
+}
+
+int vc_ba_linearize_points_loss(const double* cams, int n_cams, const uint8_t* const_mask, const double* points, int n_points,
+                                const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda, int loss,
+                                double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
+                                uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
+  return ba_launch_linearize_points<true>(cams, n_cams, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda,
+                                          BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, out_obs_w,
+                                          out_total_cost, stream);
 }
 
 int vc_ba_reduce_cameras(int n_cams, const uint8_t* const_mask, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
@@ -692,17 +825,16 @@ int vc_ba_linearize_intrinsics(const double* cams, int n_cams, const int32_t* ca
                                const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
                                const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_obs_xn,
                                double* out_T, double* out_terms, vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_points == 0 || n_groups == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS) return VC_ERR_UNSUPPORTED;
-  if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_group)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !out_obs_xn)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
-  hipLaunchKernelGGL(ba_linearize_intrinsics_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, out_obs_xn, out_T,
-                     out_terms);
-  return vc::check_launch();
+  return ba_launch_linearize_intrinsics<false>(cams, n_cams, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
+                                               obs_ok, obs_lin, nullptr, out_obs_xn, out_T, out_terms, stream);
+}
+
+int vc_ba_linearize_intrinsics_loss(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                                    const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                                    const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* obs_w,
+                                    double* out_obs_xn, double* out_T, double* out_terms, vc_stream_t stream) {
+  return ba_launch_linearize_intrinsics<true>(cams, n_cams, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
+                                              obs_ok, obs_lin, obs_w, out_obs_xn, out_T, out_terms, stream);
 }
 
 int vc_ba_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
@@ -710,24 +842,17 @@ int vc_ba_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, cons
                         double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
                         const double* T, const double* terms, double* out_sums, double* out_B, double* out_C, double* out_h,
                         uint8_t* out_free, vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_groups == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
-  if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_xn)) return VC_ERR_INVALID_ARG;
-  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
-  const BaGroups gr{cam_group, intr_mask, n_groups};
-  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
-                     out_sums);
-  hipLaunchKernelGGL(ba_border_system_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h, out_free);
-  if (n_cams > 0) {
-    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
-    hipLaunchKernelGGL(ba_reduce_border_kernel, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
-                       BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_xn, T, out_B);
-  }
-  return vc::check_launch();
+  return ba_launch_reduce_border<false>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs, obs_point,
+                                        lambda, vinv, obs_ok, obs_lin, obs_xn, nullptr, T, terms, out_sums, out_B, out_C, out_h, out_free, stream);
+}
+
+int vc_ba_reduce_border_loss(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
+                             const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
+                             double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
+                             const double* obs_w, const double* T, const double* terms, double* out_sums, double* out_B, double* out_C,
+                             double* out_h, uint8_t* out_free, vc_stream_t stream) {
+  return ba_launch_reduce_border<true>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs, obs_point,
+                                       lambda, vinv, obs_ok, obs_lin, obs_xn, obs_w, T, terms, out_sums, out_B, out_C, out_h, out_free, stream);
 }
 
 int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,

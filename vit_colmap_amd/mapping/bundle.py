@@ -4,8 +4,11 @@ the rule; then the rescale to a unit baseline and the filter of observations and
 tests/util_bundle.py.  This build's own published rule; parity with COLMAP's bundle adjuster and with Ceres is unpinned.
 With `refine_focal_length` the adjustment also refines the focal length(s) of every camera (one group of intrinsics per
 camera_id, a border of the reduced system, which mapping/bundle_intr.py, imported only then, supplies to the one loop here;
-specification: tests/util_bundle_intr.py).  Still missing on the way to a mapper: adjustment per round and local adjustment,
-re-triangulation, merging of points, a robust loss, the principal point and distortion among the refined intrinsics.
+specification: tests/util_bundle_intr.py).  With `loss` "huber" or "soft_l1" the adjustment is iteratively reweighted
+Gauss-Newton under that loss ("The loss" in §4.2k; specification: tests/util_bundle_loss.py): the same loop on
+vc_ba_linearize_points_loss, whose outputs the other kernels take as they are.  Still missing on the way to a mapper: adjustment
+per round and local adjustment, re-triangulation, merging of points, the principal point and distortion among the refined
+intrinsics.
 
 Where the work runs
   HIP     per iteration vc_ba_linearize_points (one point per lane: residuals, Jacobians, V^-1, the cost), vc_ba_reduce_cameras
@@ -34,6 +37,7 @@ BA_LAMBDA_MIN, BA_LAMBDA_MAX = 1e-12, 1e12
 BA_MAX_ITERATIONS = 25               # linearisations
 BA_REL_DECREASE = 1e-8
 HELD_ALL = 63                        # bits 0-2: the rotation, bits 3-5: the translation
+LOSSES = {"trivial": 0, "huber": 1, "soft_l1": 2}      # VC_BA_LOSS_* (include/vitcolmap_hip.h)
 MIN_TRI_ANGLE_TAN2 = float(np.tan(FILTER_MIN_TRI_ANGLE) ** 2)
 
 
@@ -59,9 +63,10 @@ def camera_index(obs_cam, offsets, n_cams):
 
 
 class _Buffers:
-    """The outputs of one vc_ba_linearize_points call; two of them alternate between the current parameters and the candidate."""
+    """The outputs of one vc_ba_linearize_points call (with a loss: of vc_ba_linearize_points_loss, obs_w among them); two of
+    them alternate between the current parameters and the candidate."""
 
-    def __init__(self, torch, n_cams, n_points, total, device):
+    def __init__(self, torch, n_cams, n_points, total, device, with_loss=False):
         f64 = dict(dtype=torch.float64, device=device)
         self.cams, self.points = torch.zeros((n_cams, 16), **f64), torch.zeros((n_points, 3), **f64)
         self.vinv, self.gp, self.cost = torch.zeros((n_points, 6), **f64), torch.zeros((n_points, 3), **f64), torch.zeros(n_points, **f64)
@@ -69,10 +74,26 @@ class _Buffers:
         self.obs_ok = torch.zeros(total, dtype=torch.uint8, device=device)
         self.obs_lin = torch.zeros((total, 32), **f64)
         self.total_cost = torch.zeros(1, **f64)
+        if with_loss:
+            self.obs_w = torch.zeros(total, **f64)
+
+
+def check_loss(loss, loss_scale):
+    """-> (VC_BA_LOSS_* of the name, the scale as a float); ValueError, naming the options, for anything else."""
+    if loss not in LOSSES:
+        raise ValueError(f"bundle_adjust: unknown loss {loss!r}, expected one of {', '.join(LOSSES)}")
+    try:
+        scale = float(loss_scale)
+    except (TypeError, ValueError):
+        scale = float("nan")
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"bundle_adjust: loss_scale must be a finite positive number of pixels (got {loss_scale!r}); the losses are "
+                         f"{', '.join(LOSSES)}")
+    return LOSSES[loss], scale
 
 
 def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cuda", max_iterations=BA_MAX_ITERATIONS, cam_group=None,
-                  intr_mask=None):
+                  intr_mask=None, loss="trivial", loss_scale=1.0):
     """cams float64 (n_cams, 16) as vc_triangulate_tracks has them, points float64 (n_points, 3), offsets int32 (n_points + 1,),
     obs_cam int32 (total,), obs_xy float64 (total, 2), const_mask uint8 (n_cams,) (bit i: pose parameter i is held), numpy
     -> cams, points (numpy, adjusted) and the report dict(iterations, accepted_steps, initial_cost, final_cost, final_lambda,
@@ -80,7 +101,11 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     cam_group int32 (n_cams,) and intr_mask uint8 (n_groups,), both or neither: the intrinsics of every group of cameras are
     refined too (mapping/bundle_intr.py; bits 0-3 of a group's mask: fx, fy, cx, cy held, bit 4: fx and fy tied; a slot whose
     group is outside [0, n_groups) keeps its intrinsics), the report gains `intrinsics` = dict(before, after), (n_groups, 4)
-    each.  Raises ValueError above VC_BA_MAX_GROUPS groups."""
+    each.  Raises ValueError above VC_BA_MAX_GROUPS groups.
+    loss "trivial", "huber" or "soft_l1" with loss_scale in px ("The loss" in §4.2k): with "trivial" exactly today's calls;
+    otherwise vc_ba_linearize_points_loss and, with groups, the border's _loss entry points; the costs of the report are the
+    robust ones.  The report carries loss and loss_scale.  Raises ValueError for an unknown loss or a scale that is not finite
+    and positive."""
     import torch
 
     from .. import _lib
@@ -90,6 +115,7 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     offsets, obs_cam = np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(obs_cam, np.int32)
     obs_xy, const_mask = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2), np.ascontiguousarray(const_mask, np.uint8)
     n_cams, n_points, total = len(cams), len(points), len(obs_cam)
+    loss_kind, loss_scale = check_loss(loss, loss_scale)
     if n_cams > _lib.VC_BA_MAX_CAMS:
         raise ValueError(f"bundle_adjust: {n_cams} cameras, the reduction kernel holds at most {_lib.VC_BA_MAX_CAMS} (VC_BA_MAX_CAMS)")
     if offsets.shape != (n_points + 1,) or obs_xy.shape != (total, 2) or const_mask.shape != (n_cams,):
@@ -100,8 +126,9 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
             raise ValueError("bundle_adjust needs cam_group and intr_mask together")
         from .bundle_intr import Border
 
-        border = Border(cams, cam_group, intr_mask)
-    report = dict(iterations=0, accepted_steps=0, initial_cost=0.0, final_cost=0.0, final_lambda=BA_LAMBDA0, decisions=[])
+        border = Border(cams, cam_group, intr_mask, with_loss=loss_kind != 0)
+    report = dict(iterations=0, accepted_steps=0, initial_cost=0.0, final_cost=0.0, final_lambda=BA_LAMBDA0, decisions=[], loss=loss,
+                  loss_scale=loss_scale)
     if n_cams == 0 or n_points == 0:
         return cams.copy(), points.copy(), report if border is None else border.report(report, cams)
     lib = _lib.load()
@@ -113,7 +140,7 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     cam_offsets, cam_obs, obs_point = (on_device(a) for a in camera_index(obs_cam, offsets, n_cams))
     d_offsets, d_obs_cam, d_obs_xy, d_mask = on_device(offsets), on_device(obs_cam), on_device(obs_xy), on_device(const_mask)
     free = on_device(np.array([[not (int(m) >> i) & 1 for i in range(6)] for m in const_mask], bool).reshape(-1))
-    cur, cand = _Buffers(torch, n_cams, n_points, total, dev), _Buffers(torch, n_cams, n_points, total, dev)
+    cur, cand = (_Buffers(torch, n_cams, n_points, total, dev, with_loss=loss_kind != 0) for _ in range(2))
     cur.cams.copy_(on_device(cams)), cur.points.copy_(on_device(points))
     S = torch.zeros((6 * n_cams, 6 * n_cams), dtype=torch.float64, device=dev)
     g = torch.zeros(6 * n_cams, dtype=torch.float64, device=dev)
@@ -123,6 +150,12 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
         border.upload(on_device, d_offsets, d_obs_cam, (cam_offsets, cam_obs, obs_point))
 
     def linearize(b, lam):
+        if loss_kind != 0:
+            _lib.check(lib.vc_ba_linearize_points_loss(p(b.cams), n_cams, p(d_mask), p(b.points), n_points, p(d_offsets), p(d_obs_cam),
+                                                       p(d_obs_xy), total, float(lam), loss_kind, loss_scale, p(b.vinv), p(b.gp), p(b.cost),
+                                                       p(b.count), p(b.obs_ok), p(b.obs_lin), p(b.obs_w), p(b.total_cost), stream),
+                       "vc_ba_linearize_points_loss")
+            return
         _lib.check(lib.vc_ba_linearize_points(p(b.cams), n_cams, p(d_mask), p(b.points), n_points, p(d_offsets), p(d_obs_cam), p(d_obs_xy),
                                               total, float(lam), p(b.vinv), p(b.gp), p(b.cost), p(b.count), p(b.obs_ok), p(b.obs_lin),
                                               p(b.total_cost), stream), "vc_ba_linearize_points")
@@ -168,7 +201,7 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
             iterations += 1
     out_cams = cur.cams.cpu().numpy()
     report = dict(iterations=iterations, accepted_steps=int(sum(decisions)), initial_cost=initial, final_cost=cost, final_lambda=lam,
-                  decisions=decisions)
+                  decisions=decisions, loss=loss, loss_scale=loss_scale)
     return out_cams, cur.points.cpu().numpy(), report if border is None else border.report(report, out_cams)
 
 
@@ -181,7 +214,7 @@ def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
 
 
 def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
-                         grown=None, refine_focal_length=False) -> SparseModel:
+                         grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0) -> SparseModel:
     """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
     is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
     Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
@@ -191,8 +224,13 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     point is held); bundle_fn is then also given cam_group=, intr_mask= and max_iterations=REFINE_MAX_ITERATIONS (the same
     loop under a higher cap: a model grown under a wrong focal starts far from a minimum), the model's cameras carry the refined values, the
     filter and `error` use them and the report gains `intrinsics` {camera_id: dict(before, after)}.  Raises ValueError above
-    VC_BA_MAX_GROUPS cameras."""
+    VC_BA_MAX_GROUPS cameras.
+    `loss`, `loss_scale`: the loss of the adjustment ("The loss" in §4.2k); bundle_fn is given loss= and loss_scale= only when
+    the loss is not "trivial", and `stats()["bundle_adjustment"]` carries them then.  The filter stays MAX_ERROR px on the
+    unweighted error.  Raises ValueError for an unknown loss or a scale that is not finite and positive."""
     bundle_fn = bundle_fn or bundle_adjust
+    check_loss(loss, loss_scale)
+    loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=float(loss_scale))
     if grown is None:
         grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn)
     _, _, K, _, _ = _read_database(database_path)
@@ -223,9 +261,9 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
         cam_group = np.array([cids.index(grown.images[i]["camera_id"]) for i in ids], np.int32)
         intr_mask = np.array([HOLD_CX | HOLD_CY | (TIED if has_one_focal(grown.cameras[c]) else 0) for c in cids], np.uint8)
         cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group, intr_mask=intr_mask,
-                                         max_iterations=REFINE_MAX_ITERATIONS)
+                                         max_iterations=REFINE_MAX_ITERATIONS, **loss_args)
     else:
-        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device)
+        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, **loss_args)
     cams, points = np.array(cams, np.float64), np.array(points, np.float64)
 
     # every t and X rescaled so that the pair's baseline is 1 again (§4.2i)
@@ -235,7 +273,8 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     points = points * scale
 
     model = SparseModel(initial_pair=grown.initial_pair, rounds=grown.rounds,
-                        bundle_adjustment={k: v for k, v in report.items() if k not in ("decisions", "intrinsics")})
+                        bundle_adjustment={k: v for k, v in report.items() if k not in ("decisions", "intrinsics", "loss", "loss_scale")})
+    model.bundle_adjustment.update(loss_args)
     model.cameras = copy.deepcopy(grown.cameras)
     if refine_focal_length:
         # the cameras carry the refined focal length(s); the filter below and `error` use the refined K

@@ -45,10 +45,10 @@ class Border:
     checked here; the border's device buffers; per iteration the bordered system of the current linearisation and the step
     under (dc, dtheta); `intrinsics` = dict(before (n_groups, 4), after (n_groups, 4)) in the report."""
 
-    def __init__(self, cams, cam_group, intr_mask):
+    def __init__(self, cams, cam_group, intr_mask, with_loss=False):
         from .. import _lib
 
-        self._lib = _lib
+        self._lib, self.with_loss = _lib, with_loss                           # with a loss: the _loss entry points and the buffer's obs_w
         self.cam_group, self.intr_mask = np.ascontiguousarray(cam_group, np.int32), np.ascontiguousarray(intr_mask, np.uint8)
         self.n_cams, self.G = len(cams), len(self.intr_mask)
         if self.cam_group.shape != (self.n_cams,) or self.intr_mask.ndim != 1 or self.G < 1:
@@ -82,13 +82,23 @@ class Border:
 
         _lib, n_cams, G, n_points, total, nc = self._lib, self.n_cams, self.G, self.n_points, self.total, 6 * self.n_cams
         lib, p, stream = _lib.load(), _lib.ptr, _lib.stream_ptr()
-        _lib.check(lib.vc_ba_linearize_intrinsics(p(cur.cams), n_cams, p(self.group), G, p(self.intr), p(cur.points), n_points, p(self.offsets),
-                                                  p(self.obs_cam), total, p(cur.vinv), p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(self.obs_xn),
-                                                  p(self.T), p(self.terms), stream), "vc_ba_linearize_intrinsics")
-        _lib.check(lib.vc_ba_reduce_border(n_cams, p(self.group), G, p(self.intr), n_points, p(self.offsets), p(self.obs_cam), total,
-                                           *(p(a) for a in self.index), float(lam), p(cur.vinv), p(cur.obs_ok), p(cur.obs_lin), p(self.obs_xn),
-                                           p(self.T), p(self.terms), p(self.sums), p(self.B), p(self.C), p(self.h), p(self.free_t), stream),
-                   "vc_ba_reduce_border")
+        if self.with_loss:
+            _lib.check(lib.vc_ba_linearize_intrinsics_loss(p(cur.cams), n_cams, p(self.group), G, p(self.intr), p(cur.points), n_points,
+                                                           p(self.offsets), p(self.obs_cam), total, p(cur.vinv), p(cur.gp), p(cur.obs_ok),
+                                                           p(cur.obs_lin), p(cur.obs_w), p(self.obs_xn), p(self.T), p(self.terms), stream),
+                       "vc_ba_linearize_intrinsics_loss")
+            _lib.check(lib.vc_ba_reduce_border_loss(n_cams, p(self.group), G, p(self.intr), n_points, p(self.offsets), p(self.obs_cam), total,
+                                                    *(p(a) for a in self.index), float(lam), p(cur.vinv), p(cur.obs_ok), p(cur.obs_lin),
+                                                    p(self.obs_xn), p(cur.obs_w), p(self.T), p(self.terms), p(self.sums), p(self.B), p(self.C),
+                                                    p(self.h), p(self.free_t), stream), "vc_ba_reduce_border_loss")
+        else:
+            _lib.check(lib.vc_ba_linearize_intrinsics(p(cur.cams), n_cams, p(self.group), G, p(self.intr), p(cur.points), n_points, p(self.offsets),
+                                                      p(self.obs_cam), total, p(cur.vinv), p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(self.obs_xn),
+                                                      p(self.T), p(self.terms), stream), "vc_ba_linearize_intrinsics")
+            _lib.check(lib.vc_ba_reduce_border(n_cams, p(self.group), G, p(self.intr), n_points, p(self.offsets), p(self.obs_cam), total,
+                                               *(p(a) for a in self.index), float(lam), p(cur.vinv), p(cur.obs_ok), p(cur.obs_lin), p(self.obs_xn),
+                                               p(self.T), p(self.terms), p(self.sums), p(self.B), p(self.C), p(self.h), p(self.free_t), stream),
+                       "vc_ba_reduce_border")
         M, rhs = self.M, self.rhs
         M[:nc, :nc], M[:nc, nc:], M[nc:, :nc], M[nc:, nc:] = S, self.B, self.B.T, self.C
         rhs[:nc], rhs[nc:] = g, self.h

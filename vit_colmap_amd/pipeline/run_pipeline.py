@@ -19,6 +19,7 @@ from ..utils.config import Config
 logger = logging.getLogger(__name__)
 
 MATCHER_TYPES = ("exhaustive", "retrieval")   # MatchingConfig.matcher_type / --matcher
+BA_LOSSES = ("trivial", "huber", "soft_l1")   # ReconstructionConfig.ba_loss / --ba-loss (mapping.bundle.LOSSES)
 
 
 class Pipeline:
@@ -78,6 +79,15 @@ class Pipeline:
         refine_focal_length = bool(getattr(self.config.reconstruction, "refine_focal_length", False))
         if refine_focal_length and not bundle_adjustment:       # it is one more unknown of that adjustment (§4.2k)
             raise ValueError("refine_focal_length needs reconstruction.bundle_adjustment (--bundle-adjustment)")
+        ba_loss = str(getattr(self.config.reconstruction, "ba_loss", "trivial"))
+        ba_loss_scale = float(getattr(self.config.reconstruction, "ba_loss_scale", 1.0))
+        if ba_loss not in BA_LOSSES:
+            raise ValueError(f"unknown ba_loss {ba_loss!r}: expected one of {', '.join(BA_LOSSES)}")
+        if ba_loss != "trivial" and not bundle_adjustment:      # it is the loss of that adjustment (§4.2k)
+            raise ValueError("ba_loss needs reconstruction.bundle_adjustment (--bundle-adjustment)")
+        if not 0.0 < ba_loss_scale < float("inf"):
+            raise ValueError(f"ba_loss_scale must be a finite positive number of pixels (got {ba_loss_scale})")
+        loss_args = {} if ba_loss == "trivial" else dict(loss=ba_loss, loss_scale=ba_loss_scale)
         for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
             if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
                 continue
@@ -135,9 +145,10 @@ class Pipeline:
             self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
         if sparse_model:
             if refine_focal_length:
-                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True, refine_focal_length=True)
+                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True, refine_focal_length=True,
+                                         **loss_args)
             else:
-                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment)
+                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment, **loss_args)
 
         reconstructions = None
         if self.config.do_reconstruction:
@@ -177,10 +188,11 @@ class Pipeline:
         logger.info("Seed model: pair %s, %d images, %d points", *[model.stats()[k] for k in
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
-    def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False):
+    def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
         `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
-        `refine_focal_length`: that adjustment also refines the cameras' focal lengths."""
+        `refine_focal_length`: that adjustment also refines the cameras' focal lengths; `loss`, `loss_scale`: its loss, passed on
+        only where it is not the trivial one."""
         from ..mapping.grow import build_sparse_model
 
         try:
@@ -195,10 +207,11 @@ class Pipeline:
         if adjust:
             from ..mapping.bundle import build_adjusted_model
 
+            loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=loss_scale)
             if refine_focal_length:
-                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=True)
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=True, **loss_args)
             else:
-                adjusted = build_adjusted_model(str(db_path), device=device, grown=model)
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, **loss_args)
             adjusted.write_text(str(Path(output_dir) / "sparse" / "adjusted"))
             self.last_stats = dict(self.last_stats, bundle_adjustment=adjusted.stats())
             logger.info("Adjusted model: %d images, %d points, cost %.6g -> %.6g", len(adjusted.images), len(adjusted.points3D),
@@ -254,6 +267,11 @@ def main() -> None:
     ap.add_argument("--refine-focal-length", dest="refine_focal_length", action="store_true",
                     help="with --bundle-adjustment: the adjustment also refines the focal length(s) of every camera; the "
                          "adjusted model's cameras.txt carries the refined values")
+    ap.add_argument("--ba-loss", dest="ba_loss", choices=list(BA_LOSSES), default="trivial",
+                    help="with --bundle-adjustment: the loss of the adjustment; huber and soft_l1 keep observations that are tens "
+                         "of pixels off their point from setting the poses")
+    ap.add_argument("--ba-loss-scale", dest="ba_loss_scale", type=float, default=1.0, metavar="PX",
+                    help="the residual in pixels at which --ba-loss leaves the square")
     ap.add_argument("--matcher", choices=list(MATCHER_TYPES), default="exhaustive",
                     help="exhaustive: every image pair; retrieval: each image against its --num-neighbors nearest images")
     ap.add_argument("--num-neighbors", dest="num_neighbors", type=int, default=20,

@@ -109,6 +109,8 @@ class ReconstructionConfig:
     sparse_model: bool = False   # write output_dir/sparse/grown: the seed model grown by rounds of triangulation and registration (§4.2j)
     bundle_adjustment: bool = False   # with sparse_model: write output_dir/sparse/adjusted, the grown model bundle-adjusted once (§4.2k)
     refine_focal_length: bool = False   # with bundle_adjustment: the adjustment also refines every camera's focal length(s) (§4.2k)
+    ba_loss: str = "trivial"     # with bundle_adjustment: the loss of the adjustment, "trivial", "huber" or "soft_l1" (§4.2k, "The loss")
+    ba_loss_scale: float = 1.0   # px: the residual at which the loss leaves the square
 
     def to_mapper_options(self):
         import pycolmap  # noqa: PLC0415 - optional, third party
@@ -174,6 +176,10 @@ class Config:
             config.reconstruction.bundle_adjustment = True
         if getattr(args, "refine_focal_length", False):
             config.reconstruction.refine_focal_length = True
+        if getattr(args, "ba_loss", None):
+            config.reconstruction.ba_loss = args.ba_loss
+        if getattr(args, "ba_loss_scale", None) is not None:
+            config.reconstruction.ba_loss_scale = float(args.ba_loss_scale)
         if getattr(args, "matcher", None):
             config.matching.matcher_type = args.matcher
         if getattr(args, "num_neighbors", None) is not None:
