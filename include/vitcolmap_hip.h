@@ -610,9 +610,10 @@ int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int
  *                           H % 128 == 0; VC_ERR_UNSUPPORTED otherwise), out must not alias x.  No copy or permutation of
  *                           the weight: a tile fetches its W operand from the two row ranges.
  * Two tile forms behind the one entry: a 256 x 256 persistent tile (one workgroup per CU, 128 KiB staging ring) when
- * n_out % 256 == 0 and rows >= 1024 — the ViT-B / ViT-L / ViT-g layers — and a 128 x 128 tile otherwise, for every
+ * n_out % 256 == 0 and its tiles fill at least half the device's CUs, ceil(rows / 256) * (n_out / 256) * 2 >= CUs (128
+ * tiles on 256 CUs) — the ViT-B / ViT-L / ViT-g layers on a batch of frames — and a 128 x 128 tile otherwise, for every
  * epilogue (VC_EPI_SWIGLU: a tile then makes 128 resp. 64 output columns); same arithmetic, the accumulation order over
- * k_in is the same in both.
+ * k_in is the same in both.  vc_linear_tile_rows answers which form a shape takes.
  * Replaces the nn.Linear / GELU / residual-add calls inside the hub model's blocks
  * (reference vit_extractor.py:135-146).
  */
@@ -622,6 +623,10 @@ int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int
 #define VC_EPI_SWIGLU 4 /* (3 is taken inside the library: the patch-embedding epilogue, not accepted here) */
 int vc_linear_bf16(const void* x, const void* weight, const void* bias, const void* residual_or_null,
                    void* out, int rows, int n_out, int k_in, int epilogue, vc_stream_t stream);
+
+/* The tile form vc_linear_bf16 takes for [rows] x [n_out] on the current device, by the rule above: 256 or 128 (the rows of
+ * a tile), or a negative VC_ERR_* status (n_out % 128 != 0: VC_ERR_UNSUPPORTED).  Host code only, nothing is launched. */
+int vc_linear_tile_rows(int rows, int n_out);
 
 /*
  * Convolution over a channels-last image batch as an implicit GEMM on the 256 x 256 tile (the convolutional heads of the

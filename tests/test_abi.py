@@ -56,6 +56,8 @@ def test_argument_validation_needs_no_gpu():
     assert lib.vc_prepare_descriptors(None, None, 1, 512, 384, None, None) == -1
     assert lib.vc_match_pairs_u8(None, None, 1, 512, 384, None, 1, 0.8, 0.7, 1, None, None, None) == -1
     assert lib.vc_theta_table(None, 4, None) == -1
+    assert lib.vc_linear_tile_rows(-1, 256) == -1 and lib.vc_linear_tile_rows(1024, 0) == -1
+    assert lib.vc_linear_tile_rows(1024, 200) == -2       # n_out % 128 != 0: vc_linear_bf16 has no tile for it
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

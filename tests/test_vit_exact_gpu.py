@@ -194,10 +194,12 @@ def test_linear_bits(rows, K, N, epi):
 def test_linear_bits_on_the_256_tile(epi):
     """vc_linear_bf16 takes the 256 x 256 tile once its tiles fill half the CUs (gemm.hip vc_linear_bf16: tiles x 2 >= CUs).
     4097 rows are 17 row tiles, ragged; the width is chosen from the device's CU count so that the condition holds
-    (2048 columns up to 272 CUs)."""
+    (2048 columns up to 272 CUs); hip_ops.linear_tile_rows answers for the form."""
+    from vit_colmap_amd.vit.hip_ops import linear_tile_rows
+
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     tiles_n = max(8, -(-cus // (2 * 17)))
-    assert 17 * tiles_n * 2 >= cus
+    assert linear_tile_rows(4097, 256 * tiles_n) == 256, (cus, tiles_n)
     _linear_bits(4097, 64, 256 * tiles_n, epi)
 
 

@@ -94,18 +94,30 @@ def test_attention_structured_values_catch_layout_errors():
     assert (out - ref).abs().max().item() < 2e-2
 
 
+# the shapes of test_linear_matches_float32_reference that reach the 256 x 256 tile (at least 144 large tiles: up to 288 CUs)
+LARGE_TILE_SHAPES = {(5000, 1024, 4096), (3062, 1024, 3072), (3062, 1024, 4096), (19382, 768, 2304)}
+
+
 @pytest.mark.parametrize("rows,K,N", [(1531 * 2, 384, 1152), (300, 384, 384), (1531, 384, 1536), (1000, 1536, 384),
                                       (1, 64, 128), (129, 768, 2304), (128, 128, 256),
                                       (1531 * 3, 1536, 384), (4096, 64, 128), (4097, 640, 384),
-                                      # the 256 x 256 tile kernel (n_out % 256 == 0, >= 1024 rows): ragged last row tile, one and many K steps
-                                      (1531 * 2, 768, 2304), (1024, 64, 256), (1025, 3072, 768), (2047, 768, 768), (5000, 1024, 4096),
-                                      # ViT-L at two 640 x 480 frames (qkv, proj, fc1, fc2) and ViT-B at two DTU frames (qkv)
+                                      # n_out % 256 == 0, ragged last row tile, one and many K steps; the 256 x 256 tile is taken
+                                      # from CUs / 2 large tiles on (128 on 256 CUs): these four are 108, 4, 15 and 24 large
+                                      # tiles and run the 128 x 128 tile below CUs / 2 large tiles ...
+                                      (1531 * 2, 768, 2304), (1024, 64, 256), (1025, 3072, 768), (2047, 768, 768),
+                                      # ... and this one, 320 tiles, the 256 x 256 tile (LARGE_TILE_SHAPES)
+                                      (5000, 1024, 4096),
+                                      # ViT-L at two 640 x 480 frames (qkv, proj, fc1, fc2) and ViT-B at two DTU frames (qkv): 144,
+                                      # 48, 192, 48 and 684 large tiles, so proj and fc2 (N = 1024) run the 128 x 128 tile too
                                       (3062, 1024, 3072), (3062, 1024, 1024), (3062, 1024, 4096), (3062, 4096, 1024),
                                       (19382, 768, 2304)])
 @pytest.mark.parametrize("epi", [0, 1, 2])
 def test_linear_matches_float32_reference(rows, K, N, epi):
     """Hand-written bf16 GEMM + fused epilogue (through the C ABI) vs the float32 evaluation of the same bf16 data."""
-    from vit_colmap_amd.vit.hip_ops import linear
+    from vit_colmap_amd.vit.hip_ops import linear, linear_tile_rows
+
+    if (rows, K, N) in LARGE_TILE_SHAPES:
+        assert linear_tile_rows(rows, N) == 256, (rows, N, torch.cuda.get_device_properties(0).multi_processor_count)
 
     g = torch.Generator(device="cuda").manual_seed(rows + K + N + epi)
     x = torch.randn(rows, K, device="cuda", generator=g).to(torch.bfloat16)

@@ -1,4 +1,5 @@
-"""Exact-operand cases for the ViT kernels (x-stationary GEMM, fused MLP, attention) and their comparators.
+"""Exact-operand cases for the ViT kernels (x-stationary GEMM, fused MLP, attention; the staged GEMMs behind vc_linear_bf16,
+vc_patch_embed_bf16 and vc_conv_taps_bf16; add + LayerNorm) and their comparators.
 
 The kernels' documented arithmetic is bf16 operands, float32 accumulation, bf16 results.  The operands built here are
 chosen so that this arithmetic has ONE possible result: every product and every partial sum is exactly representable in
@@ -9,7 +10,8 @@ case is the same wherever it is built.
 
 Comparators take (got, case) and raise AssertionError on a mismatch; `got` is a bf16 tensor (or its bit patterns).
 The float32 emulations (emulate_*) restate a kernel's contract step by step on the CPU in float32 and take single-defect
-mutations; tests/test_vit_exact_spec.py proves with them that the comparators accept the contract and reject the defects.
+mutations; tests/test_vit_exact_spec.py and tests/test_staged_exact_spec.py prove with them that the comparators accept the
+contract and reject the defects.
 """
 import math
 
@@ -84,10 +86,12 @@ def choice(values, shape, g: torch.Generator) -> torch.Tensor:
 
 
 # ---- LayerNorm rows -----------------------------------------------------------------------------------------------------
-def ln_rows(rows: int, g: torch.Generator, level_sets=LEVEL_SETS, scales=SCALES, pool: int = 2048):
-    """[rows][384] float32 (bf16-exact values): each row = one level set (equal counts), one scale, one random permutation.
+def ln_rows(rows: int, g: torch.Generator, level_sets=LEVEL_SETS, scales=SCALES, pool: int = 2048, width: int = K):
+    """[rows][width] float32 (bf16-exact values): each row = one level set (equal counts), one scale, one random permutation.
     More than `pool` rows are drawn (with a random, non-periodic index) from a pool of that many distinct rows.
+    width: 384, the K of the GEMM cases, or any multiple of 4 (the level sets hold 2 or 4 levels).
     -> (x, set index, scale)."""
+    K = width
     n = min(rows, pool)
     si = torch.randint(0, len(level_sets), (n,), generator=g)
     sc = torch.tensor(scales, dtype=F64)[torch.randint(0, len(scales), (n,), generator=g)]
@@ -544,3 +548,306 @@ def emulate_attention(case: dict, q_prescaled: bool, mutate=None) -> torch.Tenso
     l = p.sum(dim=-1, keepdim=True) + l_extra
     o = p.to(torch.bfloat16).to(f32) @ v
     return (o * (1.0 / l)).transpose(1, 2).reshape(B, N, H * HD).to(torch.bfloat16)
+
+
+# ---- the staged GEMMs (gemm.hip gemm_kernel, gemm256_kernel): linear, patch embedding, convolution -----------------------
+# Operands of two kinds.  'dense': x in multiples of 1/4 in [-2, 2], W in {+-1/4, +-1/2, +-1}, bias in multiples of 1/4,
+# residual / pos_embed in multiples of 1/8 with |r| <= 4: products are multiples of 2^-4 and sum |product| <= 2 K, at K = 4096
+# 2^17 units — every partial sum in any order is a float32 number.  'sparse': x from {+-1/4, +-1/2, +-1} (no zero), W with 6
+# non-zeros per row from the same set at columns drawn over the whole of K, bias an odd multiple of 2^-5 with |b| <= 1: the
+# pre-activation h is an odd multiple of 2^-5 with 2^-5 <= |h| < 8, every such value is a bf16 number (8 significant bits),
+# so every single dropped, doubled or misplaced non-zero product (an even multiple of 2^-5, not 0) changes the output bits.
+EPI_SWIGLU = 4                # VC_EPI_SWIGLU
+BK = 64                       # K tile of both staged kernels
+SPARSE_NNZ = 6
+PM = (-1.0, -0.5, -0.25, 0.25, 0.5, 1.0)
+
+
+def _ints(lo: int, hi: int, shape, g: torch.Generator) -> torch.Tensor:
+    """Integers lo .. hi (inclusive) drawn on the CPU as int8: the long cases widen them on the device."""
+    return torch.randint(lo, hi + 1, tuple(shape), generator=g, dtype=torch.int8)
+
+
+def dyadic(lo: int, hi: int, step: float, shape, g: torch.Generator, device="cpu") -> torch.Tensor:
+    """Multiples of `step` from lo step to hi step, float64 on `device`."""
+    return _ints(lo, hi, shape, g).to(device).to(F64) * step
+
+
+def pm_values(shape, g: torch.Generator, device="cpu") -> torch.Tensor:
+    """Values from {+-1/4, +-1/2, +-1}, float64 on `device`."""
+    return torch.tensor(PM, dtype=F64, device=device)[_ints(0, len(PM) - 1, shape, g).to(device).long()]
+
+
+def odd_bias32(n: int, g: torch.Generator) -> torch.Tensor:
+    """Odd multiples of 2^-5 with |b| <= 1."""
+    return (2 * _ints(-16, 15, (n,), g).to(F64) + 1) * 2.0 ** -5
+
+
+def staged_sparse_weight(n_out: int, k: int, g: torch.Generator, nnz: int = SPARSE_NNZ) -> torch.Tensor:
+    """[n_out][k] with `nnz` non-zeros per row from {+-1/4, +-1/2, +-1} at columns drawn over the whole of k.  Asserted: every
+    K tile of 64 holds a non-zero of some row of every 256-column tile (a K tile the kernel drops or takes twice is seen in
+    every output tile)."""
+    cols = torch.rand(n_out, k, generator=g).argsort(dim=1)[:, :nnz]
+    w = torch.zeros(n_out, k, dtype=F64)
+    w.scatter_(1, cols, pm_values((n_out, nnz), g))
+    assert bool(((w != 0).sum(dim=1) == nnz).all())
+    for n0 in range(0, n_out, 256):
+        assert bool((w[n0:n0 + 256] != 0).any(dim=0).reshape(k // BK, BK).any(dim=1).all()), "a K tile without a non-zero"
+    return w
+
+
+def assert_sparse_range(h: torch.Tensor):
+    """h is an odd multiple of 2^-5 with 2^-5 <= |h| < 8 (then a bf16 number)."""
+    m = h * 32
+    assert bool((m == torch.round(m)).all()) and bool((m.abs() % 2 == 1).all()) and bool((h.abs() < 8.0).all())
+    assert is_bf16_exact(h)
+
+
+def silu_mul_f64(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    return a / (1.0 + torch.exp(-a)) * b
+
+
+def bound_ratio(got: torch.Tensor, case: dict) -> float:
+    """max |got - ref| / bound of a case judged by a bound (what the tests print beside their assertion)."""
+    val = bits_to_f64(bits_of(got)).reshape(case["ref"].shape)
+    ref, bound = case["ref"].to(val.device), case["bound"].to(val.device)
+    return float(((val - ref).abs() / bound).max())
+
+
+def _epilogue_expectation(case: dict, h: torch.Tensor, res):
+    """EPI_BIAS / EPI_RESIDUAL: bits of bf16(h (+ r)).  EPI_GELU: gelu_f64(h) under the float path's bound, 2^-8 |ref| + 2e-7
+    (1 + |h|), the one xs_case(gelu_float=True) uses.  EPI_SWIGLU: see linear_case."""
+    epi = case["epi"]
+    if epi == EPI_GELU:
+        case["ref"] = gelu_f64(h)
+        case["bound"] = 2.0 ** -8 * case["ref"].abs() + 2e-7 * (1 + h.abs())
+    elif epi == EPI_SWIGLU:
+        hh = h.shape[-1] // 2
+        a, b = h[..., :hh], h[..., hh:]
+        case["ref"] = silu_mul_f64(a, b)
+        case["bound"] = ulp_bf16(case["ref"]) + 2.0 ** -20 * (1 + a.abs()) * case["ref"].abs()
+    else:
+        case["expect_bits"] = f64_to_bits(bf16_rne(h if res is None else h + res))
+    return case
+
+
+def _operands(kind: str, x_shape, n_out: int, k: int, g: torch.Generator, device):
+    """(x, W, bias, unit of the products and the bias) of one kind."""
+    if kind == "dense":
+        return dyadic(-8, 8, 0.25, x_shape, g, device), pm_values((n_out, k), g), dyadic(-8, 8, 0.25, (n_out,), g), 2.0 ** -4
+    assert kind == "sparse"
+    return pm_values(x_shape, g, device), staged_sparse_weight(n_out, k, g), odd_bias32(n_out, g), 2.0 ** -5
+
+
+def linear_case(rows: int, k: int, n_out: int, kind: str, epi: int, seed: int, device="cpu") -> dict:
+    """vc_linear_bf16 on exact operands (kinds above).  EPI_BIAS / EPI_RESIDUAL: out bits = bf16(h64 (+ r)).  EPI_GELU (sparse):
+    gelu_f64(h) under 2^-8 |ref| + 2e-7 (1 + |h|).  EPI_SWIGLU (sparse; n_out is the width of the product, gate rows then
+    value rows, so gate a and value b are exact): ref = a / (1 + exp(-a)) b in float64, bound = ulp_bf16(ref) + 2^-20 (1 + |a|)
+    |ref|.  The second term: the exponent a * -log2(e) carries 2^-24 relative, |a| 2^-24 relative in exp2; v_exp_f32 and
+    v_rcp_f32 are 1 ulp each, two multiplications: under (|a| + 4) 2^-23, and the term gives it eight times that.
+    Measured (test_staged_exact_spec.py::test_swiglu_emulation_stays_inside_its_bound): the float32 emulation (torch exp2 and
+    reciprocal) reaches err / bound = 0.50, all of it the rounding to bf16 (half an ulp of a full-ulp term); the float32
+    term is not widened."""
+    g = gen(seed)
+    x, w, b, unit = _operands(kind, (rows, k), n_out, k, g, device)
+    res = dyadic(-32, 32, 0.125, (rows, n_out), g, device) if epi == EPI_RESIDUAL else None
+    w, b = w.to(device), b.to(device)
+    h = x @ w.t() + b                                                    # exact: every partial sum is a float64 number
+    # sum |product| + |bias| + |residual| <= max |x| sum |W| + ..: every partial sum, in any order, is a float32 number
+    assert sum_fits_float32(x.abs().amax(dim=1, keepdim=True) * w.abs().sum(dim=1)[None, :] + b.abs() + 4.0, unit)
+    if kind == "sparse":
+        assert_sparse_range(h)
+    assert epi in (EPI_BIAS, EPI_RESIDUAL) or kind == "sparse"
+    case = dict(name=f"linear {kind} {rows}x{k}x{n_out} epi={epi}", kind=kind, epi=epi, x=to_bf16(x), w=to_bf16(w), b=to_bf16(b),
+                residual=None if res is None else to_bf16(res), h=h)
+    return _epilogue_expectation(case, h, res)
+
+
+def _f32_products(x: torch.Tensor, w: torch.Tensor, order_seed: int, mutate=None) -> torch.Tensor:
+    """sum_k x[:, k] w[:, k] in float32, the products added one by one in a random order.  mutate: ('drop' | 'double', row, col,
+    k) that product of that output; ('ktile', t) K tile t taken twice, in place of its neighbour t + 1."""
+    k = x.shape[1]
+    src = torch.arange(k)
+    if mutate is not None and mutate[0] == "ktile":
+        t = mutate[1]
+        src[(t + 1) * BK:(t + 2) * BK] = torch.arange(t * BK, (t + 1) * BK)
+    acc = torch.zeros(x.shape[0], w.shape[0], dtype=torch.float32)
+    for kk in src[torch.randperm(k, generator=gen(4000 + order_seed))].tolist():
+        acc += x[:, kk, None] * w[None, :, kk]
+    if mutate is not None and mutate[0] in ("drop", "double"):
+        kind, r, c, kk = mutate
+        acc[r, c] += {"drop": -1.0, "double": 1.0}[kind] * x[r, kk] * w[c, kk]
+    return acc
+
+
+def _f32_epilogue(acc: torch.Tensor, case: dict, mutate=None) -> torch.Tensor:
+    """The staged kernels' epilogues on float32 pre-activations -> bf16.  mutate ('swiglu_swap', col): gate and value of that
+    output column exchanged; ('rows', r1, r2): two output rows exchanged."""
+    f32 = torch.float32
+    epi = case["epi"]
+    if epi == EPI_RESIDUAL:
+        acc = acc + case["residual"].cpu().to(f32)
+    elif epi == EPI_GELU:
+        acc = gelu_float_path(acc.to(F64)).to(f32)
+    elif epi == EPI_SWIGLU:
+        hh = acc.shape[1] // 2
+        a, b = acc[:, :hh].clone(), acc[:, hh:].clone()
+        if mutate is not None and mutate[0] == "swiglu_swap":
+            a[:, mutate[1]], b[:, mutate[1]] = acc[:, hh + mutate[1]], acc[:, mutate[1]]
+        e = torch.exp2(a * torch.tensor(-1.4426950408889634, dtype=f32))
+        acc = a * torch.reciprocal(1.0 + e) * b
+    out = acc.to(torch.bfloat16)
+    if mutate is not None and mutate[0] == "rows":
+        out[[mutate[1], mutate[2]]] = out[[mutate[2], mutate[1]]]
+    return out
+
+
+def emulate_linear(case: dict, order_seed: int = 0, mutate=None) -> torch.Tensor:
+    """gemm_kernel / gemm256_kernel's contract in float32 on the CPU: bf16 operands, the K products added one by one in a
+    random order, + bias, epilogue (GELU by the float path's formula, SwiGLU by exp2 and a reciprocal), one rounding."""
+    f32 = torch.float32
+    acc = _f32_products(case["x"].cpu().to(f32), case["w"].cpu().to(f32), order_seed, mutate) + case["b"].cpu().to(f32)
+    return _f32_epilogue(acc, case, mutate)
+
+
+def patch_case(B: int, T: int, n_out: int, k_in: int, seed: int, device="cpu") -> dict:
+    """vc_patch_embed_bf16 on dense operands, pos_embed [1 + T][n_out] in multiples of 1/8: out[b, 1 + t] bits =
+    bf16(patches[b, t] W^T + bias + pos_embed[1 + t]); expect_bits is [B][T][n_out], the rows the kernel writes."""
+    g = gen(seed)
+    x, w, b, unit = _operands("dense", (B, T, k_in), n_out, k_in, g, device)
+    pos = dyadic(-32, 32, 0.125, (T + 1, n_out), g, device)
+    w, b = w.to(device), b.to(device)
+    assert sum_fits_float32(torch.tensor(2.0 * k_in + 2.0 + 4.0), unit)
+    h = x @ w.t() + b + pos[1:]
+    return dict(name=f"patch_embed B={B} T={T} n={n_out} k={k_in}", x=to_bf16(x), w=to_bf16(w), b=to_bf16(b), pos=to_bf16(pos),
+                expect_bits=f64_to_bits(bf16_rne(h)))
+
+
+def emulate_patch(case: dict, order_seed: int = 0, mutate=None) -> torch.Tensor:
+    """EPI_PATCH in float32: products in a random order, + bias, + pos_embed[1 + t], one rounding -> [B][T][n_out] bf16.
+    mutate ('pos',): pos_embed[t] in place of pos_embed[1 + t]; the product mutations of _f32_products on row b T + t."""
+    f32 = torch.float32
+    B, T, k = case["x"].shape
+    acc = _f32_products(case["x"].cpu().to(f32).reshape(B * T, k), case["w"].cpu().to(f32), order_seed, mutate) + case["b"].cpu().to(f32)
+    pos = case["pos"].cpu().to(f32)
+    pos = pos[:-1] if mutate is not None and mutate[0] == "pos" else pos[1:]
+    return (acc.reshape(B, T, -1) + pos).to(torch.bfloat16)
+
+
+def conv_gather(img: torch.Tensor, kh: int, kw: int, dy0: int, dx0: int, nudge=None) -> torch.Tensor:
+    """vc_conv_taps_bf16's definition as a gather: [B][H][W][C] -> [B H W][kh kw C], k = (tap, channel); tap t of output pixel
+    (y, x) is pixel (y + dy0 + t / kw, x + dx0 + t % kw) of the same image, zero outside it.  nudge = t: that tap reads the
+    pixel to the right of its own (the single-defect mutant)."""
+    B, H, W, C = img.shape
+    out = torch.zeros(B, H, W, kh * kw, C, dtype=img.dtype, device=img.device)
+    for t in range(kh * kw):
+        dy, dx = dy0 + t // kw, dx0 + t % kw + (1 if nudge == t else 0)
+        ys, ye, xs, xe = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)
+        if ys < ye and xs < xe:
+            out[:, ys:ye, xs:xe, t] = img[:, ys + dy:ye + dy, xs + dx:xe + dx]
+    return out.reshape(B * H * W, kh * kw * C)
+
+
+def conv_case(B: int, H: int, W: int, C: int, n_out: int, kh: int, kw: int, dy0: int, dx0: int, kind: str, epi: int, seed: int,
+              device="cpu", img=None, weight=None, bias=None) -> dict:
+    """vc_conv_taps_bf16 on exact operands: x_rows [B H W + 1][C] (the spare row holds junk: the call must zero it), weight
+    [n_out][kh kw C].  EPI_BIAS: bits of bf16(h64); EPI_GELU (sparse): the float path's bound.  A tap outside the image
+    leaves its products out, which keeps a sparse h an odd multiple of 2^-5.  img / weight / bias (float64): given operands
+    in place of drawn ones (the parity classes of a transposed convolution)."""
+    g = gen(seed)
+    k = kh * kw * C
+    x, w, b, unit = _operands(kind, (B * H * W + 1, C), n_out, k, g, device)
+    if img is not None:
+        x = torch.cat([img.reshape(B * H * W, C).to(device), x[-1:]])
+    w, b = (w if weight is None else weight).to(device), (b if bias is None else bias).to(device)
+    assert sum_fits_float32(torch.tensor(2.0 * k + 2.0), unit)
+    h = conv_gather(x[:-1].reshape(B, H, W, C), kh, kw, dy0, dx0) @ w.t() + b
+    if kind == "sparse":
+        assert_sparse_range(h)
+    case = dict(name=f"conv {kind} ({B},{H},{W},{C})->{n_out} taps {kh}x{kw} at ({dy0},{dx0}) epi={epi}", kind=kind, epi=epi,
+                geometry=(B, H, W, kh, kw, dy0, dx0), x_rows=to_bf16(x), w=to_bf16(w), b=to_bf16(b), residual=None, h=h)
+    return _epilogue_expectation(case, h, None)
+
+
+def emulate_conv(case: dict, order_seed: int = 0, mutate=None) -> torch.Tensor:
+    """The implicit GEMM in float32: the (tap, channel) products in a random order, + bias, epilogue, one rounding.
+    mutate ('tap', t): tap t read from the neighbouring pixel; the product mutations of _f32_products."""
+    f32 = torch.float32
+    B, H, W, kh, kw, dy0, dx0 = case["geometry"]
+    x = case["x_rows"].cpu().to(f32)[:-1]
+    cols = conv_gather(x.reshape(B, H, W, -1), kh, kw, dy0, dx0, nudge=mutate[1] if mutate is not None and mutate[0] == "tap" else None)
+    acc = _f32_products(cols, case["w"].cpu().to(f32), order_seed, mutate) + case["b"].cpu().to(f32)
+    return _f32_epilogue(acc, case, mutate)
+
+
+# ---- add + LayerNorm (vit_ops.hip add_layernorm_kernel) ------------------------------------------------------------------
+# The float32 term of the bound: LN_T 2^-24 (|gamma| (1 + max |v| / sigma) + |beta|), sigma = sqrt(var + eps).  The mean's error
+# is a few 2^-24 max |v| and reaches y as |gamma| / sigma times that (the row 96 + 0.5 k: max |v| / sigma ~ 100); the variance's
+# and the last three operations' are a few 2^-24 of |x-hat gamma| and |y|.  Half an ulp is what the rounding to bf16 alone
+# costs next to a tie, so the constant is measured on the values BEFORE that rounding (test_staged_exact_spec.py::
+# test_layernorm_emulation_stays_inside_its_bound): the float32 emulation of the kernel's sequence reaches |y32 - ref| =
+# 0.43 of the term with LN_T = 8 (0.86 with 4) over the shapes and both eps of the GPU test, at C = 2048.
+LN_T = 8.0
+LN_WIDTHS = (8, 72, 384, 520, 1536, 2048)
+LN_ROWS = (1, 5, 777)
+LN_EPS = (1e-6, 1e-5)
+
+
+def ln_case(rows: int, C: int, eps: float, seed: int) -> dict:
+    """x + residual -> (sum rounded to bf16, LayerNorm of the rounded sum).  `rows` rows of ln_rows (one level set, one scale)
+    plus a residual in multiples of 1/8, gamma in {1/2, 1, 2}, beta in {-1/2, 0, 1/2}, and three more rows: a constant row
+    (x = 3 - r: y must equal beta exactly), a row 96 + 0.5 k with |k| <= 3 (a large offset), a row of +-2^-7 (variance 2^-14:
+    eps decides the result).  sum_bits by bits; y against float64 LayerNorm of the rounded sum within 0.5 ulp_bf16(ref) + the
+    float32 term above.  (CPU tensors; the comparators move them.)"""
+    g = gen(seed)
+    x = ln_rows(rows, g, width=C)[0].to(F64)
+    r = dyadic(-32, 32, 0.125, (rows, C), g)
+    rc = dyadic(-32, 32, 0.125, (1, C), g)
+    zero = torch.zeros(1, C, dtype=F64)
+    x = torch.cat([x, 3.0 - rc, 96.0 + 0.5 * dyadic(-3, 3, 1.0, (1, C), g), (2.0 * _ints(0, 1, (1, C), g).to(F64) - 1.0) * 2.0 ** -7])
+    r = torch.cat([r, rc, zero, zero])
+    gamma, beta = choice((0.5, 1.0, 2.0), (C,), g), choice((-0.5, 0.0, 0.5), (C,), g)
+    v = bf16_rne(x + r)                                                  # (the float32 sum of two bf16 numbers is exact)
+    d = v - v.mean(dim=1, keepdim=True)
+    sigma = torch.sqrt((d * d).mean(dim=1, keepdim=True) + float(np.float32(eps)))
+    ref = d / sigma * gamma + beta
+    t = LN_T * 2.0 ** -24 * (gamma.abs() * (1 + v.abs().amax(dim=1, keepdim=True) / sigma) + beta.abs())
+    assert bool((v[rows] == 3.0).all()) and bool((ref[rows] == beta).all())
+    return dict(name=f"add_layernorm rows={rows}+3 C={C} eps={eps}", x=to_bf16(x), residual=to_bf16(r), gamma=to_bf16(gamma),
+                beta=to_bf16(beta), eps=eps, sum_bits=f64_to_bits(v), ref=ref, bound=0.5 * ulp_bf16(ref) + t, t=t,
+                const_row=rows, offset_row=rows + 1, tiny_row=rows + 2)
+
+
+def emulate_layernorm(case: dict, mutate=None, rounded: bool = True) -> torch.Tensor:
+    """add_layernorm_kernel's sequence in float32 on the CPU: the sum rounded to bf16; lane l sums its chunks l, l + 64, .. (8
+    values each) in order, the 64 lanes combine by the xor butterfly 32, 16, .., 1; mean = sum / C; the squares of v - mean the
+    same way; rstd = rsqrt(q / C + eps); ((v - mean) * rstd) * gamma + beta, every operation rounded (no contraction), one
+    rounding to bf16.  mutate ('eps', value): another eps; ('skip_chunk', ch): chunk ch left out of both sums.
+    -> y bf16, or (rounded=False) the float32 values before that rounding."""
+    f32 = torch.float32
+    v = (case["x"].cpu().to(f32) + case["residual"].cpu().to(f32)).to(torch.bfloat16).to(f32)
+    rows, C = v.shape
+    live = torch.zeros(256, dtype=f32)
+    live[: C // 8] = 1.0
+    if mutate is not None and mutate[0] == "skip_chunk":
+        live[mutate[1]] = 0.0
+    live = live.reshape(4, 64)[None, :, :, None]                         # chunk ch = lane + 64 k -> [k][lane]
+    lanes = torch.arange(64)
+
+    def wave_sum(t):                                                     # t [rows][C] -> [rows][1]
+        t = torch.nn.functional.pad(t, (0, 2048 - C)).reshape(rows, 4, 64, 8) * live
+        s = torch.zeros(rows, 64, dtype=f32)
+        for k in range(4):
+            for i in range(8):
+                s = s + t[:, k, :, i]
+        for o in (32, 16, 8, 4, 2, 1):
+            s = s + s[:, lanes ^ o]
+        return s[:, :1]
+
+    eps = torch.tensor(mutate[1] if mutate is not None and mutate[0] == "eps" else case["eps"], dtype=f32)
+    cf = torch.tensor(float(C), dtype=f32)
+    mean = wave_sum(v) / cf
+    d = v - mean
+    rstd = torch.rsqrt(wave_sum(d * d) / cf + eps)
+    y = d * rstd * case["gamma"].cpu().to(f32) + case["beta"].cpu().to(f32)
+    return y.to(torch.bfloat16) if rounded else y

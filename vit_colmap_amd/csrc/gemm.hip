@@ -1356,7 +1356,22 @@ static int for_row_ranges(long long rows, int n_cols, int tile_rows, F&& launch)
   return VC_OK;
 }
 
+// The tile form of vc_linear_bf16: the 256 x 256 tile for wide layers with enough of those tiles to occupy at least half the
+// CUs (one workgroup per CU); below that the 128 x 128 tile, two workgroups per CU, fills the chip better (a single image of
+// ViT-B is 18-72 large tiles).
+static bool linear_takes_large_tile(int rows, int n_out, int cus) {
+  return n_out % G2N == 0 && (long long)((rows + G2M - 1) / G2M) * (n_out / G2N) * 2 >= (long long)cus;
+}
+
 extern "C" {
+
+int vc_linear_tile_rows(int rows, int n_out) {
+  if (rows < 0 || n_out <= 0) return VC_ERR_INVALID_ARG;
+  if (n_out % BN != 0) return VC_ERR_UNSUPPORTED;
+  int cus = 0;
+  if (int st = vc::cu_count(&cus)) return st;
+  return linear_takes_large_tile(rows, n_out, cus) ? G2M : BM;
+}
 
 int vc_linear_bf16(const void* x, const void* weight, const void* bias, const void* residual_or_null, void* out,
                    int rows, int n_out, int k_in, int epilogue, vc_stream_t stream) {
@@ -1374,9 +1389,7 @@ int vc_linear_bf16(const void* x, const void* weight, const void* bias, const vo
   __bf16* po = (__bf16*)out;
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
-  // wide layers with enough 256 x 256 tiles to occupy at least half the CUs (one workgroup per CU); below that the 128 x 128
-  // tile, two workgroups per CU, fills the chip better (a single image of ViT-B is 18-72 large tiles)
-  if (n_out % G2N == 0 && (long long)((rows + G2M - 1) / G2M) * (n_out / G2N) * 2 >= (long long)cus) {
+  if (linear_takes_large_tile(rows, n_out, cus)) {
     const int tiles_m = (rows + G2M - 1) / G2M, tiles_n = n_out / G2N;
     const long long nt = (long long)tiles_m * tiles_n;
     if (nt > 0x7fffffffLL) return VC_ERR_UNSUPPORTED;

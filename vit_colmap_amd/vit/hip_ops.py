@@ -92,6 +92,15 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, epilogue: 
     return out
 
 
+def linear_tile_rows(rows: int, n_out: int) -> int:
+    """The tile `linear` takes for [rows] x [n_out] on the current device: 256 (the persistent 256 x 256 tile, once
+    ceil(rows / 256) * (n_out / 256) * 2 >= CUs and n_out % 256 == 0) or 128 (vc_linear_tile_rows)."""
+    t = _lib.load().vc_linear_tile_rows(rows, n_out)
+    if t < 0:
+        _lib.check(t, "vc_linear_tile_rows")
+    return t
+
+
 def conv_rows(batch: int, height: int, width: int, channels: int, device) -> torch.Tensor:
     """A channels-last activation buffer for `conv_taps`: [batch * height * width + 1][channels] bf16 — the image batch plus
     the spare row the kernel keeps at zero for taps outside the image."""
