@@ -437,6 +437,68 @@ int vc_ba_reduce_border_loss(int n_cams, const int32_t* cam_group, int n_groups,
                              double* out_h, uint8_t* out_free, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bundle adjustment with radial distortion ("The distortion"): COLMAP's SIMPLE_RADIAL (k2 held at 0)
+ * and RADIAL camera models.  The distortion travels beside the 16-number camera row, which does not change:
+ *   cam_dist    [n_cams][2] float64: (k1, k2) of each camera slot
+ * This build's own published rule; parity with COLMAP / Ceres is unpinned.  Specification: tests/util_bundle_radial.py.
+ * float64, single operations in the written order (left to right, the usual precedence), sqrt the only library call, no atomics.
+ * For camera row c = (R, t, fx, fy, cx, cy) and the point X:
+ *   Y = R X, Xc = Y + t, iu = 1 / Xc_z, xu = Xc_x / Xc_z, xv = Xc_y / Xc_z,
+ *   nu_k = iu (R_0k - xu R_2k), nv_k = iu (R_1k - xv R_2k)                         (the pinhole J_p at fx = fy = 1)
+ *   rho = xu xu + xv xv,  s = 1 + k1 rho + k2 rho rho,  e = 2 (k1 + 2 k2 rho)
+ *   d00 = s + xu xu e,  d01 = xu xv e,  d11 = s + xv xv e                           (the 2x2 Jacobian of (xu, xv) -> (xu s, xv s))
+ *   xd = xu s, yd = xv s,  r = (fx xd + cx - u, fy yd + cy - v)
+ *   J_p row u = fx (d00 nu + d01 nv), row v = fy (d01 nu + d11 nv)
+ *   J_c likewise from the pinhole rows at fx = fy = 1: au = iu xu, av = iu xv,
+ *       mu = (-(au Y_1), iu Y_2 + au Y_0, -(iu Y_1), iu, 0, -au), mv = (-(iu Y_2 + av Y_1), av Y_0, iu Y_0, 0, iu, -av),
+ *       row u = fx (d00 mu + d01 mv), row v = fy (d01 mu + d11 mv)
+ *   pu = fx xu rho, pv = fy xv rho, qu = pu rho, qv = pv rho
+ *   J_theta, six columns (fx, fy, cx, cy, k1, k2): row u = (xd, 0, 1, 0, pu, qu), row v = (0, yd, 0, 1, pv, qv); tied: column 0 =
+ *   (xd, yd), column 1 = 0; a held column is 0.
+ * An observation is usable under the conditions of vc_ba_linearize_points and finite k1, k2 of its camera.  Every entry point
+ * takes the loss (loss, loss_scale as vc_ba_linearize_points_loss; VC_BA_LOSS_TRIVIAL is the plain case: sw = 1 and every product
+ * with it is exact) and the weight array obs_w.
+ *
+ * vc_ba_linearize_points_radial: vc_ba_linearize_points_loss under the projection above; its outputs mean what they mean there,
+ * so vc_ba_reduce_cameras runs on them as it is.
+ * vc_ba_linearize_intrinsics_radial, vc_ba_reduce_border_radial, vc_ba_step_radial: the border with six unknowns per group,
+ * theta_g = (fx, fy, cx, cy, k1, k2); the layouts of the three entry points of "The border" with 6 in the place of 4:
+ *   intr_mask   bits 0-4 as there; bit 5 = k1 held, bit 6 = k2 held
+ *   out_obs_jt  [total][6]: (xd, yd, pu, pv, qu, qv) of a usable observation (unscaled by the loss), 0 otherwise: what the B pass
+ *               rebuilds J_theta from
+ *   out_T       [n_points][n_groups][18] (6x3 row-major)
+ *   out_terms   [48 G + 36 G^2][n_points]: rows 36 g + 6 i + k: q_jg; 36 G + 6 g + i: hq_jg; 42 G + 6 g + i: T V^-1 g_p;
+ *               48 G + 36 (g G + g') + 6 i + k: T_jg V^-1 T_jg''
+ *   out_sums    [48 G + 36 G^2], out_C [6 G][6 G], out_h [6 G], out_free [6 G], out_B [6 n_cams][6 G] (entry 36 g + 6 r + i of a
+ *               camera's row block owned by lane (36 g + 6 r + i) mod 64)
+ *   vc_ba_step_radial: dtheta [6 G]; out_dist [n_cams][2] = cam_dist + (dtheta_4, dtheta_5) of the slot's group (copied where
+ *               the slot has none); out_valid: 0 where the slot's group is in the table and its new fx or fy is not finite or not
+ *               positive, or its new k1 or k2 is not finite.
+ * n_groups <= VC_BA_MAX_GROUPS_RADIAL (the terms grow with 36 G^2 numbers per point and a lane of the B pass keeps
+ * ceil(36 G / 64) = 3 entries in registers), VC_ERR_UNSUPPORTED above; sizes of 0, null pointers, negative sizes, a bad loss and a
+ * bad lambda as the entry points above; every index is checked; skipped points and cameras write nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_BA_MAX_GROUPS_RADIAL 4
+int vc_ba_linearize_points_radial(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
+                                  int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                                  int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
+                                  uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream);
+int vc_ba_linearize_intrinsics_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
+                                      const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets,
+                                      const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
+                                      const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
+                                      double* out_terms, vc_stream_t stream);
+int vc_ba_reduce_border_radial(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
+                               const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs,
+                               const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
+                               const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
+                               double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream);
+int vc_ba_step_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                      const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
+                      const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
+                      double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

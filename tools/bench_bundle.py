@@ -7,7 +7,10 @@ neighbouring cameras, 0.5 px noise, poses and points moved off the truth.  A ker
 after 3 warm-up launches, by device events; the loop's is wall clock around bundle_adjust, synchronised, the median of --loops
 runs.  --refine-focal: the same two problems with every focal 3 % off and one tied group of intrinsics refined (§4.2k, "The
 border"): also the three entry points of the border and the bordered solve, and the refined loop beside the plain loop of the
-same build, the two alternating.  --loss huber|soft_l1 (--loss-scale PX, default 1): after those columns also the points pass
+same build, the two alternating.  --radial: after every other column the four entry points with radial distortion on the same
+problem (one group of six unknowns, k1 free from 0 and, with --refine-focal, the tied focal free too): the points pass, the
+border's two passes and the step, beside the plain points pass and the border with four unknowns of the columns before; and
+the loop that refines k1, alternating with the others.  --loss huber|soft_l1 (--loss-scale PX, default 1): after those columns also the points pass
 under the loss (vc_ba_linearize_points_loss) and, with --refine-focal, the border's two passes with obs_w, on the same buffers;
 and the loop under the loss beside the plain loop, alternating (with --refine-focal the refined loop under the loss too).
 Prints one JSON line.  Needs a GPU."""
@@ -83,7 +86,7 @@ def device_ms(fn, iters):
     return float(np.median(times))
 
 
-def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0):
+def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radial=False):
     cams, points, offsets, obs_cam, obs_xy, mask = problem
     if refine:
         cams = cams.copy()
@@ -170,6 +173,39 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0):
                                                         p(free), stream), "vc_ba_reduce_border_loss")
 
             stages += [("linearize_intrinsics_loss_ms", linearize_intrinsics_loss), ("reduce_border_loss_ms", reduce_border_loss)]
+    radial_args = {}
+    if radial:                                                        # after every other column: the _radial entry points, one group, k1 free
+        f64 = dict(dtype=torch.float64, device=dev)
+        rb = bundle._Buffers(torch, c, n, t, dev, with_dist=True)
+        radial_args = dict(cam_group=np.zeros(c, np.int32), intr_mask=np.array([(16 | 4 | 8 if refine else 15) | 64], np.uint8),
+                           cam_dist=np.zeros((c, 2)))
+        rg, ri = torch.from_numpy(radial_args["cam_group"]).to(dev), torch.from_numpy(radial_args["intr_mask"]).to(dev)
+        jt, T6, terms6, sums6 = torch.zeros((t, 6), **f64), torch.zeros((n, 1, 18), **f64), torch.zeros((84, n), **f64), torch.zeros(84, **f64)
+        B6, C6, h6, free6 = torch.zeros((6 * c, 6), **f64), torch.zeros((6, 6), **f64), torch.zeros(6, **f64), torch.zeros(6, dtype=torch.uint8, device=dev)
+        dtheta6, out_dist, valid6 = torch.zeros(6, **f64), torch.zeros((c, 2), **f64), torch.zeros(c, dtype=torch.uint8, device=dev)
+
+        def linearize_radial():
+            _lib.check(lib.vc_ba_linearize_points_radial(p(d[0]), c, p(rb.dist), p(d[1]), p(d[2]), n, p(d[3]), p(d[4]), p(d[5]), t, lam, 0, 1.0,
+                                                         p(rb.vinv), p(rb.gp), p(rb.cost), p(rb.count), p(rb.obs_ok), p(rb.obs_lin), p(rb.obs_w),
+                                                         p(rb.total_cost), stream), "vc_ba_linearize_points_radial")
+
+        def linearize_intrinsics_radial():
+            _lib.check(lib.vc_ba_linearize_intrinsics_radial(p(d[0]), c, p(rb.dist), p(rg), 1, p(ri), p(d[2]), n, p(d[3]), p(d[4]), t, 0, 1.0,
+                                                             p(rb.vinv), p(rb.gp), p(rb.obs_ok), p(rb.obs_lin), p(rb.obs_w), p(jt), p(T6), p(terms6),
+                                                             stream), "vc_ba_linearize_intrinsics_radial")
+
+        def reduce_border_radial():
+            _lib.check(lib.vc_ba_reduce_border_radial(c, p(rg), 1, p(ri), n, p(d[3]), p(d[4]), t, p(x[0]), p(x[1]), p(x[2]), lam, 0, 1.0, p(rb.vinv),
+                                                      p(rb.obs_ok), p(rb.obs_lin), p(jt), p(rb.obs_w), p(T6), p(terms6), p(sums6), p(B6), p(C6),
+                                                      p(h6), p(free6), stream), "vc_ba_reduce_border_radial")
+
+        def step_radial():
+            _lib.check(lib.vc_ba_step_radial(p(d[0]), c, p(rb.dist), p(rg), 1, p(ri), p(d[2]), n, p(d[3]), p(d[4]), t, p(rb.vinv), p(rb.gp),
+                                             p(rb.obs_ok), p(rb.obs_lin), p(T6), p(dc), p(dtheta6), p(out_cams), p(out_dist), p(out_points), p(dx),
+                                             p(valid6), stream), "vc_ba_step_radial")
+
+        stages += [("linearize_radial_ms", linearize_radial), ("linearize_intrinsics_radial_ms", linearize_intrinsics_radial),
+                   ("reduce_border_radial_ms", reduce_border_radial), ("step_radial_ms", step_radial)]
     for name, fn in stages:
         out[name] = round(device_ms(fn, iters), 4)
 
@@ -180,7 +216,7 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0):
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0), report, cams_out
 
-    walls, refined_walls, loss_walls, refined_loss_walls = [], [], [], []
+    walls, refined_walls, loss_walls, refined_loss_walls, radial_walls = [], [], [], [], []
     loss_args = {} if loss is None else dict(loss=loss, loss_scale=loss_scale)
     for _ in range(loops + 1):                                        # the first run warms up; the loops alternate
         wall, report, _ = loop()
@@ -194,6 +230,9 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0):
             if refine:
                 wall, refined_robust, robust_cams = loop(**groups, **loss_args)
                 refined_loss_walls.append(wall)
+        if radial:
+            wall, with_k, _ = loop(**radial_args)
+            radial_walls.append(wall)
     out.update(loop_ms=round(float(np.median(walls[1:])), 3), iterations=report["iterations"], accepted_steps=report["accepted_steps"],
                initial_cost=report["initial_cost"], final_cost=report["final_cost"])
     if refine:
@@ -205,6 +244,9 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0):
         if refine:
             out.update(refined_loss_loop_ms=round(float(np.median(refined_loss_walls[1:])), 3), refined_loss_iterations=refined_robust["iterations"],
                        refined_loss_final_cost=refined_robust["final_cost"], refined_loss_focal=float(robust_cams[0, 12]))
+    if radial:
+        out.update(radial_loop_ms=round(float(np.median(radial_walls[1:])), 3), radial_iterations=with_k["iterations"],
+                   radial_final_cost=with_k["final_cost"], radial_k1=float(with_k["cam_dist"][0, 0]))
     return out
 
 
@@ -219,10 +261,13 @@ def main():
     ap.add_argument("--loss", choices=[k for k in bundle.LOSSES if k != "trivial"], default=None,
                     help="also time the entry points that take a loss and the loop under it (DESIGN.md §4.2k, \"The loss\")")
     ap.add_argument("--loss-scale", dest="loss_scale", type=float, default=1.0, metavar="PX")
+    ap.add_argument("--radial", action="store_true",
+                    help="also time the entry points with radial distortion (six unknowns in one group, k1 free from 0) and the loop that "
+                         "refines k1 (DESIGN.md §4.2k, \"The distortion\")")
     args = ap.parse_args()
-    extra = (args.refine_focal, args.loss, args.loss_scale)
+    extra = (args.refine_focal, args.loss, args.loss_scale, args.radial)
     print(json.dumps(dict(tool="bench_bundle", iters=args.iters, loops=args.loops, refine_focal=args.refine_focal, loss=args.loss,
-                          loss_scale=args.loss_scale, windowed=measure(windowed_problem(), args.iters, args.loops, *extra),
+                          loss_scale=args.loss_scale, radial=args.radial, windowed=measure(windowed_problem(), args.iters, args.loops, *extra),
                           arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops, *extra))))
 
 

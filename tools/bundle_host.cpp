@@ -22,6 +22,12 @@
 // loss_scale, every routine that has a loss variant runs it (vc_ba_linearize_points_loss, vc_ba_linearize_intrinsics_loss,
 // vc_ba_reduce_border_loss) and result.bin ends with one more array, float64 obs_w (total).  A loss that the entry point refuses
 // (ba_loss_valid) is refused here: one line on stderr, exit status 3, no result.  Without the extension nothing changes.
+// The distortion ("The distortion" in §4.2k) is a further extension: where problem.bin goes on after loss_scale with int32 1,
+// float64 cam_dist (n_cams, 2), dtheta (n_groups, 6), the routines of the _radial entry points run (the file's dtheta (n_groups, 4)
+// is then not used; VC_BA_LOSS_TRIVIAL, 1.0 is the plain case) and result.bin has the layout above with six unknowns per group:
+// the plain section as it is (its step under dc alone), then with G >= 1 float64 obs_jt (total, 6), T (n_points, G, 18), terms
+// (48 G + 36 G^2, n_points), sums (48 G + 36 G^2), B (6 n_cams, 6 G), C (6 G, 6 G), h (6 G), out_cams, out_points, dx, out_dist
+// (n_cams, 2); uint8 free (6 G), valid (n_cams); then obs_w.  More than VC_BA_MAX_GROUPS_RADIAL groups: exit status 3.
 #include "../vit_colmap_amd/csrc/bundle.hip"
 #include "host_io.h"
 
@@ -61,6 +67,90 @@ static Step take_step(const BaProblem& d, const BaLinear& l, const BaGroups& gr,
   return s;
 }
 
+// The radial extension: every routine under kRadial and the loss (the kernels of the _radial entry points), six unknowns per group.
+static int run_radial(const char* path, const BaProblem& d, const BaGroups& gr, const BaLoss& loss, double lambda, const int32_t* cam_offsets,
+                      const int32_t* cam_obs, const int32_t* obs_point, const double* cam_dist, const double* dc, const double* dtheta) {
+  const int n_cams = d.n_cams, n_points = d.n_points, total = d.total, G = gr.n_groups;
+  std::vector<double> vinv(6 * (size_t)n_points), gp(3 * (size_t)n_points), cost(n_points), total_cost(1, 0.0);
+  std::vector<double> obs_lin((size_t)kBaLin * total), obs_w(total);
+  std::vector<int32_t> count(n_points);
+  std::vector<uint8_t> obs_ok(total);
+  for (int j = 0; j < n_points; ++j) {
+    double v[6], g[3];
+    count[j] = ba_linearize_point<true, true>(d, loss, j, lambda, v, g, cost[j], obs_ok.data(), obs_lin.data(), obs_w.data(), cam_dist);
+    for (int k = 0; k < 6; ++k) vinv[6 * (size_t)j + k] = v[k];
+    for (int k = 0; k < 3; ++k) gp[3 * (size_t)j + k] = g[k];
+    total_cost[0] += cost[j];
+  }
+  const BaLinear l{vinv.data(), gp.data(), obs_ok.data(), obs_lin.data()};
+  std::vector<double> S(36 * (size_t)n_cams * n_cams), g(6 * (size_t)n_cams), acc(36 * (size_t)n_cams);
+  for (int a = 0; a < n_cams; ++a) {
+    BaLane lanes[kBaWave];
+    for (int lane = 0; lane < kBaWave; ++lane) lanes[lane] = BaLane{0.0, 0.0, 0.0};
+    for (double& v : acc) v = 0.0;
+    camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, [&](int lane, int o, int j, int lo, int hi, const double* y) {
+      ba_lane_update(d, l, a, o, j, lo, hi, lane, y, acc.data(), lanes[lane]);
+    });
+    for (int lane = 0; lane < kBaWave; ++lane) ba_lane_finish(n_cams, d.const_mask[a], lambda, a, lane, acc.data(), lanes[lane], S.data(), g.data());
+  }
+  auto take = [&](const BaGroups& groups, const double* T, const double* dth, Step& s, std::vector<double>& dist) {
+    s = Step{std::vector<double>(16 * (size_t)n_cams), std::vector<double>(3 * (size_t)n_points), std::vector<double>(3 * (size_t)n_points),
+             std::vector<uint8_t>(n_cams)};
+    dist.assign(2 * (size_t)n_cams, 0.0);
+    for (int j = 0; j < n_points; ++j) {
+      double dX[3];
+      ba_point_step<6>(d, l, T, groups.n_groups, dc, dth, j, dX);
+      for (int k = 0; k < 3; ++k) s.dx[3 * (size_t)j + k] = dX[k], s.points[3 * (size_t)j + k] = d.points[3 * (size_t)j + k] + dX[k];
+    }
+    for (int a = 0; a < n_cams; ++a)
+      s.valid[a] = ba_camera_step_radial(d.cams + 16 * (size_t)a, cam_dist + 2 * (size_t)a, dc + 6 * (size_t)a, groups, a, dth,
+                                         s.cams.data() + 16 * (size_t)a, dist.data() + 2 * (size_t)a) ? 1 : 0;
+  };
+  Step plain, step;
+  std::vector<double> plain_dist, out_dist;
+  take(BaGroups{nullptr, nullptr, 0}, nullptr, nullptr, plain, plain_dist);
+
+  std::FILE* out = open_output(path);
+  if (!out) return 2;
+  write_all(out, vinv), write_all(out, gp), write_all(out, cost), write_all(out, total_cost), write_all(out, S), write_all(out, g);
+  write_all(out, plain.cams), write_all(out, plain.points), write_all(out, plain.dx), write_all(out, obs_lin), write_all(out, count);
+  write_all(out, obs_ok);
+  if (G >= 1) {
+    const int rows = ba_term_rows<6>(G), m = 6 * G;
+    std::vector<double> obs_jt((size_t)kBaJt * total), T((size_t)n_points * G * 18), terms((size_t)rows * n_points), sums(rows);
+    for (int j = 0; j < n_points; ++j)
+      ba_linearize_point_intrinsics<true, true>(d, l, gr, obs_w.data(), j, obs_jt.data(), T.data(), terms.data(), cam_dist);
+    for (int r = 0; r < rows; ++r) {
+      double sum = 0.0;
+      for (int j = 0; j < n_points; ++j) sum += terms[(size_t)r * n_points + j];
+      sums[r] = sum;
+    }
+    std::vector<double> B(6 * (size_t)n_cams * m), C((size_t)m * m), h(m);
+    std::vector<uint8_t> free_(m);
+    for (int idx = 0; idx < m * m; ++idx) C[idx] = ba_border_c<6>(sums.data(), gr, lambda, idx / m, idx % m);
+    for (int row = 0; row < m; ++row)
+      h[row] = ba_border_h<6>(sums.data(), gr, row), free_[row] = ba_theta_free<6>(sums.data(), gr, row / 6, row % 6) ? 1 : 0;
+    for (int a = 0; a < n_cams; ++a) {
+      BaBorderLane lanes[kBaWave];
+      for (int lane = 0; lane < kBaWave; ++lane)
+        for (int k = 0; k < kBaBorderSlots; ++k) lanes[lane].jt[k] = lanes[lane].yt[k] = 0.0;
+      const int ga = ba_group_of(gr, a);
+      camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, [&](int lane, int o, int j, int, int, const double* y) {
+        ba_border_update<true, true>(l, gr, obs_jt.data(), obs_w.data(), T.data(), ga, o, j, lane, y, lanes[lane]);
+      });
+      for (int lane = 0; lane < kBaWave; ++lane) ba_border_finish<6>(G, a, lane, lanes[lane], B.data());
+    }
+    take(gr, T.data(), dtheta, step, out_dist);
+    write_all(out, obs_jt), write_all(out, T), write_all(out, terms), write_all(out, sums), write_all(out, B), write_all(out, C);
+    write_all(out, h), write_all(out, step.cams), write_all(out, step.points), write_all(out, step.dx), write_all(out, out_dist);
+    write_all(out, free_), write_all(out, step.valid);
+  }
+  write_all(out, obs_w);
+  std::fclose(out);
+  std::printf("%d cameras, %d points, %d observations, %d groups, radial, cost %.17g\n", n_cams, n_points, total, G, total_cost[0]);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   std::FILE* in = open_input(argc, argv, "problem.bin result.bin");
   if (!in) return 2;
@@ -85,8 +175,13 @@ int main(int argc, char** argv) {
   const bool with_loss = ok && std::fread(&loss_kind, sizeof(int32_t), 1, in) == 1;
   const bool loss_read = !with_loss || std::fread(&loss.scale, sizeof(double), 1, in) == 1;
   loss.kind = loss_kind;
+  // the optional distortion after the loss: nothing, or the marker 1 and both of its arrays
+  int32_t radial_mark = 0;
+  const bool with_radial = with_loss && loss_read && std::fread(&radial_mark, sizeof(int32_t), 1, in) == 1;
+  std::vector<double> cam_dist(with_radial ? 2 * (size_t)n_cams : 0), dtheta6(with_radial ? 6 * (size_t)G : 0);
+  const bool radial_read = !with_radial || (radial_mark == 1 && read_all(in, cam_dist) && read_all(in, dtheta6));
   std::fclose(in);
-  if (!ok || !loss_read) {
+  if (!ok || !loss_read || !radial_read) {
     std::fprintf(stderr, "%s: shorter than its header says\n", argv[1]);
     return 2;
   }
@@ -94,9 +189,18 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "%s: loss %d with scale %g is refused\n", argv[1], loss.kind, loss.scale);
     return 3;
   }
+  if (with_radial && G > VC_BA_MAX_GROUPS_RADIAL) {
+    std::fprintf(stderr, "%s: %d groups with the distortion are refused (VC_BA_MAX_GROUPS_RADIAL)\n", argv[1], G);
+    return 3;
+  }
   std::vector<uint8_t> const_mask(n_cams), intr_mask(G);
   for (int a = 0; a < n_cams; ++a) const_mask[a] = (uint8_t)mask32[a];
   for (int g = 0; g < G; ++g) intr_mask[g] = (uint8_t)intr32[g];
+  if (with_radial)
+    return run_radial(argv[2], BaProblem{cams.data(), const_mask.data(), points.data(), offsets.data(), obs_cam.data(), obs_xy.data(), n_cams,
+                                         n_points, total},
+                      BaGroups{cam_group.data(), intr_mask.data(), G}, loss, lambda, cam_offsets.data(), cam_obs.data(), obs_point.data(),
+                      cam_dist.data(), dc.data(), dtheta6.data());
 
   // 1. the points pass and the total cost
   std::vector<double> vinv(6 * (size_t)n_points), gp(3 * (size_t)n_points), cost(n_points), total_cost(1, 0.0);

@@ -6,8 +6,17 @@
 // the caller.  Under a loss (Huber, soft L1: vc_ba_linearize_points_loss, vc_ba_linearize_intrinsics_loss,
 // vc_ba_reduce_border_loss) every observation's J_c, J_p, r and J_theta are multiplied by the square root of its weight before
 // anything is formed from them, and the other three entry points run unchanged on the result; the routines take the loss as a
-// template argument, and without it return the bytes they returned.  Specification: tests/util_bundle.py, tests/util_bundle_intr.py,
-// tests/util_bundle_loss.py.  This build's own published rule; parity with COLMAP / Ceres is unpinned.
+// template argument, and without it return the bytes they returned.  With radial distortion (vc_ba_linearize_points_radial,
+// vc_ba_linearize_intrinsics_radial, vc_ba_reduce_border_radial, vc_ba_step_radial; COLMAP's SIMPLE_RADIAL and RADIAL) the
+// camera's (k1, k2) travel beside its row as cam_dist [n_cams][2] and theta_g = (fx, fy, cx, cy, k1, k2); the routines take the
+// distortion as a second template argument, and without it are what they were.  The order of operations, in full (BaRadial,
+// ba_project_radial, ba_observe): ba_project on the row with fx = fy = 1 gives iu = 1 / Xc_z, (xu, xv) and their Jacobian
+// (nu; nv); rho = xu xu + xv xv, s = 1 + k1 rho + k2 rho rho, e = 2 (k1 + 2 k2 rho), d00 = s + xu xu e, d01 = xu xv e,
+// d11 = s + xv xv e; xd = xu s, yd = xv s, r = (fx xd + cx - u, fy yd + cy - v); J_p = (fx (d00 nu + d01 nv); fy (d01 nu + d11 nv))
+// and J_c the same map of the pinhole rows at fx = fy = 1; pu = fx xu rho, pv = fy xv rho, qu = pu rho, qv = pv rho and J_theta =
+// ((xd, 0, 1, 0, pu, qu); (0, yd, 0, 1, pv, qv)); every product and sum left to right as written.  Specification:
+// tests/util_bundle.py, tests/util_bundle_intr.py, tests/util_bundle_loss.py, tests/util_bundle_radial.py.  This build's own
+// published rule; parity with COLMAP / Ceres is unpinned.
 //
 // float64 in single operations in the written order (-ffp-contract=off), the only library call is sqrt, no atomics.
 //   points pass  one point per lane, one wave per workgroup, no LDS.  ba_linearize_points_kernel: every observation of the point's
@@ -115,12 +124,47 @@ __host__ __device__ __forceinline__ void ba_loss(const BaLoss& loss, double s, d
   }
 }
 
+// The radial distortion of a camera ("The distortion" in DESIGN.md §4.2k): (xu, xv) -> (xu s, xv s), s = 1 + k1 rho + k2 rho rho,
+// rho = xu xu + xv xv.  What an observation needs of it, each in the written order:
+//   s = 1 + k1 rho + k2 rho rho, e = 2 (k1 + 2 k2 rho), the symmetric 2x2 Jacobian D of the map: d00 = s + xu xu e, d01 = xu xv e,
+//   d11 = s + xv xv e, and the six numbers from which the border rebuilds J_theta (obs_jt of the radial entry points):
+//   xd = xu s, yd = xv s, pu = fx xu rho, pv = fy xv rho, qu = pu rho, qv = pv rho.
+struct BaRadial {
+  double d00, d01, d11, jt[6];
+};
+
+// X in the camera of row c[16] under (k1, k2): ba_project on the row with fx = fy = 1, so that iu = 1 / Xc_z and (nu, nv) is the
+// Jacobian of (xu, xv); then J_p = diag(fx, fy) D (nu; nv): ju = fx (d00 nu + d01 nv), jv = fy (d01 nu + d11 nv).
+__host__ __device__ __forceinline__ void ba_project_radial(const double* c, double k1, double k2, const double (&X)[3], double (&Y)[3],
+                                                           double (&Xc)[3], double& iu, double& xu, double& xv, BaRadial& rd,
+                                                           double (&ju)[3], double (&jv)[3]) {
+  double n[16], iv, nu[3], nv[3];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) n[k] = k == 12 || k == 13 ? 1.0 : c[k];
+  ba_project(n, X, Y, Xc, iu, iv, xu, xv, nu, nv);
+  const double fx = c[12], fy = c[13];
+  const double rho = xu * xu + xv * xv;
+  const double s = 1.0 + k1 * rho + k2 * rho * rho;
+  const double e = 2.0 * (k1 + 2.0 * k2 * rho);
+  rd.d00 = s + xu * xu * e, rd.d01 = xu * xv * e, rd.d11 = s + xv * xv * e;
+  rd.jt[0] = xu * s, rd.jt[1] = xv * s, rd.jt[2] = fx * xu * rho, rd.jt[3] = fy * xv * rho;
+  rd.jt[4] = rd.jt[2] * rho, rd.jt[5] = rd.jt[3] * rho;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    ju[k] = fx * (rd.d00 * nu[k] + rd.d01 * nv[k]);
+    jv[k] = fy * (rd.d01 * nu[k] + rd.d11 * nv[k]);
+  }
+}
+
 // Observation o of point X: usable -> lin[32] (zeros otherwise) and J_p (2x3).  With a loss the rows of J_c and J_p and r are
 // multiplied by sw = sqrt(w) before anything is formed from them, and rho is the loss of the unweighted residual, the
-// observation's term of the cost.
-template <bool kLoss>
+// observation's term of the cost.  kRadial: the camera's (k1, k2) of cam_dist [n_cams][2] must be finite too, the projection
+// is ba_project_radial's, r = (fx xd + cx - u, fy yd + cy - v) and J_c = diag(fx, fy) D (the pinhole rows at fx = fy = 1);
+// without it cam_dist is absent and not read.
+template <bool kLoss, bool kRadial = false>
 __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const BaLoss& loss, int o, const double (&X)[3],
-                                                    double* __restrict__ lin, double (&ju)[3], double (&jv)[3], double& rho, double& sw) {
+                                                    double* __restrict__ lin, double (&ju)[3], double (&jv)[3], double& rho, double& sw,
+                                                    const double* __restrict__ cam_dist = nullptr) {
   const int slot = d.obs_cam[o];
   bool ok = slot >= 0 && slot < d.n_cams;
   const double* c = d.cams + (long long)(ok ? slot : 0) * 16;
@@ -134,16 +178,32 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
   ok = ok && ba_finite(u) && ba_finite(v);
   const unsigned held = ok ? d.const_mask[slot] : 0u;
   double Y[3], Xc[3], fu, fv, xu, xv;
-  ba_project(row, X, Y, Xc, fu, fv, xu, xv, ju, jv);
+  BaRadial rd;
+  if (kRadial) {
+    const double k1 = ok ? cam_dist[2 * (long long)slot] : NAN, k2 = ok ? cam_dist[2 * (long long)slot + 1] : NAN;
+    ok = ok && ba_finite(k1) && ba_finite(k2);
+    ba_project_radial(row, k1, k2, X, Y, Xc, fu, xu, xv, rd, ju, jv);
+    fv = fu;                                                 // 1 / Xc_z: the rows of J_c below are then the pinhole ones at fx = fy = 1
+  } else {
+    ba_project(row, X, Y, Xc, fu, fv, xu, xv, ju, jv);
+  }
   const double z = Xc[2];
   ok = ok && z > 0.0;                                        // false for NaN
   const double fx = row[12], fy = row[13], cx = row[14], cy = row[15];
-  double ru = fx * Xc[0] / z + cx - u, rv = fy * Xc[1] / z + cy - v;
+  double ru = kRadial ? fx * rd.jt[0] + cx - u : fx * Xc[0] / z + cx - u, rv = kRadial ? fy * rd.jt[1] + cy - v : fy * Xc[1] / z + cy - v;
   const double au = fu * xu, av = fv * xv;
   // J_c = J_pi [ -[R X]x | I ]: the pose is perturbed on the left, Xc(w, dt) = Rot(w) (R X) + t + dt
   double cu[6] = {-(au * Y[1]), fu * Y[2] + au * Y[0], -(fu * Y[1]), fu, 0.0, -au};
   double cv[6] = {-(fv * Y[2] + av * Y[1]), av * Y[0], fv * Y[0], 0.0, fv, -av};
-  rho = 0.0, sw = 1.0;                                       // without a loss the caller forms |r|^2 itself, as it always did
+  if (kRadial) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      const double mu = cu[i], mv = cv[i];
+      cu[i] = fx * (rd.d00 * mu + rd.d01 * mv);
+      cv[i] = fy * (rd.d01 * mu + rd.d11 * mv);
+    }
+  }
+  rho = 0.0, sw = 1.0;                                      // without a loss the caller forms |r|^2 itself, as it always did
   if (kLoss) {
     double w;
     ba_loss(loss, ru * ru + rv * rv, rho, w);
@@ -171,10 +231,11 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
 
 // One point: its track linearised -> V^-1 (damped, 0 where the point is constant), g_p, cost, the usable count; per
 // observation of the track obs_ok and obs_lin and, with a loss, obs_w: sw of a usable observation, 0 of any other.
-template <bool kLoss>
+template <bool kLoss, bool kRadial = false>
 __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, const BaLoss& loss, int j, double lambda, double (&vinv)[6],
                                                            double (&gp)[3], double& cost, uint8_t* __restrict__ obs_ok,
-                                                           double* __restrict__ obs_lin, double* __restrict__ obs_w) {
+                                                           double* __restrict__ obs_lin, double* __restrict__ obs_w,
+                                                           const double* __restrict__ cam_dist = nullptr) {
 #pragma unroll
   for (int k = 0; k < 6; ++k) vinv[k] = 0.0;
   gp[0] = gp[1] = gp[2] = 0.0;
@@ -186,7 +247,7 @@ __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, c
   for (int o = lo; o < hi; ++o) {
     double* lin = obs_lin + (long long)o * kBaLin;
     double ju[3], jv[3], rho, sw;
-    const bool ok = ba_observe<kLoss>(d, loss, o, X, lin, ju, jv, rho, sw);
+    const bool ok = ba_observe<kLoss, kRadial>(d, loss, o, X, lin, ju, jv, rho, sw, cam_dist);
     obs_ok[o] = ok ? 1 : 0;
     if (kLoss) obs_w[o] = ok ? sw : 0.0;
     if (!ok) continue;
@@ -344,22 +405,31 @@ __host__ __device__ __forceinline__ void ba_pose_step(const double* __restrict__
 // ---- the border of the intrinsics (vc_ba_linearize_intrinsics, vc_ba_reduce_border, vc_ba_step_intrinsics) ----------------------
 // The unknowns theta_g = (fx, fy, cx, cy) of every group of cameras join the reduced system as a border [[S, B], [B', C]];
 // S and g stay vc_ba_reduce_cameras'.
+// With the distortion (the _radial entry points) theta_g = (fx, fy, cx, cy, k1, k2): the same routines with N = 6 unknowns per
+// group where they have N = 4 without it.
 constexpr int kBaT = 12;                                                      // T_{j,g} = sum J_theta' J_p, 4x3 row-major
 constexpr int kBaBorderSlots = (24 * VC_BA_MAX_GROUPS + kBaWave - 1) / kBaWave;   // entries of a camera's B row block per lane
+static_assert((36 * VC_BA_MAX_GROUPS_RADIAL + kBaWave - 1) / kBaWave <= kBaBorderSlots, "B_a [6][6 G] of the radial limit must fit a lane's slots");
+constexpr int kBaJt = 6;                                                      // obs_jt: xd, yd, pu, pv, qu, qv (BaRadial)
 
 struct BaGroups {
   const int32_t* __restrict__ cam_group;       // [n_cams]
-  const uint8_t* __restrict__ intr_mask;       // [n_groups]: bits 0-3 fx fy cx cy held, bit 4 fx and fy tied
+  const uint8_t* __restrict__ intr_mask;       // [n_groups]: bits 0-3 fx fy cx cy held, bit 4 fx and fy tied; radial: bits 5, 6 k1, k2 held
   int n_groups;
 };
 
 // The rows of the per-point terms [ba_term_rows(G)][n_points] (entry-major: a point per lane writes a row and a wave per row
-// reads it, both coalesced): q_{j,g} 4x4, hq_{j,g}, p_{j,g} = T V^-1 g_p, P_{j,g,g'} = T_g V^-1 T_g'' 4x4.
-__host__ __device__ constexpr int ba_term_q(int G, int g) { return 16 * g; }
-__host__ __device__ constexpr int ba_term_hq(int G, int g) { return 16 * G + 4 * g; }
-__host__ __device__ constexpr int ba_term_p(int G, int g) { return 20 * G + 4 * g; }
-__host__ __device__ constexpr int ba_term_P(int G, int g, int g2) { return 24 * G + 16 * (g * G + g2); }
-__host__ __device__ constexpr int ba_term_rows(int G) { return 24 * G + 16 * G * G; }
+// reads it, both coalesced): q_{j,g} NxN, hq_{j,g}, p_{j,g} = T V^-1 g_p, P_{j,g,g'} = T_g V^-1 T_g'' NxN.
+template <int N = 4>
+__host__ __device__ constexpr int ba_term_q(int G, int g) { return N * N * g; }
+template <int N = 4>
+__host__ __device__ constexpr int ba_term_hq(int G, int g) { return N * N * G + N * g; }
+template <int N = 4>
+__host__ __device__ constexpr int ba_term_p(int G, int g) { return (N * N + N) * G + N * g; }
+template <int N = 4>
+__host__ __device__ constexpr int ba_term_P(int G, int g, int g2) { return (N * N + 2 * N) * G + N * N * (g * G + g2); }
+template <int N = 4>
+__host__ __device__ constexpr int ba_term_rows(int G) { return (N * N + 2 * N) * G + N * N * G * G; }
 
 // Camera slot -> its group, -1 where the slot's group is outside [0, n_groups): its intrinsics are held.  Without groups
 // cam_group is not read.
@@ -379,6 +449,23 @@ __host__ __device__ __forceinline__ void ba_jtheta(unsigned mask, double x, doub
   if (ba_theta_held(mask, i)) tu = tv = 0.0;
 }
 
+// The six unknowns: parameter i < 4 as above; k1 (i = 4) is held by bit 5 of the mask, k2 (i = 5) by bit 6.
+__host__ __device__ __forceinline__ bool ba_theta_held_radial(unsigned mask, int i) {
+  return i < 4 ? ba_theta_held(mask, i) : ((mask >> (i + 1)) & 1u) != 0;
+}
+
+template <int N>
+__host__ __device__ __forceinline__ bool ba_held(unsigned mask, int i) { return N == 6 ? ba_theta_held_radial(mask, i) : ba_theta_held(mask, i); }
+
+// Column i of J_theta = [[xd, 0, 1, 0, pu, qu], [0, yd, 0, 1, pv, qv]] from jt = (xd, yd, pu, pv, qu, qv); tied: column 0 is
+// (xd, yd); a held column is 0.  i may be a runtime value: the column is selected, not indexed.
+__host__ __device__ __forceinline__ void ba_jtheta_radial(unsigned mask, const double* jt, int i, double& tu, double& tv) {
+  const bool tied = (mask >> 4) & 1u;
+  tu = i == 0 ? jt[0] : i == 2 ? 1.0 : i == 4 ? jt[2] : i == 5 ? jt[4] : 0.0;
+  tv = i == 0 ? (tied ? jt[1] : 0.0) : i == 1 ? jt[1] : i == 3 ? 1.0 : i == 4 ? jt[3] : i == 5 ? jt[5] : 0.0;
+  if (ba_theta_held_radial(mask, i)) tu = tv = 0.0;
+}
+
 // A usable observation of X in camera row c again: x = Xc_x / Xc_z, y = Xc_y / Xc_z and J_p.
 __host__ __device__ __forceinline__ void ba_observe_point(const double* __restrict__ c, const double (&X)[3], double& xu, double& xv,
                                                           double (&ju)[3], double (&jv)[3]) {
@@ -389,11 +476,14 @@ __host__ __device__ __forceinline__ void ba_observe_point(const double* __restri
 // One point: obs_xn of its track; per group (outside) over the track (inside) T, q, hq; then the point's products with V^-1.
 // A point whose offsets delimit nothing has T and its terms 0 and nothing of its track read or written.  With a loss J_p and
 // J_theta (its constant columns too) are multiplied by obs_w[o], as the points pass multiplied what it left in obs_lin; obs_xn
-// stays the unscaled (x, y).
-template <bool kLoss>
+// stays the unscaled (x, y).  kRadial: N = 6 unknowns per group, the observation is ba_project_radial's under cam_dist, and
+// obs_xn is obs_jt [total][6], the unscaled (xd, yd, pu, pv, qu, qv) of a usable observation and zeros of any other.
+template <bool kLoss, bool kRadial = false>
 __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaProblem& d, const BaLinear& l, const BaGroups& gr,
                                                                        const double* __restrict__ obs_w, int j, double* __restrict__ obs_xn,
-                                                                       double* T, double* __restrict__ terms) {
+                                                                       double* T, double* __restrict__ terms,
+                                                                       const double* __restrict__ cam_dist = nullptr) {
+  constexpr int N = kRadial ? 6 : 4, NT = kRadial ? 3 * N : kBaT;
   const int G = gr.n_groups;
   const long long n = d.n_points;
   int lo, hi;
@@ -402,95 +492,121 @@ __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaP
   if (lo < hi) X[0] = d.points[3 * (long long)j], X[1] = d.points[3 * (long long)j + 1], X[2] = d.points[3 * (long long)j + 2];
   for (int o = lo; o < hi; ++o) {
     const int slot = d.obs_cam[o];
-    double x = 0.0, y = 0.0, ju[3], jv[3];
-    if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
-    obs_xn[2 * (long long)o] = x, obs_xn[2 * (long long)o + 1] = y;
+    if (kRadial) {
+      BaRadial rd;
+#pragma unroll
+      for (int k = 0; k < kBaJt; ++k) rd.jt[k] = 0.0;
+      if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) {
+        double Y[3], Xc[3], iu, xu, xv, ju[3], jv[3];
+        ba_project_radial(d.cams + 16 * (long long)slot, cam_dist[2 * (long long)slot], cam_dist[2 * (long long)slot + 1], X, Y, Xc, iu, xu, xv,
+                          rd, ju, jv);
+      }
+#pragma unroll
+      for (int k = 0; k < kBaJt; ++k) obs_xn[kBaJt * (long long)o + k] = rd.jt[k];
+    } else {
+      double x = 0.0, y = 0.0, ju[3], jv[3];
+      if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
+      obs_xn[2 * (long long)o] = x, obs_xn[2 * (long long)o + 1] = y;
+    }
   }
-  double* Tj = T + (long long)j * G * kBaT;
+  double* Tj = T + (long long)j * G * NT;
   for (int g = 0; g < G; ++g) {
     const unsigned mask = gr.intr_mask[g];
-    double t[kBaT], q[16], hq[4];
+    double t[NT], q[N * N], hq[N];
 #pragma unroll
-    for (int k = 0; k < kBaT; ++k) t[k] = 0.0;
+    for (int k = 0; k < NT; ++k) t[k] = 0.0;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) q[k] = 0.0;
+    for (int k = 0; k < N * N; ++k) q[k] = 0.0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) hq[k] = 0.0;
+    for (int k = 0; k < N; ++k) hq[k] = 0.0;
     for (int o = lo; o < hi; ++o) {
       const int slot = d.obs_cam[o];
       if (!l.obs_ok[o] || slot < 0 || slot >= d.n_cams || ba_group_of(gr, slot) != g) continue;
-      double x, y, ju[3], jv[3], tu[4], tv[4];
-      ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
+      double ju[3], jv[3], tu[N], tv[N];
+      if (kRadial) {
+        BaRadial rd;
+        double Y[3], Xc[3], iu, xu, xv;
+        ba_project_radial(d.cams + 16 * (long long)slot, cam_dist[2 * (long long)slot], cam_dist[2 * (long long)slot + 1], X, Y, Xc, iu, xu, xv,
+                          rd, ju, jv);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) ba_jtheta(mask, x, y, i, tu[i], tv[i]);
+        for (int i = 0; i < N; ++i) ba_jtheta_radial(mask, rd.jt, i, tu[i], tv[i]);
+      } else {
+        double x, y;
+        ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
+#pragma unroll
+        for (int i = 0; i < N; ++i) ba_jtheta(mask, x, y, i, tu[i], tv[i]);
+      }
       if (kLoss) {
         const double sw = obs_w[o];
 #pragma unroll
         for (int k = 0; k < 3; ++k) ju[k] = sw * ju[k], jv[k] = sw * jv[k];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) tu[i] = sw * tu[i], tv[i] = sw * tv[i];
+        for (int i = 0; i < N; ++i) tu[i] = sw * tu[i], tv[i] = sw * tv[i];
       }
       const double ru = l.obs_lin[(long long)o * kBaLin + kBaLinR], rv = l.obs_lin[(long long)o * kBaLin + kBaLinR + 1];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
+      for (int i = 0; i < N; ++i) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) t[3 * i + k] += tu[i] * ju[k] + tv[i] * jv[k];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) q[4 * i + k] += tu[i] * tu[k] + tv[i] * tv[k];
+        for (int k = 0; k < N; ++k) q[N * i + k] += tu[i] * tu[k] + tv[i] * tv[k];
         hq[i] += tu[i] * ru + tv[i] * rv;
       }
     }
 #pragma unroll
-    for (int k = 0; k < kBaT; ++k) Tj[g * kBaT + k] = t[k];
+    for (int k = 0; k < NT; ++k) Tj[g * NT + k] = t[k];
 #pragma unroll
-    for (int k = 0; k < 16; ++k) terms[(ba_term_q(G, g) + k) * n + j] = q[k];
+    for (int k = 0; k < N * N; ++k) terms[(ba_term_q<N>(G, g) + k) * n + j] = q[k];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) terms[(ba_term_hq(G, g) + k) * n + j] = hq[k];
+    for (int k = 0; k < N; ++k) terms[(ba_term_hq<N>(G, g) + k) * n + j] = hq[k];
   }
   const double* v = l.vinv + (long long)j * 6;
   const double v00 = v[0], v01 = v[1], v02 = v[2], v11 = v[3], v12 = v[4], v22 = v[5];
   const double g0 = l.gp[3 * (long long)j], g1 = l.gp[3 * (long long)j + 1], g2 = l.gp[3 * (long long)j + 2];
   for (int g = 0; g < G; ++g) {
-    double tv[kBaT];                                                          // T_g V^-1, as Y = W V^-1 is formed
+    double tv[NT];                                                            // T_g V^-1, as Y = W V^-1 is formed
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const double t0 = Tj[g * kBaT + 3 * i], t1 = Tj[g * kBaT + 3 * i + 1], t2 = Tj[g * kBaT + 3 * i + 2];
+    for (int i = 0; i < N; ++i) {
+      const double t0 = Tj[g * NT + 3 * i], t1 = Tj[g * NT + 3 * i + 1], t2 = Tj[g * NT + 3 * i + 2];
       tv[3 * i] = t0 * v00 + t1 * v01 + t2 * v02;
       tv[3 * i + 1] = t0 * v01 + t1 * v11 + t2 * v12;
       tv[3 * i + 2] = t0 * v02 + t1 * v12 + t2 * v22;
-      terms[(ba_term_p(G, g) + i) * n + j] = tv[3 * i] * g0 + tv[3 * i + 1] * g1 + tv[3 * i + 2] * g2;
+      terms[(ba_term_p<N>(G, g) + i) * n + j] = tv[3 * i] * g0 + tv[3 * i + 1] * g1 + tv[3 * i + 2] * g2;
     }
     for (int h = 0; h < G; ++h) {
-      const double* th = Tj + h * kBaT;
+      const double* th = Tj + h * NT;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < N; ++i)
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          terms[(ba_term_P(G, g, h) + 4 * i + k) * n + j] = tv[3 * i] * th[3 * k] + tv[3 * i + 1] * th[3 * k + 1] + tv[3 * i + 2] * th[3 * k + 2];
+        for (int k = 0; k < N; ++k)
+          terms[(ba_term_P<N>(G, g, h) + N * i + k) * n + j] = tv[3 * i] * th[3 * k] + tv[3 * i + 1] * th[3 * k + 1] + tv[3 * i + 2] * th[3 * k + 2];
     }
   }
 }
 
 // Parameter i of group g moves: not held, not parameter 1 of a tied group, and some usable observation moves it (Q_ii != 0).
+template <int N = 4>
 __host__ __device__ __forceinline__ bool ba_theta_free(const double* __restrict__ sums, const BaGroups& gr, int g, int i) {
-  return !ba_theta_held(gr.intr_mask[g], i) && sums[ba_term_q(gr.n_groups, g) + 5 * i] != 0.0;
+  return !ba_held<N>(gr.intr_mask[g], i) && sums[ba_term_q<N>(gr.n_groups, g) + (N + 1) * i] != 0.0;
 }
 
 // Entry (row, col) of C from the ordered sums: delta Q (its diagonal damped) - sum P; the identity where a parameter does not move.
+template <int N = 4>
 __host__ __device__ __forceinline__ double ba_border_c(const double* __restrict__ sums, const BaGroups& gr, double lambda, int row, int col) {
-  const int G = gr.n_groups, g = row / 4, i = row % 4, h = col / 4, k = col % 4;
-  if (!ba_theta_free(sums, gr, g, i) || !ba_theta_free(sums, gr, h, k)) return row == col ? 1.0 : 0.0;
+  const int G = gr.n_groups, g = row / N, i = row % N, h = col / N, k = col % N;
+  if (!ba_theta_free<N>(sums, gr, g, i) || !ba_theta_free<N>(sums, gr, h, k)) return row == col ? 1.0 : 0.0;
   double q = 0.0;
   if (g == h) {
-    q = sums[ba_term_q(G, g) + 4 * i + k];
+    q = sums[ba_term_q<N>(G, g) + N * i + k];
     if (i == k) q += lambda * q;
   }
-  return q - sums[ba_term_P(G, g, h) + 4 * i + k];
+  return q - sums[ba_term_P<N>(G, g, h) + N * i + k];
 }
 
+template <int N = 4>
 __host__ __device__ __forceinline__ double ba_border_h(const double* __restrict__ sums, const BaGroups& gr, int row) {
-  const int G = gr.n_groups, g = row / 4, i = row % 4;
-  return ba_theta_free(sums, gr, g, i) ? sums[ba_term_hq(G, g) + i] - sums[ba_term_p(G, g) + i] : 0.0;
+  const int G = gr.n_groups, g = row / N, i = row % N;
+  return ba_theta_free<N>(sums, gr, g, i) ? sums[ba_term_hq<N>(G, g) + i] - sums[ba_term_p<N>(G, g) + i] : 0.0;
 }
 
 // The registers of one lane of the border's camera pass: entry idx = lane + 64 k of the row block B_a [6][4 G], as g = idx / 24,
@@ -501,41 +617,52 @@ struct BaBorderLane {
 
 // One lane's additions for the usable observation o of camera a (its group ga or -1, its point j, y as ba_prepare left it).
 // With a loss the column of J_theta is multiplied by obs_w[o]; obs_lin and T carry the weight already.
-template <bool kLoss>
+// kRadial: the row block is B_a [6][6 G], entry idx as g = idx / 36, r = idx % 36 / 6, i = idx % 6, and obs_xn is obs_jt.
+template <bool kLoss, bool kRadial = false>
 __host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, const BaGroups& gr, const double* __restrict__ obs_xn,
                                                           const double* __restrict__ obs_w, const double* __restrict__ T, int ga, int o,
                                                           int j, int lane, const double* y, BaBorderLane& s) {
+  constexpr int N = kRadial ? 6 : 4;
   const int G = gr.n_groups;
   const double sw = kLoss ? obs_w[o] : 1.0;
   const double* lin = l.obs_lin + (long long)o * kBaLin;
   const unsigned mask = ga >= 0 ? gr.intr_mask[ga] : 0u;
-  const double x = obs_xn[2 * (long long)o], yn = obs_xn[2 * (long long)o + 1];
+  double jt[kBaJt];
+  if (kRadial) {
+#pragma unroll
+    for (int k = 0; k < kBaJt; ++k) jt[k] = obs_xn[kBaJt * (long long)o + k];
+  } else {
+    jt[0] = obs_xn[2 * (long long)o], jt[1] = obs_xn[2 * (long long)o + 1];
+  }
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) {
     const int idx = lane + kBaWave * k;
-    if (idx >= 24 * G) continue;
-    const int g = idx / 24, r = idx % 24 / 4, i = idx % 4;
+    if (idx >= 6 * N * G) continue;
+    const int g = idx / (6 * N), r = idx % (6 * N) / N, i = idx % N;
     if (g == ga) {
       double tu, tv;
-      ba_jtheta(mask, x, yn, i, tu, tv);
+      if (kRadial) ba_jtheta_radial(mask, jt, i, tu, tv);
+      else ba_jtheta(mask, jt[0], jt[1], i, tu, tv);
       if (kLoss) tu = sw * tu, tv = sw * tv;
       s.jt[k] += lin[r] * tu + lin[6 + r] * tv;
     }
-    const double* t = T + ((long long)j * G + g) * kBaT + 3 * i;
+    const double* t = T + ((long long)j * G + g) * (3 * N) + 3 * i;
     s.yt[k] += y[3 * r] * t[0] + y[3 * r + 1] * t[1] + y[3 * r + 2] * t[2];
   }
 }
 
+template <int N = 4>
 __host__ __device__ __forceinline__ void ba_border_finish(int G, int a, int lane, const BaBorderLane& s, double* __restrict__ B) {
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) {
     const int idx = lane + kBaWave * k;
-    if (idx < 24 * G) B[(long long)(6 * a + idx % 24 / 4) * (4 * G) + 4 * (idx / 24) + idx % 4] = s.jt[k] - s.yt[k];
+    if (idx < 6 * N * G) B[(long long)(6 * a + idx % (6 * N) / N) * (N * G) + N * (idx / (6 * N)) + idx % N] = s.jt[k] - s.yt[k];
   }
 }
 
 // One point's step: dX = -V^-1 (g_p + sum W' dc + sum_g T_g' dtheta_g), the track in track order, then the groups in ascending
 // order; 0 where the point's offsets delimit nothing.  Without groups T and dtheta are not read.
+template <int N = 4>
 __host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const BaLinear& l, const double* __restrict__ T, int G,
                                                        const double* __restrict__ dc, const double* __restrict__ dtheta, int j,
                                                        double (&dX)[3]) {
@@ -554,10 +681,13 @@ __host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const
       s[k] += w[k] * e[0] + w[3 + k] * e[1] + w[6 + k] * e[2] + w[9 + k] * e[3] + w[12 + k] * e[4] + w[15 + k] * e[5];
   }
   for (int g = 0; g < G; ++g) {
-    const double* t = T + ((long long)j * G + g) * kBaT;
-    const double* e = dtheta + 4 * g;
+    const double* t = T + ((long long)j * G + g) * (3 * N);
+    const double* e = dtheta + N * g;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3];
+    for (int k = 0; k < 3; ++k) {
+      if (N == 6) s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3] + t[12 + k] * e[4] + t[15 + k] * e[5];
+      else s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3];
+    }
   }
   const double* v = l.vinv + (long long)j * 6;
   dX[0] = -(v[0] * s[0] + v[1] * s[1] + v[2] * s[2]);
@@ -577,6 +707,25 @@ __host__ __device__ __forceinline__ bool ba_camera_step(const double* __restrict
   const double fx = cam[12] + th[0], fy = cam[13] + (tied ? th[0] : th[1]);
   out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
   return ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0;
+}
+
+// The same with six unknowns per group: (k1, k2) of dist[2] += dtheta_4, dtheta_5 into out_dist[2] (copied where the intrinsics
+// are held) -> focal lengths finite and positive, k1 and k2 finite.
+__host__ __device__ __forceinline__ bool ba_camera_step_radial(const double* __restrict__ cam, const double* __restrict__ dist,
+                                                               const double* __restrict__ e, const BaGroups& gr, int a,
+                                                               const double* __restrict__ dtheta, double* __restrict__ out,
+                                                               double* __restrict__ out_dist) {
+  ba_pose_step(cam, e, out);
+  out_dist[0] = dist[0], out_dist[1] = dist[1];
+  const int g = ba_group_of(gr, a);
+  if (g < 0) return true;
+  const double* th = dtheta + 6 * g;
+  const bool tied = (gr.intr_mask[g] >> 4) & 1u;
+  const double fx = cam[12] + th[0], fy = cam[13] + (tied ? th[0] : th[1]);
+  const double k1 = dist[0] + th[4], k2 = dist[1] + th[5];
+  out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
+  out_dist[0] = k1, out_dist[1] = k2;
+  return ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0 && ba_finite(k1) && ba_finite(k2);
 }
 
 // kLoss = false: loss and out_obs_w are absent and not read (vc_ba_linearize_points).  What a loss adds comes last in the three
@@ -686,6 +835,83 @@ __global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(const double* 
   if (a >= n_cams) return;
   const bool valid = ba_camera_step(cams + 16 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a);
   if (out_valid) out_valid[a] = valid ? 1 : 0;
+}
+
+// ---- the kernels of the _radial entry points: the routines above under kRadial, every one with the loss (VC_BA_LOSS_TRIVIAL
+// gives rho = s and sw = 1, and a product with 1.0 is exact) ------------------------------------------------------------------------
+__global__ __launch_bounds__(kBaWave) void ba_linearize_points_radial_kernel(BaProblem d, const double* __restrict__ cam_dist, double lambda,
+                                                                             BaLoss loss, double* __restrict__ out_vinv,
+                                                                             double* __restrict__ out_gp, double* __restrict__ out_cost,
+                                                                             int32_t* __restrict__ out_count, uint8_t* __restrict__ out_obs_ok,
+                                                                             double* __restrict__ out_obs_lin, double* __restrict__ out_obs_w) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j >= d.n_points) return;
+  double vinv[6], gp[3], cost;
+  const int count = ba_linearize_point<true, true>(d, loss, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin, out_obs_w, cam_dist);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) out_vinv[6 * j + k] = vinv[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out_gp[3 * j + k] = gp[k];
+  out_cost[j] = cost;
+  out_count[j] = count;
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_radial_kernel(BaProblem d, BaLinear l, BaGroups gr,
+                                                                                 const double* __restrict__ cam_dist,
+                                                                                 const double* __restrict__ obs_w, double* __restrict__ out_obs_jt,
+                                                                                 double* out_T, double* __restrict__ out_terms) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j < d.n_points) ba_linearize_point_intrinsics<true, true>(d, l, gr, obs_w, (int)j, out_obs_jt, out_T, out_terms, cam_dist);
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_border_system_radial_kernel(const double* __restrict__ sums, BaGroups gr, double lambda,
+                                                                          double* __restrict__ out_C, double* __restrict__ out_h,
+                                                                          uint8_t* __restrict__ out_free) {
+  const int m = 6 * gr.n_groups;
+  for (int idx = threadIdx.x; idx < m * m; idx += kBaWave) out_C[idx] = ba_border_c<6>(sums, gr, lambda, idx / m, idx % m);
+  for (int row = threadIdx.x; row < m; row += kBaWave) {
+    out_h[row] = ba_border_h<6>(sums, gr, row);
+    out_free[row] = ba_theta_free<6>(sums, gr, row / 6, row % 6) ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_reduce_border_radial_kernel(BaProblem d, BaLinear l, BaGroups gr,
+                                                                          const int32_t* __restrict__ cam_offsets,
+                                                                          const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
+                                                                          const double* __restrict__ obs_jt, const double* __restrict__ obs_w,
+                                                                          const double* __restrict__ T, double* __restrict__ out_B) {
+  __shared__ BaBatch batch;
+  const int a = blockIdx.x, lane = threadIdx.x;
+  const int ga = ba_group_of(gr, a);
+  BaBorderLane s;
+#pragma unroll
+  for (int k = 0; k < kBaBorderSlots; ++k) s.jt[k] = s.yt[k] = 0.0;
+  ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
+                 [&](int o, int j, int, int, const double* y) { ba_border_update<true, true>(l, gr, obs_jt, obs_w, T, ga, o, j, lane, y, s); });
+  ba_border_finish<6>(gr.n_groups, a, lane, s, out_B);
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_step_points_radial_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
+                                                                        const double* __restrict__ dc, const double* __restrict__ dtheta,
+                                                                        double* __restrict__ out_points, double* __restrict__ out_dx) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j >= d.n_points) return;
+  double dX[3];
+  ba_point_step<6>(d, l, T, n_groups, dc, dtheta, (int)j, dX);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    out_dx[3 * j + k] = dX[k];
+    out_points[3 * j + k] = d.points[3 * j + k] + dX[k];
+  }
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_step_cameras_radial_kernel(const double* __restrict__ cams, const double* __restrict__ cam_dist,
+                                                                         int n_cams, BaGroups gr, const double* __restrict__ dc,
+                                                                         const double* __restrict__ dtheta, double* __restrict__ out_cams,
+                                                                         double* __restrict__ out_dist, uint8_t* __restrict__ out_valid) {
+  const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (a >= n_cams) return;
+  out_valid[a] = ba_camera_step_radial(cams + 16 * a, cam_dist + 2 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a, out_dist + 2 * a) ? 1 : 0;
 }
 
 // The two kernels of a step; vc_ba_step has no groups: then T, dtheta, cam_group and out_valid are absent and none is read.
@@ -869,6 +1095,94 @@ int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_gro
   if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
   return ba_launch_step(BaProblem{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total}, BaLinear{vinv, gp, obs_ok, obs_lin},
                         BaGroups{cam_group, intr_mask, n_groups}, T, dc, dtheta, out_cams, out_points, out_dx, out_valid, stream);
+}
+
+// ---- the distortion: the checks of the entry points above, cam_dist and the loss among them ---------------------------------------
+int vc_ba_linearize_points_radial(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
+                                  int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                                  int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
+                                  uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
+  if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (n_points == 0) return VC_OK;
+  if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_dist || !const_mask)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin || !out_obs_w)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_linearize_points_radial_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, cam_dist, lambda, BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok,
+                     out_obs_lin, out_obs_w);
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
+  return vc::check_launch();
+}
+
+int vc_ba_linearize_intrinsics_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
+                                      const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets,
+                                      const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
+                                      const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
+                                      double* out_terms, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (n_points == 0 || n_groups == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS_RADIAL) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_dist || !cam_group)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !obs_w || !out_obs_jt)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_linearize_intrinsics_radial_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, cam_dist, obs_w,
+                     out_obs_jt, out_T, out_terms);
+  return vc::check_launch();
+}
+
+int vc_ba_reduce_border_radial(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
+                               const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs,
+                               const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
+                               const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
+                               double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (n_groups == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS_RADIAL || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_jt || !obs_w)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaGroups gr{cam_group, intr_mask, n_groups};
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows<6>(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
+                     out_sums);
+  hipLaunchKernelGGL(ba_border_system_radial_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h,
+                     out_free);
+  if (n_cams > 0) {
+    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
+    hipLaunchKernelGGL(ba_reduce_border_radial_kernel, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
+                       BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_jt, obs_w, T, out_B);
+  }
+  return vc::check_launch();
+}
+
+int vc_ba_step_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                      const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
+                      const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
+                      double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_cams == 0 && n_points == 0) return VC_OK;
+  if (n_groups > VC_BA_MAX_GROUPS_RADIAL) return VC_ERR_UNSUPPORTED;
+  if (n_groups > 0 && (!intr_mask || !dtheta)) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_dist || !cam_group || !dc || !out_cams || !out_dist || !out_valid)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx || (n_groups > 0 && !T))) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  const BaGroups gr{cam_group, intr_mask, n_groups};
+  if (n_points > 0)
+    hipLaunchKernelGGL(ba_step_points_radial_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       d, BaLinear{vinv, gp, obs_ok, obs_lin}, T, n_groups, dc, dtheta, out_points, out_dx);
+  if (n_cams > 0)
+    hipLaunchKernelGGL(ba_step_cameras_radial_kernel, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       cams, cam_dist, n_cams, gr, dc, dtheta, out_cams, out_dist, out_valid);
+  return vc::check_launch();
 }
 
 }  // extern "C"

@@ -6,9 +6,12 @@ With `refine_focal_length` the adjustment also refines the focal length(s) of ev
 camera_id, a border of the reduced system, which mapping/bundle_intr.py, imported only then, supplies to the one loop here;
 specification: tests/util_bundle_intr.py).  With `loss` "huber" or "soft_l1" the adjustment is iteratively reweighted
 Gauss-Newton under that loss ("The loss" in §4.2k; specification: tests/util_bundle_loss.py): the same loop on
-vc_ba_linearize_points_loss, whose outputs the other kernels take as they are.  Still missing on the way to a mapper: adjustment
-per round and local adjustment, re-triangulation, merging of points, the principal point and distortion among the refined
-intrinsics.
+vc_ba_linearize_points_loss, whose outputs the other kernels take as they are.  With `refine_distortion` it also refines the radial
+distortion of SIMPLE_RADIAL (k1) and RADIAL (k1, k2) cameras from the values their params carry ("The distortion" in §4.2k;
+specification: tests/util_bundle_radial.py): the same loop on the _radial entry points, six unknowns per group in the border.
+Still missing on the way to a mapper: adjustment per round and local adjustment, re-triangulation, merging of points; among the
+intrinsics a known non-zero distortion into the solvers (undistorted points in front of E, P3P and triangulation), OPENCV's
+tangential terms and the principal point from the command line.
 
 Where the work runs
   HIP     per iteration vc_ba_linearize_points (one point per lane: residuals, Jacobians, V^-1, the cost), vc_ba_reduce_cameras
@@ -66,7 +69,7 @@ class _Buffers:
     """The outputs of one vc_ba_linearize_points call (with a loss: of vc_ba_linearize_points_loss, obs_w among them); two of
     them alternate between the current parameters and the candidate."""
 
-    def __init__(self, torch, n_cams, n_points, total, device, with_loss=False):
+    def __init__(self, torch, n_cams, n_points, total, device, with_loss=False, with_dist=False):
         f64 = dict(dtype=torch.float64, device=device)
         self.cams, self.points = torch.zeros((n_cams, 16), **f64), torch.zeros((n_points, 3), **f64)
         self.vinv, self.gp, self.cost = torch.zeros((n_points, 6), **f64), torch.zeros((n_points, 3), **f64), torch.zeros(n_points, **f64)
@@ -74,8 +77,10 @@ class _Buffers:
         self.obs_ok = torch.zeros(total, dtype=torch.uint8, device=device)
         self.obs_lin = torch.zeros((total, 32), **f64)
         self.total_cost = torch.zeros(1, **f64)
-        if with_loss:
+        if with_loss or with_dist:
             self.obs_w = torch.zeros(total, **f64)
+        if with_dist:
+            self.dist = torch.zeros((n_cams, 2), **f64)              # (k1, k2) beside the camera rows (the _radial entry points)
 
 
 def check_loss(loss, loss_scale):
@@ -93,7 +98,7 @@ def check_loss(loss, loss_scale):
 
 
 def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cuda", max_iterations=BA_MAX_ITERATIONS, cam_group=None,
-                  intr_mask=None, loss="trivial", loss_scale=1.0):
+                  intr_mask=None, loss="trivial", loss_scale=1.0, cam_dist=None):
     """cams float64 (n_cams, 16) as vc_triangulate_tracks has them, points float64 (n_points, 3), offsets int32 (n_points + 1,),
     obs_cam int32 (total,), obs_xy float64 (total, 2), const_mask uint8 (n_cams,) (bit i: pose parameter i is held), numpy
     -> cams, points (numpy, adjusted) and the report dict(iterations, accepted_steps, initial_cost, final_cost, final_lambda,
@@ -105,7 +110,12 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     loss "trivial", "huber" or "soft_l1" with loss_scale in px ("The loss" in §4.2k): with "trivial" exactly today's calls;
     otherwise vc_ba_linearize_points_loss and, with groups, the border's _loss entry points; the costs of the report are the
     robust ones.  The report carries loss and loss_scale.  Raises ValueError for an unknown loss or a scale that is not finite
-    and positive."""
+    and positive.
+    cam_dist float64 (n_cams, 2): (k1, k2) of every slot ("The distortion" in §4.2k; COLMAP's SIMPLE_RADIAL and RADIAL).  The same
+    loop then runs the _radial entry points, with any loss; bits 5 and 6 of a group's mask hold k1 and k2; without groups every
+    slot is in one group whose six intrinsics are all held.  The report gains `cam_dist`, the adjusted (n_cams, 2), and its
+    `intrinsics` are (n_groups, 6): (fx, fy, cx, cy, k1, k2).  Raises ValueError above VC_BA_MAX_GROUPS_RADIAL groups.  Without
+    cam_dist exactly the calls and the report described above."""
     import torch
 
     from .. import _lib
@@ -121,16 +131,25 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     if offsets.shape != (n_points + 1,) or obs_xy.shape != (total, 2) or const_mask.shape != (n_cams,):
         raise ValueError("bundle_adjust needs offsets (n_points + 1,), obs_cam (total,), obs_xy (total, 2), const_mask (n_cams,)")
     border = None
+    radial = cam_dist is not None
+    if radial:
+        cam_dist = np.ascontiguousarray(cam_dist, np.float64)
+        if cam_dist.shape != (n_cams, 2):
+            raise ValueError("bundle_adjust needs cam_dist (n_cams, 2): k1, k2 of every camera slot")
+        if cam_group is None and intr_mask is None:
+            from .bundle_intr import HOLD_ALL_RADIAL
+
+            cam_group, intr_mask = np.zeros(n_cams, np.int32), np.array([HOLD_ALL_RADIAL], np.uint8)
     if cam_group is not None or intr_mask is not None:
         if cam_group is None or intr_mask is None:
             raise ValueError("bundle_adjust needs cam_group and intr_mask together")
         from .bundle_intr import Border
 
-        border = Border(cams, cam_group, intr_mask, with_loss=loss_kind != 0)
+        border = Border(cams, cam_group, intr_mask, with_loss=loss_kind != 0, cam_dist=cam_dist, loss=(loss_kind, loss_scale))
     report = dict(iterations=0, accepted_steps=0, initial_cost=0.0, final_cost=0.0, final_lambda=BA_LAMBDA0, decisions=[], loss=loss,
                   loss_scale=loss_scale)
     if n_cams == 0 or n_points == 0:
-        return cams.copy(), points.copy(), report if border is None else border.report(report, cams)
+        return cams.copy(), points.copy(), report if border is None else border.report(report, cams, cam_dist)
     lib = _lib.load()
     dev = torch.device(device)
 
@@ -140,8 +159,10 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     cam_offsets, cam_obs, obs_point = (on_device(a) for a in camera_index(obs_cam, offsets, n_cams))
     d_offsets, d_obs_cam, d_obs_xy, d_mask = on_device(offsets), on_device(obs_cam), on_device(obs_xy), on_device(const_mask)
     free = on_device(np.array([[not (int(m) >> i) & 1 for i in range(6)] for m in const_mask], bool).reshape(-1))
-    cur, cand = (_Buffers(torch, n_cams, n_points, total, dev, with_loss=loss_kind != 0) for _ in range(2))
+    cur, cand = (_Buffers(torch, n_cams, n_points, total, dev, with_loss=loss_kind != 0, with_dist=radial) for _ in range(2))
     cur.cams.copy_(on_device(cams)), cur.points.copy_(on_device(points))
+    if radial:
+        cur.dist.copy_(on_device(cam_dist))
     S = torch.zeros((6 * n_cams, 6 * n_cams), dtype=torch.float64, device=dev)
     g = torch.zeros(6 * n_cams, dtype=torch.float64, device=dev)
     dx = torch.zeros((n_points, 3), dtype=torch.float64, device=dev)
@@ -150,6 +171,12 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
         border.upload(on_device, d_offsets, d_obs_cam, (cam_offsets, cam_obs, obs_point))
 
     def linearize(b, lam):
+        if radial:
+            _lib.check(lib.vc_ba_linearize_points_radial(p(b.cams), n_cams, p(b.dist), p(d_mask), p(b.points), n_points, p(d_offsets),
+                                                         p(d_obs_cam), p(d_obs_xy), total, float(lam), loss_kind, loss_scale, p(b.vinv),
+                                                         p(b.gp), p(b.cost), p(b.count), p(b.obs_ok), p(b.obs_lin), p(b.obs_w),
+                                                         p(b.total_cost), stream), "vc_ba_linearize_points_radial")
+            return
         if loss_kind != 0:
             _lib.check(lib.vc_ba_linearize_points_loss(p(b.cams), n_cams, p(d_mask), p(b.points), n_points, p(d_offsets), p(d_obs_cam),
                                                        p(d_obs_xy), total, float(lam), loss_kind, loss_scale, p(b.vinv), p(b.gp), p(b.cost),
@@ -202,7 +229,8 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     out_cams = cur.cams.cpu().numpy()
     report = dict(iterations=iterations, accepted_steps=int(sum(decisions)), initial_cost=initial, final_cost=cost, final_lambda=lam,
                   decisions=decisions, loss=loss, loss_scale=loss_scale)
-    return out_cams, cur.points.cpu().numpy(), report if border is None else border.report(report, out_cams)
+    return out_cams, cur.points.cpu().numpy(), (report if border is None else
+                                                border.report(report, out_cams, cur.dist.cpu().numpy() if radial else None))
 
 
 def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
@@ -213,8 +241,20 @@ def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
     return bool(np.any(np.triu(np.ones_like(dots, bool), 1) & ((dots <= 0) | (cross2 >= tan2 * dots * dots))))
 
 
+def _pixel_errors_radial(K, k, R, t, xyz, obs):
+    """seed._pixel_errors under the distortion k = (k1, k2): the pixel is K (xu s, xv s, 1), s = 1 + k1 rho + k2 rho rho."""
+    Xc = xyz @ R.T + t
+    with np.errstate(all="ignore"):
+        xu, xv = Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2]
+        rho = xu * xu + xv * xv
+        s = 1.0 + k[0] * rho + k[1] * rho * rho
+        p = np.stack([K[0, 0] * (xu * s) + K[0, 2], K[1, 1] * (xv * s) + K[1, 2]], axis=1)
+        err = np.linalg.norm(p - obs, axis=1)
+    return np.where(Xc[:, 2] > 0, err, np.inf)
+
+
 def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
-                         grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0) -> SparseModel:
+                         grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False) -> SparseModel:
     """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
     is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
     Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
@@ -227,7 +267,15 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     VC_BA_MAX_GROUPS cameras.
     `loss`, `loss_scale`: the loss of the adjustment ("The loss" in §4.2k); bundle_fn is given loss= and loss_scale= only when
     the loss is not "trivial", and `stats()["bundle_adjustment"]` carries them then.  The filter stays MAX_ERROR px on the
-    unweighted error.  Raises ValueError for an unknown loss or a scale that is not finite and positive."""
+    unweighted error.  Raises ValueError for an unknown loss or a scale that is not finite and positive.
+    `refine_distortion` ("The distortion" in §4.2k): the adjustment also refines the radial distortion, one group per camera_id as
+    for the focal: k1 of a SIMPLE_RADIAL camera, k1 and k2 of a RADIAL one, from the values in the camera's params (0 where the
+    pipeline wrote them); every other model keeps both held, which is logged once per camera, and where no registered camera
+    has a radial parameter a ValueError names the two models.  Alone the flag holds fx, fy, cx, cy; with refine_focal_length both
+    are free.  bundle_fn is then also given cam_group=, intr_mask= (bit 5: k1 held, bit 6: k2 held), max_iterations=
+    REFINE_MAX_ITERATIONS and cam_dist= (n_cams, 2), and its report carries `cam_dist`; the cameras carry the refined k (params[3],
+    or params[3:5]), the filter and `error` use the distorted projection and `intrinsics` has six numbers per camera: fx, fy, cx,
+    cy, k1, k2.  Raises ValueError above VC_BA_MAX_GROUPS_RADIAL cameras."""
     bundle_fn = bundle_fn or bundle_adjust
     check_loss(loss, loss_scale)
     loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=float(loss_scale))
@@ -250,7 +298,34 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     mask = np.zeros(len(ids), np.uint8)
     mask[a] = HELD_ALL
     mask[b] = 1 << (3 + int(np.argmax(np.abs(cams[b, 9:12]))))
-    if refine_focal_length:
+    dist = None
+    if refine_distortion:
+        from .. import _lib
+        from .bundle_intr import (HOLD_CX, HOLD_CY, HOLD_FX, HOLD_FY, HOLD_K1, HOLD_K2, REFINE_MAX_ITERATIONS, TIED, has_one_focal,
+                                  radial_parameters)
+
+        cids = sorted({grown.images[i]["camera_id"] for i in ids})
+        n_radial = [radial_parameters(grown.cameras[c]) for c in cids]
+        if not any(n_radial):
+            raise ValueError("refine_distortion: no registered camera has a radial parameter to refine; the camera models with one are "
+                             "SIMPLE_RADIAL (k) and RADIAL (k1, k2)")
+        if len(cids) > _lib.VC_BA_MAX_GROUPS_RADIAL:
+            raise ValueError(f"refine_distortion: the registered images have {len(cids)} cameras, the radial border kernels hold at most "
+                             f"{_lib.VC_BA_MAX_GROUPS_RADIAL} groups of intrinsics (VC_BA_MAX_GROUPS_RADIAL)")
+        for c, n in zip(cids, n_radial):
+            if not n:
+                logger.info("refine_distortion: camera %d is %s, which has no radial parameter here; its k1 and k2 stay held", c,
+                            grown.cameras[c].model)
+        cam_group = np.array([cids.index(grown.images[i]["camera_id"]) for i in ids], np.int32)
+        # the focal as refine_focal_length frees it, or held; then k1 (SIMPLE_RADIAL, RADIAL) and k2 (RADIAL)
+        focal = [HOLD_CX | HOLD_CY | (TIED if has_one_focal(grown.cameras[c]) else 0) if refine_focal_length else
+                 HOLD_FX | HOLD_FY | HOLD_CX | HOLD_CY for c in cids]
+        intr_mask = np.array([f | (HOLD_K1 if n < 1 else 0) | (HOLD_K2 if n < 2 else 0) for f, n in zip(focal, n_radial)], np.uint8)
+        group_dist = np.array([[float(v) for v in list(grown.cameras[c].params[3:3 + n]) + [0.0] * (2 - n)] for c, n in zip(cids, n_radial)])
+        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group, intr_mask=intr_mask,
+                                         max_iterations=REFINE_MAX_ITERATIONS, cam_dist=group_dist[cam_group], **loss_args)
+        dist = np.array(report["cam_dist"], np.float64).reshape(-1, 2)
+    elif refine_focal_length:
         from .. import _lib
         from .bundle_intr import HOLD_CX, HOLD_CY, REFINE_MAX_ITERATIONS, TIED, has_one_focal
 
@@ -273,15 +348,22 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     points = points * scale
 
     model = SparseModel(initial_pair=grown.initial_pair, rounds=grown.rounds,
-                        bundle_adjustment={k: v for k, v in report.items() if k not in ("decisions", "intrinsics", "loss", "loss_scale")})
+                        bundle_adjustment={k: v for k, v in report.items()
+                                           if k not in ("decisions", "intrinsics", "loss", "loss_scale", "cam_dist")})
     model.bundle_adjustment.update(loss_args)
     model.cameras = copy.deepcopy(grown.cameras)
+    if refine_distortion:
+        # the cameras carry the refined k: params[3] of SIMPLE_RADIAL, params[3:5] of RADIAL; the filter and `error` use it
+        for g, (cid, n) in enumerate(zip(cids, n_radial)):
+            cam = model.cameras[cid]
+            cam.params = list(cam.params[:3]) + [float(v) for v in report["intrinsics"]["after"][g][4:4 + n]] + list(cam.params[3 + n:])
     if refine_focal_length:
         # the cameras carry the refined focal length(s); the filter below and `error` use the refined K
         for g, cid in enumerate(cids):
             fx, fy = (float(v) for v in report["intrinsics"]["after"][g][:2])
             cam = model.cameras[cid]
             cam.params = [fx] + list(cam.params[1:]) if has_one_focal(cam) else [fx, fy] + list(cam.params[2:])
+    if refine_focal_length or refine_distortion:
         K = {i: np.array([[cams[slot[i], 12], 0.0, cams[slot[i], 14]], [0.0, cams[slot[i], 13], cams[slot[i], 15]], [0.0, 0.0, 1.0]]) for i in ids}
         model.bundle_adjustment["intrinsics"] = {cid: dict(before=[float(v) for v in report["intrinsics"]["before"][g]],
                                                            after=[float(v) for v in report["intrinsics"]["after"][g]])
@@ -295,8 +377,12 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     dropped_obs = 0
     for j, pid in enumerate(pids):
         rows = cams[obs_cam[offsets[j]:offsets[j + 1]]]
-        err = np.array([_pixel_errors(K[i], row[:9].reshape(3, 3), row[9:12], points[j][None], obs_xy[o][None])[0]
-                        for o, row, (i, _) in zip(range(offsets[j], offsets[j + 1]), rows, tracks[j])])
+        if dist is None:
+            err = np.array([_pixel_errors(K[i], row[:9].reshape(3, 3), row[9:12], points[j][None], obs_xy[o][None])[0]
+                            for o, row, (i, _) in zip(range(offsets[j], offsets[j + 1]), rows, tracks[j])])
+        else:
+            err = np.array([_pixel_errors_radial(K[i], dist[slot[i]], row[:9].reshape(3, 3), row[9:12], points[j][None], obs_xy[o][None])[0]
+                            for o, row, (i, _) in zip(range(offsets[j], offsets[j + 1]), rows, tracks[j])])
         keep = err <= MAX_ERROR
         dropped_obs += int((~keep).sum())
         if keep.sum() < 2:

@@ -30,12 +30,24 @@ def has_one_focal(camera):
     return model in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL")
 
 
-def _group_intrinsics(cams, cam_group, n_groups):
-    """-> float64 (n_groups, 4): (fx, fy, cx, cy) of the first slot of each group, NaN for a group without a slot."""
-    out = np.full((n_groups, 4), np.nan)
+HOLD_K1, HOLD_K2 = 32, 64                                              # with the distortion: bits 5 and 6 hold k1 and k2
+HOLD_ALL_RADIAL = HOLD_FX | HOLD_FY | HOLD_CX | HOLD_CY | HOLD_K1 | HOLD_K2
+
+
+def radial_parameters(camera):
+    """How many radial parameters the camera's model has for the adjustment to refine: 1 for SIMPLE_RADIAL (k = params[3]), 2 for
+    RADIAL (k1, k2 = params[3:5]), 0 for every other model."""
+    model = camera.model if isinstance(camera.model, str) else getattr(camera.model, "name", str(camera.model))
+    return {"SIMPLE_RADIAL": 1, "RADIAL": 2}.get(model, 0)
+
+
+def _group_intrinsics(cams, cam_group, n_groups, cam_dist=None):
+    """-> float64 (n_groups, 4): (fx, fy, cx, cy) of the first slot of each group, NaN for a group without a slot; with cam_dist
+    (n_groups, 6): k1, k2 after them."""
+    out = np.full((n_groups, 4 if cam_dist is None else 6), np.nan)
     for a in range(len(cams) - 1, -1, -1):
         if 0 <= cam_group[a] < n_groups:
-            out[cam_group[a]] = cams[a, 12:16]
+            out[cam_group[a]] = cams[a, 12:16] if cam_dist is None else np.concatenate([cams[a, 12:16], cam_dist[a]])
     return out
 
 
@@ -43,22 +55,30 @@ class Border:
     """What refined intrinsics add to the loop of `bundle.bundle_adjust`: cam_group int32 (n_cams,) (a slot whose group is outside
     [0, n_groups) keeps its intrinsics) and intr_mask uint8 (n_groups,) (bits 0-3: fx, fy, cx, cy held; bit 4: fx and fy tied),
     checked here; the border's device buffers; per iteration the bordered system of the current linearisation and the step
-    under (dc, dtheta); `intrinsics` = dict(before (n_groups, 4), after (n_groups, 4)) in the report."""
+    under (dc, dtheta); `intrinsics` = dict(before (n_groups, 4), after (n_groups, 4)) in the report.
+    With cam_dist (n_cams, 2) ("The distortion" in §4.2k) the unknowns of a group are (fx, fy, cx, cy, k1, k2): N = 6 in the place of
+    4 in every shape, bits 5 and 6 of the mask hold k1 and k2, the _radial entry points run under loss = (kind, scale) and the
+    buffers carry dist beside cams; the report's `intrinsics` are (n_groups, 6) and it gains `cam_dist`."""
 
-    def __init__(self, cams, cam_group, intr_mask, with_loss=False):
+    def __init__(self, cams, cam_group, intr_mask, with_loss=False, cam_dist=None, loss=(0, 1.0)):
         from .. import _lib
 
         self._lib, self.with_loss = _lib, with_loss                           # with a loss: the _loss entry points and the buffer's obs_w
+        self.radial, self.loss, self.N = cam_dist is not None, loss, 4 if cam_dist is None else 6
         self.cam_group, self.intr_mask = np.ascontiguousarray(cam_group, np.int32), np.ascontiguousarray(intr_mask, np.uint8)
         self.n_cams, self.G = len(cams), len(self.intr_mask)
         if self.cam_group.shape != (self.n_cams,) or self.intr_mask.ndim != 1 or self.G < 1:
             raise ValueError("bundle_adjust needs cam_group (n_cams,) and intr_mask (n_groups,) with n_groups >= 1")
+        if self.radial and self.G > _lib.VC_BA_MAX_GROUPS_RADIAL:
+            raise ValueError(f"bundle_adjust: {self.G} groups of intrinsics with distortion, the radial border kernels hold at most "
+                             f"{_lib.VC_BA_MAX_GROUPS_RADIAL} (VC_BA_MAX_GROUPS_RADIAL)")
         if self.G > _lib.VC_BA_MAX_GROUPS:
             raise ValueError(f"bundle_adjust: {self.G} groups of intrinsics, the border kernels hold at most {_lib.VC_BA_MAX_GROUPS} (VC_BA_MAX_GROUPS)")
-        self.before = _group_intrinsics(cams, self.cam_group, self.G)
+        self.before = _group_intrinsics(cams, self.cam_group, self.G, cam_dist)
 
-    def report(self, report, cams):
-        return dict(report, intrinsics=dict(before=self.before, after=_group_intrinsics(cams, self.cam_group, self.G)))
+    def report(self, report, cams, cam_dist=None):
+        out = dict(report, intrinsics=dict(before=self.before, after=_group_intrinsics(cams, self.cam_group, self.G, cam_dist)))
+        return dict(out, cam_dist=np.array(cam_dist, np.float64)) if self.radial else out
 
     def upload(self, on_device, offsets, obs_cam, index):
         """The loop's device tensors offsets, obs_cam and index = (cam_offsets, cam_obs, obs_point); the border's own are made."""
@@ -69,11 +89,13 @@ class Border:
         self.n_points, self.total = len(offsets) - 1, len(obs_cam)
         f64 = dict(dtype=torch.float64, device=offsets.device)
         u8 = dict(dtype=torch.uint8, device=offsets.device)
-        nc, nt, rows = 6 * self.n_cams, 4 * self.G, 24 * self.G + 16 * self.G * self.G
+        N = self.N
+        nc, nt, rows = 6 * self.n_cams, N * self.G, (N * N + 2 * N) * self.G + N * N * self.G * self.G
         self.M, self.rhs = torch.zeros((nc + nt, nc + nt), **f64), torch.zeros(nc + nt, **f64)
         self.B, self.C, self.h = torch.zeros((nc, nt), **f64), torch.zeros((nt, nt), **f64), torch.zeros(nt, **f64)
         self.free_t, self.valid = torch.zeros(nt, **u8), torch.zeros(self.n_cams, **u8)
-        self.obs_xn, self.T = torch.zeros((self.total, 2), **f64), torch.zeros((self.n_points, self.G, 12), **f64)
+        # per observation what the B pass rebuilds J_theta from: (x, y), or with the distortion obs_jt's six numbers
+        self.obs_xn, self.T = torch.zeros((self.total, 6 if self.radial else 2), **f64), torch.zeros((self.n_points, self.G, 3 * N), **f64)
         self.terms, self.sums = torch.zeros((rows, self.n_points), **f64), torch.zeros(rows, **f64)
 
     def system(self, cur, lam, S, g, free):
@@ -82,7 +104,17 @@ class Border:
 
         _lib, n_cams, G, n_points, total, nc = self._lib, self.n_cams, self.G, self.n_points, self.total, 6 * self.n_cams
         lib, p, stream = _lib.load(), _lib.ptr, _lib.stream_ptr()
-        if self.with_loss:
+        if self.radial:
+            kind, scale = self.loss
+            _lib.check(lib.vc_ba_linearize_intrinsics_radial(p(cur.cams), n_cams, p(cur.dist), p(self.group), G, p(self.intr), p(cur.points),
+                                                             n_points, p(self.offsets), p(self.obs_cam), total, kind, scale, p(cur.vinv),
+                                                             p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(cur.obs_w), p(self.obs_xn), p(self.T),
+                                                             p(self.terms), stream), "vc_ba_linearize_intrinsics_radial")
+            _lib.check(lib.vc_ba_reduce_border_radial(n_cams, p(self.group), G, p(self.intr), n_points, p(self.offsets), p(self.obs_cam), total,
+                                                      *(p(a) for a in self.index), float(lam), kind, scale, p(cur.vinv), p(cur.obs_ok),
+                                                      p(cur.obs_lin), p(self.obs_xn), p(cur.obs_w), p(self.T), p(self.terms), p(self.sums),
+                                                      p(self.B), p(self.C), p(self.h), p(self.free_t), stream), "vc_ba_reduce_border_radial")
+        elif self.with_loss:
             _lib.check(lib.vc_ba_linearize_intrinsics_loss(p(cur.cams), n_cams, p(self.group), G, p(self.intr), p(cur.points), n_points,
                                                            p(self.offsets), p(self.obs_cam), total, p(cur.vinv), p(cur.gp), p(cur.obs_ok),
                                                            p(cur.obs_lin), p(cur.obs_w), p(self.obs_xn), p(self.T), p(self.terms), stream),
@@ -108,6 +140,12 @@ class Border:
         """The candidate under x = (dc, dtheta) -> whether all its focal lengths are finite and positive (a device scalar)."""
         _lib, nc = self._lib, 6 * self.n_cams
         p, dc, dtheta = _lib.ptr, x[:nc].contiguous(), x[nc:].contiguous()
+        if self.radial:
+            _lib.check(_lib.load().vc_ba_step_radial(p(cur.cams), self.n_cams, p(cur.dist), p(self.group), self.G, p(self.intr), p(cur.points),
+                                                     self.n_points, p(self.offsets), p(self.obs_cam), self.total, p(cur.vinv), p(cur.gp),
+                                                     p(cur.obs_ok), p(cur.obs_lin), p(self.T), p(dc), p(dtheta), p(cand.cams), p(cand.dist),
+                                                     p(cand.points), p(dx), p(self.valid), _lib.stream_ptr()), "vc_ba_step_radial")
+            return self.valid.bool().all()
         _lib.check(_lib.load().vc_ba_step_intrinsics(p(cur.cams), self.n_cams, p(self.group), self.G, p(self.intr), p(cur.points), self.n_points,
                                                      p(self.offsets), p(self.obs_cam), self.total, p(cur.vinv), p(cur.gp), p(cur.obs_ok),
                                                      p(cur.obs_lin), p(self.T), p(dc), p(dtheta), p(cand.cams), p(cand.points), p(dx),

@@ -1,7 +1,7 @@
 """Growth of the seed model: the tracks of the match graph are triangulated under the registered poses
 and the remaining images registered against the new points, in rounds, until a round adds neither a point nor an image.
 It is still not a mapper: no bundle adjustment here (mapping/bundle.py adjusts the result once, §4.2k), no re-triangulation or
-merging of existing points, no point filtering after the rounds, no distortion models.  Specification: tests/util_mapper.py (`grow_model`).  This build's own published rule;
+merging of existing points, no point filtering after the rounds, no distortion inside the rounds (a SIMPLE_RADIAL or RADIAL camera with k = 0 is grown under the pinhole assumption and mapping/bundle.py refines k afterwards).  Specification: tests/util_mapper.py (`grow_model`).  This build's own published rule;
 parity with COLMAP's mapper is unpinned.
 
 Where the work runs

@@ -23,7 +23,9 @@ from .absolute_pose import (ABS_POSE_MIN_NUM_INLIERS, FILTER_MIN_TRI_ANGLE, INIT
 
 logger = logging.getLogger(__name__)
 
-SEED_CAMERA_MODELS = ("SIMPLE_PINHOLE", "PINHOLE")
+# SIMPLE_RADIAL and RADIAL only with every distortion parameter zero (camera_prior refuses the others): the model is then grown
+# under the pinhole assumption and the bundle adjustment may refine k from 0 (mapping/bundle.py, refine_distortion)
+SEED_CAMERA_MODELS = ("SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL")
 
 
 @dataclass

@@ -79,7 +79,10 @@ class Pipeline:
         refine_focal_length = bool(getattr(self.config.reconstruction, "refine_focal_length", False))
         if refine_focal_length and not bundle_adjustment:       # it is one more unknown of that adjustment (§4.2k)
             raise ValueError("refine_focal_length needs reconstruction.bundle_adjustment (--bundle-adjustment)")
-        ba_loss = str(getattr(self.config.reconstruction, "ba_loss", "trivial"))
+        refine_distortion = bool(getattr(self.config.reconstruction, "refine_distortion", False))
+        if refine_distortion and not bundle_adjustment:         # k1 (and k2) are further unknowns of that adjustment (§4.2k)
+            raise ValueError("refine_distortion needs reconstruction.bundle_adjustment (--bundle-adjustment)")
+        ba_loss =str(getattr(self.config.reconstruction, "ba_loss", "trivial"))
         ba_loss_scale = float(getattr(self.config.reconstruction, "ba_loss_scale", 1.0))
         if ba_loss not in BA_LOSSES:
             raise ValueError(f"unknown ba_loss {ba_loss!r}: expected one of {', '.join(BA_LOSSES)}")
@@ -144,7 +147,10 @@ class Pipeline:
         if seed_model:                                          # under torchrun only rank 0 arrives here
             self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
         if sparse_model:
-            if refine_focal_length:
+            if refine_distortion:
+                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True,
+                                         refine_focal_length=refine_focal_length, refine_distortion=True, **loss_args)
+            elif refine_focal_length:
                 self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True, refine_focal_length=True,
                                          **loss_args)
             else:
@@ -188,11 +194,12 @@ class Pipeline:
         logger.info("Seed model: pair %s, %d images, %d points", *[model.stats()[k] for k in
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
-    def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0):
+    def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0,
+                            refine_distortion=False):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
         `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
         `refine_focal_length`: that adjustment also refines the cameras' focal lengths; `loss`, `loss_scale`: its loss, passed on
-        only where it is not the trivial one."""
+        only where it is not the trivial one; `refine_distortion`: it also refines k1 (k2) of SIMPLE_RADIAL and RADIAL cameras."""
         from ..mapping.grow import build_sparse_model
 
         try:
@@ -208,7 +215,10 @@ class Pipeline:
             from ..mapping.bundle import build_adjusted_model
 
             loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=loss_scale)
-            if refine_focal_length:
+            if refine_distortion:
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=refine_focal_length,
+                                                refine_distortion=True, **loss_args)
+            elif refine_focal_length:
                 adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=True, **loss_args)
             else:
                 adjusted = build_adjusted_model(str(db_path), device=device, grown=model, **loss_args)
@@ -267,6 +277,9 @@ def main() -> None:
     ap.add_argument("--refine-focal-length", dest="refine_focal_length", action="store_true",
                     help="with --bundle-adjustment: the adjustment also refines the focal length(s) of every camera; the "
                          "adjusted model's cameras.txt carries the refined values")
+    ap.add_argument("--refine-distortion", dest="refine_distortion", action="store_true",
+                    help="with --bundle-adjustment: the adjustment also refines the radial distortion, k of SIMPLE_RADIAL cameras and "
+                         "k1, k2 of RADIAL ones, from the values in the database (0 as the extractors write them)")
     ap.add_argument("--ba-loss", dest="ba_loss", choices=list(BA_LOSSES), default="trivial",
                     help="with --bundle-adjustment: the loss of the adjustment; huber and soft_l1 keep observations that are tens "
                          "of pixels off their point from setting the poses")
