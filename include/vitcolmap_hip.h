@@ -188,7 +188,8 @@ int vc_two_view_inliers(const float* pts, const int32_t* offsets, int n_pairs, c
  *   offsets    [n_pairs + 1] int32: pair p owns pts_n[offsets[p] .. offsets[p+1])
  *   samples    [n_pairs][n_hyp][5] int32 indices into the pair's own list; samples[..][0] < 0: the hypothesis is void
  *   out_E      [n_pairs][n_hyp][10][9] float64: row-major 3x3 at unit Frobenius norm, ascending in the solver's root
- *              variable; the slots past out_count are NaN
+ *              variable; the slots past out_count are NaN.  A root of magnitude 1 of that variable, where the solver's two
+ *              root ranges used to meet, is inside the first range (which ends at 1 + 2^-10) and is returned once.
  *   out_count  [n_pairs][n_hyp] int32: number of real solutions, 0 .. 10.  0 for a void sample, an index outside the
  *              pair's list, a repeated index or point, non-finite points and a singular elimination; a matrix that is
  *              not finite is never counted.
@@ -230,7 +231,12 @@ int vc_two_view_pose(const double* pts_n, const int32_t* offsets, int n_pairs, c
  *   xyz        [total][3] float64: the world points
  *   samples    [n_prob][n_hyp][3] int32 indices into the problem's own list; samples[..][0] < 0: the hypothesis is void
  *   out_pose   [n_prob][n_hyp][4][12] float64: R row-major then t, ascending in the solver's root variable (the depth
- *              ratio s2 / s1); the slots past out_count are NaN
+ *              ratio s2 / s1 along the unit rays of the sample's second and first point); the slots past out_count are NaN.
+ *              At most four DISTINCT poses.  Two geometries that used to lose poses are solved: two points equally far from
+ *              the camera (s2 / s1 = 1, on the seam of the solver's two root ranges: the first now ends at 1 + 2^-10, the
+ *              pose is returned once), and a third ray perpendicular to the side between the first two points in the camera
+ *              frame (two poses share s2 / s1, a double root: the solver then eliminates under another labelling of the
+ *              three points and sorts the poses back into this order).
  *   out_count  [n_prob][n_hyp] int32: 0 .. 4.  0 for a void sample, an index outside the problem's list, a repeated index,
  *              two coincident world points or rays, collinear world points, non-finite input and a quartic without a
  *              finite non-zero coefficient; a pose that is not finite and proper (|det R - 1| < 1e-9) is never counted.

@@ -215,16 +215,25 @@ def verify_pair(kp1, kp2, matches, pair_id, num_f=NUM_HYP_F, num_h=NUM_HYP_H):
     return res
 
 
-def synthetic_two_view(seed, n_points=300, outlier_frac=0.3, planar=False, width=640, height=480, noise=0.5):
+def synthetic_two_view(seed, n_points=300, outlier_frac=0.3, planar=False, width=640, height=480, noise=0.5, R=None, t=None):
     """A seeded two-view scene for tests: 3-D points seen by two pinhole cameras (or a plane: every point on z = 6),
-    pixel noise, and a fraction of wrong matches.  -> kp1 (N, 2), kp2 (N, 2) float32, matches (N, 2) uint32, is_inlier."""
+    pixel noise, and a fraction of wrong matches.  -> kp1 (N, 2), kp2 (N, 2) float32, matches (N, 2) uint32, is_inlier.
+    R, t: the motion X2 = R X1 + t (default: 0.12 rad about y, t = (-0.8, 0.05, 0.1)); under a motion that is given, a point
+    that is not at least 0.5 in front of the second camera is drawn again."""
     rs = np.random.RandomState(seed)
     K = np.array([[600.0, 0, width / 2], [0, 600.0, height / 2], [0, 0, 1]])
     X = np.stack([rs.uniform(-3, 3, n_points), rs.uniform(-2, 2, n_points),
                   np.full(n_points, 6.0) if planar else rs.uniform(4, 9, n_points)], axis=1)
     a = 0.12
-    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
-    t = np.array([-0.8, 0.05, 0.1])
+    given = R is not None or t is not None
+    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]) if R is None else np.asarray(R, np.float64)
+    t = np.array([-0.8, 0.05, 0.1]) if t is None else np.asarray(t, np.float64)
+    while given:                                                       # the default scene draws exactly what it always drew
+        behind = (X @ R.T + t)[:, 2] < 0.5
+        if not behind.any():
+            break
+        k = int(behind.sum())
+        X[behind] = np.stack([rs.uniform(-3, 3, k), rs.uniform(-2, 2, k), np.full(k, 6.0) if planar else rs.uniform(4, 9, k)], axis=1)
     p1 = (K @ X.T).T
     p2 = (K @ (R @ X.T + t[:, None])).T
     kp1 = (p1[:, :2] / p1[:, 2:]) + rs.normal(0, noise, (n_points, 2))

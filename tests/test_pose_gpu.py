@@ -57,10 +57,19 @@ def run_kernel(pairs, points=True, workspace=True):
     return front.cpu().numpy(), best.cpu().numpy(), tri.cpu().numpy(), None if pts is None else pts.cpu().numpy(), offsets
 
 
-def scene_points(rs, n, wrong=0.0):
-    """n correspondences of the scene's motion in normalised coordinates with 1e-3 noise; a fraction is replaced by random ones."""
+def scene_points(rs, n, wrong=0.0, R=None, t=None):
+    """n correspondences of the scene's motion (or of X2 = R X + t) in normalised coordinates with 1e-3 noise; a fraction is
+    replaced by random ones.  Under a motion that is given, a point not at least 0.5 in front of the second camera is drawn again."""
     X = np.stack([rs.uniform(-3, 3, n), rs.uniform(-2, 2, n), rs.uniform(4, 9, n)], axis=1)
-    X2 = X @ ue.SCENE_R.T + ue.SCENE_T
+    given = R is not None or t is not None
+    R, t = ue.SCENE_R if R is None else np.asarray(R, np.float64), ue.SCENE_T if t is None else np.asarray(t, np.float64)
+    while given:                                                        # the default scene draws exactly what it always drew
+        behind = (X @ R.T + t)[:, 2] < 0.5
+        if not behind.any():
+            break
+        k = int(behind.sum())
+        X[behind] = np.stack([rs.uniform(-3, 3, k), rs.uniform(-2, 2, k), rs.uniform(4, 9, k)], axis=1)
+    X2 = X @ R.T + t
     xn = np.concatenate([X[:, :2] / X[:, 2:], X2[:, :2] / X2[:, 2:]], axis=1) + 1e-3 * rs.standard_normal((n, 4))
     bad = rs.uniform(size=n) < wrong
     xn[bad] = rs.uniform(-0.5, 0.5, (int(bad.sum()), 4))

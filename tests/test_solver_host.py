@@ -17,13 +17,17 @@ import util_essential as ue
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 PROGRAMS = ("five_point_host", "p3p_host")
+_BUILT = {}
 
 
 @pytest.fixture(scope="session")
 def host_programs(tmp_path_factory):
-    """Both programs, built side by side with the line their sources give -> {name: path}."""
+    """Both programs, built side by side with the line their sources give -> {name: path}; built once however many test
+    modules import the fixture (test_solver_families_host.py does)."""
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc to build the host programs with")
+    if _BUILT:
+        return _BUILT
     out = tmp_path_factory.mktemp("solver_host")
     builds = {name: subprocess.Popen([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-o",
                                       str(out / name), os.path.join(ROOT, "tools", name + ".cpp")],
@@ -31,7 +35,8 @@ def host_programs(tmp_path_factory):
     for name, proc in builds.items():
         log, _ = proc.communicate()
         assert proc.returncode == 0, f"{name} does not build:\n{log}"
-    return {name: str(out / name) for name in PROGRAMS}
+    _BUILT.update({name: str(out / name) for name in PROGRAMS})
+    return _BUILT
 
 
 def run_program(path, records, out_width, tmp_path):

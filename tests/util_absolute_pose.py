@@ -275,12 +275,21 @@ def estimate_absolute_pose(obs, xyz, K, seed, n_hyp=NUM_HYP_P, max_error=ABS_POS
                 inlier_mask=mask)
 
 
-def registration_problem(seed, n, outlier_frac, noise=0.5):
-    """n correspondences under (SCENE_R, SCENE_T) and SCENE_K with pixel noise; an outlier observes a uniform random pixel
-    -> obs float32 (n, 2), xyz float32 (n, 3), the inlier flags."""
+def registration_problem(seed, n, outlier_frac, noise=0.5, R=None, t=None):
+    """n correspondences under (SCENE_R, SCENE_T), or the pose (R, t) given, and SCENE_K with pixel noise; an outlier observes
+    a uniform random pixel -> obs float32 (n, 2), xyz float32 (n, 3), the inlier flags.  Under a pose that is given, a point
+    not at least 0.5 in front of the camera is drawn again."""
     rs = np.random.RandomState(seed)
     X = np.stack([rs.uniform(-3, 3, n), rs.uniform(-2, 2, n), rs.uniform(4, 9, n)], axis=1)
-    Xc = X @ ue.SCENE_R.T + ue.SCENE_T
+    given = R is not None or t is not None
+    R, t = ue.SCENE_R if R is None else np.asarray(R, np.float64), ue.SCENE_T if t is None else np.asarray(t, np.float64)
+    while given:                                                     # the default scene draws exactly what it always drew
+        behind = (X @ R.T + t)[:, 2] < 0.5
+        if not behind.any():
+            break
+        k = int(behind.sum())
+        X[behind] = np.stack([rs.uniform(-3, 3, k), rs.uniform(-2, 2, k), rs.uniform(4, 9, k)], axis=1)
+    Xc = X @ R.T + t
     p = (ue.SCENE_K @ Xc.T).T
     obs = p[:, :2] / p[:, 2:] + rs.normal(0, noise, (n, 2))
     is_in = rs.uniform(size=n) >= outlier_frac

@@ -43,10 +43,20 @@ def _ql(q, a):
 
 
 def null_space(x1, x2):
-    """x1, x2 (5, 2) float64 normalised points -> (4, 3, 3): an orthonormal basis of {E : x2' E x1 = 0 for the five}."""
-    a = np.stack([x2[:, 0] * x1[:, 0], x2[:, 0] * x1[:, 1], x2[:, 0], x2[:, 1] * x1[:, 0], x2[:, 1] * x1[:, 1], x2[:, 1],
-                  x1[:, 0], x1[:, 1], np.ones(5)], axis=1)
+    """x1, x2 (5, 2) float64 normalised points, or (5, 3) homogeneous ones -> (4, 3, 3): an orthonormal basis of
+    {E : x2' E x1 = 0 for the five}."""
+    h1, h2 = (x if x.shape[1] == 3 else np.concatenate([x, np.ones((5, 1))], axis=1) for x in (x1, x2))
+    a = (h2[:, :, None] * h1[:, None, :]).reshape(5, 9)
     return np.linalg.svd(a)[2][5:].reshape(4, 3, 3)
+
+
+def _frame(seed):
+    """A fixed rotation far from every axis, for `five_point`'s image frames."""
+    q = np.linalg.qr(np.random.RandomState(seed).normal(size=(3, 3)))[0]
+    return q * np.sign(np.linalg.det(q))
+
+
+_FRAME1, _FRAME2 = _frame(0x5E1), _frame(0x5E2)
 
 
 def constraint_matrix(basis):
@@ -96,13 +106,22 @@ def _polish(m, xyz, steps=3):
 
 def five_point(x1, x2):
     """x1, x2 (5, 2) float64 normalised image points -> (n, 3, 3), n <= 10: every real essential matrix through the five
-    correspondences, unit Frobenius norm (no solution for a degenerate sample)."""
+    correspondences, unit Frobenius norm (no solution for a degenerate sample).
+
+    The action matrix is built on a fixed monomial basis and needs the ten cubics to be solvable for the ten cubic monomials;
+    a motion aligned with the image axes (R = I with t along x: E has two non-zero entries) makes that system singular for
+    every choice of points.  So the problem is solved in image frames turned by two fixed generic rotations, h1 -> Q1 h1 and
+    h2 -> Q2 h2 on homogeneous points, under which E -> Q2 E Q1' and no axis is special, and the solutions are turned back."""
     x1, x2 = np.asarray(x1, np.float64), np.asarray(x2, np.float64)
     if not (np.all(np.isfinite(x1)) and np.all(np.isfinite(x2))):
         return np.zeros((0, 3, 3))
     try:
         with np.errstate(all="ignore"):
-            basis = null_space(x1, x2)
+            h1 = np.concatenate([x1, np.ones((5, 1))], axis=1) @ _FRAME1.T
+            h2 = np.concatenate([x2, np.ones((5, 1))], axis=1) @ _FRAME2.T
+            if np.linalg.matrix_rank((h2[:, :, None] * h1[:, None, :]).reshape(5, 9)) < 5:
+                return np.zeros((0, 3, 3))                              # dependent equations: more than four dimensions of E
+            basis = null_space(h1, h2)
             m = constraint_matrix(basis)
         if not np.all(np.isfinite(m)):
             return np.zeros((0, 3, 3))
@@ -124,7 +143,7 @@ def five_point(x1, x2):
             continue
         vec = v[:, k].real
         xyz = _polish(m, vec[6:9] / vec[9])
-        E = xyz[0] * basis[0] + xyz[1] * basis[1] + xyz[2] * basis[2] + basis[3]
+        E = _FRAME2.T @ (xyz[0] * basis[0] + xyz[1] * basis[1] + xyz[2] * basis[2] + basis[3]) @ _FRAME1
         n = np.linalg.norm(E)
         if np.isfinite(n) and n > 0:
             out.append(E / n)

@@ -14,14 +14,18 @@
 // The specification eliminates u instead (a resultant, a quartic in v) and takes the roots from numpy's eigensolver, so that
 // the two agree is a test of both.  Per lane:
 //   1. the quartic's coefficients, scaled to unit maximum
-//   2. real roots   u in [0, 1] of the quartic and, for u > 1, w = 1 / u in (0, 1) of its reversal: the roots of the k-th
+//   2. real roots   u in [0, e] of the quartic and, for u > e, w = 1 / u in (0, 1 / e) of its reversal (e just above 1, so
+//                   that u = 1, two points equally far from the camera, lies inside the first range: minimal_solver.h
+//                   kSeamEnd): the roots of the k-th
 //                   derivative bracket those of the (k-1)-th, each bracket is bisected at most kBisections times.  A root list
 //                   is positional (slot s: the root between breakpoints s-1 and s, NaN for none), every loop fully unrolled,
 //                   so no array has a run-time index
 //   3. depths       v = N / D, s1 from d12; at most kPolish Newton steps on the three distance equations themselves take out
-//                   the rounding of the quartic's coefficients and of the division by D
-//   4. pose         an orthonormal frame on the world triangle and one on the camera-frame triangle: R = Fc Fw', t from the
-//                   centroids
+//                   the rounding of the quartic's coefficients and of the division by D.  Where D nearly vanishes at a root, v
+//                   comes from the first conic; where the quartic has a double root, the points are relabelled and steps 1 to
+//                   3 run again (solve_p3p)
+//   4. pose         an orthonormal frame on the world triangle and one on the camera-frame triangle, both along the world
+//                   triangle's longest side: R = Fc Fw', t from the centroids
 // Every loop has a constant trip count but the bisection and the polish, which are capped.  The kernel around solve_p3p and
 // the pieces of the root bracketing are those of minimal_solver.h, shared with the five-point solver.  The solver functions are
 // __host__ __device__: tools/p3p_host.cpp includes this file and calls solve_p3p on one problem after another.
@@ -42,11 +46,13 @@ constexpr int kMaxPoses = 4;
 constexpr int kPolish = 3;
 constexpr double kParallelTol = 1e-20;      // squared sine below which two rays, or two sides of the world triangle, are parallel
 constexpr double kProperTol = 1e-9;         // |det R - 1| of a returned rotation
+constexpr double kTouch = 1e-12;            // |p| over the sum of its terms' magnitudes below which p touches zero at a root of p'
+constexpr double kSmallD = 1e-4;            // |D(u)| over the sum of its terms' magnitudes below which v is not taken from N / D
 
-// One level of the bracketing: the (4 - DEG)-th derivative of sum a[i] t^i over (4 - DEG)!, of degree DEG, on [0, 1].  prev:
-// the roots of its derivative in positional slots 0 .. DEG - 2 (NaN: none), ascending among the slots that are set; with 0
-// and 1 they cut the interval into pieces on which this polynomial is monotone, so a sign change over a piece brackets one
-// root.  cur[s]: the root of the piece that ends at breakpoint s (s = DEG - 1: at 1), or NaN.
+// One level of the bracketing: the (4 - DEG)-th derivative of sum a[i] t^i over (4 - DEG)!, of degree DEG, on [0, vc::kSeamEnd].
+// prev: the roots of its derivative in positional slots 0 .. DEG - 2 (NaN: none), ascending among the slots that are set; with 0
+// and the end they cut the interval into pieces on which this polynomial is monotone, so a sign change over a piece brackets
+// one root.  cur[s]: the root of the piece that ends at breakpoint s (s = DEG - 1: at the end), or NaN.
 template <int DEG>
 __host__ __device__ __forceinline__ void roots_level(const double (&a)[5], const double (&prev)[4], double (&cur)[4]) {
   constexpr int K = 4 - DEG;
@@ -55,7 +61,7 @@ __host__ __device__ __forceinline__ void roots_level(const double (&a)[5], const
   double lo = 0.0, f_lo = vc::horner(coef, DEG, 0.0);
 #pragma unroll
   for (int s = 0; s < DEG; ++s) {
-    const double hi = s < DEG - 1 ? prev[s] : 1.0;
+    const double hi = s < DEG - 1 ? prev[s] : vc::kSeamEnd;
     double root = NAN;
     if (hi == hi) {                                          // a breakpoint that is set
       const double f_hi = vc::horner(coef, DEG, hi);
@@ -68,13 +74,23 @@ __host__ __device__ __forceinline__ void roots_level(const double (&a)[5], const
   for (int s = DEG; s < 4; ++s) cur[s] = NAN;
 }
 
-// The real roots in [0, 1] of sum a[i] t^i, ascending over the slots that are set.
-__host__ __device__ __forceinline__ void real_roots_unit(const double (&a)[5], double (&roots)[4]) {
+// The real roots in [0, vc::kSeamEnd] of sum a[i] t^i, ascending over the slots that are set.  -> true when the polynomial
+// comes within kTouch of its terms' sum at a root of its derivative: a double root, or two that rounding may have merged, which
+// a sign change does not find reliably.
+__host__ __device__ __forceinline__ bool real_roots_unit(const double (&a)[5], double (&roots)[4]) {
   double none[4] = {NAN, NAN, NAN, NAN}, r1[4], r2[4], r3[4];
   roots_level<1>(a, none, r1);
   roots_level<2>(a, r1, r2);
   roots_level<3>(a, r2, r3);
   roots_level<4>(a, r3, roots);
+  bool touches = false;
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const double b = r3[s];                                  // in (0, kSeamEnd) or NaN, for which the comparison is false
+    const double terms = (((fabs(a[4]) * b + fabs(a[3])) * b + fabs(a[2])) * b + fabs(a[1])) * b + fabs(a[0]);
+    touches = touches || fabs(vc::horner(a, 4, b)) <= kTouch * terms;
+  }
+  return touches;
 }
 
 struct Triangle {
@@ -149,11 +165,19 @@ __host__ __device__ __forceinline__ void polish_depths(const Triangle& g, double
   }
 }
 
-// A right-handed orthonormal frame on the triangle p0 p1 p2: columns e1 along p1 - p0, e2 in the plane, e3 the normal.
-__host__ __device__ __forceinline__ void frame_of(const double (&p)[3][3], double (&e)[3][3]) {
+// A right-handed orthonormal frame on the triangle p0 p1 p2: columns e1 along one side, e2 in the plane, e3 the normal.
+// side 0: e1 along p1 - p0, the plane through p2; side 1: along p2 - p0, through p1; side 2: along p2 - p1, through p0.  The
+// world frame and the camera frame of a pose take the same side, the longest of the world triangle: the depths along two rays
+// that nearly coincide are determined only to rounding over the sine of their angle, and a frame laid along the short side
+// between them would turn the third point by that error times the ratio of the sides.
+__host__ __device__ __forceinline__ void frame_of(const double (&p)[3][3], int side, double (&e)[3][3]) {
   double a[3], b[3], n[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) a[k] = p[1][k] - p[0][k], b[k] = p[2][k] - p[0][k];
+  for (int k = 0; k < 3; ++k) {
+    const double from = side == 2 ? p[1][k] : p[0][k], to = side == 0 ? p[1][k] : p[2][k];
+    const double third = side == 0 ? p[2][k] : side == 1 ? p[1][k] : p[0][k];
+    a[k] = to - from, b[k] = third - from;
+  }
   const double ia = 1.0 / sqrt(dot3(a, a));
 #pragma unroll
   for (int k = 0; k < 3; ++k) e[0][k] = a[k] * ia;
@@ -165,12 +189,23 @@ __host__ __device__ __forceinline__ void frame_of(const double (&p)[3][3], doubl
 }
 
 // One pose from a root: u = s2 / s1 (reversed: the root is w = 1 / u).  out: R row-major, then t.  -> false when a depth is
-// not positive or the pose is not finite and proper.
-__host__ __device__ __forceinline__ bool pose_from_root(const Triangle& g, const double (&fw)[3][3], const double (&n)[3],
+// not positive or the pose is not finite and proper.  Where D(u) cancels to within kSmallD of its terms, N / D has lost that
+// many digits (N vanishes with D), and v is a root of the first conic instead, v^2 - 2 c13 v + 1 - A (1 + u^2 - 2 u c12) = 0:
+// the one that leaves the smaller residual in the second conic.  (Both leave none where D = 0 exactly; the quartic then has a
+// double root, which solve_p3p handles.)
+__host__ __device__ __forceinline__ bool pose_from_root(const Triangle& g, const double (&fw)[3][3], int side, const double (&n)[3],
                                                         const double (&dd)[2], double root, bool reversed, double* out) {
   const double u = reversed ? 1.0 / root : root;
   if (!(u > 0.0 && u < INFINITY)) return false;
-  const double v = ((n[2] * u + n[1]) * u + n[0]) / (dd[1] * u + dd[0]);
+  const double d = dd[1] * u + dd[0];
+  double v = ((n[2] * u + n[1]) * u + n[0]) / d;
+  if (!(fabs(d) > kSmallD * (fabs(dd[1] * u) + fabs(dd[0])))) {
+    const double A = g.d13 / g.d12, B = g.d23 / g.d12, q = (u - 2.0 * g.c12) * u + 1.0;
+    const double sq = sqrt(fmax(g.c13 * g.c13 - 1.0 + A * q, 0.0));
+    const double va = g.c13 - sq, vb = g.c13 + sq;
+    const double ra = fabs(B * q - (u * u + va * va - 2.0 * u * va * g.c23)), rb = fabs(B * q - (u * u + vb * vb - 2.0 * u * vb * g.c23));
+    v = ra <= rb ? va : vb;
+  }
   if (!(v > 0.0 && v < INFINITY)) return false;
   const double s1 = sqrt(g.d12 / ((u - 2.0 * g.c12) * u + 1.0));
   double s[3] = {s1, u * s1, v * s1};
@@ -181,7 +216,7 @@ __host__ __device__ __forceinline__ bool pose_from_root(const Triangle& g, const
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int k = 0; k < 3; ++k) pc[i][k] = s[i] * g.f[i][k];
-  frame_of(pc, fc);
+  frame_of(pc, side, fc);
   double r[9], t[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -209,9 +244,12 @@ __host__ __device__ __forceinline__ bool pose_from_root(const Triangle& g, const
   return true;
 }
 
-// Three 2D-3D correspondences (normalised image points (x, y), world points g.X filled by the caller) -> up to four poses at
-// `out` (12 doubles each), ascending in u; -> their number.
-__host__ __device__ __forceinline__ int solve_p3p(const double (&x)[3], const double (&y)[3], Triangle& g, double* out) {
+// Three 2D-3D correspondences (normalised image points (x, y), world points g.X filled by the caller) under the labelling they
+// come in -> up to four poses at `out` (12 doubles each), ascending in u; -> their number.  `clean` is cleared where this
+// labelling's elimination is not to be trusted: the quartic touches zero (a double root, or two that rounding may merge).
+__host__ __device__ __forceinline__ int solve_labelled(const double (&x)[3], const double (&y)[3], Triangle& g, double* out,
+                                                       bool& clean) {
+  clean = true;
   if (!make_triangle(x, y, g)) return 0;
   const double A = g.d13 / g.d12, B = g.d23 / g.d12;
   const double n[3] = {A - B - 1.0, -2.0 * (A - B) * g.c12, A - B + 1.0};      // N(u), from the constant up
@@ -236,21 +274,94 @@ __host__ __device__ __forceinline__ int solve_p3p(const double (&x)[3], const do
 #pragma unroll
   for (int i = 0; i < 5; ++i) rev[i] = p[4 - i];
   double fw[3][3];
-  frame_of(g.X, fw);
+  const int side = g.d12 >= g.d13 && g.d12 >= g.d23 ? 0 : g.d13 >= g.d23 ? 1 : 2;
+  frame_of(g.X, side, fw);
   double direct[4], inverse[4];
-  real_roots_unit(p, direct);
-  real_roots_unit(rev, inverse);
-  // ascending u: the roots in [0, 1], then those above 1 (w in (0, 1), descending)
+  bool doubtful = real_roots_unit(p, direct);
+  doubtful = real_roots_unit(rev, inverse) || doubtful;
+  // ascending u: the roots in [0, kSeamEnd], then those above (w in (0, kSeamInv), descending)
   int count = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if (direct[i] == direct[i] && count < kMaxPoses && pose_from_root(g, fw, n, dd, direct[i], false, out + 12 * count)) ++count;
+    if (direct[i] == direct[i] && count < kMaxPoses && pose_from_root(g, fw, side, n, dd, direct[i], false, out + 12 * count))
+      ++count;
 #pragma unroll
   for (int i = 3; i >= 0; --i) {
     const double w = inverse[i];
-    if (w > 0.0 && w < 1.0 && count < kMaxPoses && pose_from_root(g, fw, n, dd, w, true, out + 12 * count)) ++count;
+    if (w > 0.0 && w < vc::kSeamInv && count < kMaxPoses && pose_from_root(g, fw, side, n, dd, w, true, out + 12 * count))
+      ++count;
   }
+  clean = !doubtful;
   return count;
+}
+
+// |R X + t|: the depth of the world point X along its unit ray under the pose at `pose`.
+__host__ __device__ __forceinline__ double depth_under(const double* pose, const double (&X)[3]) {
+  double c[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) c[i] = pose[3 * i] * X[0] + pose[3 * i + 1] * X[1] + pose[3 * i + 2] * X[2] + pose[9 + i];
+  return sqrt(dot3(c, c));
+}
+
+// Three 2D-3D correspondences (normalised image points (x, y), world points g.X filled by the caller) -> up to four poses at
+// `out` (12 doubles each), ascending in u = s2 / s1; -> their number.  The elimination of v fails where two solutions share
+// their u: D(u) = 2 (c23 u - c13) vanishes at a solution exactly when the third ray is perpendicular to the side between the
+// first two points in the camera frame, N vanishes with it, the line u = const lies in the conics' difference and meets each
+// conic twice, so the quartic has a double root there (no sign change) and v = 0 / 0.  Which point is the third is a choice:
+// when a labelling's result is not clean the points are rotated (2 3 1, then 3 1 2), under which the same poses have other
+// (u, v), until one is clean; the last one stands when none is.  The poses do not depend on the labelling, their order does:
+// after a rotation they are sorted by the depth ratio of the points the caller calls second and first.
+// `load(turn, x, y, g)` fills x, y and g.X with the problem's points turned `turn` times (0: as the caller labels them; 1:
+// 2 3 1; 2: 3 1 2).  One loop that is not unrolled, so the elimination exists once in the kernel and nothing of the problem has
+// to stay in registers through it: the kernel's loader reads the points again.
+template <typename Load>
+__host__ __device__ __forceinline__ int solve_p3p_turning(const Load& load, Triangle& g, double* out) {
+  int count = 0, turn = 0;
+#pragma unroll 1
+  for (;; ++turn) {
+    double x[3], y[3];
+    load(turn, x, y, g);
+    bool clean;
+    count = solve_labelled(x, y, g, out, clean);
+    if (clean || turn == 2) break;
+  }
+  if (turn == 0) return count;
+  double X0[3], X1[3];                                       // the caller's first and second point: after one turn in slots 2 and 0
+#pragma unroll
+  for (int k = 0; k < 3; ++k) X0[k] = turn == 1 ? g.X[2][k] : g.X[1][k], X1[k] = turn == 1 ? g.X[0][k] : g.X[2][k];
+  // insertion sort of at most four poses by u under the caller's labelling
+  for (int i = 1; i < count; ++i)
+    for (int j = i; j > 0; --j) {
+      double* a = out + 12 * (j - 1);
+      double* b = out + 12 * j;
+      if (!(depth_under(b, X1) * depth_under(a, X0) < depth_under(a, X1) * depth_under(b, X0))) break;
+      for (int k = 0; k < 12; ++k) {
+        const double v = a[k];
+        a[k] = b[k], b[k] = v;
+      }
+    }
+  return count;
+}
+
+// The problem in arrays (the host programs): x, y and world (3, 3).
+struct ArrayLoad {
+  const double* x;
+  const double* y;
+  const double* world;
+  __host__ __device__ void operator()(int turn, double (&xo)[3], double (&yo)[3], Triangle& g) const {
+    for (int i = 0; i < 3; ++i) {
+      const int k = (i + turn) % 3;
+      xo[i] = x[k], yo[i] = y[k];
+      for (int c = 0; c < 3; ++c) g.X[i][c] = world[3 * k + c];
+    }
+  }
+};
+
+// solve_p3p_turning on a problem in arrays, g.X filled by the caller: what the host programs call.
+__host__ __device__ __forceinline__ int solve_p3p(const double (&x)[3], const double (&y)[3], Triangle& g, double* out) {
+  double world[9];
+  for (int i = 0; i < 9; ++i) world[i] = g.X[i / 3][i % 3];
+  return solve_p3p_turning(ArrayLoad{x, y, world}, g, out);
 }
 
 struct Correspondences { const double* __restrict__ rays_n; const double* __restrict__ xyz; };   // normalised (x, y); world points
@@ -261,16 +372,23 @@ struct P3P {
   static bool usable(Data d) { return d.rays_n && d.xyz; }
   static __device__ __forceinline__ int solve(Data d, long long lo, const int (&s)[3], double*, int, double* out) {
     Triangle g;
-    double x[3], y[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const double* r = d.rays_n + (lo + s[i]) * 2;
-      const double* w = d.xyz + (lo + s[i]) * 3;
-      x[i] = r[0], y[i] = r[1];
-      g.X[i][0] = w[0], g.X[i][1] = w[1], g.X[i][2] = w[2];
-    }
-    return solve_p3p(x, y, g, out);
+    return solve_p3p_turning(SampleLoad{d, lo, s[0], s[1], s[2]}, g, out);
   }
+  struct SampleLoad {                                        // reads the sample's points from memory, turned by selects on the indices
+    Data d;
+    long long lo;
+    int s0, s1, s2;
+    __device__ __forceinline__ void operator()(int turn, double (&x)[3], double (&y)[3], Triangle& g) const {
+      const int idx[3] = {turn == 0 ? s0 : turn == 1 ? s1 : s2, turn == 0 ? s1 : turn == 1 ? s2 : s0, turn == 0 ? s2 : turn == 1 ? s0 : s1};
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double* r = d.rays_n + (lo + idx[i]) * 2;
+        const double* w = d.xyz + (lo + idx[i]) * 3;
+        x[i] = r[0], y[i] = r[1];
+        g.X[i][0] = w[0], g.X[i][1] = w[1], g.X[i][2] = w[2];
+      }
+    }
+  };
 };
 
 // ---- scoring ------------------------------------------------------------------------------------------------------------------

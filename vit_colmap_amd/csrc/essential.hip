@@ -12,7 +12,8 @@
 //   3. elimination  Gauss-Jordan with partial pivoting on the first ten columns; every loop is fully unrolled, every index a
 //                   compile-time constant and a row exchange a pair of selects, so the matrix has no run-time index
 //   4. polynomial   rows e..j give a 3x3 matrix B(z) of polynomials with B(z) (x, y, 1)' = 0; det B(z) has degree 10
-//   5. real roots   in [-1, 1] for the polynomial and, for |z| > 1, in (-1, 1) for its reversal in w = 1 / z; the roots of
+//   5. real roots   in [-e, e] for the polynomial and, for |z| > e, in (-1 / e, 1 / e) for its reversal in w = 1 / z (e just
+//                   above 1, so that a root at |z| = 1 lies inside the first range: minimal_solver.h kSeamEnd); the roots of
 //                   the k-th derivative bracket those of the (k-1)-th, each bracket is bisected at most 64 times
 //   6. back-substitution  (x, y, 1) is the null vector of B(z) (the largest cross product of two rows); at most three
 //                   Gauss-Newton steps on the ten constraints themselves, evaluated on the orthonormal basis, take out the
@@ -225,9 +226,9 @@ struct Poly10 {
   __host__ __device__ __forceinline__ double operator[](int i) const { return reversed ? a[10 - i] : a[i]; }
 };
 
-// The real roots in [-1, 1] of sum a[i] t^i (reversed: of sum a[10 - i] t^i), ascending, into the list the function
-// returns through `roots`; -> their number.  Level k works on the k-th derivative over k!, whose coefficients are
-// a[i + k] binomial(i + k, k); its roots in [-1, 1] and the two ends split the interval into pieces on which the
+// The real roots in [-e, e], e = vc::kSeamEnd just above 1 (see there), of sum a[i] t^i (reversed: of sum a[10 - i] t^i),
+// ascending, into the list the function returns through `roots`; -> their number.  Level k works on the k-th derivative over k!,
+// whose coefficients are a[i + k] binomial(i + k, k); its roots in [-e, e] and the two ends split the interval into pieces on which the
 // (k - 1)-th derivative is monotone, so a sign change at the ends of a piece brackets exactly one root.
 __host__ __device__ __forceinline__ int real_roots_unit(const Poly10 a, const Strided coef, Strided prev, Strided cur, Strided* roots) {
   int n_prev = 0;
@@ -235,9 +236,9 @@ __host__ __device__ __forceinline__ int real_roots_unit(const Poly10 a, const St
     const int degree = 10 - k;
     vc::derivative_coefficients(coef, degree, k, a);
     int n_cur = 0;
-    double lo = -1.0, f_lo = vc::horner(coef, degree, lo);
+    double lo = -vc::kSeamEnd, f_lo = vc::horner(coef, degree, lo);
     for (int s = 0; s <= n_prev; ++s) {
-      const double hi = s < n_prev ? prev[s] : 1.0;
+      const double hi = s < n_prev ? prev[s] : vc::kSeamEnd;
       const double f_hi = vc::horner(coef, degree, hi);
       const double root = vc::root_of_piece(coef, degree, lo, hi, f_lo, f_hi);
       if (root == root && n_cur < kMaxSolutions) cur[n_cur++] = root;
@@ -456,17 +457,17 @@ __host__ __device__ __forceinline__ int solve_five_point(const double (&x1)[5], 
   const int n_dir = real_roots_unit({poly, false}, coef, r0, r1, &roots);
   for (int i = 0; i < n_dir; ++i) mid[i] = roots[i];
   const int n_rev = real_roots_unit({poly, true}, coef, r0, r1, &roots);
-  // ascending z: the roots below -1 (w in (-1, 0), descending), those in [-1, 1], those above 1 (w in (0, 1), descending)
+  // ascending z: the roots below -e (w in (-1 / e, 0), descending), those in [-e, e], those above e (w in (0, 1 / e), descending)
   int count = 0;
   for (int i = n_rev - 1; i >= 0; --i) {
     const double w = roots[i];
-    if (w < 0.0 && w > -1.0 && count < kMaxSolutions && back_substitute(bx, by, b1, n, w, true, out_e + 9 * count)) ++count;
+    if (w < 0.0 && w > -vc::kSeamInv && count < kMaxSolutions && back_substitute(bx, by, b1, n, w, true, out_e + 9 * count)) ++count;
   }
   for (int i = 0; i < n_dir; ++i)
     if (count < kMaxSolutions && back_substitute(bx, by, b1, n, mid[i], false, out_e + 9 * count)) ++count;
   for (int i = n_rev - 1; i >= 0; --i) {
     const double w = roots[i];
-    if (w > 0.0 && w < 1.0 && count < kMaxSolutions && back_substitute(bx, by, b1, n, w, true, out_e + 9 * count)) ++count;
+    if (w > 0.0 && w < vc::kSeamInv && count < kMaxSolutions && back_substitute(bx, by, b1, n, w, true, out_e + 9 * count)) ++count;
   }
   return count;
 }

@@ -16,6 +16,13 @@ namespace vc {
 
 constexpr int kSolverWave = 64;
 constexpr int kBisections = 64;
+// Both solvers look for a root variable of magnitude up to 1 in the polynomial itself and for a larger one through its
+// reciprocal in the reversed polynomial.  A root on the seam between the two (P3P: two points equally far from the camera) shows
+// either range only a rounding-sized value at its end, of either sign, so no sign change brackets it.  The direct range therefore
+// reaches past the seam, to kSeamEnd, and a reversed root counts only below 1 / kSeamEnd: a root at 1 is inside the direct
+// range and is reported once.  The new seam lies at no value that a symmetry of the scene produces.
+constexpr double kSeamEnd = 1.0 + 1.0 / 1024.0;
+constexpr double kSeamInv = 1.0 / kSeamEnd;
 
 // sum c[i] t^i over i <= degree
 template <typename C>
