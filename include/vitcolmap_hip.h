@@ -295,6 +295,32 @@ int vc_triangulate_tracks(const double* obs_xy, const int32_t* obs_cam, const in
                           uint8_t* out_mask, int32_t* out_count, double* out_error, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Keypoint undistortion: the pixel an ideal pinhole camera with the same K would see in place of
+ * a raw keypoint of a camera with known distortion, one keypoint per lane, float64 in single operations in the written order
+ * (left to right, the usual precedence; no fused multiply-add, no library call).  Specification: tests/util_undistort.py.
+ *   xy         [n][2] float32: raw pixel keypoints as the database holds them
+ *   cam        [n] int32: the keypoint's slot into cams
+ *   cams       [n_cams][8] float64: fx, fy, cx, cy, k1, k2, p1, p2, COLMAP's OPENCV parameterisation; SIMPLE_RADIAL and RADIAL
+ *              are the cases p1 = p2 = 0, SIMPLE_RADIAL also k2 = 0
+ *   out_xy     [n][2] float64: (fx x + cx, fy y + cy) with (x, y) the undistorted normalised point; NaN where invalid
+ *   out_valid  [n] uint8: 1 where the iteration stopped, else 0
+ * The rule for a keypoint (u, v), every value float64:
+ *   start      xd = (u - cx) / fx, yd = (v - cy) / fy, (x, y) = (xd, yd)
+ *   iterate    rho = x x + y y, s = 1 + k1 rho + k2 rho rho, e = 2 (k1 + 2 k2 rho)
+ *              gx = x s + 2 p1 x y + p2 (rho + 2 x x) - xd, gy = y s + p1 (rho + 2 y y) + 2 p2 x y - yd
+ *              a = s + x x e + 2 p1 y + 6 p2 x, b = x y e + 2 p1 x + 2 p2 y, d = s + y y e + 6 p1 y + 2 p2 x
+ *              det = a d - b b; not det > 0 (NaN included) at any iterate: the keypoint is invalid
+ *   step       sx = (d gx - b gy) / det, sy = (a gy - b gx) / det, x = x - sx, y = y - sy
+ *   stop       valid once sx sx + sy sy <= 1e-24, within at most 20 steps (a bound: 12 were the most met); invalid otherwise
+ * With every distortion parameter zero the first step is exactly 0 and out_xy = fx ((u - cx) / fx) + cx.
+ * n == 0: VC_OK whatever the pointers are, nothing launched.  A null pointer, a negative size, n_cams == 0 with n > 0, or
+ * a slot of cam outside [0, n_cams): VC_ERR_INVALID_ARG, nothing written.  The slots are device data, so this entry point,
+ * unlike the others, waits for the stream once (a one-flag check kernel) before the launch that writes.
+ * ------------------------------------------------------------------------------------------ */
+int vc_undistort_points(const float* xy, const int32_t* cam, int n, const double* cams, int n_cams, double* out_xy,
+                        uint8_t* out_valid, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bundle adjustment: the three steps of one Levenberg-Marquardt iteration over every pose and
  * every point, by the Schur complement of the points; float64 in single operations in the written order, the only library
  * call is sqrt, no atomics: two calls return the same bytes.  The caller solves S dc = -g between the last two and runs the

@@ -9,9 +9,10 @@ Gauss-Newton under that loss ("The loss" in §4.2k; specification: tests/util_bu
 vc_ba_linearize_points_loss, whose outputs the other kernels take as they are.  With `refine_distortion` it also refines the radial
 distortion of SIMPLE_RADIAL (k1) and RADIAL (k1, k2) cameras from the values their params carry ("The distortion" in §4.2k;
 specification: tests/util_bundle_radial.py): the same loop on the _radial entry points, six unknowns per group in the border.
+With `known_distortion` the grown model was solved on undistorted keypoints; the adjustment then takes the raw
+observations and the known (k1, k2) of every camera as `cam_dist`, held unless refine_distortion frees them.
 Still missing on the way to a mapper: adjustment per round and local adjustment, re-triangulation, merging of points; among the
-intrinsics a known non-zero distortion into the solvers (undistorted points in front of E, P3P and triangulation), OPENCV's
-tangential terms and the principal point from the command line.
+intrinsics OPENCV's tangential terms.
 
 Where the work runs
   HIP     per iteration vc_ba_linearize_points (one point per lane: residuals, Jacobians, V^-1, the cost), vc_ba_reduce_cameras
@@ -31,7 +32,7 @@ from ..matching._common import MAX_ERROR
 from ..matching.essential import rot_to_quat
 from .absolute_pose import FILTER_MIN_TRI_ANGLE
 from .grow import build_sparse_model
-from .seed import SparseModel, _pixel_errors, _read_database
+from .seed import SparseModel, _pixel_errors, _pixel_errors_radial, _read_database
 
 logger = logging.getLogger(__name__)
 
@@ -241,20 +242,9 @@ def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
     return bool(np.any(np.triu(np.ones_like(dots, bool), 1) & ((dots <= 0) | (cross2 >= tan2 * dots * dots))))
 
 
-def _pixel_errors_radial(K, k, R, t, xyz, obs):
-    """seed._pixel_errors under the distortion k = (k1, k2): the pixel is K (xu s, xv s, 1), s = 1 + k1 rho + k2 rho rho."""
-    Xc = xyz @ R.T + t
-    with np.errstate(all="ignore"):
-        xu, xv = Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2]
-        rho = xu * xu + xv * xv
-        s = 1.0 + k[0] * rho + k[1] * rho * rho
-        p = np.stack([K[0, 0] * (xu * s) + K[0, 2], K[1, 1] * (xv * s) + K[1, 2]], axis=1)
-        err = np.linalg.norm(p - obs, axis=1)
-    return np.where(Xc[:, 2] > 0, err, np.inf)
-
-
 def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
-                         grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False) -> SparseModel:
+                         grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False,
+                         known_distortion=False, undistort_fn=None) -> SparseModel:
     """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
     is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
     Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
@@ -275,15 +265,30 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     are free.  bundle_fn is then also given cam_group=, intr_mask= (bit 5: k1 held, bit 6: k2 held), max_iterations=
     REFINE_MAX_ITERATIONS and cam_dist= (n_cams, 2), and its report carries `cam_dist`; the cameras carry the refined k (params[3],
     or params[3:5]), the filter and `error` use the distorted projection and `intrinsics` has six numbers per camera: fx, fy, cx,
-    cy, k1, k2.  Raises ValueError above VC_BA_MAX_GROUPS_RADIAL cameras."""
+    cy, k1, k2.  Raises ValueError above VC_BA_MAX_GROUPS_RADIAL cameras.
+    `known_distortion` (§4.2l; `undistort_fn` as in build_sparse_model, used only where `grown` is not given): the model was grown on
+    undistorted keypoints and its `xys` are the raw ones, so the adjustment gets the raw observations and, where a registered
+    camera has a non-zero k, cam_dist= the known (k1, k2) of every slot: held without refine_distortion (with refine_focal_length
+    alone the groups then carry bits 5 and 6 and the limit is VC_BA_MAX_GROUPS_RADIAL), the starting values with it, as
+    before.  The filter and `error` use the distorted projection.  Without the option exactly the calls described above."""
     bundle_fn = bundle_fn or bundle_adjust
     check_loss(loss, loss_scale)
     loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=float(loss_scale))
     if grown is None:
-        grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn)
-    _, _, K, _, _ = _read_database(database_path)
+        known_args = dict(known_distortion=True, undistort_fn=undistort_fn) if known_distortion else {}
+        grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, **known_args)
     ids, pids = sorted(grown.images), sorted(grown.points3D)
     slot = {i: s for s, i in enumerate(ids)}
+    known_dist = None
+    if known_distortion:
+        from ..matching.undistort import camera_calibration
+
+        calibration = {i: camera_calibration(grown.cameras[grown.images[i]["camera_id"]]) for i in ids}
+        K = {i: c[0] for i, c in calibration.items()}
+        if any(c[1].any() for c in calibration.values()):
+            known_dist = np.array([calibration[i][1][:2] for i in ids], np.float64).reshape(-1, 2)
+    else:
+        _, _, K, _, _ = _read_database(database_path)
     cams = np.stack([np.concatenate([_quat_to_rot(grown.images[i]["qvec"]).reshape(9), np.asarray(grown.images[i]["tvec"], np.float64),
                                      [K[i][0, 0], K[i][1, 1], K[i][0, 2], K[i][1, 2]]]) for i in ids])
     points = np.array([grown.points3D[pid]["xyz"] for pid in pids], np.float64).reshape(-1, 3)
@@ -327,16 +332,27 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
         dist = np.array(report["cam_dist"], np.float64).reshape(-1, 2)
     elif refine_focal_length:
         from .. import _lib
-        from .bundle_intr import HOLD_CX, HOLD_CY, REFINE_MAX_ITERATIONS, TIED, has_one_focal
+        from .bundle_intr import HOLD_CX, HOLD_CY, HOLD_K1, HOLD_K2, REFINE_MAX_ITERATIONS, TIED, has_one_focal
 
         cids = sorted({grown.images[i]["camera_id"] for i in ids})
-        if len(cids) > _lib.VC_BA_MAX_GROUPS:
+        limit, name = ((_lib.VC_BA_MAX_GROUPS, "VC_BA_MAX_GROUPS") if known_dist is None else
+                       (_lib.VC_BA_MAX_GROUPS_RADIAL, "VC_BA_MAX_GROUPS_RADIAL"))
+        if len(cids) > limit:
             raise ValueError(f"refine_focal_length: the registered images have {len(cids)} cameras, the border kernels hold at most "
-                             f"{_lib.VC_BA_MAX_GROUPS} groups of intrinsics (VC_BA_MAX_GROUPS)")
+                             f"{limit} groups of intrinsics ({name})")
         cam_group = np.array([cids.index(grown.images[i]["camera_id"]) for i in ids], np.int32)
         intr_mask = np.array([HOLD_CX | HOLD_CY | (TIED if has_one_focal(grown.cameras[c]) else 0) for c in cids], np.uint8)
-        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group, intr_mask=intr_mask,
-                                         max_iterations=REFINE_MAX_ITERATIONS, **loss_args)
+        if known_dist is None:
+            cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group, intr_mask=intr_mask,
+                                             max_iterations=REFINE_MAX_ITERATIONS, **loss_args)
+        else:                                                    # the known k stays held beside the free focal (§4.2l)
+            cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group,
+                                             intr_mask=intr_mask | np.uint8(HOLD_K1 | HOLD_K2), max_iterations=REFINE_MAX_ITERATIONS,
+                                             cam_dist=known_dist, **loss_args)
+            dist = known_dist
+    elif known_dist is not None:
+        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_dist=known_dist, **loss_args)
+        dist = known_dist
     else:
         cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, **loss_args)
     cams, points = np.array(cams, np.float64), np.array(points, np.float64)

@@ -1,7 +1,9 @@
 """Growth of the seed model: the tracks of the match graph are triangulated under the registered poses
 and the remaining images registered against the new points, in rounds, until a round adds neither a point nor an image.
 It is still not a mapper: no bundle adjustment here (mapping/bundle.py adjusts the result once, §4.2k), no re-triangulation or
-merging of existing points, no point filtering after the rounds, no distortion inside the rounds (a SIMPLE_RADIAL or RADIAL camera with k = 0 is grown under the pinhole assumption and mapping/bundle.py refines k afterwards).  Specification: tests/util_mapper.py (`grow_model`).  This build's own published rule;
+merging of existing points, no point filtering after the rounds, no distortion inside the rounds: a SIMPLE_RADIAL or RADIAL
+camera with k = 0 is grown under the pinhole assumption and mapping/bundle.py refines k afterwards; one with a known non-zero k
+is, with `known_distortion`, grown on keypoints that vc_undistort_points undistorted first.  Specification: tests/util_mapper.py (`grow_model`).  This build's own published rule;
 parity with COLMAP's mapper is unpinned.
 
 Where the work runs
@@ -17,7 +19,7 @@ import numpy as np
 
 from ..database.colmap_db import _quat_to_rot
 from .absolute_pose import ABS_POSE_MIN_NUM_INLIERS, estimate_absolute_poses
-from .seed import SparseModel, _pixel_errors, _read_database, _seed_model
+from .seed import SparseModel, _observation_errors, _read_database, _seed_model
 
 logger = logging.getLogger(__name__)
 
@@ -71,14 +73,20 @@ def _components(kps, K, rows):
     return comps
 
 
-def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None) -> SparseModel:
+def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, known_distortion=False,
+                       undistort_fn=None) -> SparseModel:
     """Read a matched database -> the seed model grown by rounds.  Raises the seed model's ValueErrors unchanged.
     `two_view_pose_fn` and `estimate_fn` as in build_seed_model; `triangulate_fn(obs_xy, obs_cam, offsets, cams, seeds,
-    device) -> (xyz, mask, count, error)` on numpy arrays replaces the triangulation launch (tests)."""
+    device) -> (xyz, mask, count, error)` on numpy arrays replaces the triangulation launch (tests).
+    `known_distortion`, `undistort_fn` as in build_seed_model (§4.2l): the seed and every round solve on the undistorted
+    keypoints, a keypoint that does not invert is in no track, `xys` are the raw keypoints and `error` uses the distorted
+    projection."""
     estimate_fn = estimate_fn or estimate_absolute_poses
     triangulate_fn = triangulate_fn or _gpu_triangulate
-    database = _read_database(database_path)
-    images, cameras, K, kps, rows = database
+    database = _read_database(database_path, True, undistort_fn, device) if known_distortion else _read_database(database_path)
+    images, cameras, K, kps, rows = database[:5]
+    known = database[5] if len(database) > 5 else None
+    raw = kps if known is None else known["raw"]
     seed = _seed_model(database, device, two_view_pose_fn, estimate_fn)
 
     poses = {i: (_quat_to_rot(im["qvec"]), np.asarray(im["tvec"], np.float64), im["qvec"]) for i, im in seed.images.items()}
@@ -154,12 +162,12 @@ def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, esti
     for i, (_, t, q) in sorted(poses.items()):
         cid = images[i].camera_id
         model.cameras[cid] = cameras[cid]
-        model.images[i] = dict(qvec=q, tvec=t, camera_id=cid, name=images[i].name, xys=kps[i].astype(np.float64),
+        model.images[i] = dict(qvec=q, tvec=t, camera_id=cid, name=images[i].name, xys=raw[i].astype(np.float64),
                                point3D_ids=np.full(len(kps[i]), -1, np.int64))
     for pid in sorted(xyz):
         errs = []
         for i, kp in tracks[pid]:
             model.images[i]["point3D_ids"][kp] = pid
-            errs.append(_pixel_errors(K[i], poses[i][0], poses[i][1], xyz[pid][None], kps[i][kp][None].astype(np.float64))[0])
+            errs.append(_observation_errors(K, kps, known, i, poses[i][0], poses[i][1], xyz[pid][None], kp)[0])
         model.points3D[pid] = dict(xyz=xyz[pid].copy(), rgb=(0, 0, 0), error=float(np.mean(errs)), track=list(tracks[pid]))
     return model

@@ -24,7 +24,9 @@ from .absolute_pose import (ABS_POSE_MIN_NUM_INLIERS, FILTER_MIN_TRI_ANGLE, INIT
 logger = logging.getLogger(__name__)
 
 # SIMPLE_RADIAL and RADIAL only with every distortion parameter zero (camera_prior refuses the others): the model is then grown
-# under the pinhole assumption and the bundle adjustment may refine k from 0 (mapping/bundle.py, refine_distortion)
+# under the pinhole assumption and the bundle adjustment may refine k from 0 (mapping/bundle.py, refine_distortion); with
+# `known_distortion` also with a non-zero k, on undistorted keypoints.  OPENCV is not among them: the
+# adjustment has no tangential terms
 SEED_CAMERA_MODELS = ("SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL")
 
 
@@ -167,38 +169,91 @@ def _pixel_errors(K, R, t, xyz, obs):
     return np.where(Xc[:, 2] > 0, err, np.inf)
 
 
-def _read_database(database_path):
+def _pixel_errors_radial(K, k, R, t, xyz, obs):
+    """_pixel_errors under the distortion k = (k1, k2): the pixel is K (xu s, xv s, 1), s = 1 + k1 rho + k2 rho rho."""
+    Xc = xyz @ R.T + t
+    with np.errstate(all="ignore"):
+        xu, xv = Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2]
+        rho = xu * xu + xv * xv
+        s = 1.0 + k[0] * rho + k[1] * rho * rho
+        p = np.stack([K[0, 0] * (xu * s) + K[0, 2], K[1, 1] * (xv * s) + K[1, 2]], axis=1)
+        err = np.linalg.norm(p - obs, axis=1)
+    return np.where(Xc[:, 2] > 0, err, np.inf)
+
+
+def _read_database(database_path, known_distortion=False, undistort_fn=None, device="cuda"):
     """The rows the seed model and its growth read -> images {image_id: Image}, cameras {camera_id: Camera}, K {image_id: (3, 3)
     or None where the camera has no usable prior or another model}, kps {image_id: float32 (n, 2)}, rows {(i, j), i < j: the
-    two_view_geometries row} of every CALIBRATED or PLANAR row with inliers."""
+    two_view_geometries row} of every CALIBRATED or PLANAR row with inliers.
+    `known_distortion`: a sixth entry follows, `known` = dict(raw {image_id: the keypoints as the database
+    holds them}, dist {image_id: (k1, k2)} of the images that were undistorted).  K is then also usable for a flagged
+    SIMPLE_RADIAL or RADIAL camera with a non-zero k (matching.undistort.camera_calibration; OPENCV stays refused:
+    SEED_CAMERA_MODELS), the kps of such an image are its undistorted pixels in float64, NaN where a keypoint does not invert,
+    and the rows have lost the inlier matches that touch such a keypoint, so it is in no track.  `undistort_fn(xy, cam, cams,
+    device) -> (xy64, valid)` on numpy arrays replaces the launch of vc_undistort_points (tests)."""
     with ColmapDatabase.open_database(str(database_path)) as db:
         images = {im.image_id: im for im in db.read_all_images()}
-        cameras, K, kps = {}, {}, {}
+        cameras, K, kps, distorted = {}, {}, {}, {}
         for iid, im in images.items():
             if im.camera_id not in cameras:
                 cameras[im.camera_id] = db.read_camera(im.camera_id)
             cam = cameras[im.camera_id]
             Kc, ok, _ = camera_prior(cam)
             K[iid] = Kc if ok and cam.model in SEED_CAMERA_MODELS else None
+            if known_distortion and K[iid] is None and cam.model in SEED_CAMERA_MODELS:
+                from ..matching.undistort import camera_calibration
+
+                Kc, dist, usable = camera_calibration(cam)
+                if usable:
+                    K[iid], distorted[iid] = Kc, (Kc, dist)
             kp = db.read_keypoints(iid)
             kps[iid] = np.zeros((0, 2), np.float32) if kp is None else kp[:, :2]
         rows = {}
         for i, j, n, config in db.read_two_view_geometry_pairs():
             if n > 0 and config in (CONFIG_CALIBRATED, CONFIG_PLANAR) and i in images and j in images:
                 rows[(i, j)] = db.read_two_view_geometry(i, j)
-    return images, cameras, K, kps, rows
+    if not known_distortion:
+        return images, cameras, K, kps, rows
+    from ..matching.undistort import undistort_images
+
+    known = dict(raw=dict(kps), dist={iid: (float(d[0]), float(d[1])) for iid, (_, d) in distorted.items()})
+    kps, invalid = dict(kps), 0
+    for iid, (xy64, valid) in undistort_images(known["raw"], distorted, device, undistort_fn).items():
+        kps[iid] = np.where(valid[:, None], xy64, np.nan)
+        invalid += int((~valid).sum())
+    for (i, j), g in rows.items():
+        m = g["inlier_matches"].astype(np.int64).reshape(-1, 2)
+        keep = np.isfinite(kps[i][m[:, 0]]).all(axis=1) & np.isfinite(kps[j][m[:, 1]]).all(axis=1)
+        if not keep.all():
+            rows[(i, j)] = dict(g, inlier_matches=g["inlier_matches"][keep])
+    logger.info("known distortion: the keypoints of %d of %d images undistorted (%d do not invert)", len(distorted), len(images), invalid)
+    return images, cameras, K, kps, rows, known
 
 
-def build_seed_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None) -> SparseModel:
+def _observation_errors(K, kps, known, iid, R, t, xyz, kp):
+    """The pixel error of the point(s) xyz (n, 3) at keypoint(s) `kp` of image iid: against the keypoints the solvers used or,
+    for an image that was undistorted (§4.2l), by the distorted projection against the raw keypoints."""
+    if known is None or iid not in known["dist"]:
+        return _pixel_errors(K[iid], R, t, xyz, kps[iid][kp].astype(np.float64).reshape(-1, 2))
+    return _pixel_errors_radial(K[iid], known["dist"][iid], R, t, xyz, known["raw"][iid][kp].astype(np.float64).reshape(-1, 2))
+
+
+def build_seed_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, known_distortion=False,
+                     undistort_fn=None) -> SparseModel:
     """Read a matched database -> the seed model.  Raises ValueError, naming the condition, when no pair can start it.
-    `two_view_pose_fn(xn_rows, cand, device)` and `estimate_fn(problems, device)` replace the two GPU steps (tests)."""
-    return _seed_model(_read_database(database_path), device, two_view_pose_fn, estimate_fn)
+    `two_view_pose_fn(xn_rows, cand, device)` and `estimate_fn(problems, device)` replace the two GPU steps (tests).
+    `known_distortion` (§4.2l): the model is solved on the undistorted keypoints of the flagged SIMPLE_RADIAL and RADIAL cameras
+    (`_read_database`); its `xys` are the raw keypoints, as COLMAP's are, and `error` uses the distorted projection."""
+    database = _read_database(database_path, True, undistort_fn, device) if known_distortion else _read_database(database_path)
+    return _seed_model(database, device, two_view_pose_fn, estimate_fn)
 
 
 def _seed_model(database, device, two_view_pose_fn, estimate_fn):
     two_view_pose_fn = two_view_pose_fn or _gpu_two_view_pose
     estimate_fn = estimate_fn or estimate_absolute_poses
-    images, cameras, K, kps, rows = database
+    images, cameras, K, kps, rows = database[:5]
+    known = database[5] if len(database) > 5 else None                 # the raw keypoints and k of undistorted images (§4.2l)
+    raw = kps if known is None else known["raw"]
     geoms = {pair: g for pair, g in rows.items() if g["config"] == CONFIG_CALIBRATED}
 
     def directed(i, j):
@@ -276,13 +331,13 @@ def _seed_model(database, device, two_view_pose_fn, estimate_fn):
     for iid, (q, tv) in sorted(poses.items()):
         cid = images[iid].camera_id
         model.cameras[cid] = cameras[cid]
-        model.images[iid] = dict(qvec=q, tvec=tv, camera_id=cid, name=images[iid].name, xys=kps[iid].astype(np.float64),
+        model.images[iid] = dict(qvec=q, tvec=tv, camera_id=cid, name=images[iid].name, xys=raw[iid].astype(np.float64),
                                  point3D_ids=np.full(len(kps[iid]), -1, np.int64))
     for k, track in enumerate(tracks):
         errs = []
         for iid, kp in track:
             model.images[iid]["point3D_ids"][kp] = k + 1
             q, tv = poses[iid]
-            errs.append(_pixel_errors(K[iid], _quat_to_rot(q), tv, xyz[k][None], kps[iid][kp][None].astype(np.float64))[0])
+            errs.append(_observation_errors(K, kps, known, iid, _quat_to_rot(q), tv, xyz[k][None], kp)[0])
         model.points3D[k + 1] = dict(xyz=xyz[k].copy(), rgb=(0, 0, 0), error=float(np.mean(errs)), track=list(track))
     return model

@@ -40,9 +40,10 @@ def camera_prior(camera):
     return K, flagged and plain, flagged and not plain
 
 
-def camera_table(db, ids):
+def camera_table(db, ids, warn_distorted=True):
     """(K float64 (n, 3, 3), prior uint8 (n,)) for the images `ids` of an open database (None: no row, no prior): the form
-    the cameras travel in, next to the keypoints.  A flagged camera with distortion is logged once and has no prior."""
+    the cameras travel in, next to the keypoints.  A flagged camera with distortion is logged once and has no prior
+    (`warn_distorted=False`: not logged, where matching/undistort.py gives it one afterwards)."""
     image_camera = {im.image_id: im.camera_id for im in db.read_all_images()}
     cams, warned = {}, set()
     K = np.tile(np.eye(3), (len(ids), 1, 1))
@@ -55,7 +56,7 @@ def camera_table(db, ids):
             cams[cid] = camera_prior(db.read_camera(cid))
         K[k], ok, distorted = cams[cid]
         prior[k] = ok
-        if distorted and cid not in warned:
+        if distorted and warn_distorted and cid not in warned:
             warned.add(cid)
             logger.warning("camera %d has a focal-length prior and non-zero distortion: its pairs are verified without the prior",
                            cid)

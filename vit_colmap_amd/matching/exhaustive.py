@@ -33,6 +33,7 @@ from .hip_matcher import (MODEL_KIND, exhaustive_pairs, match_pairs, match_pairs
                           prepare_descriptors)
 from .two_view import (CONFIG_DEGENERATE, CONFIG_PANORAMIC, CONFIG_PLANAR, MAX_ERROR, read_keypoints_by_index,
                        verify_pair_lists, write_two_view_rows)
+from .undistort import drop_invalid_matches, undistort_for_matching
 
 logger = logging.getLogger(__name__)
 
@@ -56,6 +57,12 @@ def _relative_pose_option(matching_options, sift_options) -> bool:
     return bool(getattr(opts, "compute_relative_pose", False) or getattr(getattr(opts, "sift", None), "compute_relative_pose", False))
 
 
+def _known_distortion_option(matching_options, sift_options) -> bool:
+    """`known_distortion` of the options object, looked up where `guided_matching` is."""
+    opts = matching_options if matching_options is not None else sift_options
+    return bool(getattr(opts, "known_distortion", False) or getattr(getattr(opts, "sift", None), "known_distortion", False))
+
+
 @dataclass(frozen=True)
 class MatchSettings:
     """What a run reads from its options objects, looked up once."""
@@ -64,13 +71,15 @@ class MatchSettings:
     cross_check: bool
     guided: bool            # the options' guided_matching; needs `verify`
     relative_pose: bool     # the options' compute_relative_pose; needs `verify`
+    known_distortion: bool = False   # the options' known_distortion; needs `verify`
 
     @classmethod
     def from_options(cls, matching_options=None, sift_options=None, verify: bool = True):
         sift = _sift_options(matching_options, sift_options)
         return cls(float(sift.max_ratio), float(sift.max_distance), bool(sift.cross_check),
                    verify and _guided_option(matching_options, sift_options),
-                   verify and _relative_pose_option(matching_options, sift_options))
+                   verify and _relative_pose_option(matching_options, sift_options),
+                   verify and _known_distortion_option(matching_options, sift_options))
 
 
 def new_stats(images: int, pairs: int, ranks: int) -> dict:
@@ -214,7 +223,7 @@ def _unpack_keypoints(arr, cnt):
 
 def match_exhaustive(database_path: str, matching_options=None, sift_options=None, device="cuda",
                      pair_chunk: int = 16384, distributed=None, match_fn=None, verify: bool = True, verify_fn=None,
-                     guided_fn=None) -> dict:
+                     guided_fn=None, undistort_fn=None) -> dict:
     """Returns a small stats dict (pairs, matches, seconds); the result proper is in the database.
     Multi-rank (`distributed`): rank 0 — the only process that touches the SQLite file — reads descriptors and keypoints
     and broadcasts them; EVERY rank matches and geometrically verifies its share of the pair list (pair p -> rank
@@ -233,13 +242,20 @@ def match_exhaustive(database_path: str, matching_options=None, sift_options=Non
     hip_guided_blocks in the CPU tests.
     Relative pose (the options' `compute_relative_pose`, off by default; needs `verify` and usable priors):
     `verify_fn` then also gets the keyword `relative_pose=True`; the stats gain `pose_pairs`, `planar_pairs`,
-    `panoramic_pairs` and `median_tri_angle_deg` (over the posed pairs that are not PANORAMIC)."""
+    `panoramic_pairs` and `median_tri_angle_deg` (over the posed pairs that are not PANORAMIC).
+    Known distortion (the options' `known_distortion`, off by default; needs `verify`): rank 0 replaces the
+    keypoints of every image whose camera is flagged and distorted by their undistorted pixels (one launch of
+    vc_undistort_points) and gives the image a usable prior, so F, H, E, the relative pose and guided matching see an ideal
+    pinhole camera; the matches that touch a keypoint that does not invert reach neither the verifier nor the guided lists
+    (their number is logged and in the stats as `undistort_dropped_matches`), the `matches` table keeps the raw lists,
+    `inlier_matches` stay keypoint indices and the stored F and H relate undistorted pixels.  `undistort_fn(xy, cam, cams,
+    device) -> (xy64, valid)` on numpy arrays replaces the launch in the CPU tests."""
     return match_database(database_path, matching_options, sift_options, device, pair_chunk, distributed, match_fn, verify,
-                          verify_fn, guided_fn)
+                          verify_fn, guided_fn, undistort_fn=undistort_fn)
 
 
 def match_database(database_path, matching_options, sift_options, device, pair_chunk, distributed, match_fn, verify,
-                   verify_fn, guided_fn, select_pairs=None, what="match_exhaustive") -> dict:
+                   verify_fn, guided_fn, select_pairs=None, what="match_exhaustive", undistort_fn=None) -> dict:
     """The database-in / database-out entry that match_exhaustive and matching.retrieval.match_retrieval share; they differ
     only in where the pair list comes from.  `select_pairs` None: every pair (a < b), dealt to the ranks by
     dist.pairs_for_rank.  Otherwise rank 0 calls `select_pairs(block, counts, stats)` once the descriptor blocks are
@@ -264,7 +280,11 @@ def match_database(database_path, matching_options, sift_options, device, pair_c
         kp_arr = kp_cnt = cam_k = cam_prior = None
         if verify and D != 0:
             kp_arr, kp_cnt = _pack_keypoints(read_keypoints_by_index(db, ids), len(ids))
-            cam_k, cam_prior = camera_table(db, ids)                           # focal-length priors
+            if settings.known_distortion:                                      # undistorted pixels, a prior for their images (§4.2l)
+                cam_k, cam_prior = camera_table(db, ids, warn_distorted=False)
+                kp_arr, cam_k, cam_prior = undistort_for_matching(db, ids, kp_arr, kp_cnt, cam_k, cam_prior, device, undistort_fn)
+            else:
+                cam_k, cam_prior = camera_table(db, ids)                       # focal-length priors
             if settings.relative_pose and not cam_prior.any():
                 logger.warning("compute_relative_pose is set and no camera has a usable focal-length prior: it has no effect")
         return ids, D, [block, counts, kp_arr, kp_cnt, cam_k, cam_prior]
@@ -318,8 +338,11 @@ def match_loaded(ids, block, counts, kp_arr, kp_cnt, cameras, all_pairs, my_pair
     takes them as host arrays.  `distributed` False runs every collective step locally, whatever process group exists.
     An error on any rank is raised on every rank (`write_what` names rank 0's writing phase in the others' message).
     `skip_empty_share`: a rank whose share is empty calls neither the matcher nor the verifier.
+    With `settings.known_distortion` (§4.2l) the keypoints are the undistorted ones, NaN where a keypoint does not invert: the
+    matches that touch such a keypoint are dropped from what the verifier gets and from the guided lists, not from `matches`.
     Returns `stats` with the totals filled in — rank 0's, on every rank."""
     s = settings
+    kp_ok = np.isfinite(_host(kp_arr)).all(axis=2) if s.known_distortion and verify and kp_arr is not None else None
     empty = not _host(counts).any()                                            # no descriptors anywhere: every pair is empty
     if s.guided and not empty:
         check_guided_block_size(int(block.shape[1]))                           # before any matching starts, on every rank
@@ -341,10 +364,16 @@ def match_loaded(ids, block, counts, kp_arr, kp_cnt, cameras, all_pairs, my_pair
         if not verify:
             return lists, None
         vdev = device if (verify_fn is not None or torch.cuda.is_available()) else "cpu"
-        results = verify_pair_lists(_unpack_keypoints(kp_arr, kp_cnt), ids, my_pairs, lists, device=vdev, verify_fn=verify_fn,
+        usable = lists if kp_ok is None else drop_invalid_matches(lists, my_pairs, kp_ok)[0]
+        results = verify_pair_lists(_unpack_keypoints(kp_arr, kp_cnt), ids, my_pairs, usable, device=vdev, verify_fn=verify_fn,
                                     cameras=cameras, relative_pose=s.relative_pose)
         if s.guided:
-            rematch_guided(*g_blocks, kp_arr, my_pairs, results, s.max_ratio, s.max_distance, s.cross_check, guided_fn)
+            # a keypoint that does not invert is at no pixel: it is given (0, 0) and its matches are taken out of the lists again
+            rematch_guided(*g_blocks, kp_arr if kp_ok is None else np.nan_to_num(_host(kp_arr)), my_pairs, results, s.max_ratio,
+                           s.max_distance, s.cross_check, guided_fn)
+            if kp_ok is not None:
+                for r, kept in zip(results, drop_invalid_matches([r["inlier_matches"] for r in results], my_pairs, kp_ok)[0]):
+                    r["inlier_matches"] = kept
         return lists, results
 
     t1 = time.perf_counter()
@@ -360,6 +389,11 @@ def match_loaded(ids, block, counts, kp_arr, kp_cnt, cameras, all_pairs, my_pair
             db.write_matches(ids[a], ids[b], m, commit=False)
             stats["matches"] += len(m)
         db.commit()
+        if kp_ok is not None:
+            order = [(int(a), int(b)) for a, b in all_pairs]
+            stats["undistort_dropped_matches"] = drop_invalid_matches([merged[p] for p in order], order, kp_ok)[1]
+            logger.info("known distortion: %d of %d matches touch a keypoint that does not invert and were not verified",
+                        stats["undistort_dropped_matches"], stats["matches"])
         if verified is not None:
             stats["verified_pairs"] = write_two_view_rows(db, ids, verified)
             stats["guided_pairs"] = sum(r["config"] != CONFIG_DEGENERATE for r in verified.values()) if s.guided else 0

@@ -34,6 +34,7 @@ from ..features.base_extractor import add_image_row, camera_policy, default_came
 from ..matching.essential import camera_table
 from ..matching.exhaustive import MatchSettings, match_loaded, new_stats
 from ..matching.hip_matcher import exhaustive_pairs
+from ..matching.undistort import undistort_for_matching
 
 logger = logging.getLogger(__name__)
 
@@ -41,7 +42,11 @@ logger = logging.getLogger(__name__)
 def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn=None, matching_options=None,
                 match_fn=None, do_matching=True, verify=True, device="cuda", batch_size=50, verify_fn=None,
                 camera_params_for=default_camera_params, camera_per_image=False, guided_fn=None,
-                prior_focal_length=False, matcher_type="exhaustive") -> dict:
+                prior_focal_length=False, matcher_type="exhaustive", undistort_fn=None) -> dict:
+    """With the options' `known_distortion` (needs `prior_focal_length`) rank 0 undistorts the gathered
+    keypoints of the flagged, distorted cameras by the helper match_database uses (matching/undistort.py) and broadcasts
+    them with the camera table; the database keeps the raw keypoints.  `undistort_fn` replaces the launch (tests)."""
+    settings = MatchSettings.from_options(matching_options, None, verify)
     if matcher_type != "exhaustive":
         # the in-memory path matches every pair; the choice of pairs exists database to database only
         raise ValueError(f"the sharded in-memory pipeline matches exhaustively: for matcher_type {matcher_type!r} extract to "
@@ -94,30 +99,37 @@ def run_sharded(image_dir, db_path, camera_model, camera_params=None, feature_fn
                                   prior_focal_length)
         db = ColmapDatabase(str(db_path))
         ids = [add_image_row(db, f.name, camera_of(h, w)) if h else None for f, (h, w) in zip(image_files, all_hw)]
-        cameras = camera_table(db.db, ids) if prior_focal_length else None   # (K, usable prior) per file, read back from the rows
+        undistort = prior_focal_length and settings.known_distortion and do_matching
+        cameras = None
+        if prior_focal_length:      # (K, usable prior) per file, read back from the rows; a distorted camera may get its prior below
+            cameras = camera_table(db.db, ids, warn_distorted=False) if undistort else camera_table(db.db, ids)
         d_np = all_desc.cpu().numpy()
         for k, image_id in enumerate(ids):
             if image_id is not None and cnt[k] > 0:
                 db.add_keypoints(image_id, kp_np[k, : cnt[k]])
                 db.add_descriptors(image_id, d_np[k, : cnt[k]])
         db.commit()
-        return ids, cameras
+        if undistort:
+            kp_u, K, prior = undistort_for_matching(db.db, ids, kp_np[:n, :, :2], cnt[:n], *cameras, device, undistort_fn)
+            return ids, (K, prior), kp_u
+        return ids, cameras, None
 
     try:
         rows = vd.run_guarded(write_rows, "writing images / features")
         if not do_matching:
             return stats
         # ---- matching + verification: images with a database row, in id order; pairs dealt round-robin -----------------
-        ids, cameras = vd.broadcast_object(rows, 0)                          # pair ids seed the verification sampler
+        ids, cameras, kp_u = vd.broadcast_object(rows, 0)                    # pair ids seed the verification sampler
+        kp_xy = kp_np[:, :, :2] if kp_u is None else kp_u                  # undistorted where a camera's distortion is known
         keep = np.nonzero(all_readable)[0]
         if cameras is not None:                                             # calibrated pairs
             cameras = (cameras[0][keep], cameras[1][keep])
         m = len(keep)
         stats["pairs"] = m * (m - 1) // 2
         return match_loaded([ids[k] for k in keep], all_desc[torch.from_numpy(keep).to(all_desc.device)],
-                            all_counts[torch.from_numpy(keep).to(all_counts.device)], kp_np[keep][:, :, :2], cnt[keep], cameras,
+                            all_counts[torch.from_numpy(keep).to(all_counts.device)], kp_xy[keep], cnt[keep], cameras,
                             exhaustive_pairs(m).numpy(), vd.pairs_for_rank(m, rank, world),
-                            MatchSettings.from_options(matching_options, None, verify), verify,
+                            settings, verify,
                             db.db if db is not None else None, stats, match_fn=match_fn, verify_fn=verify_fn,
                             guided_fn=guided_fn, device=device, distributed=vd.is_distributed(),
                             write_what="writing matches / two-view geometries")

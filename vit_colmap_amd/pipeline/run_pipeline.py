@@ -14,7 +14,7 @@ from typing import Optional
 from ..database.colmap_db import ColmapDatabase
 from ..features.base_extractor import BaseExtractor
 from ..features.dummy_extractor import DummyExtractor
-from ..utils.config import Config
+from ..utils.config import CAMERA_PARAM_NAMES, Config, parse_camera_params
 
 logger = logging.getLogger(__name__)
 
@@ -91,6 +91,12 @@ class Pipeline:
         if not 0.0 < ba_loss_scale < float("inf"):
             raise ValueError(f"ba_loss_scale must be a finite positive number of pixels (got {ba_loss_scale})")
         loss_args = {} if ba_loss == "trivial" else dict(loss=ba_loss, loss_scale=ba_loss_scale)
+        known_distortion = bool(getattr(self.config.camera, "known_distortion", False))
+        if known_distortion and not self.config.camera.prior_focal_length:   # it is what makes the intrinsics trusted (§4.2l)
+            raise ValueError("known_distortion needs camera.prior_focal_length (--prior-focal-length)")
+        if camera_params is not None and camera_model in CAMERA_PARAM_NAMES:   # the count, before any database is created
+            camera_params = parse_camera_params(camera_params, camera_model)
+        known_args = dict(known_distortion=True) if known_distortion else {}
         for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
             if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
                 continue
@@ -117,7 +123,7 @@ class Pipeline:
                                           camera_params_for=extractor.camera_params_for,
                                           camera_per_image=extractor.camera_per_image,
                                           prior_focal_length=extractor.prior_focal_length,
-                                          matching_options=self.config.matching.to_matching_options(),
+                                          matching_options=self._matching_options(),
                                           do_matching=self.config.do_matching, device=str(getattr(extractor, "device", "cuda")),
                                           matcher_type=matcher_type)
             if vd.rank_world()[0] != 0:
@@ -133,7 +139,7 @@ class Pipeline:
                 from ..matching import match_exhaustive, match_retrieval
 
                 logger.info("Running feature matching...")
-                opts = self.config.matching.to_matching_options()
+                opts = self._matching_options()
                 if matcher_type == "retrieval":
                     self.last_stats = match_retrieval(database_path=str(db_path), matching_options=opts,
                                                       num_neighbors=num_neighbors)
@@ -145,16 +151,17 @@ class Pipeline:
                 logger.info(f"Matched {num_pairs} image pairs ({db_check.num_verified_image_pairs()} geometrically verified)")
 
         if seed_model:                                          # under torchrun only rank 0 arrives here
-            self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")))
+            self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), **known_args)
         if sparse_model:
             if refine_distortion:
                 self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True,
-                                         refine_focal_length=refine_focal_length, refine_distortion=True, **loss_args)
+                                         refine_focal_length=refine_focal_length, refine_distortion=True, **loss_args, **known_args)
             elif refine_focal_length:
                 self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True, refine_focal_length=True,
-                                         **loss_args)
+                                         **loss_args, **known_args)
             else:
-                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment, **loss_args)
+                self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment, **loss_args,
+                                         **known_args)
 
         reconstructions = None
         if self.config.do_reconstruction:
@@ -180,12 +187,21 @@ class Pipeline:
             self.extract_and_export_metrics(db_path, output_dir, reconstructions, dataset, scene, results_dir)
         return reconstructions
 
-    def _write_seed_model(self, db_path, output_dir, device):
-        """output_dir/sparse/seed and `last_stats["seed_model"]`; a scene without an admissible initial pair writes nothing."""
+    def _matching_options(self):
+        """The matching options with `camera.known_distortion` on them (§4.2l), set only where it is on."""
+        opts = self.config.matching.to_matching_options()
+        if getattr(self.config.camera, "known_distortion", False):
+            opts.known_distortion = opts.sift.known_distortion = True
+        return opts
+
+    def _write_seed_model(self, db_path, output_dir, device, known_distortion=False):
+        """output_dir/sparse/seed and `last_stats["seed_model"]`; a scene without an admissible initial pair writes nothing.
+        `known_distortion`: passed on only where it is on (§4.2l)."""
         from ..mapping import build_seed_model
 
+        known_args = dict(known_distortion=True) if known_distortion else {}
         try:
-            model = build_seed_model(str(db_path), device=device)
+            model = build_seed_model(str(db_path), device=device, **known_args)
         except ValueError as e:
             logger.warning("no seed model written: %s", e)
             return
@@ -195,15 +211,17 @@ class Pipeline:
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
     def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0,
-                            refine_distortion=False):
+                            refine_distortion=False, known_distortion=False):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
         `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
         `refine_focal_length`: that adjustment also refines the cameras' focal lengths; `loss`, `loss_scale`: its loss, passed on
-        only where it is not the trivial one; `refine_distortion`: it also refines k1 (k2) of SIMPLE_RADIAL and RADIAL cameras."""
+        only where it is not the trivial one; `refine_distortion`: it also refines k1 (k2) of SIMPLE_RADIAL and RADIAL cameras;
+        `known_distortion`: both models are built on undistorted keypoints (§4.2l), passed on only where it is on."""
         from ..mapping.grow import build_sparse_model
 
+        known_args = dict(known_distortion=True) if known_distortion else {}
         try:
-            model = build_sparse_model(str(db_path), device=device)
+            model = build_sparse_model(str(db_path), device=device, **known_args)
         except ValueError as e:
             logger.warning("no sparse model written: %s", e)
             return
@@ -217,11 +235,11 @@ class Pipeline:
             loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=loss_scale)
             if refine_distortion:
                 adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=refine_focal_length,
-                                                refine_distortion=True, **loss_args)
+                                                refine_distortion=True, **loss_args, **known_args)
             elif refine_focal_length:
-                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=True, **loss_args)
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=True, **loss_args, **known_args)
             else:
-                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, **loss_args)
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, **loss_args, **known_args)
             adjusted.write_text(str(Path(output_dir) / "sparse" / "adjusted"))
             self.last_stats = dict(self.last_stats, bundle_adjustment=adjusted.stats())
             logger.info("Adjusted model: %d images, %d points, cost %.6g -> %.6g", len(adjusted.images), len(adjusted.points3D),
@@ -255,6 +273,12 @@ def main() -> None:
     ap.add_argument("--camera-model", dest="camera_model", default="SIMPLE_PINHOLE")
     ap.add_argument("--prior-focal-length", dest="prior_focal_length", action="store_true",
                     help="mark the cameras as calibrated: pairs are also verified under an essential matrix")
+    ap.add_argument("--camera-params", dest="camera_params", default=None, metavar="P1,P2,...",
+                    help="the intrinsics of --camera-model as a comma-separated list in COLMAP's order (SIMPLE_RADIAL: f,cx,cy,k; "
+                         "OPENCV: fx,fy,cx,cy,k1,k2,p1,p2); by default f = max(w, h) and the image centre")
+    ap.add_argument("--known-distortion", dest="known_distortion", action="store_true",
+                    help="with --prior-focal-length: trust a non-zero distortion in --camera-params too; keypoints are undistorted "
+                         "on the GPU in front of verification, relative pose, registration and triangulation")
     ap.add_argument("--extractor", choices=["vit", "trainable_vit", "hybrid", "sift", "colmap_sift", "dummy"], default="vit")
     ap.add_argument("--detector", choices=["sift", "fast", "gftt"], default="sift",
                     help="keypoint detector of --extractor hybrid (runs on the GPU)")

@@ -28,6 +28,7 @@ class CameraConfig:
     height: Optional[int] = None
     params: Optional[list[float]] = None
     prior_focal_length: bool = False   # the intrinsics are trusted: pairs are also verified under E (not set by the reference)
+    known_distortion: bool = False     # with prior_focal_length: a non-zero distortion in `params` is trusted too, keypoints are undistorted in front of the solvers (§4.2l)
 
     def get_default_params(self, width: int, height: int) -> list[float]:
         if self.params is not None:
@@ -38,6 +39,27 @@ class CameraConfig:
             return default_camera_params(self.model, width, height)
         except ValueError:
             raise ValueError(f"Unsupported camera model: {self.model}")
+
+
+CAMERA_PARAM_NAMES = {"SIMPLE_PINHOLE": "f, cx, cy", "PINHOLE": "fx, fy, cx, cy", "SIMPLE_RADIAL": "f, cx, cy, k",
+                      "RADIAL": "f, cx, cy, k1, k2", "OPENCV": "fx, fy, cx, cy, k1, k2, p1, p2"}
+
+
+def parse_camera_params(text, model) -> list[float]:
+    """--camera-params: a comma-separated list of floats (or a sequence of numbers) for `model` -> the list; ValueError, naming
+    the model and the count it takes, for another length, an unknown model or something that is no finite number."""
+    if model not in CAMERA_PARAM_NAMES:
+        raise ValueError(f"camera_params: unknown camera model {model!r}, expected one of {', '.join(CAMERA_PARAM_NAMES)}")
+    names = CAMERA_PARAM_NAMES[model]
+    want = len(names.split(", "))
+    fields = [w.strip() for w in text.split(",")] if isinstance(text, str) else list(text)
+    try:
+        params = [float(w) for w in fields]
+    except (TypeError, ValueError):
+        params = None
+    if params is None or len(params) != want or not all(abs(v) < float("inf") for v in params):
+        raise ValueError(f"camera_params: camera model {model} takes {want} finite numbers ({names}), got {text!r}")
+    return params
 
 
 @dataclass
@@ -51,6 +73,7 @@ class SiftMatchingOptions:
     num_threads: int = -1
     guided_matching: bool = False   # pycolmap 3.12 keeps the option here [recalled]
     compute_relative_pose: bool = False   # carried as guided_matching is (COLMAP: TwoViewGeometryOptions [recalled])
+    known_distortion: bool = False   # carried likewise: CameraConfig.known_distortion on its way to the matcher (§4.2l)
 
 
 @dataclass
@@ -61,6 +84,7 @@ class FeatureMatchingOptions:
     num_threads: int = -1
     guided_matching: bool = False   # pycolmap 3.13 moved the option to the outer object [recalled]
     compute_relative_pose: bool = False
+    known_distortion: bool = False
     sift: SiftMatchingOptions = field(default_factory=SiftMatchingOptions)
 
 
@@ -153,6 +177,10 @@ class Config:
             config.camera.model = args.camera_model
         if getattr(args, "prior_focal_length", False):
             config.camera.prior_focal_length = True
+        if getattr(args, "known_distortion", False):
+            config.camera.known_distortion = True
+        if getattr(args, "camera_params", None) is not None:
+            config.camera.params = parse_camera_params(args.camera_params, config.camera.model)
         if hasattr(args, "extractor") and args.extractor:
             config.extractor.extractor_type = args.extractor
         elif hasattr(args, "use_colmap_sift") and args.use_colmap_sift:
