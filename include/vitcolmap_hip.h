@@ -682,6 +682,22 @@ int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int
                       void* out, vc_stream_t stream);
 
 /*
+ * Layouts of a 384-wide bf16 activation tensor [rows][384] between the kernels of a ViT-S block (vc_attention_bf16_l,
+ * vc_linear_xs_bf16_l, vc_mlp_bf16_l).  VC_ACT_ROW_MAJOR: rows of 768 bytes.  VC_ACT_FRAGMENT: the order in which the
+ * 32x32x16 MFMA reads the tensor as its B operand — ceil(rows / 32) blocks of 24 KiB, element (m, k) at byte
+ *   ((m >> 5) * 24 + (k >> 4)) * 1024 + (((k >> 3) & 1) * 32 + (m & 31)) * 16 + (k & 7) * 2;
+ * the buffer holds vc_act_fragment_bytes(rows) bytes, i.e. the row count padded to a multiple of 32.  The kernels never
+ * read the padding's content and may write into it.  The values are the same in both layouts, bit for bit.
+ */
+#define VC_ACT_ROW_MAJOR 0
+#define VC_ACT_FRAGMENT 1
+size_t vc_act_fragment_bytes(long long rows);
+/* vc_attention_bf16 with out in `out_layout`: VC_ACT_FRAGMENT needs n_heads * 64 == 384 (VC_ERR_UNSUPPORTED otherwise);
+ * out is then one tensor of batch * n_tokens rows (a wave's 32 queries may lie in two of its 32-row blocks). */
+int vc_attention_bf16_l(const void* qkv, int batch, int n_tokens, int n_heads, int head_dim, int q_prescaled,
+                        void* out, int out_layout, vc_stream_t stream);
+
+/*
  * Linear layer with fused epilogue (bf16 in, float32 accumulate on MFMA, bf16 out):
  *   out = epi(x W^T + bias),  x [rows][k_in], weight [n_out][k_in] (torch.nn.Linear layout),
  *   bias [n_out], out [rows][n_out].
@@ -764,6 +780,14 @@ int vc_linear_xs_prepare(const float* weight, const float* bias_or_null, const f
 int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias_folded,
                       const void* residual_or_null, void* out, int rows, int n_out, int k_in, int epilogue,
                       int fuse_layernorm, float ln_eps, const void* gelu_table_or_null, vc_stream_t stream);
+/* vc_linear_xs_bf16 with the layouts of x, the residual and out (above).  All VC_ACT_ROW_MAJOR: vc_linear_xs_bf16.
+ * Otherwise x is VC_ACT_FRAGMENT and the call is one of the two a ViT-S block makes: VC_EPI_BIAS with fuse_layernorm and a
+ * row-major out (attn.qkv), or VC_EPI_RESIDUAL without LayerNorm, n_out == 384 and out VC_ACT_FRAGMENT, the residual in
+ * either layout (attn.proj; a residual in fragment order may alias out).  Anything else: VC_ERR_UNSUPPORTED. */
+int vc_linear_xs_bf16_l(const void* x, const void* weight_tiled, const float* bias_folded,
+                        const void* residual_or_null, void* out, int rows, int n_out, int k_in, int epilogue,
+                        int fuse_layernorm, float ln_eps, const void* gelu_table_or_null, int x_layout,
+                        int residual_layout, int out_layout, vc_stream_t stream);
 /*
  * GELU table for VC_EPI_GELU (optional): with a table the epilogue evaluates the GELU as the standard bf16
  * pipeline does — on the bf16-ROUNDED pre-activation, result rounded to bf16, bit for bit
@@ -804,6 +828,12 @@ int vc_mlp_prepare(const float* w1, const float* b1_or_null, const float* ln_gam
                    void* weights_tiled, float* b1_folded, float* b2_out, vc_stream_t stream);
 int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded, const float* b2,
                 const void* gelu_table, int rows, int n_hidden, int dim, float ln_eps, vc_stream_t stream);
+/* vc_mlp_bf16 with layouts (above): both VC_ACT_ROW_MAJOR or both VC_ACT_FRAGMENT update x_inout in place (out_or_null NULL
+ * or x_inout); x VC_ACT_FRAGMENT with out VC_ACT_ROW_MAJOR leaves x_inout as it is and writes the rows to out_or_null, a
+ * buffer of its own (the last block of the stack).  Row-major in, fragment order out: VC_ERR_INVALID_ARG. */
+int vc_mlp_bf16_l(void* x_inout, void* out_or_null, const void* weights_tiled, const float* b1_folded, const float* b2,
+                  const void* gelu_table, int rows, int n_hidden, int dim, float ln_eps, int x_layout, int out_layout,
+                  vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * SIFT with COLMAP's default SiftExtractionOptions, computed as VLFeat's vl_sift does — replaces the

@@ -85,7 +85,8 @@ __device__ inline uint32_t v_off(int key, int byte_in_row) {
 // LAZY = false (q not pre-scaled) needs the multiply by scale_log2e per score anyway and runs the exact pass only.
 constexpr float kLazyTh = 6.0f;
 constexpr float kLMaxPerKey = 64.0f;   // 2^kLazyTh: the fast pass is final for a row with l <= N * this
-template <int QT, bool LAZY>
+// OF: out in the GEMMs' fragment order (include/vitcolmap_hip.h, VC_ACT_FRAGMENT; H * 64 == 384) instead of row-major.
+template <int QT, bool LAZY, bool OF = false>
 __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const __bf16* __restrict__ qkv,
                                                                            __bf16* __restrict__ out, int N, int H,
                                                                            float scale_log2e, int n_units, int nqb) {
@@ -368,8 +369,11 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
   // issue.  Instead v_permlane32_swap gives every lane 16 consecutive d of its query (as in the GEMM epilogues), the wave
   // turns its QT x 32 queries x 64 d through 4 KiB x QT of the K/V ring — idle once every wave is past its last key block —
   // and writes whole rows: 8 queries x 128 contiguous bytes (one head's 64 d) per store instruction, 4 QT per lane.
+  // OF: behind the swap a lane holds two finished 16-byte chunks of its query, d = 32 dt + 16 hh + 8 c .. + 7 — slot
+  // 32 c + (row & 31) of piece 4 h + 2 dt + hh of the flat row's 32-row block — and stores them as they are: no turn
+  // through the ring and no barrier.  batch * N rows are one tensor, so the wave's 32 queries may lie in two blocks.
   typedef uint32_t v4u32a __attribute__((ext_vector_type(4)));
-  __syncthreads();
+  if (!OF) __syncthreads();
   uint8_t* const stg = (uint8_t*)lds + wave_u * (QT * 4096);   // (the scalar copy: no VGPR holds the wave index across the passes)
   auto stg_at = [&](int row, int slot16) { return stg + row * 128 + ((slot16 ^ ((row >> 1) & 7)) << 4); };
 #pragma unroll
@@ -393,11 +397,21 @@ __global__ __launch_bounds__(256, (QT == 1 ? 3 : 2)) void attention_kernel(const
         ep[k + 4] = sw[1];
       }
       const int row = 32 * qt + r;
-      *(v4u32a*)stg_at(row, 4 * dt + 2 * hh) = (v4u32a){ep[0], ep[1], ep[4], ep[5]};
-      *(v4u32a*)stg_at(row, 4 * dt + 2 * hh + 1) = (v4u32a){ep[2], ep[3], ep[6], ep[7]};
+      if (OF) {
+        const int q = q_base + wave_u * (kQW * QT) + row;
+        if (q < N) {
+          const size_t m = (size_t)b * N + q;
+          uint8_t* const dst = (uint8_t*)out + (m >> 5) * (size_t)(24 * 1024) + (size_t)(4 * h + 2 * dt + hh) * 1024 + (m & 31) * 16;
+          *(v4u32a*)dst = (v4u32a){ep[0], ep[1], ep[4], ep[5]};
+          *(v4u32a*)(dst + 512) = (v4u32a){ep[2], ep[3], ep[6], ep[7]};
+        }
+      } else {
+        *(v4u32a*)stg_at(row, 4 * dt + 2 * hh) = (v4u32a){ep[0], ep[1], ep[4], ep[5]};
+        *(v4u32a*)stg_at(row, 4 * dt + 2 * hh + 1) = (v4u32a){ep[2], ep[3], ep[6], ep[7]};
+      }
     }
   }
-  {
+  if (!OF) {
     const int lrow = lane >> 3, lslot = lane & 7;
     const int q_wave0 = q_base + wave_u * (kQW * QT);
 #pragma unroll
@@ -416,8 +430,16 @@ extern "C" {
 
 int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int head_dim, int q_prescaled, void* out,
                       vc_stream_t stream) {
+  return vc_attention_bf16_l(qkv, batch, n_tokens, n_heads, head_dim, q_prescaled, out, VC_ACT_ROW_MAJOR, stream);
+}
+
+int vc_attention_bf16_l(const void* qkv, int batch, int n_tokens, int n_heads, int head_dim, int q_prescaled, void* out,
+                        int out_layout, vc_stream_t stream) {
   if (!qkv || !out || batch < 0 || n_tokens <= 0 || n_heads <= 0) return VC_ERR_INVALID_ARG;
+  if (out_layout != VC_ACT_ROW_MAJOR && out_layout != VC_ACT_FRAGMENT) return VC_ERR_INVALID_ARG;
   if (head_dim != kHD) return VC_ERR_UNSUPPORTED;
+  const bool of = out_layout == VC_ACT_FRAGMENT;
+  if (of && n_heads * kHD != 384) return VC_ERR_UNSUPPORTED;
   if ((((uintptr_t)qkv) | ((uintptr_t)out)) % 16 != 0) return VC_ERR_INVALID_ARG;
   if (batch == 0) return VC_OK;
   // q_prescaled: the q rows already carry 1/sqrt(64) * log2(e) (folded into the qkv projection)
@@ -428,8 +450,13 @@ int vc_attention_bf16(const void* qkv, int batch, int n_tokens, int n_heads, int
   __bf16* po = (__bf16*)out;
   hipStream_t st = (hipStream_t)stream;
   const int bh = batch * n_heads;
-#define VC_ATT(Q, L, UNITS, NQB) \
-  hipLaunchKernelGGL((attention_kernel<Q, L>), dim3(UNITS), dim3(256), 0, st, pq, po, n_tokens, n_heads, scale_log2e, UNITS, NQB)
+#define VC_ATT(Q, L, UNITS, NQB)                                                                                                   \
+  do {                                                                                                                             \
+    if (of) hipLaunchKernelGGL((attention_kernel<Q, L, true>), dim3(UNITS), dim3(256), 0, st, pq, po, n_tokens, n_heads,            \
+                               scale_log2e, UNITS, NQB);                                                                           \
+    else hipLaunchKernelGGL((attention_kernel<Q, L>), dim3(UNITS), dim3(256), 0, st, pq, po, n_tokens, n_heads, scale_log2e, UNITS, \
+                            NQB);                                                                                                  \
+  } while (0)
   if (qt == 1) {
     const int nqb = (n_tokens + kQB - 1) / kQB;
     if (q_prescaled) VC_ATT(1, true, nqb * bh, nqb); else VC_ATT(1, false, nqb * bh, nqb);

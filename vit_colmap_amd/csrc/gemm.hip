@@ -10,9 +10,11 @@
 //   2. gemm256_kernel<EPI, CONV>  256 x 256 persistent tile for the wide layers of ViT-B / L / g, also as an implicit-GEMM
 //                                 convolution (vc_linear_bf16, vc_conv_taps_bf16);
 //   -- shared section of the two K = 384 kernels: x-row load + LayerNorm, table GELU, the steps by which a 32 x 32 block
-//      leaves through the wave's transposer, bias as initial value, the 24-MFMA stage loop, the fc1 weight fold --
-//   3. xs_kernel<EPI, LN, GT>     x-stationary GEMM for K = 384: qkv, proj, fc1 of ViT-S (vc_linear_xs_bf16) + its prepare kernel;
-//   4. mlp2_kernel                the whole MLP of a 384-wide block in one kernel (vc_mlp_bf16) + its prepare kernel.
+//      leaves through the wave's transposer, bias as initial value, the 24-MFMA stage loop, the fc1 weight fold; the same
+//      load, store and residual steps for tensors kept in fragment order ("FM"), which need no transposer --
+//   3. xs_kernel<EPI, LN, GT, XF, RF, OF>  x-stationary GEMM for K = 384: qkv, proj, fc1 of ViT-S (vc_linear_xs_bf16,
+//                                 vc_linear_xs_bf16_l: x / residual / out in fragment order) + its prepare kernel;
+//   4. mlp2_kernel<XF, OF>        the whole MLP of a 384-wide block in one kernel (vc_mlp_bf16, vc_mlp_bf16_l) + its prepare kernel.
 // 3 and 4 take their LDS layout from one constexpr plan each (xs_lds, mlp_lds), which the host entry points read too.
 // Vector types, bf16 pair conversions, the GELU forms, the XCD-aware tile order and the swizzled fragment offset of the two
 // staged kernels come first; the host helpers and the C entry points are at the end.
@@ -640,23 +642,27 @@ constexpr int MNS = 2;                             // ... its ring slots
 
 // xs_kernel: [ring of XNS stages][bias area: float32 bias of the N features, behind it (GT) the GELU table]
 //            [per wave 8 KiB: the x transposer, later the out (+0) and residual (+2048) transposers of the epilogue]
+// Second form (x in fragment order, below): no x transposer; 4 KiB per wave where a row-major residual or output still
+// takes the epilogue's transposers, nothing where both are in fragment order.
 struct XsLds {
   uint32_t ring, bias, bias_bytes, tr, end;
   __host__ __device__ constexpr bool bias_fits(int n_out) const { return (uint32_t)n_out * 4 <= bias_bytes; }
   __host__ __device__ constexpr uint32_t table(int n_out) const { return bias + (uint32_t)((n_out * 4 + 15) & ~15); }
   __host__ __device__ constexpr bool table_fits(int n_out) const { return table(n_out) + kGtBytes <= bias + bias_bytes; }
 };
-__host__ __device__ constexpr XsLds xs_lds() {
+__host__ __device__ constexpr XsLds xs_lds(bool x_fm = false, bool epi_row_major = true) {
   vc::LdsCursor c{0};
   XsLds l{};
   l.ring = c.take(XNS * XStage, 1024);
   l.bias_bytes = 16 * 1024;
   l.bias = c.take(l.bias_bytes, 16);
-  l.tr = c.take(8 * 2 * XChunk, 16);
+  l.tr = c.take(!x_fm ? 8 * 2 * XChunk : epi_row_major ? 8 * XChunk : 0, 16);
   l.end = c.at;
   return l;
 }
 static_assert(xs_lds().end == 152 * 1024, "xs_kernel: 72 + 16 + 64 KiB");
+static_assert(xs_lds(true, true).end == 120 * 1024 && xs_lds(true, false).end == 88 * 1024,
+              "xs_kernel, x in fragment order: 72 + 16 + 32 KiB with a row-major residual or output, 72 + 16 KiB without");
 static_assert(xs_lds().ring % 1024 == 0 && XStage % 1024 == 0, "xs_kernel: every LDS-DMA piece lands on a 1 KiB boundary");
 static_assert(xs_lds().bias % 16 == 0 && xs_lds().tr % 16 == 0 && XChunk % 16 == 0, "xs_kernel: table and transposers take 16-byte accesses");
 static_assert(xs_lds().table_fits(1920) && !xs_lds().table_fits(1952) && xs_lds().table_fits(1536) && xs_lds().bias_fits(4096),
@@ -708,6 +714,7 @@ __device__ __forceinline__ void x_rows_issue(v8bf (&xf)[XKS], const __bf16* X, i
     for (int c = 0; c < XK / 64; ++c) *(v4u*)&xf[4 * c + p] = *(const v4u*)(src + c * 128);   // raw lines land in xf itself
   }
 }
+__device__ __forceinline__ void x_layernorm(v8bf (&xf)[XKS], float eps);
 template <bool LN>
 __device__ __forceinline__ void x_rows_finish(v8bf (&xf)[XKS], uint8_t* tp, int lane, float eps) {
   const int r = lane & 31, h = lane >> 5, prow = lane >> 3;
@@ -723,7 +730,11 @@ __device__ __forceinline__ void x_rows_finish(v8bf (&xf)[XKS], uint8_t* tp, int 
     for (int k4 = 0; k4 < 4; ++k4)
       xf[4 * c + k4] = *(const v8bf*)(tp + r * 128 + (((2 * k4 + h) ^ fsw) << 4));
   }
-  if (LN) {
+  if (LN) x_layernorm(xf, eps);
+}
+// LayerNorm of the rows in xf (without gamma / beta: the prepare step folds them into W and the bias).
+__device__ __forceinline__ void x_layernorm(v8bf (&xf)[XKS], float eps) {
+  {
     // a lane and its partner (l ^ 32) hold one whole row: two-pass float32 statistics with packed (2-wide) VALU ops;
     // the passes re-expand the bf16 pairs (shift / mask) instead of keeping 192 floats live
     v2f s2 = {0.f, 0.f};
@@ -763,6 +774,45 @@ __device__ __forceinline__ void x_rows_finish(v8bf (&xf)[XKS], uint8_t* tp, int 
       }
     }
   }
+}
+
+// ---- fragment order ("FM") of an [M][384] bf16 tensor in HBM ------------------------------------------------------------
+// ceil(M / 32) blocks of 24 KiB; piece ks of block m >> 5 is xf[ks] of the wave that owns rows 32 (m >> 5) .. + 31:
+// element (m, k) at byte ((m >> 5) * 24 + (k >> 4)) * 1024 + (((k >> 3) & 1) * 32 + (m & 31)) * 16 + (k & 7) * 2.
+// What the K = 384 kernels hold in registers is what lies in memory, so x needs no transposer (24 loads of 1 KiB
+// contiguous) and a 32 x 32 block enters and leaves without LDS: behind half_swap a lane holds the two 16-byte chunks
+// k = col0 + 16 h + 8 c .. + 7 (c = 0, 1) of its token, slot 32 c + r of piece col0 / 16 + h — per instruction two runs of
+// 512 B.  The buffer has the padded row count; a lane whose row is >= M reads row M - 1's slot, as the row-major loaders
+// do, so the padding's content never matters, and stores into it are harmless.  row0 is a multiple of 32 everywhere.
+constexpr int FmBlock = XKS * 1024;
+__device__ __forceinline__ void half_swap(uint32_t (&ep)[8]);   // (with the block-leaving steps below)
+__device__ __forceinline__ size_t fm_row_byte(int m, int h) { return (size_t)(m >> 5) * FmBlock + (size_t)((h * 32 + (m & 31)) * 16); }
+__device__ __forceinline__ void x_frags_load(v8bf (&xf)[XKS], const __bf16* X, int row0, int M, int lane) {
+  const uint8_t* src = (const uint8_t*)X + fm_row_byte(min(row0 + (lane & 31), M - 1), lane >> 5);
+#pragma unroll
+  for (int ks = 0; ks < XKS; ++ks) xf[ks] = *(const v8bf*)(src + ks * 1024);
+}
+// chunk c of the block's results behind half_swap; rows past the padded M fall outside num_records and are dropped
+__device__ __forceinline__ void block_store_fm(const uint32_t (&ep)[8], __amdgpu_buffer_rsrc_t out_rs, int row0, int nb, int lane, int c) {
+  const v4u v = c == 0 ? (v4u){ep[0], ep[1], ep[4], ep[5]} : (v4u){ep[2], ep[3], ep[6], ep[7]};
+  __builtin_amdgcn_raw_buffer_store_b128(v, out_rs, (row0 >> 5) * FmBlock + (2 * nb + (lane >> 5)) * 1024 + (c * 32 + (lane & 31)) * 16, 0, 0);
+}
+__host__ __device__ constexpr size_t fm_bytes(long long rows) { return (size_t)((rows + 31) / 32) * FmBlock; }
+// The residual of a block: the same two chunks, loaded (2 loads of 16 bytes per lane, as many as the row-major form issues:
+// xs_kernel's counted vmcnt(7) / vmcnt(5) stay what they are) ...
+__device__ __forceinline__ v4u res_load_fm(const __bf16* res, int row0, int M, int nb, int lane, int c) {
+  const int m = min(row0 + (lane & 31), M - 1);
+  return *(const v4u*)((const uint8_t*)res + (size_t)(m >> 5) * FmBlock + (2 * nb + (lane >> 5)) * 1024 + (c * 32 + (m & 31)) * 16);
+}
+// ... and taken back into the accumulator layout by half_swap, which is its own inverse: rp[2g], rp[2g + 1] = features
+// 8g + 4h .. + 3 of token r as bf16 pairs
+__device__ __forceinline__ void res_unswap_fm(uint32_t (&rp)[8], const v4u (&resq)[2]) {
+  rp[0] = resq[0][0]; rp[1] = resq[0][1]; rp[4] = resq[0][2]; rp[5] = resq[0][3];
+  rp[2] = resq[1][0]; rp[3] = resq[1][1]; rp[6] = resq[1][2]; rp[7] = resq[1][3];
+  half_swap(rp);
+}
+__device__ __forceinline__ v4bf res_group_fm(const uint32_t (&rp)[8], int g) {
+  return __builtin_bit_cast(v4bf, (v2u){rp[2 * g], rp[2 * g + 1]});
 }
 
 // ---- table GELU of one 32 x 32 block, cut into slices 0-15 that ride between the MFMAs of the next block ---------------
@@ -905,12 +955,15 @@ __device__ __forceinline__ float fc1_row_to_fragments(const float* __restrict__ 
 constexpr int XReadAhead = 8;  // W fragments read ahead of the MFMA that uses them
 constexpr int XIssue0 = 1;      // MFMA behind which the first piece of stage i + 2 is issued ...
 constexpr int XIssueStep = 8;   // ... and the distance to the next (the last one stays ahead of the result stores at slice 19)
-template <int EPI, bool LN, bool GT>
+// XF / RF / OF: x, the residual, the output in fragment order (FM, shared section) instead of row-major; OF needs N == 384.
+template <int EPI, bool LN, bool GT, bool XF = false, bool RF = false, bool OF = false>
 __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X, const uint8_t* __restrict__ Wp,
                                                     const float* __restrict__ biasf, const __bf16* res,
                                                     __bf16* out, int M, int N, int n_nb, int n_stages, float eps,
                                                     const uint16_t* __restrict__ gelu_tab) {
-  constexpr XsLds L = xs_lds();
+  constexpr bool RES_RM = EPI == EPI_RESIDUAL && !RF;      // the epilogue's transposers are in use
+  constexpr XsLds L = xs_lds(XF, RES_RM || !OF);
+  constexpr int TrWave = XF ? XChunk : 2 * XChunk;
   __shared__ __attribute__((aligned(1024))) uint8_t lds[L.end];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -951,7 +1004,7 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
 
   // ---- x rows of this wave as B fragments (x_rows_issue / x_rows_finish) ----------------------------------------
   v8bf xf[XKS];
-  uint8_t* const tr_out = lds + L.tr + wave * (2 * XChunk);   // x transposer, then out / residual transposers (idle x staging)
+  uint8_t* const tr_out = lds + L.tr + wave * TrWave;   // x transposer, then out / residual transposers (idle x staging)
   uint8_t* const tr_res = tr_out + 2048;
 
   // ---- epilogue of one 32 (features) x 32 (tokens) block (the block-leaving steps above).
@@ -960,7 +1013,7 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
   // not overlap with the matrix pipe on this part however it is arranged (integer VALU work does), so this
   // costs the same as running the epilogue as a cluster — time = MFMA time + float VALU time — and is kept
   // for its simplicity; the lever for this kernel is fewer float instructions per output.
-  const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)M * N * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, OF ? (int)fm_bytes(M) : (int)((size_t)M * N * 2), 0x00020000);
   constexpr bool TABLE = EPI == EPI_GELU && GT;
   // the slices at which a finished block (s.ep) is exchanged, written to the transposer, read back and stored: behind the
   // table's 16 slices, or behind 8 slices of float work (values 2 sl, 2 sl + 1) and 4 of packing
@@ -968,6 +1021,7 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
   constexpr Leave at = TABLE ? Leave{16, 17, 19, 22} : Leave{12, 13, 15, 19};
   // state that flows from slice to slice
   v4u resq[2];      // the next block's residual lines
+  uint32_t rp[8];   // (RF) the pending block's residual in the accumulator layout
   v16f pa;          // the pending block's accumulators
   float ev[16];     // ... after GELU / residual
   BlockState s;     // ... packed to bf16 pairs
@@ -976,13 +1030,17 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
   auto load_res = [&](int m_base, int nb) {
     if (EPI == EPI_RESIDUAL) {
 #pragma unroll
-      for (int q = 0; q < 2; ++q) resq[q] = res_load(res, m_base, M, N, nb * 32, lane, q);
+      for (int q = 0; q < 2; ++q) resq[q] = RF ? res_load_fm(res, m_base, M, nb, lane, q) : res_load(res, m_base, M, N, nb * 32, lane, q);
     }
   };
-  auto res_to_lds = [&]() {   // the pending block's residual (loaded an iteration ago) enters the transposer
+  auto res_to_lds = [&]() {   // the pending block's residual (loaded an iteration ago) enters the transposer (RF: rp)
     if (EPI == EPI_RESIDUAL) {
+      if (RF) {
+        res_unswap_fm(rp, resq);
+      } else {
 #pragma unroll
-      for (int q = 0; q < 2; ++q) res_write(tr_res, resq[q], lane, q);
+        for (int q = 0; q < 2; ++q) res_write(tr_res, resq[q], lane, q);
+      }
     }
   };
   auto slice = [&](int sl) {
@@ -997,7 +1055,7 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
       } else if (EPI == EPI_RESIDUAL) {
         if ((sl & 1) == 0) {            // one 8-byte read serves values 4g .. 4g + 3
           const int g = sl >> 1;
-          const v4bf rv = res_read(tr_res, lane, g);
+          const v4bf rv = RF ? res_group_fm(rp, g) : res_read(tr_res, lane, g);
 #pragma unroll
           for (int j = 0; j < 4; ++j) ev[4 * g + j] = pa[4 * g + j] + (float)rv[j];
         }
@@ -1010,14 +1068,17 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
       pack_group(s.ep, g, ev[4 * g], ev[4 * g + 1], ev[4 * g + 2], ev[4 * g + 3]);
     }
     if (sl == at.swap) half_swap(s.ep);
-    if (sl == at.write) tr_write(tr_out, s.ep, lane);
-    if (sl == at.read) {
+    if (!OF && sl == at.write) tr_write(tr_out, s.ep, lane);
+    if (!OF && sl == at.read) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) eo[q] = tr_read(tr_out, lane, q);
     }
-    if (sl == at.store) {
+    if (sl == at.store) {   // (OF: at the same slice, behind the stage's last LDS-DMA piece, which the vmcnt counts rely on)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) block_store(eo[q], out_rs, pm_base, N, pnb * 32, lane, q);
+      for (int q = 0; q < 2; ++q) {
+        if (OF) block_store_fm(s.ep, out_rs, pm_base, pnb, lane, q);
+        else block_store(eo[q], out_rs, pm_base, N, pnb * 32, lane, q);
+      }
     }
   };
 
@@ -1046,12 +1107,14 @@ __global__ __launch_bounds__(512, 1) void xs_kernel(const __bf16* __restrict__ X
     const int m_base = mt * XRows + wave * 32;
     if (reload) {
       // new row tile: the pending block cannot ride under this block's MFMAs (its x loads come first)
-      x_rows_issue(xf, X, m_base, M, lane);
+      if (XF) x_frags_load(xf, X, m_base, M, lane);
+      else x_rows_issue(xf, X, m_base, M, lane);
       if (pending) {
 #pragma unroll
         for (int sl = 0; sl < XKS; ++sl) slice(sl);
       }
-      x_rows_finish<LN>(xf, tr_out, lane, eps);
+      if (!XF) x_rows_finish<LN>(xf, tr_out, lane, eps);
+      else if (LN) x_layernorm(xf, eps);
       mt_cur = mt;
     }
     load_res(m_base, nb);
@@ -1122,10 +1185,14 @@ constexpr int M2PiecesA = 3;      // LDS-DMA pieces of a stage issued by each fc
 constexpr int M2Issue0 = 1;       // first MFMA behind which a piece of the next stage is issued ...
 constexpr int M2IssueStep = 3;    // ... and the distance to the next one (sweep: 1+3k 228 us, 1+2k 229, 0+k 233, 1+4k 235)
 constexpr int M2IssueStepB = 2;   // the distance on an fc2 wave with more than six pieces per stage
+// XF: x (read by the fc1 waves, and again as the residual) in fragment order (FM, shared section); OF: the result too, in
+// place.  XF without OF writes row-major rows into Out, a buffer of its own; otherwise Out is not looked at.
+template <bool XF = false, bool OF = false>
 __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, const uint8_t* __restrict__ Wm,
                                                       const float* __restrict__ b1f, const float* __restrict__ b2f,
                                                       int M, int n_chunks, int n_tiles, float eps,
-                                                      const uint16_t* __restrict__ gelu_tab) {
+                                                      const uint16_t* __restrict__ gelu_tab, __bf16* Out) {
+  static_assert(XF || !OF, "mlp2_kernel: a row-major x is updated in place");
   constexpr MlpLds L = mlp_lds();
   __shared__ __attribute__((aligned(1024))) uint8_t lds[L.end];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1203,8 +1270,13 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
       if (do_issue && !(i < n && i > 0)) issue_stage(i + 1, slot ^ 1);
       if (i < n) {
         if (chunk == 0) {
-          x_rows_issue(xf, X, tile * 128 + pairw * 32, M, lane);
-          x_rows_finish<true>(xf, tp, lane, eps);
+          if (XF) {
+            x_frags_load(xf, X, tile * 128 + pairw * 32, M, lane);
+            x_layernorm(xf, eps);
+          } else {
+            x_rows_issue(xf, X, tile * 128 + pairw * 32, M, lane);
+            x_rows_finish<true>(xf, tp, lane, eps);
+          }
         }
         const uint8_t* st = lds + slot * MStage + lane * 16;
         v16f hacc;
@@ -1233,7 +1305,8 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
   } else {
     // =========================== B: fc2 accumulators, two stages behind, tile epilogue ==========================
     v16f oacc[12];
-    const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(X, 0, (int)((size_t)M * XK * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t out_rs =
+        __builtin_amdgcn_make_buffer_rsrc(XF && !OF ? Out : X, 0, OF ? (int)fm_bytes(M) : (int)((size_t)M * XK * 2), 0x00020000);
     uint8_t* const tr_out = lds + L.tr_b + pairw * XChunk;
     uint8_t* const tr_res = tr_out + 2048;
     int pchunk = 0;                                  // chunk consumed in this iteration (that of fc1 stage i-2)
@@ -1273,9 +1346,14 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
             // the block-leaving steps of the shared section, as one cluster
             v4u resq[2];
 #pragma unroll
-            for (int q = 0; q < 2; ++q) resq[q] = res_load(X, m0w, M, XK, ob * 32, lane, q);
+            for (int q = 0; q < 2; ++q) resq[q] = XF ? res_load_fm(X, m0w, M, ob, lane, q) : res_load(X, m0w, M, XK, ob * 32, lane, q);
+            uint32_t rp[8];
+            if (XF) {
+              res_unswap_fm(rp, resq);
+            } else {
 #pragma unroll
-            for (int q = 0; q < 2; ++q) res_write(tr_res, resq[q], lane, q);
+              for (int q = 0; q < 2; ++q) res_write(tr_res, resq[q], lane, q);
+            }
             v16f oa;
             switch (ob) {   // dynamic index into the register tiles
 #define VC_OB(k) case k: oa = oacc[k]; break;
@@ -1286,7 +1364,7 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
             uint32_t ep[8];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-              const v4bf rv = res_read(tr_res, lane, g);
+              const v4bf rv = XF ? res_group_fm(rp, g) : res_read(tr_res, lane, g);
               const v4f bv = *(const v4f*)(b2_l + ob * 32 + 8 * g + 4 * (lane >> 5));
               float v[4];
 #pragma unroll
@@ -1294,9 +1372,14 @@ __global__ __launch_bounds__(512, 2) void mlp2_kernel(__bf16* __restrict__ X, co
               pack_group(ep, g, v[0], v[1], v[2], v[3]);
             }
             half_swap(ep);
-            tr_write(tr_out, ep, lane);
+            if (OF) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q) block_store(tr_read(tr_out, lane, q), out_rs, m0w, XK, ob * 32, lane, q);
+              for (int q = 0; q < 2; ++q) block_store_fm(ep, out_rs, m0w, ob, lane, q);
+            } else {
+              tr_write(tr_out, ep, lane);
+#pragma unroll
+              for (int q = 0; q < 2; ++q) block_store(tr_read(tr_out, lane, q), out_rs, m0w, XK, ob * 32, lane, q);
+            }
           }
           tile += G;
         }
@@ -1340,6 +1423,8 @@ template <typename... P>
 static bool aligned16(const P*... p) {
   return ((uintptr_t)0 | ... | (uintptr_t)p) % 16 == 0;
 }
+
+static bool valid_layout(int layout) { return layout == VC_ACT_ROW_MAJOR || layout == VC_ACT_FRAGMENT; }
 
 // Grid of a persistent kernel: one workgroup per CU, fewer when there is less work.
 static unsigned persistent_grid(long long work_items, int cus) { return (unsigned)(work_items < cus ? work_items : cus); }
@@ -1466,6 +1551,8 @@ int vc_linear_xs_prepare(const float* weight, const float* bias_or_null, const f
 
 size_t vc_gelu_table_bytes(void) { return (size_t)kGtBytes; }
 
+size_t vc_act_fragment_bytes(long long rows) { return rows > 0 ? fm_bytes(rows) : 0; }
+
 int vc_gelu_table_bf16(void* table, vc_stream_t stream) {
   if (!table || !aligned16(table)) return VC_ERR_INVALID_ARG;
   hipLaunchKernelGGL(gelu_table_kernel, dim3((kGtN * 2 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (uint16_t*)table);
@@ -1475,6 +1562,22 @@ int vc_gelu_table_bf16(void* table, vc_stream_t stream) {
 int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias_folded, const void* residual_or_null,
                       void* out, int rows, int n_out, int k_in, int epilogue, int fuse_layernorm, float ln_eps,
                       const void* gelu_table_or_null, vc_stream_t stream) {
+  return vc_linear_xs_bf16_l(x, weight_tiled, bias_folded, residual_or_null, out, rows, n_out, k_in, epilogue, fuse_layernorm, ln_eps,
+                             gelu_table_or_null, VC_ACT_ROW_MAJOR, VC_ACT_ROW_MAJOR, VC_ACT_ROW_MAJOR, stream);
+}
+
+int vc_linear_xs_bf16_l(const void* x, const void* weight_tiled, const float* bias_folded, const void* residual_or_null,
+                        void* out, int rows, int n_out, int k_in, int epilogue, int fuse_layernorm, float ln_eps,
+                        const void* gelu_table_or_null, int x_layout, int residual_layout, int out_layout, vc_stream_t stream) {
+  if (!valid_layout(x_layout) || !valid_layout(residual_layout) || !valid_layout(out_layout)) return VC_ERR_INVALID_ARG;
+  if (!residual_or_null && residual_layout != VC_ACT_ROW_MAJOR) return VC_ERR_INVALID_ARG;
+  // fragment order: what the 384-wide block loop runs — LayerNorm + bias from FM x to row-major rows (qkv), and the
+  // residual epilogue from FM x to an FM [rows][384] output, the residual in either layout (proj)
+  const bool fm = x_layout != VC_ACT_ROW_MAJOR || residual_layout != VC_ACT_ROW_MAJOR || out_layout != VC_ACT_ROW_MAJOR;
+  const bool fm_qkv = x_layout == VC_ACT_FRAGMENT && out_layout == VC_ACT_ROW_MAJOR && epilogue == EPI_BIAS && fuse_layernorm;
+  const bool fm_proj = x_layout == VC_ACT_FRAGMENT && out_layout == VC_ACT_FRAGMENT && epilogue == EPI_RESIDUAL &&
+                       !fuse_layernorm && n_out == XK;
+  if (fm && !fm_qkv && !fm_proj) return VC_ERR_UNSUPPORTED;
   if (!x || !weight_tiled || !bias_folded || !out || rows < 0 || n_out <= 0) return VC_ERR_INVALID_ARG;
   if (epilogue < EPI_BIAS || epilogue > EPI_RESIDUAL) return VC_ERR_INVALID_ARG;
   if ((epilogue == EPI_RESIDUAL) != (residual_or_null != nullptr)) return VC_ERR_INVALID_ARG;
@@ -1500,6 +1603,21 @@ int vc_linear_xs_bf16(const void* x, const void* weight_tiled, const float* bias
                          ln_eps, gt);
       return vc::check_launch();
     };
+    // (a row range starts at a multiple of 256 rows: the same byte offset in both layouts)
+    if (fm_qkv) {
+      hipLaunchKernelGGL((xs_kernel<EPI_BIAS, true, false, true, false, false>), grid, block, 0, s, px, pw, bias_folded, pr, po, m,
+                         n_out, n_nb, stages, ln_eps, gt);
+      return vc::check_launch();
+    }
+    if (fm_proj) {
+      if (residual_layout == VC_ACT_FRAGMENT)
+        hipLaunchKernelGGL((xs_kernel<EPI_RESIDUAL, false, false, true, true, true>), grid, block, 0, s, px, pw, bias_folded, pr, po,
+                           m, n_out, n_nb, stages, ln_eps, gt);
+      else
+        hipLaunchKernelGGL((xs_kernel<EPI_RESIDUAL, false, false, true, false, true>), grid, block, 0, s, px, pw, bias_folded, pr, po,
+                           m, n_out, n_nb, stages, ln_eps, gt);
+      return vc::check_launch();
+    }
     return vc::dispatch<EPI_BIAS, EPI_GELU, EPI_RESIDUAL>(epilogue, [&](auto epi) {
       return vc::dispatch<true, false>(fuse_layernorm != 0, [&](auto ln) {
         if constexpr (epi == EPI_GELU) {   // only the GELU epilogue has a table variant
@@ -1545,20 +1663,40 @@ int vc_mlp_prepare(const float* w1, const float* b1_or_null, const float* ln_gam
   return vc::check_launch();
 }
 
-int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded, const float* b2, const void* gelu_table,
-                int rows, int n_hidden, int dim, float ln_eps, vc_stream_t stream) {
+int vc_mlp_bf16_l(void* x_inout, void* out_or_null, const void* weights_tiled, const float* b1_folded, const float* b2,
+                  const void* gelu_table, int rows, int n_hidden, int dim, float ln_eps, int x_layout, int out_layout,
+                  vc_stream_t stream) {
   if (!x_inout || !weights_tiled || !b1_folded || !b2 || !gelu_table || rows < 0) return VC_ERR_INVALID_ARG;
+  if (!valid_layout(x_layout) || !valid_layout(out_layout)) return VC_ERR_INVALID_ARG;
+  // in place in either layout, or fragment order in and row-major rows out into a buffer of their own
+  const bool separate = x_layout != out_layout;
+  if (separate && (x_layout != VC_ACT_FRAGMENT || !out_or_null || out_or_null == x_inout)) return VC_ERR_INVALID_ARG;
+  if (!separate && out_or_null && out_or_null != x_inout) return VC_ERR_INVALID_ARG;
   if (vc_mlp_weight_bytes(n_hidden, dim) == 0) return VC_ERR_UNSUPPORTED;
-  if (!aligned16(x_inout, weights_tiled, b1_folded, b2, gelu_table)) return VC_ERR_INVALID_ARG;
+  if (!aligned16(x_inout, out_or_null, weights_tiled, b1_folded, b2, gelu_table)) return VC_ERR_INVALID_ARG;
   if (rows == 0) return VC_OK;
   int cus = 0;
   if (int st = vc::cu_count(&cus)) return st;
+  // (a row range starts at a multiple of 128 rows: the same byte offset in both layouts)
   return for_row_ranges(rows, XK, 128, [&](long long r0, int m) {
     const int n_tiles = (m + 127) / 128;
-    hipLaunchKernelGGL(mlp2_kernel, dim3(persistent_grid(n_tiles, cus)), dim3(512), 0, (hipStream_t)stream, (__bf16*)x_inout + (size_t)r0 * XK,
-                       (const uint8_t*)weights_tiled, b1_folded, b2, m, n_hidden / 32, n_tiles, ln_eps, (const uint16_t*)gelu_table);
-    return vc::check_launch();
+    __bf16* po = separate ? (__bf16*)out_or_null + (size_t)r0 * XK : nullptr;
+    auto launch = [&](auto xf, auto of) {
+      hipLaunchKernelGGL((mlp2_kernel<xf, of>), dim3(persistent_grid(n_tiles, cus)), dim3(512), 0, (hipStream_t)stream,
+                         (__bf16*)x_inout + (size_t)r0 * XK, (const uint8_t*)weights_tiled, b1_folded, b2, m, n_hidden / 32, n_tiles,
+                         ln_eps, (const uint16_t*)gelu_table, po);
+      return vc::check_launch();
+    };
+    if (x_layout == VC_ACT_ROW_MAJOR) return launch(std::false_type{}, std::false_type{});
+    if (separate) return launch(std::true_type{}, std::false_type{});
+    return launch(std::true_type{}, std::true_type{});
   });
+}
+
+int vc_mlp_bf16(void* x_inout, const void* weights_tiled, const float* b1_folded, const float* b2, const void* gelu_table,
+                int rows, int n_hidden, int dim, float ln_eps, vc_stream_t stream) {
+  return vc_mlp_bf16_l(x_inout, nullptr, weights_tiled, b1_folded, b2, gelu_table, rows, n_hidden, dim, ln_eps, VC_ACT_ROW_MAJOR,
+                       VC_ACT_ROW_MAJOR, stream);
 }
 
 }  // extern "C"

@@ -404,13 +404,38 @@ class DinoV2(nn.Module):
             return self._blocks_gemm(x, drop_cls)
         blocks, hip = list(self.blocks), self._hip
 
-        def layer(i, xi):
+        def layer_row_major(i, xi):
             blk, hw = blocks[i], hip[i]
             a = ops.attention(hw["qkv"](xi), blk.attn.num_heads, q_prescaled=True)   # LN1 + qkv (q pre-scaled), flash attention
             hw["proj"](a, ops.EPI_RESIDUAL, residual=xi, out=xi)            # x += proj(a)
             hw["mlp"](xi)                                                   # x += fc2(gelu(fc1(LN2 x))), one kernel
 
-        return self._run_sharded(x, layer, *self._final_norm(x, drop_cls))
+        # The same loop with the residual stream and the attention output in the GEMMs' fragment order between the kernels
+        # (DESIGN.md §3): the first proj takes the shard's row-major rows as its residual and writes a tensor in fragment
+        # order, which is the shard's residual stream from there on, the last MLP writes row-major rows back into the shard.
+        # qkv itself stays row-major (the attention kernel's K / V copies).  Every shard owns its tensors: a batch slice of
+        # a tensor in fragment order is not a view.
+        FM, n_layers, stream_of = ops.FRAGMENT, len(blocks), {}
+
+        def layer(i, xi):
+            blk, hw = blocks[i], hip[i]
+            B, N, _ = xi.shape
+            rows, key = B * N, xi.data_ptr()
+            qkv = hw["qkv"](xi) if i == 0 else hw["qkv"](stream_of[key], rows=rows, x_layout=FM).view(B, N, -1)
+            a = ops.attention(qkv, blk.attn.num_heads, q_prescaled=True, out_layout=FM)
+            if i == 0:
+                stream_of[key] = hw["proj"](a, ops.EPI_RESIDUAL, residual=xi, rows=rows, x_layout=FM, out_layout=FM)
+            xf = stream_of[key]
+            if i > 0:
+                hw["proj"](a, ops.EPI_RESIDUAL, residual=xf, out=xf, rows=rows, x_layout=FM, residual_layout=FM, out_layout=FM)
+            if i == n_layers - 1:
+                hw["mlp"](stream_of.pop(key), rows=rows, x_layout=FM, out=xi)
+            else:
+                hw["mlp"](xf, rows=rows, x_layout=FM)
+
+        return self._run_sharded(x, layer if self.fragment_layout else layer_row_major, *self._final_norm(x, drop_cls))
+
+    fragment_layout = True   # False: the row-major block loop above (the equality tests and the A/B measurement use it)
 
     def _final_norm(self, x, drop_cls):
         """-> (final_fn, out): the last LayerNorm as a per-shard step writing into a batch slice of `out`."""

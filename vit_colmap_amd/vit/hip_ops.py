@@ -35,16 +35,29 @@ def layernorm_drop_first(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tens
 Q_PRESCALE = 0.125 * 1.4426950408889634   # 1/sqrt(64) * log2(e): what `q_prescaled=True` expects folded into q
 
 
-def attention(qkv: torch.Tensor, n_heads: int, q_prescaled: bool = False) -> torch.Tensor:
-    """qkv (B, N, 3*H*64) bf16 contiguous -> softmax(QK^T/8)V as (B, N, H*64) bf16 (csrc/attention.hip).
+ROW_MAJOR, FRAGMENT = 0, 1   # VC_ACT_ROW_MAJOR, VC_ACT_FRAGMENT: layouts of a [rows][384] activation tensor
+
+
+def fm_empty(rows: int, device) -> torch.Tensor:
+    """A [rows][384] bf16 tensor in fragment order (include/vitcolmap_hip.h, VC_ACT_FRAGMENT): ceil(rows / 32) blocks of
+    24 pieces x 64 lanes x 8 elements.  It is one tensor: a slice of its rows is not a view of it."""
+    return torch.empty(((rows + 31) // 32, 24, 64, 8), dtype=torch.bfloat16, device=device)
+
+
+def attention(qkv: torch.Tensor, n_heads: int, q_prescaled: bool = False, out_layout: int = ROW_MAJOR) -> torch.Tensor:
+    """qkv (B, N, 3*H*64) bf16 contiguous -> softmax(QK^T/8)V as (B, N, H*64) bf16 (csrc/attention.hip), or with
+    out_layout=FRAGMENT as the B * N rows of one `fm_empty` tensor.
     q_prescaled: the q part already carries Q_PRESCALE (folded into the qkv projection)."""
     assert qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
     B, N, C3 = qkv.shape
     hd = C3 // (3 * n_heads)
     lib = _lib.load()
-    out = torch.empty((B, N, C3 // 3), dtype=torch.bfloat16, device=qkv.device)
-    _lib.check(lib.vc_attention_bf16(_lib.ptr(qkv), B, N, n_heads, hd, int(q_prescaled), _lib.ptr(out), _lib.stream_ptr()),
-               "vc_attention_bf16")
+    if out_layout == FRAGMENT:
+        out = fm_empty(B * N, qkv.device)
+    else:
+        out = torch.empty((B, N, C3 // 3), dtype=torch.bfloat16, device=qkv.device)
+    _lib.check(lib.vc_attention_bf16_l(_lib.ptr(qkv), B, N, n_heads, hd, int(q_prescaled), _lib.ptr(out), out_layout,
+                                       _lib.stream_ptr()), "vc_attention_bf16_l")
     return out
 
 
@@ -151,17 +164,33 @@ class XsLinear:
         _lib.check(lib.vc_linear_xs_prepare(_lib.ptr(w), _lib.ptr(b), _lib.ptr(g), _lib.ptr(be), n, k, _lib.ptr(self.wp),
                                             _lib.ptr(self.bias), _lib.stream_ptr()), "vc_linear_xs_prepare")
 
-    def __call__(self, x: torch.Tensor, epilogue: int = EPI_BIAS, residual=None, out=None, gelu_table=None) -> torch.Tensor:
-        assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[-1] == self.k
-        rows = x.numel() // self.k
-        if out is None:
-            out = torch.empty(x.shape[:-1] + (self.n,), dtype=torch.bfloat16, device=x.device)
-        if residual is not None:
-            assert residual.shape == out.shape and residual.dtype == torch.bfloat16 and residual.is_contiguous()
+    def __call__(self, x: torch.Tensor, epilogue: int = EPI_BIAS, residual=None, out=None, gelu_table=None, rows=None,
+                 x_layout: int = ROW_MAJOR, residual_layout: int = ROW_MAJOR, out_layout: int = ROW_MAJOR) -> torch.Tensor:
+        """`rows` (with any layout FRAGMENT): the row count, which a tensor in fragment order does not carry; a row-major
+        out is then (rows, n), a FRAGMENT out an `fm_empty` tensor."""
+        assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
+        fm = FRAGMENT in (x_layout, residual_layout, out_layout)
+        if not fm:
+            assert x.shape[-1] == self.k
+            rows = x.numel() // self.k
+            if out is None:
+                out = torch.empty(x.shape[:-1] + (self.n,), dtype=torch.bfloat16, device=x.device)
+            if residual is not None:
+                assert residual.shape == out.shape
+        else:
+            numel = lambda layout, width: ((rows + 31) // 32 * 32 if layout == FRAGMENT else rows) * width
+            assert rows is not None and x.numel() == numel(x_layout, self.k)
+            if out is None:
+                out = fm_empty(rows, x.device) if out_layout == FRAGMENT else torch.empty((rows, self.n), dtype=torch.bfloat16, device=x.device)
+            assert out.numel() == numel(out_layout, self.n)
+            assert residual is None or residual.numel() == numel(residual_layout, self.n)
+        assert out.dtype == torch.bfloat16 and out.is_contiguous()
+        assert residual is None or (residual.dtype == torch.bfloat16 and residual.is_contiguous())
         lib = _lib.load()
-        _lib.check(lib.vc_linear_xs_bf16(_lib.ptr(x), _lib.ptr(self.wp), _lib.ptr(self.bias), _lib.ptr(residual),
-                                         _lib.ptr(out), rows, self.n, self.k, epilogue, int(self.ln), self.eps,
-                                         _lib.ptr(gelu_table), _lib.stream_ptr()), "vc_linear_xs_bf16")
+        _lib.check(lib.vc_linear_xs_bf16_l(_lib.ptr(x), _lib.ptr(self.wp), _lib.ptr(self.bias), _lib.ptr(residual),
+                                           _lib.ptr(out), rows, self.n, self.k, epilogue, int(self.ln), self.eps,
+                                           _lib.ptr(gelu_table), x_layout, residual_layout, out_layout, _lib.stream_ptr()),
+                   "vc_linear_xs_bf16_l")
         return out
 
 
@@ -220,9 +249,19 @@ class FusedMlp:
                                       n_hid, dim, _lib.ptr(self.wm), _lib.ptr(self.b1), _lib.ptr(self.b2), _lib.stream_ptr()),
                    "vc_mlp_prepare")
 
-    def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[-1] == self.dim
+    def __call__(self, x: torch.Tensor, rows=None, x_layout: int = ROW_MAJOR, out=None) -> torch.Tensor:
+        """Row-major x: updated in place.  x_layout=FRAGMENT (an `fm_empty` tensor of `rows` rows): updated in place, or
+        with `out`, a row-major (rows, dim) tensor, left as it is and the result written there.  -> the tensor written."""
+        assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
+        if x_layout == FRAGMENT:
+            assert rows is not None and x.numel() == (rows + 31) // 32 * 32 * self.dim
+            assert out is None or (out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == rows * self.dim)
+        else:
+            assert x.shape[-1] == self.dim and out is None
+            rows = x.numel() // self.dim
+        out_layout = ROW_MAJOR if out is not None else x_layout
         lib = _lib.load()
-        _lib.check(lib.vc_mlp_bf16(_lib.ptr(x), _lib.ptr(self.wm), _lib.ptr(self.b1), _lib.ptr(self.b2), _lib.ptr(self.table),
-                                   x.numel() // self.dim, self.n_hid, self.dim, self.eps, _lib.stream_ptr()), "vc_mlp_bf16")
-        return x
+        _lib.check(lib.vc_mlp_bf16_l(_lib.ptr(x), _lib.ptr(out), _lib.ptr(self.wm), _lib.ptr(self.b1), _lib.ptr(self.b2),
+                                     _lib.ptr(self.table), rows, self.n_hid, self.dim, self.eps, x_layout, out_layout,
+                                     _lib.stream_ptr()), "vc_mlp_bf16_l")
+        return x if out is None else out
