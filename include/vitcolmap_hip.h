@@ -295,6 +295,23 @@ int vc_triangulate_tracks(const double* obs_xy, const int32_t* obs_cam, const in
                           uint8_t* out_mask, int32_t* out_count, double* out_error, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Track refinement: every track of a call evaluated again at a point it already has, after the
+ * poses moved (one bundle adjustment per growth round).  The arrays, the thresholds, the outputs, the launch shape and the
+ * arithmetic are vc_triangulate_tracks'; init_xyz [n_tracks][3] float64 takes the place of the seeds and of the hypotheses.
+ * Specification: tests/util_rounds.py (`refine_track`).  The rule for a track:
+ *   usable      as above; an init_xyz with a non-finite entry rejects the track
+ *   start       the inliers of X0 = init_xyz over every usable observation (the inlier test above); fewer than two reject
+ *   refit       as above, from X0 over those inliers; taken iff finite with no fewer inliers over all usable observations
+ *   accepted    as above; out_mask are the inliers of the final X: observations that left the threshold are dropped, nodes
+ *               that are now inside it are picked up
+ * n_tracks == 0: VC_OK whatever the pointers are.  A null pointer, a negative size, a threshold that is negative or not
+ * finite: VC_ERR_INVALID_ARG.  A negative or descending pair of offsets rejects the track and nothing of it is read.
+ * ------------------------------------------------------------------------------------------ */
+int vc_refine_tracks(const double* obs_xy, const int32_t* obs_cam, const int32_t* offsets, int n_tracks, const double* cams, int n_cams,
+                     const double* init_xyz, double max_error_px, double min_tri_angle_tan2, double* out_xyz, uint8_t* out_mask,
+                     int32_t* out_count, double* out_error, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint undistortion: the pixel an ideal pinhole camera with the same K would see in place of
  * a raw keypoint of a camera with known distortion, one keypoint per lane, float64 in single operations in the written order
  * (left to right, the usual precedence; no fused multiply-add, no library call).  Specification: tests/util_undistort.py.

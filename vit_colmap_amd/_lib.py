@@ -61,6 +61,8 @@ SIGNATURES = {
     "vc_absolute_pose_inliers": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p]),
     "vc_triangulate_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_refine_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "vc_undistort_points": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vc_ba_linearize_points": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

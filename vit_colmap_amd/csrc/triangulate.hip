@@ -18,6 +18,10 @@
 // loop but those over observations, hypotheses and refit steps is fully unrolled.  Angles are tested without trigonometry
 // and the only library call is sqrt, so the host build of triangulate_track (tools/triangulate_host.cpp includes this file)
 // and the device agree; what a lane computes is sequential, so two launches return the same bits.
+//
+// vc_refine_tracks (specification: tests/util_rounds.py, `refine_track`) is steps 3 and 4 from a point the
+// track has already: after a bundle adjustment moved the poses, the inliers of that point over every usable observation
+// take the winner's place.  finish_track is the one statement of those steps; tools/refine_tracks_host.cpp is its host build.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -205,35 +209,10 @@ __host__ __device__ __forceinline__ void sampled_pair(uint32_t seed, int h, int 
   p = a < b ? a : b, q = a < b ? b : a;
 }
 
-// One track: observations lo .. lo + n of the call.  -> the number of inliers (0: rejected); X, the mean pixel error of the
-// inliers and mask[0 .. n) (the track's own slots) are written either way, NaN and 0 for a rejected track.
-__host__ __device__ __forceinline__ int triangulate_track(const Tracks& d, long long lo, int n, uint32_t seed, double max_error,
-                                                          double tan2, double (&X)[3], uint8_t* mask, double& error) {
-  const double e2 = max_error * max_error;
-  double best[3] = {NAN, NAN, NAN};
-  int best_count = 0;
-  const bool all_pairs = (long long)n * (n - 1) / 2 <= kTriMaxHypotheses;
-  const int n_hyp = n < 2 ? 0 : all_pairs ? n * (n - 1) / 2 : kTriMaxHypotheses;
-  int p = 0, q = 0;                                          // all pairs: (0, 1), (0, 2), ...
-  for (int h = 0; h < n_hyp; ++h) {
-    if (all_pairs) {
-      if (++q >= n) ++p, q = p + 1;
-    } else {
-      sampled_pair(seed, h, n, p, q);
-    }
-    View vp, vq;
-    load_view(d, lo + p, vp);
-    load_view(d, lo + q, vq);
-    double Xh[3], sq, z;
-    if (!(vp.ok && vq.ok && midpoint(vp, vq, tan2, Xh))) continue;
-    if (!(inlier(vp, Xh, e2, sq, z) && inlier(vq, Xh, e2, sq, z))) continue;
-    const int count = count_inliers(d, lo, n, Xh, e2);
-    if (count > best_count) {                                // the lowest h on ties
-      best_count = count;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) best[k] = Xh[k];
-    }
-  }
+// The tail both entry points share, from a point `best` with best_count inliers (0: there is none): the refit, its acceptance,
+// the parallax test and the outputs as triangulate_track states them.
+__host__ __device__ __forceinline__ int finish_track(const Tracks& d, long long lo, int n, const double (&best)[3], int best_count,
+                                                     double e2, double tan2, double (&X)[3], uint8_t* mask, double& error) {
   int count = best_count;
 #pragma unroll
   for (int k = 0; k < 3; ++k) X[k] = best[k];
@@ -286,6 +265,48 @@ __host__ __device__ __forceinline__ int triangulate_track(const Tracks& d, long 
   return count;
 }
 
+// One track: observations lo .. lo + n of the call.  -> the number of inliers (0: rejected); X, the mean pixel error of the
+// inliers and mask[0 .. n) (the track's own slots) are written either way, NaN and 0 for a rejected track.
+__host__ __device__ __forceinline__ int triangulate_track(const Tracks& d, long long lo, int n, uint32_t seed, double max_error,
+                                                          double tan2, double (&X)[3], uint8_t* mask, double& error) {
+  const double e2 = max_error * max_error;
+  double best[3] = {NAN, NAN, NAN};
+  int best_count = 0;
+  const bool all_pairs = (long long)n * (n - 1) / 2 <= kTriMaxHypotheses;
+  const int n_hyp = n < 2 ? 0 : all_pairs ? n * (n - 1) / 2 : kTriMaxHypotheses;
+  int p = 0, q = 0;                                          // all pairs: (0, 1), (0, 2), ...
+  for (int h = 0; h < n_hyp; ++h) {
+    if (all_pairs) {
+      if (++q >= n) ++p, q = p + 1;
+    } else {
+      sampled_pair(seed, h, n, p, q);
+    }
+    View vp, vq;
+    load_view(d, lo + p, vp);
+    load_view(d, lo + q, vq);
+    double Xh[3], sq, z;
+    if (!(vp.ok && vq.ok && midpoint(vp, vq, tan2, Xh))) continue;
+    if (!(inlier(vp, Xh, e2, sq, z) && inlier(vq, Xh, e2, sq, z))) continue;
+    const int count = count_inliers(d, lo, n, Xh, e2);
+    if (count > best_count) {                                // the lowest h on ties
+      best_count = count;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) best[k] = Xh[k];
+    }
+  }
+  return finish_track(d, lo, n, best, best_count, e2, tan2, X, mask, error);
+}
+
+// One track re-evaluated at a point it has already: X0's inliers over every usable observation, fewer than two
+// or a non-finite X0 reject; then the tail of triangulate_track.  Outputs as there.
+__host__ __device__ __forceinline__ int refine_track(const Tracks& d, long long lo, int n, const double (&X0)[3], double max_error,
+                                                     double tan2, double (&X)[3], uint8_t* mask, double& error) {
+  const double e2 = max_error * max_error;
+  const bool given = is_finite(X0[0]) && is_finite(X0[1]) && is_finite(X0[2]);
+  const int count0 = given ? count_inliers(d, lo, n, X0, e2) : 0;
+  return finish_track(d, lo, n, X0, count0 >= 2 ? count0 : 0, e2, tan2, X, mask, error);
+}
+
 __global__ __launch_bounds__(kTriWave) void triangulate_tracks_kernel(Tracks d, const int32_t* __restrict__ offsets, int n_tracks,
                                                                       const int32_t* __restrict__ seeds, double max_error, double tan2,
                                                                       double* __restrict__ out_xyz, uint8_t* __restrict__ out_mask,
@@ -297,6 +318,25 @@ __global__ __launch_bounds__(kTriWave) void triangulate_tracks_kernel(Tracks d, 
   int count = 0;
   if (lo >= 0 && hi >= lo)                                   // a track whose offsets do not delimit a list is rejected, nothing of it read
     count = triangulate_track(d, lo, (int)(hi - lo), (uint32_t)seeds[t], max_error, tan2, X, out_mask + lo, error);
+  out_xyz[3 * t] = X[0], out_xyz[3 * t + 1] = X[1], out_xyz[3 * t + 2] = X[2];
+  out_count[t] = count;
+  out_error[t] = error;
+}
+
+// vc_refine_tracks: the shape of triangulate_tracks_kernel, init_xyz in place of the seeds.
+__global__ __launch_bounds__(kTriWave) void refine_tracks_kernel(Tracks d, const int32_t* __restrict__ offsets, int n_tracks,
+                                                                 const double* __restrict__ init_xyz, double max_error, double tan2,
+                                                                 double* __restrict__ out_xyz, uint8_t* __restrict__ out_mask,
+                                                                 int32_t* __restrict__ out_count, double* __restrict__ out_error) {
+  const long long t = (long long)blockIdx.x * kTriWave + threadIdx.x;
+  if (t >= n_tracks) return;
+  const long long lo = offsets[t], hi = offsets[t + 1];
+  double X[3] = {NAN, NAN, NAN}, error = NAN;
+  int count = 0;
+  if (lo >= 0 && hi >= lo) {                                 // as in triangulate_tracks_kernel
+    const double X0[3] = {init_xyz[3 * t], init_xyz[3 * t + 1], init_xyz[3 * t + 2]};
+    count = refine_track(d, lo, (int)(hi - lo), X0, max_error, tan2, X, out_mask + lo, error);
+  }
   out_xyz[3 * t] = X[0], out_xyz[3 * t + 1] = X[1], out_xyz[3 * t + 2] = X[2];
   out_count[t] = count;
   out_error[t] = error;
@@ -318,6 +358,22 @@ int vc_triangulate_tracks(const double* obs_xy, const int32_t* obs_cam, const in
   const int blocks = (n_tracks + kTriWave - 1) / kTriWave;
   hipLaunchKernelGGL(triangulate_tracks_kernel, dim3((unsigned)blocks), dim3(kTriWave), 0, (hipStream_t)stream,
                      Tracks{obs_xy, obs_cam, cams, n_cams}, offsets, n_tracks, seeds, max_error_px, min_tri_angle_tan2, out_xyz, out_mask,
+                     out_count, out_error);
+  return vc::check_launch();
+}
+
+int vc_refine_tracks(const double* obs_xy, const int32_t* obs_cam, const int32_t* offsets, int n_tracks, const double* cams, int n_cams,
+                     const double* init_xyz, double max_error_px, double min_tri_angle_tan2, double* out_xyz, uint8_t* out_mask,
+                     int32_t* out_count, double* out_error, vc_stream_t stream) {
+  if (n_tracks < 0 || n_cams < 0) return VC_ERR_INVALID_ARG;
+  if (n_tracks == 0) return VC_OK;
+  if (!obs_xy || !obs_cam || !offsets || !init_xyz || !out_xyz || !out_mask || !out_count || !out_error) return VC_ERR_INVALID_ARG;
+  if (!cams && n_cams > 0) return VC_ERR_INVALID_ARG;
+  if (!(max_error_px >= 0.0 && max_error_px < INFINITY && min_tri_angle_tan2 >= 0.0 && min_tri_angle_tan2 < INFINITY))
+    return VC_ERR_INVALID_ARG;
+  const int blocks = (n_tracks + kTriWave - 1) / kTriWave;
+  hipLaunchKernelGGL(refine_tracks_kernel, dim3((unsigned)blocks), dim3(kTriWave), 0, (hipStream_t)stream,
+                     Tracks{obs_xy, obs_cam, cams, n_cams}, offsets, n_tracks, init_xyz, max_error_px, min_tri_angle_tan2, out_xyz, out_mask,
                      out_count, out_error);
   return vc::check_launch();
 }

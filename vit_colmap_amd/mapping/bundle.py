@@ -11,7 +11,8 @@ distortion of SIMPLE_RADIAL (k1) and RADIAL (k1, k2) cameras from the values the
 specification: tests/util_bundle_radial.py): the same loop on the _radial entry points, six unknowns per group in the border.
 With `known_distortion` the grown model was solved on undistorted keypoints; the adjustment then takes the raw
 observations and the known (k1, k2) of every camera as `cam_dist`, held unless refine_distortion frees them.
-Still missing on the way to a mapper: adjustment per round and local adjustment, re-triangulation, merging of points; among the
+The same adjustment after every growth round, with the tracks re-evaluated, is mapping/rounds.py (§4.2m).
+Still missing on the way to a mapper: local adjustment, merging of points; among the
 intrinsics OPENCV's tangential terms.
 
 Where the work runs

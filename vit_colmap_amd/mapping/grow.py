@@ -1,7 +1,8 @@
 """Growth of the seed model: the tracks of the match graph are triangulated under the registered poses
 and the remaining images registered against the new points, in rounds, until a round adds neither a point nor an image.
-It is still not a mapper: no bundle adjustment here (mapping/bundle.py adjusts the result once, §4.2k), no re-triangulation or
-merging of existing points, no point filtering after the rounds, no distortion inside the rounds: a SIMPLE_RADIAL or RADIAL
+It is still not a mapper: no bundle adjustment here (mapping/bundle.py adjusts the result once, §4.2k; mapping/rounds.py runs
+this loop with one adjustment and one re-evaluation of the tracks per round, §4.2m), no local adjustment, no merging of
+existing points, no distortion inside the rounds: a SIMPLE_RADIAL or RADIAL
 camera with k = 0 is grown under the pinhole assumption and mapping/bundle.py refines k afterwards; one with a known non-zero k
 is, with `known_distortion`, grown on keypoints that vc_undistort_points undistorted first.  Specification: tests/util_mapper.py (`grow_model`).  This build's own published rule;
 parity with COLMAP's mapper is unpinned.
@@ -14,6 +15,7 @@ Where the work runs
           tries, the point ids and tracks, the final reprojection errors
 """
 import logging
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -73,14 +75,13 @@ def _components(kps, K, rows):
     return comps
 
 
-def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, known_distortion=False,
-                       undistort_fn=None) -> SparseModel:
-    """Read a matched database -> the seed model grown by rounds.  Raises the seed model's ValueErrors unchanged.
-    `two_view_pose_fn` and `estimate_fn` as in build_seed_model; `triangulate_fn(obs_xy, obs_cam, offsets, cams, seeds,
-    device) -> (xyz, mask, count, error)` on numpy arrays replaces the triangulation launch (tests).
-    `known_distortion`, `undistort_fn` as in build_seed_model (§4.2l): the seed and every round solve on the undistorted
-    keypoints, a keypoint that does not invert is in no track, `xys` are the raw keypoints and `error` uses the distorted
-    projection."""
+def _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, known_distortion, undistort_fn, round_fn=None) -> SparseModel:
+    """The growth loop of build_sparse_model, which states the arguments.  `round_fn(growth)`, if given, is called at the end of
+    every round that added a point or an image (mapping/rounds.py) with the loop's state: device, images, K,
+    kps (the keypoints the solvers see), ids, slot, comps, slots, initial_pair and, to change in place, poses {image id: (R, t,
+    qvec)}, xyz and tracks {point id: ...} and point_of {component: point id}.  A point it removes frees its component for the
+    T-step under the rule below: the component is tried again only once more of its nodes are registered than at its last
+    attempt.  Point ids are never reused."""
     estimate_fn = estimate_fn or estimate_absolute_poses
     triangulate_fn = triangulate_fn or _gpu_triangulate
     database = _read_database(database_path, True, undistort_fn, device) if known_distortion else _read_database(database_path)
@@ -107,6 +108,8 @@ def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, esti
     slots = [np.array([slot[int(i)] for i in nodes[:, 0]], np.int32) for nodes in comps]
     next_id = max(xyz, default=0) + 1
     tried_t, tried_r, rounds = np.zeros(len(comps), np.int64), {}, 0
+    growth = SimpleNamespace(device=device, images=images, K=K, kps=kps, ids=ids, slot=slot, comps=comps, slots=slots,
+                             initial_pair=seed.initial_pair, poses=poses, xyz=xyz, tracks=tracks, point_of=point_of)
     while True:
         # T-step: every track without a point that two registered images see, in one launch
         cams = np.full((len(ids), 16), np.nan)
@@ -157,6 +160,8 @@ def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, esti
             break
         rounds += 1
         logger.info("Growth round %d: %d new points, %d new images", rounds, new_points, new_images)
+        if round_fn is not None:
+            round_fn(growth)
 
     model = SparseModel(initial_pair=seed.initial_pair, rounds=rounds)
     for i, (_, t, q) in sorted(poses.items()):
@@ -171,3 +176,14 @@ def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, esti
             errs.append(_observation_errors(K, kps, known, i, poses[i][0], poses[i][1], xyz[pid][None], kp)[0])
         model.points3D[pid] = dict(xyz=xyz[pid].copy(), rgb=(0, 0, 0), error=float(np.mean(errs)), track=list(tracks[pid]))
     return model
+
+
+def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, known_distortion=False,
+                       undistort_fn=None) -> SparseModel:
+    """Read a matched database -> the seed model grown by rounds.  Raises the seed model's ValueErrors unchanged.
+    `two_view_pose_fn` and `estimate_fn` as in build_seed_model; `triangulate_fn(obs_xy, obs_cam, offsets, cams, seeds,
+    device) -> (xyz, mask, count, error)` on numpy arrays replaces the triangulation launch (tests).
+    `known_distortion`, `undistort_fn` as in build_seed_model (§4.2l): the seed and every round solve on the undistorted
+    keypoints, a keypoint that does not invert is in no track, `xys` are the raw keypoints and `error` uses the distorted
+    projection."""
+    return _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, known_distortion, undistort_fn)

@@ -42,6 +42,7 @@ class SparseModel:
     initial_pair: tuple = None
     rounds: int = None                   # growth rounds that added a point or an image (§4.2j); None: a seed model
     bundle_adjustment: dict = None       # the report of the adjustment (§4.2k); None: a model that was not adjusted
+    round_adjustments: list = None       # the reports of the adjustments per growth round (§4.2m); None: there were none
 
     def mean_track_length(self):
         return float(np.mean([len(p["track"]) for p in self.points3D.values()])) if self.points3D else 0.0
@@ -50,7 +51,8 @@ class SparseModel:
         s = dict(initial_pair=list(self.initial_pair) if self.initial_pair else None, registered_images=len(self.images),
                  num_points3D=len(self.points3D), mean_track_length=self.mean_track_length())
         s = s if self.rounds is None else dict(s, rounds=self.rounds)
-        return s if self.bundle_adjustment is None else dict(s, bundle_adjustment=dict(self.bundle_adjustment))
+        s = s if self.bundle_adjustment is None else dict(s, bundle_adjustment=dict(self.bundle_adjustment))
+        return s if self.round_adjustments is None else dict(s, round_adjustments=[dict(r) for r in self.round_adjustments])
 
     # COLMAP's text layout [recalled: colmap/src/colmap/scene/reconstruction_io.cc]; floats are written with repr, so a model
     # reads back equal

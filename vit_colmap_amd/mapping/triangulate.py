@@ -64,3 +64,35 @@ def triangulate_tracks(obs_xy, obs_cam, offsets, cams, seeds, max_error=MAX_ERRO
         unsorted[src] = mask
         xyz, count, error, mask = xyz[inverse], count[inverse], error[inverse], unsorted
     return xyz, mask.bool(), count, error
+
+
+def refine_tracks(obs_xy, obs_cam, offsets, cams, init_xyz, max_error=MAX_ERROR, min_tri_angle_tan2=MIN_TRI_ANGLE_TAN2):
+    """The tracks of triangulate_tracks evaluated again at the points they have, one launch of
+    vc_refine_tracks: init_xyz float64 (T, 3) in place of the seeds, every other tensor and the four results as there.  A track
+    whose point is not finite or has fewer than two inliers is rejected; otherwise the point is refitted over its inliers and
+    `mask` are the inliers of the result.  Specification: tests/util_rounds.py (`refine_track`)."""
+    if not (obs_xy.is_cuda and obs_xy.dtype == torch.float64 and cams.dtype == torch.float64 and init_xyz.dtype == torch.float64
+            and obs_cam.dtype == torch.int32 and offsets.dtype == torch.int32):
+        raise ValueError("refine_tracks needs float64 observations, cameras and points and int32 slots / offsets on the GPU")
+    dev = obs_xy.device
+    if any(t.device != dev for t in (obs_cam, offsets, cams, init_xyz)):
+        raise ValueError("refine_tracks needs every tensor on the same GPU")
+    T, total = int(init_xyz.shape[0]), int(obs_cam.shape[0])
+    if (init_xyz.shape != (T, 3) or offsets.shape != (T + 1,) or obs_xy.shape != (total, 2) or cams.dim() != 2
+            or cams.shape[1] != 16):
+        raise ValueError("refine_tracks needs obs_xy (total, 2), obs_cam (total,), offsets (T + 1,), cams (n_cams, 16), init_xyz (T, 3)")
+    xyz = torch.full((T, 3), float("nan"), dtype=torch.float64, device=dev)
+    mask = torch.zeros((total,), dtype=torch.uint8, device=dev)
+    count = torch.zeros((T,), dtype=torch.int32, device=dev)
+    error = torch.full((T,), float("nan"), dtype=torch.float64, device=dev)
+    if T == 0 or total == 0:
+        return xyz, mask.bool(), count, error
+    off64 = offsets.to(torch.int64)
+    if int(off64[0]) != 0 or int(off64[-1]) != total or bool((off64[1:] < off64[:-1]).any()):
+        raise ValueError("refine_tracks needs offsets that ascend from 0 to the number of observations")
+    lib = _lib.load()
+    obs_xy, obs_cam, offsets, cams, init_xyz = (t.contiguous() for t in (obs_xy, obs_cam, offsets, cams, init_xyz))
+    _lib.check(lib.vc_refine_tracks(_lib.ptr(obs_xy), _lib.ptr(obs_cam), _lib.ptr(offsets), T, _lib.ptr(cams), int(cams.shape[0]),
+                                    _lib.ptr(init_xyz), float(max_error), float(min_tri_angle_tan2), _lib.ptr(xyz), _lib.ptr(mask),
+                                    _lib.ptr(count), _lib.ptr(error), _lib.stream_ptr()), "vc_refine_tracks")
+    return xyz, mask.bool(), count, error

@@ -82,6 +82,9 @@ class Pipeline:
         refine_distortion = bool(getattr(self.config.reconstruction, "refine_distortion", False))
         if refine_distortion and not bundle_adjustment:         # k1 (and k2) are further unknowns of that adjustment (§4.2k)
             raise ValueError("refine_distortion needs reconstruction.bundle_adjustment (--bundle-adjustment)")
+        adjust_rounds = bool(getattr(self.config.reconstruction, "adjust_rounds", False))
+        if adjust_rounds and not bundle_adjustment:             # it is that adjustment after every growth round (§4.2m)
+            raise ValueError("adjust_rounds needs reconstruction.bundle_adjustment (--bundle-adjustment)")
         ba_loss =str(getattr(self.config.reconstruction, "ba_loss", "trivial"))
         ba_loss_scale = float(getattr(self.config.reconstruction, "ba_loss_scale", 1.0))
         if ba_loss not in BA_LOSSES:
@@ -97,6 +100,7 @@ class Pipeline:
         if camera_params is not None and camera_model in CAMERA_PARAM_NAMES:   # the count, before any database is created
             camera_params = parse_camera_params(camera_params, camera_model)
         known_args = dict(known_distortion=True) if known_distortion else {}
+        rounds_args = dict(adjust_rounds=True) if adjust_rounds else {}   # passed on only where it is on, as known_distortion is
         for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
             if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
                 continue
@@ -155,13 +159,14 @@ class Pipeline:
         if sparse_model:
             if refine_distortion:
                 self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True,
-                                         refine_focal_length=refine_focal_length, refine_distortion=True, **loss_args, **known_args)
+                                         refine_focal_length=refine_focal_length, refine_distortion=True, **loss_args, **known_args,
+                                         **rounds_args)
             elif refine_focal_length:
                 self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=True, refine_focal_length=True,
-                                         **loss_args, **known_args)
+                                         **loss_args, **known_args, **rounds_args)
             else:
                 self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment, **loss_args,
-                                         **known_args)
+                                         **known_args, **rounds_args)
 
         reconstructions = None
         if self.config.do_reconstruction:
@@ -211,12 +216,15 @@ class Pipeline:
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
     def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0,
-                            refine_distortion=False, known_distortion=False):
+                            refine_distortion=False, known_distortion=False, adjust_rounds=False):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
         `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
         `refine_focal_length`: that adjustment also refines the cameras' focal lengths; `loss`, `loss_scale`: its loss, passed on
         only where it is not the trivial one; `refine_distortion`: it also refines k1 (k2) of SIMPLE_RADIAL and RADIAL cameras;
-        `known_distortion`: both models are built on undistorted keypoints (§4.2l), passed on only where it is on."""
+        `known_distortion`: both models are built on undistorted keypoints (§4.2l), passed on only where it is on;
+        `adjust_rounds` (with `adjust`): also output_dir/sparse/mapped and `last_stats["mapped_model"]`, the model grown with an
+        adjustment and a re-evaluation of its tracks after every round (§4.2m), under the same options; the other two models are
+        built and written as without it."""
         from ..mapping.grow import build_sparse_model
 
         known_args = dict(known_distortion=True) if known_distortion else {}
@@ -244,6 +252,16 @@ class Pipeline:
             self.last_stats = dict(self.last_stats, bundle_adjustment=adjusted.stats())
             logger.info("Adjusted model: %d images, %d points, cost %.6g -> %.6g", len(adjusted.images), len(adjusted.points3D),
                         adjusted.bundle_adjustment["initial_cost"], adjusted.bundle_adjustment["final_cost"])
+            if adjust_rounds:
+                from ..mapping.rounds import build_mapped_model
+
+                refine_args = dict(refine_focal_length=refine_focal_length, refine_distortion=refine_distortion)
+                mapped = build_mapped_model(str(db_path), device=device, **{k: v for k, v in refine_args.items() if v}, **loss_args,
+                                            **known_args)
+                mapped.write_text(str(Path(output_dir) / "sparse" / "mapped"))
+                self.last_stats = dict(self.last_stats, mapped_model=mapped.stats())
+                logger.info("Mapped model: %d images, %d points, %d round adjustments", len(mapped.images), len(mapped.points3D),
+                            len(mapped.round_adjustments))
 
     def extract_and_export_metrics(self, db_path, output_dir, reconstructions, dataset, scene, results_dir=None):
         """Database metrics -> `{results_dir}/{dataset}/{scene}/{extractor}.json` + summary.csv row
@@ -304,6 +322,9 @@ def main() -> None:
     ap.add_argument("--refine-distortion", dest="refine_distortion", action="store_true",
                     help="with --bundle-adjustment: the adjustment also refines the radial distortion, k of SIMPLE_RADIAL cameras and "
                          "k1, k2 of RADIAL ones, from the values in the database (0 as the extractors write them)")
+    ap.add_argument("--adjust-rounds", dest="adjust_rounds", action="store_true",
+                    help="with --bundle-adjustment: also write output/sparse/mapped, the model grown with a bundle adjustment and a "
+                         "re-evaluation of every track after each growth round; what long sequences need")
     ap.add_argument("--ba-loss", dest="ba_loss", choices=list(BA_LOSSES), default="trivial",
                     help="with --bundle-adjustment: the loss of the adjustment; huber and soft_l1 keep observations that are tens "
                          "of pixels off their point from setting the poses")

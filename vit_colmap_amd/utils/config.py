@@ -136,6 +136,7 @@ class ReconstructionConfig:
     ba_loss: str = "trivial"     # with bundle_adjustment: the loss of the adjustment, "trivial", "huber" or "soft_l1" (§4.2k, "The loss")
     ba_loss_scale: float = 1.0   # px: the residual at which the loss leaves the square
     refine_distortion: bool = False   # with bundle_adjustment: it also refines k of SIMPLE_RADIAL, k1 and k2 of RADIAL cameras (§4.2k)
+    adjust_rounds: bool = False   # with bundle_adjustment: write output_dir/sparse/mapped, grown with an adjustment and a re-evaluation of the tracks per round (§4.2m)
 
     def to_mapper_options(self):
         import pycolmap  # noqa: PLC0415 - optional, third party
@@ -207,6 +208,8 @@ class Config:
             config.reconstruction.refine_focal_length = True
         if getattr(args, "refine_distortion", False):
             config.reconstruction.refine_distortion = True
+        if getattr(args, "adjust_rounds", False):
+            config.reconstruction.adjust_rounds = True
         if getattr(args, "ba_loss", None):
             config.reconstruction.ba_loss = args.ba_loss
         if getattr(args, "ba_loss_scale", None) is not None:
