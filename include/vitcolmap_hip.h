@@ -393,6 +393,40 @@ int vc_ba_step(const double* cams, int n_cams, const double* points, int n_point
                double* out_cams, double* out_points, double* out_dx, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bundle adjustment without the dense S ("The solver"): what preconditioned conjugate gradients on
+ * S dc = -g need, for any number of cameras.  Both entry points take the index arrays and the outputs of vc_ba_linearize_points
+ * (or of vc_ba_linearize_points_loss, as they are) exactly as vc_ba_reduce_cameras does; same arithmetic conventions, no
+ * atomics, every sum has one owner lane and runs in list order: two calls return the same bytes.  Specification:
+ * tests/util_bundle_pcg.py.
+ * vc_ba_camera_blocks, per camera a over its observations in ascending order (one wave per camera):
+ *   out_U     [n_cams][36]  U_a = sum J_c' J_c, U_ii += lambda U_ii
+ *   out_g     [6 n_cams]    g_a = sum J_c' r - sum Y g_p, Y = W V^-1: the bytes of vc_ba_reduce_cameras' out_g
+ *   out_D     [n_cams][36]  D_a = S_aa = U_a - sum Y W_a' over the elements of the point's track whose camera is a, in track
+ *                           order (the observation itself and a camera twice in a track included): the bytes of the diagonal
+ *                           block of vc_ba_reduce_cameras' out_S
+ *   out_fixed [6 n_cams]    uint8, 1 where the parameter is held or its undamped U_ii is 0: there the diagonal of U_a and D_a is 1
+ *                           (rows and columns are 0, as no usable observation moves it) and g is 0
+ *   out_Minv  [n_cams][36]  D_a^-1 column by column: D = L L' by rows, L y = e_k, L' x = y, every sum subtracted from its first
+ *                           term left to right; the identity where a pivot is not finite and positive
+ * vc_ba_schur_product: out_q [6 n_cams] = S p without S, two launches.  Entries of p at fixed parameters are read as 0.
+ *   points    one point per lane, track order: s_j = V_j^-1 (sum over usable observations W_o' p_cam(o)) into workspace_s
+ *             [n_points][3]; 0 for a constant point and for a point whose offsets delimit nothing
+ *   cameras   one workgroup per camera over its list in ascending order: q_a = U_a p_a - sum W_o s_point(o), the row of U_a left
+ *             to right; q_i = p_i at a fixed parameter.  U and fixed are vc_ba_camera_blocks' (U carries the damping).
+ * This equals out_S p of vc_ba_reduce_cameras up to rounding (the sum is associated differently).  No limit on n_cams.
+ * n_cams = 0: VC_OK whatever the pointers are.  A null pointer that a size needs, a negative size, for vc_ba_camera_blocks a
+ * lambda that is negative or not finite: VC_ERR_INVALID_ARG, nothing is launched.  Offsets that are negative, descend or pass
+ * total skip their point or camera as above (a skipped camera has the blocks of one without observations); every index is checked.
+ * ------------------------------------------------------------------------------------------ */
+int vc_ba_camera_blocks(int n_cams, const uint8_t* const_mask, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                        const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point, double lambda, const double* vinv,
+                        const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_U, double* out_D, double* out_Minv,
+                        double* out_g, uint8_t* out_fixed, vc_stream_t stream);
+int vc_ba_schur_product(int n_cams, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets,
+                        const int32_t* cam_obs, const int32_t* obs_point, const double* vinv, const uint8_t* obs_ok, const double* obs_lin,
+                        const double* U, const uint8_t* fixed, const double* p, double* workspace_s, double* out_q, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Bundle adjustment with refined intrinsics ("The border"): the three entry points above never move
  * an intrinsic; these three add theta_g = (fx, fy, cx, cy) of every group of cameras as a border of the reduced system,
  *   [[S, B], [B', C]] (dc, dtheta) = -(g, h),  S and g from vc_ba_reduce_cameras unchanged,

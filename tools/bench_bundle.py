@@ -13,6 +13,11 @@ border's two passes and the step, beside the plain points pass and the border wi
 the loop that refines k1, alternating with the others.  --loss huber|soft_l1 (--loss-scale PX, default 1): after those columns also the points pass
 under the loss (vc_ba_linearize_points_loss) and, with --refine-focal, the border's two passes with obs_w, on the same buffers;
 and the loop under the loss beside the plain loop, alternating (with --refine-focal the refined loop under the loss too).
+--solver pcg ("The solver" in §4.2k): after every other column vc_ba_camera_blocks, vc_ba_schur_product (both launches), one
+whole solve by conjugate gradients on the first linearisation (wall clock, its host reads included) beside the Cholesky column,
+the same number of iterations without the host read, and the pcg loop alternating with the dense loop; also a third arc of
+--big-cams cameras (default 512, --big-points points) and, with pcg alone, a fourth of --above-cams cameras (default 1024), which
+the dense route refuses.
 Prints one JSON line.  Needs a GPU."""
 import argparse
 import json
@@ -86,7 +91,7 @@ def device_ms(fn, iters):
     return float(np.median(times))
 
 
-def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radial=False):
+def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radial=False, solver=None):
     cams, points, offsets, obs_cam, obs_xy, mask = problem
     if refine:
         cams = cams.copy()
@@ -97,7 +102,7 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
     d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (cams, mask, points, offsets, obs_cam, obs_xy)]
     x = [torch.from_numpy(a).to(dev) for a in bundle.camera_index(obs_cam, offsets, c)]
     b = bundle._Buffers(torch, c, n, t, dev, with_loss=loss is not None)
-    S = torch.zeros((6 * c, 6 * c), dtype=torch.float64, device=dev)
+    S = torch.zeros((6 * c, 6 * c) if c <= _lib.VC_BA_MAX_CAMS else (1, 1), dtype=torch.float64, device=dev)
     g, dc = torch.zeros(6 * c, dtype=torch.float64, device=dev), torch.zeros(6 * c, dtype=torch.float64, device=dev)
     out_cams, out_points, dx = torch.zeros_like(d[0]), torch.zeros_like(d[2]), torch.zeros_like(d[2])
     p, stream, lam = _lib.ptr, _lib.stream_ptr(), bundle.BA_LAMBDA0
@@ -119,7 +124,8 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
                                   p(out_points), p(dx), stream), "vc_ba_step")
 
     out = dict(cameras=c, points=n, observations=t)
-    stages = [("linearize_ms", linearize), ("reduce_ms", reduce), ("solve_ms", solve), ("step_ms", step)]
+    dense = c <= _lib.VC_BA_MAX_CAMS                                  # above the cap only what pcg needs is measured
+    stages = [("linearize_ms", linearize), ("reduce_ms", reduce), ("solve_ms", solve), ("step_ms", step)] if dense else [("linearize_ms", linearize)]
     groups = {}
     if refine:                                                        # one tied group, the principal point held
         f64 = dict(dtype=torch.float64, device=dev)
@@ -206,8 +212,52 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
 
         stages += [("linearize_radial_ms", linearize_radial), ("linearize_intrinsics_radial_ms", linearize_intrinsics_radial),
                    ("reduce_border_radial_ms", reduce_border_radial), ("step_radial_ms", step_radial)]
+    if solver == "pcg":
+        pcg = bundle._Pcg(torch, lib, c, n, dev, bundle.PCG_REL_TOL, bundle.PCG_MAX_ITERATIONS)
+        vector = torch.randn(6 * c, dtype=torch.float64, device=dev)
+
+        def blocks(s=pcg):
+            _lib.check(lib.vc_ba_camera_blocks(c, p(d[1]), n, p(d[3]), p(d[4]), t, p(x[0]), p(x[1]), p(x[2]), lam, p(b.vinv), p(b.gp), p(b.obs_ok),
+                                               p(b.obs_lin), p(s.U), p(s.D), p(s.Minv), p(s.g), p(s.fixed), stream), "vc_ba_camera_blocks")
+
+        def product(s=pcg, v=vector):
+            _lib.check(lib.vc_ba_schur_product(c, n, p(d[3]), p(d[4]), t, p(x[0]), p(x[1]), p(x[2]), p(b.vinv), p(b.obs_ok), p(b.obs_lin), p(s.U),
+                                               p(s.fixed), p(v), p(s.s), p(s.q), stream), "vc_ba_schur_product")
+
+        stages += [("blocks_ms", blocks), ("product_ms", product)]
     for name, fn in stages:
         out[name] = round(device_ms(fn, iters), 4)
+    if solver == "pcg":
+        # one whole solve on the first linearisation, wall clock with its host reads; then the same number of iterations of the same
+        # device work without the read per iteration, which is what the read costs
+        linearize()
+        solves, blind = [], []
+        for _ in range(loops + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, _, k = pcg.solve(blocks, product)
+            torch.cuda.synchronize()
+            solves.append(1e3 * (time.perf_counter() - t0))
+            Minv, free = pcg.Minv.view(-1, 6, 6), pcg.fixed == 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            blocks()
+            r = torch.where(free, -pcg.g, torch.zeros_like(pcg.g))
+            z = (Minv * r.view(-1, 1, 6)).sum(dim=2).reshape(-1)
+            q_, rz, xs = z.clone(), torch.dot(r, z), torch.zeros_like(r)
+            for _ in range(k):
+                product(pcg, q_)
+                pq = torch.dot(q_, pcg.q)
+                alpha = rz / pq
+                xs, r = xs + alpha * q_, r - alpha * pcg.q
+                torch.where(torch.isfinite(pq) & (pq > 0), torch.dot(r, r), pcg.nan)
+                z = (Minv * r.view(-1, 1, 6)).sum(dim=2).reshape(-1)
+                rz_new = torch.dot(r, z)
+                q_, rz = z + (rz_new / rz) * q_, rz_new
+            torch.cuda.synchronize()
+            blind.append(1e3 * (time.perf_counter() - t0))
+        out.update(pcg_solve_ms=round(float(np.median(solves[1:])), 3), pcg_solve_iterations=k,
+                   pcg_solve_without_reads_ms=round(float(np.median(blind[1:])), 3))
 
     def loop(**kw):
         torch.cuda.synchronize()
@@ -216,9 +266,14 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0), report, cams_out
 
-    walls, refined_walls, loss_walls, refined_loss_walls, radial_walls = [], [], [], [], []
+    walls, refined_walls, loss_walls, refined_loss_walls, radial_walls, pcg_walls = [], [], [], [], [], []
     loss_args = {} if loss is None else dict(loss=loss, loss_scale=loss_scale)
     for _ in range(loops + 1):                                        # the first run warms up; the loops alternate
+        if solver == "pcg":
+            wall, with_pcg, _ = loop(solver="pcg")
+            pcg_walls.append(wall)
+        if not dense:
+            continue
         wall, report, _ = loop()
         walls.append(wall)
         if refine:
@@ -233,8 +288,13 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
         if radial:
             wall, with_k, _ = loop(**radial_args)
             radial_walls.append(wall)
-    out.update(loop_ms=round(float(np.median(walls[1:])), 3), iterations=report["iterations"], accepted_steps=report["accepted_steps"],
-               initial_cost=report["initial_cost"], final_cost=report["final_cost"])
+    if dense:
+        out.update(loop_ms=round(float(np.median(walls[1:])), 3), iterations=report["iterations"], accepted_steps=report["accepted_steps"],
+                   initial_cost=report["initial_cost"], final_cost=report["final_cost"])
+    if solver == "pcg":
+        out.update(pcg_loop_ms=round(float(np.median(pcg_walls[1:])), 3), pcg_loop_iterations=with_pcg["iterations"],
+                   pcg_accepted_steps=with_pcg["accepted_steps"], pcg_initial_cost=with_pcg["initial_cost"],
+                   pcg_final_cost=with_pcg["final_cost"], pcg_iterations=with_pcg["pcg_iterations"])
     if refine:
         out.update(refined_loop_ms=round(float(np.median(refined_walls[1:])), 3), refined_iterations=refined["iterations"],
                    refined_accepted_steps=refined["accepted_steps"], refined_final_cost=refined["final_cost"], refined_focal=float(cams_out[0, 12]))
@@ -264,11 +324,22 @@ def main():
     ap.add_argument("--radial", action="store_true",
                     help="also time the entry points with radial distortion (six unknowns in one group, k1 free from 0) and the loop that "
                          "refines k1 (DESIGN.md §4.2k, \"The distortion\")")
+    ap.add_argument("--solver", choices=["pcg"], default=None,
+                    help="also time the two entry points of the matrix-free solver, one solve and the pcg loop beside the dense one, on a "
+                         "third arc of --big-cams cameras too and on a fourth of --above-cams with pcg alone (DESIGN.md §4.2k, \"The solver\")")
+    ap.add_argument("--big-cams", dest="big_cams", type=int, default=512)
+    ap.add_argument("--big-points", dest="big_points", type=int, default=51200)
+    ap.add_argument("--above-cams", dest="above_cams", type=int, default=1024)
+    ap.add_argument("--above-points", dest="above_points", type=int, default=102400)
     args = ap.parse_args()
-    extra = (args.refine_focal, args.loss, args.loss_scale, args.radial)
-    print(json.dumps(dict(tool="bench_bundle", iters=args.iters, loops=args.loops, refine_focal=args.refine_focal, loss=args.loss,
-                          loss_scale=args.loss_scale, radial=args.radial, windowed=measure(windowed_problem(), args.iters, args.loops, *extra),
-                          arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops, *extra))))
+    extra = (args.refine_focal, args.loss, args.loss_scale, args.radial, args.solver)
+    out = dict(tool="bench_bundle", iters=args.iters, loops=args.loops, refine_focal=args.refine_focal, loss=args.loss,
+               loss_scale=args.loss_scale, radial=args.radial, solver=args.solver, windowed=measure(windowed_problem(), args.iters, args.loops, *extra),
+               arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops, *extra))
+    if args.solver == "pcg":
+        out.update(big_arc=measure(arc_problem(args.big_cams, args.big_points), args.iters, args.loops, *extra),
+                   above_arc=measure(arc_problem(args.above_cams, args.above_points), args.iters, args.loops, False, None, 1.0, False, "pcg"))
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":

@@ -70,6 +70,9 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vc_ba_step": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_ba_camera_blocks": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double]
+                            + [c_void_p] * 10),
+    "vc_ba_schur_product": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 12),
     "vc_ba_linearize_intrinsics": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]
                                    + [c_void_p] * 8),
     "vc_ba_reduce_border": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,

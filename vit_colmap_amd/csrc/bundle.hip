@@ -9,13 +9,16 @@
 // template argument, and without it return the bytes they returned.  With radial distortion (vc_ba_linearize_points_radial,
 // vc_ba_linearize_intrinsics_radial, vc_ba_reduce_border_radial, vc_ba_step_radial; COLMAP's SIMPLE_RADIAL and RADIAL) the
 // camera's (k1, k2) travel beside its row as cam_dist [n_cams][2] and theta_g = (fx, fy, cx, cy, k1, k2); the routines take the
-// distortion as a second template argument, and without it are what they were.  The order of operations, in full (BaRadial,
+// distortion as a second template argument, and without it are what they were.  Without the dense S ("The solver" in §4.2k:
+// vc_ba_camera_blocks, vc_ba_schur_product) the caller solves S dc = -g by preconditioned conjugate gradients: the first gives
+// per camera U_a, the diagonal block D_a = S_aa, D_a^-1, g_a and which parameters are fixed, the second q = S p in two passes
+// over what the points pass left, for any number of cameras.  The order of operations, in full (BaRadial,
 // ba_project_radial, ba_observe): ba_project on the row with fx = fy = 1 gives iu = 1 / Xc_z, (xu, xv) and their Jacobian
 // (nu; nv); rho = xu xu + xv xv, s = 1 + k1 rho + k2 rho rho, e = 2 (k1 + 2 k2 rho), d00 = s + xu xu e, d01 = xu xv e,
 // d11 = s + xv xv e; xd = xu s, yd = xv s, r = (fx xd + cx - u, fy yd + cy - v); J_p = (fx (d00 nu + d01 nv); fy (d01 nu + d11 nv))
 // and J_c the same map of the pinhole rows at fx = fy = 1; pu = fx xu rho, pv = fy xv rho, qu = pu rho, qv = pv rho and J_theta =
 // ((xd, 0, 1, 0, pu, qu); (0, yd, 0, 1, pv, qv)); every product and sum left to right as written.  Specification:
-// tests/util_bundle.py, tests/util_bundle_intr.py, tests/util_bundle_loss.py, tests/util_bundle_radial.py.  This build's own
+// tests/util_bundle.py, tests/util_bundle_intr.py, tests/util_bundle_loss.py, tests/util_bundle_radial.py, tests/util_bundle_pcg.py.  This build's own
 // published rule; parity with COLMAP / Ceres is unpinned.
 //
 // float64 in single operations in the written order (-ffp-contract=off), the only library call is sqrt, no atomics.
@@ -35,6 +38,10 @@
 //                the order of a lane's additions is the rule's: camera a's observations in ascending order and, inside each, the
 //                track of its point in track order (the next element's flag and camera are loaded while the current element's W
 //                is on its way).  ba_reduce_border_kernel keeps a lane's entries of B_a [6][4 G] in its registers.
+//   solver       ba_camera_blocks_kernel, one wave per camera through ba_camera_walk: lane e < 36 keeps entry e of U_a and of
+//                (sum Y W')_aa in its registers, six lanes invert D_a by a 6x6 Cholesky factorisation, a column each.
+//                ba_product_points_kernel, one point per lane: s_j = V^-1 sum W' p.  ba_product_cameras_kernel, four waves per
+//                camera: 256 entries of the list resolved at once, W s left in LDS, six owner lanes add them in list order.
 //   step         ba_step_points_kernel, one point per lane: dX = -V^-1 (g_p + sum W' dc + sum T_g' dtheta_g) in track order, then
 //                group order, X + dX; ba_step_cameras_kernel, one camera per lane: q = (1, w / 2) normalised, R(q) R, t + dt, its
 //                group's dtheta added, whether the focal lengths stay positive.  vc_ba_step launches both without groups: T,
@@ -273,14 +280,19 @@ __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, c
 
 // Entry idx of camera a's list -> the observation and its point's track; false where the entry names no usable
 // observation of camera a (the point's offsets, the observation's owner and its slot are checked here).
-__host__ __device__ __forceinline__ bool ba_camera_obs(const BaProblem& d, const BaLinear& l, const int32_t* __restrict__ cam_obs,
-                                                       const int32_t* __restrict__ obs_point, int a, int idx, int& o, int& j,
-                                                       int& lo, int& hi) {
-  o = cam_obs[idx];
+__host__ __device__ __forceinline__ bool ba_camera_obs_at(const BaProblem& d, const BaLinear& l, const int32_t* __restrict__ obs_point, int a,
+                                                          int o, int& j, int& lo, int& hi) {
   if (o < 0 || o >= d.total) return false;
   j = obs_point[o];
   if (j < 0 || j >= d.n_points || !ba_track(d.offsets, j, d.total, lo, hi) || o < lo || o >= hi) return false;
   return d.obs_cam[o] == a && l.obs_ok[o] != 0;
+}
+
+__host__ __device__ __forceinline__ bool ba_camera_obs(const BaProblem& d, const BaLinear& l, const int32_t* __restrict__ cam_obs,
+                                                       const int32_t* __restrict__ obs_point, int a, int idx, int& o, int& j,
+                                                       int& lo, int& hi) {
+  o = cam_obs[idx];
+  return ba_camera_obs_at(d, l, obs_point, a, o, j, lo, hi);
 }
 
 // The registers of one lane of the camera pass: its entry of U_a (the lanes that own block a), of sum J_c' r and of sum Y g_p
@@ -381,6 +393,155 @@ __host__ __device__ __forceinline__ void ba_lane_finish(int n_cams, unsigned hel
     S[(long long)(6 * a + r) * (6 * n_cams) + 6 * b + c] = u - acc[idx];
   }
   if (lane < 6) g[6 * a + lane] = s.gr - s.gy;
+}
+
+// ---- the solver without S (vc_ba_camera_blocks, vc_ba_schur_product; "The solver" in DESIGN.md §4.2k) -----------------------------
+// Preconditioned conjugate gradients on S dc = -g need, per camera, U_a, the diagonal block D_a = S_aa, its inverse and g_a, and
+// per iteration q = S p = U p - sum W V^-1 sum W' p, which two passes over what the points pass left compute without S.
+constexpr int kBaProductThreads = 256;         // entries of a camera's list that the product's camera pass resolves between barriers
+
+// The registers of one lane of the blocks pass: entry e = lane = 6 r + c of U_a and of (sum Y W')_aa (lanes 0 .. 35), the two sums
+// of g_a (lanes 0 .. 5).
+struct BaBlockLane {
+  double u, acc, gr, gy;
+};
+
+// One lane's additions for observation o of camera a (point j, track lo .. hi): what ba_lane_update adds to its entries of block
+// a and of g, in its order, and nothing of any other block.
+__host__ __device__ __forceinline__ void ba_block_update(const BaProblem& d, const BaLinear& l, int a, int o, int j, int lo, int hi,
+                                                         int lane, const double* y, BaBlockLane& s) {
+  const double* lin = l.obs_lin + (long long)o * kBaLin;
+  if (lane < 6) {
+    const double* gp = l.gp + (long long)j * 3;
+    s.gr += lin[lane] * lin[kBaLinR] + lin[6 + lane] * lin[kBaLinR + 1];
+    s.gy += y[3 * lane] * gp[0] + y[3 * lane + 1] * gp[1] + y[3 * lane + 2] * gp[2];
+  }
+  if (lane >= 36) return;
+  const int r = lane / 6, c = lane % 6;
+  s.u += lin[r] * lin[c] + lin[6 + r] * lin[6 + c];
+  const double* yr = y + 3 * r;
+  for (int o2 = lo; o2 < hi; ++o2) {
+    if (!l.obs_ok[o2] || d.obs_cam[o2] != a) continue;                        // the observation itself and a camera twice in a track included
+    const double* w = l.obs_lin + (long long)o2 * kBaLin + kBaLinW + 3 * c;
+    s.acc += yr[0] * w[0] + yr[1] * w[1] + yr[2] * w[2];
+  }
+}
+
+// Entry e of U_a as the system has it: the diagonal damped, or 1 where the parameter is fixed (held, or no usable observation
+// moves it) -> fixed, for the diagonal entries.
+__host__ __device__ __forceinline__ double ba_block_u(unsigned held, double lambda, int e, double u, bool& fixed) {
+  fixed = false;
+  if (e / 6 != e % 6) return u;
+  fixed = ((held >> (e / 6)) & 1u) || u == 0.0;
+  return fixed ? 1.0 : u + lambda * u;
+}
+
+// Column k of D^-1 for the symmetric 6x6 D (row-major, its lower triangle is read): D = L L' by rows, L y = e_k, L' x = y, every
+// sum subtracted from its first term left to right.  A pivot that is not finite and positive: column k of the identity.
+__host__ __device__ __forceinline__ void ba_block_inverse(const double* D, int k, double (&x)[6]) {
+  double L[6][6], y[6];
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double s = D[6 * j + j];
+#pragma unroll
+    for (int m = 0; m < j; ++m) s -= L[j][m] * L[j][m];
+    ok = ok && s > 0.0 && s < INFINITY;                                       // false for NaN
+    const double piv = sqrt(s);
+    L[j][j] = piv;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double t = D[6 * i + j];
+#pragma unroll
+      for (int m = 0; m < j; ++m) t -= L[i][m] * L[j][m];
+      L[i][j] = t / piv;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = i == k ? 1.0 : 0.0;
+#pragma unroll
+    for (int m = 0; m < i; ++m) s -= L[i][m] * y[m];
+    y[i] = s / L[i][i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i];
+#pragma unroll
+    for (int m = i + 1; m < 6; ++m) s -= L[m][i] * x[m];
+    x[i] = s / L[i][i];
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) x[i] = ok ? x[i] : i == k ? 1.0 : 0.0;
+}
+
+// Entry i of p as the product reads it: 0 at a fixed parameter.
+__host__ __device__ __forceinline__ double ba_product_entry(const uint8_t* __restrict__ fixed, const double* __restrict__ p, long long i) {
+  return fixed[i] ? 0.0 : p[i];
+}
+
+// The points pass of the product, point j: s_j = V^-1 sum W' p over the usable observations of the track in track order; 0 where
+// the point's offsets delimit nothing (nothing of it is read) and where the point is constant.
+__host__ __device__ __forceinline__ void ba_product_point(const BaProblem& d, const BaLinear& l, const uint8_t* __restrict__ fixed,
+                                                          const double* __restrict__ p, int j, double (&s)[3]) {
+  s[0] = s[1] = s[2] = 0.0;
+  int lo, hi;
+  if (!ba_track(d.offsets, j, d.total, lo, hi)) return;
+  double t[3] = {0.0, 0.0, 0.0};
+  for (int o = lo; o < hi; ++o) {
+    if (!l.obs_ok[o]) continue;
+    const int b = d.obs_cam[o];
+    if (b < 0 || b >= d.n_cams) continue;
+    const double* w = l.obs_lin + (long long)o * kBaLin + kBaLinW;
+    double e[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) e[i] = ba_product_entry(fixed, p, 6 * (long long)b + i);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      t[k] += w[k] * e[0] + w[3 + k] * e[1] + w[6 + k] * e[2] + w[9 + k] * e[3] + w[12 + k] * e[4] + w[15 + k] * e[5];
+  }
+  const double* v = l.vinv + (long long)j * 6;
+  s[0] = v[0] * t[0] + v[1] * t[1] + v[2] * t[2];
+  s[1] = v[1] * t[0] + v[3] * t[1] + v[4] * t[2];
+  s[2] = v[2] * t[0] + v[4] * t[1] + v[5] * t[2];
+}
+
+// What the lanes of the product's camera pass leave for the six owners: whether entry base + lane of camera a's list is a usable
+// observation and, for one, W s of its point (6 numbers), parameter-major so that the lanes' stores do not collide.
+struct BaProductBatch {
+  int ok[kBaProductThreads];
+  double c[6][kBaProductThreads];
+};
+
+// o: the entry of cam_obs that lane `lane` of the batch resolves, -1 past the end of the list.
+__host__ __device__ __forceinline__ void ba_product_prepare(const BaProblem& d, const BaLinear& l, const int32_t* __restrict__ obs_point,
+                                                            const double* __restrict__ s, int a, int o, int lane, BaProductBatch& batch) {
+  int j = 0, lo = 0, hi = 0;
+  const bool ok = ba_camera_obs_at(d, l, obs_point, a, o, j, lo, hi);
+  batch.ok[lane] = ok ? 1 : 0;
+  if (!ok) return;
+  const double* w = l.obs_lin + (long long)o * kBaLin + kBaLinW;
+  const double s0 = s[3 * (long long)j], s1 = s[3 * (long long)j + 1], s2 = s[3 * (long long)j + 2];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) batch.c[r][lane] = w[3 * r] * s0 + w[3 * r + 1] * s1 + w[3 * r + 2] * s2;
+}
+
+// Owner lane i adds the first m entries of a batch to its sum, in list order.
+__host__ __device__ __forceinline__ void ba_product_add(const BaProductBatch& batch, int m, int i, double& sum) {
+  for (int k = 0; k < m; ++k)
+    if (batch.ok[k]) sum += batch.c[i][k];
+}
+
+// Entry i of q_a = U_a p_a - sum W s, the row of U left to right; a fixed parameter returns its entry of p as it is.
+__host__ __device__ __forceinline__ double ba_product_finish(const double* __restrict__ U, const uint8_t* __restrict__ fixed,
+                                                             const double* __restrict__ p, int a, int i, double sum) {
+  const long long at = 6 * (long long)a;
+  if (fixed[at + i]) return p[at + i];
+  const double* u = U + 36 * (long long)a + 6 * i;
+  double e[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) e[k] = ba_product_entry(fixed, p, at + k);
+  return (u[0] * e[0] + u[1] * e[1] + u[2] * e[2] + u[3] * e[3] + u[4] * e[4] + u[5] * e[5]) - sum;
 }
 
 // One camera's pose update without trigonometry: q = (1, w / 2) / |(1, w / 2)|, R <- R(q) R, t <- t + dt; the intrinsics are copied.
@@ -776,6 +937,78 @@ __global__ __launch_bounds__(kBaWave) void ba_reduce_cameras_kernel(BaProblem d,
   ba_lane_finish(d.n_cams, d.const_mask[a], lambda, a, lane, acc, s, out_S, out_g);
 }
 
+// U_a, D_a, D_a^-1, g_a and the fixed flags: one wave per camera over its list, a lane's entry of the two blocks in its registers;
+// D_a passes through LDS to the six lanes that each invert it for one column.
+__global__ __launch_bounds__(kBaWave) void ba_camera_blocks_kernel(BaProblem d, BaLinear l, const int32_t* __restrict__ cam_offsets,
+                                                                   const int32_t* __restrict__ cam_obs,
+                                                                   const int32_t* __restrict__ obs_point, double lambda,
+                                                                   double* __restrict__ out_U, double* __restrict__ out_D,
+                                                                   double* __restrict__ out_Minv, double* __restrict__ out_g,
+                                                                   uint8_t* __restrict__ out_fixed) {
+  __shared__ BaBatch batch;
+  __shared__ double block[36];
+  __shared__ int fixed_of[6];
+  const int a = blockIdx.x, lane = threadIdx.x;
+  BaBlockLane s{0.0, 0.0, 0.0, 0.0};
+  ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
+                 [&](int o, int j, int lo, int hi, const double* y) { ba_block_update(d, l, a, o, j, lo, hi, lane, y, s); });
+  if (lane < 36) {
+    bool fixed;
+    const double u = ba_block_u(d.const_mask[a], lambda, lane, s.u, fixed);
+    const double dd = u - s.acc;
+    out_U[36 * (long long)a + lane] = u, out_D[36 * (long long)a + lane] = dd;
+    block[lane] = dd;
+    if (lane / 6 == lane % 6) fixed_of[lane / 6] = fixed ? 1 : 0, out_fixed[6 * (long long)a + lane / 6] = fixed ? 1 : 0;
+  }
+  __syncthreads();
+  if (lane < 6) {
+    out_g[6 * (long long)a + lane] = fixed_of[lane] ? 0.0 : s.gr - s.gy;
+    double x[6];
+    ba_block_inverse(block, lane, x);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) out_Minv[36 * (long long)a + 6 * i + lane] = x[i];
+  }
+}
+
+__global__ __launch_bounds__(kBaWave) void ba_product_points_kernel(BaProblem d, BaLinear l, const uint8_t* __restrict__ fixed,
+                                                                    const double* __restrict__ p, double* __restrict__ out_s) {
+  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
+  if (j >= d.n_points) return;
+  double s[3];
+  ba_product_point(d, l, fixed, p, (int)j, s);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out_s[3 * j + k] = s[k];
+}
+
+// q_a: one workgroup of four waves per camera.  Every lane resolves one entry of the list and forms W s for it; lanes 0 .. 5 own
+// the six sums and add a batch in list order.  Two batches alternate in LDS and the owners add batch n - 1 after the first load
+// of batch n is on its way, so one barrier per batch is enough: a batch is overwritten two barriers after it was written, and
+// the owners have added it before the barrier in between.
+__global__ __launch_bounds__(kBaProductThreads) void ba_product_cameras_kernel(BaProblem d, BaLinear l, const int32_t* __restrict__ cam_offsets,
+                                                                               const int32_t* __restrict__ cam_obs,
+                                                                               const int32_t* __restrict__ obs_point,
+                                                                               const double* __restrict__ U, const uint8_t* __restrict__ fixed,
+                                                                               const double* __restrict__ p, const double* __restrict__ s,
+                                                                               double* __restrict__ out_q) {
+  __shared__ BaProductBatch batch[2];
+  const int a = blockIdx.x, lane = threadIdx.x;
+  double sum = 0.0;
+  int first, last;
+  if (ba_camera_list(cam_offsets, a, d.total, first, last)) {
+    int buf = 0, pending = 0;                                                 // entries of the batch the owners have not added yet
+    for (long long base = first; base < last; base += kBaProductThreads, buf ^= 1) {
+      const int m = last - base < kBaProductThreads ? (int)(last - base) : kBaProductThreads;
+      const int o = lane < m ? cam_obs[base + lane] : -1;
+      if (lane < 6) ba_product_add(batch[buf ^ 1], pending, lane, sum);
+      ba_product_prepare(d, l, obs_point, s, a, o, lane, batch[buf]);
+      pending = m;
+      __syncthreads();
+    }
+    if (lane < 6) ba_product_add(batch[buf ^ 1], pending, lane, sum);
+  }
+  if (lane < 6) out_q[6 * (long long)a + lane] = ba_product_finish(U, fixed, p, a, lane, sum);
+}
+
 template <bool kLoss>
 __global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_kernel(BaProblem d, BaLinear l, BaGroups gr, double* __restrict__ out_obs_xn,
                                                                           double* out_T, double* __restrict__ out_terms,
@@ -1032,6 +1265,40 @@ int vc_ba_reduce_cameras(int n_cams, const uint8_t* const_mask, int n_points, co
   const BaProblem d{nullptr, const_mask, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
   hipLaunchKernelGGL(ba_reduce_cameras_kernel, dim3((unsigned)n_cams), dim3(kBaWave), (size_t)ba_reduce_lds_bytes(n_cams),
                      (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, cam_offsets, cam_obs, obs_point, lambda, out_S, out_g);
+  return vc::check_launch();
+}
+
+int vc_ba_camera_blocks(int n_cams, const uint8_t* const_mask, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                        const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point, double lambda, const double* vinv,
+                        const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_U, double* out_D, double* out_Minv,
+                        double* out_g, uint8_t* out_fixed, vc_stream_t stream) {
+  if (n_cams < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_cams == 0) return VC_OK;
+  if (!const_mask || !cam_offsets || !out_U || !out_D || !out_Minv || !out_g || !out_fixed) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!offsets || !vinv || !gp)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{nullptr, const_mask, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_camera_blocks_kernel, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
+                     BaLinear{vinv, gp, obs_ok, obs_lin}, cam_offsets, cam_obs, obs_point, lambda, out_U, out_D, out_Minv, out_g, out_fixed);
+  return vc::check_launch();
+}
+
+int vc_ba_schur_product(int n_cams, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets,
+                        const int32_t* cam_obs, const int32_t* obs_point, const double* vinv, const uint8_t* obs_ok, const double* obs_lin,
+                        const double* U, const uint8_t* fixed, const double* p, double* workspace_s, double* out_q, vc_stream_t stream) {
+  if (n_cams < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_cams == 0) return VC_OK;
+  if (!cam_offsets || !U || !fixed || !p || !out_q) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!offsets || !vinv || !workspace_s)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  const BaLinear l{vinv, nullptr, obs_ok, obs_lin};
+  if (n_points > 0)
+    hipLaunchKernelGGL(ba_product_points_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       d, l, fixed, p, workspace_s);
+  hipLaunchKernelGGL(ba_product_cameras_kernel, dim3((unsigned)n_cams), dim3(kBaProductThreads), 0, (hipStream_t)stream, d, l, cam_offsets,
+                     cam_obs, obs_point, U, fixed, p, workspace_s, out_q);
   return vc::check_launch();
 }
 

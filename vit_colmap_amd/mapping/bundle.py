@@ -11,6 +11,9 @@ distortion of SIMPLE_RADIAL (k1) and RADIAL (k1, k2) cameras from the values the
 specification: tests/util_bundle_radial.py): the same loop on the _radial entry points, six unknowns per group in the border.
 With `known_distortion` the grown model was solved on undistorted keypoints; the adjustment then takes the raw
 observations and the known (k1, k2) of every camera as `cam_dist`, held unless refine_distortion frees them.
+With `solver` "pcg" ("The solver" in §4.2k; specification: tests/util_bundle_pcg.py) the reduced system is not formed: it is
+solved by preconditioned conjugate gradients on vc_ba_camera_blocks and vc_ba_schur_product, for any number of cameras, poses
+and points only.
 The same adjustment after every growth round, with the tracks re-evaluated, is mapping/rounds.py (§4.2m).
 Still missing on the way to a mapper: local adjustment, merging of points; among the
 intrinsics OPENCV's tangential terms.
@@ -20,7 +23,8 @@ Where the work runs
           (one workgroup per camera: the reduced system S, g) and vc_ba_step (back-substitution, the trig-free pose update)
   torch   the solve of S dc = -g (with a border: of the bordered system) in float64 on the device (cholesky_ex +
           cholesky_solve) and the loop's scalars; the accept / reject decision is the only host read of an iteration: one
-          number, the candidate's cost (NaN where the system did not factor)
+          number, the candidate's cost (NaN where the system did not factor); under solver "pcg" the vector updates and dot
+          products of conjugate gradients, and one more host read per product: |r|^2 for the stopping test
   host    Python / numpy: the model's arrays, the camera-major index, the gauge, the rescale, the filter
 """
 import copy
@@ -43,6 +47,9 @@ BA_MAX_ITERATIONS = 25               # linearisations
 BA_REL_DECREASE = 1e-8
 HELD_ALL = 63                        # bits 0-2: the rotation, bits 3-5: the translation
 LOSSES = {"trivial": 0, "huber": 1, "soft_l1": 2}      # VC_BA_LOSS_* (include/vitcolmap_hip.h)
+SOLVERS = ("dense", "pcg")           # how S dc = -g is solved ("The solver" in §4.2k)
+PCG_REL_TOL = 1e-6                   # |r| <= PCG_REL_TOL |r_0| ends a solve
+PCG_MAX_ITERATIONS = 500             # [recalled: Ceres' default max_linear_solver_iterations]
 MIN_TRI_ANGLE_TAN2 = float(np.tan(FILTER_MIN_TRI_ANGLE) ** 2)
 
 
@@ -99,8 +106,72 @@ def check_loss(loss, loss_scale):
     return LOSSES[loss], scale
 
 
+def check_solver(solver):
+    """ValueError, naming the options, for a solver that is none of SOLVERS."""
+    if solver not in SOLVERS:
+        raise ValueError(f"bundle_adjust: unknown solver {solver!r}, expected one of {', '.join(SOLVERS)}")
+
+
+class _Pcg:
+    """S dc = -g by preconditioned conjugate gradients without S ("The solver" in §4.2k): vc_ba_camera_blocks once per solve,
+    vc_ba_schur_product (two launches) once per iteration, the vector updates and dot products in torch float64 on the device,
+    M^-1 r a batched 6x6 product.  One host read per iteration: |r|^2, NaN where p'q is not finite and positive."""
+
+    def __init__(self, torch, lib, n_cams, n_points, device, tol, max_iterations):
+        f64 = dict(dtype=torch.float64, device=device)
+        self.torch, self.lib, self.n_cams, self.tol, self.max_iterations = torch, lib, n_cams, float(tol), int(max_iterations)
+        self.U, self.D, self.Minv = (torch.zeros((n_cams, 36), **f64) for _ in range(3))
+        self.g, self.q = torch.zeros(6 * n_cams, **f64), torch.zeros(6 * n_cams, **f64)
+        self.fixed = torch.zeros(6 * n_cams, dtype=torch.uint8, device=device)
+        self.s = torch.zeros((max(n_points, 1), 3), **f64)
+        self.nan = torch.full((), float("nan"), **f64)
+
+    def solve(self, launch_blocks, launch_product):
+        """launch_blocks(self) and launch_product(self, p) call the two entry points on the current linearisation -> (x, a 0-dim
+        bool tensor: the solve ended well, the number of products)."""
+        torch = self.torch
+        launch_blocks(self)
+        free = self.fixed == 0
+        Minv = self.Minv.view(-1, 6, 6)
+
+        def precondition(r):
+            return (Minv * r.view(-1, 1, 6)).sum(dim=2).reshape(-1)
+
+        x = torch.zeros_like(self.g)
+        r = torch.where(free, -self.g, torch.zeros_like(self.g))
+        rr0 = float(torch.dot(r, r).item())
+        if rr0 == 0.0:
+            return x, torch.ones((), dtype=torch.bool, device=x.device), 0
+        if not np.isfinite(rr0):
+            return x, torch.zeros((), dtype=torch.bool, device=x.device), 0
+        bound = self.tol * float(np.sqrt(rr0))
+        z = precondition(r)
+        p, rz = z.clone(), torch.dot(r, z)
+        k, well = 0, True
+        while k < self.max_iterations:
+            k += 1
+            launch_product(self, p.contiguous())
+            pq = torch.dot(p, self.q)
+            alpha = rz / pq
+            x = x + alpha * p
+            r = r - alpha * self.q
+            rr = float(torch.where(torch.isfinite(pq) & (pq > 0), torch.dot(r, r), self.nan).item())    # the iteration's host read
+            if not np.isfinite(rr):
+                well = False
+                break
+            if float(np.sqrt(rr)) <= bound:
+                break
+            z = precondition(r)
+            rz_new = torch.dot(r, z)
+            p, rz = z + (rz_new / rz) * p, rz_new
+        # a non-finite x stays non-finite under every later update, so one test here is the rule's test after every update
+        ended_well = torch.isfinite(x).all() & torch.tensor(well, device=x.device)
+        return torch.where(free, x, torch.zeros_like(x)), ended_well, k
+
+
 def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cuda", max_iterations=BA_MAX_ITERATIONS, cam_group=None,
-                  intr_mask=None, loss="trivial", loss_scale=1.0, cam_dist=None):
+                  intr_mask=None, loss="trivial", loss_scale=1.0, cam_dist=None, solver="dense", pcg_tol=PCG_REL_TOL,
+                  pcg_max_iterations=PCG_MAX_ITERATIONS):
     """cams float64 (n_cams, 16) as vc_triangulate_tracks has them, points float64 (n_points, 3), offsets int32 (n_points + 1,),
     obs_cam int32 (total,), obs_xy float64 (total, 2), const_mask uint8 (n_cams,) (bit i: pose parameter i is held), numpy
     -> cams, points (numpy, adjusted) and the report dict(iterations, accepted_steps, initial_cost, final_cost, final_lambda,
@@ -117,7 +188,13 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     loop then runs the _radial entry points, with any loss; bits 5 and 6 of a group's mask hold k1 and k2; without groups every
     slot is in one group whose six intrinsics are all held.  The report gains `cam_dist`, the adjusted (n_cams, 2), and its
     `intrinsics` are (n_groups, 6): (fx, fy, cx, cy, k1, k2).  Raises ValueError above VC_BA_MAX_GROUPS_RADIAL groups.  Without
-    cam_dist exactly the calls and the report described above."""
+    cam_dist exactly the calls and the report described above.
+    solver "dense" or "pcg" ("The solver" in §4.2k).  "dense" is everything above, the ValueError above VC_BA_MAX_CAMS included.
+    "pcg" solves S dc = -g by preconditioned conjugate gradients (block-Jacobi, |r| <= pcg_tol |r_0| or pcg_max_iterations
+    products) on vc_ba_camera_blocks and vc_ba_schur_product: S is not allocated and there is no limit on the cameras; a solve
+    that ends on a p'q that is not finite and positive, or on a non-finite x, is what a system that did not factor is.  The report
+    gains `solver` and `pcg_iterations`, one count per solve.  With cam_group, intr_mask or cam_dist "pcg" raises ValueError:
+    the border needs the dense solver.  Raises ValueError for an unknown solver."""
     import torch
 
     from .. import _lib
@@ -128,7 +205,12 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     obs_xy, const_mask = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2), np.ascontiguousarray(const_mask, np.uint8)
     n_cams, n_points, total = len(cams), len(points), len(obs_cam)
     loss_kind, loss_scale = check_loss(loss, loss_scale)
-    if n_cams > _lib.VC_BA_MAX_CAMS:
+    check_solver(solver)
+    pcg = solver == "pcg"
+    if pcg and (cam_group is not None or intr_mask is not None or cam_dist is not None):
+        raise ValueError("bundle_adjust: solver 'pcg' solves the cameras' system alone; cam_group, intr_mask and cam_dist add a border "
+                         "to it, which needs the dense solver (solver='dense')")
+    if not pcg and n_cams > _lib.VC_BA_MAX_CAMS:
         raise ValueError(f"bundle_adjust: {n_cams} cameras, the reduction kernel holds at most {_lib.VC_BA_MAX_CAMS} (VC_BA_MAX_CAMS)")
     if offsets.shape != (n_points + 1,) or obs_xy.shape != (total, 2) or const_mask.shape != (n_cams,):
         raise ValueError("bundle_adjust needs offsets (n_points + 1,), obs_cam (total,), obs_xy (total, 2), const_mask (n_cams,)")
@@ -150,6 +232,8 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
         border = Border(cams, cam_group, intr_mask, with_loss=loss_kind != 0, cam_dist=cam_dist, loss=(loss_kind, loss_scale))
     report = dict(iterations=0, accepted_steps=0, initial_cost=0.0, final_cost=0.0, final_lambda=BA_LAMBDA0, decisions=[], loss=loss,
                   loss_scale=loss_scale)
+    if pcg:
+        report.update(solver=solver, pcg_iterations=[])
     if n_cams == 0 or n_points == 0:
         return cams.copy(), points.copy(), report if border is None else border.report(report, cams, cam_dist)
     lib = _lib.load()
@@ -165,8 +249,9 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     cur.cams.copy_(on_device(cams)), cur.points.copy_(on_device(points))
     if radial:
         cur.dist.copy_(on_device(cam_dist))
-    S = torch.zeros((6 * n_cams, 6 * n_cams), dtype=torch.float64, device=dev)
-    g = torch.zeros(6 * n_cams, dtype=torch.float64, device=dev)
+    if not pcg:
+        S = torch.zeros((6 * n_cams, 6 * n_cams), dtype=torch.float64, device=dev)
+        g = torch.zeros(6 * n_cams, dtype=torch.float64, device=dev)
     dx = torch.zeros((n_points, 3), dtype=torch.float64, device=dev)
     p, stream = _lib.ptr, _lib.stream_ptr()
     if border is not None:
@@ -189,22 +274,38 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
                                               total, float(lam), p(b.vinv), p(b.gp), p(b.cost), p(b.count), p(b.obs_ok), p(b.obs_lin),
                                               p(b.total_cost), stream), "vc_ba_linearize_points")
 
+    def launch_blocks(s):
+        _lib.check(lib.vc_ba_camera_blocks(n_cams, p(d_mask), n_points, p(d_offsets), p(d_obs_cam), total, p(cam_offsets), p(cam_obs),
+                                           p(obs_point), float(lam), p(cur.vinv), p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(s.U), p(s.D),
+                                           p(s.Minv), p(s.g), p(s.fixed), stream), "vc_ba_camera_blocks")
+
+    def launch_product(s, vector):
+        _lib.check(lib.vc_ba_schur_product(n_cams, n_points, p(d_offsets), p(d_obs_cam), total, p(cam_offsets), p(cam_obs), p(obs_point),
+                                           p(cur.vinv), p(cur.obs_ok), p(cur.obs_lin), p(s.U), p(s.fixed), p(vector), p(s.s), p(s.q), stream),
+                   "vc_ba_schur_product")
+
     lam = BA_LAMBDA0
     linearize(cur, lam)
     cost = initial = float(cur.total_cost.item())
-    iterations, decisions = 1, []
+    iterations, decisions, pcg_counts = 1, [], []
+    solve = _Pcg(torch, lib, n_cams, n_points, dev, pcg_tol, pcg_max_iterations) if pcg else None
     while iterations < max_iterations:
-        _lib.check(lib.vc_ba_reduce_cameras(n_cams, p(d_mask), n_points, p(d_offsets), p(d_obs_cam), total, p(cam_offsets), p(cam_obs),
-                                            p(obs_point), float(lam), p(cur.vinv), p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(S), p(g),
-                                            stream), "vc_ba_reduce_cameras")
-        # the system A x = -rhs and which of its unknowns move: the cameras', or with a border the cameras' and the intrinsics'
-        A, rhs, moves = (S, g, free) if border is None else border.system(cur, lam, S, g, free)
-        L, info = torch.linalg.cholesky_ex(A)
-        x = torch.cholesky_solve(-rhs[:, None], L)[:, 0]
-        factored = (info == 0) & torch.isfinite(x).all()
-        # a parameter that does not move steps by exactly 0; a system that did not factor still takes a (finite, zero) step
-        # through the kernels, whose cost is then replaced by NaN: the decision stays one scalar read
-        x = torch.where(moves & factored, x, torch.zeros_like(x)).contiguous()
+        if pcg:
+            x, factored, products = solve.solve(launch_blocks, launch_product)
+            pcg_counts.append(products)
+            x = torch.where(free & factored, x, torch.zeros_like(x)).contiguous()
+        else:
+            _lib.check(lib.vc_ba_reduce_cameras(n_cams, p(d_mask), n_points, p(d_offsets), p(d_obs_cam), total, p(cam_offsets), p(cam_obs),
+                                                p(obs_point), float(lam), p(cur.vinv), p(cur.gp), p(cur.obs_ok), p(cur.obs_lin), p(S), p(g),
+                                                stream), "vc_ba_reduce_cameras")
+            # the system A x = -rhs and which of its unknowns move: the cameras', or with a border the cameras' and the intrinsics'
+            A, rhs, moves = (S, g, free) if border is None else border.system(cur, lam, S, g, free)
+            L, info = torch.linalg.cholesky_ex(A)
+            x = torch.cholesky_solve(-rhs[:, None], L)[:, 0]
+            factored = (info == 0) & torch.isfinite(x).all()
+            # a parameter that does not move steps by exactly 0; a system that did not factor still takes a (finite, zero) step
+            # through the kernels, whose cost is then replaced by NaN: the decision stays one scalar read
+            x = torch.where(moves & factored, x, torch.zeros_like(x)).contiguous()
         if border is None:
             _lib.check(lib.vc_ba_step(p(cur.cams), n_cams, p(cur.points), n_points, p(d_offsets), p(d_obs_cam), total, p(cur.vinv), p(cur.gp),
                                       p(cur.obs_ok), p(cur.obs_lin), p(x), p(cand.cams), p(cand.points), p(dx), stream), "vc_ba_step")
@@ -231,6 +332,8 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     out_cams = cur.cams.cpu().numpy()
     report = dict(iterations=iterations, accepted_steps=int(sum(decisions)), initial_cost=initial, final_cost=cost, final_lambda=lam,
                   decisions=decisions, loss=loss, loss_scale=loss_scale)
+    if pcg:
+        report.update(solver=solver, pcg_iterations=pcg_counts)
     return out_cams, cur.points.cpu().numpy(), (report if border is None else
                                                 border.report(report, out_cams, cur.dist.cpu().numpy() if radial else None))
 
@@ -245,7 +348,7 @@ def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
 
 def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
                          grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False,
-                         known_distortion=False, undistort_fn=None) -> SparseModel:
+                         known_distortion=False, undistort_fn=None, solver="dense") -> SparseModel:
     """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
     is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
     Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
@@ -271,9 +374,18 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     undistorted keypoints and its `xys` are the raw ones, so the adjustment gets the raw observations and, where a registered
     camera has a non-zero k, cam_dist= the known (k1, k2) of every slot: held without refine_distortion (with refine_focal_length
     alone the groups then carry bits 5 and 6 and the limit is VC_BA_MAX_GROUPS_RADIAL), the starting values with it, as
-    before.  The filter and `error` use the distorted projection.  Without the option exactly the calls described above."""
+    before.  The filter and `error` use the distorted projection.  Without the option exactly the calls described above.
+    `solver` ("The solver" in §4.2k): "dense", exactly the calls described above, or "pcg": bundle_fn is then also given
+    solver="pcg", `stats()["bundle_adjustment"]` carries solver and pcg_iterations, and there is no limit on the registered images.
+    With refine_focal_length, refine_distortion or known_distortion "pcg" raises ValueError: they add a border to the system or
+    take the _radial entry points, which need the dense solver.  Raises ValueError for an unknown solver."""
     bundle_fn = bundle_fn or bundle_adjust
     check_loss(loss, loss_scale)
+    check_solver(solver)
+    if solver != "dense" and (refine_focal_length or refine_distortion or known_distortion):
+        raise ValueError(f"solver {solver!r} adjusts poses and points only: refine_focal_length, refine_distortion and known_distortion go "
+                         "through the border of the system or the _radial entry points, which need the dense solver (out of scope of pcg)")
+    solver_args = {} if solver == "dense" else dict(solver=solver)
     loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=float(loss_scale))
     if grown is None:
         known_args = dict(known_distortion=True, undistort_fn=undistort_fn) if known_distortion else {}
@@ -355,7 +467,7 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
         cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_dist=known_dist, **loss_args)
         dist = known_dist
     else:
-        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, **loss_args)
+        cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, **loss_args, **solver_args)
     cams, points = np.array(cams, np.float64), np.array(points, np.float64)
 
     # every t and X rescaled so that the pair's baseline is 1 again (§4.2i)

@@ -24,7 +24,7 @@ import numpy as np
 
 from .. import _lib
 from ..matching.essential import rot_to_quat
-from .bundle import HELD_ALL, build_adjusted_model, bundle_adjust, check_loss
+from .bundle import HELD_ALL, build_adjusted_model, bundle_adjust, check_loss, check_solver
 from .grow import _grow
 from .seed import SparseModel
 
@@ -45,10 +45,12 @@ def _camera_row(R, t, K):
     return np.concatenate([R.reshape(9), t, [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]])
 
 
-def _round_steps(g, bundle_fn, refine_fn, loss_args, reports):
-    """The A-step and the E-step on the growth's state `g` (mapping/grow.py, `_grow`), which they change in place."""
+def _round_steps(g, bundle_fn, refine_fn, adjust_args, reports):
+    """The A-step and the E-step on the growth's state `g` (mapping/grow.py, `_grow`), which they change in place.  `adjust_args`:
+    what the A-step hands to bundle_fn beside the arrays: loss= and loss_scale= where the loss is not "trivial", solver= where it is
+    not "dense"; the dense solver's limit on the cameras holds only under it."""
     reg, pids = sorted(g.poses), sorted(g.xyz)
-    if len(reg) > _lib.VC_BA_MAX_CAMS:
+    if adjust_args.get("solver", "dense") == "dense" and len(reg) > _lib.VC_BA_MAX_CAMS:
         raise ValueError(f"adjust_rounds: {len(reg)} registered images, the reduction kernel of the adjustment holds at most "
                          f"{_lib.VC_BA_MAX_CAMS} (VC_BA_MAX_CAMS)")
     # A-step
@@ -62,7 +64,7 @@ def _round_steps(g, bundle_fn, refine_fn, loss_args, reports):
     mask[a] = HELD_ALL
     mask[b] = 1 << (3 + int(np.argmax(np.abs(cams[b, 9:12]))))
     points = np.array([g.xyz[p] for p in pids], np.float64).reshape(-1, 3)
-    cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, g.device, **loss_args)
+    cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, g.device, **adjust_args)
     cams, points = np.array(cams, np.float64), np.array(points, np.float64)
     for i in reg:
         R = cams[rslot[i], :9].reshape(3, 3).copy()
@@ -99,32 +101,38 @@ def _round_steps(g, bundle_fn, refine_fn, loss_args, reports):
 
 
 def build_mapped_rounds(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
-                        refine_fn=None, loss="trivial", loss_scale=1.0, known_distortion=False, undistort_fn=None):
+                        refine_fn=None, loss="trivial", loss_scale=1.0, known_distortion=False, undistort_fn=None, solver="dense"):
     """The model as the rounds leave it, before the tail -> (SparseModel, the round reports).  Arguments as build_mapped_model."""
     check_loss(loss, loss_scale)
-    loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=float(loss_scale))
+    check_solver(solver)
+    adjust_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=float(loss_scale))
+    if solver != "dense":
+        adjust_args["solver"] = solver
     bundle_fn, refine_fn, reports = bundle_fn or bundle_adjust, refine_fn or _gpu_refine, []
     model = _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, known_distortion, undistort_fn,
-                  round_fn=lambda g: _round_steps(g, bundle_fn, refine_fn, loss_args, reports))
+                  round_fn=lambda g: _round_steps(g, bundle_fn, refine_fn, adjust_args, reports))
     return model, reports
 
 
 def build_mapped_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
                        refine_fn=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False,
-                       known_distortion=False, undistort_fn=None) -> SparseModel:
+                       known_distortion=False, undistort_fn=None, solver="dense") -> SparseModel:
     """Read a matched database -> the seed model grown by rounds, adjusted and its tracks re-evaluated after every round that
     added a point or an image (the module's header), then build_adjusted_model's tail on that model with every option given:
     one more adjustment (with refine_focal_length / refine_distortion the one that refines them), the rescale to a unit
     baseline, the filter.  The result's `round_adjustments` are the rounds' reports: dict(iterations, accepted_steps,
     initial_cost, final_cost, decisions, added_observations, dropped_observations (both over the points that stay),
     dropped_points) each.  Raises the seed model's and build_adjusted_model's ValueErrors unchanged, and ValueError above
-    VC_BA_MAX_CAMS registered images.
+    VC_BA_MAX_CAMS registered images under the dense solver.  `solver` "pcg" ("The solver" in §4.2k): every adjustment, the
+    rounds' and the tail's, solves its system by conjugate gradients and has no such limit; bundle_fn is given solver= only then.
     `refine_fn(obs_xy, obs_cam, offsets, cams, init_xyz, device) -> (xyz, mask, count, error)` on numpy arrays replaces the
     launch of vc_refine_tracks (tests); `bundle_fn` as in build_adjusted_model, in the rounds given loss= and loss_scale= where
     the loss is not "trivial" and nothing else, so the cap is BA_MAX_ITERATIONS; the other seams as in build_sparse_model."""
     model, reports = build_mapped_rounds(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, bundle_fn, refine_fn,
-                                         loss, loss_scale, known_distortion, undistort_fn)
+                                         loss, loss_scale, known_distortion, undistort_fn, solver)
+    solver_args = {} if solver == "dense" else dict(solver=solver)
     mapped = build_adjusted_model(database_path, device, bundle_fn=bundle_fn, grown=model, refine_focal_length=refine_focal_length,
-                                  loss=loss, loss_scale=loss_scale, refine_distortion=refine_distortion, known_distortion=known_distortion)
+                                  loss=loss, loss_scale=loss_scale, refine_distortion=refine_distortion, known_distortion=known_distortion,
+                                  **solver_args)
     mapped.round_adjustments = reports
     return mapped

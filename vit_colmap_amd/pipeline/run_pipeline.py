@@ -19,6 +19,7 @@ from ..utils.config import CAMERA_PARAM_NAMES, Config, parse_camera_params
 logger = logging.getLogger(__name__)
 
 MATCHER_TYPES = ("exhaustive", "retrieval")   # MatchingConfig.matcher_type / --matcher
+BA_SOLVERS = ("dense", "pcg")                 # ReconstructionConfig.ba_solver / --ba-solver (mapping.bundle.SOLVERS)
 BA_LOSSES = ("trivial", "huber", "soft_l1")   # ReconstructionConfig.ba_loss / --ba-loss (mapping.bundle.LOSSES)
 
 
@@ -97,6 +98,16 @@ class Pipeline:
         known_distortion = bool(getattr(self.config.camera, "known_distortion", False))
         if known_distortion and not self.config.camera.prior_focal_length:   # it is what makes the intrinsics trusted (§4.2l)
             raise ValueError("known_distortion needs camera.prior_focal_length (--prior-focal-length)")
+        ba_solver = str(getattr(self.config.reconstruction, "ba_solver", "dense"))
+        if ba_solver not in BA_SOLVERS:
+            raise ValueError(f"unknown ba_solver {ba_solver!r}: expected one of {', '.join(BA_SOLVERS)}")
+        if ba_solver != "dense" and not bundle_adjustment:      # it is how that adjustment solves its system (§4.2k, "The solver")
+            raise ValueError("ba_solver needs reconstruction.bundle_adjustment (--bundle-adjustment)")
+        if ba_solver != "dense" and (refine_focal_length or refine_distortion or known_distortion):
+            raise ValueError(f"ba_solver {ba_solver!r} adjusts poses and points only: refine_focal_length, refine_distortion and "
+                             "known_distortion go through the border of the system or the _radial entry points, which need the dense "
+                             "solver (out of scope of pcg)")
+        solver_args = {} if ba_solver == "dense" else dict(solver=ba_solver)   # passed on only where it is not the default
         if camera_params is not None and camera_model in CAMERA_PARAM_NAMES:   # the count, before any database is created
             camera_params = parse_camera_params(camera_params, camera_model)
         known_args = dict(known_distortion=True) if known_distortion else {}
@@ -166,7 +177,7 @@ class Pipeline:
                                          **loss_args, **known_args, **rounds_args)
             else:
                 self._write_sparse_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), adjust=bundle_adjustment, **loss_args,
-                                         **known_args, **rounds_args)
+                                         **known_args, **rounds_args, **solver_args)
 
         reconstructions = None
         if self.config.do_reconstruction:
@@ -216,7 +227,7 @@ class Pipeline:
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
     def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0,
-                            refine_distortion=False, known_distortion=False, adjust_rounds=False):
+                            refine_distortion=False, known_distortion=False, adjust_rounds=False, solver="dense"):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
         `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
         `refine_focal_length`: that adjustment also refines the cameras' focal lengths; `loss`, `loss_scale`: its loss, passed on
@@ -224,7 +235,8 @@ class Pipeline:
         `known_distortion`: both models are built on undistorted keypoints (§4.2l), passed on only where it is on;
         `adjust_rounds` (with `adjust`): also output_dir/sparse/mapped and `last_stats["mapped_model"]`, the model grown with an
         adjustment and a re-evaluation of its tracks after every round (§4.2m), under the same options; the other two models are
-        built and written as without it."""
+        built and written as without it.  `solver`: how the adjustments solve their system ("The solver" in §4.2k), passed on
+        only where it is not "dense"."""
         from ..mapping.grow import build_sparse_model
 
         known_args = dict(known_distortion=True) if known_distortion else {}
@@ -241,13 +253,14 @@ class Pipeline:
             from ..mapping.bundle import build_adjusted_model
 
             loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=loss_scale)
+            solver_args = {} if solver == "dense" else dict(solver=solver)
             if refine_distortion:
                 adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=refine_focal_length,
                                                 refine_distortion=True, **loss_args, **known_args)
             elif refine_focal_length:
                 adjusted = build_adjusted_model(str(db_path), device=device, grown=model, refine_focal_length=True, **loss_args, **known_args)
             else:
-                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, **loss_args, **known_args)
+                adjusted = build_adjusted_model(str(db_path), device=device, grown=model, **loss_args, **known_args, **solver_args)
             adjusted.write_text(str(Path(output_dir) / "sparse" / "adjusted"))
             self.last_stats = dict(self.last_stats, bundle_adjustment=adjusted.stats())
             logger.info("Adjusted model: %d images, %d points, cost %.6g -> %.6g", len(adjusted.images), len(adjusted.points3D),
@@ -257,7 +270,7 @@ class Pipeline:
 
                 refine_args = dict(refine_focal_length=refine_focal_length, refine_distortion=refine_distortion)
                 mapped = build_mapped_model(str(db_path), device=device, **{k: v for k, v in refine_args.items() if v}, **loss_args,
-                                            **known_args)
+                                            **known_args, **solver_args)
                 mapped.write_text(str(Path(output_dir) / "sparse" / "mapped"))
                 self.last_stats = dict(self.last_stats, mapped_model=mapped.stats())
                 logger.info("Mapped model: %d images, %d points, %d round adjustments", len(mapped.images), len(mapped.points3D),
@@ -330,6 +343,10 @@ def main() -> None:
                          "of pixels off their point from setting the poses")
     ap.add_argument("--ba-loss-scale", dest="ba_loss_scale", type=float, default=1.0, metavar="PX",
                     help="the residual in pixels at which --ba-loss leaves the square")
+    ap.add_argument("--ba-solver", dest="ba_solver", choices=list(BA_SOLVERS), default="dense",
+                    help="with --bundle-adjustment: dense factors the reduced camera system (at most 512 registered images); pcg solves "
+                         "it by preconditioned conjugate gradients without forming it and has no such limit (poses and points only: "
+                         "not with --refine-focal-length, --refine-distortion or --known-distortion)")
     ap.add_argument("--matcher", choices=list(MATCHER_TYPES), default="exhaustive",
                     help="exhaustive: every image pair; retrieval: each image against its --num-neighbors nearest images")
     ap.add_argument("--num-neighbors", dest="num_neighbors", type=int, default=20,

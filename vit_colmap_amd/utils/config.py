@@ -136,6 +136,7 @@ class ReconstructionConfig:
     ba_loss: str = "trivial"     # with bundle_adjustment: the loss of the adjustment, "trivial", "huber" or "soft_l1" (§4.2k, "The loss")
     ba_loss_scale: float = 1.0   # px: the residual at which the loss leaves the square
     refine_distortion: bool = False   # with bundle_adjustment: it also refines k of SIMPLE_RADIAL, k1 and k2 of RADIAL cameras (§4.2k)
+    ba_solver: str = "dense"     # with bundle_adjustment: how the reduced camera system is solved, "dense" (Cholesky of S, at most VC_BA_MAX_CAMS images) or "pcg" (conjugate gradients without S, no limit; §4.2k, "The solver")
     adjust_rounds: bool = False   # with bundle_adjustment: write output_dir/sparse/mapped, grown with an adjustment and a re-evaluation of the tracks per round (§4.2m)
 
     def to_mapper_options(self):
@@ -214,6 +215,8 @@ class Config:
             config.reconstruction.ba_loss = args.ba_loss
         if getattr(args, "ba_loss_scale", None) is not None:
             config.reconstruction.ba_loss_scale = float(args.ba_loss_scale)
+        if getattr(args, "ba_solver", None):
+            config.reconstruction.ba_solver = args.ba_solver
         if getattr(args, "matcher", None):
             config.matching.matcher_type = args.matcher
         if getattr(args, "num_neighbors", None) is not None:
