@@ -312,6 +312,47 @@ int vc_refine_tracks(const double* obs_xy, const int32_t* obs_cam, const int32_t
                      int32_t* out_count, double* out_error, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Track splitting: a component of the match graph that holds more than one scene point (two of
+ * its nodes lie in one image) is split into up to max_points points, every component of a call in one launch, one component
+ * per lane.  Arrays, thresholds, launch shape and arithmetic (usable, midpoint, parallax test, inlier test, refit) are
+ * vc_triangulate_tracks'.  Specification: tests/util_split.py (`split_component`).  This build's own published rule: parity
+ * with COLMAP's recursive triangulation is unpinned.
+ *   obs_xy, obs_cam, cams, n_cams, max_error_px, min_tri_angle_tan2   as vc_triangulate_tracks has them, a row per node
+ *   offsets     [n_comps + 1] int32: component t owns rows offsets[t] .. offsets[t+1]) of the per-node arrays.  The caller
+ *               sorts the nodes of a component by (image, keypoint), so that the nodes of one image are adjacent
+ *   seeds       [n_comps] int32, read as 32 unsigned bits
+ *   max_points  in [1, VC_SPLIT_MAX_POINTS]: the slots of every component
+ *   node_point  [total] int32, in and out: -1 a free node; k in [0, max_points) a node of slot k; any other value a node that
+ *               is never free, belongs to no slot and is never written
+ *   points_xyz  [n_comps][max_points][3] float64, in and out: a slot is occupied iff its three numbers are finite
+ *   out_count   [n_comps][max_points] int32: the nodes that carry each slot after the call
+ *   out_new     [n_comps][max_points] uint8: 1 for a slot this call created
+ *   out_error   [n_comps][max_points] float64: the mean pixel error of the nodes of a slot this call created, NaN otherwise
+ * The rule for a component of n nodes:
+ *   run         a maximal stretch of adjacent nodes with equal obs_cam
+ *   selection   under a point X, for slot k: in every run that holds no node of slot k, among its free usable nodes that
+ *               pass the inlier test at X the one with the smallest sq = (..)^2 + (..)^2 of that test (one camera row and
+ *               hence one Xc_z per run: the smallest pixel error), the lowest index on ties.  With runs of length 1 it is
+ *               the inlier set
+ *   attach      every slot k occupied on input, in ascending order: the nodes selected under X_k take label k; X_k stays
+ *   peel        every slot k empty on input, in ascending order: hypotheses are the pairs of vc_triangulate_tracks over all n
+ *               nodes under the seed seed + k * 0x9E3779B9 (32-bit), tried only if p and q are free, usable and of
+ *               different obs_cam; one counts iff its midpoint is valid and p and q are in the selection under it, its score
+ *               is the size of that selection, the largest wins, the lowest index on ties; the refit of
+ *               vc_triangulate_tracks over the winner's selection, taken iff finite with no smaller a selection; accepted
+ *               iff at least two nodes are selected, some pair of which passes the parallax test at the final X.  Accepted:
+ *               the selected nodes take label k, points_xyz[k] = X.  Rejected: the slot stays empty and no later slot is tried
+ * n_comps == 0: VC_OK whatever the pointers are.  A null pointer, a negative size, a max_points outside [1, 4], a threshold
+ * that is negative or not finite: VC_ERR_INVALID_ARG without a launch.  A negative or descending pair of offsets rejects the
+ * component: nothing of it is read, its labels and points stay, its outputs are 0 / 0 / NaN.  Offsets past the arrays are the
+ * caller's to exclude, as for vc_triangulate_tracks: the call is not told their length.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_SPLIT_MAX_POINTS 4
+int vc_split_tracks(const double* obs_xy, const int32_t* obs_cam, const int32_t* offsets, int n_comps, const double* cams, int n_cams,
+                    const int32_t* seeds, int max_points, double max_error_px, double min_tri_angle_tan2, int32_t* node_point,
+                    double* points_xyz, int32_t* out_count, uint8_t* out_new, double* out_error, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint undistortion: the pixel an ideal pinhole camera with the same K would see in place of
  * a raw keypoint of a camera with known distortion, one keypoint per lane, float64 in single operations in the written order
  * (left to right, the usual precedence; no fused multiply-add, no library call).  Specification: tests/util_undistort.py.

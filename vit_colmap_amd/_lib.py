@@ -63,6 +63,8 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "vc_refine_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vc_split_tracks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_double, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vc_undistort_points": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vc_ba_linearize_points": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -348,7 +348,7 @@ def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
 
 def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
                          grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False,
-                         known_distortion=False, undistort_fn=None, solver="dense") -> SparseModel:
+                         known_distortion=False, undistort_fn=None, solver="dense", split_tracks=False, split_fn=None) -> SparseModel:
     """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
     is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
     Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
@@ -378,7 +378,9 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     `solver` ("The solver" in §4.2k): "dense", exactly the calls described above, or "pcg": bundle_fn is then also given
     solver="pcg", `stats()["bundle_adjustment"]` carries solver and pcg_iterations, and there is no limit on the registered images.
     With refine_focal_length, refine_distortion or known_distortion "pcg" raises ValueError: they add a border to the system or
-    take the _radial entry points, which need the dense solver.  Raises ValueError for an unknown solver."""
+    take the _radial entry points, which need the dense solver.  Raises ValueError for an unknown solver.
+    `split_tracks`, `split_fn` (§4.2n) as in build_sparse_model, which is given them only where the flag is on and `grown` is not
+    given; the model keeps the grown model's split_components and split_points either way."""
     bundle_fn = bundle_fn or bundle_adjust
     check_loss(loss, loss_scale)
     check_solver(solver)
@@ -389,6 +391,8 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     loss_args = {} if loss == "trivial" else dict(loss=loss, loss_scale=float(loss_scale))
     if grown is None:
         known_args = dict(known_distortion=True, undistort_fn=undistort_fn) if known_distortion else {}
+        if split_tracks:
+            known_args.update(split_tracks=True, split_fn=split_fn)
         grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, **known_args)
     ids, pids = sorted(grown.images), sorted(grown.points3D)
     slot = {i: s for s, i in enumerate(ids)}
@@ -480,6 +484,7 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
                         bundle_adjustment={k: v for k, v in report.items()
                                            if k not in ("decisions", "intrinsics", "loss", "loss_scale", "cam_dist")})
     model.bundle_adjustment.update(loss_args)
+    model.split_components, model.split_points = grown.split_components, grown.split_points
     model.cameras = copy.deepcopy(grown.cameras)
     if refine_distortion:
         # the cameras carry the refined k: params[3] of SIMPLE_RADIAL, params[3:5] of RADIAL; the filter and `error` use it

@@ -2,8 +2,8 @@
 round that added a point or an image, then the tail of mapping/bundle.py.  Past 20 or so views one adjustment at the end of
 the growth starts too far from the minimum; one per round keeps every start close.  Specification: tests/util_rounds.py
 (`map_model`).  This build's own published rule; parity with COLMAP's mapper is unpinned.  Still missing on the way to a
-mapper: no local adjustment, no merging of points, no splitting of inconsistent components, no intrinsics refined inside the
-rounds.
+mapper: no local adjustment, no merging of points, no intrinsics refined inside the rounds; inconsistent components are split
+only under `split_tracks` (§4.2n), and their points take no part in registration.
 
   A-step  one bundle_adjust (mapping/bundle.py) over every registered pose and every point on the current tracks, the gauge of
           build_adjusted_model on the initial pair, BA_MAX_ITERATIONS, poses and points only, under the configured loss, on the
@@ -101,7 +101,8 @@ def _round_steps(g, bundle_fn, refine_fn, adjust_args, reports):
 
 
 def build_mapped_rounds(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
-                        refine_fn=None, loss="trivial", loss_scale=1.0, known_distortion=False, undistort_fn=None, solver="dense"):
+                        refine_fn=None, loss="trivial", loss_scale=1.0, known_distortion=False, undistort_fn=None, solver="dense",
+                        split_tracks=False, split_fn=None):
     """The model as the rounds leave it, before the tail -> (SparseModel, the round reports).  Arguments as build_mapped_model."""
     check_loss(loss, loss_scale)
     check_solver(solver)
@@ -109,14 +110,15 @@ def build_mapped_rounds(database_path, device="cuda", two_view_pose_fn=None, est
     if solver != "dense":
         adjust_args["solver"] = solver
     bundle_fn, refine_fn, reports = bundle_fn or bundle_adjust, refine_fn or _gpu_refine, []
+    split_args = dict(split_tracks=True, split_fn=split_fn) if split_tracks else {}
     model = _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, known_distortion, undistort_fn,
-                  round_fn=lambda g: _round_steps(g, bundle_fn, refine_fn, adjust_args, reports))
+                  round_fn=lambda g: _round_steps(g, bundle_fn, refine_fn, adjust_args, reports), **split_args)
     return model, reports
 
 
 def build_mapped_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
                        refine_fn=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False,
-                       known_distortion=False, undistort_fn=None, solver="dense") -> SparseModel:
+                       known_distortion=False, undistort_fn=None, solver="dense", split_tracks=False, split_fn=None) -> SparseModel:
     """Read a matched database -> the seed model grown by rounds, adjusted and its tracks re-evaluated after every round that
     added a point or an image (the module's header), then build_adjusted_model's tail on that model with every option given:
     one more adjustment (with refine_focal_length / refine_distortion the one that refines them), the rescale to a unit
@@ -127,9 +129,12 @@ def build_mapped_model(database_path, device="cuda", two_view_pose_fn=None, esti
     rounds' and the tail's, solves its system by conjugate gradients and has no such limit; bundle_fn is given solver= only then.
     `refine_fn(obs_xy, obs_cam, offsets, cams, init_xyz, device) -> (xyz, mask, count, error)` on numpy arrays replaces the
     launch of vc_refine_tracks (tests); `bundle_fn` as in build_adjusted_model, in the rounds given loss= and loss_scale= where
-    the loss is not "trivial" and nothing else, so the cap is BA_MAX_ITERATIONS; the other seams as in build_sparse_model."""
+    the loss is not "trivial" and nothing else, so the cap is BA_MAX_ITERATIONS; the other seams as in build_sparse_model.
+    `split_tracks`, `split_fn` (§4.2n) as in build_sparse_model: the growth splits its inconsistent components; their points are
+    adjusted with the others, the E-step evaluates each over its own track, and one it removes frees its slot for the next round."""
+    split_args = dict(split_tracks=True, split_fn=split_fn) if split_tracks else {}
     model, reports = build_mapped_rounds(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, bundle_fn, refine_fn,
-                                         loss, loss_scale, known_distortion, undistort_fn, solver)
+                                         loss, loss_scale, known_distortion, undistort_fn, solver, **split_args)
     solver_args = {} if solver == "dense" else dict(solver=solver)
     mapped = build_adjusted_model(database_path, device, bundle_fn=bundle_fn, grown=model, refine_focal_length=refine_focal_length,
                                   loss=loss, loss_scale=loss_scale, refine_distortion=refine_distortion, known_distortion=known_distortion,

@@ -43,6 +43,8 @@ class SparseModel:
     rounds: int = None                   # growth rounds that added a point or an image (§4.2j); None: a seed model
     bundle_adjustment: dict = None       # the report of the adjustment (§4.2k); None: a model that was not adjusted
     round_adjustments: list = None       # the reports of the adjustments per growth round (§4.2m); None: there were none
+    split_components: int = None         # inconsistent components that took part in the growth (§4.2n); None: split_tracks was off
+    split_points: list = None            # ids of the points made out of them, whether the model still has them or not; None as above
 
     def mean_track_length(self):
         return float(np.mean([len(p["track"]) for p in self.points3D.values()])) if self.points3D else 0.0
@@ -52,7 +54,9 @@ class SparseModel:
                  num_points3D=len(self.points3D), mean_track_length=self.mean_track_length())
         s = s if self.rounds is None else dict(s, rounds=self.rounds)
         s = s if self.bundle_adjustment is None else dict(s, bundle_adjustment=dict(self.bundle_adjustment))
-        return s if self.round_adjustments is None else dict(s, round_adjustments=[dict(r) for r in self.round_adjustments])
+        s = s if self.round_adjustments is None else dict(s, round_adjustments=[dict(r) for r in self.round_adjustments])
+        return s if self.split_points is None else dict(s, split_components=self.split_components,
+                                                        split_points=sum(pid in self.points3D for pid in self.split_points))
 
     # COLMAP's text layout [recalled: colmap/src/colmap/scene/reconstruction_io.cc]; floats are written with repr, so a model
     # reads back equal

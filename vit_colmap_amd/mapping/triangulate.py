@@ -96,3 +96,46 @@ def refine_tracks(obs_xy, obs_cam, offsets, cams, init_xyz, max_error=MAX_ERROR,
                                     _lib.ptr(init_xyz), float(max_error), float(min_tri_angle_tan2), _lib.ptr(xyz), _lib.ptr(mask),
                                     _lib.ptr(count), _lib.ptr(error), _lib.stream_ptr()), "vc_refine_tracks")
     return xyz, mask.bool(), count, error
+
+
+SPLIT_MAX_POINTS = 4                 # VC_SPLIT_MAX_POINTS of include/vitcolmap_hip.h
+
+
+def split_tracks(obs_xy, obs_cam, offsets, cams, seeds, node_point, points_xyz, max_error=MAX_ERROR,
+                 min_tri_angle_tan2=MIN_TRI_ANGLE_TAN2):
+    """The components of the match graph that hold more than one scene point, split into up to max_points points each
+    (DESIGN.md §4.2n), one launch of vc_split_tracks, whose header states the rule: obs_xy, obs_cam, offsets (C + 1,), cams and
+    seeds (C,) as triangulate_tracks has them, a row per node, the nodes of a component sorted by (image, keypoint); node_point
+    int32 (total,) (-1: free, k: of slot k) and points_xyz float64 (C, max_points, 3) (a NaN row: an empty slot), max_points in
+    [1, SPLIT_MAX_POINTS].  -> node_point, points_xyz (new tensors, the inputs stay), count int32, new bool and error float64
+    (C, max_points).  Specification: tests/util_split.py (`split_tracks`)."""
+    if not (obs_xy.is_cuda and obs_xy.dtype == torch.float64 and cams.dtype == torch.float64 and points_xyz.dtype == torch.float64
+            and obs_cam.dtype == torch.int32 and offsets.dtype == torch.int32 and seeds.dtype == torch.int32
+            and node_point.dtype == torch.int32):
+        raise ValueError("split_tracks needs float64 observations, cameras and points and int32 slots / offsets / seeds / labels on the GPU")
+    dev = obs_xy.device
+    if any(t.device != dev for t in (obs_cam, offsets, cams, seeds, node_point, points_xyz)):
+        raise ValueError("split_tracks needs every tensor on the same GPU")
+    C, total = int(seeds.shape[0]), int(obs_cam.shape[0])
+    if (offsets.shape != (C + 1,) or obs_xy.shape != (total, 2) or cams.dim() != 2 or cams.shape[1] != 16 or node_point.shape != (total,)
+            or points_xyz.dim() != 3 or points_xyz.shape[0] != C or points_xyz.shape[2] != 3
+            or not 1 <= points_xyz.shape[1] <= SPLIT_MAX_POINTS):
+        raise ValueError("split_tracks needs obs_xy (total, 2), obs_cam and node_point (total,), offsets (C + 1,), cams (n_cams, 16), "
+                         f"seeds (C,), points_xyz (C, 1 to {SPLIT_MAX_POINTS}, 3)")
+    max_points = int(points_xyz.shape[1])
+    node_point, points_xyz = node_point.clone().contiguous(), points_xyz.clone().contiguous()
+    count = torch.zeros((C, max_points), dtype=torch.int32, device=dev)
+    new = torch.zeros((C, max_points), dtype=torch.uint8, device=dev)
+    error = torch.full((C, max_points), float("nan"), dtype=torch.float64, device=dev)
+    if C == 0:
+        return node_point, points_xyz, count, new.bool(), error
+    off64 = offsets.to(torch.int64)
+    if int(off64[0]) != 0 or int(off64[-1]) != total or bool((off64[1:] < off64[:-1]).any()):
+        raise ValueError("split_tracks needs offsets that ascend from 0 to the number of nodes")
+    lib = _lib.load()
+    obs_xy, obs_cam, offsets, cams, seeds = (t.contiguous() for t in (obs_xy, obs_cam, offsets, cams, seeds))
+    _lib.check(lib.vc_split_tracks(_lib.ptr(obs_xy), _lib.ptr(obs_cam), _lib.ptr(offsets), C, _lib.ptr(cams), int(cams.shape[0]),
+                                   _lib.ptr(seeds), max_points, float(max_error), float(min_tri_angle_tan2), _lib.ptr(node_point),
+                                   _lib.ptr(points_xyz), _lib.ptr(count), _lib.ptr(new), _lib.ptr(error), _lib.stream_ptr()),
+               "vc_split_tracks")
+    return node_point, points_xyz, count, new.bool(), error

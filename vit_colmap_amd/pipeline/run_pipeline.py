@@ -83,6 +83,9 @@ class Pipeline:
         refine_distortion = bool(getattr(self.config.reconstruction, "refine_distortion", False))
         if refine_distortion and not bundle_adjustment:         # k1 (and k2) are further unknowns of that adjustment (§4.2k)
             raise ValueError("refine_distortion needs reconstruction.bundle_adjustment (--bundle-adjustment)")
+        split_tracks = bool(getattr(self.config.reconstruction, "split_tracks", False))
+        if split_tracks and not sparse_model:                   # it is a step of that model's growth (§4.2n)
+            raise ValueError("split_tracks needs reconstruction.sparse_model (--sparse-model)")
         adjust_rounds = bool(getattr(self.config.reconstruction, "adjust_rounds", False))
         if adjust_rounds and not bundle_adjustment:             # it is that adjustment after every growth round (§4.2m)
             raise ValueError("adjust_rounds needs reconstruction.bundle_adjustment (--bundle-adjustment)")
@@ -112,6 +115,8 @@ class Pipeline:
             camera_params = parse_camera_params(camera_params, camera_model)
         known_args = dict(known_distortion=True) if known_distortion else {}
         rounds_args = dict(adjust_rounds=True) if adjust_rounds else {}   # passed on only where it is on, as known_distortion is
+        if split_tracks:                                        # likewise; it goes wherever the growth runs
+            rounds_args["split_tracks"] = True
         for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
             if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
                 continue
@@ -227,7 +232,7 @@ class Pipeline:
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
     def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0,
-                            refine_distortion=False, known_distortion=False, adjust_rounds=False, solver="dense"):
+                            refine_distortion=False, known_distortion=False, adjust_rounds=False, solver="dense", split_tracks=False):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
         `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
         `refine_focal_length`: that adjustment also refines the cameras' focal lengths; `loss`, `loss_scale`: its loss, passed on
@@ -236,12 +241,14 @@ class Pipeline:
         `adjust_rounds` (with `adjust`): also output_dir/sparse/mapped and `last_stats["mapped_model"]`, the model grown with an
         adjustment and a re-evaluation of its tracks after every round (§4.2m), under the same options; the other two models are
         built and written as without it.  `solver`: how the adjustments solve their system ("The solver" in §4.2k), passed on
-        only where it is not "dense"."""
+        only where it is not "dense".  `split_tracks`: the growth of the grown and of the mapped model splits its inconsistent
+        components (§4.2n), passed on only where it is on; the adjusted model is the grown one adjusted, so it has their points too."""
         from ..mapping.grow import build_sparse_model
 
         known_args = dict(known_distortion=True) if known_distortion else {}
+        split_args = dict(split_tracks=True) if split_tracks else {}
         try:
-            model = build_sparse_model(str(db_path), device=device, **known_args)
+            model = build_sparse_model(str(db_path), device=device, **known_args, **split_args)
         except ValueError as e:
             logger.warning("no sparse model written: %s", e)
             return
@@ -270,7 +277,7 @@ class Pipeline:
 
                 refine_args = dict(refine_focal_length=refine_focal_length, refine_distortion=refine_distortion)
                 mapped = build_mapped_model(str(db_path), device=device, **{k: v for k, v in refine_args.items() if v}, **loss_args,
-                                            **known_args, **solver_args)
+                                            **known_args, **solver_args, **split_args)
                 mapped.write_text(str(Path(output_dir) / "sparse" / "mapped"))
                 self.last_stats = dict(self.last_stats, mapped_model=mapped.stats())
                 logger.info("Mapped model: %d images, %d points, %d round adjustments", len(mapped.images), len(mapped.points3D),
@@ -326,6 +333,9 @@ def main() -> None:
     ap.add_argument("--sparse-model", dest="sparse_model", action="store_true",
                     help="write output/sparse/grown: the seed model grown by rounds of track triangulation and registration "
                          "(needs --prior-focal-length and --relative-pose)")
+    ap.add_argument("--split-tracks", dest="split_tracks", action="store_true",
+                    help="with --sparse-model: a track that a wrong match fused with another (two of its keypoints in one image) is "
+                         "split into up to 4 points instead of being discarded")
     ap.add_argument("--bundle-adjustment", dest="bundle_adjustment", action="store_true",
                     help="with --sparse-model: also write output/sparse/adjusted, the grown model after one global bundle "
                          "adjustment, rescaled to a unit baseline and filtered")

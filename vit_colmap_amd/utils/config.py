@@ -131,6 +131,7 @@ class ReconstructionConfig:
     multiple_models: bool = True
     seed_model: bool = False     # write output_dir/sparse/seed: an initial pair, its points, every other image registered (§4.2i)
     sparse_model: bool = False   # write output_dir/sparse/grown: the seed model grown by rounds of triangulation and registration (§4.2j)
+    split_tracks: bool = False   # with sparse_model: tracks with two keypoints in one image are split into up to 4 points, not discarded (§4.2n)
     bundle_adjustment: bool = False   # with sparse_model: write output_dir/sparse/adjusted, the grown model bundle-adjusted once (§4.2k)
     refine_focal_length: bool = False   # with bundle_adjustment: the adjustment also refines every camera's focal length(s) (§4.2k)
     ba_loss: str = "trivial"     # with bundle_adjustment: the loss of the adjustment, "trivial", "huber" or "soft_l1" (§4.2k, "The loss")
@@ -203,6 +204,8 @@ class Config:
             config.reconstruction.seed_model = True
         if getattr(args, "sparse_model", False):
             config.reconstruction.sparse_model = True
+        if getattr(args, "split_tracks", False):
+            config.reconstruction.split_tracks = True
         if getattr(args, "bundle_adjustment", False):
             config.reconstruction.bundle_adjustment = True
         if getattr(args, "refine_focal_length", False):
