@@ -623,6 +623,69 @@ int vc_ba_step_radial(const double* cams, int n_cams, const double* cam_dist, co
                       double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Bundle adjustment with radial and tangential distortion ("The tangential terms"): COLMAP's OPENCV
+ * camera model, (fx, fy, cx, cy, k1, k2, p1, p2).  The distortion travels beside the 16-number camera row:
+ *   cam_dist    [n_cams][4] float64: (k1, k2, p1, p2) of each camera slot
+ * This build's own published rule; parity with COLMAP / Ceres is unpinned.  Specification: tests/util_bundle_opencv.py.  The
+ * forward model and its symmetric Jacobian are the ones vc_undistort_keypoints inverts, in its order of operations: the radial
+ * term first, the tangential terms added after it.
+ * float64, single operations in the written order (left to right, the usual precedence), sqrt the only library call, no atomics.
+ * With Y, Xc, iu, (xu, xv), (nu; nv), (mu; mv) as in the radial rule above (ba_project on the row at fx = fy = 1):
+ *   rho = xu xu + xv xv,  s = 1 + k1 rho + k2 rho rho,  e = 2 (k1 + 2 k2 rho)
+ *   xd = xu s + 2 p1 xu xv + p2 (rho + 2 xu xu)
+ *   yd = xv s + p1 (rho + 2 xv xv) + 2 p2 xu xv
+ *   d00 = s + xu xu e + 2 p1 xv + 6 p2 xu
+ *   d01 = xu xv e + 2 p1 xu + 2 p2 xv
+ *   d11 = s + xv xv e + 6 p1 xv + 2 p2 xu
+ *   r = (fx xd + cx - u, fy yd + cy - v)
+ *   J_p row u = fx (d00 nu + d01 nv), row v = fy (d01 nu + d11 nv); J_c row u = fx (d00 mu + d01 mv), row v = fy (d01 mu + d11 mv)
+ *   J_theta, eight columns (fx, fy, cx, cy, k1, k2, p1, p2):
+ *     row u = (xd, 0, 1, 0, fx xu rho, (fx xu rho) rho, fx 2 xu xv,          fx (rho + 2 xu xu))
+ *     row v = (0, yd, 0, 1, fy xv rho, (fy xv rho) rho, fy (rho + 2 xv xv),  fy 2 xu xv)
+ *   tied: column 0 = (xd, yd), column 1 = 0; a held column is 0.
+ * An observation is usable under the conditions of vc_ba_linearize_points and finite k1, k2, p1, p2 of its camera.  Every entry
+ * point takes the loss and obs_w as the _radial ones do.
+ *
+ * vc_ba_linearize_points_opencv writes exactly the arrays of vc_ba_linearize_points_loss: vc_ba_reduce_cameras, vc_ba_step and
+ * the entry points of the solver without S run on them as they are.
+ * vc_ba_linearize_intrinsics_opencv, vc_ba_reduce_border_opencv, vc_ba_step_opencv: the border with eight unknowns per group,
+ * theta_g = (fx, fy, cx, cy, k1, k2, p1, p2); the layouts of "The border" with 8 in the place of 4:
+ *   intr_mask   bits 0-6 as in the radial rule; bit 7 = p1 and p2 held, both
+ *   out_obs_jt  [total][10]: xd, yd, then the entries of the k1, k2, p1 and p2 columns of J_theta, (row u, row v) of each, of a
+ *               usable observation (unscaled by the loss), 0 otherwise: what the B pass rebuilds J_theta from
+ *   out_T       [n_points][n_groups][24] (8x3 row-major)
+ *   out_terms   [80 G + 64 G^2][n_points]: rows 64 g + 8 i + k: q_jg; 64 G + 8 g + i: hq_jg; 72 G + 8 g + i: T V^-1 g_p;
+ *               80 G + 64 (g G + g') + 8 i + k: T_jg V^-1 T_jg''
+ *   out_sums    [80 G + 64 G^2], out_C [8 G][8 G], out_h [8 G], out_free [8 G], out_B [6 n_cams][8 G] (entry 48 g + 8 r + i of a
+ *               camera's row block owned by lane (48 g + 8 r + i) mod 64)
+ *   vc_ba_step_opencv: dtheta [8 G]; out_dist [n_cams][4] = cam_dist + dtheta_4 .. dtheta_7 of the slot's group (copied where the
+ *               slot has none); out_valid: 0 where the slot's group is in the table and its new fx or fy is not finite or not
+ *               positive, or one of its four new distortion numbers is not finite.
+ * n_groups <= VC_BA_MAX_GROUPS_OPENCV (the terms grow with 64 G^2 numbers per point, 1344 rows at G = 4, and a lane of the B pass
+ * keeps ceil(48 G / 64) = 3 entries in registers), VC_ERR_UNSUPPORTED above; sizes of 0, null pointers, negative sizes, a bad loss
+ * and a bad lambda as the _radial entry points; every index is checked; skipped points and cameras write nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define VC_BA_MAX_GROUPS_OPENCV 4
+int vc_ba_linearize_points_opencv(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
+                                  int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                                  int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
+                                  uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream);
+int vc_ba_linearize_intrinsics_opencv(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
+                                      const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets,
+                                      const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
+                                      const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
+                                      double* out_terms, vc_stream_t stream);
+int vc_ba_reduce_border_opencv(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
+                               const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs,
+                               const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
+                               const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
+                               double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream);
+int vc_ba_step_opencv(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                      const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
+                      const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
+                      double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Keypoint selection + descriptors over the ViT token grid — replaces
  * ViTExtractor._dense_to_sparse and helpers (reference vit_colmap/features/vit_extractor.py:168-653).
  * Specification: oracle/select_oracle.py.  All functions are batched over n_images.

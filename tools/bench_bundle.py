@@ -10,7 +10,10 @@ border"): also the three entry points of the border and the bordered solve, and 
 same build, the two alternating.  --radial: after every other column the four entry points with radial distortion on the same
 problem (one group of six unknowns, k1 free from 0 and, with --refine-focal, the tied focal free too): the points pass, the
 border's two passes and the step, beside the plain points pass and the border with four unknowns of the columns before; and
-the loop that refines k1, alternating with the others.  --loss huber|soft_l1 (--loss-scale PX, default 1): after those columns also the points pass
+the loop that refines k1, alternating with the others.  --opencv (with --radial): the four entry points with the tangential terms
+on the same problem (one group of eight unknowns, k1, k2, p1, p2 free from 0), and one whole pass (linearise, the border's two
+passes, the step) of the _opencv entry points beside the same pass of the _radial ones, the two alternating ("The tangential
+terms" in §4.2k).  --loss huber|soft_l1 (--loss-scale PX, default 1): after those columns also the points pass
 under the loss (vc_ba_linearize_points_loss) and, with --refine-focal, the border's two passes with obs_w, on the same buffers;
 and the loop under the loss beside the plain loop, alternating (with --refine-focal the refined loop under the loss too).
 --solver pcg ("The solver" in §4.2k): after every other column vc_ba_camera_blocks, vc_ba_schur_product (both launches), one
@@ -91,7 +94,7 @@ def device_ms(fn, iters):
     return float(np.median(times))
 
 
-def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radial=False, solver=None):
+def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radial=False, solver=None, opencv=False):
     cams, points, offsets, obs_cam, obs_xy, mask = problem
     if refine:
         cams = cams.copy()
@@ -182,7 +185,7 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
     radial_args = {}
     if radial:                                                        # after every other column: the _radial entry points, one group, k1 free
         f64 = dict(dtype=torch.float64, device=dev)
-        rb = bundle._Buffers(torch, c, n, t, dev, with_dist=True)
+        rb = bundle._Buffers(torch, c, n, t, dev, with_dist=2)
         radial_args = dict(cam_group=np.zeros(c, np.int32), intr_mask=np.array([(16 | 4 | 8 if refine else 15) | 64], np.uint8),
                            cam_dist=np.zeros((c, 2)))
         rg, ri = torch.from_numpy(radial_args["cam_group"]).to(dev), torch.from_numpy(radial_args["intr_mask"]).to(dev)
@@ -212,6 +215,38 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
 
         stages += [("linearize_radial_ms", linearize_radial), ("linearize_intrinsics_radial_ms", linearize_intrinsics_radial),
                    ("reduce_border_radial_ms", reduce_border_radial), ("step_radial_ms", step_radial)]
+    passes = {}
+    if radial and opencv:                                             # the same columns with eight unknowns: all four distortion numbers free
+        ob = bundle._Buffers(torch, c, n, t, dev, with_dist=4)
+        oi = torch.tensor([(16 | 4 | 8 if refine else 15)], dtype=torch.uint8, device=dev)
+        jt8, T8, terms8, sums8 = torch.zeros((t, 10), **f64), torch.zeros((n, 1, 24), **f64), torch.zeros((144, n), **f64), torch.zeros(144, **f64)
+        B8, C8, h8, free8 = torch.zeros((6 * c, 8), **f64), torch.zeros((8, 8), **f64), torch.zeros(8, **f64), torch.zeros(8, dtype=torch.uint8, device=dev)
+        dtheta8, out_dist8 = torch.zeros(8, **f64), torch.zeros((c, 4), **f64)
+
+        def linearize_opencv():
+            _lib.check(lib.vc_ba_linearize_points_opencv(p(d[0]), c, p(ob.dist), p(d[1]), p(d[2]), n, p(d[3]), p(d[4]), p(d[5]), t, lam, 0, 1.0,
+                                                         p(ob.vinv), p(ob.gp), p(ob.cost), p(ob.count), p(ob.obs_ok), p(ob.obs_lin), p(ob.obs_w),
+                                                         p(ob.total_cost), stream), "vc_ba_linearize_points_opencv")
+
+        def linearize_intrinsics_opencv():
+            _lib.check(lib.vc_ba_linearize_intrinsics_opencv(p(d[0]), c, p(ob.dist), p(rg), 1, p(oi), p(d[2]), n, p(d[3]), p(d[4]), t, 0, 1.0,
+                                                             p(ob.vinv), p(ob.gp), p(ob.obs_ok), p(ob.obs_lin), p(ob.obs_w), p(jt8), p(T8), p(terms8),
+                                                             stream), "vc_ba_linearize_intrinsics_opencv")
+
+        def reduce_border_opencv():
+            _lib.check(lib.vc_ba_reduce_border_opencv(c, p(rg), 1, p(oi), n, p(d[3]), p(d[4]), t, p(x[0]), p(x[1]), p(x[2]), lam, 0, 1.0, p(ob.vinv),
+                                                      p(ob.obs_ok), p(ob.obs_lin), p(jt8), p(ob.obs_w), p(T8), p(terms8), p(sums8), p(B8), p(C8),
+                                                      p(h8), p(free8), stream), "vc_ba_reduce_border_opencv")
+
+        def step_opencv():
+            _lib.check(lib.vc_ba_step_opencv(p(d[0]), c, p(ob.dist), p(rg), 1, p(oi), p(d[2]), n, p(d[3]), p(d[4]), t, p(ob.vinv), p(ob.gp),
+                                             p(ob.obs_ok), p(ob.obs_lin), p(T8), p(dc), p(dtheta8), p(out_cams), p(out_dist8), p(out_points), p(dx),
+                                             p(valid6), stream), "vc_ba_step_opencv")
+
+        stages += [("linearize_opencv_ms", linearize_opencv), ("linearize_intrinsics_opencv_ms", linearize_intrinsics_opencv),
+                   ("reduce_border_opencv_ms", reduce_border_opencv), ("step_opencv_ms", step_opencv)]
+        passes = dict(radial_pass_ms=lambda: (linearize_radial(), linearize_intrinsics_radial(), reduce_border_radial(), step_radial()),
+                      opencv_pass_ms=lambda: (linearize_opencv(), linearize_intrinsics_opencv(), reduce_border_opencv(), step_opencv()))
     if solver == "pcg":
         pcg = bundle._Pcg(torch, lib, c, n, dev, bundle.PCG_REL_TOL, bundle.PCG_MAX_ITERATIONS)
         vector = torch.randn(6 * c, dtype=torch.float64, device=dev)
@@ -227,6 +262,12 @@ def measure(problem, iters, loops, refine=False, loss=None, loss_scale=1.0, radi
         stages += [("blocks_ms", blocks), ("product_ms", product)]
     for name, fn in stages:
         out[name] = round(device_ms(fn, iters), 4)
+    if passes:                                                        # one whole pass of either family, the two alternating
+        rounds = {name: [] for name in passes}
+        for _ in range(loops):
+            for name, fn in passes.items():
+                rounds[name].append(device_ms(fn, iters))
+        out.update({name: round(float(np.median(v)), 4) for name, v in rounds.items()})
     if solver == "pcg":
         # one whole solve on the first linearisation, wall clock with its host reads; then the same number of iterations of the same
         # device work without the read per iteration, which is what the read costs
@@ -324,6 +365,9 @@ def main():
     ap.add_argument("--radial", action="store_true",
                     help="also time the entry points with radial distortion (six unknowns in one group, k1 free from 0) and the loop that "
                          "refines k1 (DESIGN.md §4.2k, \"The distortion\")")
+    ap.add_argument("--opencv", action="store_true",
+                    help="with --radial: also time the entry points with the tangential terms (eight unknowns in one group) and one whole pass "
+                         "of them beside the same pass of the radial ones, alternating")
     ap.add_argument("--solver", choices=["pcg"], default=None,
                     help="also time the two entry points of the matrix-free solver, one solve and the pcg loop beside the dense one, on a "
                          "third arc of --big-cams cameras too and on a fourth of --above-cams with pcg alone (DESIGN.md §4.2k, \"The solver\")")
@@ -332,7 +376,9 @@ def main():
     ap.add_argument("--above-cams", dest="above_cams", type=int, default=1024)
     ap.add_argument("--above-points", dest="above_points", type=int, default=102400)
     args = ap.parse_args()
-    extra = (args.refine_focal, args.loss, args.loss_scale, args.radial, args.solver)
+    if args.opencv and not args.radial:
+        ap.error("--opencv times its columns beside the radial ones: it needs --radial")
+    extra = (args.refine_focal, args.loss, args.loss_scale, args.radial, args.solver, args.opencv)
     out = dict(tool="bench_bundle", iters=args.iters, loops=args.loops, refine_focal=args.refine_focal, loss=args.loss,
                loss_scale=args.loss_scale, radial=args.radial, solver=args.solver, windowed=measure(windowed_problem(), args.iters, args.loops, *extra),
                arc=measure(arc_problem(args.cams, args.points), args.iters, args.loops, *extra))

@@ -28,6 +28,10 @@
 // the plain section as it is (its step under dc alone), then with G >= 1 float64 obs_jt (total, 6), T (n_points, G, 18), terms
 // (48 G + 36 G^2, n_points), sums (48 G + 36 G^2), B (6 n_cams, 6 G), C (6 G, 6 G), h (6 G), out_cams, out_points, dx, out_dist
 // (n_cams, 2); uint8 free (6 G), valid (n_cams); then obs_w.  More than VC_BA_MAX_GROUPS_RADIAL groups: exit status 3.
+// The tangential terms ("The tangential terms" in §4.2k) are the same extension under the marker int32 2: float64 cam_dist
+// (n_cams, 4), dtheta (n_groups, 8), the routines of the _opencv entry points, and the radial layout with eight unknowns per group:
+// obs_jt (total, 10), T (n_points, G, 24), terms and sums (80 G + 64 G^2), B (6 n_cams, 8 G), C (8 G, 8 G), h (8 G), out_dist
+// (n_cams, 4), free (8 G).  More than VC_BA_MAX_GROUPS_OPENCV groups: exit status 3.  Files without the marker 2 are read as before.
 #include "../vit_colmap_amd/csrc/bundle.hip"
 #include "host_io.h"
 
@@ -67,9 +71,12 @@ static Step take_step(const BaProblem& d, const BaLinear& l, const BaGroups& gr,
   return s;
 }
 
-// The radial extension: every routine under kRadial and the loss (the kernels of the _radial entry points), six unknowns per group.
-static int run_radial(const char* path, const BaProblem& d, const BaGroups& gr, const BaLoss& loss, double lambda, const int32_t* cam_offsets,
+// The distortion's extensions: every routine under kDist and the loss (the kernels of the _radial and the _opencv entry points),
+// six or eight unknowns per group.
+template <int kDist>
+static int run_dist(const char* path, const BaProblem& d, const BaGroups& gr, const BaLoss& loss, double lambda, const int32_t* cam_offsets,
                       const int32_t* cam_obs, const int32_t* obs_point, const double* cam_dist, const double* dc, const double* dtheta) {
+  constexpr int N = ba_dist_unknowns(kDist), kParams = ba_dist_params(kDist);
   const int n_cams = d.n_cams, n_points = d.n_points, total = d.total, G = gr.n_groups;
   std::vector<double> vinv(6 * (size_t)n_points), gp(3 * (size_t)n_points), cost(n_points), total_cost(1, 0.0);
   std::vector<double> obs_lin((size_t)kBaLin * total), obs_w(total);
@@ -77,7 +84,7 @@ static int run_radial(const char* path, const BaProblem& d, const BaGroups& gr, 
   std::vector<uint8_t> obs_ok(total);
   for (int j = 0; j < n_points; ++j) {
     double v[6], g[3];
-    count[j] = ba_linearize_point<true, true>(d, loss, j, lambda, v, g, cost[j], obs_ok.data(), obs_lin.data(), obs_w.data(), cam_dist);
+    count[j] = ba_linearize_point<true, kDist>(d, loss, j, lambda, v, g, cost[j], obs_ok.data(), obs_lin.data(), obs_w.data(), cam_dist);
     for (int k = 0; k < 6; ++k) vinv[6 * (size_t)j + k] = v[k];
     for (int k = 0; k < 3; ++k) gp[3 * (size_t)j + k] = g[k];
     total_cost[0] += cost[j];
@@ -96,15 +103,20 @@ static int run_radial(const char* path, const BaProblem& d, const BaGroups& gr, 
   auto take = [&](const BaGroups& groups, const double* T, const double* dth, Step& s, std::vector<double>& dist) {
     s = Step{std::vector<double>(16 * (size_t)n_cams), std::vector<double>(3 * (size_t)n_points), std::vector<double>(3 * (size_t)n_points),
              std::vector<uint8_t>(n_cams)};
-    dist.assign(2 * (size_t)n_cams, 0.0);
+    dist.assign(kParams * (size_t)n_cams, 0.0);
     for (int j = 0; j < n_points; ++j) {
       double dX[3];
-      ba_point_step<6>(d, l, T, groups.n_groups, dc, dth, j, dX);
+      ba_point_step<N>(d, l, T, groups.n_groups, dc, dth, j, dX);
       for (int k = 0; k < 3; ++k) s.dx[3 * (size_t)j + k] = dX[k], s.points[3 * (size_t)j + k] = d.points[3 * (size_t)j + k] + dX[k];
     }
-    for (int a = 0; a < n_cams; ++a)
-      s.valid[a] = ba_camera_step_radial(d.cams + 16 * (size_t)a, cam_dist + 2 * (size_t)a, dc + 6 * (size_t)a, groups, a, dth,
-                                         s.cams.data() + 16 * (size_t)a, dist.data() + 2 * (size_t)a) ? 1 : 0;
+    for (int a = 0; a < n_cams; ++a) {
+      if constexpr (kDist == kBaDistOpencv)
+        s.valid[a] = ba_camera_step_opencv(d.cams + 16 * (size_t)a, cam_dist + 4 * (size_t)a, dc + 6 * (size_t)a, groups, a, dth,
+                                           s.cams.data() + 16 * (size_t)a, dist.data() + 4 * (size_t)a) ? 1 : 0;
+      else
+        s.valid[a] = ba_camera_step_radial(d.cams + 16 * (size_t)a, cam_dist + 2 * (size_t)a, dc + 6 * (size_t)a, groups, a, dth,
+                                           s.cams.data() + 16 * (size_t)a, dist.data() + 2 * (size_t)a) ? 1 : 0;
+    }
   };
   Step plain, step;
   std::vector<double> plain_dist, out_dist;
@@ -116,10 +128,10 @@ static int run_radial(const char* path, const BaProblem& d, const BaGroups& gr, 
   write_all(out, plain.cams), write_all(out, plain.points), write_all(out, plain.dx), write_all(out, obs_lin), write_all(out, count);
   write_all(out, obs_ok);
   if (G >= 1) {
-    const int rows = ba_term_rows<6>(G), m = 6 * G;
-    std::vector<double> obs_jt((size_t)kBaJt * total), T((size_t)n_points * G * 18), terms((size_t)rows * n_points), sums(rows);
+    const int rows = ba_term_rows<N>(G), m = N * G;
+    std::vector<double> obs_jt((size_t)ba_dist_jt(kDist) * total), T((size_t)n_points * G * 3 * N), terms((size_t)rows * n_points), sums(rows);
     for (int j = 0; j < n_points; ++j)
-      ba_linearize_point_intrinsics<true, true>(d, l, gr, obs_w.data(), j, obs_jt.data(), T.data(), terms.data(), cam_dist);
+      ba_linearize_point_intrinsics<true, kDist>(d, l, gr, obs_w.data(), j, obs_jt.data(), T.data(), terms.data(), cam_dist);
     for (int r = 0; r < rows; ++r) {
       double sum = 0.0;
       for (int j = 0; j < n_points; ++j) sum += terms[(size_t)r * n_points + j];
@@ -127,18 +139,18 @@ static int run_radial(const char* path, const BaProblem& d, const BaGroups& gr, 
     }
     std::vector<double> B(6 * (size_t)n_cams * m), C((size_t)m * m), h(m);
     std::vector<uint8_t> free_(m);
-    for (int idx = 0; idx < m * m; ++idx) C[idx] = ba_border_c<6>(sums.data(), gr, lambda, idx / m, idx % m);
+    for (int idx = 0; idx < m * m; ++idx) C[idx] = ba_border_c<N>(sums.data(), gr, lambda, idx / m, idx % m);
     for (int row = 0; row < m; ++row)
-      h[row] = ba_border_h<6>(sums.data(), gr, row), free_[row] = ba_theta_free<6>(sums.data(), gr, row / 6, row % 6) ? 1 : 0;
+      h[row] = ba_border_h<N>(sums.data(), gr, row), free_[row] = ba_theta_free<N>(sums.data(), gr, row / N, row % N) ? 1 : 0;
     for (int a = 0; a < n_cams; ++a) {
       BaBorderLane lanes[kBaWave];
       for (int lane = 0; lane < kBaWave; ++lane)
         for (int k = 0; k < kBaBorderSlots; ++k) lanes[lane].jt[k] = lanes[lane].yt[k] = 0.0;
       const int ga = ba_group_of(gr, a);
       camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, [&](int lane, int o, int j, int, int, const double* y) {
-        ba_border_update<true, true>(l, gr, obs_jt.data(), obs_w.data(), T.data(), ga, o, j, lane, y, lanes[lane]);
+        ba_border_update<true, kDist>(l, gr, obs_jt.data(), obs_w.data(), T.data(), ga, o, j, lane, y, lanes[lane]);
       });
-      for (int lane = 0; lane < kBaWave; ++lane) ba_border_finish<6>(G, a, lane, lanes[lane], B.data());
+      for (int lane = 0; lane < kBaWave; ++lane) ba_border_finish<N>(G, a, lane, lanes[lane], B.data());
     }
     take(gr, T.data(), dtheta, step, out_dist);
     write_all(out, obs_jt), write_all(out, T), write_all(out, terms), write_all(out, sums), write_all(out, B), write_all(out, C);
@@ -147,7 +159,8 @@ static int run_radial(const char* path, const BaProblem& d, const BaGroups& gr, 
   }
   write_all(out, obs_w);
   std::fclose(out);
-  std::printf("%d cameras, %d points, %d observations, %d groups, radial, cost %.17g\n", n_cams, n_points, total, G, total_cost[0]);
+  std::printf("%d cameras, %d points, %d observations, %d groups, %s, cost %.17g\n", n_cams, n_points, total, G,
+              kDist == kBaDistOpencv ? "opencv" : "radial", total_cost[0]);
   return 0;
 }
 
@@ -175,13 +188,14 @@ int main(int argc, char** argv) {
   const bool with_loss = ok && std::fread(&loss_kind, sizeof(int32_t), 1, in) == 1;
   const bool loss_read = !with_loss || std::fread(&loss.scale, sizeof(double), 1, in) == 1;
   loss.kind = loss_kind;
-  // the optional distortion after the loss: nothing, or the marker 1 and both of its arrays
-  int32_t radial_mark = 0;
-  const bool with_radial = with_loss && loss_read && std::fread(&radial_mark, sizeof(int32_t), 1, in) == 1;
-  std::vector<double> cam_dist(with_radial ? 2 * (size_t)n_cams : 0), dtheta6(with_radial ? 6 * (size_t)G : 0);
-  const bool radial_read = !with_radial || (radial_mark == 1 && read_all(in, cam_dist) && read_all(in, dtheta6));
+  // the optional distortion after the loss: nothing, or the marker (1: radial, 2: with the tangential terms) and both of its arrays
+  int32_t dist_mark = 0;
+  const bool with_dist = with_loss && loss_read && std::fread(&dist_mark, sizeof(int32_t), 1, in) == 1;
+  const bool opencv = with_dist && dist_mark == 2;
+  std::vector<double> cam_dist(with_dist ? (opencv ? 4 : 2) * (size_t)n_cams : 0), dist_dtheta(with_dist ? (opencv ? 8 : 6) * (size_t)G : 0);
+  const bool dist_read = !with_dist || ((dist_mark == 1 || opencv) && read_all(in, cam_dist) && read_all(in, dist_dtheta));
   std::fclose(in);
-  if (!ok || !loss_read || !radial_read) {
+  if (!ok || !loss_read || !dist_read) {
     std::fprintf(stderr, "%s: shorter than its header says\n", argv[1]);
     return 2;
   }
@@ -189,18 +203,25 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "%s: loss %d with scale %g is refused\n", argv[1], loss.kind, loss.scale);
     return 3;
   }
-  if (with_radial && G > VC_BA_MAX_GROUPS_RADIAL) {
+  if (opencv && G > VC_BA_MAX_GROUPS_OPENCV) {
+    std::fprintf(stderr, "%s: %d groups with the tangential terms are refused (VC_BA_MAX_GROUPS_OPENCV)\n", argv[1], G);
+    return 3;
+  }
+  if (with_dist && !opencv && G > VC_BA_MAX_GROUPS_RADIAL) {
     std::fprintf(stderr, "%s: %d groups with the distortion are refused (VC_BA_MAX_GROUPS_RADIAL)\n", argv[1], G);
     return 3;
   }
   std::vector<uint8_t> const_mask(n_cams), intr_mask(G);
   for (int a = 0; a < n_cams; ++a) const_mask[a] = (uint8_t)mask32[a];
   for (int g = 0; g < G; ++g) intr_mask[g] = (uint8_t)intr32[g];
-  if (with_radial)
-    return run_radial(argv[2], BaProblem{cams.data(), const_mask.data(), points.data(), offsets.data(), obs_cam.data(), obs_xy.data(), n_cams,
-                                         n_points, total},
-                      BaGroups{cam_group.data(), intr_mask.data(), G}, loss, lambda, cam_offsets.data(), cam_obs.data(), obs_point.data(),
-                      cam_dist.data(), dc.data(), dtheta6.data());
+  if (with_dist) {
+    const BaProblem d{cams.data(), const_mask.data(), points.data(), offsets.data(), obs_cam.data(), obs_xy.data(), n_cams, n_points, total};
+    const BaGroups gr{cam_group.data(), intr_mask.data(), G};
+    return opencv ? run_dist<kBaDistOpencv>(argv[2], d, gr, loss, lambda, cam_offsets.data(), cam_obs.data(), obs_point.data(), cam_dist.data(),
+                                            dc.data(), dist_dtheta.data())
+                  : run_dist<kBaDistRadial>(argv[2], d, gr, loss, lambda, cam_offsets.data(), cam_obs.data(), obs_point.data(), cam_dist.data(),
+                                            dc.data(), dist_dtheta.data());
+  }
 
   // 1. the points pass and the total cost
   std::vector<double> vinv(6 * (size_t)n_points), gp(3 * (size_t)n_points), cost(n_points), total_cost(1, 0.0);

@@ -19,6 +19,7 @@ VC_MAX_NEIGHBOURS = 64
 VC_BA_MAX_CAMS = 512
 VC_BA_MAX_GROUPS = 8
 VC_BA_MAX_GROUPS_RADIAL = 4
+VC_BA_MAX_GROUPS_OPENCV = 4
 VC_BA_LOSS_TRIVIAL, VC_BA_LOSS_HUBER, VC_BA_LOSS_SOFT_L1 = 0, 1, 2
 VC_ERR_INVALID_ARG, VC_ERR_UNSUPPORTED, VC_ERR_LAUNCH, VC_ERR_WORKSPACE = -1, -2, -3, -4
 
@@ -94,6 +95,14 @@ SIGNATURES = {
     "vc_ba_reduce_border_radial": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                            c_double, c_int, c_double] + [c_void_p] * 13),
     "vc_ba_step_radial": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]
+                          + [c_void_p] * 13),
+    "vc_ba_linearize_points_opencv": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                              c_double, c_int, c_double] + [c_void_p] * 9),
+    "vc_ba_linearize_intrinsics_opencv": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                                  c_int, c_int, c_double] + [c_void_p] * 9),
+    "vc_ba_reduce_border_opencv": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_double, c_int, c_double] + [c_void_p] * 13),
+    "vc_ba_step_opencv": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]
                           + [c_void_p] * 13),
     "vc_structure_tensor": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vc_score_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -9,7 +9,10 @@
 // template argument, and without it return the bytes they returned.  With radial distortion (vc_ba_linearize_points_radial,
 // vc_ba_linearize_intrinsics_radial, vc_ba_reduce_border_radial, vc_ba_step_radial; COLMAP's SIMPLE_RADIAL and RADIAL) the
 // camera's (k1, k2) travel beside its row as cam_dist [n_cams][2] and theta_g = (fx, fy, cx, cy, k1, k2); the routines take the
-// distortion as a second template argument, and without it are what they were.  Without the dense S ("The solver" in §4.2k:
+// distortion as a second template argument, and without it are what they were.  With the tangential terms
+// (vc_ba_linearize_points_opencv, vc_ba_linearize_intrinsics_opencv, vc_ba_reduce_border_opencv, vc_ba_step_opencv; COLMAP's OPENCV)
+// cam_dist is [n_cams][4] = (k1, k2, p1, p2), theta_g has eight unknowns and bit 7 of a group's mask holds p1 and p2 together: the
+// third value of that template argument (BaDistortion, ba_project_opencv below; tests/util_bundle_opencv.py).  Without the dense S ("The solver" in §4.2k:
 // vc_ba_camera_blocks, vc_ba_schur_product) the caller solves S dc = -g by preconditioned conjugate gradients: the first gives
 // per camera U_a, the diagonal block D_a = S_aa, D_a^-1, g_a and which parameters are fixed, the second q = S p in two passes
 // over what the points pass left, for any number of cameras.  The order of operations, in full (BaRadial,
@@ -136,9 +139,23 @@ __host__ __device__ __forceinline__ void ba_loss(const BaLoss& loss, double s, d
 //   s = 1 + k1 rho + k2 rho rho, e = 2 (k1 + 2 k2 rho), the symmetric 2x2 Jacobian D of the map: d00 = s + xu xu e, d01 = xu xv e,
 //   d11 = s + xv xv e, and the six numbers from which the border rebuilds J_theta (obs_jt of the radial entry points):
 //   xd = xu s, yd = xv s, pu = fx xu rho, pv = fy xv rho, qu = pu rho, qv = pv rho.
-struct BaRadial {
-  double d00, d01, d11, jt[6];
+// With the tangential terms ("The tangential terms" in §4.2k; COLMAP's OPENCV, cam_dist [n_cams][4] = (k1, k2, p1, p2)) the map is
+//   xd = xu s + 2 p1 xu xv + p2 (rho + 2 xu xu), yd = xv s + p1 (rho + 2 xv xv) + 2 p2 xu xv, the radial term first as
+//   csrc/undistort.hip writes it, D gains d00 += 2 p1 xv + 6 p2 xu, d01 += 2 p1 xu + 2 p2 xv, d11 += 6 p1 xv + 2 p2 xu, and obs_jt
+//   has ten numbers: the six above, then the p1 column (fx 2 xu xv, fy (rho + 2 xv xv)) and the p2 column (fx (rho + 2 xu xu),
+//   fy 2 xu xv) of J_theta.
+// The routines take the distortion as a template argument kDist; kBaDistNone is the pinhole they were written for.
+constexpr int kBaDistNone = 0, kBaDistRadial = 1, kBaDistOpencv = 2;
+__host__ __device__ constexpr int ba_dist_params(int dist) { return dist == kBaDistOpencv ? 4 : 2; }     // numbers per row of cam_dist
+__host__ __device__ constexpr int ba_dist_jt(int dist) { return dist == kBaDistOpencv ? 10 : 6; }        // numbers per row of obs_jt
+__host__ __device__ constexpr int ba_dist_unknowns(int dist) { return dist == kBaDistOpencv ? 8 : dist == kBaDistRadial ? 6 : 4; }
+
+template <int kDist>
+struct BaDistortion {
+  double d00, d01, d11, jt[ba_dist_jt(kDist)];
 };
+using BaRadial = BaDistortion<kBaDistRadial>;
+using BaOpencv = BaDistortion<kBaDistOpencv>;
 
 // X in the camera of row c[16] under (k1, k2): ba_project on the row with fx = fy = 1, so that iu = 1 / Xc_z and (nu, nv) is the
 // Jacobian of (xu, xv); then J_p = diag(fx, fy) D (nu; nv): ju = fx (d00 nu + d01 nv), jv = fy (d01 nu + d11 nv).
@@ -163,12 +180,49 @@ __host__ __device__ __forceinline__ void ba_project_radial(const double* c, doub
   }
 }
 
+// The same under (k1, k2, p1, p2): the radial term first, the tangential terms added after it, left to right.
+__host__ __device__ __forceinline__ void ba_project_opencv(const double* c, double k1, double k2, double p1, double p2, const double (&X)[3],
+                                                           double (&Y)[3], double (&Xc)[3], double& iu, double& xu, double& xv, BaOpencv& rd,
+                                                           double (&ju)[3], double (&jv)[3]) {
+  double n[16], iv, nu[3], nv[3];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) n[k] = k == 12 || k == 13 ? 1.0 : c[k];
+  ba_project(n, X, Y, Xc, iu, iv, xu, xv, nu, nv);
+  const double fx = c[12], fy = c[13];
+  const double rho = xu * xu + xv * xv;
+  const double s = 1.0 + k1 * rho + k2 * rho * rho;
+  const double e = 2.0 * (k1 + 2.0 * k2 * rho);
+  rd.d00 = s + xu * xu * e + 2.0 * p1 * xv + 6.0 * p2 * xu;
+  rd.d01 = xu * xv * e + 2.0 * p1 * xu + 2.0 * p2 * xv;
+  rd.d11 = s + xv * xv * e + 6.0 * p1 * xv + 2.0 * p2 * xu;
+  rd.jt[0] = xu * s + 2.0 * p1 * xu * xv + p2 * (rho + 2.0 * xu * xu);
+  rd.jt[1] = xv * s + p1 * (rho + 2.0 * xv * xv) + 2.0 * p2 * xu * xv;
+  rd.jt[2] = fx * xu * rho, rd.jt[3] = fy * xv * rho;
+  rd.jt[4] = rd.jt[2] * rho, rd.jt[5] = rd.jt[3] * rho;
+  rd.jt[6] = fx * 2.0 * xu * xv, rd.jt[7] = fy * (rho + 2.0 * xv * xv);
+  rd.jt[8] = fx * (rho + 2.0 * xu * xu), rd.jt[9] = fy * 2.0 * xu * xv;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    ju[k] = fx * (rd.d00 * nu[k] + rd.d01 * nv[k]);
+    jv[k] = fy * (rd.d01 * nu[k] + rd.d11 * nv[k]);
+  }
+}
+
+// ba_project_radial or ba_project_opencv on the row dist of cam_dist, whichever kDist names.
+template <int kDist>
+__host__ __device__ __forceinline__ void ba_project_dist(const double* c, const double* __restrict__ dist, const double (&X)[3], double (&Y)[3],
+                                                         double (&Xc)[3], double& iu, double& xu, double& xv, BaDistortion<kDist>& rd,
+                                                         double (&ju)[3], double (&jv)[3]) {
+  if constexpr (kDist == kBaDistOpencv) ba_project_opencv(c, dist[0], dist[1], dist[2], dist[3], X, Y, Xc, iu, xu, xv, rd, ju, jv);
+  else ba_project_radial(c, dist[0], dist[1], X, Y, Xc, iu, xu, xv, rd, ju, jv);
+}
+
 // Observation o of point X: usable -> lin[32] (zeros otherwise) and J_p (2x3).  With a loss the rows of J_c and J_p and r are
 // multiplied by sw = sqrt(w) before anything is formed from them, and rho is the loss of the unweighted residual, the
 // observation's term of the cost.  kRadial: the camera's (k1, k2) of cam_dist [n_cams][2] must be finite too, the projection
 // is ba_project_radial's, r = (fx xd + cx - u, fy yd + cy - v) and J_c = diag(fx, fy) D (the pinhole rows at fx = fy = 1);
-// without it cam_dist is absent and not read.
-template <bool kLoss, bool kRadial = false>
+// without it cam_dist is absent and not read.  kBaDistOpencv: the four numbers of cam_dist [n_cams][4] and ba_project_opencv.
+template <bool kLoss, int kDist = kBaDistNone>
 __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const BaLoss& loss, int o, const double (&X)[3],
                                                     double* __restrict__ lin, double (&ju)[3], double (&jv)[3], double& rho, double& sw,
                                                     const double* __restrict__ cam_dist = nullptr) {
@@ -185,8 +239,18 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
   ok = ok && ba_finite(u) && ba_finite(v);
   const unsigned held = ok ? d.const_mask[slot] : 0u;
   double Y[3], Xc[3], fu, fv, xu, xv;
-  BaRadial rd;
-  if (kRadial) {
+  constexpr bool kRadial = kDist != kBaDistNone;
+  BaDistortion<kDist> rd;
+  if constexpr (kDist == kBaDistOpencv) {
+    double k[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      k[i] = ok ? cam_dist[4 * (long long)slot + i] : NAN;
+      ok = ok && ba_finite(k[i]);
+    }
+    ba_project_opencv(row, k[0], k[1], k[2], k[3], X, Y, Xc, fu, xu, xv, rd, ju, jv);
+    fv = fu;
+  } else if constexpr (kDist == kBaDistRadial) {
     const double k1 = ok ? cam_dist[2 * (long long)slot] : NAN, k2 = ok ? cam_dist[2 * (long long)slot + 1] : NAN;
     ok = ok && ba_finite(k1) && ba_finite(k2);
     ba_project_radial(row, k1, k2, X, Y, Xc, fu, xu, xv, rd, ju, jv);
@@ -238,7 +302,7 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
 
 // One point: its track linearised -> V^-1 (damped, 0 where the point is constant), g_p, cost, the usable count; per
 // observation of the track obs_ok and obs_lin and, with a loss, obs_w: sw of a usable observation, 0 of any other.
-template <bool kLoss, bool kRadial = false>
+template <bool kLoss, int kDist = kBaDistNone>
 __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, const BaLoss& loss, int j, double lambda, double (&vinv)[6],
                                                            double (&gp)[3], double& cost, uint8_t* __restrict__ obs_ok,
                                                            double* __restrict__ obs_lin, double* __restrict__ obs_w,
@@ -254,7 +318,7 @@ __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, c
   for (int o = lo; o < hi; ++o) {
     double* lin = obs_lin + (long long)o * kBaLin;
     double ju[3], jv[3], rho, sw;
-    const bool ok = ba_observe<kLoss, kRadial>(d, loss, o, X, lin, ju, jv, rho, sw, cam_dist);
+    const bool ok = ba_observe<kLoss, kDist>(d, loss, o, X, lin, ju, jv, rho, sw, cam_dist);
     obs_ok[o] = ok ? 1 : 0;
     if (kLoss) obs_w[o] = ok ? sw : 0.0;
     if (!ok) continue;
@@ -571,11 +635,11 @@ __host__ __device__ __forceinline__ void ba_pose_step(const double* __restrict__
 constexpr int kBaT = 12;                                                      // T_{j,g} = sum J_theta' J_p, 4x3 row-major
 constexpr int kBaBorderSlots = (24 * VC_BA_MAX_GROUPS + kBaWave - 1) / kBaWave;   // entries of a camera's B row block per lane
 static_assert((36 * VC_BA_MAX_GROUPS_RADIAL + kBaWave - 1) / kBaWave <= kBaBorderSlots, "B_a [6][6 G] of the radial limit must fit a lane's slots");
-constexpr int kBaJt = 6;                                                      // obs_jt: xd, yd, pu, pv, qu, qv (BaRadial)
+static_assert((48 * VC_BA_MAX_GROUPS_OPENCV + kBaWave - 1) / kBaWave <= kBaBorderSlots, "B_a [6][8 G] of the OPENCV limit must fit a lane's slots");
 
 struct BaGroups {
   const int32_t* __restrict__ cam_group;       // [n_cams]
-  const uint8_t* __restrict__ intr_mask;       // [n_groups]: bits 0-3 fx fy cx cy held, bit 4 fx and fy tied; radial: bits 5, 6 k1, k2 held
+  const uint8_t* __restrict__ intr_mask;       // [n_groups]: bits 0-3 fx fy cx cy held, bit 4 tied; radial: bits 5, 6 k1, k2 held; OPENCV: bit 7 p1, p2
   int n_groups;
 };
 
@@ -615,8 +679,15 @@ __host__ __device__ __forceinline__ bool ba_theta_held_radial(unsigned mask, int
   return i < 4 ? ba_theta_held(mask, i) : ((mask >> (i + 1)) & 1u) != 0;
 }
 
+// The eight unknowns: parameter i < 6 as above; p1 (i = 6) and p2 (i = 7) are held together by bit 7.
+__host__ __device__ __forceinline__ bool ba_theta_held_opencv(unsigned mask, int i) {
+  return i < 6 ? ba_theta_held_radial(mask, i) : ((mask >> 7) & 1u) != 0;
+}
+
 template <int N>
-__host__ __device__ __forceinline__ bool ba_held(unsigned mask, int i) { return N == 6 ? ba_theta_held_radial(mask, i) : ba_theta_held(mask, i); }
+__host__ __device__ __forceinline__ bool ba_held(unsigned mask, int i) {
+  return N == 8 ? ba_theta_held_opencv(mask, i) : N == 6 ? ba_theta_held_radial(mask, i) : ba_theta_held(mask, i);
+}
 
 // Column i of J_theta = [[xd, 0, 1, 0, pu, qu], [0, yd, 0, 1, pv, qv]] from jt = (xd, yd, pu, pv, qu, qv); tied: column 0 is
 // (xd, yd); a held column is 0.  i may be a runtime value: the column is selected, not indexed.
@@ -625,6 +696,21 @@ __host__ __device__ __forceinline__ void ba_jtheta_radial(unsigned mask, const d
   tu = i == 0 ? jt[0] : i == 2 ? 1.0 : i == 4 ? jt[2] : i == 5 ? jt[4] : 0.0;
   tv = i == 0 ? (tied ? jt[1] : 0.0) : i == 1 ? jt[1] : i == 3 ? 1.0 : i == 4 ? jt[3] : i == 5 ? jt[5] : 0.0;
   if (ba_theta_held_radial(mask, i)) tu = tv = 0.0;
+}
+
+// Column i of the eight-column J_theta from jt[10]: the six of ba_jtheta_radial, then the p1 column (jt[6], jt[7]) and the p2
+// column (jt[8], jt[9]); selected by compares, as there.
+__host__ __device__ __forceinline__ void ba_jtheta_opencv(unsigned mask, const double* jt, int i, double& tu, double& tv) {
+  const bool tied = (mask >> 4) & 1u;
+  tu = i == 0 ? jt[0] : i == 2 ? 1.0 : i == 4 ? jt[2] : i == 5 ? jt[4] : i == 6 ? jt[6] : i == 7 ? jt[8] : 0.0;
+  tv = i == 0 ? (tied ? jt[1] : 0.0) : i == 1 ? jt[1] : i == 3 ? 1.0 : i == 4 ? jt[3] : i == 5 ? jt[5] : i == 6 ? jt[7] : i == 7 ? jt[9] : 0.0;
+  if (ba_theta_held_opencv(mask, i)) tu = tv = 0.0;
+}
+
+template <int kDist>
+__host__ __device__ __forceinline__ void ba_jtheta_dist(unsigned mask, const double* jt, int i, double& tu, double& tv) {
+  if constexpr (kDist == kBaDistOpencv) ba_jtheta_opencv(mask, jt, i, tu, tv);
+  else ba_jtheta_radial(mask, jt, i, tu, tv);
 }
 
 // A usable observation of X in camera row c again: x = Xc_x / Xc_z, y = Xc_y / Xc_z and J_p.
@@ -639,12 +725,14 @@ __host__ __device__ __forceinline__ void ba_observe_point(const double* __restri
 // J_theta (its constant columns too) are multiplied by obs_w[o], as the points pass multiplied what it left in obs_lin; obs_xn
 // stays the unscaled (x, y).  kRadial: N = 6 unknowns per group, the observation is ba_project_radial's under cam_dist, and
 // obs_xn is obs_jt [total][6], the unscaled (xd, yd, pu, pv, qu, qv) of a usable observation and zeros of any other.
-template <bool kLoss, bool kRadial = false>
+// kBaDistOpencv: N = 8, ba_project_opencv, obs_jt [total][10].
+template <bool kLoss, int kDist = kBaDistNone>
 __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaProblem& d, const BaLinear& l, const BaGroups& gr,
                                                                        const double* __restrict__ obs_w, int j, double* __restrict__ obs_xn,
                                                                        double* T, double* __restrict__ terms,
                                                                        const double* __restrict__ cam_dist = nullptr) {
-  constexpr int N = kRadial ? 6 : 4, NT = kRadial ? 3 * N : kBaT;
+  constexpr bool kRadial = kDist != kBaDistNone;
+  constexpr int N = ba_dist_unknowns(kDist), NT = kRadial ? 3 * N : kBaT, kJt = ba_dist_jt(kDist), kParams = ba_dist_params(kDist);
   const int G = gr.n_groups;
   const long long n = d.n_points;
   int lo, hi;
@@ -653,17 +741,16 @@ __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaP
   if (lo < hi) X[0] = d.points[3 * (long long)j], X[1] = d.points[3 * (long long)j + 1], X[2] = d.points[3 * (long long)j + 2];
   for (int o = lo; o < hi; ++o) {
     const int slot = d.obs_cam[o];
-    if (kRadial) {
-      BaRadial rd;
+    if constexpr (kRadial) {
+      BaDistortion<kDist> rd;
 #pragma unroll
-      for (int k = 0; k < kBaJt; ++k) rd.jt[k] = 0.0;
+      for (int k = 0; k < kJt; ++k) rd.jt[k] = 0.0;
       if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) {
         double Y[3], Xc[3], iu, xu, xv, ju[3], jv[3];
-        ba_project_radial(d.cams + 16 * (long long)slot, cam_dist[2 * (long long)slot], cam_dist[2 * (long long)slot + 1], X, Y, Xc, iu, xu, xv,
-                          rd, ju, jv);
+        ba_project_dist<kDist>(d.cams + 16 * (long long)slot, cam_dist + kParams * (long long)slot, X, Y, Xc, iu, xu, xv, rd, ju, jv);
       }
 #pragma unroll
-      for (int k = 0; k < kBaJt; ++k) obs_xn[kBaJt * (long long)o + k] = rd.jt[k];
+      for (int k = 0; k < kJt; ++k) obs_xn[kJt * (long long)o + k] = rd.jt[k];
     } else {
       double x = 0.0, y = 0.0, ju[3], jv[3];
       if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
@@ -684,13 +771,12 @@ __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaP
       const int slot = d.obs_cam[o];
       if (!l.obs_ok[o] || slot < 0 || slot >= d.n_cams || ba_group_of(gr, slot) != g) continue;
       double ju[3], jv[3], tu[N], tv[N];
-      if (kRadial) {
-        BaRadial rd;
+      if constexpr (kRadial) {
+        BaDistortion<kDist> rd;
         double Y[3], Xc[3], iu, xu, xv;
-        ba_project_radial(d.cams + 16 * (long long)slot, cam_dist[2 * (long long)slot], cam_dist[2 * (long long)slot + 1], X, Y, Xc, iu, xu, xv,
-                          rd, ju, jv);
+        ba_project_dist<kDist>(d.cams + 16 * (long long)slot, cam_dist + kParams * (long long)slot, X, Y, Xc, iu, xu, xv, rd, ju, jv);
 #pragma unroll
-        for (int i = 0; i < N; ++i) ba_jtheta_radial(mask, rd.jt, i, tu[i], tv[i]);
+        for (int i = 0; i < N; ++i) ba_jtheta_dist<kDist>(mask, rd.jt, i, tu[i], tv[i]);
       } else {
         double x, y;
         ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
@@ -779,19 +865,21 @@ struct BaBorderLane {
 // One lane's additions for the usable observation o of camera a (its group ga or -1, its point j, y as ba_prepare left it).
 // With a loss the column of J_theta is multiplied by obs_w[o]; obs_lin and T carry the weight already.
 // kRadial: the row block is B_a [6][6 G], entry idx as g = idx / 36, r = idx % 36 / 6, i = idx % 6, and obs_xn is obs_jt.
-template <bool kLoss, bool kRadial = false>
+// kBaDistOpencv: B_a [6][8 G], g = idx / 48, r = idx % 48 / 8, i = idx % 8, obs_jt [total][10].
+template <bool kLoss, int kDist = kBaDistNone>
 __host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, const BaGroups& gr, const double* __restrict__ obs_xn,
                                                           const double* __restrict__ obs_w, const double* __restrict__ T, int ga, int o,
                                                           int j, int lane, const double* y, BaBorderLane& s) {
-  constexpr int N = kRadial ? 6 : 4;
+  constexpr bool kRadial = kDist != kBaDistNone;
+  constexpr int N = ba_dist_unknowns(kDist), kJt = ba_dist_jt(kDist);
   const int G = gr.n_groups;
   const double sw = kLoss ? obs_w[o] : 1.0;
   const double* lin = l.obs_lin + (long long)o * kBaLin;
   const unsigned mask = ga >= 0 ? gr.intr_mask[ga] : 0u;
-  double jt[kBaJt];
+  double jt[kJt];
   if (kRadial) {
 #pragma unroll
-    for (int k = 0; k < kBaJt; ++k) jt[k] = obs_xn[kBaJt * (long long)o + k];
+    for (int k = 0; k < kJt; ++k) jt[k] = obs_xn[kJt * (long long)o + k];
   } else {
     jt[0] = obs_xn[2 * (long long)o], jt[1] = obs_xn[2 * (long long)o + 1];
   }
@@ -802,7 +890,7 @@ __host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, con
     const int g = idx / (6 * N), r = idx % (6 * N) / N, i = idx % N;
     if (g == ga) {
       double tu, tv;
-      if (kRadial) ba_jtheta_radial(mask, jt, i, tu, tv);
+      if constexpr (kRadial) ba_jtheta_dist<kDist>(mask, jt, i, tu, tv);
       else ba_jtheta(mask, jt[0], jt[1], i, tu, tv);
       if (kLoss) tu = sw * tu, tv = sw * tv;
       s.jt[k] += lin[r] * tu + lin[6 + r] * tv;
@@ -846,7 +934,10 @@ __host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const
     const double* e = dtheta + N * g;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      if (N == 6) s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3] + t[12 + k] * e[4] + t[15 + k] * e[5];
+      if (N == 8)
+        s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3] + t[12 + k] * e[4] + t[15 + k] * e[5] + t[18 + k] * e[6] +
+                t[21 + k] * e[7];
+      else if (N == 6) s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3] + t[12 + k] * e[4] + t[15 + k] * e[5];
       else s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3];
     }
   }
@@ -887,6 +978,31 @@ __host__ __device__ __forceinline__ bool ba_camera_step_radial(const double* __r
   out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
   out_dist[0] = k1, out_dist[1] = k2;
   return ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0 && ba_finite(k1) && ba_finite(k2);
+}
+
+// The same with eight unknowns per group: (k1, k2, p1, p2) of dist[4] += dtheta_4 .. dtheta_7 into out_dist[4] (copied where the
+// intrinsics are held) -> focal lengths finite and positive, all four distortion numbers finite.
+__host__ __device__ __forceinline__ bool ba_camera_step_opencv(const double* __restrict__ cam, const double* __restrict__ dist,
+                                                               const double* __restrict__ e, const BaGroups& gr, int a,
+                                                               const double* __restrict__ dtheta, double* __restrict__ out,
+                                                               double* __restrict__ out_dist) {
+  ba_pose_step(cam, e, out);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out_dist[i] = dist[i];
+  const int g = ba_group_of(gr, a);
+  if (g < 0) return true;
+  const double* th = dtheta + 8 * g;
+  const bool tied = (gr.intr_mask[g] >> 4) & 1u;
+  const double fx = cam[12] + th[0], fy = cam[13] + (tied ? th[0] : th[1]);
+  out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
+  bool valid = ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const double k = dist[i] + th[4 + i];
+    out_dist[i] = k;
+    valid = valid && ba_finite(k);
+  }
+  return valid;
 }
 
 // kLoss = false: loss and out_obs_w are absent and not read (vc_ba_linearize_points).  What a loss adds comes last in the three
@@ -1070,9 +1186,10 @@ __global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(const double* 
   if (out_valid) out_valid[a] = valid ? 1 : 0;
 }
 
-// ---- the kernels of the _radial entry points: the routines above under kRadial, every one with the loss (VC_BA_LOSS_TRIVIAL
-// gives rho = s and sw = 1, and a product with 1.0 is exact) ------------------------------------------------------------------------
-__global__ __launch_bounds__(kBaWave) void ba_linearize_points_radial_kernel(BaProblem d, const double* __restrict__ cam_dist, double lambda,
+// ---- the kernels of the _radial and _opencv entry points: the routines above under kDist = kBaDistRadial and kBaDistOpencv,
+// every one with the loss (VC_BA_LOSS_TRIVIAL gives rho = s and sw = 1, and a product with 1.0 is exact) --------------------------
+template <int kDist>
+__global__ __launch_bounds__(kBaWave) void ba_linearize_points_dist_kernel(BaProblem d, const double* __restrict__ cam_dist, double lambda,
                                                                              BaLoss loss, double* __restrict__ out_vinv,
                                                                              double* __restrict__ out_gp, double* __restrict__ out_cost,
                                                                              int32_t* __restrict__ out_count, uint8_t* __restrict__ out_obs_ok,
@@ -1080,7 +1197,7 @@ __global__ __launch_bounds__(kBaWave) void ba_linearize_points_radial_kernel(BaP
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (j >= d.n_points) return;
   double vinv[6], gp[3], cost;
-  const int count = ba_linearize_point<true, true>(d, loss, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin, out_obs_w, cam_dist);
+  const int count = ba_linearize_point<true, kDist>(d, loss, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin, out_obs_w, cam_dist);
 #pragma unroll
   for (int k = 0; k < 6; ++k) out_vinv[6 * j + k] = vinv[k];
 #pragma unroll
@@ -1089,26 +1206,29 @@ __global__ __launch_bounds__(kBaWave) void ba_linearize_points_radial_kernel(BaP
   out_count[j] = count;
 }
 
-__global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_radial_kernel(BaProblem d, BaLinear l, BaGroups gr,
+template <int kDist>
+__global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_dist_kernel(BaProblem d, BaLinear l, BaGroups gr,
                                                                                  const double* __restrict__ cam_dist,
                                                                                  const double* __restrict__ obs_w, double* __restrict__ out_obs_jt,
                                                                                  double* out_T, double* __restrict__ out_terms) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (j < d.n_points) ba_linearize_point_intrinsics<true, true>(d, l, gr, obs_w, (int)j, out_obs_jt, out_T, out_terms, cam_dist);
+  if (j < d.n_points) ba_linearize_point_intrinsics<true, kDist>(d, l, gr, obs_w, (int)j, out_obs_jt, out_T, out_terms, cam_dist);
 }
 
-__global__ __launch_bounds__(kBaWave) void ba_border_system_radial_kernel(const double* __restrict__ sums, BaGroups gr, double lambda,
-                                                                          double* __restrict__ out_C, double* __restrict__ out_h,
-                                                                          uint8_t* __restrict__ out_free) {
-  const int m = 6 * gr.n_groups;
-  for (int idx = threadIdx.x; idx < m * m; idx += kBaWave) out_C[idx] = ba_border_c<6>(sums, gr, lambda, idx / m, idx % m);
+template <int N>
+__global__ __launch_bounds__(kBaWave) void ba_border_system_dist_kernel(const double* __restrict__ sums, BaGroups gr, double lambda,
+                                                                        double* __restrict__ out_C, double* __restrict__ out_h,
+                                                                        uint8_t* __restrict__ out_free) {
+  const int m = N * gr.n_groups;
+  for (int idx = threadIdx.x; idx < m * m; idx += kBaWave) out_C[idx] = ba_border_c<N>(sums, gr, lambda, idx / m, idx % m);
   for (int row = threadIdx.x; row < m; row += kBaWave) {
-    out_h[row] = ba_border_h<6>(sums, gr, row);
-    out_free[row] = ba_theta_free<6>(sums, gr, row / 6, row % 6) ? 1 : 0;
+    out_h[row] = ba_border_h<N>(sums, gr, row);
+    out_free[row] = ba_theta_free<N>(sums, gr, row / N, row % N) ? 1 : 0;
   }
 }
 
-__global__ __launch_bounds__(kBaWave) void ba_reduce_border_radial_kernel(BaProblem d, BaLinear l, BaGroups gr,
+template <int kDist>
+__global__ __launch_bounds__(kBaWave) void ba_reduce_border_dist_kernel(BaProblem d, BaLinear l, BaGroups gr,
                                                                           const int32_t* __restrict__ cam_offsets,
                                                                           const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
                                                                           const double* __restrict__ obs_jt, const double* __restrict__ obs_w,
@@ -1120,17 +1240,18 @@ __global__ __launch_bounds__(kBaWave) void ba_reduce_border_radial_kernel(BaProb
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) s.jt[k] = s.yt[k] = 0.0;
   ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
-                 [&](int o, int j, int, int, const double* y) { ba_border_update<true, true>(l, gr, obs_jt, obs_w, T, ga, o, j, lane, y, s); });
-  ba_border_finish<6>(gr.n_groups, a, lane, s, out_B);
+                 [&](int o, int j, int, int, const double* y) { ba_border_update<true, kDist>(l, gr, obs_jt, obs_w, T, ga, o, j, lane, y, s); });
+  ba_border_finish<ba_dist_unknowns(kDist)>(gr.n_groups, a, lane, s, out_B);
 }
 
-__global__ __launch_bounds__(kBaWave) void ba_step_points_radial_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
+template <int N>
+__global__ __launch_bounds__(kBaWave) void ba_step_points_dist_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
                                                                         const double* __restrict__ dc, const double* __restrict__ dtheta,
                                                                         double* __restrict__ out_points, double* __restrict__ out_dx) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (j >= d.n_points) return;
   double dX[3];
-  ba_point_step<6>(d, l, T, n_groups, dc, dtheta, (int)j, dX);
+  ba_point_step<N>(d, l, T, n_groups, dc, dtheta, (int)j, dX);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     out_dx[3 * j + k] = dX[k];
@@ -1138,13 +1259,18 @@ __global__ __launch_bounds__(kBaWave) void ba_step_points_radial_kernel(BaProble
   }
 }
 
-__global__ __launch_bounds__(kBaWave) void ba_step_cameras_radial_kernel(const double* __restrict__ cams, const double* __restrict__ cam_dist,
+template <int kDist>
+__global__ __launch_bounds__(kBaWave) void ba_step_cameras_dist_kernel(const double* __restrict__ cams, const double* __restrict__ cam_dist,
                                                                          int n_cams, BaGroups gr, const double* __restrict__ dc,
                                                                          const double* __restrict__ dtheta, double* __restrict__ out_cams,
                                                                          double* __restrict__ out_dist, uint8_t* __restrict__ out_valid) {
   const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (a >= n_cams) return;
-  out_valid[a] = ba_camera_step_radial(cams + 16 * a, cam_dist + 2 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a, out_dist + 2 * a) ? 1 : 0;
+  bool valid;
+  if constexpr (kDist == kBaDistOpencv)
+    valid = ba_camera_step_opencv(cams + 16 * a, cam_dist + 4 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a, out_dist + 4 * a);
+  else valid = ba_camera_step_radial(cams + 16 * a, cam_dist + 2 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a, out_dist + 2 * a);
+  out_valid[a] = valid ? 1 : 0;
 }
 
 // The two kernels of a step; vc_ba_step has no groups: then T, dtheta, cam_group and out_valid are absent and none is read.
@@ -1227,6 +1353,103 @@ int ba_launch_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, 
 
 constexpr int ba_reduce_lds_bytes(int n_cams) { return 36 * n_cams * (int)sizeof(double); }
 static_assert(ba_reduce_lds_bytes(VC_BA_MAX_CAMS) + (int)sizeof(BaBatch) <= 160 * 1024, "the row block of VC_BA_MAX_CAMS cameras must fit the CU's LDS");
+
+// ---- the distortion: the checks of the entry points above, cam_dist and the loss among them, once for the _radial and the _opencv
+// entry points ----------------------------------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int ba_dist_max_groups(int dist) { return dist == kBaDistOpencv ? VC_BA_MAX_GROUPS_OPENCV : VC_BA_MAX_GROUPS_RADIAL; }
+
+template <int kDist>
+int ba_launch_linearize_points_dist(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
+                                  int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                                  int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
+                                  uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
+  if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (n_points == 0) return VC_OK;
+  if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_dist || !const_mask)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin || !out_obs_w)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_linearize_points_dist_kernel<kDist>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, cam_dist, lambda, BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok,
+                     out_obs_lin, out_obs_w);
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
+  return vc::check_launch();
+}
+
+template <int kDist>
+int ba_launch_linearize_intrinsics_dist(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
+                                      const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets,
+                                      const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
+                                      const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
+                                      double* out_terms, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (n_points == 0 || n_groups == 0) return VC_OK;
+  if (n_groups > ba_dist_max_groups(kDist)) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_dist || !cam_group)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !obs_w || !out_obs_jt)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  hipLaunchKernelGGL(ba_linearize_intrinsics_dist_kernel<kDist>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, cam_dist, obs_w,
+                     out_obs_jt, out_T, out_terms);
+  return vc::check_launch();
+}
+
+template <int kDist>
+int ba_launch_reduce_border_dist(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
+                               const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs,
+                               const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
+                               const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
+                               double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (n_groups == 0) return VC_OK;
+  if (n_groups > ba_dist_max_groups(kDist) || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
+  if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_jt || !obs_w)) return VC_ERR_INVALID_ARG;
+  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
+  constexpr int N = ba_dist_unknowns(kDist);
+  const BaGroups gr{cam_group, intr_mask, n_groups};
+  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows<N>(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
+                     out_sums);
+  hipLaunchKernelGGL(ba_border_system_dist_kernel<N>, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h,
+                     out_free);
+  if (n_cams > 0) {
+    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
+    hipLaunchKernelGGL(ba_reduce_border_dist_kernel<kDist>, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
+                       BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_jt, obs_w, T, out_B);
+  }
+  return vc::check_launch();
+}
+
+template <int kDist>
+int ba_launch_step_dist(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                      const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
+                      const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
+                      double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
+  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
+  if (n_cams == 0 && n_points == 0) return VC_OK;
+  if (n_groups > ba_dist_max_groups(kDist)) return VC_ERR_UNSUPPORTED;
+  if (n_groups > 0 && (!intr_mask || !dtheta)) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || !cam_dist || !cam_group || !dc || !out_cams || !out_dist || !out_valid)) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx || (n_groups > 0 && !T))) return VC_ERR_INVALID_ARG;
+  if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
+  constexpr int N = ba_dist_unknowns(kDist);
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  const BaGroups gr{cam_group, intr_mask, n_groups};
+  if (n_points > 0)
+    hipLaunchKernelGGL(ba_step_points_dist_kernel<N>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       d, BaLinear{vinv, gp, obs_ok, obs_lin}, T, n_groups, dc, dtheta, out_points, out_dx);
+  if (n_cams > 0)
+    hipLaunchKernelGGL(ba_step_cameras_dist_kernel<kDist>, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       cams, cam_dist, n_cams, gr, dc, dtheta, out_cams, out_dist, out_valid);
+  return vc::check_launch();
+}
 
 }  // namespace
 
@@ -1364,24 +1587,14 @@ int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_gro
                         BaGroups{cam_group, intr_mask, n_groups}, T, dc, dtheta, out_cams, out_points, out_dx, out_valid, stream);
 }
 
-// ---- the distortion: the checks of the entry points above, cam_dist and the loss among them ---------------------------------------
+// ---- the distortion: the _radial and the _opencv entry points, two instances of the launchers above --------------------------------
 int vc_ba_linearize_points_radial(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
                                   int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
                                   int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
                                   uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
-  if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
-  if (n_points == 0) return VC_OK;
-  if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_dist || !const_mask)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin || !out_obs_w)) return VC_ERR_INVALID_ARG;
-  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
-  hipLaunchKernelGGL(ba_linearize_points_radial_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                     (hipStream_t)stream, d, cam_dist, lambda, BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok,
-                     out_obs_lin, out_obs_w);
-  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
-  return vc::check_launch();
+  return ba_launch_linearize_points_dist<kBaDistRadial>(cams, n_cams, cam_dist, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda, loss,
+                                             loss_scale, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, out_obs_w, out_total_cost,
+                                             stream);
 }
 
 int vc_ba_linearize_intrinsics_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
@@ -1389,18 +1602,8 @@ int vc_ba_linearize_intrinsics_radial(const double* cams, int n_cams, const doub
                                       const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
                                       const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
                                       double* out_terms, vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
-  if (n_points == 0 || n_groups == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS_RADIAL) return VC_ERR_UNSUPPORTED;
-  if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_dist || !cam_group)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !obs_w || !out_obs_jt)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
-  hipLaunchKernelGGL(ba_linearize_intrinsics_radial_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, cam_dist, obs_w,
-                     out_obs_jt, out_T, out_terms);
-  return vc::check_launch();
+  return ba_launch_linearize_intrinsics_dist<kBaDistRadial>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total,
+                                                 loss, loss_scale, vinv, gp, obs_ok, obs_lin, obs_w, out_obs_jt, out_T, out_terms, stream);
 }
 
 int vc_ba_reduce_border_radial(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
@@ -1408,48 +1611,53 @@ int vc_ba_reduce_border_radial(int n_cams, const int32_t* cam_group, int n_group
                                const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
                                const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
                                double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
-  if (n_groups == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS_RADIAL || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
-  if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_jt || !obs_w)) return VC_ERR_INVALID_ARG;
-  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
-  const BaGroups gr{cam_group, intr_mask, n_groups};
-  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows<6>(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
-                     out_sums);
-  hipLaunchKernelGGL(ba_border_system_radial_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h,
-                     out_free);
-  if (n_cams > 0) {
-    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
-    hipLaunchKernelGGL(ba_reduce_border_radial_kernel, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
-                       BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_jt, obs_w, T, out_B);
-  }
-  return vc::check_launch();
+  return ba_launch_reduce_border_dist<kBaDistRadial>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
+                                          obs_point, lambda, loss, loss_scale, vinv, obs_ok, obs_lin, obs_jt, obs_w, T, terms, out_sums, out_B,
+                                          out_C, out_h, out_free, stream);
 }
 
 int vc_ba_step_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
                       const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
                       const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
                       double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_cams == 0 && n_points == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS_RADIAL) return VC_ERR_UNSUPPORTED;
-  if (n_groups > 0 && (!intr_mask || !dtheta)) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_dist || !cam_group || !dc || !out_cams || !out_dist || !out_valid)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx || (n_groups > 0 && !T))) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
-  const BaGroups gr{cam_group, intr_mask, n_groups};
-  if (n_points > 0)
-    hipLaunchKernelGGL(ba_step_points_radial_kernel, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       d, BaLinear{vinv, gp, obs_ok, obs_lin}, T, n_groups, dc, dtheta, out_points, out_dx);
-  if (n_cams > 0)
-    hipLaunchKernelGGL(ba_step_cameras_radial_kernel, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       cams, cam_dist, n_cams, gr, dc, dtheta, out_cams, out_dist, out_valid);
-  return vc::check_launch();
+  return ba_launch_step_dist<kBaDistRadial>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
+                                 obs_ok, obs_lin, T, dc, dtheta, out_cams, out_dist, out_points, out_dx, out_valid, stream);
+}
+
+int vc_ba_linearize_points_opencv(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
+                                  int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                                  int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
+                                  uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
+  return ba_launch_linearize_points_dist<kBaDistOpencv>(cams, n_cams, cam_dist, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda, loss,
+                                             loss_scale, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, out_obs_w, out_total_cost,
+                                             stream);
+}
+
+int vc_ba_linearize_intrinsics_opencv(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
+                                      const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets,
+                                      const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
+                                      const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
+                                      double* out_terms, vc_stream_t stream) {
+  return ba_launch_linearize_intrinsics_dist<kBaDistOpencv>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total,
+                                                 loss, loss_scale, vinv, gp, obs_ok, obs_lin, obs_w, out_obs_jt, out_T, out_terms, stream);
+}
+
+int vc_ba_reduce_border_opencv(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
+                               const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs,
+                               const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
+                               const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
+                               double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream) {
+  return ba_launch_reduce_border_dist<kBaDistOpencv>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
+                                          obs_point, lambda, loss, loss_scale, vinv, obs_ok, obs_lin, obs_jt, obs_w, T, terms, out_sums, out_B,
+                                          out_C, out_h, out_free, stream);
+}
+
+int vc_ba_step_opencv(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
+                      const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
+                      const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
+                      double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
+  return ba_launch_step_dist<kBaDistOpencv>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
+                                 obs_ok, obs_lin, T, dc, dtheta, out_cams, out_dist, out_points, out_dx, out_valid, stream);
 }
 
 }  // extern "C"

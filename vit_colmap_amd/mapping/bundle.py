@@ -15,8 +15,9 @@ With `solver` "pcg" ("The solver" in §4.2k; specification: tests/util_bundle_pc
 solved by preconditioned conjugate gradients on vc_ba_camera_blocks and vc_ba_schur_product, for any number of cameras, poses
 and points only.
 The same adjustment after every growth round, with the tracks re-evaluated, is mapping/rounds.py (§4.2m).
-Still missing on the way to a mapper: local adjustment, merging of points; among the
-intrinsics OPENCV's tangential terms.
+With `tangential` ("The tangential terms" in §4.2k; specification: tests/util_bundle_opencv.py) OPENCV cameras are adjusted too:
+`cam_dist` then carries (k1, k2, p1, p2), the loop runs the _opencv entry points and the border has eight unknowns per group.
+Still missing on the way to a mapper: local adjustment, merging of points.
 
 Where the work runs
   HIP     per iteration vc_ba_linearize_points (one point per lane: residuals, Jacobians, V^-1, the cost), vc_ba_reduce_cameras
@@ -37,7 +38,7 @@ from ..matching._common import MAX_ERROR
 from ..matching.essential import rot_to_quat
 from .absolute_pose import FILTER_MIN_TRI_ANGLE
 from .grow import build_sparse_model
-from .seed import SparseModel, _pixel_errors, _pixel_errors_radial, _read_database
+from .seed import SparseModel, _pixel_errors, _pixel_errors_opencv, _pixel_errors_radial, _read_database
 
 logger = logging.getLogger(__name__)
 
@@ -78,7 +79,7 @@ class _Buffers:
     """The outputs of one vc_ba_linearize_points call (with a loss: of vc_ba_linearize_points_loss, obs_w among them); two of
     them alternate between the current parameters and the candidate."""
 
-    def __init__(self, torch, n_cams, n_points, total, device, with_loss=False, with_dist=False):
+    def __init__(self, torch, n_cams, n_points, total, device, with_loss=False, with_dist=0):
         f64 = dict(dtype=torch.float64, device=device)
         self.cams, self.points = torch.zeros((n_cams, 16), **f64), torch.zeros((n_points, 3), **f64)
         self.vinv, self.gp, self.cost = torch.zeros((n_points, 6), **f64), torch.zeros((n_points, 3), **f64), torch.zeros(n_points, **f64)
@@ -89,7 +90,8 @@ class _Buffers:
         if with_loss or with_dist:
             self.obs_w = torch.zeros(total, **f64)
         if with_dist:
-            self.dist = torch.zeros((n_cams, 2), **f64)              # (k1, k2) beside the camera rows (the _radial entry points)
+            # (k1, k2) beside the camera rows (the _radial entry points), or (k1, k2, p1, p2) (the _opencv ones): with_dist columns
+            self.dist = torch.zeros((n_cams, int(with_dist)), **f64)
 
 
 def check_loss(loss, loss_scale):
@@ -189,6 +191,9 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     slot is in one group whose six intrinsics are all held.  The report gains `cam_dist`, the adjusted (n_cams, 2), and its
     `intrinsics` are (n_groups, 6): (fx, fy, cx, cy, k1, k2).  Raises ValueError above VC_BA_MAX_GROUPS_RADIAL groups.  Without
     cam_dist exactly the calls and the report described above.
+    cam_dist float64 (n_cams, 4): (k1, k2, p1, p2) of every slot ("The tangential terms" in §4.2k; COLMAP's OPENCV).  The loop runs
+    the _opencv entry points; bit 7 of a group's mask holds p1 and p2 together; the report's `cam_dist` is (n_cams, 4) and its
+    `intrinsics` are (n_groups, 8): (fx, fy, cx, cy, k1, k2, p1, p2).  Raises ValueError above VC_BA_MAX_GROUPS_OPENCV groups.
     solver "dense" or "pcg" ("The solver" in §4.2k).  "dense" is everything above, the ValueError above VC_BA_MAX_CAMS included.
     "pcg" solves S dc = -g by preconditioned conjugate gradients (block-Jacobi, |r| <= pcg_tol |r_0| or pcg_max_iterations
     products) on vc_ba_camera_blocks and vc_ba_schur_product: S is not allocated and there is no limit on the cameras; a solve
@@ -218,12 +223,13 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     radial = cam_dist is not None
     if radial:
         cam_dist = np.ascontiguousarray(cam_dist, np.float64)
-        if cam_dist.shape != (n_cams, 2):
-            raise ValueError("bundle_adjust needs cam_dist (n_cams, 2): k1, k2 of every camera slot")
+        if cam_dist.shape not in ((n_cams, 2), (n_cams, 4)):
+            raise ValueError("bundle_adjust needs cam_dist (n_cams, 2): k1, k2 of every camera slot, or (n_cams, 4): k1, k2, p1, p2")
         if cam_group is None and intr_mask is None:
-            from .bundle_intr import HOLD_ALL_RADIAL
+            from .bundle_intr import HOLD_ALL_OPENCV, HOLD_ALL_RADIAL
 
-            cam_group, intr_mask = np.zeros(n_cams, np.int32), np.array([HOLD_ALL_RADIAL], np.uint8)
+            cam_group = np.zeros(n_cams, np.int32)
+            intr_mask = np.array([HOLD_ALL_OPENCV if cam_dist.shape[1] == 4 else HOLD_ALL_RADIAL], np.uint8)
     if cam_group is not None or intr_mask is not None:
         if cam_group is None or intr_mask is None:
             raise ValueError("bundle_adjust needs cam_group and intr_mask together")
@@ -245,7 +251,8 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
     cam_offsets, cam_obs, obs_point = (on_device(a) for a in camera_index(obs_cam, offsets, n_cams))
     d_offsets, d_obs_cam, d_obs_xy, d_mask = on_device(offsets), on_device(obs_cam), on_device(obs_xy), on_device(const_mask)
     free = on_device(np.array([[not (int(m) >> i) & 1 for i in range(6)] for m in const_mask], bool).reshape(-1))
-    cur, cand = (_Buffers(torch, n_cams, n_points, total, dev, with_loss=loss_kind != 0, with_dist=radial) for _ in range(2))
+    cur, cand = (_Buffers(torch, n_cams, n_points, total, dev, with_loss=loss_kind != 0, with_dist=cam_dist.shape[1] if radial else 0)
+                 for _ in range(2))
     cur.cams.copy_(on_device(cams)), cur.points.copy_(on_device(points))
     if radial:
         cur.dist.copy_(on_device(cam_dist))
@@ -259,10 +266,11 @@ def bundle_adjust(cams, points, offsets, obs_cam, obs_xy, const_mask, device="cu
 
     def linearize(b, lam):
         if radial:
-            _lib.check(lib.vc_ba_linearize_points_radial(p(b.cams), n_cams, p(b.dist), p(d_mask), p(b.points), n_points, p(d_offsets),
-                                                         p(d_obs_cam), p(d_obs_xy), total, float(lam), loss_kind, loss_scale, p(b.vinv),
-                                                         p(b.gp), p(b.cost), p(b.count), p(b.obs_ok), p(b.obs_lin), p(b.obs_w),
-                                                         p(b.total_cost), stream), "vc_ba_linearize_points_radial")
+            entry = "vc_ba_linearize_points_opencv" if cam_dist.shape[1] == 4 else "vc_ba_linearize_points_radial"
+            _lib.check(getattr(lib, entry)(p(b.cams), n_cams, p(b.dist), p(d_mask), p(b.points), n_points, p(d_offsets),
+                                           p(d_obs_cam), p(d_obs_xy), total, float(lam), loss_kind, loss_scale, p(b.vinv),
+                                           p(b.gp), p(b.cost), p(b.count), p(b.obs_ok), p(b.obs_lin), p(b.obs_w),
+                                           p(b.total_cost), stream), entry)
             return
         if loss_kind != 0:
             _lib.check(lib.vc_ba_linearize_points_loss(p(b.cams), n_cams, p(d_mask), p(b.points), n_points, p(d_offsets), p(d_obs_cam),
@@ -348,7 +356,8 @@ def _wide(X, centres, tan2=MIN_TRI_ANGLE_TAN2):
 
 def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
                          grown=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False,
-                         known_distortion=False, undistort_fn=None, solver="dense", split_tracks=False, split_fn=None) -> SparseModel:
+                         known_distortion=False, undistort_fn=None, solver="dense", split_tracks=False, split_fn=None,
+                         tangential=False) -> SparseModel:
     """Read a matched database -> the grown model (build_sparse_model, or `grown` where the caller has built it already; it
     is not changed), adjusted once over all poses and points, rescaled to a unit baseline of the initial pair and filtered.
     Raises the seed model's ValueErrors unchanged.  `bundle_fn(cams, points, offsets, obs_cam, obs_xy, const_mask, device) ->
@@ -378,9 +387,17 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     `solver` ("The solver" in §4.2k): "dense", exactly the calls described above, or "pcg": bundle_fn is then also given
     solver="pcg", `stats()["bundle_adjustment"]` carries solver and pcg_iterations, and there is no limit on the registered images.
     With refine_focal_length, refine_distortion or known_distortion "pcg" raises ValueError: they add a border to the system or
-    take the _radial entry points, which need the dense solver.  Raises ValueError for an unknown solver.
+    take the _radial (or _opencv) entry points, which need the dense solver.  Raises ValueError for an unknown solver.
     `split_tracks`, `split_fn` (§4.2n) as in build_sparse_model, which is given them only where the flag is on and `grown` is not
-    given; the model keeps the grown model's split_components and split_points either way."""
+    given; the model keeps the grown model's split_components and split_points either way.
+    `tangential` ("The tangential terms" in §4.2k): build_sparse_model is given it, so OPENCV cameras are mapped, and where a
+    registered camera is OPENCV the adjustment takes the four-number path: cam_dist= is (n_cams, 4), (k1, k2, p1, p2) of every slot
+    (p = 0 for the other models), the groups carry bit 7 (HOLD_TANGENTIAL: p1 and p2 held) beside bits 5 and 6, and the limit is
+    VC_BA_MAX_GROUPS_OPENCV.  With refine_distortion an OPENCV camera frees k1, k2, p1 and p2 and gets them back in params[4:8];
+    SIMPLE_RADIAL and RADIAL cameras beside it keep bit 7 and their p at 0, every other model holds all four; `intrinsics` has eight
+    numbers per camera.  With known_distortion alone the known four are held; with refine_focal_length alone the groups carry bits
+    5, 6 and 7.  The filter and `error` use the full distorted projection.  Where no registered camera is OPENCV, and with the flag
+    off, exactly the calls described above."""
     bundle_fn = bundle_fn or bundle_adjust
     check_loss(loss, loss_scale)
     check_solver(solver)
@@ -393,17 +410,24 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
         known_args = dict(known_distortion=True, undistort_fn=undistort_fn) if known_distortion else {}
         if split_tracks:
             known_args.update(split_tracks=True, split_fn=split_fn)
+        if tangential:
+            known_args.update(tangential=True)
         grown = build_sparse_model(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, **known_args)
     ids, pids = sorted(grown.images), sorted(grown.points3D)
     slot = {i: s for s, i in enumerate(ids)}
     known_dist = None
+    # the four-number path ("The tangential terms" in §4.2k): only where a registered camera is OPENCV
+    opencv = bool(tangential) and any(grown.cameras[grown.images[i]["camera_id"]].model == "OPENCV" for i in ids)
+    n_dist = 4 if opencv else 2
     if known_distortion:
         from ..matching.undistort import camera_calibration
 
         calibration = {i: camera_calibration(grown.cameras[grown.images[i]["camera_id"]]) for i in ids}
         K = {i: c[0] for i, c in calibration.items()}
         if any(c[1].any() for c in calibration.values()):
-            known_dist = np.array([calibration[i][1][:2] for i in ids], np.float64).reshape(-1, 2)
+            known_dist = np.array([calibration[i][1][:n_dist] for i in ids], np.float64).reshape(-1, n_dist)
+    elif opencv:
+        _, _, K, _, _ = _read_database(database_path, tangential=True)
     else:
         _, _, K, _, _ = _read_database(database_path)
     cams = np.stack([np.concatenate([_quat_to_rot(grown.images[i]["qvec"]).reshape(9), np.asarray(grown.images[i]["tvec"], np.float64),
@@ -423,19 +447,23 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     dist = None
     if refine_distortion:
         from .. import _lib
-        from .bundle_intr import (HOLD_CX, HOLD_CY, HOLD_FX, HOLD_FY, HOLD_K1, HOLD_K2, REFINE_MAX_ITERATIONS, TIED, has_one_focal,
-                                  radial_parameters)
+        from .bundle_intr import (HOLD_CX, HOLD_CY, HOLD_FX, HOLD_FY, HOLD_K1, HOLD_K2, HOLD_TANGENTIAL, REFINE_MAX_ITERATIONS, TIED,
+                                  has_one_focal, is_opencv, radial_parameters)
 
         cids = sorted({grown.images[i]["camera_id"] for i in ids})
         n_radial = [radial_parameters(grown.cameras[c]) for c in cids]
-        if not any(n_radial):
+        free_all = [opencv and is_opencv(grown.cameras[c]) for c in cids]       # an OPENCV camera frees k1, k2, p1 and p2
+        if not any(n_radial) and not any(free_all):
             raise ValueError("refine_distortion: no registered camera has a radial parameter to refine; the camera models with one are "
-                             "SIMPLE_RADIAL (k) and RADIAL (k1, k2)")
-        if len(cids) > _lib.VC_BA_MAX_GROUPS_RADIAL:
+                             "SIMPLE_RADIAL (k) and RADIAL (k1, k2)" + (" and OPENCV (k1, k2, p1, p2)" if tangential else ""))
+        if opencv and len(cids) > _lib.VC_BA_MAX_GROUPS_OPENCV:
+            raise ValueError(f"refine_distortion: the registered images have {len(cids)} cameras, the OPENCV border kernels hold at most "
+                             f"{_lib.VC_BA_MAX_GROUPS_OPENCV} groups of intrinsics (VC_BA_MAX_GROUPS_OPENCV)")
+        if not opencv and len(cids) > _lib.VC_BA_MAX_GROUPS_RADIAL:
             raise ValueError(f"refine_distortion: the registered images have {len(cids)} cameras, the radial border kernels hold at most "
                              f"{_lib.VC_BA_MAX_GROUPS_RADIAL} groups of intrinsics (VC_BA_MAX_GROUPS_RADIAL)")
-        for c, n in zip(cids, n_radial):
-            if not n:
+        for c, n, every in zip(cids, n_radial, free_all):
+            if not n and not every:
                 logger.info("refine_distortion: camera %d is %s, which has no radial parameter here; its k1 and k2 stay held", c,
                             grown.cameras[c].model)
         cam_group = np.array([cids.index(grown.images[i]["camera_id"]) for i in ids], np.int32)
@@ -443,16 +471,22 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
         focal = [HOLD_CX | HOLD_CY | (TIED if has_one_focal(grown.cameras[c]) else 0) if refine_focal_length else
                  HOLD_FX | HOLD_FY | HOLD_CX | HOLD_CY for c in cids]
         intr_mask = np.array([f | (HOLD_K1 if n < 1 else 0) | (HOLD_K2 if n < 2 else 0) for f, n in zip(focal, n_radial)], np.uint8)
-        group_dist = np.array([[float(v) for v in list(grown.cameras[c].params[3:3 + n]) + [0.0] * (2 - n)] for c, n in zip(cids, n_radial)])
+        group_dist = np.array([[float(v) for v in list(grown.cameras[c].params[3:3 + n]) + [0.0] * (n_dist - n)] for c, n in zip(cids, n_radial)])
+        if opencv:                                                   # every model but OPENCV keeps bit 7 and its p at 0
+            intr_mask = np.array([f if every else m | HOLD_TANGENTIAL for f, m, every in zip(focal, intr_mask, free_all)], np.uint8)
+            for g, (c, every) in enumerate(zip(cids, free_all)):
+                if every:
+                    group_dist[g] = [float(v) for v in grown.cameras[c].params[4:8]]
         cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group, intr_mask=intr_mask,
                                          max_iterations=REFINE_MAX_ITERATIONS, cam_dist=group_dist[cam_group], **loss_args)
-        dist = np.array(report["cam_dist"], np.float64).reshape(-1, 2)
+        dist = np.array(report["cam_dist"], np.float64).reshape(-1, n_dist)
     elif refine_focal_length:
         from .. import _lib
-        from .bundle_intr import HOLD_CX, HOLD_CY, HOLD_K1, HOLD_K2, REFINE_MAX_ITERATIONS, TIED, has_one_focal
+        from .bundle_intr import HOLD_CX, HOLD_CY, HOLD_K1, HOLD_K2, HOLD_TANGENTIAL, REFINE_MAX_ITERATIONS, TIED, has_one_focal
 
         cids = sorted({grown.images[i]["camera_id"] for i in ids})
         limit, name = ((_lib.VC_BA_MAX_GROUPS, "VC_BA_MAX_GROUPS") if known_dist is None else
+                       (_lib.VC_BA_MAX_GROUPS_OPENCV, "VC_BA_MAX_GROUPS_OPENCV") if opencv else
                        (_lib.VC_BA_MAX_GROUPS_RADIAL, "VC_BA_MAX_GROUPS_RADIAL"))
         if len(cids) > limit:
             raise ValueError(f"refine_focal_length: the registered images have {len(cids)} cameras, the border kernels hold at most "
@@ -464,7 +498,8 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
                                              max_iterations=REFINE_MAX_ITERATIONS, **loss_args)
         else:                                                    # the known k stays held beside the free focal (§4.2l)
             cams, points, report = bundle_fn(cams, points, offsets, obs_cam, obs_xy, mask, device, cam_group=cam_group,
-                                             intr_mask=intr_mask | np.uint8(HOLD_K1 | HOLD_K2), max_iterations=REFINE_MAX_ITERATIONS,
+                                             intr_mask=intr_mask | np.uint8(HOLD_K1 | HOLD_K2 | (HOLD_TANGENTIAL if opencv else 0)),
+                                             max_iterations=REFINE_MAX_ITERATIONS,
                                              cam_dist=known_dist, **loss_args)
             dist = known_dist
     elif known_dist is not None:
@@ -488,9 +523,13 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
     model.cameras = copy.deepcopy(grown.cameras)
     if refine_distortion:
         # the cameras carry the refined k: params[3] of SIMPLE_RADIAL, params[3:5] of RADIAL; the filter and `error` use it
-        for g, (cid, n) in enumerate(zip(cids, n_radial)):
+        # and params[4:8] of OPENCV (k1, k2, p1, p2)
+        for g, (cid, n, every) in enumerate(zip(cids, n_radial, free_all)):
             cam = model.cameras[cid]
-            cam.params = list(cam.params[:3]) + [float(v) for v in report["intrinsics"]["after"][g][4:4 + n]] + list(cam.params[3 + n:])
+            if every:
+                cam.params = list(cam.params[:4]) + [float(v) for v in report["intrinsics"]["after"][g][4:8]] + list(cam.params[8:])
+            else:
+                cam.params = list(cam.params[:3]) + [float(v) for v in report["intrinsics"]["after"][g][4:4 + n]] + list(cam.params[3 + n:])
     if refine_focal_length:
         # the cameras carry the refined focal length(s); the filter below and `error` use the refined K
         for g, cid in enumerate(cids):
@@ -515,7 +554,8 @@ def build_adjusted_model(database_path, device="cuda", two_view_pose_fn=None, es
             err = np.array([_pixel_errors(K[i], row[:9].reshape(3, 3), row[9:12], points[j][None], obs_xy[o][None])[0]
                             for o, row, (i, _) in zip(range(offsets[j], offsets[j + 1]), rows, tracks[j])])
         else:
-            err = np.array([_pixel_errors_radial(K[i], dist[slot[i]], row[:9].reshape(3, 3), row[9:12], points[j][None], obs_xy[o][None])[0]
+            errors = _pixel_errors_opencv if dist.shape[1] == 4 else _pixel_errors_radial
+            err = np.array([errors(K[i], dist[slot[i]], row[:9].reshape(3, 3), row[9:12], points[j][None], obs_xy[o][None])[0]
                             for o, row, (i, _) in zip(range(offsets[j], offsets[j + 1]), rows, tracks[j])])
         keep = err <= MAX_ERROR
         dropped_obs += int((~keep).sum())

@@ -23,7 +23,7 @@ import numpy as np
 
 from ..database.colmap_db import _quat_to_rot
 from .absolute_pose import ABS_POSE_MIN_NUM_INLIERS, estimate_absolute_poses
-from .seed import SparseModel, _observation_errors, _read_database, _seed_model
+from .seed import SparseModel, _database, _observation_errors, _seed_model
 
 SPLIT_MAX_POINTS = 4                 # VC_SPLIT_MAX_POINTS; mapping/triangulate.py, which needs torch, has it too
 
@@ -95,7 +95,7 @@ def _gpu_split(obs_xy, obs_cam, offsets, cams, seeds, node_point, points_xyz, de
 
 
 def _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, known_distortion, undistort_fn, round_fn=None,
-          split_tracks=False, split_fn=None) -> SparseModel:
+          split_tracks=False, split_fn=None, tangential=False) -> SparseModel:
     """The growth loop of build_sparse_model, which states the arguments.  `round_fn(growth)`, if given, is called at the end of
     every round that added a point or an image (mapping/rounds.py) with the loop's state: device, images, K,
     kps (the keypoints the solvers see), ids, slot, comps, slots, initial_pair and, to change in place, poses {image id: (R, t,
@@ -106,7 +106,7 @@ def _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, 
     holds is kept here, and a point that round_fn removes frees its slot."""
     estimate_fn = estimate_fn or estimate_absolute_poses
     triangulate_fn = triangulate_fn or _gpu_triangulate
-    database = _read_database(database_path, True, undistort_fn, device) if known_distortion else _read_database(database_path)
+    database = _database(database_path, device, known_distortion, undistort_fn, tangential)     # `tangential` only where it is on
     images, cameras, K, kps, rows = database[:5]
     known = database[5] if len(database) > 5 else None
     raw = kps if known is None else known["raw"]
@@ -249,7 +249,7 @@ def _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, 
 
 
 def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, known_distortion=False,
-                       undistort_fn=None, split_tracks=False, split_fn=None) -> SparseModel:
+                       undistort_fn=None, split_tracks=False, split_fn=None, tangential=False) -> SparseModel:
     """Read a matched database -> the seed model grown by rounds.  Raises the seed model's ValueErrors unchanged.
     `two_view_pose_fn` and `estimate_fn` as in build_seed_model; `triangulate_fn(obs_xy, obs_cam, offsets, cams, seeds,
     device) -> (xyz, mask, count, error)` on numpy arrays replaces the triangulation launch (tests).
@@ -261,6 +261,8 @@ def build_sparse_model(database_path, device="cuda", two_view_pose_fn=None, esti
     component has and peels new points off the rest, up to SPLIT_MAX_POINTS per component.  Those points take no part in
     registration.  `split_fn(obs_xy, obs_cam, offsets, cams, seeds, node_point, points_xyz, device) -> (node_point, points_xyz,
     count, new, error)` on numpy arrays replaces that launch (tests).  The model's statistics gain split_components (the
-    inconsistent components that took part) and split_points (the points made out of them that the model has)."""
+    inconsistent components that took part) and split_points (the points made out of them that the model has).
+    `tangential` ("The tangential terms" in §4.2k) as in build_seed_model: OPENCV cameras are read as the other models are."""
+    tangential_args = dict(tangential=True) if tangential else {}
     return _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, known_distortion, undistort_fn,
-                 split_tracks=split_tracks, split_fn=split_fn)
+                 split_tracks=split_tracks, split_fn=split_fn, **tangential_args)

@@ -102,7 +102,7 @@ def _round_steps(g, bundle_fn, refine_fn, adjust_args, reports):
 
 def build_mapped_rounds(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
                         refine_fn=None, loss="trivial", loss_scale=1.0, known_distortion=False, undistort_fn=None, solver="dense",
-                        split_tracks=False, split_fn=None):
+                        split_tracks=False, split_fn=None, tangential=False):
     """The model as the rounds leave it, before the tail -> (SparseModel, the round reports).  Arguments as build_mapped_model."""
     check_loss(loss, loss_scale)
     check_solver(solver)
@@ -111,6 +111,8 @@ def build_mapped_rounds(database_path, device="cuda", two_view_pose_fn=None, est
         adjust_args["solver"] = solver
     bundle_fn, refine_fn, reports = bundle_fn or bundle_adjust, refine_fn or _gpu_refine, []
     split_args = dict(split_tracks=True, split_fn=split_fn) if split_tracks else {}
+    if tangential:                                                    # passed on only where it is on, as known_distortion is
+        split_args["tangential"] = True
     model = _grow(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, known_distortion, undistort_fn,
                   round_fn=lambda g: _round_steps(g, bundle_fn, refine_fn, adjust_args, reports), **split_args)
     return model, reports
@@ -118,7 +120,8 @@ def build_mapped_rounds(database_path, device="cuda", two_view_pose_fn=None, est
 
 def build_mapped_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, triangulate_fn=None, bundle_fn=None,
                        refine_fn=None, refine_focal_length=False, loss="trivial", loss_scale=1.0, refine_distortion=False,
-                       known_distortion=False, undistort_fn=None, solver="dense", split_tracks=False, split_fn=None) -> SparseModel:
+                       known_distortion=False, undistort_fn=None, solver="dense", split_tracks=False, split_fn=None,
+                       tangential=False) -> SparseModel:
     """Read a matched database -> the seed model grown by rounds, adjusted and its tracks re-evaluated after every round that
     added a point or an image (the module's header), then build_adjusted_model's tail on that model with every option given:
     one more adjustment (with refine_focal_length / refine_distortion the one that refines them), the rescale to a unit
@@ -131,11 +134,17 @@ def build_mapped_model(database_path, device="cuda", two_view_pose_fn=None, esti
     launch of vc_refine_tracks (tests); `bundle_fn` as in build_adjusted_model, in the rounds given loss= and loss_scale= where
     the loss is not "trivial" and nothing else, so the cap is BA_MAX_ITERATIONS; the other seams as in build_sparse_model.
     `split_tracks`, `split_fn` (§4.2n) as in build_sparse_model: the growth splits its inconsistent components; their points are
-    adjusted with the others, the E-step evaluates each over its own track, and one it removes frees its slot for the next round."""
+    adjusted with the others, the E-step evaluates each over its own track, and one it removes frees its slot for the next round.
+    `tangential` ("The tangential terms" in §4.2k): OPENCV cameras are mapped; the A-steps run on undistorted keypoints and need
+    nothing new, the tail is build_adjusted_model's with the flag."""
     split_args = dict(split_tracks=True, split_fn=split_fn) if split_tracks else {}
+    if tangential:
+        split_args["tangential"] = True
     model, reports = build_mapped_rounds(database_path, device, two_view_pose_fn, estimate_fn, triangulate_fn, bundle_fn, refine_fn,
                                          loss, loss_scale, known_distortion, undistort_fn, solver, **split_args)
     solver_args = {} if solver == "dense" else dict(solver=solver)
+    if tangential:
+        solver_args["tangential"] = True
     mapped = build_adjusted_model(database_path, device, bundle_fn=bundle_fn, grown=model, refine_focal_length=refine_focal_length,
                                   loss=loss, loss_scale=loss_scale, refine_distortion=refine_distortion, known_distortion=known_distortion,
                                   **solver_args)

@@ -25,9 +25,10 @@ logger = logging.getLogger(__name__)
 
 # SIMPLE_RADIAL and RADIAL only with every distortion parameter zero (camera_prior refuses the others): the model is then grown
 # under the pinhole assumption and the bundle adjustment may refine k from 0 (mapping/bundle.py, refine_distortion); with
-# `known_distortion` also with a non-zero k, on undistorted keypoints.  OPENCV is not among them: the
-# adjustment has no tangential terms
+# `known_distortion` also with a non-zero k, on undistorted keypoints.  OPENCV joins them only under `tangential`
+# ("The tangential terms" in §4.2k: the adjustment then runs the _opencv entry points); without it the mapper refuses it, as it did
 SEED_CAMERA_MODELS = ("SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL")
+TANGENTIAL_CAMERA_MODELS = SEED_CAMERA_MODELS + ("OPENCV",)
 
 
 @dataclass
@@ -187,16 +188,35 @@ def _pixel_errors_radial(K, k, R, t, xyz, obs):
     return np.where(Xc[:, 2] > 0, err, np.inf)
 
 
-def _read_database(database_path, known_distortion=False, undistort_fn=None, device="cuda"):
+def _pixel_errors_opencv(K, k, R, t, xyz, obs):
+    """_pixel_errors under the distortion k = (k1, k2, p1, p2), the forward model of csrc/undistort.hip: the radial term first, the
+    tangential terms added after it."""
+    Xc = xyz @ R.T + t
+    with np.errstate(all="ignore"):
+        xu, xv = Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2]
+        rho = xu * xu + xv * xv
+        s = 1.0 + k[0] * rho + k[1] * rho * rho
+        xd = xu * s + 2.0 * k[2] * xu * xv + k[3] * (rho + 2.0 * xu * xu)
+        yd = xv * s + k[2] * (rho + 2.0 * xv * xv) + 2.0 * k[3] * xu * xv
+        p = np.stack([K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]], axis=1)
+        err = np.linalg.norm(p - obs, axis=1)
+    return np.where(Xc[:, 2] > 0, err, np.inf)
+
+
+def _read_database(database_path, known_distortion=False, undistort_fn=None, device="cuda", tangential=False):
     """The rows the seed model and its growth read -> images {image_id: Image}, cameras {camera_id: Camera}, K {image_id: (3, 3)
     or None where the camera has no usable prior or another model}, kps {image_id: float32 (n, 2)}, rows {(i, j), i < j: the
     two_view_geometries row} of every CALIBRATED or PLANAR row with inliers.
     `known_distortion`: a sixth entry follows, `known` = dict(raw {image_id: the keypoints as the database
     holds them}, dist {image_id: (k1, k2)} of the images that were undistorted).  K is then also usable for a flagged
-    SIMPLE_RADIAL or RADIAL camera with a non-zero k (matching.undistort.camera_calibration; OPENCV stays refused:
+    SIMPLE_RADIAL or RADIAL camera with a non-zero k (matching.undistort.camera_calibration; without `tangential` OPENCV stays refused:
     SEED_CAMERA_MODELS), the kps of such an image are its undistorted pixels in float64, NaN where a keypoint does not invert,
     and the rows have lost the inlier matches that touch such a keypoint, so it is in no track.  `undistort_fn(xy, cam, cams,
-    device) -> (xy64, valid)` on numpy arrays replaces the launch of vc_undistort_points (tests)."""
+    device) -> (xy64, valid)` on numpy arrays replaces the launch of vc_undistort_points (tests).
+    `tangential` ("The tangential terms" in §4.2k): OPENCV is a model like the other four: usable with all four distortion
+    parameters zero and, under known_distortion, with any finite ones, through the same launch; `known["dist"]` then carries
+    (k1, k2, p1, p2) for the images of such a camera.  Off, nothing changes."""
+    models = TANGENTIAL_CAMERA_MODELS if tangential else SEED_CAMERA_MODELS
     with ColmapDatabase.open_database(str(database_path)) as db:
         images = {im.image_id: im for im in db.read_all_images()}
         cameras, K, kps, distorted = {}, {}, {}, {}
@@ -205,8 +225,8 @@ def _read_database(database_path, known_distortion=False, undistort_fn=None, dev
                 cameras[im.camera_id] = db.read_camera(im.camera_id)
             cam = cameras[im.camera_id]
             Kc, ok, _ = camera_prior(cam)
-            K[iid] = Kc if ok and cam.model in SEED_CAMERA_MODELS else None
-            if known_distortion and K[iid] is None and cam.model in SEED_CAMERA_MODELS:
+            K[iid] = Kc if ok and cam.model in models else None
+            if known_distortion and K[iid] is None and cam.model in models:
                 from ..matching.undistort import camera_calibration
 
                 Kc, dist, usable = camera_calibration(cam)
@@ -222,7 +242,8 @@ def _read_database(database_path, known_distortion=False, undistort_fn=None, dev
         return images, cameras, K, kps, rows
     from ..matching.undistort import undistort_images
 
-    known = dict(raw=dict(kps), dist={iid: (float(d[0]), float(d[1])) for iid, (_, d) in distorted.items()})
+    known = dict(raw=dict(kps), dist={iid: tuple(float(v) for v in (d if cameras[images[iid].camera_id].model == "OPENCV" else d[:2]))
+                                      for iid, (_, d) in distorted.items()})
     kps, invalid = dict(kps), 0
     for iid, (xy64, valid) in undistort_images(known["raw"], distorted, device, undistort_fn).items():
         kps[iid] = np.where(valid[:, None], xy64, np.nan)
@@ -241,17 +262,26 @@ def _observation_errors(K, kps, known, iid, R, t, xyz, kp):
     for an image that was undistorted (§4.2l), by the distorted projection against the raw keypoints."""
     if known is None or iid not in known["dist"]:
         return _pixel_errors(K[iid], R, t, xyz, kps[iid][kp].astype(np.float64).reshape(-1, 2))
-    return _pixel_errors_radial(K[iid], known["dist"][iid], R, t, xyz, known["raw"][iid][kp].astype(np.float64).reshape(-1, 2))
+    errors = _pixel_errors_opencv if len(known["dist"][iid]) == 4 else _pixel_errors_radial
+    return errors(K[iid], known["dist"][iid], R, t, xyz, known["raw"][iid][kp].astype(np.float64).reshape(-1, 2))
+
+
+def _database(database_path, device, known_distortion, undistort_fn, tangential):
+    """_read_database with `known_distortion` and `tangential` passed on only where they are on."""
+    tangential_args = dict(tangential=True) if tangential else {}
+    if known_distortion:
+        return _read_database(database_path, True, undistort_fn, device, **tangential_args)
+    return _read_database(database_path, **tangential_args)
 
 
 def build_seed_model(database_path, device="cuda", two_view_pose_fn=None, estimate_fn=None, known_distortion=False,
-                     undistort_fn=None) -> SparseModel:
+                     undistort_fn=None, tangential=False) -> SparseModel:
     """Read a matched database -> the seed model.  Raises ValueError, naming the condition, when no pair can start it.
     `two_view_pose_fn(xn_rows, cand, device)` and `estimate_fn(problems, device)` replace the two GPU steps (tests).
     `known_distortion` (§4.2l): the model is solved on the undistorted keypoints of the flagged SIMPLE_RADIAL and RADIAL cameras
-    (`_read_database`); its `xys` are the raw keypoints, as COLMAP's are, and `error` uses the distorted projection."""
-    database = _read_database(database_path, True, undistort_fn, device) if known_distortion else _read_database(database_path)
-    return _seed_model(database, device, two_view_pose_fn, estimate_fn)
+    (`_read_database`); its `xys` are the raw keypoints, as COLMAP's are, and `error` uses the distorted projection.
+    `tangential`: OPENCV cameras are read as the other models are (`_read_database`)."""
+    return _seed_model(_database(database_path, device, known_distortion, undistort_fn, tangential), device, two_view_pose_fn, estimate_fn)
 
 
 def _seed_model(database, device, two_view_pose_fn, estimate_fn):

@@ -86,6 +86,10 @@ class Pipeline:
         split_tracks = bool(getattr(self.config.reconstruction, "split_tracks", False))
         if split_tracks and not sparse_model:                   # it is a step of that model's growth (§4.2n)
             raise ValueError("split_tracks needs reconstruction.sparse_model (--sparse-model)")
+        tangential = bool(getattr(self.config.reconstruction, "tangential_distortion", False))
+        if tangential and not (seed_model or sparse_model):     # it lets OPENCV cameras into those models (§4.2k, "The tangential terms")
+            raise ValueError("tangential_distortion needs reconstruction.seed_model (--seed-model) or reconstruction.sparse_model "
+                             "(--sparse-model)")
         adjust_rounds = bool(getattr(self.config.reconstruction, "adjust_rounds", False))
         if adjust_rounds and not bundle_adjustment:             # it is that adjustment after every growth round (§4.2m)
             raise ValueError("adjust_rounds needs reconstruction.bundle_adjustment (--bundle-adjustment)")
@@ -114,6 +118,8 @@ class Pipeline:
         if camera_params is not None and camera_model in CAMERA_PARAM_NAMES:   # the count, before any database is created
             camera_params = parse_camera_params(camera_params, camera_model)
         known_args = dict(known_distortion=True) if known_distortion else {}
+        if tangential:                                          # travels with it: passed on only where it is on
+            known_args["tangential"] = True
         rounds_args = dict(adjust_rounds=True) if adjust_rounds else {}   # passed on only where it is on, as known_distortion is
         if split_tracks:                                        # likewise; it goes wherever the growth runs
             rounds_args["split_tracks"] = True
@@ -215,12 +221,14 @@ class Pipeline:
             opts.known_distortion = opts.sift.known_distortion = True
         return opts
 
-    def _write_seed_model(self, db_path, output_dir, device, known_distortion=False):
+    def _write_seed_model(self, db_path, output_dir, device, known_distortion=False, tangential=False):
         """output_dir/sparse/seed and `last_stats["seed_model"]`; a scene without an admissible initial pair writes nothing.
-        `known_distortion`: passed on only where it is on (§4.2l)."""
+        `known_distortion`: passed on only where it is on (§4.2l); `tangential` likewise ("The tangential terms" in §4.2k)."""
         from ..mapping import build_seed_model
 
         known_args = dict(known_distortion=True) if known_distortion else {}
+        if tangential:
+            known_args["tangential"] = True
         try:
             model = build_seed_model(str(db_path), device=device, **known_args)
         except ValueError as e:
@@ -232,7 +240,8 @@ class Pipeline:
                                                                     ("initial_pair", "registered_images", "num_points3D")])
 
     def _write_sparse_model(self, db_path, output_dir, device, adjust=False, refine_focal_length=False, loss="trivial", loss_scale=1.0,
-                            refine_distortion=False, known_distortion=False, adjust_rounds=False, solver="dense", split_tracks=False):
+                            refine_distortion=False, known_distortion=False, adjust_rounds=False, solver="dense", split_tracks=False,
+                            tangential=False):
         """output_dir/sparse/grown and `last_stats["sparse_model"]`; a scene without an admissible initial pair writes nothing.
         `adjust`: also output_dir/sparse/adjusted and `last_stats["bundle_adjustment"]`, the grown model bundle-adjusted;
         `refine_focal_length`: that adjustment also refines the cameras' focal lengths; `loss`, `loss_scale`: its loss, passed on
@@ -242,10 +251,14 @@ class Pipeline:
         adjustment and a re-evaluation of its tracks after every round (§4.2m), under the same options; the other two models are
         built and written as without it.  `solver`: how the adjustments solve their system ("The solver" in §4.2k), passed on
         only where it is not "dense".  `split_tracks`: the growth of the grown and of the mapped model splits its inconsistent
-        components (§4.2n), passed on only where it is on; the adjusted model is the grown one adjusted, so it has their points too."""
+        components (§4.2n), passed on only where it is on; the adjusted model is the grown one adjusted, so it has their points too.
+        `tangential`: OPENCV cameras are mapped and adjusted ("The tangential terms" in §4.2k), passed on to all three builders only
+        where it is on."""
         from ..mapping.grow import build_sparse_model
 
         known_args = dict(known_distortion=True) if known_distortion else {}
+        if tangential:
+            known_args["tangential"] = True
         split_args = dict(split_tracks=True) if split_tracks else {}
         try:
             model = build_sparse_model(str(db_path), device=device, **known_args, **split_args)
@@ -345,6 +358,9 @@ def main() -> None:
     ap.add_argument("--refine-distortion", dest="refine_distortion", action="store_true",
                     help="with --bundle-adjustment: the adjustment also refines the radial distortion, k of SIMPLE_RADIAL cameras and "
                          "k1, k2 of RADIAL ones, from the values in the database (0 as the extractors write them)")
+    ap.add_argument("--tangential-distortion", dest="tangential_distortion", action="store_true",
+                    help="with --seed-model or --sparse-model: OPENCV cameras are mapped and, with --bundle-adjustment, adjusted under "
+                         "their full distortion k1, k2, p1, p2 (with --refine-distortion all four are refined)")
     ap.add_argument("--adjust-rounds", dest="adjust_rounds", action="store_true",
                     help="with --bundle-adjustment: also write output/sparse/mapped, the model grown with a bundle adjustment and a "
                          "re-evaluation of every track after each growth round; what long sequences need")

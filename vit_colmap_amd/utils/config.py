@@ -138,6 +138,7 @@ class ReconstructionConfig:
     ba_loss_scale: float = 1.0   # px: the residual at which the loss leaves the square
     refine_distortion: bool = False   # with bundle_adjustment: it also refines k of SIMPLE_RADIAL, k1 and k2 of RADIAL cameras (§4.2k)
     ba_solver: str = "dense"     # with bundle_adjustment: how the reduced camera system is solved, "dense" (Cholesky of S, at most VC_BA_MAX_CAMS images) or "pcg" (conjugate gradients without S, no limit; §4.2k, "The solver")
+    tangential_distortion: bool = False   # with seed_model or sparse_model: OPENCV cameras are mapped and adjusted under k1, k2, p1, p2 (§4.2k, "The tangential terms")
     adjust_rounds: bool = False   # with bundle_adjustment: write output_dir/sparse/mapped, grown with an adjustment and a re-evaluation of the tracks per round (§4.2m)
 
     def to_mapper_options(self):
@@ -212,6 +213,8 @@ class Config:
             config.reconstruction.refine_focal_length = True
         if getattr(args, "refine_distortion", False):
             config.reconstruction.refine_distortion = True
+        if getattr(args, "tangential_distortion", False):
+            config.reconstruction.tangential_distortion = True
         if getattr(args, "adjust_rounds", False):
             config.reconstruction.adjust_rounds = True
         if getattr(args, "ba_loss", None):
