@@ -173,6 +173,12 @@ class SqliteColmapDatabase:
         self._conn.commit()
         return cur.lastrowid
 
+    def update_camera(self, camera_id: int, params, has_prior_focal_length: bool):
+        """Replaces the params and the prior_focal_length flag of an existing camera row; its model and size stay."""
+        self._conn.execute("UPDATE cameras SET params = ?, prior_focal_length = ? WHERE camera_id = ?",
+                           (np.asarray(params, dtype=np.float64).tobytes(), int(bool(has_prior_focal_length)), int(camera_id)))
+        self._conn.commit()
+
     def write_image(self, image, use_image_id: bool = False) -> int:
         img_id = getattr(image, "image_id", None) if use_image_id else None
         cur = self._conn.execute("INSERT INTO images VALUES (?, ?, ?)", (img_id, image.name, int(image.camera_id)))
@@ -313,6 +319,10 @@ class SqliteColmapDatabase:
         """-> [(image_id1, image_id2, rows, config)] of every two_view_geometries row, ascending in pair_id."""
         return [pair_id_to_image_ids(int(pid)) + (int(rows), int(config)) for pid, rows, config in
                 self._conn.execute("SELECT pair_id, rows, config FROM two_view_geometries ORDER BY pair_id")]
+
+    def read_matched_image_pairs(self):
+        """-> [(image_id1, image_id2)] of every matches row, ascending in pair_id."""
+        return [pair_id_to_image_ids(int(pid)) for pid, in self._conn.execute("SELECT pair_id FROM matches ORDER BY pair_id")]
 
     def read_matches(self, image_id1: int, image_id2: int):
         m = self._read_blob("matches", "pair_id", pair_id_of(image_id1, image_id2), np.uint32)

@@ -297,10 +297,11 @@ def write_two_view_rows(db, ids, results) -> int:
     return int(n_ok)
 
 
-def verify_database_pairs(db, ids, merged, device="cuda", verify_fn=None) -> int:
-    """Single-process form: verify every matched pair of a database that is open for writing and write its rows.
-    `merged`: {(a, b): uint32 (M, 2)} with a < b image indices into `ids`.  Returns the number of verified pairs."""
+def verify_database_pairs(db, ids, merged, device="cuda", verify_fn=None, relative_pose=False) -> int:
+    """Single-process form: verify every matched pair of a database that is open for writing and write its rows (a row that
+    is there already is replaced).  `merged`: {(a, b): uint32 (M, 2)} with a < b image indices into `ids`; `relative_pose` as
+    verify_pair_lists takes it.  Returns the number of verified pairs."""
     pairs = sorted(merged)
     res = verify_pair_lists(read_keypoints_by_index(db, ids), ids, pairs, [merged[p] for p in pairs], device=device,
-                            verify_fn=verify_fn, cameras=camera_table(db, ids))
+                            verify_fn=verify_fn, cameras=camera_table(db, ids), relative_pose=relative_pose)
     return write_two_view_rows(db, ids, dict(zip(pairs, res)))

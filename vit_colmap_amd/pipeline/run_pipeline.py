@@ -105,6 +105,10 @@ class Pipeline:
         known_distortion = bool(getattr(self.config.camera, "known_distortion", False))
         if known_distortion and not self.config.camera.prior_focal_length:   # it is what makes the intrinsics trusted (§4.2l)
             raise ValueError("known_distortion needs camera.prior_focal_length (--prior-focal-length)")
+        estimate_focal_length = bool(getattr(self.config.camera, "estimate_focal_length", False))
+        if estimate_focal_length and known_distortion:         # an estimated focal length is not a known camera (§4.2o)
+            raise ValueError("estimate_focal_length cannot be combined with camera.known_distortion (--known-distortion): an "
+                             "estimated focal length is not a known camera")
         ba_solver = str(getattr(self.config.reconstruction, "ba_solver", "dense"))
         if ba_solver not in BA_SOLVERS:
             raise ValueError(f"unknown ba_solver {ba_solver!r}: expected one of {', '.join(BA_SOLVERS)}")
@@ -126,7 +130,8 @@ class Pipeline:
         for wanted, name in ((seed_model, "seed_model"), (sparse_model, "sparse_model")):
             if not wanted:                                      # both read calibrated rows with a pose (§4.2i, §4.2j)
                 continue
-            for on, flag in ((self.config.camera.prior_focal_length, "camera.prior_focal_length (--prior-focal-length)"),
+            for on, flag in ((self.config.camera.prior_focal_length or estimate_focal_length,   # either makes rows CALIBRATED (§4.2o)
+                              "camera.prior_focal_length (--prior-focal-length)"),
                              (self.config.matching.compute_relative_pose, "matching.compute_relative_pose (--relative-pose)"),
                              (self.config.do_matching, "do_matching (no --skip-matching)")):
                 if not on:
@@ -176,7 +181,9 @@ class Pipeline:
                 num_pairs = ColmapDatabase.get_db_count(db_check, "num_matched_image_pairs")
                 logger.info(f"Matched {num_pairs} image pairs ({db_check.num_verified_image_pairs()} geometrically verified)")
 
-        if seed_model:                                          # under torchrun only rank 0 arrives here
+        if estimate_focal_length and self.config.do_matching:   # under torchrun only rank 0 arrives here
+            self._estimate_focal_lengths(db_path, str(getattr(extractor, "device", "cuda")))
+        if seed_model:
             self._write_seed_model(db_path, output_dir, str(getattr(extractor, "device", "cuda")), **known_args)
         if sparse_model:
             if refine_distortion:
@@ -220,6 +227,27 @@ class Pipeline:
         if getattr(self.config.camera, "known_distortion", False):
             opts.known_distortion = opts.sift.known_distortion = True
         return opts
+
+    def _estimate_focal_lengths(self, db_path, device, cost_fn=None, verify_fn=None):
+        """`camera.estimate_focal_length` (§4.2o): the focal length of every camera without a prior from its UNCALIBRATED rows
+        (`last_stats["focal_estimates"]`), written into the cameras table with the prior flag; if any camera changed, every
+        matched pair is verified again from the stored `matches`, with `relative_pose` as configured, and its row replaced
+        (`last_stats["focal_reverified_pairs"]`).  `cost_fn` and `verify_fn` replace the launches in the CPU tests."""
+        from ..matching.focal import apply_focal_estimates, estimate_focal_lengths, reverify_database
+
+        with ColmapDatabase.open_database(str(db_path)) as db:
+            ids = [im.image_id for im in db.read_all_images()]
+            estimates = estimate_focal_lengths(db, ids, device, cost_fn)
+            changed = apply_focal_estimates(db, estimates)
+            self.last_stats = dict(self.last_stats or {}, focal_estimates=estimates)
+            if changed:
+                if self.config.matching.guided_matching:
+                    logger.warning("estimate_focal_length: the pairs are verified again from the stored matches; their rows "
+                                   "carry the verifier's inliers, not the guided lists")
+                n = reverify_database(db, ids, device, verify_fn, bool(self.config.matching.compute_relative_pose))
+                self.last_stats["focal_reverified_pairs"] = n
+                logger.info("Estimated the focal length of %d camera(s); %d pairs verified again (%d verified)", len(changed),
+                            ColmapDatabase.get_db_count(db, "num_matched_image_pairs"), n)
 
     def _write_seed_model(self, db_path, output_dir, device, known_distortion=False, tangential=False):
         """output_dir/sparse/seed and `last_stats["seed_model"]`; a scene without an admissible initial pair writes nothing.
@@ -324,6 +352,11 @@ def main() -> None:
     ap.add_argument("--camera-model", dest="camera_model", default="SIMPLE_PINHOLE")
     ap.add_argument("--prior-focal-length", dest="prior_focal_length", action="store_true",
                     help="mark the cameras as calibrated: pairs are also verified under an essential matrix")
+    ap.add_argument("--estimate-focal-length", dest="estimate_focal_length", action="store_true",
+                    help="the focal length is unknown: after matching it is estimated per camera from the fundamental matrices of "
+                         "the verified pairs (one scale on the stored focal length, a quarter to four times it), the camera is "
+                         "marked calibrated and every pair is verified again; stands in for --prior-focal-length in front of "
+                         "--seed-model and --sparse-model (not with --known-distortion)")
     ap.add_argument("--camera-params", dest="camera_params", default=None, metavar="P1,P2,...",
                     help="the intrinsics of --camera-model as a comma-separated list in COLMAP's order (SIMPLE_RADIAL: f,cx,cy,k; "
                          "OPENCV: fx,fy,cx,cy,k1,k2,p1,p2); by default f = max(w, h) and the image centre")

@@ -28,6 +28,7 @@ class CameraConfig:
     height: Optional[int] = None
     params: Optional[list[float]] = None
     prior_focal_length: bool = False   # the intrinsics are trusted: pairs are also verified under E (not set by the reference)
+    estimate_focal_length: bool = False   # the focal length is unknown: it is estimated from the UNCALIBRATED pairs after matching, the camera is flagged and every pair verified again (§4.2o)
     known_distortion: bool = False     # with prior_focal_length: a non-zero distortion in `params` is trusted too, keypoints are undistorted in front of the solvers (§4.2l)
 
     def get_default_params(self, width: int, height: int) -> list[float]:
@@ -183,6 +184,8 @@ class Config:
             config.camera.prior_focal_length = True
         if getattr(args, "known_distortion", False):
             config.camera.known_distortion = True
+        if getattr(args, "estimate_focal_length", False):
+            config.camera.estimate_focal_length = True
         if getattr(args, "camera_params", None) is not None:
             config.camera.params = parse_camera_params(args.camera_params, config.camera.model)
         if hasattr(args, "extractor") and args.extractor:
