@@ -54,8 +54,8 @@ int main(int argc, char** argv) {
   const BaProblem d{cams.data(), const_mask.data(), points.data(), offsets.data(), obs_cam.data(), obs_xy.data(), n_cams, n_points, total};
   for (int j = 0; j < n_points; ++j) {
     double v[6], g[3], cost;
-    if (loss.kind == VC_BA_LOSS_TRIVIAL) ba_linearize_point<false>(d, loss, j, lambda, v, g, cost, obs_ok.data(), obs_lin.data(), nullptr);
-    else ba_linearize_point<true>(d, loss, j, lambda, v, g, cost, obs_ok.data(), obs_lin.data(), obs_w.data());
+    if (loss.kind == VC_BA_LOSS_TRIVIAL) ba_linearize_point<false, kBaDistNone>(d, loss, j, lambda, v, g, cost, obs_ok.data(), obs_lin.data(), nullptr);
+    else ba_linearize_point<true, kBaDistNone>(d, loss, j, lambda, v, g, cost, obs_ok.data(), obs_lin.data(), obs_w.data());
     for (int k = 0; k < 6; ++k) vinv[6 * (size_t)j + k] = v[k];
     for (int k = 0; k < 3; ++k) gp[3 * (size_t)j + k] = g[k];
     total_cost[0] += cost;

@@ -1,35 +1,31 @@
 // Bundle adjustment (gfx950): the kernels of one Levenberg-Marquardt iteration over every pose and every point
-// of a sparse model and, where groups of cameras are given, over their intrinsics (fx, fy, cx, cy), by the Schur complement of
-// the points.  vit_colmap_amd/mapping/bundle.py repeats vc_ba_linearize_points, vc_ba_reduce_cameras and vc_ba_step; with groups
-// (mapping/bundle_intr.py) vc_ba_linearize_intrinsics and vc_ba_reduce_border follow the reduction and vc_ba_step_intrinsics takes
-// the step: the groups' unknowns border the reduced system, [[S, B], [B', C]] (dc, dtheta) = -(g, h).  The system is solved by
-// the caller.  Under a loss (Huber, soft L1: vc_ba_linearize_points_loss, vc_ba_linearize_intrinsics_loss,
-// vc_ba_reduce_border_loss) every observation's J_c, J_p, r and J_theta are multiplied by the square root of its weight before
-// anything is formed from them, and the other three entry points run unchanged on the result; the routines take the loss as a
-// template argument, and without it return the bytes they returned.  With radial distortion (vc_ba_linearize_points_radial,
-// vc_ba_linearize_intrinsics_radial, vc_ba_reduce_border_radial, vc_ba_step_radial; COLMAP's SIMPLE_RADIAL and RADIAL) the
-// camera's (k1, k2) travel beside its row as cam_dist [n_cams][2] and theta_g = (fx, fy, cx, cy, k1, k2); the routines take the
-// distortion as a second template argument, and without it are what they were.  With the tangential terms
-// (vc_ba_linearize_points_opencv, vc_ba_linearize_intrinsics_opencv, vc_ba_reduce_border_opencv, vc_ba_step_opencv; COLMAP's OPENCV)
-// cam_dist is [n_cams][4] = (k1, k2, p1, p2), theta_g has eight unknowns and bit 7 of a group's mask holds p1 and p2 together: the
-// third value of that template argument (BaDistortion, ba_project_opencv below; tests/util_bundle_opencv.py).  Without the dense S ("The solver" in §4.2k:
-// vc_ba_camera_blocks, vc_ba_schur_product) the caller solves S dc = -g by preconditioned conjugate gradients: the first gives
-// per camera U_a, the diagonal block D_a = S_aa, D_a^-1, g_a and which parameters are fixed, the second q = S p in two passes
-// over what the points pass left, for any number of cameras.  The order of operations, in full (BaRadial,
-// ba_project_radial, ba_observe): ba_project on the row with fx = fy = 1 gives iu = 1 / Xc_z, (xu, xv) and their Jacobian
-// (nu; nv); rho = xu xu + xv xv, s = 1 + k1 rho + k2 rho rho, e = 2 (k1 + 2 k2 rho), d00 = s + xu xu e, d01 = xu xv e,
-// d11 = s + xv xv e; xd = xu s, yd = xv s, r = (fx xd + cx - u, fy yd + cy - v); J_p = (fx (d00 nu + d01 nv); fy (d01 nu + d11 nv))
-// and J_c the same map of the pinhole rows at fx = fy = 1; pu = fx xu rho, pv = fy xv rho, qu = pu rho, qv = pv rho and J_theta =
-// ((xd, 0, 1, 0, pu, qu); (0, yd, 0, 1, pv, qv)); every product and sum left to right as written.  Specification:
-// tests/util_bundle.py, tests/util_bundle_intr.py, tests/util_bundle_loss.py, tests/util_bundle_radial.py, tests/util_bundle_pcg.py.  This build's own
-// published rule; parity with COLMAP / Ceres is unpinned.
+// of a sparse model and, where groups of cameras are given, over the groups' intrinsics, by the Schur complement of the points.
+// The callers (vit_colmap_amd/mapping/bundle.py, mapping/bundle_intr.py) repeat linearize points, reduce cameras, step; with
+// groups linearize intrinsics and reduce border follow the reduction: the groups' unknowns theta_g border the reduced system,
+// [[S, B], [B', C]] (dc, dtheta) = -(g, h), which the caller solves.  Without the dense S ("The solver" in §4.2k:
+// vc_ba_camera_blocks, vc_ba_schur_product) the caller solves S dc = -g by preconditioned conjugate gradients.
+//
+// Every pass that sees an observation is one template over (kLoss, kDist); four instances exist:
+//   (false, kBaDistNone)    vc_ba_linearize_points, vc_ba_linearize_intrinsics, vc_ba_reduce_border: the pinhole, no loss; loss, obs_w
+//                           and cam_dist are absent and not read.
+//   (true, kBaDistNone)     the _loss entry points: every observation's J_c, J_p, r and J_theta are multiplied by sw = sqrt(w) of its
+//                           loss (Huber, soft L1) before anything is formed from them; the points pass writes obs_w [total], the other
+//                           two read it.
+//   (true, kBaDistRadial)   the _radial entry points (COLMAP's SIMPLE_RADIAL and RADIAL): cam_dist [n_cams][2] = (k1, k2) travels
+//                           beside the cameras' rows, theta_g = (fx, fy, cx, cy, k1, k2).
+//   (true, kBaDistOpencv)   the _opencv entry points (COLMAP's OPENCV): cam_dist [n_cams][4] = (k1, k2, p1, p2), theta_g has eight
+//                           unknowns and bit 7 of a group's mask holds p1 and p2 together.
+// Everything a model sets is a constexpr function of kDist (ba_dist_unknowns, ba_dist_params, ba_dist_jt, ba_dist_max_groups); the
+// routines that see only a group's unknowns (the terms' rows, C and h, the points' step) take their number N = ba_dist_unknowns(kDist).
+// Under a distortion the loss is always on: VC_BA_LOSS_TRIVIAL gives rho = s and sw = 1, and a product with 1.0 is exact.
 //
 // float64 in single operations in the written order (-ffp-contract=off), the only library call is sqrt, no atomics.
 //   points pass  one point per lane, one wave per workgroup, no LDS.  ba_linearize_points_kernel: every observation of the point's
-//                track is linearised (ba_project; residual r, J_c 2x6, W = J_c' J_p 6x3, written per observation: 32 numbers),
+//                track is linearised (ba_observe; residual r, J_c 2x6, W = J_c' J_p 6x3, written per observation: 32 numbers),
 //                V = sum J_p' J_p, g_p and the cost are accumulated in track order, V is damped and inverted by the adjugate.
-//                ba_linearize_intrinsics_kernel: the groups outside and the track inside, T = sum J_theta' J_p, q, hq (ba_project
-//                again for x, y and J_p) and the point's products T V^-1 T', T V^-1 g_p; nothing is a register array indexed by a
+//                ba_linearize_intrinsics_kernel: obs_jt [total][ba_dist_jt] (what J_theta is rebuilt from; the pinhole's (x, y), its
+//                entry points' obs_xn), then the groups outside and the track inside, T = sum J_theta' J_p, q, hq (the observation
+//                projected again) and the point's products T V^-1 T', T V^-1 g_p; nothing is a register array indexed by a
 //                runtime value.
 //   ordered sums ba_ordered_sums_kernel, one wave per row of [rows][n], adds the row in ascending order: the total cost is the one
 //                row of the points' costs, the border's C and h come from the rows of its terms (ba_border_system_kernel).
@@ -40,18 +36,20 @@
 //                belongs to lane (36 b + e) mod 64 for the whole launch; nobody else reads or writes it, so there is no atomic and
 //                the order of a lane's additions is the rule's: camera a's observations in ascending order and, inside each, the
 //                track of its point in track order (the next element's flag and camera are loaded while the current element's W
-//                is on its way).  ba_reduce_border_kernel keeps a lane's entries of B_a [6][4 G] in its registers.
+//                is on its way).  ba_reduce_border_kernel keeps a lane's entries of B_a [6][N G] in its registers.
 //   solver       ba_camera_blocks_kernel, one wave per camera through ba_camera_walk: lane e < 36 keeps entry e of U_a and of
 //                (sum Y W')_aa in its registers, six lanes invert D_a by a 6x6 Cholesky factorisation, a column each.
 //                ba_product_points_kernel, one point per lane: s_j = V^-1 sum W' p.  ba_product_cameras_kernel, four waves per
 //                camera: 256 entries of the list resolved at once, W s left in LDS, six owner lanes add them in list order.
 //   step         ba_step_points_kernel, one point per lane: dX = -V^-1 (g_p + sum W' dc + sum T_g' dtheta_g) in track order, then
 //                group order, X + dX; ba_step_cameras_kernel, one camera per lane: q = (1, w / 2) normalised, R(q) R, t + dt, its
-//                group's dtheta added, whether the focal lengths stay positive.  vc_ba_step launches both without groups: T,
-//                dtheta, cam_group and the valid flags are then absent and not read.
+//                group's dtheta added to its intrinsics and its row of cam_dist, whether the candidate is valid.  vc_ba_step
+//                launches both without groups: T, dtheta, cam_group and the valid flags are then absent and not read.
 // What a lane computes is sequential and nothing depends on the order in which lanes or workgroups run, so two launches
 // return the same bits, and the same routines compiled for the host (tools/bundle_host.cpp includes this file) return the
-// device's.  Every index read from an input array is checked against the array it indexes before it is used.
+// device's.  Every index read from an input array is checked against the array it indexes before it is used.  Specification:
+// tests/util_bundle.py, util_bundle_intr.py, util_bundle_loss.py, util_bundle_radial.py, util_bundle_opencv.py, util_bundle_pcg.py.
+// This build's own published rule; parity with COLMAP / Ceres is unpinned.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -73,6 +71,7 @@ struct BaProblem {
   const int32_t* __restrict__ obs_cam;         // [total]
   const double* __restrict__ obs_xy;           // [total][2]
   int n_cams, n_points, total;
+  const double* __restrict__ cam_dist;         // [n_cams][ba_dist_params]; null for the pinhole
 };
 
 // What the points pass leaves for the other two.
@@ -119,6 +118,10 @@ __host__ __device__ __forceinline__ bool ba_loss_valid(const BaLoss& loss) {
   return loss.kind >= VC_BA_LOSS_TRIVIAL && loss.kind <= VC_BA_LOSS_SOFT_L1 && loss.scale > 0.0 && loss.scale < INFINITY;
 }
 
+// What an entry point without loss arguments hands its launcher: not read without a loss, and valid for the two _loss entry
+// points whose weights come in obs_w.
+constexpr BaLoss kBaNoLoss{VC_BA_LOSS_TRIVIAL, 1.0};
+
 // s = |r|^2 of the unweighted residual -> rho(s) and the weight w = rho'(s).
 __host__ __device__ __forceinline__ void ba_loss(const BaLoss& loss, double s, double& rho, double& w) {
   const double c = loss.scale;
@@ -144,88 +147,67 @@ __host__ __device__ __forceinline__ void ba_loss(const BaLoss& loss, double s, d
 //   csrc/undistort.hip writes it, D gains d00 += 2 p1 xv + 6 p2 xu, d01 += 2 p1 xu + 2 p2 xv, d11 += 6 p1 xv + 2 p2 xu, and obs_jt
 //   has ten numbers: the six above, then the p1 column (fx 2 xu xv, fy (rho + 2 xv xv)) and the p2 column (fx (rho + 2 xu xu),
 //   fy 2 xu xv) of J_theta.
-// The routines take the distortion as a template argument kDist; kBaDistNone is the pinhole they were written for.
+// The residual is r = (fx xd + cx - u, fy yd + cy - v); J_p = diag(fx, fy) D (nu; nv) with (nu; nv) the Jacobian of (xu, xv), which
+// ba_project gives on the row with fx = fy = 1, and J_c the same map of the pinhole rows at fx = fy = 1; J_theta =
+// ((xd, 0, 1, 0, pu, qu, ..); (0, yd, 0, 1, pv, qv, ..)).  Every product and sum left to right as written.
+// The model is the template argument kDist; what it sets:
 constexpr int kBaDistNone = 0, kBaDistRadial = 1, kBaDistOpencv = 2;
-__host__ __device__ constexpr int ba_dist_params(int dist) { return dist == kBaDistOpencv ? 4 : 2; }     // numbers per row of cam_dist
-__host__ __device__ constexpr int ba_dist_jt(int dist) { return dist == kBaDistOpencv ? 10 : 6; }        // numbers per row of obs_jt
-__host__ __device__ constexpr int ba_dist_unknowns(int dist) { return dist == kBaDistOpencv ? 8 : dist == kBaDistRadial ? 6 : 4; }
+__host__ __device__ constexpr int ba_dist_unknowns(int dist) { return dist == kBaDistOpencv ? 8 : dist == kBaDistRadial ? 6 : 4; }   // per group
+__host__ __device__ constexpr int ba_dist_params(int dist) { return ba_dist_unknowns(dist) - 4; }        // numbers per row of cam_dist
+__host__ __device__ constexpr int ba_dist_jt(int dist) { return dist == kBaDistOpencv ? 10 : dist == kBaDistRadial ? 6 : 2; }   // per row of obs_jt
+__host__ __device__ constexpr int ba_dist_max_groups(int dist) {
+  return dist == kBaDistOpencv ? VC_BA_MAX_GROUPS_OPENCV : dist == kBaDistRadial ? VC_BA_MAX_GROUPS_RADIAL : VC_BA_MAX_GROUPS;
+}
 
+// What an observation keeps of its projection: D and the numbers of its row of obs_jt; the pinhole has jt = (x, y) and no D.
 template <int kDist>
 struct BaDistortion {
   double d00, d01, d11, jt[ba_dist_jt(kDist)];
 };
-using BaRadial = BaDistortion<kBaDistRadial>;
-using BaOpencv = BaDistortion<kBaDistOpencv>;
 
-// X in the camera of row c[16] under (k1, k2): ba_project on the row with fx = fy = 1, so that iu = 1 / Xc_z and (nu, nv) is the
-// Jacobian of (xu, xv); then J_p = diag(fx, fy) D (nu; nv): ju = fx (d00 nu + d01 nv), jv = fy (d01 nu + d11 nv).
-__host__ __device__ __forceinline__ void ba_project_radial(const double* c, double k1, double k2, const double (&X)[3], double (&Y)[3],
-                                                           double (&Xc)[3], double& iu, double& xu, double& xv, BaRadial& rd,
-                                                           double (&ju)[3], double (&jv)[3]) {
+// X in the camera of row c[16] under the row k of cam_dist, kDist != kBaDistNone: ba_project on the row with fx = fy = 1, so that
+// iu = 1 / Xc_z and (nu, nv) is the Jacobian of (xu, xv); then J_p = diag(fx, fy) D (nu; nv): ju = fx (d00 nu + d01 nv),
+// jv = fy (d01 nu + d11 nv).  The radial term first, the tangential terms added after it, left to right.
+template <int kDist>
+__host__ __device__ __forceinline__ void ba_project_dist(const double* c, const double* k, const double (&X)[3], double (&Y)[3],
+                                                         double (&Xc)[3], double& iu, double& xu, double& xv, BaDistortion<kDist>& rd,
+                                                         double (&ju)[3], double (&jv)[3]) {
+  static_assert(kDist != kBaDistNone, "the pinhole is ba_project's");
   double n[16], iv, nu[3], nv[3];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) n[k] = k == 12 || k == 13 ? 1.0 : c[k];
+  for (int i = 0; i < 16; ++i) n[i] = i == 12 || i == 13 ? 1.0 : c[i];
   ba_project(n, X, Y, Xc, iu, iv, xu, xv, nu, nv);
-  const double fx = c[12], fy = c[13];
+  const double fx = c[12], fy = c[13], k1 = k[0], k2 = k[1];
   const double rho = xu * xu + xv * xv;
   const double s = 1.0 + k1 * rho + k2 * rho * rho;
   const double e = 2.0 * (k1 + 2.0 * k2 * rho);
   rd.d00 = s + xu * xu * e, rd.d01 = xu * xv * e, rd.d11 = s + xv * xv * e;
   rd.jt[0] = xu * s, rd.jt[1] = xv * s, rd.jt[2] = fx * xu * rho, rd.jt[3] = fy * xv * rho;
   rd.jt[4] = rd.jt[2] * rho, rd.jt[5] = rd.jt[3] * rho;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    ju[k] = fx * (rd.d00 * nu[k] + rd.d01 * nv[k]);
-    jv[k] = fy * (rd.d01 * nu[k] + rd.d11 * nv[k]);
+  if constexpr (kDist == kBaDistOpencv) {
+    const double p1 = k[2], p2 = k[3];
+    rd.d00 = rd.d00 + 2.0 * p1 * xv + 6.0 * p2 * xu;
+    rd.d01 = rd.d01 + 2.0 * p1 * xu + 2.0 * p2 * xv;
+    rd.d11 = rd.d11 + 6.0 * p1 * xv + 2.0 * p2 * xu;
+    rd.jt[0] = rd.jt[0] + 2.0 * p1 * xu * xv + p2 * (rho + 2.0 * xu * xu);
+    rd.jt[1] = rd.jt[1] + p1 * (rho + 2.0 * xv * xv) + 2.0 * p2 * xu * xv;
+    rd.jt[6] = fx * 2.0 * xu * xv, rd.jt[7] = fy * (rho + 2.0 * xv * xv);
+    rd.jt[8] = fx * (rho + 2.0 * xu * xu), rd.jt[9] = fy * 2.0 * xu * xv;
   }
-}
-
-// The same under (k1, k2, p1, p2): the radial term first, the tangential terms added after it, left to right.
-__host__ __device__ __forceinline__ void ba_project_opencv(const double* c, double k1, double k2, double p1, double p2, const double (&X)[3],
-                                                           double (&Y)[3], double (&Xc)[3], double& iu, double& xu, double& xv, BaOpencv& rd,
-                                                           double (&ju)[3], double (&jv)[3]) {
-  double n[16], iv, nu[3], nv[3];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) n[k] = k == 12 || k == 13 ? 1.0 : c[k];
-  ba_project(n, X, Y, Xc, iu, iv, xu, xv, nu, nv);
-  const double fx = c[12], fy = c[13];
-  const double rho = xu * xu + xv * xv;
-  const double s = 1.0 + k1 * rho + k2 * rho * rho;
-  const double e = 2.0 * (k1 + 2.0 * k2 * rho);
-  rd.d00 = s + xu * xu * e + 2.0 * p1 * xv + 6.0 * p2 * xu;
-  rd.d01 = xu * xv * e + 2.0 * p1 * xu + 2.0 * p2 * xv;
-  rd.d11 = s + xv * xv * e + 6.0 * p1 * xv + 2.0 * p2 * xu;
-  rd.jt[0] = xu * s + 2.0 * p1 * xu * xv + p2 * (rho + 2.0 * xu * xu);
-  rd.jt[1] = xv * s + p1 * (rho + 2.0 * xv * xv) + 2.0 * p2 * xu * xv;
-  rd.jt[2] = fx * xu * rho, rd.jt[3] = fy * xv * rho;
-  rd.jt[4] = rd.jt[2] * rho, rd.jt[5] = rd.jt[3] * rho;
-  rd.jt[6] = fx * 2.0 * xu * xv, rd.jt[7] = fy * (rho + 2.0 * xv * xv);
-  rd.jt[8] = fx * (rho + 2.0 * xu * xu), rd.jt[9] = fy * 2.0 * xu * xv;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    ju[k] = fx * (rd.d00 * nu[k] + rd.d01 * nv[k]);
-    jv[k] = fy * (rd.d01 * nu[k] + rd.d11 * nv[k]);
+  for (int i = 0; i < 3; ++i) {
+    ju[i] = fx * (rd.d00 * nu[i] + rd.d01 * nv[i]);
+    jv[i] = fy * (rd.d01 * nu[i] + rd.d11 * nv[i]);
   }
-}
-
-// ba_project_radial or ba_project_opencv on the row dist of cam_dist, whichever kDist names.
-template <int kDist>
-__host__ __device__ __forceinline__ void ba_project_dist(const double* c, const double* __restrict__ dist, const double (&X)[3], double (&Y)[3],
-                                                         double (&Xc)[3], double& iu, double& xu, double& xv, BaDistortion<kDist>& rd,
-                                                         double (&ju)[3], double (&jv)[3]) {
-  if constexpr (kDist == kBaDistOpencv) ba_project_opencv(c, dist[0], dist[1], dist[2], dist[3], X, Y, Xc, iu, xu, xv, rd, ju, jv);
-  else ba_project_radial(c, dist[0], dist[1], X, Y, Xc, iu, xu, xv, rd, ju, jv);
 }
 
 // Observation o of point X: usable -> lin[32] (zeros otherwise) and J_p (2x3).  With a loss the rows of J_c and J_p and r are
 // multiplied by sw = sqrt(w) before anything is formed from them, and rho is the loss of the unweighted residual, the
-// observation's term of the cost.  kRadial: the camera's (k1, k2) of cam_dist [n_cams][2] must be finite too, the projection
-// is ba_project_radial's, r = (fx xd + cx - u, fy yd + cy - v) and J_c = diag(fx, fy) D (the pinhole rows at fx = fy = 1);
-// without it cam_dist is absent and not read.  kBaDistOpencv: the four numbers of cam_dist [n_cams][4] and ba_project_opencv.
-template <bool kLoss, int kDist = kBaDistNone>
+// observation's term of the cost.  Under a distortion the camera's row of cam_dist must be finite too and the projection is
+// ba_project_dist's; the pinhole's is ba_project's on the row as it is.
+template <bool kLoss, int kDist>
 __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const BaLoss& loss, int o, const double (&X)[3],
-                                                    double* __restrict__ lin, double (&ju)[3], double (&jv)[3], double& rho, double& sw,
-                                                    const double* __restrict__ cam_dist = nullptr) {
+                                                    double* __restrict__ lin, double (&ju)[3], double (&jv)[3], double& rho, double& sw) {
   const int slot = d.obs_cam[o];
   bool ok = slot >= 0 && slot < d.n_cams;
   const double* c = d.cams + (long long)(ok ? slot : 0) * 16;
@@ -239,21 +221,21 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
   ok = ok && ba_finite(u) && ba_finite(v);
   const unsigned held = ok ? d.const_mask[slot] : 0u;
   double Y[3], Xc[3], fu, fv, xu, xv;
-  constexpr bool kRadial = kDist != kBaDistNone;
+  constexpr bool kDistorted = kDist != kBaDistNone;
   BaDistortion<kDist> rd;
-  if constexpr (kDist == kBaDistOpencv) {
-    double k[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      k[i] = ok ? cam_dist[4 * (long long)slot + i] : NAN;
-      ok = ok && ba_finite(k[i]);
-    }
-    ba_project_opencv(row, k[0], k[1], k[2], k[3], X, Y, Xc, fu, xu, xv, rd, ju, jv);
-    fv = fu;
-  } else if constexpr (kDist == kBaDistRadial) {
-    const double k1 = ok ? cam_dist[2 * (long long)slot] : NAN, k2 = ok ? cam_dist[2 * (long long)slot + 1] : NAN;
+  if constexpr (kDistorted) {
+    // the row of cam_dist as the projection reads it: the radial pair, then the tangential pair.  Not a loop over kParams: every loop
+    // form tried computes the same and compiles the radial points kernel to 130 VGPRs where this form keeps its 128, the last count
+    // with four waves per SIMD (profiles/bundle_one_template_resource_usage.md)
+    constexpr int kParams = ba_dist_params(kDist);
+    const double k1 = ok ? d.cam_dist[kParams * (long long)slot] : NAN, k2 = ok ? d.cam_dist[kParams * (long long)slot + 1] : NAN;
     ok = ok && ba_finite(k1) && ba_finite(k2);
-    ba_project_radial(row, k1, k2, X, Y, Xc, fu, xu, xv, rd, ju, jv);
+    double k[kParams] = {k1, k2};
+    if constexpr (kDist == kBaDistOpencv) {
+      k[2] = ok ? d.cam_dist[kParams * (long long)slot + 2] : NAN, k[3] = ok ? d.cam_dist[kParams * (long long)slot + 3] : NAN;
+      ok = ok && ba_finite(k[2]) && ba_finite(k[3]);
+    }
+    ba_project_dist<kDist>(row, k, X, Y, Xc, fu, xu, xv, rd, ju, jv);
     fv = fu;                                                 // 1 / Xc_z: the rows of J_c below are then the pinhole ones at fx = fy = 1
   } else {
     ba_project(row, X, Y, Xc, fu, fv, xu, xv, ju, jv);
@@ -261,12 +243,12 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
   const double z = Xc[2];
   ok = ok && z > 0.0;                                        // false for NaN
   const double fx = row[12], fy = row[13], cx = row[14], cy = row[15];
-  double ru = kRadial ? fx * rd.jt[0] + cx - u : fx * Xc[0] / z + cx - u, rv = kRadial ? fy * rd.jt[1] + cy - v : fy * Xc[1] / z + cy - v;
+  double ru = kDistorted ? fx * rd.jt[0] + cx - u : fx * Xc[0] / z + cx - u, rv = kDistorted ? fy * rd.jt[1] + cy - v : fy * Xc[1] / z + cy - v;
   const double au = fu * xu, av = fv * xv;
   // J_c = J_pi [ -[R X]x | I ]: the pose is perturbed on the left, Xc(w, dt) = Rot(w) (R X) + t + dt
   double cu[6] = {-(au * Y[1]), fu * Y[2] + au * Y[0], -(fu * Y[1]), fu, 0.0, -au};
   double cv[6] = {-(fv * Y[2] + av * Y[1]), av * Y[0], fv * Y[0], 0.0, fv, -av};
-  if (kRadial) {
+  if (kDistorted) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       const double mu = cu[i], mv = cv[i];
@@ -274,7 +256,7 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
       cv[i] = fy * (rd.d01 * mu + rd.d11 * mv);
     }
   }
-  rho = 0.0, sw = 1.0;                                      // without a loss the caller forms |r|^2 itself, as it always did
+  rho = 0.0, sw = 1.0;                                      // without a loss the caller forms |r|^2 itself
   if (kLoss) {
     double w;
     ba_loss(loss, ru * ru + rv * rv, rho, w);
@@ -302,11 +284,10 @@ __host__ __device__ __forceinline__ bool ba_observe(const BaProblem& d, const Ba
 
 // One point: its track linearised -> V^-1 (damped, 0 where the point is constant), g_p, cost, the usable count; per
 // observation of the track obs_ok and obs_lin and, with a loss, obs_w: sw of a usable observation, 0 of any other.
-template <bool kLoss, int kDist = kBaDistNone>
+template <bool kLoss, int kDist>
 __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, const BaLoss& loss, int j, double lambda, double (&vinv)[6],
                                                            double (&gp)[3], double& cost, uint8_t* __restrict__ obs_ok,
-                                                           double* __restrict__ obs_lin, double* __restrict__ obs_w,
-                                                           const double* __restrict__ cam_dist = nullptr) {
+                                                           double* __restrict__ obs_lin, double* __restrict__ obs_w) {
 #pragma unroll
   for (int k = 0; k < 6; ++k) vinv[k] = 0.0;
   gp[0] = gp[1] = gp[2] = 0.0;
@@ -318,7 +299,7 @@ __host__ __device__ __forceinline__ int ba_linearize_point(const BaProblem& d, c
   for (int o = lo; o < hi; ++o) {
     double* lin = obs_lin + (long long)o * kBaLin;
     double ju[3], jv[3], rho, sw;
-    const bool ok = ba_observe<kLoss, kDist>(d, loss, o, X, lin, ju, jv, rho, sw, cam_dist);
+    const bool ok = ba_observe<kLoss, kDist>(d, loss, o, X, lin, ju, jv, rho, sw);
     obs_ok[o] = ok ? 1 : 0;
     if (kLoss) obs_w[o] = ok ? sw : 0.0;
     if (!ok) continue;
@@ -627,12 +608,10 @@ __host__ __device__ __forceinline__ void ba_pose_step(const double* __restrict__
   for (int i = 12; i < 16; ++i) out[i] = cam[i];
 }
 
-// ---- the border of the intrinsics (vc_ba_linearize_intrinsics, vc_ba_reduce_border, vc_ba_step_intrinsics) ----------------------
-// The unknowns theta_g = (fx, fy, cx, cy) of every group of cameras join the reduced system as a border [[S, B], [B', C]];
-// S and g stay vc_ba_reduce_cameras'.
-// With the distortion (the _radial entry points) theta_g = (fx, fy, cx, cy, k1, k2): the same routines with N = 6 unknowns per
-// group where they have N = 4 without it.
-constexpr int kBaT = 12;                                                      // T_{j,g} = sum J_theta' J_p, 4x3 row-major
+// ---- the border of the intrinsics (linearize intrinsics, reduce border, the step with groups) -----------------------------------
+// The N = ba_dist_unknowns(kDist) unknowns theta_g of every group of cameras, (fx, fy, cx, cy) and the model's row of cam_dist
+// after them, join the reduced system as a border [[S, B], [B', C]]; S and g stay vc_ba_reduce_cameras'.  T_{j,g} = sum J_theta' J_p
+// is Nx3 row-major.
 constexpr int kBaBorderSlots = (24 * VC_BA_MAX_GROUPS + kBaWave - 1) / kBaWave;   // entries of a camera's B row block per lane
 static_assert((36 * VC_BA_MAX_GROUPS_RADIAL + kBaWave - 1) / kBaWave <= kBaBorderSlots, "B_a [6][6 G] of the radial limit must fit a lane's slots");
 static_assert((48 * VC_BA_MAX_GROUPS_OPENCV + kBaWave - 1) / kBaWave <= kBaBorderSlots, "B_a [6][8 G] of the OPENCV limit must fit a lane's slots");
@@ -645,15 +624,15 @@ struct BaGroups {
 
 // The rows of the per-point terms [ba_term_rows(G)][n_points] (entry-major: a point per lane writes a row and a wave per row
 // reads it, both coalesced): q_{j,g} NxN, hq_{j,g}, p_{j,g} = T V^-1 g_p, P_{j,g,g'} = T_g V^-1 T_g'' NxN.
-template <int N = 4>
+template <int N>
 __host__ __device__ constexpr int ba_term_q(int G, int g) { return N * N * g; }
-template <int N = 4>
+template <int N>
 __host__ __device__ constexpr int ba_term_hq(int G, int g) { return N * N * G + N * g; }
-template <int N = 4>
+template <int N>
 __host__ __device__ constexpr int ba_term_p(int G, int g) { return (N * N + N) * G + N * g; }
-template <int N = 4>
+template <int N>
 __host__ __device__ constexpr int ba_term_P(int G, int g, int g2) { return (N * N + 2 * N) * G + N * N * (g * G + g2); }
-template <int N = 4>
+template <int N>
 __host__ __device__ constexpr int ba_term_rows(int G) { return (N * N + 2 * N) * G + N * N * G * G; }
 
 // Camera slot -> its group, -1 where the slot's group is outside [0, n_groups): its intrinsics are held.  Without groups
@@ -664,75 +643,53 @@ __host__ __device__ __forceinline__ int ba_group_of(const BaGroups& gr, int slot
   return g >= 0 && g < gr.n_groups ? g : -1;
 }
 
-__host__ __device__ __forceinline__ bool ba_theta_held(unsigned mask, int i) { return ((mask >> i) & 1u) || (((mask >> 4) & 1u) && i == 1); }
-
-// Column i of J_theta = [[x, 0, 1, 0], [0, y, 0, 1]] at the normalised point (x, y); tied: column 0 is (x, y); a held column is 0.
-__host__ __device__ __forceinline__ void ba_jtheta(unsigned mask, double x, double y, int i, double& tu, double& tv) {
-  const bool tied = (mask >> 4) & 1u;
-  tu = i == 0 ? x : i == 2 ? 1.0 : 0.0;
-  tv = i == 0 ? (tied ? y : 0.0) : i == 1 ? y : i == 3 ? 1.0 : 0.0;
-  if (ba_theta_held(mask, i)) tu = tv = 0.0;
-}
-
-// The six unknowns: parameter i < 4 as above; k1 (i = 4) is held by bit 5 of the mask, k2 (i = 5) by bit 6.
-__host__ __device__ __forceinline__ bool ba_theta_held_radial(unsigned mask, int i) {
-  return i < 4 ? ba_theta_held(mask, i) : ((mask >> (i + 1)) & 1u) != 0;
-}
-
-// The eight unknowns: parameter i < 6 as above; p1 (i = 6) and p2 (i = 7) are held together by bit 7.
-__host__ __device__ __forceinline__ bool ba_theta_held_opencv(unsigned mask, int i) {
-  return i < 6 ? ba_theta_held_radial(mask, i) : ((mask >> 7) & 1u) != 0;
-}
-
+// Parameter i < N of a group is held: fx fy cx cy by bits 0-3 of its mask, fy of a tied group (bit 4) too; k1 (i = 4) by bit 5,
+// k2 (i = 5) by bit 6; p1 (i = 6) and p2 (i = 7) together by bit 7.
 template <int N>
-__host__ __device__ __forceinline__ bool ba_held(unsigned mask, int i) {
-  return N == 8 ? ba_theta_held_opencv(mask, i) : N == 6 ? ba_theta_held_radial(mask, i) : ba_theta_held(mask, i);
+__host__ __device__ __forceinline__ bool ba_theta_held(unsigned mask, int i) {
+  if (N > 6 && i >= 6) return ((mask >> 7) & 1u) != 0;
+  if (N > 4 && i >= 4) return ((mask >> (i + 1)) & 1u) != 0;
+  return ((mask >> i) & 1u) || (((mask >> 4) & 1u) && i == 1);
 }
 
-// Column i of J_theta = [[xd, 0, 1, 0, pu, qu], [0, yd, 0, 1, pv, qv]] from jt = (xd, yd, pu, pv, qu, qv); tied: column 0 is
-// (xd, yd); a held column is 0.  i may be a runtime value: the column is selected, not indexed.
-__host__ __device__ __forceinline__ void ba_jtheta_radial(unsigned mask, const double* jt, int i, double& tu, double& tv) {
-  const bool tied = (mask >> 4) & 1u;
-  tu = i == 0 ? jt[0] : i == 2 ? 1.0 : i == 4 ? jt[2] : i == 5 ? jt[4] : 0.0;
-  tv = i == 0 ? (tied ? jt[1] : 0.0) : i == 1 ? jt[1] : i == 3 ? 1.0 : i == 4 ? jt[3] : i == 5 ? jt[5] : 0.0;
-  if (ba_theta_held_radial(mask, i)) tu = tv = 0.0;
-}
-
-// Column i of the eight-column J_theta from jt[10]: the six of ba_jtheta_radial, then the p1 column (jt[6], jt[7]) and the p2
-// column (jt[8], jt[9]); selected by compares, as there.
-__host__ __device__ __forceinline__ void ba_jtheta_opencv(unsigned mask, const double* jt, int i, double& tu, double& tv) {
-  const bool tied = (mask >> 4) & 1u;
-  tu = i == 0 ? jt[0] : i == 2 ? 1.0 : i == 4 ? jt[2] : i == 5 ? jt[4] : i == 6 ? jt[6] : i == 7 ? jt[8] : 0.0;
-  tv = i == 0 ? (tied ? jt[1] : 0.0) : i == 1 ? jt[1] : i == 3 ? 1.0 : i == 4 ? jt[3] : i == 5 ? jt[5] : i == 6 ? jt[7] : i == 7 ? jt[9] : 0.0;
-  if (ba_theta_held_opencv(mask, i)) tu = tv = 0.0;
-}
-
+// Column i of J_theta = [[xd, 0, 1, 0, pu, qu, ..], [0, yd, 0, 1, pv, qv, ..]] from the observation's row jt of obs_jt: (x, y) for the
+// pinhole, (xd, yd, pu, pv, qu, qv) under the radial distortion, then the p1 column (jt[6], jt[7]) and the p2 column (jt[8], jt[9])
+// under OPENCV; tied: column 0 is (xd, yd); a held column is 0.  i may be a runtime value: the column is selected, not indexed.
 template <int kDist>
-__host__ __device__ __forceinline__ void ba_jtheta_dist(unsigned mask, const double* jt, int i, double& tu, double& tv) {
-  if constexpr (kDist == kBaDistOpencv) ba_jtheta_opencv(mask, jt, i, tu, tv);
-  else ba_jtheta_radial(mask, jt, i, tu, tv);
+__host__ __device__ __forceinline__ void ba_jtheta(unsigned mask, const double* jt, int i, double& tu, double& tv) {
+  const bool tied = (mask >> 4) & 1u;
+  tu = i == 0 ? jt[0] : i == 2 ? 1.0 : 0.0;
+  tv = i == 0 ? (tied ? jt[1] : 0.0) : i == 1 ? jt[1] : i == 3 ? 1.0 : 0.0;
+  if constexpr (kDist != kBaDistNone) {
+    tu = i == 4 ? jt[2] : i == 5 ? jt[4] : tu;
+    tv = i == 4 ? jt[3] : i == 5 ? jt[5] : tv;
+  }
+  if constexpr (kDist == kBaDistOpencv) {
+    tu = i == 6 ? jt[6] : i == 7 ? jt[8] : tu;
+    tv = i == 6 ? jt[7] : i == 7 ? jt[9] : tv;
+  }
+  if (ba_theta_held<ba_dist_unknowns(kDist)>(mask, i)) tu = tv = 0.0;
 }
 
-// A usable observation of X in camera row c again: x = Xc_x / Xc_z, y = Xc_y / Xc_z and J_p.
-__host__ __device__ __forceinline__ void ba_observe_point(const double* __restrict__ c, const double (&X)[3], double& xu, double& xv,
+// A usable observation of X in camera slot again: its row of obs_jt and J_p.  The pinhole projects with the row as it is.
+template <int kDist>
+__host__ __device__ __forceinline__ void ba_observe_point(const BaProblem& d, int slot, const double (&X)[3], BaDistortion<kDist>& rd,
                                                           double (&ju)[3], double (&jv)[3]) {
-  double Y[3], Xc[3], fu, fv;
-  ba_project(c, X, Y, Xc, fu, fv, xu, xv, ju, jv);
+  const double* c = d.cams + 16 * (long long)slot;
+  double Y[3], Xc[3], fu, fv, xu, xv;
+  if constexpr (kDist == kBaDistNone) ba_project(c, X, Y, Xc, fu, fv, rd.jt[0], rd.jt[1], ju, jv);
+  else ba_project_dist<kDist>(c, d.cam_dist + ba_dist_params(kDist) * (long long)slot, X, Y, Xc, fu, xu, xv, rd, ju, jv);
 }
 
-// One point: obs_xn of its track; per group (outside) over the track (inside) T, q, hq; then the point's products with V^-1.
+// One point: obs_jt of its track; per group (outside) over the track (inside) T, q, hq; then the point's products with V^-1.
 // A point whose offsets delimit nothing has T and its terms 0 and nothing of its track read or written.  With a loss J_p and
-// J_theta (its constant columns too) are multiplied by obs_w[o], as the points pass multiplied what it left in obs_lin; obs_xn
-// stays the unscaled (x, y).  kRadial: N = 6 unknowns per group, the observation is ba_project_radial's under cam_dist, and
-// obs_xn is obs_jt [total][6], the unscaled (xd, yd, pu, pv, qu, qv) of a usable observation and zeros of any other.
-// kBaDistOpencv: N = 8, ba_project_opencv, obs_jt [total][10].
-template <bool kLoss, int kDist = kBaDistNone>
+// J_theta (its constant columns too) are multiplied by obs_w[o], as the points pass multiplied what it left in obs_lin; obs_jt
+// stays unscaled: the row of ba_observe_point of a usable observation, zeros of any other.
+template <bool kLoss, int kDist>
 __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaProblem& d, const BaLinear& l, const BaGroups& gr,
-                                                                       const double* __restrict__ obs_w, int j, double* __restrict__ obs_xn,
-                                                                       double* T, double* __restrict__ terms,
-                                                                       const double* __restrict__ cam_dist = nullptr) {
-  constexpr bool kRadial = kDist != kBaDistNone;
-  constexpr int N = ba_dist_unknowns(kDist), NT = kRadial ? 3 * N : kBaT, kJt = ba_dist_jt(kDist), kParams = ba_dist_params(kDist);
+                                                                       const double* __restrict__ obs_w, int j, double* __restrict__ obs_jt,
+                                                                       double* T, double* __restrict__ terms) {
+  constexpr int N = ba_dist_unknowns(kDist), NT = 3 * N, kJt = ba_dist_jt(kDist);
   const int G = gr.n_groups;
   const long long n = d.n_points;
   int lo, hi;
@@ -741,21 +698,13 @@ __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaP
   if (lo < hi) X[0] = d.points[3 * (long long)j], X[1] = d.points[3 * (long long)j + 1], X[2] = d.points[3 * (long long)j + 2];
   for (int o = lo; o < hi; ++o) {
     const int slot = d.obs_cam[o];
-    if constexpr (kRadial) {
-      BaDistortion<kDist> rd;
+    BaDistortion<kDist> rd;
+    double ju[3], jv[3];
 #pragma unroll
-      for (int k = 0; k < kJt; ++k) rd.jt[k] = 0.0;
-      if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) {
-        double Y[3], Xc[3], iu, xu, xv, ju[3], jv[3];
-        ba_project_dist<kDist>(d.cams + 16 * (long long)slot, cam_dist + kParams * (long long)slot, X, Y, Xc, iu, xu, xv, rd, ju, jv);
-      }
+    for (int k = 0; k < kJt; ++k) rd.jt[k] = 0.0;
+    if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) ba_observe_point<kDist>(d, slot, X, rd, ju, jv);
 #pragma unroll
-      for (int k = 0; k < kJt; ++k) obs_xn[kJt * (long long)o + k] = rd.jt[k];
-    } else {
-      double x = 0.0, y = 0.0, ju[3], jv[3];
-      if (l.obs_ok[o] && slot >= 0 && slot < d.n_cams) ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
-      obs_xn[2 * (long long)o] = x, obs_xn[2 * (long long)o + 1] = y;
-    }
+    for (int k = 0; k < kJt; ++k) obs_jt[kJt * (long long)o + k] = rd.jt[k];
   }
   double* Tj = T + (long long)j * G * NT;
   for (int g = 0; g < G; ++g) {
@@ -770,19 +719,11 @@ __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaP
     for (int o = lo; o < hi; ++o) {
       const int slot = d.obs_cam[o];
       if (!l.obs_ok[o] || slot < 0 || slot >= d.n_cams || ba_group_of(gr, slot) != g) continue;
+      BaDistortion<kDist> rd;
       double ju[3], jv[3], tu[N], tv[N];
-      if constexpr (kRadial) {
-        BaDistortion<kDist> rd;
-        double Y[3], Xc[3], iu, xu, xv;
-        ba_project_dist<kDist>(d.cams + 16 * (long long)slot, cam_dist + kParams * (long long)slot, X, Y, Xc, iu, xu, xv, rd, ju, jv);
+      ba_observe_point<kDist>(d, slot, X, rd, ju, jv);
 #pragma unroll
-        for (int i = 0; i < N; ++i) ba_jtheta_dist<kDist>(mask, rd.jt, i, tu[i], tv[i]);
-      } else {
-        double x, y;
-        ba_observe_point(d.cams + 16 * (long long)slot, X, x, y, ju, jv);
-#pragma unroll
-        for (int i = 0; i < N; ++i) ba_jtheta(mask, x, y, i, tu[i], tv[i]);
-      }
+      for (int i = 0; i < N; ++i) ba_jtheta<kDist>(mask, rd.jt, i, tu[i], tv[i]);
       if (kLoss) {
         const double sw = obs_w[o];
 #pragma unroll
@@ -832,13 +773,13 @@ __host__ __device__ __forceinline__ void ba_linearize_point_intrinsics(const BaP
 }
 
 // Parameter i of group g moves: not held, not parameter 1 of a tied group, and some usable observation moves it (Q_ii != 0).
-template <int N = 4>
+template <int N>
 __host__ __device__ __forceinline__ bool ba_theta_free(const double* __restrict__ sums, const BaGroups& gr, int g, int i) {
-  return !ba_held<N>(gr.intr_mask[g], i) && sums[ba_term_q<N>(gr.n_groups, g) + (N + 1) * i] != 0.0;
+  return !ba_theta_held<N>(gr.intr_mask[g], i) && sums[ba_term_q<N>(gr.n_groups, g) + (N + 1) * i] != 0.0;
 }
 
 // Entry (row, col) of C from the ordered sums: delta Q (its diagonal damped) - sum P; the identity where a parameter does not move.
-template <int N = 4>
+template <int N>
 __host__ __device__ __forceinline__ double ba_border_c(const double* __restrict__ sums, const BaGroups& gr, double lambda, int row, int col) {
   const int G = gr.n_groups, g = row / N, i = row % N, h = col / N, k = col % N;
   if (!ba_theta_free<N>(sums, gr, g, i) || !ba_theta_free<N>(sums, gr, h, k)) return row == col ? 1.0 : 0.0;
@@ -850,39 +791,32 @@ __host__ __device__ __forceinline__ double ba_border_c(const double* __restrict_
   return q - sums[ba_term_P<N>(G, g, h) + N * i + k];
 }
 
-template <int N = 4>
+template <int N>
 __host__ __device__ __forceinline__ double ba_border_h(const double* __restrict__ sums, const BaGroups& gr, int row) {
   const int G = gr.n_groups, g = row / N, i = row % N;
   return ba_theta_free<N>(sums, gr, g, i) ? sums[ba_term_hq<N>(G, g) + i] - sums[ba_term_p<N>(G, g) + i] : 0.0;
 }
 
-// The registers of one lane of the border's camera pass: entry idx = lane + 64 k of the row block B_a [6][4 G], as g = idx / 24,
-// r = idx % 24 / 4, i = idx % 4, and its two sums.
+// The registers of one lane of the border's camera pass: entry idx = lane + 64 k of the row block B_a [6][N G], as g = idx / (6 N),
+// r = idx % (6 N) / N, i = idx % N, and its two sums.
 struct BaBorderLane {
   double jt[kBaBorderSlots], yt[kBaBorderSlots];
 };
 
 // One lane's additions for the usable observation o of camera a (its group ga or -1, its point j, y as ba_prepare left it).
 // With a loss the column of J_theta is multiplied by obs_w[o]; obs_lin and T carry the weight already.
-// kRadial: the row block is B_a [6][6 G], entry idx as g = idx / 36, r = idx % 36 / 6, i = idx % 6, and obs_xn is obs_jt.
-// kBaDistOpencv: B_a [6][8 G], g = idx / 48, r = idx % 48 / 8, i = idx % 8, obs_jt [total][10].
-template <bool kLoss, int kDist = kBaDistNone>
-__host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, const BaGroups& gr, const double* __restrict__ obs_xn,
+template <bool kLoss, int kDist>
+__host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, const BaGroups& gr, const double* __restrict__ obs_jt,
                                                           const double* __restrict__ obs_w, const double* __restrict__ T, int ga, int o,
                                                           int j, int lane, const double* y, BaBorderLane& s) {
-  constexpr bool kRadial = kDist != kBaDistNone;
   constexpr int N = ba_dist_unknowns(kDist), kJt = ba_dist_jt(kDist);
   const int G = gr.n_groups;
   const double sw = kLoss ? obs_w[o] : 1.0;
   const double* lin = l.obs_lin + (long long)o * kBaLin;
   const unsigned mask = ga >= 0 ? gr.intr_mask[ga] : 0u;
   double jt[kJt];
-  if (kRadial) {
 #pragma unroll
-    for (int k = 0; k < kJt; ++k) jt[k] = obs_xn[kJt * (long long)o + k];
-  } else {
-    jt[0] = obs_xn[2 * (long long)o], jt[1] = obs_xn[2 * (long long)o + 1];
-  }
+  for (int k = 0; k < kJt; ++k) jt[k] = obs_jt[kJt * (long long)o + k];
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) {
     const int idx = lane + kBaWave * k;
@@ -890,8 +824,7 @@ __host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, con
     const int g = idx / (6 * N), r = idx % (6 * N) / N, i = idx % N;
     if (g == ga) {
       double tu, tv;
-      if constexpr (kRadial) ba_jtheta_dist<kDist>(mask, jt, i, tu, tv);
-      else ba_jtheta(mask, jt[0], jt[1], i, tu, tv);
+      ba_jtheta<kDist>(mask, jt, i, tu, tv);
       if (kLoss) tu = sw * tu, tv = sw * tv;
       s.jt[k] += lin[r] * tu + lin[6 + r] * tv;
     }
@@ -900,7 +833,7 @@ __host__ __device__ __forceinline__ void ba_border_update(const BaLinear& l, con
   }
 }
 
-template <int N = 4>
+template <int N>
 __host__ __device__ __forceinline__ void ba_border_finish(int G, int a, int lane, const BaBorderLane& s, double* __restrict__ B) {
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) {
@@ -910,8 +843,9 @@ __host__ __device__ __forceinline__ void ba_border_finish(int G, int a, int lane
 }
 
 // One point's step: dX = -V^-1 (g_p + sum W' dc + sum_g T_g' dtheta_g), the track in track order, then the groups in ascending
-// order; 0 where the point's offsets delimit nothing.  Without groups T and dtheta are not read.
-template <int N = 4>
+// order, a group's N products added left to right onto the first; 0 where the point's offsets delimit nothing.  Without groups T
+// and dtheta are not read.
+template <int N>
 __host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const BaLinear& l, const double* __restrict__ T, int G,
                                                        const double* __restrict__ dc, const double* __restrict__ dtheta, int j,
                                                        double (&dX)[3]) {
@@ -934,11 +868,10 @@ __host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const
     const double* e = dtheta + N * g;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      if (N == 8)
-        s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3] + t[12 + k] * e[4] + t[15 + k] * e[5] + t[18 + k] * e[6] +
-                t[21 + k] * e[7];
-      else if (N == 6) s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3] + t[12 + k] * e[4] + t[15 + k] * e[5];
-      else s[k] += t[k] * e[0] + t[3 + k] * e[1] + t[6 + k] * e[2] + t[9 + k] * e[3];
+      double sum = t[k] * e[0];
+#pragma unroll
+      for (int i = 1; i < N; ++i) sum = sum + t[3 * i + k] * e[i];
+      s[k] += sum;
     }
   }
   const double* v = l.vinv + (long long)j * 6;
@@ -947,57 +880,28 @@ __host__ __device__ __forceinline__ void ba_point_step(const BaProblem& d, const
   dX[2] = -(v[2] * s[0] + v[4] * s[1] + v[5] * s[2]);
 }
 
-// One camera's step: ba_pose_step, then (fx, fy, cx, cy) += dtheta of its group (tied: dtheta_0 to both focal lengths) -> whether
-// the candidate's focal lengths are finite and positive (true where the intrinsics are held: no group, or one outside the table).
-__host__ __device__ __forceinline__ bool ba_camera_step(const double* __restrict__ cam, const double* __restrict__ e, const BaGroups& gr,
-                                                        int a, const double* __restrict__ dtheta, double* __restrict__ out) {
-  ba_pose_step(cam, e, out);
-  const int g = ba_group_of(gr, a);
-  if (g < 0) return true;
-  const double* th = dtheta + 4 * g;
-  const bool tied = (gr.intr_mask[g] >> 4) & 1u;
-  const double fx = cam[12] + th[0], fy = cam[13] + (tied ? th[0] : th[1]);
-  out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
-  return ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0;
-}
-
-// The same with six unknowns per group: (k1, k2) of dist[2] += dtheta_4, dtheta_5 into out_dist[2] (copied where the intrinsics
-// are held) -> focal lengths finite and positive, k1 and k2 finite.
-__host__ __device__ __forceinline__ bool ba_camera_step_radial(const double* __restrict__ cam, const double* __restrict__ dist,
-                                                               const double* __restrict__ e, const BaGroups& gr, int a,
-                                                               const double* __restrict__ dtheta, double* __restrict__ out,
-                                                               double* __restrict__ out_dist) {
-  ba_pose_step(cam, e, out);
-  out_dist[0] = dist[0], out_dist[1] = dist[1];
-  const int g = ba_group_of(gr, a);
-  if (g < 0) return true;
-  const double* th = dtheta + 6 * g;
-  const bool tied = (gr.intr_mask[g] >> 4) & 1u;
-  const double fx = cam[12] + th[0], fy = cam[13] + (tied ? th[0] : th[1]);
-  const double k1 = dist[0] + th[4], k2 = dist[1] + th[5];
-  out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
-  out_dist[0] = k1, out_dist[1] = k2;
-  return ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0 && ba_finite(k1) && ba_finite(k2);
-}
-
-// The same with eight unknowns per group: (k1, k2, p1, p2) of dist[4] += dtheta_4 .. dtheta_7 into out_dist[4] (copied where the
-// intrinsics are held) -> focal lengths finite and positive, all four distortion numbers finite.
-__host__ __device__ __forceinline__ bool ba_camera_step_opencv(const double* __restrict__ cam, const double* __restrict__ dist,
-                                                               const double* __restrict__ e, const BaGroups& gr, int a,
-                                                               const double* __restrict__ dtheta, double* __restrict__ out,
-                                                               double* __restrict__ out_dist) {
+// One camera's step: ba_pose_step, then (fx, fy, cx, cy) += dtheta_0 .. dtheta_3 of its group (tied: dtheta_0 to both focal lengths)
+// and its row of cam_dist += the dtheta after them into out_dist (copied where the intrinsics are held: no group, or one outside
+// the table) -> whether the candidate's focal lengths are finite and positive and its distortion finite (true where held).  The
+// pinhole has neither dist nor out_dist.
+template <int kDist>
+__host__ __device__ __forceinline__ bool ba_camera_step(const double* __restrict__ cam, const double* __restrict__ dist,
+                                                        const double* __restrict__ e, const BaGroups& gr, int a,
+                                                        const double* __restrict__ dtheta, double* __restrict__ out,
+                                                        double* __restrict__ out_dist) {
+  constexpr int kParams = ba_dist_params(kDist);
   ba_pose_step(cam, e, out);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) out_dist[i] = dist[i];
+  for (int i = 0; i < kParams; ++i) out_dist[i] = dist[i];
   const int g = ba_group_of(gr, a);
   if (g < 0) return true;
-  const double* th = dtheta + 8 * g;
+  const double* th = dtheta + ba_dist_unknowns(kDist) * g;
   const bool tied = (gr.intr_mask[g] >> 4) & 1u;
   const double fx = cam[12] + th[0], fy = cam[13] + (tied ? th[0] : th[1]);
   out[12] = fx, out[13] = fy, out[14] = cam[14] + th[2], out[15] = cam[15] + th[3];
   bool valid = ba_finite(fx) && ba_finite(fy) && fx > 0.0 && fy > 0.0;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < kParams; ++i) {
     const double k = dist[i] + th[4 + i];
     out_dist[i] = k;
     valid = valid && ba_finite(k);
@@ -1005,18 +909,16 @@ __host__ __device__ __forceinline__ bool ba_camera_step_opencv(const double* __r
   return valid;
 }
 
-// kLoss = false: loss and out_obs_w are absent and not read (vc_ba_linearize_points).  What a loss adds comes last in the three
-// kernels' arguments, so that without it the others sit where they sat.
-template <bool kLoss>
-__global__ __launch_bounds__(kBaWave) void ba_linearize_points_kernel(BaProblem d, double lambda, double* __restrict__ out_vinv,
+// ---- the kernels of the passes.  Without a loss, loss and obs_w are absent and not read; cam_dist travels in the BaProblem ------
+template <bool kLoss, int kDist>
+__global__ __launch_bounds__(kBaWave) void ba_linearize_points_kernel(BaProblem d, double lambda, BaLoss loss, double* __restrict__ out_vinv,
                                                                       double* __restrict__ out_gp, double* __restrict__ out_cost,
                                                                       int32_t* __restrict__ out_count, uint8_t* __restrict__ out_obs_ok,
-                                                                      double* __restrict__ out_obs_lin, BaLoss loss,
-                                                                      double* __restrict__ out_obs_w) {
+                                                                      double* __restrict__ out_obs_lin, double* __restrict__ out_obs_w) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (j >= d.n_points) return;
   double vinv[6], gp[3], cost;
-  const int count = ba_linearize_point<kLoss>(d, loss, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin, out_obs_w);
+  const int count = ba_linearize_point<kLoss, kDist>(d, loss, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin, out_obs_w);
 #pragma unroll
   for (int k = 0; k < 6; ++k) out_vinv[6 * j + k] = vinv[k];
 #pragma unroll
@@ -1125,100 +1027,19 @@ __global__ __launch_bounds__(kBaProductThreads) void ba_product_cameras_kernel(B
   if (lane < 6) out_q[6 * (long long)a + lane] = ba_product_finish(U, fixed, p, a, lane, sum);
 }
 
-template <bool kLoss>
-__global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_kernel(BaProblem d, BaLinear l, BaGroups gr, double* __restrict__ out_obs_xn,
-                                                                          double* out_T, double* __restrict__ out_terms,
-                                                                          const double* __restrict__ obs_w) {
+template <bool kLoss, int kDist>
+__global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_kernel(BaProblem d, BaLinear l, BaGroups gr, const double* __restrict__ obs_w,
+                                                                          double* __restrict__ out_obs_jt, double* out_T,
+                                                                          double* __restrict__ out_terms) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (j < d.n_points) ba_linearize_point_intrinsics<kLoss>(d, l, gr, obs_w, (int)j, out_obs_xn, out_T, out_terms);
+  if (j < d.n_points) ba_linearize_point_intrinsics<kLoss, kDist>(d, l, gr, obs_w, (int)j, out_obs_jt, out_T, out_terms);
 }
 
 // C, h and which parameters move, from the ordered sums: one entry per lane.
+template <int N>
 __global__ __launch_bounds__(kBaWave) void ba_border_system_kernel(const double* __restrict__ sums, BaGroups gr, double lambda,
                                                                    double* __restrict__ out_C, double* __restrict__ out_h,
                                                                    uint8_t* __restrict__ out_free) {
-  const int m = 4 * gr.n_groups;
-  for (int idx = threadIdx.x; idx < m * m; idx += kBaWave) out_C[idx] = ba_border_c(sums, gr, lambda, idx / m, idx % m);
-  for (int row = threadIdx.x; row < m; row += kBaWave) {
-    out_h[row] = ba_border_h(sums, gr, row);
-    out_free[row] = ba_theta_free(sums, gr, row / 4, row % 4) ? 1 : 0;
-  }
-}
-
-// B_a: one wave per camera over its list, a lane's entries in its registers.
-template <bool kLoss>
-__global__ __launch_bounds__(kBaWave) void ba_reduce_border_kernel(BaProblem d, BaLinear l, BaGroups gr, const int32_t* __restrict__ cam_offsets,
-                                                                   const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
-                                                                   const double* __restrict__ obs_xn, const double* __restrict__ T,
-                                                                   double* __restrict__ out_B, const double* __restrict__ obs_w) {
-  __shared__ BaBatch batch;
-  const int a = blockIdx.x, lane = threadIdx.x;
-  const int ga = ba_group_of(gr, a);
-  BaBorderLane s;
-#pragma unroll
-  for (int k = 0; k < kBaBorderSlots; ++k) s.jt[k] = s.yt[k] = 0.0;
-  ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
-                 [&](int o, int j, int, int, const double* y) { ba_border_update<kLoss>(l, gr, obs_xn, obs_w, T, ga, o, j, lane, y, s); });
-  ba_border_finish(gr.n_groups, a, lane, s, out_B);
-}
-
-__global__ __launch_bounds__(kBaWave) void ba_step_points_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
-                                                                 const double* __restrict__ dc, const double* __restrict__ dtheta,
-                                                                 double* __restrict__ out_points, double* __restrict__ out_dx) {
-  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (j >= d.n_points) return;
-  double dX[3];
-  ba_point_step(d, l, T, n_groups, dc, dtheta, (int)j, dX);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    out_dx[3 * j + k] = dX[k];
-    out_points[3 * j + k] = d.points[3 * j + k] + dX[k];
-  }
-}
-
-// out_valid may be absent (vc_ba_step: no intrinsics move, every candidate is valid).
-__global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(const double* __restrict__ cams, int n_cams, BaGroups gr,
-                                                                  const double* __restrict__ dc, const double* __restrict__ dtheta,
-                                                                  double* __restrict__ out_cams, uint8_t* __restrict__ out_valid) {
-  const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (a >= n_cams) return;
-  const bool valid = ba_camera_step(cams + 16 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a);
-  if (out_valid) out_valid[a] = valid ? 1 : 0;
-}
-
-// ---- the kernels of the _radial and _opencv entry points: the routines above under kDist = kBaDistRadial and kBaDistOpencv,
-// every one with the loss (VC_BA_LOSS_TRIVIAL gives rho = s and sw = 1, and a product with 1.0 is exact) --------------------------
-template <int kDist>
-__global__ __launch_bounds__(kBaWave) void ba_linearize_points_dist_kernel(BaProblem d, const double* __restrict__ cam_dist, double lambda,
-                                                                             BaLoss loss, double* __restrict__ out_vinv,
-                                                                             double* __restrict__ out_gp, double* __restrict__ out_cost,
-                                                                             int32_t* __restrict__ out_count, uint8_t* __restrict__ out_obs_ok,
-                                                                             double* __restrict__ out_obs_lin, double* __restrict__ out_obs_w) {
-  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (j >= d.n_points) return;
-  double vinv[6], gp[3], cost;
-  const int count = ba_linearize_point<true, kDist>(d, loss, (int)j, lambda, vinv, gp, cost, out_obs_ok, out_obs_lin, out_obs_w, cam_dist);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) out_vinv[6 * j + k] = vinv[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) out_gp[3 * j + k] = gp[k];
-  out_cost[j] = cost;
-  out_count[j] = count;
-}
-
-template <int kDist>
-__global__ __launch_bounds__(kBaWave) void ba_linearize_intrinsics_dist_kernel(BaProblem d, BaLinear l, BaGroups gr,
-                                                                                 const double* __restrict__ cam_dist,
-                                                                                 const double* __restrict__ obs_w, double* __restrict__ out_obs_jt,
-                                                                                 double* out_T, double* __restrict__ out_terms) {
-  const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (j < d.n_points) ba_linearize_point_intrinsics<true, kDist>(d, l, gr, obs_w, (int)j, out_obs_jt, out_T, out_terms, cam_dist);
-}
-
-template <int N>
-__global__ __launch_bounds__(kBaWave) void ba_border_system_dist_kernel(const double* __restrict__ sums, BaGroups gr, double lambda,
-                                                                        double* __restrict__ out_C, double* __restrict__ out_h,
-                                                                        uint8_t* __restrict__ out_free) {
   const int m = N * gr.n_groups;
   for (int idx = threadIdx.x; idx < m * m; idx += kBaWave) out_C[idx] = ba_border_c<N>(sums, gr, lambda, idx / m, idx % m);
   for (int row = threadIdx.x; row < m; row += kBaWave) {
@@ -1227,12 +1048,12 @@ __global__ __launch_bounds__(kBaWave) void ba_border_system_dist_kernel(const do
   }
 }
 
-template <int kDist>
-__global__ __launch_bounds__(kBaWave) void ba_reduce_border_dist_kernel(BaProblem d, BaLinear l, BaGroups gr,
-                                                                          const int32_t* __restrict__ cam_offsets,
-                                                                          const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
-                                                                          const double* __restrict__ obs_jt, const double* __restrict__ obs_w,
-                                                                          const double* __restrict__ T, double* __restrict__ out_B) {
+// B_a: one wave per camera over its list, a lane's entries in its registers.
+template <bool kLoss, int kDist>
+__global__ __launch_bounds__(kBaWave) void ba_reduce_border_kernel(BaProblem d, BaLinear l, BaGroups gr, const int32_t* __restrict__ cam_offsets,
+                                                                   const int32_t* __restrict__ cam_obs, const int32_t* __restrict__ obs_point,
+                                                                   const double* __restrict__ obs_jt, const double* __restrict__ obs_w,
+                                                                   const double* __restrict__ T, double* __restrict__ out_B) {
   __shared__ BaBatch batch;
   const int a = blockIdx.x, lane = threadIdx.x;
   const int ga = ba_group_of(gr, a);
@@ -1240,14 +1061,14 @@ __global__ __launch_bounds__(kBaWave) void ba_reduce_border_dist_kernel(BaProble
 #pragma unroll
   for (int k = 0; k < kBaBorderSlots; ++k) s.jt[k] = s.yt[k] = 0.0;
   ba_camera_walk(d, l, cam_offsets, cam_obs, obs_point, a, lane, batch,
-                 [&](int o, int j, int, int, const double* y) { ba_border_update<true, kDist>(l, gr, obs_jt, obs_w, T, ga, o, j, lane, y, s); });
+                 [&](int o, int j, int, int, const double* y) { ba_border_update<kLoss, kDist>(l, gr, obs_jt, obs_w, T, ga, o, j, lane, y, s); });
   ba_border_finish<ba_dist_unknowns(kDist)>(gr.n_groups, a, lane, s, out_B);
 }
 
 template <int N>
-__global__ __launch_bounds__(kBaWave) void ba_step_points_dist_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
-                                                                        const double* __restrict__ dc, const double* __restrict__ dtheta,
-                                                                        double* __restrict__ out_points, double* __restrict__ out_dx) {
+__global__ __launch_bounds__(kBaWave) void ba_step_points_kernel(BaProblem d, BaLinear l, const double* __restrict__ T, int n_groups,
+                                                                 const double* __restrict__ dc, const double* __restrict__ dtheta,
+                                                                 double* __restrict__ out_points, double* __restrict__ out_dx) {
   const long long j = (long long)blockIdx.x * kBaWave + threadIdx.x;
   if (j >= d.n_points) return;
   double dX[3];
@@ -1259,197 +1080,119 @@ __global__ __launch_bounds__(kBaWave) void ba_step_points_dist_kernel(BaProblem 
   }
 }
 
+// out_valid may be absent (vc_ba_step: no intrinsics move, every candidate is valid); the pinhole has no out_dist.
 template <int kDist>
-__global__ __launch_bounds__(kBaWave) void ba_step_cameras_dist_kernel(const double* __restrict__ cams, const double* __restrict__ cam_dist,
-                                                                         int n_cams, BaGroups gr, const double* __restrict__ dc,
-                                                                         const double* __restrict__ dtheta, double* __restrict__ out_cams,
-                                                                         double* __restrict__ out_dist, uint8_t* __restrict__ out_valid) {
+__global__ __launch_bounds__(kBaWave) void ba_step_cameras_kernel(BaProblem d, BaGroups gr, const double* __restrict__ dc,
+                                                                  const double* __restrict__ dtheta, double* __restrict__ out_cams,
+                                                                  double* __restrict__ out_dist, uint8_t* __restrict__ out_valid) {
+  constexpr int kParams = ba_dist_params(kDist);
   const long long a = (long long)blockIdx.x * kBaWave + threadIdx.x;
-  if (a >= n_cams) return;
-  bool valid;
-  if constexpr (kDist == kBaDistOpencv)
-    valid = ba_camera_step_opencv(cams + 16 * a, cam_dist + 4 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a, out_dist + 4 * a);
-  else valid = ba_camera_step_radial(cams + 16 * a, cam_dist + 2 * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a, out_dist + 2 * a);
-  out_valid[a] = valid ? 1 : 0;
+  if (a >= d.n_cams) return;
+  const bool valid = ba_camera_step<kDist>(d.cams + 16 * a, d.cam_dist + kParams * a, dc + 6 * a, gr, (int)a, dtheta, out_cams + 16 * a,
+                                           out_dist + kParams * a);
+  if (out_valid) out_valid[a] = valid ? 1 : 0;
 }
 
-// The two kernels of a step; vc_ba_step has no groups: then T, dtheta, cam_group and out_valid are absent and none is read.
-int ba_launch_step(const BaProblem& d, const BaLinear& l, const BaGroups& gr, const double* T, const double* dc, const double* dtheta,
-                   double* out_cams, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
-  if (d.n_points > 0)
-    hipLaunchKernelGGL(ba_step_points_kernel, dim3((unsigned)((d.n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       d, l, T, gr.n_groups, dc, dtheta, out_points, out_dx);
-  if (d.n_cams > 0)
-    hipLaunchKernelGGL(ba_step_cameras_kernel, dim3((unsigned)((d.n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       d.cams, d.n_cams, gr, dc, dtheta, out_cams, out_valid);
-  return vc::check_launch();
-}
-
-// The three entry points that exist with and without a loss: the checks and the launches of both, once.  kLoss = false: loss,
-// out_obs_w and obs_w are absent and none is read.
-template <bool kLoss>
-int ba_launch_linearize_points(const double* cams, int n_cams, const uint8_t* const_mask, const double* points, int n_points,
-                               const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda, BaLoss loss,
-                               double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count, uint8_t* out_obs_ok,
+// ---- the launchers: the checks and the launches of an entry-point family, once.  cam_dist and out_dist are required exactly under
+// a distortion, obs_w and a valid loss exactly with kLoss; what an entry point does not have it passes as null ----------------------
+template <bool kLoss, int kDist>
+int ba_launch_linearize_points(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
+                               int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
+                               BaLoss loss, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count, uint8_t* out_obs_ok,
                                double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
+  constexpr bool kDistorted = kDist != kBaDistNone;
   if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
   if (kLoss && !ba_loss_valid(loss)) return VC_ERR_INVALID_ARG;
   if (n_points == 0) return VC_OK;
   if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !const_mask)) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || (kDistorted && !cam_dist) || !const_mask)) return VC_ERR_INVALID_ARG;
   if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin || (kLoss && !out_obs_w))) return VC_ERR_INVALID_ARG;
   if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
-  const int blocks = (n_points + kBaWave - 1) / kBaWave;
-  hipLaunchKernelGGL(ba_linearize_points_kernel<kLoss>, dim3((unsigned)blocks), dim3(kBaWave), 0, (hipStream_t)stream, d, lambda, out_vinv,
-                     out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, loss, out_obs_w);
+  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total, cam_dist};
+  hipLaunchKernelGGL((ba_linearize_points_kernel<kLoss, kDist>), dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, lambda, loss, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, out_obs_w);
   hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
   return vc::check_launch();
 }
 
-template <bool kLoss>
-int ba_launch_linearize_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
-                                   const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
-                                   const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* obs_w,
-                                   double* out_obs_xn, double* out_T, double* out_terms, vc_stream_t stream) {
+template <bool kLoss, int kDist>
+int ba_launch_linearize_intrinsics(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
+                                   const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets,
+                                   const int32_t* obs_cam, int total, BaLoss loss, const double* vinv, const double* gp,
+                                   const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
+                                   double* out_terms, vc_stream_t stream) {
+  constexpr bool kDistorted = kDist != kBaDistNone;
   if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_points == 0 || n_groups == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS) return VC_ERR_UNSUPPORTED;
-  if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_group)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !out_obs_xn || (kLoss && !obs_w))) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
-  hipLaunchKernelGGL(ba_linearize_intrinsics_kernel<kLoss>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, out_obs_xn, out_T,
-                     out_terms, obs_w);
-  return vc::check_launch();
-}
-
-template <bool kLoss>
-int ba_launch_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
-                            const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
-                            double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
-                            const double* obs_w, const double* T, const double* terms, double* out_sums, double* out_B, double* out_C,
-                            double* out_h, uint8_t* out_free, vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_groups == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
-  if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_xn || (kLoss && !obs_w))) return VC_ERR_INVALID_ARG;
-  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
-  const BaGroups gr{cam_group, intr_mask, n_groups};
-  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
-                     out_sums);
-  hipLaunchKernelGGL(ba_border_system_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h, out_free);
-  if (n_cams > 0) {
-    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
-    hipLaunchKernelGGL(ba_reduce_border_kernel<kLoss>, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
-                       BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_xn, T, out_B, obs_w);
-  }
-  return vc::check_launch();
-}
-
-constexpr int ba_reduce_lds_bytes(int n_cams) { return 36 * n_cams * (int)sizeof(double); }
-static_assert(ba_reduce_lds_bytes(VC_BA_MAX_CAMS) + (int)sizeof(BaBatch) <= 160 * 1024, "the row block of VC_BA_MAX_CAMS cameras must fit the CU's LDS");
-
-// ---- the distortion: the checks of the entry points above, cam_dist and the loss among them, once for the _radial and the _opencv
-// entry points ----------------------------------------------------------------------------------------------------------------------
-__host__ __device__ constexpr int ba_dist_max_groups(int dist) { return dist == kBaDistOpencv ? VC_BA_MAX_GROUPS_OPENCV : VC_BA_MAX_GROUPS_RADIAL; }
-
-template <int kDist>
-int ba_launch_linearize_points_dist(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
-                                  int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
-                                  int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
-                                  uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
-  if (n_points < 0 || n_cams < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
-  if (n_points == 0) return VC_OK;
-  if (!points || !offsets || !out_vinv || !out_gp || !out_cost || !out_count || !out_total_cost) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_dist || !const_mask)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !obs_xy || !out_obs_ok || !out_obs_lin || !out_obs_w)) return VC_ERR_INVALID_ARG;
-  if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, const_mask, points, offsets, obs_cam, obs_xy, n_cams, n_points, total};
-  hipLaunchKernelGGL(ba_linearize_points_dist_kernel<kDist>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                     (hipStream_t)stream, d, cam_dist, lambda, BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok,
-                     out_obs_lin, out_obs_w);
-  hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_cost, n_points, out_total_cost);
-  return vc::check_launch();
-}
-
-template <int kDist>
-int ba_launch_linearize_intrinsics_dist(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
-                                      const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets,
-                                      const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
-                                      const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
-                                      double* out_terms, vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (kLoss && !ba_loss_valid(loss)) return VC_ERR_INVALID_ARG;
   if (n_points == 0 || n_groups == 0) return VC_OK;
   if (n_groups > ba_dist_max_groups(kDist)) return VC_ERR_UNSUPPORTED;
   if (!intr_mask || !points || !offsets || !vinv || !gp || !out_T || !out_terms) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_dist || !cam_group)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || !obs_w || !out_obs_jt)) return VC_ERR_INVALID_ARG;
-  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
-  hipLaunchKernelGGL(ba_linearize_intrinsics_dist_kernel<kDist>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
-                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, cam_dist, obs_w,
-                     out_obs_jt, out_T, out_terms);
+  if (n_cams > 0 && (!cams || (kDistorted && !cam_dist) || !cam_group)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !obs_ok || !obs_lin || (kLoss && !obs_w) || !out_obs_jt)) return VC_ERR_INVALID_ARG;
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total, cam_dist};
+  hipLaunchKernelGGL((ba_linearize_intrinsics_kernel<kLoss, kDist>), dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                     (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, BaGroups{cam_group, intr_mask, n_groups}, obs_w, out_obs_jt,
+                     out_T, out_terms);
   return vc::check_launch();
 }
 
-template <int kDist>
-int ba_launch_reduce_border_dist(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
-                               const int32_t* offsets, const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs,
-                               const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
-                               const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
-                               double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream) {
+template <bool kLoss, int kDist>
+int ba_launch_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
+                            const int32_t* obs_cam, int total, const int32_t* cam_offsets, const int32_t* cam_obs, const int32_t* obs_point,
+                            double lambda, BaLoss loss, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_jt,
+                            const double* obs_w, const double* T, const double* terms, double* out_sums, double* out_B, double* out_C,
+                            double* out_h, uint8_t* out_free, vc_stream_t stream) {
   if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (!ba_loss_valid(BaLoss{loss, loss_scale})) return VC_ERR_INVALID_ARG;
+  if (kLoss && !ba_loss_valid(loss)) return VC_ERR_INVALID_ARG;
   if (n_groups == 0) return VC_OK;
   if (n_groups > ba_dist_max_groups(kDist) || n_cams > VC_BA_MAX_CAMS) return VC_ERR_UNSUPPORTED;
   if (!intr_mask || !out_sums || !out_C || !out_h || !out_free) return VC_ERR_INVALID_ARG;
   if (n_cams > 0 && (!cam_group || !cam_offsets || !out_B)) return VC_ERR_INVALID_ARG;
   if (n_points > 0 && (!offsets || !vinv || !T || !terms)) return VC_ERR_INVALID_ARG;
-  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_jt || !obs_w)) return VC_ERR_INVALID_ARG;
+  if (total > 0 && (!obs_cam || !cam_obs || !obs_point || !obs_ok || !obs_lin || !obs_jt || (kLoss && !obs_w))) return VC_ERR_INVALID_ARG;
   if (!(lambda >= 0.0 && lambda < INFINITY)) return VC_ERR_INVALID_ARG;
   constexpr int N = ba_dist_unknowns(kDist);
   const BaGroups gr{cam_group, intr_mask, n_groups};
   hipLaunchKernelGGL(ba_ordered_sums_kernel, dim3((unsigned)ba_term_rows<N>(n_groups)), dim3(kBaWave), 0, (hipStream_t)stream, terms, n_points,
                      out_sums);
-  hipLaunchKernelGGL(ba_border_system_dist_kernel<N>, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h,
-                     out_free);
+  hipLaunchKernelGGL(ba_border_system_kernel<N>, dim3(1), dim3(kBaWave), 0, (hipStream_t)stream, out_sums, gr, lambda, out_C, out_h, out_free);
   if (n_cams > 0) {
-    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total};
-    hipLaunchKernelGGL(ba_reduce_border_dist_kernel<kDist>, dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
+    const BaProblem d{nullptr, nullptr, nullptr, offsets, obs_cam, nullptr, n_cams, n_points, total, nullptr};
+    hipLaunchKernelGGL((ba_reduce_border_kernel<kLoss, kDist>), dim3((unsigned)n_cams), dim3(kBaWave), 0, (hipStream_t)stream, d,
                        BaLinear{vinv, nullptr, obs_ok, obs_lin}, gr, cam_offsets, cam_obs, obs_point, obs_jt, obs_w, T, out_B);
   }
   return vc::check_launch();
 }
 
+// The two kernels of a step.  grouped = false is vc_ba_step: then cam_group, T, dtheta and out_valid are absent and none is read.
 template <int kDist>
-int ba_launch_step_dist(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
-                      const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
-                      const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
-                      double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
+int ba_launch_step(bool grouped, const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
+                   const uint8_t* intr_mask, const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
+                   const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc,
+                   const double* dtheta, double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid,
+                   vc_stream_t stream) {
+  constexpr bool kDistorted = kDist != kBaDistNone;
   if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
   if (n_cams == 0 && n_points == 0) return VC_OK;
   if (n_groups > ba_dist_max_groups(kDist)) return VC_ERR_UNSUPPORTED;
   if (n_groups > 0 && (!intr_mask || !dtheta)) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_dist || !cam_group || !dc || !out_cams || !out_dist || !out_valid)) return VC_ERR_INVALID_ARG;
+  if (n_cams > 0 && (!cams || (kDistorted && (!cam_dist || !out_dist)) || (grouped && (!cam_group || !out_valid)) || !dc || !out_cams))
+    return VC_ERR_INVALID_ARG;
   if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx || (n_groups > 0 && !T))) return VC_ERR_INVALID_ARG;
   if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
-  constexpr int N = ba_dist_unknowns(kDist);
-  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total};
+  const BaProblem d{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total, cam_dist};
   const BaGroups gr{cam_group, intr_mask, n_groups};
   if (n_points > 0)
-    hipLaunchKernelGGL(ba_step_points_dist_kernel<N>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       d, BaLinear{vinv, gp, obs_ok, obs_lin}, T, n_groups, dc, dtheta, out_points, out_dx);
+    hipLaunchKernelGGL(ba_step_points_kernel<ba_dist_unknowns(kDist)>, dim3((unsigned)((n_points + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0,
+                       (hipStream_t)stream, d, BaLinear{vinv, gp, obs_ok, obs_lin}, T, n_groups, dc, dtheta, out_points, out_dx);
   if (n_cams > 0)
-    hipLaunchKernelGGL(ba_step_cameras_dist_kernel<kDist>, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
-                       cams, cam_dist, n_cams, gr, dc, dtheta, out_cams, out_dist, out_valid);
+    hipLaunchKernelGGL(ba_step_cameras_kernel<kDist>, dim3((unsigned)((n_cams + kBaWave - 1) / kBaWave)), dim3(kBaWave), 0, (hipStream_t)stream,
+                       d, gr, dc, dtheta, out_cams, out_dist, out_valid);
   return vc::check_launch();
 }
+
+constexpr int ba_reduce_lds_bytes(int n_cams) { return 36 * n_cams * (int)sizeof(double); }
+static_assert(ba_reduce_lds_bytes(VC_BA_MAX_CAMS) + (int)sizeof(BaBatch) <= 160 * 1024, "the row block of VC_BA_MAX_CAMS cameras must fit the CU's LDS");
 
 }  // namespace
 
@@ -1459,17 +1202,18 @@ int vc_ba_linearize_points(const double* cams, int n_cams, const uint8_t* const_
                            const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
                            double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count, uint8_t* out_obs_ok,
                            double* out_obs_lin, double* out_total_cost, vc_stream_t stream) {
-  return ba_launch_linearize_points<false>(cams, n_cams, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda, BaLoss{0, 1.0},
-                                           out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, nullptr, out_total_cost, stream);
+  return ba_launch_linearize_points<false, kBaDistNone>(cams, n_cams, nullptr, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda,
+                                                        kBaNoLoss, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, nullptr,
+                                                        out_total_cost, stream);
 }
 
 int vc_ba_linearize_points_loss(const double* cams, int n_cams, const uint8_t* const_mask, const double* points, int n_points,
                                 const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda, int loss,
                                 double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
                                 uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
-  return ba_launch_linearize_points<true>(cams, n_cams, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda,
-                                          BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, out_obs_w,
-                                          out_total_cost, stream);
+  return ba_launch_linearize_points<true, kBaDistNone>(cams, n_cams, nullptr, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda,
+                                                       BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin,
+                                                       out_obs_w, out_total_cost, stream);
 }
 
 int vc_ba_reduce_cameras(int n_cams, const uint8_t* const_mask, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
@@ -1528,29 +1272,24 @@ int vc_ba_schur_product(int n_cams, int n_points, const int32_t* offsets, const 
 int vc_ba_step(const double* cams, int n_cams, const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam,
                int total, const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* dc,
                double* out_cams, double* out_points, double* out_dx, vc_stream_t stream) {
-  if (n_cams < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_cams == 0 && n_points == 0) return VC_OK;
-  if (n_cams > 0 && (!cams || !dc || !out_cams)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
-  return ba_launch_step(BaProblem{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total}, BaLinear{vinv, gp, obs_ok, obs_lin},
-                        BaGroups{nullptr, nullptr, 0}, nullptr, dc, nullptr, out_cams, out_points, out_dx, nullptr, stream);
+  return ba_launch_step<kBaDistNone>(false, cams, n_cams, nullptr, nullptr, 0, nullptr, points, n_points, offsets, obs_cam, total, vinv, gp, obs_ok,
+                                     obs_lin, nullptr, dc, nullptr, out_cams, nullptr, out_points, out_dx, nullptr, stream);
 }
 
 int vc_ba_linearize_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
                                const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
                                const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, double* out_obs_xn,
                                double* out_T, double* out_terms, vc_stream_t stream) {
-  return ba_launch_linearize_intrinsics<false>(cams, n_cams, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
-                                               obs_ok, obs_lin, nullptr, out_obs_xn, out_T, out_terms, stream);
+  return ba_launch_linearize_intrinsics<false, kBaDistNone>(cams, n_cams, nullptr, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam,
+                                                            total, kBaNoLoss, vinv, gp, obs_ok, obs_lin, nullptr, out_obs_xn, out_T, out_terms, stream);
 }
 
 int vc_ba_linearize_intrinsics_loss(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
                                     const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total,
                                     const double* vinv, const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* obs_w,
                                     double* out_obs_xn, double* out_T, double* out_terms, vc_stream_t stream) {
-  return ba_launch_linearize_intrinsics<true>(cams, n_cams, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
-                                              obs_ok, obs_lin, obs_w, out_obs_xn, out_T, out_terms, stream);
+  return ba_launch_linearize_intrinsics<true, kBaDistNone>(cams, n_cams, nullptr, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam,
+                                                           total, kBaNoLoss, vinv, gp, obs_ok, obs_lin, obs_w, out_obs_xn, out_T, out_terms, stream);
 }
 
 int vc_ba_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
@@ -1558,8 +1297,9 @@ int vc_ba_reduce_border(int n_cams, const int32_t* cam_group, int n_groups, cons
                         double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
                         const double* T, const double* terms, double* out_sums, double* out_B, double* out_C, double* out_h,
                         uint8_t* out_free, vc_stream_t stream) {
-  return ba_launch_reduce_border<false>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs, obs_point,
-                                        lambda, vinv, obs_ok, obs_lin, obs_xn, nullptr, T, terms, out_sums, out_B, out_C, out_h, out_free, stream);
+  return ba_launch_reduce_border<false, kBaDistNone>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
+                                                     obs_point, lambda, kBaNoLoss, vinv, obs_ok, obs_lin, obs_xn, nullptr, T, terms, out_sums, out_B,
+                                                     out_C, out_h, out_free, stream);
 }
 
 int vc_ba_reduce_border_loss(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points, const int32_t* offsets,
@@ -1567,8 +1307,9 @@ int vc_ba_reduce_border_loss(int n_cams, const int32_t* cam_group, int n_groups,
                              double lambda, const double* vinv, const uint8_t* obs_ok, const double* obs_lin, const double* obs_xn,
                              const double* obs_w, const double* T, const double* terms, double* out_sums, double* out_B, double* out_C,
                              double* out_h, uint8_t* out_free, vc_stream_t stream) {
-  return ba_launch_reduce_border<true>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs, obs_point,
-                                       lambda, vinv, obs_ok, obs_lin, obs_xn, obs_w, T, terms, out_sums, out_B, out_C, out_h, out_free, stream);
+  return ba_launch_reduce_border<true, kBaDistNone>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
+                                                    obs_point, lambda, kBaNoLoss, vinv, obs_ok, obs_lin, obs_xn, obs_w, T, terms, out_sums, out_B,
+                                                    out_C, out_h, out_free, stream);
 }
 
 int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
@@ -1576,25 +1317,18 @@ int vc_ba_step_intrinsics(const double* cams, int n_cams, const int32_t* cam_gro
                           const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc,
                           const double* dtheta, double* out_cams, double* out_points, double* out_dx, uint8_t* out_valid,
                           vc_stream_t stream) {
-  if (n_cams < 0 || n_groups < 0 || n_points < 0 || total < 0) return VC_ERR_INVALID_ARG;
-  if (n_cams == 0 && n_points == 0) return VC_OK;
-  if (n_groups > VC_BA_MAX_GROUPS) return VC_ERR_UNSUPPORTED;
-  if (n_groups > 0 && (!intr_mask || !dtheta)) return VC_ERR_INVALID_ARG;
-  if (n_cams > 0 && (!cams || !cam_group || !dc || !out_cams || !out_valid)) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && (!points || !offsets || !vinv || !gp || !out_points || !out_dx || (n_groups > 0 && !T))) return VC_ERR_INVALID_ARG;
-  if (n_points > 0 && total > 0 && (!obs_cam || !obs_ok || !obs_lin)) return VC_ERR_INVALID_ARG;
-  return ba_launch_step(BaProblem{cams, nullptr, points, offsets, obs_cam, nullptr, n_cams, n_points, total}, BaLinear{vinv, gp, obs_ok, obs_lin},
-                        BaGroups{cam_group, intr_mask, n_groups}, T, dc, dtheta, out_cams, out_points, out_dx, out_valid, stream);
+  return ba_launch_step<kBaDistNone>(true, cams, n_cams, nullptr, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
+                                     obs_ok, obs_lin, T, dc, dtheta, out_cams, nullptr, out_points, out_dx, out_valid, stream);
 }
 
-// ---- the distortion: the _radial and the _opencv entry points, two instances of the launchers above --------------------------------
+// ---- the distortion: the _radial and the _opencv entry points -----------------------------------------------------------------------
 int vc_ba_linearize_points_radial(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
                                   int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
                                   int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
                                   uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
-  return ba_launch_linearize_points_dist<kBaDistRadial>(cams, n_cams, cam_dist, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda, loss,
-                                             loss_scale, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, out_obs_w, out_total_cost,
-                                             stream);
+  return ba_launch_linearize_points<true, kBaDistRadial>(cams, n_cams, cam_dist, const_mask, points, n_points, offsets, obs_cam, obs_xy, total,
+                                                         lambda, BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok,
+                                                         out_obs_lin, out_obs_w, out_total_cost, stream);
 }
 
 int vc_ba_linearize_intrinsics_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
@@ -1602,8 +1336,9 @@ int vc_ba_linearize_intrinsics_radial(const double* cams, int n_cams, const doub
                                       const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
                                       const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
                                       double* out_terms, vc_stream_t stream) {
-  return ba_launch_linearize_intrinsics_dist<kBaDistRadial>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total,
-                                                 loss, loss_scale, vinv, gp, obs_ok, obs_lin, obs_w, out_obs_jt, out_T, out_terms, stream);
+  return ba_launch_linearize_intrinsics<true, kBaDistRadial>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets,
+                                                             obs_cam, total, BaLoss{loss, loss_scale}, vinv, gp, obs_ok, obs_lin, obs_w, out_obs_jt,
+                                                             out_T, out_terms, stream);
 }
 
 int vc_ba_reduce_border_radial(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
@@ -1611,26 +1346,26 @@ int vc_ba_reduce_border_radial(int n_cams, const int32_t* cam_group, int n_group
                                const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
                                const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
                                double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream) {
-  return ba_launch_reduce_border_dist<kBaDistRadial>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
-                                          obs_point, lambda, loss, loss_scale, vinv, obs_ok, obs_lin, obs_jt, obs_w, T, terms, out_sums, out_B,
-                                          out_C, out_h, out_free, stream);
+  return ba_launch_reduce_border<true, kBaDistRadial>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
+                                                      obs_point, lambda, BaLoss{loss, loss_scale}, vinv, obs_ok, obs_lin, obs_jt, obs_w, T, terms,
+                                                      out_sums, out_B, out_C, out_h, out_free, stream);
 }
 
 int vc_ba_step_radial(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
                       const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
                       const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
                       double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
-  return ba_launch_step_dist<kBaDistRadial>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
-                                 obs_ok, obs_lin, T, dc, dtheta, out_cams, out_dist, out_points, out_dx, out_valid, stream);
+  return ba_launch_step<kBaDistRadial>(true, cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv,
+                                       gp, obs_ok, obs_lin, T, dc, dtheta, out_cams, out_dist, out_points, out_dx, out_valid, stream);
 }
 
 int vc_ba_linearize_points_opencv(const double* cams, int n_cams, const double* cam_dist, const uint8_t* const_mask, const double* points,
                                   int n_points, const int32_t* offsets, const int32_t* obs_cam, const double* obs_xy, int total, double lambda,
                                   int loss, double loss_scale, double* out_vinv, double* out_gp, double* out_cost, int32_t* out_count,
                                   uint8_t* out_obs_ok, double* out_obs_lin, double* out_obs_w, double* out_total_cost, vc_stream_t stream) {
-  return ba_launch_linearize_points_dist<kBaDistOpencv>(cams, n_cams, cam_dist, const_mask, points, n_points, offsets, obs_cam, obs_xy, total, lambda, loss,
-                                             loss_scale, out_vinv, out_gp, out_cost, out_count, out_obs_ok, out_obs_lin, out_obs_w, out_total_cost,
-                                             stream);
+  return ba_launch_linearize_points<true, kBaDistOpencv>(cams, n_cams, cam_dist, const_mask, points, n_points, offsets, obs_cam, obs_xy, total,
+                                                         lambda, BaLoss{loss, loss_scale}, out_vinv, out_gp, out_cost, out_count, out_obs_ok,
+                                                         out_obs_lin, out_obs_w, out_total_cost, stream);
 }
 
 int vc_ba_linearize_intrinsics_opencv(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups,
@@ -1638,8 +1373,9 @@ int vc_ba_linearize_intrinsics_opencv(const double* cams, int n_cams, const doub
                                       const int32_t* obs_cam, int total, int loss, double loss_scale, const double* vinv, const double* gp,
                                       const uint8_t* obs_ok, const double* obs_lin, const double* obs_w, double* out_obs_jt, double* out_T,
                                       double* out_terms, vc_stream_t stream) {
-  return ba_launch_linearize_intrinsics_dist<kBaDistOpencv>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total,
-                                                 loss, loss_scale, vinv, gp, obs_ok, obs_lin, obs_w, out_obs_jt, out_T, out_terms, stream);
+  return ba_launch_linearize_intrinsics<true, kBaDistOpencv>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets,
+                                                             obs_cam, total, BaLoss{loss, loss_scale}, vinv, gp, obs_ok, obs_lin, obs_w, out_obs_jt,
+                                                             out_T, out_terms, stream);
 }
 
 int vc_ba_reduce_border_opencv(int n_cams, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask, int n_points,
@@ -1647,17 +1383,17 @@ int vc_ba_reduce_border_opencv(int n_cams, const int32_t* cam_group, int n_group
                                const int32_t* obs_point, double lambda, int loss, double loss_scale, const double* vinv, const uint8_t* obs_ok,
                                const double* obs_lin, const double* obs_jt, const double* obs_w, const double* T, const double* terms,
                                double* out_sums, double* out_B, double* out_C, double* out_h, uint8_t* out_free, vc_stream_t stream) {
-  return ba_launch_reduce_border_dist<kBaDistOpencv>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
-                                          obs_point, lambda, loss, loss_scale, vinv, obs_ok, obs_lin, obs_jt, obs_w, T, terms, out_sums, out_B,
-                                          out_C, out_h, out_free, stream);
+  return ba_launch_reduce_border<true, kBaDistOpencv>(n_cams, cam_group, n_groups, intr_mask, n_points, offsets, obs_cam, total, cam_offsets, cam_obs,
+                                                      obs_point, lambda, BaLoss{loss, loss_scale}, vinv, obs_ok, obs_lin, obs_jt, obs_w, T, terms,
+                                                      out_sums, out_B, out_C, out_h, out_free, stream);
 }
 
 int vc_ba_step_opencv(const double* cams, int n_cams, const double* cam_dist, const int32_t* cam_group, int n_groups, const uint8_t* intr_mask,
                       const double* points, int n_points, const int32_t* offsets, const int32_t* obs_cam, int total, const double* vinv,
                       const double* gp, const uint8_t* obs_ok, const double* obs_lin, const double* T, const double* dc, const double* dtheta,
                       double* out_cams, double* out_dist, double* out_points, double* out_dx, uint8_t* out_valid, vc_stream_t stream) {
-  return ba_launch_step_dist<kBaDistOpencv>(cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv, gp,
-                                 obs_ok, obs_lin, T, dc, dtheta, out_cams, out_dist, out_points, out_dx, out_valid, stream);
+  return ba_launch_step<kBaDistOpencv>(true, cams, n_cams, cam_dist, cam_group, n_groups, intr_mask, points, n_points, offsets, obs_cam, total, vinv,
+                                       gp, obs_ok, obs_lin, T, dc, dtheta, out_cams, out_dist, out_points, out_dx, out_valid, stream);
 }
 
 }  // extern "C"
